@@ -9,11 +9,21 @@ batch 256 sequences of length 200 PER GPU (weak scaling: the global batch is 256
 A "step" = one full train_function call (gather -> GRU -> softmax/CCE -> BPTT -> scatter -> Adam)
 on one resident batch.  Inputs live in HBM before the timed region starts.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: set up, --warmup steps,
+ONE timed region of exactly --steps steps, the outputs of its last step if --dump-outputs DIR is given
+(the cost and every parameter after it, DIR/<name>.npy, at most 64 MB: a fixed, seeded sample of large
+parameters), and the line (metric / value / unit / higher_is_better / dtype / ms_per_step ...).  The last
+timed step starts again from the seeded initial state (a device snapshot of parameters and optimizer
+moments, copied back once inside the timed region; none above 2 GiB or with row-sparse optimizer blocks),
+so its outputs depend on the arguments alone.
+
+--full adds everything else, as child runs or passes of its own, with two extra objects among them:
   roofline     -- the dominant kernel of the step, measured live with HIP events (ring of per-step
                   event sets inside libsbr_rnn.so, read back after the timed region)
   cpu_baseline -- the torch-CPU float32 port of the same step (oracle/torch_ref.py; Theano/Lasagne
                   cannot run here) timed on this box's host cores on a bounded sample.
+and the phase survey, counter passes, sustained region, training loop, other BASELINE configurations,
+strong-scaling pieces and data-parallel survey; its headline is the median of --repeats (5) regions.
 """
 import argparse
 import json
@@ -39,6 +49,8 @@ F32_MFMA_PEAK_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32,
 BF16_MFMA_PEAK_TFLOPS = 2500.0    # dense bf16 / fp16 MFMA peak: what the split products actually occupy
 HBM_PEAK_GBS = 8000.0             # HBM3E spec
 N_CUS = 256
+DUMP_BUDGET_BYTES = 60 * 10 ** 6  # --dump-outputs: array bytes of all files together (under 64 MB with the .npy headers)
+SEED_RESTORE_MAX_BYTES = 2 << 30  # the seeded-state snapshot for the last timed step: parameters + moments up to this size
 
 
 def zipf_items(rng, n_items, size, perm):
@@ -72,6 +84,25 @@ def initial_parameters(cfg, rng):
     the initialisers the reference's layers name (engine.initial_values; sparse_lstm.py:143-171, rnn_one_hot.py:65)."""
     from sbr_amd.engine import describe_params, initial_values
     return initial_values(describe_params(cfg), rng)
+
+
+def output_arrays(cost, descs, params, budget=DUMP_BUDGET_BYTES):
+    """What a caller of the timed step receives after its last step, as {file name: float32 / float64 array}: the cost, and every
+    parameter ("param.<name>").  Where the parameters exceed `budget` bytes, the large ones become a fixed, seeded sample of their
+    elements ("param.<name>.sample", the same flat indices in every run of the same configuration); the small ones stay whole."""
+    out = {"cost": np.array([cost], dtype=np.float64)}
+    share = budget // max(1, len(params))
+    small = sum(p.nbytes for p in params if p.nbytes <= share)
+    large = sum(p.nbytes for p in params if p.nbytes > share)
+    frac = 1.0 if small + large <= budget else (budget - small) / float(large)
+    for i, ((name, _), p) in enumerate(zip(descs, params)):
+        p = np.asarray(p, dtype=np.float32)
+        if frac >= 1.0 or p.nbytes <= share:
+            out["param." + name] = p
+        else:
+            idx = np.unique(np.random.default_rng(1000 + i).integers(0, p.size, size=max(1, int(p.size * frac))))
+            out["param.%s.sample" % name] = p.reshape(-1)[idx]
+    return out
 
 
 def arithmetic_note(eng):
@@ -199,7 +230,7 @@ def strong_scaling_pieces(log, budget_s=150.0):
                 out[key] = {"skipped": "time budget spent"}
                 continue
             try:
-                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--quick", "--batch", str(bl), "--steps", "20",
+                r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--full", "--quick", "--batch", str(bl), "--steps", "20",
                                     "--warmup", "5", "--repeats", "3"], capture_output=True, text=True, timeout=60, env=env)
                 d = json.loads(r.stdout.strip().splitlines()[-1])
                 out[key] = {"ranks_of_global_256": 256 // bl, "rows_per_rank": bl, "ms_per_step": d["ms_per_step"],
@@ -229,7 +260,7 @@ def other_config_lines(log, names=("c1", "c4", "c3", "c5", "c5_bf16"), budget_s=
         try:
             if key in ("c1", "c4"):
                 extra = extra + ["--brief-cpu-seconds", "25"]
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--brief", "--steps", "20", "--warmup", "5",
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--config", name, "--full", "--brief", "--steps", "20", "--warmup", "5",
                                 "--repeats", "3"] + extra, capture_output=True, text=True, timeout=min(limit, left))
             d = json.loads(r.stdout.strip().splitlines()[-1])
             rf, ch = d.get("roofline") or {}, d.get("chains") or {}
@@ -282,7 +313,13 @@ def main():
     ap.add_argument("--cpu-steps", type=int, default=3, help="max timed CPU-baseline steps")
     ap.add_argument("--cpu-seconds", type=float, default=25.0, help="time budget of the CPU-baseline sample")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = min(host cores, 16): the port scales to ~16 threads on the GPU box")
-    ap.add_argument("--repeats", type=int, default=5, help="timed regions of --steps steps each; the line reports the median region and all of them")
+    ap.add_argument("--full", action="store_true", help="everything besides the headline: phase survey, roofline, counter passes, "
+                    "sustained region, CPU baseline, training loop, other BASELINE configurations, strong-scaling pieces, data-parallel "
+                    "survey, five timed regions (without it: warm-up, one timed region of --steps steps, the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed to "
+                    "DIR/<name>.npy: the cost and every parameter after it (large ones as a fixed, seeded sample; 64 MB at most)")
+    ap.add_argument("--repeats", type=int, default=None, help="timed regions of --steps steps each; the line reports the median region "
+                    "and all of them (default 1; 5 with --full)")
     ap.add_argument("--pmc-json", default=None, help="HBM counter bytes per launch for roofline.traffic, from a separate rocprofv3 --pmc pass "
                     "of this same command (tools/pmc_summary.py output); without it traffic is null")
     ap.add_argument("--no-pmc", action="store_true", help="skip the counter passes (two rocprofv3 --pmc child runs of this command, "
@@ -310,7 +347,22 @@ def main():
     ap.add_argument("--dp-backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend of the data-parallel step: nccl = RCCL over xGMI (one rank per GPU); gloo lets several "
                          "ranks share one device (RCCL refuses that) -- how the one-GPU test box exercises --gpus 2")
+    # the options of --full's legs: a plain run measures none of them, so it refuses them (given in full or abbreviated)
+    full_only = ("no_cpu_baseline", "cpu_steps", "cpu_seconds", "cpu_threads", "pmc_json", "no_pmc", "sustained_seconds", "loop_iters",
+                 "brief", "strong_pieces", "brief_cpu_seconds", "no_other_configs", "other_configs")
+    defaults = {k: ap.get_default(k) for k in full_only}
+    ap.set_defaults(**{k: None for k in full_only})
     args = ap.parse_args()
+    given = ["--" + k.replace("_", "-") for k in full_only if getattr(args, k) is not None]
+    for k in full_only:
+        if getattr(args, k) is None:
+            setattr(args, k, defaults[k])
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
+    if not args.full:
+        if given:
+            ap.error("%s: part of --full (a plain run times the headline only)" % ", ".join(given))
+        args.quick = True          # the timed region and the line only
     if args.brief:
         args.no_pmc = args.no_other_configs = True
         args.no_cpu_baseline = args.brief_cpu_seconds <= 0
@@ -366,6 +418,22 @@ def main():
                     row_offset=rank * B, loss=loss, n_samples=n_samples, updater="adam", learning_rate=1e-3, flags=args.flags)
     params = initial_parameters(eng.cfg, np.random.default_rng(42))
     eng.set_all_param_values(params)
+    # The LAST timed step starts again from this seeded state (parameters and optimizer moments; the step count is a function
+    # of the arguments), so that what it computes -- the outputs --dump-outputs writes -- depends on the arguments alone: the
+    # scatter-add of the embedding gradient sums in float-atomic order, and a training run amplifies those rounding differences
+    # until, after thousands of steps, two runs of the same command hold O(1)-different parameters.  (Row-sparse optimizer blocks
+    # keep per-row step records outside these sections: no restore there.)  The snapshot is a device clone of the parameters and
+    # their optimizer moments (3x the parameter bytes with Adam: 22 MB at C2, 0.4 GB at C4), copied back once, inside the last
+    # timed region; above SEED_RESTORE_MAX_BYTES (dense C5: tens of GB) neither is made, and that configuration's outputs are not
+    # reproducible from run to run.
+    seeded = None
+    if eng.query("sparse_blocks") == 0:
+        secs = [eng.section("params")[0], eng.section("state")[0]]
+        if sum(v.numel() * 4 for v in secs) <= SEED_RESTORE_MAX_BYTES:
+            seeded = [(v, v.clone()) for v in secs]
+        else:
+            log("no restore of the seeded state before the last timed step: %.1f GB of parameters and moments"
+                % (sum(v.numel() * 4 for v in secs) / 1e9))
 
     # synthetic batches, resident in HBM before the timed region
     nb = 8
@@ -379,6 +447,18 @@ def main():
         dev_batches.append(d)
     dp = DataParallel(eng, dist)
     log("engine ready, arena %.1f MB" % (eng.arena_bytes / 1e6))
+
+    def restore_seeded():
+        """the seeded state back into the engine before the last timed step: a device copy on the engine's stream, behind
+        whatever the previous step still runs on its side streams (no host wait: the pipeline of steps stays full)"""
+        main = torch.cuda.current_stream()
+        for q in ("side_stream", "side_stream2"):
+            if eng.query(q):
+                ev = torch.cuda.Event()
+                ev.record(torch.cuda.ExternalStream(eng.query(q), device=dev))
+                main.wait_event(ev)
+        for v, s in seeded:
+            v.copy_(s)
 
     def step(i, exposed=None):
         d = dev_batches[i % nb]
@@ -431,7 +511,7 @@ def main():
     # data parallel: how long the engine's stream really stands still for each collective (events around every wait; a survey
     # pass like the one above, outside the timed regions)
     dp_info = None
-    if world > 1 or args.force_dp:
+    if (world > 1 or args.force_dp) and args.full:
         n_sv = min(args.steps, 10)
         eng.enable_timing(False)
         ex = {}
@@ -446,15 +526,18 @@ def main():
                            "survey pass of %d steps); the collectives are sync ops enqueued on the engine's side stream: out = output "
                            "layer (behind its gradient kernels, beside the BPTT chain), rec = the recurrent part once scatter-add, "
                            "slab reduction and the chain's partial sums are in; sparse = row-sparse blocks (engine stream)" % n_sv}
-    eng.enable_timing(True, only=dom_phase)
+    if args.full:
+        eng.enable_timing(True, only=dom_phase)
 
-    def timed_region(first, n=None):
+    def timed_region(first, n=None, last=False):
         n = args.steps if n is None else n
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         t0 = time.perf_counter()
         for i in range(n):
+            if last and i == n - 1 and seeded is not None:
+                restore_seeded()
             step(first + i)
         torch.cuda.synchronize()
         if world > 1:
@@ -467,12 +550,21 @@ def main():
         return dt
     # --repeats regions of EXACTLY --steps steps each, every one bracketed by barrier + synchronize; the headline is the
     # median region (a DVFS blip in one region cannot move it), all regions are reported
-    region_s = [timed_region(args.warmup + r * args.steps) for r in range(max(1, args.repeats))]
+    n_regions = max(1, args.repeats)
+    region_s = [timed_region(args.warmup + r * args.steps, last=r == n_regions - 1) for r in range(n_regions)]
     dt = float(np.median(region_s))
     log("timed regions done: %s ms/step" % ", ".join("%.4f" % (x / args.steps * 1e3) for x in region_s))
     cost = eng.read_cost()
     if not np.isfinite(cost):
         raise ValueError("Cost is NaN")            # rnn_base.py:291-292
+    if args.dump_outputs:      # (before anything below steps the model further)
+        vals = dp.get_all_param_values() if world > 1 else eng.get_all_param_values()
+        if rank == 0:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in output_arrays(cost, eng.param_descs, vals).items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            log("outputs of the last timed step written to", args.dump_outputs)
+        del vals
     # one long region behind the short ones: the timed regions are ~20 ms each, which the chip runs at its boost clock; this one
     # lasts --sustained-seconds (same steps, same barriers), with the chain's own clock read from its in-kernel counters
     sustained = None
@@ -604,7 +696,7 @@ def main():
         elif world == 1 and not args.quick and not args.no_pmc:
             # ... which bench.py runs itself: two rocprofv3 --pmc child passes of this very workload (counter_passes above)
             n_child = 6 + 2
-            child = ["--steps", "6", "--warmup", "2", "--repeats", "1", "--quick", "--config", args.config, "--lengths", args.lengths,
+            child = ["--full", "--steps", "6", "--warmup", "2", "--repeats", "1", "--quick", "--config", args.config, "--lengths", args.lengths,
                      "--batch", str(B), "--max_length", str(T)]
             pmc = counter_passes(child, log)
             if pmc:
@@ -649,7 +741,7 @@ def main():
                                 "note": "device time of the recurrent chain kernels alone (HIP-event pair around every launch, all layers; "
                                         "survey pass), and what is left of ms_per_step outside them"}
         if world == 1 and not args.quick and not args.no_pmc:
-            mc = mfma_counter_pass(["--steps", "6", "--warmup", "2", "--repeats", "1", "--quick", "--config", args.config, "--lengths", args.lengths,
+            mc = mfma_counter_pass(["--full", "--steps", "6", "--warmup", "2", "--repeats", "1", "--quick", "--config", args.config, "--lengths", args.lengths,
                                     "--batch", str(B), "--max_length", str(T)], log)
             if mc:
                 keep = {}

@@ -1,11 +1,13 @@
 """bench.py prints ONE JSON line with the fields the driver reads (metric / value / unit / n_gpus / steps / warmup /
-ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus `roofline` for the dominant
-kernel, measured with HIP events inside the timed region, and `cpu_baseline`."""
+ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload); with --full also `roofline` for the
+dominant kernel, measured with HIP events inside the timed region, and `cpu_baseline`.  A plain run (no --full) carries the
+headline alone and can write the outputs of its last timed step (--dump-outputs)."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -14,9 +16,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run(*extra, other_configs=False):
     # (the child runs of the other BASELINE configurations only where a test looks at them, and there without C5, which alone
-    # builds a 47 GB arena and draws 2.6e9 initial values: ~40 s; the driver's own default run carries all four)
+    # builds a 47 GB arena and draws 2.6e9 initial values: ~40 s; the driver's own --full run carries all four)
     extra = list(extra) + (["--other-configs", "c1,c4,c3"] if other_configs else ["--no-other-configs"])
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2"] + list(extra),
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "6", "--warmup", "2"] + list(extra),
                          cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.strip().splitlines() if l.strip()]
@@ -126,7 +128,7 @@ def test_one_rank_through_the_data_parallel_step():
 
 
 def test_counter_passes_sustained_region_and_training_loop_ride_in_the_default_line():
-    # what the driver's plain `python bench.py` carries besides the timed regions: HBM bytes of the dominant kernel from the
+    # what `python bench.py --full` carries besides the timed regions: HBM bytes of the dominant kernel from the
     # command's own two rocprofv3 --pmc child passes (never a stored number), the whole step's traffic against its algorithmic
     # bytes, one region of >= 2 s, and the end-to-end training loop (device batch builder + lagged cost read-back)
     d = run("--no-cpu-baseline", other_configs=True)
@@ -160,3 +162,60 @@ def test_counter_passes_sustained_region_and_training_loop_ride_in_the_default_l
     for key, ranks in (("c2_b128", 2), ("c2_b64", 4), ("c2_b32", 8), ("c4_b128", 2), ("c4_b64", 4), ("c4_b32", 8)):
         assert "skipped" in sm[key] or (sm[key]["ranks_of_global_256"] == ranks and sm[key]["ms_per_step"] > 0), (key, sm[key])
     assert "skipped" not in sm["c2_b32"]
+
+
+FULL_ONLY = ("roofline", "phases_us", "kernels", "chains", "cpu_baseline", "sustained", "train_loop", "other_configs",
+             "strong_scaling_model", "hbm_traffic", "mfma_counters", "data_parallel")
+
+
+def run_plain(*extra):
+    # the command the driver repeats for every change: no --full, nothing but the headline
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + list(extra),
+                         cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.strip().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0])
+
+
+def load_dump(d):
+    return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+
+
+def test_plain_line_times_exactly_steps_and_dumps_the_last_step(tmp_path):
+    from sbr_amd.engine import describe_params, make_config
+    a, b = tmp_path / "a", tmp_path / "b"
+    d = run_plain("--steps", "6", "--warmup", "2", "--dump-outputs", str(a))
+    assert d["metric"].startswith("user-sequences/sec") and d["unit"] == "user-sequences/s" and d["higher_is_better"] is True
+    assert (d["n_gpus"], d["steps"], d["warmup"], d["dtype"]) == (1, 6, 2, "f32") and d["config"]["workload"].startswith("c2:")
+    assert d["repeats"]["n"] == 1 and d["repeats"]["ms_per_step"] == [d["ms_per_step"]]      # ONE region of --steps steps
+    assert d["value"] == pytest.approx(d["config"]["global_batch"] / (d["ms_per_step"] * 1e-3), rel=2e-3)
+    assert not [k for k in FULL_ONLY if k in d]
+    # the outputs of the last timed step: the cost and every parameter of C2, whole (7.4 MB), float32 / float64
+    out = load_dump(str(a))
+    descs = describe_params(make_config(cell="GRU", layers=[128], n_items=3706, max_length=200, batch_size=256))
+    assert set(out) == {"cost"} | {"param." + n for n, _ in descs}
+    assert all(v.dtype in (np.float32, np.float64) and np.isfinite(v).all() for v in out.values())
+    assert all(out["param." + n].shape == s for n, s in descs)
+    assert sum(os.path.getsize(os.path.join(str(a), f)) for f in os.listdir(str(a))) <= 64e6
+    assert out["cost"].shape == (1,) and float(out["cost"][0]) == pytest.approx(d["config"]["last_cost"], abs=1e-5)
+    # the last timed step starts from the seeded state: its outputs depend on the arguments, not on how many steps came before
+    # (8 here, 2 000 below -- a training run amplifies the scatter-add's rounding-order differences to O(1) over such a run)
+    c = tmp_path / "c"
+    run_plain("--steps", "2000", "--warmup", "6", "--dump-outputs", str(b))
+    run_plain("--steps", "2000", "--warmup", "6", "--dump-outputs", str(c))
+    out_b, out_c = load_dump(str(b)), load_dump(str(c))
+    assert set(out_b) == set(out_c) == set(out)
+    assert float(out_b["cost"][0]) == float(out_c["cost"][0])      # the forward pass from the same state: bit for bit
+    for k, v in out_b.items():
+        assert np.abs(out_c[k] - v).max() <= 1e-5, k
+    # ... and they are the parameters AFTER that step, not the seeded ones: one Adam step of lr 1e-3 away from them (bias
+    # correction at step 2 006 bounds it by ~3e-3), where 2 000 steps of training move them by O(1)
+    import bench
+    seeded = bench.initial_parameters(make_config(cell="GRU", layers=[128], n_items=3706, max_length=200, batch_size=256),
+                                      np.random.default_rng(42))
+    for (n, _), p0 in zip(descs, seeded):
+        moved = float(np.abs(out_b["param." + n] - p0).max())
+        assert moved <= 1e-2, (n, moved)
+        # (hid_init's gradient crosses all 200 steps of every full-length row to reach it: it vanishes below float32's range)
+        assert moved > 0 or n == "l0.hid_init", n

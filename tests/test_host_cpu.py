@@ -422,6 +422,42 @@ def test_bench_initial_parameters_follow_the_init_law():
                 assert 0.7 < a.std() / b.std() < 1.4
 
 
+def test_bench_output_dump_is_whole_or_a_fixed_sample_within_budget():
+    # bench.py --dump-outputs: the cost and every parameter; over the budget the large parameters become the same seeded sample
+    # of their elements in every run, the small ones stay whole, and all files together stay within the budget
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(3)
+    descs = [("l0.W_in", (5000, 64)), ("l0.b", (64,)), ("out.W", (64, 5000)), ("out.b", (5000,))]
+    params = [rng.standard_normal(s).astype(np.float32) for _, s in descs]
+    whole = bench.output_arrays(1.5, descs, params)
+    assert sorted(whole) == ["cost", "param.l0.W_in", "param.l0.b", "param.out.W", "param.out.b"]
+    assert whole["cost"].dtype == np.float64 and whole["cost"].tolist() == [1.5]
+    assert all(np.array_equal(whole["param." + n], p) for (n, _), p in zip(descs, params))
+    budget = 400000                              # bytes: below the 2.6 MB of the parameters
+    got, again = (bench.output_arrays(1.5, descs, params, budget=budget) for _ in range(2))
+    assert sorted(got) == ["cost", "param.l0.W_in.sample", "param.l0.b", "param.out.W.sample", "param.out.b"]
+    assert all(v.dtype in (np.float32, np.float64) for v in got.values())
+    assert sum(v.nbytes for k, v in got.items() if k != "cost") <= budget
+    assert all(np.array_equal(got[k], again[k]) for k in got)
+    assert np.array_equal(got["param.l0.b"], params[1]) and np.array_equal(got["param.out.b"], params[3])
+    s = got["param.l0.W_in.sample"]
+    assert 0.5 * budget / 8 < s.nbytes and np.isin(s, params[0]).all()
+
+
+def test_bench_full_only_options_need_full():
+    # a plain bench.py line is the headline alone: the options of --full's legs are refused without it (before any GPU work)
+    import subprocess
+    import sys
+    for opt in (["--brief"], ["--strong-pieces"], ["--pmc-json", "x.json"], ["--no-cpu-baseline"], ["--cpu-steps", "1"],
+                ["--cpu-seconds", "5"], ["--cpu-threads", "4"], ["--no-pmc"], ["--sustained-seconds", "0"], ["--sust", "1"],
+                ["--loop-iters", "0"], ["--brief-cpu-seconds", "8"], ["--no-other-configs"], ["--other-configs", "c1"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + opt, cwd=ROOT, capture_output=True, text=True, timeout=120)
+        assert r.returncode != 0 and "--full" in r.stderr and not r.stdout.strip(), opt
+
+
 def test_documented_switches_exist_in_the_sources():
     # every SBR_* switch README.md names is read somewhere in the package sources, and every getenv("SBR_...") of the
     # library is documented (README.md, or DESIGN.md for the experiment-only ones)

@@ -1,7 +1,7 @@
 #!/bin/bash
 # throughput of the default config vs rows per GPU:  tools/batch_sweep.sh [batches...]
 for b in ${@:-128 256 512 1024 2048}; do
-  python bench.py --batch $b --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
+  python bench.py --full --batch $b --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 for l in sys.stdin:
     try: d = json.loads(l)

@@ -4,7 +4,7 @@
 #   probe:<name>                 tools/probes/<name>_probe                                  -> <tag>_probe_<name>.txt
 #   bench:<cfg>[:ENV=v,ENV2=v]   one short bench line of a configuration (no CPU / counter / loop legs) -> <tag>_<cfg>[_k]_bench.json
 #   ab:<cfg>:<envA>:<envB>...    same, once per environment variant (e.g. SBR_LIB=tools/probes/variants/libsbr_x.so), A/B on one box
-#   full                         the driver's command, `python bench.py`                    -> <tag>_bench.json
+#   full                         everything the benchmark measures, `python bench.py --full` -> <tag>_bench.json
 #   timeline:<cfg>[:ENV=v,..]    rocprofv3 --kernel-trace --stats of a short run            -> <tag>_<cfg>_kernel_stats.csv, _timeline.txt
 #   pmc:<cfg>                    FETCH_SIZE / WRITE_SIZE passes + tools/pmc_summary.py       -> <tag>_<cfg>_pmc.json
 #   phases                       in-kernel phase counters of the C2 chains                  -> <tag>_rec_phases.txt
@@ -19,7 +19,7 @@ out=$repo/gpurun_out
 mkdir -p $out
 cd $repo
 export TMPDIR=/tmp
-SHORT="--no-cpu-baseline --no-pmc --sustained-seconds 0 --loop-iters 0 --repeats 3"
+SHORT="--full --no-cpu-baseline --no-pmc --sustained-seconds 0 --loop-iters 0 --repeats 3"
 nt=0
 nab=0
 line() {      # one bench line, printed compactly
@@ -51,7 +51,7 @@ job() {
              f=$out/${tag}_${a}_ab${nab}_bench
              env $envs timeout 150 python bench.py --config $a $SHORT > $f.json 2> $f.err; line $f.json "$a $envs"
            done ;;
-    full)  timeout 900 python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -c 1200 $out/${tag}_bench.err
+    full)  timeout 900 python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err; tail -c 1200 $out/${tag}_bench.err
            python -c "
 import json; d=json.loads(open('$out/${tag}_bench.json').read().strip().splitlines()[-1])
 print({k: d.get(k) for k in ('value','ms_per_step','repeats','sustained','train_loop')}); print(d.get('roofline')); print(d.get('hbm_traffic')); print(d.get('phases_us')); print(d.get('other_configs')); print(d.get('mfma_counters'))" ;;

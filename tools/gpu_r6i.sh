@@ -10,7 +10,7 @@ for v in "X=1" "SBR_X6_F16=0 SBR_X6_F16_BWD=0 SBR_GEMM_F16=0 SBR_WGRAD_F16=0" "S
 done
 SBR_PARITY_LOG=$out/r6i_parity.jsonl timeout 1500 python -m pytest tests/test_gpu_parity.py tests/test_gpu_config_parity.py tests/test_golden.py -m gpu -q -k "not c5_as_benched" 2>&1 | tail -2
 timeout 300 python tools/cl_prof.py c5 128 > $out/r6i_cluster_phases_c5_b128.txt 2>&1; cat $out/r6i_cluster_phases_c5_b128.txt | cut -c1-420
-timeout 900 python bench.py > $out/r6i_bench.json 2> $out/r6i_bench.err; tail -c 600 $out/r6i_bench.err; python - <<'P'
+timeout 900 python bench.py --full > $out/r6i_bench.json 2> $out/r6i_bench.err; tail -c 600 $out/r6i_bench.err; python - <<'P'
 import json
 d=json.loads(open('gpurun_out/r6i_bench.json').read().strip().splitlines()[-1])
 print({k: d.get(k) for k in ('value','ms_per_step','vs_baseline')}); print(d.get('roofline')); print({k:(v.get('ms_per_step'), (v.get('cpu_baseline') or {}).get('value')) for k,v in (d.get('other_configs') or {}).items()}); print(d.get('cpu_baseline'))

@@ -2,7 +2,7 @@
 # round 6, call k: C2 with the BPTT chain timed by its own stamps (no event in front of it: the head's in-kernel gate is live)
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 out=gpurun_out; mkdir -p $out
-S="--no-cpu-baseline --no-pmc --sustained-seconds 0 --loop-iters 0 --repeats 5 --no-other-configs"
+S="--full --no-cpu-baseline --no-pmc --sustained-seconds 0 --loop-iters 0 --repeats 5 --no-other-configs"
 for v in "X=1" "SBR_BENCH_EVENTS=1" "X=2" "SBR_BENCH_EVENTS=1"; do
   env $v python bench.py $S > $out/r6k_c2_$v.json 2> $out/r6k.err; python - "$out/r6k_c2_$v.json" "$v" <<'P'
 import json,sys

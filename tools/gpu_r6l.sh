@@ -2,7 +2,7 @@
 # round 6, call l: C2 without the head's in-kernel gate: stamps against events, the training loop, head / tail tests
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 out=gpurun_out; mkdir -p $out
-S="--no-cpu-baseline --no-pmc --sustained-seconds 0 --repeats 5 --no-other-configs"
+S="--full --no-cpu-baseline --no-pmc --sustained-seconds 0 --repeats 5 --no-other-configs"
 for v in "X=1" "SBR_BENCH_EVENTS=1" "X=2" "SBR_BENCH_EVENTS=1"; do
   env $v python bench.py $S --loop-iters 1000 > $out/r6l_c2_$v.json 2> $out/r6l.err; python - "$out/r6l_c2_$v.json" "$v" <<'P'
 import json,sys

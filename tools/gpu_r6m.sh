@@ -3,7 +3,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 out=gpurun_out; mkdir -p $out
 timeout 1200 python -m pytest tests/test_gpu_round6.py tests/test_gpu_batch_builder.py tests/test_gpu_train_cli.py -m gpu -q 2>&1 | tail -5
-S="--no-cpu-baseline --no-pmc --sustained-seconds 0 --repeats 3 --no-other-configs"
+S="--full --no-cpu-baseline --no-pmc --sustained-seconds 0 --repeats 3 --no-other-configs"
 i=0
 for v in "SBR_LIB=tools/probes/variants/libsbr_prebb.so" "X=1" "SBR_LIB=tools/probes/variants/libsbr_prebb.so" "X=2"; do
   i=$((i+1))

@@ -2,7 +2,7 @@
 # round 6, call p: C2 chains, instruction trims -- A/B of libraries on one box: tools/gpu_r6p.sh <libA|-> <libB|-> ...   ('-' = this tree)
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 out=gpurun_out; mkdir -p $out
-S="--no-cpu-baseline --no-pmc --sustained-seconds 0 --repeats 5 --no-other-configs --loop-iters 0"
+S="--full --no-cpu-baseline --no-pmc --sustained-seconds 0 --repeats 5 --no-other-configs --loop-iters 0"
 i=0
 for rep in 1 2; do
 for v in "$@"; do

@@ -2,7 +2,7 @@
 # SQ counters of the recurrent kernels (one rocprofv3 --pmc pass per group); run on the GPU box.
 repo=${GRAFT_REPO_ROOT:-/root/repo}; out=$repo/gpurun_out/sq; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-short="python $repo/bench.py --steps 4 --warmup 2 --no-cpu-baseline"
+short="python $repo/bench.py --full --steps 4 --warmup 2 --no-cpu-baseline"
 rocprofv3 --list-avail 2>/dev/null | grep -o "SQ_[A-Z0-9_]*" | sort -u > $out/avail.txt
 i=0
 for grp in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU" \
