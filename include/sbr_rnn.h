@@ -300,8 +300,12 @@ int sbr_enable_timing(sbr_handle* h, int on);
  * 6 = bf16x6, 3 = fp16x3, 0 = exact-f32 MFMA kernels), "rec_rows_fwd" / "_bwd" (live batch rows among the 16 columns of an
  * MFMA tile), "rec_workgroups_fwd" / "_bwd" (workgroups of the launch = CUs it can occupy); ABI 9: "head_fused" (column chunks of
  * the one-launch full-softmax head a full batch of a training step takes, 0 = the three launches: rnn_one_hot.py:65-71 forward +
- * backward), "scatter_step" (does the scatter-add of a single-call step apply the optimizer to layer 0's index-input rows itself:
- * 0 no, 1 dense block, 2 row-sparse block -- SBR_SCAT_FUSE). */
+ * backward); "head_sampled" (1: a full batch of a training step with a sampled
+ * loss takes the one-launch head -- full 16-row blocks, 128 / 256 / 512 padded units, at most 320 cells = targets + samples --,
+ * 0: the four launches; a key of the same ABI, no new symbol); what the LAST step launched, recorded where it is launched:
+ * "scatter_form" (the scatter-add of layer 0's index-input gradient rows: -1 no step yet, 0 sorted segment reduce, 1 range form,
+ * 2 segment-parallel form, 3 per-element atomics of SBR_FLAG_ATOMIC_SCATTER, 4 / 5 the overlapped tail's polling reduce / its
+ * LDS-row kernel), "row_aware_update" (1: its optimizer pass over layer 0's W_in was the row-aware one). */
 int sbr_query(sbr_handle* h, const char* what, int64_t* value);
 int sbr_phase_times(sbr_handle* h, float us[SBR_N_PHASES]);
 /* Chain-only timing (ABI 8; tooling: bench.py prices the recurrent chain kernels of stacked layers apart from the dense GEMMs

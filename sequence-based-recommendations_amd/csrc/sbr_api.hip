@@ -715,6 +715,12 @@ static inline void layer_gemm_hint(const sbr_handle* h, bool grad_a, bool grad_b
     else if (layer_gemm_f16(h, grad_a || grad_b)) sbr_gemm_hint(2, grad_a ? 512.0f : 1.0f, grad_b ? 512.0f : 1.0f);
 }
 static inline bool simple_gemm(const sbr_handle* h) { return h->lay.cfg.flags & SBR_FLAG_SIMPLE_GEMM; }
+// Does a step over `rows` batch rows take the one-launch sampled head (head_sampled_kernel)?  Asked by the step and by sbr_query.
+static bool head_sampled_taken(const sbr_handle* h, int rows) {
+    const Layout& y = h->lay;
+    return h->head_fuse && !simple_gemm(h) && y.D == 1 && !(y.cfg.flags & SBR_FLAG_F32_MFMA) &&
+           sbr_head_sampled_ok(rows, y.C, y.HLt, y.cfg.loss);
+}
 // Overlapped step tail: time chunks for this step (0 = not taken) and steps per chunk.  Taken for a single index-input layer
 // served by rec_bwd_x6p's progress-publishing form, dense updates, the bf16x6 weight-gradient GEMM and one BPTT launch.
 static int tail_plan(sbr_handle* h, int* ch_out) {
@@ -1225,7 +1231,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         // Round 6: activations, loss, its gradient and dh in ONE launch where the shape allows it (head_sampled_kernel, sbr_head.hip):
         // four launches on twenty workgroups each were 113 us between the two chains of C3.  SBR_HEAD_FUSE=0: the launches below.
         bool head1 = false;
-        if (h->head_fuse && !sg && y.D == 1 && !(y.cfg.flags & SBR_FLAG_F32_MFMA)) {
+        if (head_sampled_taken(h, R)) {
             hipError_t he = hipSuccess;
             head1 = launch_head_sampled(s, hl, Wc, bc, h->bpop, act, h->A(y.a_rowcost), h->A(y.a_dhlast), R, C, Hp, y.Bg, y.S,
                                         y.cfg.row_offset, y.cfg.loss, y.Bg, &he,
@@ -1417,11 +1423,13 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                                                                (const int*)h->A(y.a_soff), (const int*)h->A(y.a_sP), y.cfg.input_size, tnc,
                                                                y.T * y.Bp * y.F, GHp, pl, h->tail_bounds, h->tail_scatter_units, &se,
                                                                mon_in_units, a.t_lo)) {
-                SBR_LAUNCH(se);
-            } else
+                SBR_LAUNCH(se); h->last_scatter_form = 5;
+            } else {
+            h->last_scatter_form = 4;
             SBR_LAUNCH(launch_scatter_reduce_poll(s2, h->Gd(ly.p_Win), a.dxt, (const int*)h->A(y.a_sid), (const int*)h->A(y.a_spos),
                                                   (const int*)h->A(y.a_soff), y.cfg.input_size, tnc, CH, y.T * y.Bp * y.F, GHp, y.Bp, pl,
                                                   0, &h->tail_bounds, h->tail_short_chunks, !serial && h->tail_fence_kb > 0));
+            }
             if (upd_here) SBR_LAUNCH(upd_on(s2, ly.p_Win, ly.p_b));
             SBR_HIP(hipEventRecord(h->ev_tail2, s2));
             // single-call step: the slab reduction IS the W_hid update (one launch, one pass less behind the chain); phase-by-phase
@@ -1530,6 +1538,7 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
             mark_on(h, 5, sm);
             if (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) {
                 SBR_LAUNCH(launch_scatter_rows(s, h->Gd(ly.p_Win), a.dxt, h->bX, a.len, y.T, y.Bp, y.F, GHp));
+                h->last_scatter_form = 3;
             } else {
                 if (sm == s) SBR_HIP(hipStreamWaitEvent(s, h->ev_sort, 0));      // (the sort ran on the side stream)
                 hipError_t se = hipSuccess;
@@ -1539,15 +1548,17 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                 if (range_on == 1 && y.a_srpart && GHp <= 1024 &&
                     launch_scatter_range(sm, h->Gd(ly.p_Win), a.dxt, (const int*)h->A(y.a_sid), (const int*)h->A(y.a_spos), (const int*)h->A(y.a_soff),
                                          y.cfg.input_size, GHp, h->A(y.a_srpart), (int*)h->A(y.a_srid), SBR_SCAT_RANGES, &se)) {
-                    SBR_LAUNCH(se);
+                    SBR_LAUNCH(se); h->last_scatter_form = 1;
                 } else
                 if (range_on == 2 && y.a_srpart && launch_scatter_wide(sm, h->Gd(ly.p_Win), a.dxt, (const int*)h->A(y.a_sid), (const int*)h->A(y.a_spos),
                                                                   (const int*)h->A(y.a_soff), y.cfg.input_size, y.T * y.Bp * y.F, GHp,
                                                                   h->A(y.a_srpart), (int*)h->A(y.a_srid), y.sr_slots, &se)) {
-                    SBR_LAUNCH(se);
-                } else
+                    SBR_LAUNCH(se); h->last_scatter_form = 2;
+                } else {
+                h->last_scatter_form = 0;
                 SBR_LAUNCH(launch_scatter_reduce(sm, h->Gd(ly.p_Win), a.dxt, (const int*)h->A(y.a_sid), (const int*)h->A(y.a_spos),
                                                  (const int*)h->A(y.a_soff), y.cfg.input_size, y.T * y.Bp * y.F, GHp, y.Bp));
+                }
             }
             mark_on(h, 6, sm);
         } else {
@@ -1694,6 +1705,7 @@ extern "C" int sbr_apply_update(sbr_handle* h) {
     // over W_in reads / clears the gradient of the touched rows only (launch_update_rows_aware).  SBR_ROW_AWARE_UPDATE=0: update_kernel.
     const bool row_aware = h->row_aware && h->in_train_step && y.a_srpart && !y.n_sparse && !y.E && y.D == 1 && h->tail_nc < 2 &&
                            !(y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) && !simple_gemm(h) && !simple_rec(h) && ((y.G * y.layer[0].Hp) & 3) == 0;
+    h->last_row_aware = row_aware;
     auto upd_front = [&](size_t hi) -> hipError_t {
         if (!row_aware) return upd(0, hi);
         const LayerLayout& l0 = y.layer[0];
@@ -1719,6 +1731,8 @@ extern "C" int sbr_apply_update(sbr_handle* h) {
             const SparseBlockLayout& sb = y.sparse[b];
             if (sb.kind != 0 || h->sp_exchanged[b] || !h->side_pending || y.D != 1 || y.E) continue;      // (plain index input, one direction: the scatter-add ran on this stream)
             const int nmax = y.T * y.Bp * y.F;
+            // (the atomic scatter-add reads no sorted ids, so this stream has not waited for the side stream's sort yet)
+            if (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) SBR_HIP(hipStreamWaitEvent(h->stream, h->ev_sort, 0));
             SBR_LAUNCH(launch_sparse_step_list(h->stream, sparse_rows(h, b), sparse_upd(h), (const int*)h->A(y.a_sid),
                                                (const int*)h->A(y.a_soff) + y.cfg.input_size, 0, nmax, (int)h->step_count));
             stepped[b] = true;
@@ -2105,6 +2119,11 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
         *value = (h->head_fuse && y.cfg.loss == SBR_LOSS_CCE && !simple_gemm(h) && !(y.cfg.flags & (SBR_FLAG_BF16_PROJECTION | SBR_FLAG_F32_MFMA)) &&
                   y.D == 1 && y.B == y.Bp && sbr_head_plan(y.Bp, y.N, y.HLt, &cc, &cw, &lds) && (size_t)cc * y.Bp * y.HLt <= y.ws_floats) ? cc : 0;
     }
+    else if (w == "head_sampled") *value = head_sampled_taken(h, y.B) ? 1 : 0;      // a full batch of a training step: head_sampled_kernel, or the four launches
+    // what the LAST step launched for the gradient of layer 0's index-input rows (-1: no step yet): 0 sorted segment reduce, 1 range form,
+    // 2 segment-parallel form, 3 per-element atomics (SBR_FLAG_ATOMIC_SCATTER), 4 / 5 the overlapped tail's polling reduce / LDS-row kernel
+    else if (w == "scatter_form") *value = h->last_scatter_form;
+    else if (w == "row_aware_update") *value = h->last_row_aware ? 1 : 0;      // ... and whether its optimizer pass over W_in was the row-aware one
     else if (w == "cluster") { RecArgs a = rec_args(h, (y.L - 1) * y.D); *value = (!simple_rec(h) && sbr_rec_cluster_ok(a)) ? 1 : 0; }
     else if (w == "rec_kernel") {   // family serving the top layer: 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other
         RecArgs a = rec_args(h, (y.L - 1) * y.D);

@@ -212,6 +212,7 @@ struct sbr_handle {
     hipStream_t side3; hipEvent_t ev_tail3;      // side3: the overlapped tail's monitor (tail_monitor_kernel)
     int tail_short_chunks;  // time chunks (from t = 0) whose scatter-add entries are cut into short pieces (SBR_TAIL_SHORT_CHUNKS)
     double tail_geom;       // SBR_TAIL_GEOM: growth of the small time chunks near t = 0 (<= 1: equal chunks)
+    int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
     bool tail_cost_scanned = false;                                       // this step's sort was followed by launch_scatter_cost_scan
     int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
     int tail_mon_units;                                                   // SBR_TAIL_MONITOR_IN_UNITS: the monitor is a workgroup of the scatter-add launch
@@ -479,6 +480,7 @@ bool launch_wgrad_slabs(hipStream_t s, const float* hs, const float* dxt, const 
 // sbr_head.hip: logits + softmax / CCE + dh of a full-softmax head in one launch (C1 / C2-class catalogues); false: not served
 bool sbr_head_plan(int Bp, int N, int Hp, int* CC, int* CW, size_t* lds_bytes);
 // the sampled head in one launch (sbr_head.hip: head_sampled_kernel); false: shape not served, nothing launched
+bool sbr_head_sampled_ok(int rows, int C, int Hp, int loss);      // (the shapes it serves: launch_head_sampled's own test, sbr_query's too)
 bool launch_head_sampled(hipStream_t s, const float* h, const float* Wc, const float* bc, const float* pop, float* act, float* rowcost,
                          float* dh, int rows, int C, int Hp, int Bg, int S, int row_offset, int loss, int Bglobal, hipError_t* err,
                          unsigned long long* prof = nullptr);

@@ -605,12 +605,17 @@ __global__ void __launch_bounds__(64 * NW) head_sampled_kernel(SampArgs a) {
 #undef SAMP_STAMP
 }
 
+// the shapes head_sampled_kernel serves: full 16-row blocks, Hp in {128, 256, 512}, at most 320 cells, a sampled loss
+bool sbr_head_sampled_ok(int rows, int C, int Hp, int loss) {
+    if (!(Hp == 128 || Hp == 256 || Hp == 512) || rows < 16 || (rows & 15) || C < 1 || C > 320) return false;
+    return !(loss == SBR_LOSS_CCE || SBR_LOSS_IS_MARGIN(loss));
+}
+
 // false: shape not served, nothing launched (the caller keeps the four launches)
 bool launch_head_sampled(hipStream_t s, const float* h, const float* Wc, const float* bc, const float* pop, float* act, float* rowcost,
                          float* dh, int rows, int C, int Hp, int Bg, int S, int row_offset, int loss, int Bglobal, hipError_t* err,
                          unsigned long long* prof) {
-    if (!(Hp == 128 || Hp == 256 || Hp == 512) || rows < 16 || (rows & 15) || C < 1 || C > 320) return false;
-    if (loss == SBR_LOSS_CCE || SBR_LOSS_IS_MARGIN(loss)) return false;
+    if (!sbr_head_sampled_ok(rows, C, Hp, loss)) return false;
     SampArgs a{h, Wc, bc, pop, act, rowcost, dh, C, Bg, S, row_offset, loss, 1.0f / (float)Bglobal, prof};
     const int nw = Hp == 512 ? 4 : 8;
     const size_t lds = ((size_t)nw * 16 * Hp + 3 * nw * 16) * sizeof(float);

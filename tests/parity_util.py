@@ -125,7 +125,7 @@ def params_ok(r, steps=2, bar=1e-3, tol_g=1e-4):
 
 def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater="adam", flags=0, full=False,
                  reg=0.0, steps=2, popscale=1.0, scale=None, emb=0, bi=False, zipf=False, k=None, gap=0.0, tweak=None,
-                 balance=1.0, unique=True, default_target=None, grad_floor=1e-12, queries=()):
+                 balance=1.0, unique=True, default_target=None, grad_floor=1e-12, queries=(), queries_after=()):
     """Returns dict of relative errors (engine float32 vs oracle float64).
     grad_floor: added to the largest oracle magnitude of a gradient array before dividing -- arrays far smaller than it are
     compared absolutely (the fp16 split of the BPTT chain's gradient operand has an absolute floor, csrc/sbr_rec_p.hip).
@@ -194,6 +194,8 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
             upd_t.apply(tparams, [np.asarray(g, dtype=np.float64) for g in ge])
             costs_o.append(O.train_function(oparams, cfg, upd, obatch))
             costs_e.append(eng.train_step(sync=True))
+        for qn in queries_after:      # what the last training step launched (sbr_query keys that record it): out["q:<name>"]
+            out["q:" + qn] = float(eng.query(qn))
         new = eng.get_all_param_values()
         out["params_after_%d_steps" % steps] = max(rel_err(a, b) for a, b in zip(new, oparams))
         out["params_twin"] = max(rel_err(a, b) for a, b in zip(new, tparams))

@@ -119,13 +119,14 @@ def test_batches_built_beside_the_step_in_flight_are_the_batches_the_steps_read(
 
 
 @pytest.mark.parametrize("loss", ["Blackout", "BPR", "TOP1"])
-@pytest.mark.parametrize("H", [128, 256])
+@pytest.mark.parametrize("H", [128, 256, 512])
 def test_one_launch_sampled_head_against_the_oracle_and_the_four_launches(loss, H, monkeypatch):
     """head_sampled_kernel (activations, sampled loss, its gradient and dh in one launch: full 16-row blocks, Hp in {128, 256, 512},
     at most 320 cells) against the float64 oracle through the usual step comparison, and against the same engine on the four launches
     (SBR_HEAD_FUSE=0): costs and every gradient agree to f32 rounding -- both are f32-class, the one launch on exact-f32 products."""
     from sbr_amd.engine import RNNEngine
-    r = PU.compare_step("LSTM", [H], loss, N=900, B=32, T=9, S=24, scale=0.08)
+    r = PU.compare_step("LSTM", [H], loss, N=900, B=32, T=9, S=24, scale=0.08 if H < 512 else 0.03, queries=("head_sampled",))
+    assert r["q:head_sampled"] == 1, r
     assert r["cost"] <= 2e-6 and r["grad_worst"] <= 5e-6, r
     params = O.init_params("LSTM", [H], 900, np.random.default_rng(4), dtype=np.float32)
     batch = PU.make_batch(np.random.default_rng(5), 32, 9, 900)
@@ -135,6 +136,7 @@ def test_one_launch_sampled_head_against_the_oracle_and_the_four_launches(loss, 
         monkeypatch.setenv("SBR_HEAD_FUSE", fuse)
         eng = RNNEngine(cell="LSTM", layers=[H], n_items=900, max_length=9, batch_size=32, loss=loss, n_samples=24)
         try:
+            assert eng.query("head_sampled") == int(fuse)      # (sbr_query: which of the two forms this engine's steps take)
             eng.set_all_param_values(params)
             eng.set_batch(batch["X"], batch["mask"], batch["target"], samples, batch["pop"])
             c = eng.forward_backward()
