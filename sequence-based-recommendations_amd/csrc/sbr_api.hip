@@ -9,6 +9,7 @@
 #include <algorithm>
 #include <stdlib.h>
 #include <math.h>
+#include <array>
 #include <atomic>
 #include <chrono>
 
@@ -146,10 +147,6 @@ int sbr_build_layout(const sbr_config& cfg, Layout& lay, std::string& err) {
     lay.a_ws = take(lay.ws_floats);
     lay.ws2_floats = 4 * lay.ws_floats;          // up to 256 weight-gradient slabs
     lay.a_ws2 = take(lay.ws2_floats);
-    // the split-K workspace of the dW_out GEMM when SBR_TAIL_OUT_STREAM moves it off the side stream (the polling weight-gradient
-    // GEMM owns ws2 meanwhile): an experiment switch -- taken from the arena only when it is set
-    lay.ws3_floats = 0;      // (the output layer's dW_out GEMM on a stream of its own: measured slower, profiles/round4_variants.txt calls n, q)
-    lay.a_ws3 = lay.ws3_floats ? take(lay.ws3_floats) : 0;
     lay.a_X = take((size_t)Bp * T * lay.F);
     lay.a_len = take(Bp);
     lay.a_tgt = take((size_t)std::max(lay.Bg, Bp) * lay.NT);
@@ -333,6 +330,44 @@ extern "C" int sbr_arena_bytes(const sbr_config* cfg, size_t* bytes) {
     return SBR_OK;
 }
 
+// The environment, read once per engine: the only getenv calls of the library.  A test that flips a switch between two engines of
+// a process gets what it asked for, and a switch flipped later does not reach an engine that is alive.
+static SbrSwitches sbr_read_switches() {
+    SbrSwitches sw;
+    auto num = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    auto flag = [&](const char* name, int dflt) { return num(name, dflt) != 0 ? 1 : 0; };
+    sw.rpt = num("SBR_RPT", sw.rpt);
+    sw.bwd_chunks = std::min(std::max(num("SBR_BWD_CHUNKS", sw.bwd_chunks), 1), SBR_BWD_CHUNKS);   // chunking measured neutral-to-slower at C2 (relaunch ~20 us); kept + tested
+    sw.cluster = flag("SBR_CLUSTER", sw.cluster);
+    sw.cl_linear = flag("SBR_CL_LINEAR", sw.cl_linear);
+    sw.cl16 = flag("SBR_CL16", sw.cl16);
+    sw.c16_two_level = flag("SBR_C16_TWO_LEVEL", sw.c16_two_level);
+    sw.x6_pipe = num("SBR_X6_PIPE", sw.x6_pipe);
+    sw.x6_f16 = flag("SBR_X6_F16", sw.x6_f16);
+    sw.x6_f16_bwd = flag("SBR_X6_F16_BWD", sw.x6_f16_bwd);
+    sw.fuse_gather = flag("SBR_FUSE_GATHER", sw.fuse_gather);
+    sw.gemm_f16 = num("SBR_GEMM_F16", sw.gemm_f16);
+    sw.wgrad_f16 = num("SBR_WGRAD_F16", sw.wgrad_f16);
+    sw.tail_overlap = num("SBR_TAIL_OVERLAP", sw.tail_overlap);
+    sw.tail_scatter_lds = num("SBR_TAIL_SCATTER_LDS", sw.tail_scatter_lds);
+    sw.tail_trace = num("SBR_TAIL_TRACE", sw.tail_trace);
+    sw.scat_range = num("SBR_SCAT_RANGE", sw.scat_range);
+    sw.sparse_out_early = num("SBR_SPARSE_OUT_EARLY", sw.sparse_out_early);
+    sw.head_fuse = num("SBR_HEAD_FUSE", sw.head_fuse);
+    if (const char* e = getenv("SBR_HEAD_WAIT_TICKS")) sw.head_wait_ticks = strtoull(e, nullptr, 10);
+    sw.out_fuse = flag("SBR_OUT_FUSE", sw.out_fuse);
+    sw.row_aware = flag("SBR_ROW_AWARE_UPDATE", sw.row_aware);
+    return sw;
+}
+
+// the handle's priority side streams and its disable-timing events: what sbr_create makes and sbr_destroy drains and frees
+static std::array<hipStream_t*, 3> handle_streams(sbr_handle* h) { return {&h->side, &h->side2, &h->side3}; }
+static std::array<hipEvent_t*, 15> handle_events(sbr_handle* h) {
+    return {&h->ev_fork, &h->ev_join, &h->ev_sort, &h->ev_lg, &h->ev_fill, &h->ev_og, &h->ev_tail, &h->ev_tail2, &h->ev_cells,
+            &h->ev_chunk[0], &h->ev_chunk[1], &h->ev_chunk[2], &h->ev_chunk[3], &h->ev_bb, &h->ev_bbw};
+}
+static_assert(SBR_BWD_CHUNKS == 4, "handle_events lists ev_chunk[0 .. 3]");
+
 extern "C" int sbr_create(const sbr_config* cfg, void* arena, size_t arena_bytes, void* stream, sbr_handle** out) {
     CHECK_ARG(cfg && out, "null argument");
     int ndev = 0;
@@ -357,101 +392,31 @@ extern "C" int sbr_create(const sbr_config* cfg, void* arena, size_t arena_bytes
         h->arena = (float*)p; h->own_arena = true;
     }
     sbr_param_descs(h->lay, h->descs);
-    h->rpt = 16;
-    {   // rows per workgroup of the bf16x6 recurrent kernels: the per-step latency of the chain does not depend on the
-        // tile height, so take the smallest tile whose workgroups still fit the 256 CUs in one round (measured, GRU-128
-        // T=200: B=512 548k seq/s at 4 rows vs 444k at 8; B=1024 856k vs 766k at 8 / 643k at 16; B=2048 1078k at 8 vs
-        // 922k at 4 (two rounds) / 1047k at 16; B=4096 1380k at 16 vs 1124k at 8)
-        const char* e = getenv("SBR_RPT");
-        int r = e ? atoi(e) : 0;
-        if (r != 1 && r != 2 && r != 4 && r != 8 && r != 16) { r = 4; while (r < 16 && h->lay.Bp / r > 256) r <<= 1; }
-        h->rpt = r;
-    }
-    {
-        const char* e = getenv("SBR_BWD_CHUNKS");
-        const int c = e ? atoi(e) : 1;   // chunking measured neutral-to-slower at C2 (relaunch ~20 us); kept + tested
-        h->bwd_chunks = c < 1 ? 1 : (c > SBR_BWD_CHUNKS ? SBR_BWD_CHUNKS : c);
-        h->wgrad_slices = 256;
-        const char* cl = getenv("SBR_CLUSTER");
-        h->cluster = cl ? atoi(cl) != 0 : 1;
-        const char* ln = getenv("SBR_CL_LINEAR");
-        h->cl_linear = ln ? atoi(ln) != 0 : 0;
-        h->cl_epoch = 0;
-        h->wgrad_x6 = 1;
-        h->x6_split = 1;
-        const char* xp = getenv("SBR_X6_PIPE");
-        h->x6_pipe = xp ? atoi(xp) : 1;   // 0: barrier kernels (x6s), 1: pipelined without the matrix-pipe gate, 2: with it (rounds 1-3: with
-                                          // one sparse instruction per k-block the partner's phase is over long before, the gate only costs its read)
-        const char* fg = getenv("SBR_FUSE_GATHER");
-        h->fuse_gather = fg ? atoi(fg) != 0 : 1;
-    }
-    h->n_rows = 0; h->step_count = 0; h->have_batch = false; h->fwd_done = false; h->timing = false;
-    h->grads_clean = false; h->timing_marks = 0; h->marks_shared = 0; h->tail_swapped = false;
-    h->swap_tail = true;
-    { const char* e = getenv("SBR_TAIL_OVERLAP"); h->tail_overlap = e ? atoi(e) : 1; }
-    // Tuned constants of the overlapped tail (each was an environment switch while it was being measured -- rounds 2 - 5; the A/B
-    // numbers are in profiles/round2_b_tail_variants.txt, round3_*_variants.txt, round5_variants.txt and DESIGN.md sections 3, 3a, 3d)
-    h->tail_chunks_max = 8; h->tail_pub_every = 2; h->tail_short_chunks = 3;
-    // (every switch is read here, once per handle: a test that flips one between two engines of a process gets what it asked for)
-    if (getenv("SBR_TAIL_TRACE") && atoi(getenv("SBR_TAIL_TRACE"))) {      // tools/tail_trace.py
+    h->sw = sbr_read_switches();
+    const SbrSwitches& sw = h->sw;
+    // rows per workgroup of the bf16x6 recurrent kernels: the per-step latency of the chain does not depend on the
+    // tile height, so take the smallest tile whose workgroups still fit the 256 CUs in one round (measured, GRU-128
+    // T=200: B=512 548k seq/s at 4 rows vs 444k at 8; B=1024 856k vs 766k at 8 / 643k at 16; B=2048 1078k at 8 vs
+    // 922k at 4 (two rounds) / 1047k at 16; B=4096 1380k at 16 vs 1124k at 8)
+    h->rpt = sw.rpt;
+    if (h->rpt != 1 && h->rpt != 2 && h->rpt != 4 && h->rpt != 8 && h->rpt != 16) { h->rpt = 4; while (h->rpt < 16 && h->lay.Bp / h->rpt > 256) h->rpt <<= 1; }
+    if (sw.tail_trace) {      // tools/tail_trace.py
         if (hipMalloc(&h->tail_trace, 16384 * sizeof(unsigned long long)) != hipSuccess) h->tail_trace = nullptr;
         else (void)hipMemset(h->tail_trace, 0, 16384 * sizeof(unsigned long long));
     }
-    h->tail_fence_kb = 124; h->tail_early_sort = 1; h->tail_out_stream = 0; h->tail_fuse_slabs = 1; h->tail_slab_growth = 0.35;
-    { const char* e = getenv("SBR_TAIL_SCATTER_LDS"); h->tail_scatter_lds = e ? atoi(e) : 1; }      // 0: the polling range form (also the way out when the LDS rows run out)
-    h->tail_geom = h->tail_scatter_lds ? 1.6 : 2.6;
-    h->tail_mon_units = 1; h->tail_first = 6; h->tail_scatter_units = 192; h->tail_gemm_groups = 64; h->tail_slab_max = 512;
-    h->fold_dh = true;
-    { const char* e = getenv("SBR_WGRAD_F16"); h->wgrad_f16 = e ? atoi(e) : 1; }
-    h->wgrad_x6_wgs = 512;
-    h->tail_nc = 0; h->tail_ch = 0; h->prog_epoch = 0; h->tail_updated = false; h->ev_tail = nullptr; h->ev_tail2 = nullptr; h->side2 = nullptr; h->ev_lg_rec = nullptr; h->side3 = nullptr; h->ev_tail3 = nullptr; h->tail_sorted = false; h->out3 = false;
-    h->step_open = false; h->tail_join_pending = false;
-    memset(h->ev, 0, sizeof(h->ev)); h->ring_used = 0; h->ring_cur = 0;
-    memset(h->ev_ch, 0, sizeof(h->ev_ch)); h->ch_n = 0; h->chain_timing = false;
-    h->side = nullptr; h->ev_fork = nullptr; h->ev_join = nullptr; h->ev_sort = nullptr; h->ev_lg = nullptr; h->ev_fill = nullptr; h->ev_og = nullptr;
-    for (int c = 0; c < SBR_BWD_CHUNKS; ++c) h->ev_chunk[c] = nullptr;
-    h->in_train_step = false; h->side_pending = false; h->deferred_join = false; h->fill_done = false; h->og_recorded = false;
-    h->out_early = false; h->dh_slabs_n = 0;
-    h->s_bb = nullptr; h->ev_bb = nullptr; h->ev_bbw = nullptr; h->bb_set = 0; h->batch_seq = 0; h->set_use[0] = h->set_use[1] = 0;
-    h->lg_seq = 0; h->train_fwd_open = false; h->bb_slow = 0; h->bb_unread = false;
-    { const char* e = getenv("SBR_SPARSE_OUT_EARLY"); h->sparse_out_early = e ? atoi(e) : 1; }
-    h->cells_early = false; h->wout_early = false;
-    h->ev_cells = nullptr;
-    { const char* e = getenv("SBR_HEAD_FUSE"); h->head_fuse = e ? atoi(e) : 1; }
-    { const char* e = getenv("SBR_OUT_FUSE"); h->out_fuse = e ? atoi(e) != 0 : 1; }
-    { const char* e = getenv("SBR_ROW_AWARE_UPDATE"); h->row_aware = e ? atoi(e) != 0 : 1; }
-    h->out_stepped = false;
-    h->head_epoch = 0;
-    h->lag_host = nullptr; h->lag_slot = 0; h->lag_pending = -1; h->lag_counter = 0; h->lag_seq[0] = h->lag_seq[1] = 0;
     // The side stream must not share a hardware queue with the main stream (HIP multiplexes streams onto
     // GPU_MAX_HW_QUEUES = 4 queues; with RCCL's streams alive the side stream landed on the main stream's queue and
     // every "overlapped" kernel serialised: +150 us per step in the data-parallel path).  Streams of another priority
     // level get their own queues.
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    if (hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_sort, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_lg, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_fill, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_og, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_tail, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_tail2, hipEventDisableTiming) != hipSuccess ||
-        hipStreamCreateWithPriority(&h->side2, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipStreamCreateWithPriority(&h->side3, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_tail3, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_cells, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_chunk[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_chunk[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_chunk[2], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_chunk[3], hipEventDisableTiming) != hipSuccess ||
+    bool ok = true;
+    for (hipStream_t* st : handle_streams(h)) ok = ok && hipStreamCreateWithPriority(st, hipStreamNonBlocking, prio_hi) == hipSuccess;
+    for (hipEvent_t* ev : handle_events(h)) ok = ok && hipEventCreateWithFlags(ev, hipEventDisableTiming) == hipSuccess;
 #if SBR_BB_STREAM
-        hipStreamCreateWithPriority(&h->s_bb, hipStreamNonBlocking, SBR_BB_STREAM == 2 ? prio_lo : prio_hi) != hipSuccess ||
+    ok = ok && hipStreamCreateWithPriority(&h->s_bb, hipStreamNonBlocking, SBR_BB_STREAM == 2 ? prio_lo : prio_hi) == hipSuccess;
 #endif
-        hipEventCreateWithFlags(&h->ev_bb, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&h->ev_bbw, hipEventDisableTiming) != hipSuccess ||
-        hipHostMalloc((void**)&h->lag_host, 8 * sizeof(float), hipHostMallocDefault) != hipSuccess) {
+    if (!ok || hipHostMalloc((void**)&h->lag_host, 8 * sizeof(float), hipHostMallocDefault) != hipSuccess) {
         sbr_set_error("side stream creation failed"); sbr_destroy(h); return SBR_EHIP;
     }
 #if !SBR_BB_STREAM
@@ -464,7 +429,6 @@ extern "C" int sbr_create(const sbr_config* cfg, void* arena, size_t arena_bytes
     hipError_t e = hipMemsetAsync(h->arena, 0, h->lay.s_end * sizeof(float), h->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     if (e != hipSuccess) { sbr_set_error("arena initialisation failed: %s", hipGetErrorString(e)); sbr_destroy(h); return SBR_EHIP; }
-    h->sp_exchanged[0] = h->sp_exchanged[1] = 0; h->sp_ncand[0] = h->sp_ncand[1] = 0; h->sp_epoch = 0;
     if (h->lay.n_at > 0) {
         std::vector<float> at(h->lay.n_at);
         const double lr = cfg->learning_rate, b1 = cfg->beta1, b2 = cfg->beta2;
@@ -481,32 +445,16 @@ extern "C" void sbr_destroy(sbr_handle* h) {
     // work still in flight may write into what is freed below (the lagged step's report into pinned memory, a batch build into the
     // arena's second set): let every stream of the engine drain first
     (void)hipStreamSynchronize(h->stream);
-    if (h->side) (void)hipStreamSynchronize(h->side);
-    if (h->side2) (void)hipStreamSynchronize(h->side2);
-    if (h->side3) (void)hipStreamSynchronize(h->side3);
+    for (hipStream_t* st : handle_streams(h)) if (*st) (void)hipStreamSynchronize(*st);
     for (int r = 0; r < sbr_handle::kRing; ++r)
         for (int i = 0; i < SBR_N_PHASES; ++i) if (h->ev[r][i]) (void)hipEventDestroy(h->ev[r][i]);
     for (int r = 0; r < sbr_handle::kChain; ++r)
         for (int i = 0; i < 2; ++i) if (h->ev_ch[r][i]) (void)hipEventDestroy(h->ev_ch[r][i]);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
-    if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_sort) (void)hipEventDestroy(h->ev_sort);
-    if (h->ev_lg) (void)hipEventDestroy(h->ev_lg);
-    if (h->ev_fill) (void)hipEventDestroy(h->ev_fill);
-    if (h->ev_og) (void)hipEventDestroy(h->ev_og);
-    if (h->ev_tail) (void)hipEventDestroy(h->ev_tail);
-    if (h->ev_tail2) (void)hipEventDestroy(h->ev_tail2);
-    if (h->side2) (void)hipStreamDestroy(h->side2);
+    for (hipEvent_t* ev : handle_events(h)) if (*ev) (void)hipEventDestroy(*ev);
 #if SBR_BB_STREAM
     if (h->s_bb) (void)hipStreamDestroy(h->s_bb);
 #endif
-    if (h->ev_bb) (void)hipEventDestroy(h->ev_bb);
-    if (h->ev_bbw) (void)hipEventDestroy(h->ev_bbw);
-    if (h->side3) (void)hipStreamDestroy(h->side3);
-    if (h->ev_tail3) (void)hipEventDestroy(h->ev_tail3);
-    if (h->ev_cells) (void)hipEventDestroy(h->ev_cells);
-    for (int c = 0; c < SBR_BWD_CHUNKS; ++c) if (h->ev_chunk[c]) (void)hipEventDestroy(h->ev_chunk[c]);
+    for (hipStream_t* st : handle_streams(h)) if (*st) (void)hipStreamDestroy(*st);
     if (h->lag_host) (void)hipHostFree(h->lag_host);
     if (h->own_arena && h->arena) (void)hipFree(h->arena);
     if (h->tail_trace) (void)hipFree(h->tail_trace);
@@ -676,6 +624,11 @@ extern "C" int sbr_set_batch(sbr_handle* h, const int32_t* X, const int32_t* len
 // ---------------------------------------------------------------------------------------
 // step phases
 // ---------------------------------------------------------------------------------------
+// what the kernel-family tests (sbr_rec_*_ok) and the launchers take from the engine's switches
+static inline void rec_switches(const sbr_handle* h, RecArgs& a) {
+    a.rpt = h->rpt; a.x6_pipe = h->sw.x6_pipe; a.x6_f16 = h->sw.x6_f16; a.x6_f16_bwd = h->sw.x6_f16_bwd;
+    a.cl16 = h->sw.cl16; a.c16_two_level = h->sw.c16_two_level;
+}
 static RecArgs rec_args(sbr_handle* h, int l) {
     const Layout& y = h->lay; const LayerLayout& ly = y.layer[l];
     RecArgs a; memset(&a, 0, sizeof(a));
@@ -690,11 +643,11 @@ static RecArgs rec_args(sbr_handle* h, int l) {
     for (int k = 0; k < 4; ++k) a.g[k] = h->A(ly.a_g[k]);
     a.dxt = h->A(ly.a_dxt); a.dhi = h->A(ly.a_dhi); a.part = h->A(ly.a_part);
     a.xt_blocked = 0;
-    a.rpt = h->rpt; a.x6_split = h->x6_split; a.x6_pipe = h->x6_pipe;
+    rec_switches(h, a);
     a.t_lo = 0; a.t_hi = y.T; a.chunk = 0; a.state = h->A(ly.a_state);
     a.f32_mfma = (y.cfg.flags & SBR_FLAG_F32_MFMA) ? 1 : 0;
     a.prof = (y.cfg.flags & SBR_FLAG_PROFILE_REC) ? (unsigned long long*)h->A(y.a_prof) : nullptr;
-    a.cluster = h->cluster; a.cl_linear = h->cl_linear; a.fault = (int*)h->A(y.a_fault);
+    a.cluster = h->sw.cluster; a.cl_linear = h->sw.cl_linear; a.fault = (int*)h->A(y.a_fault);
     a.clx = (int*)h->A(y.a_clx); a.epoch = (++h->cl_epoch) & 0x07FFFFFF;
     a.relu = (y.cfg.cell == SBR_CELL_VANILLA && (l / y.D > 0 || y.E)) ? 1 : 0;   // stock RecurrentLayer: rectify [3P]
     return a;
@@ -706,8 +659,7 @@ static inline bool simple_rec(const sbr_handle* h) { return h->lay.cfg.flags & S
 // (SBR_GEMM_F16=0: bf16x6 as in rounds 1-3).  SBR_FLAG_BF16_LAYERS: plain bf16 operands, one MFMA (BASELINE configs[4]).
 static inline bool layer_gemm_f16(const sbr_handle* h, bool with_gradient) {
     const Layout& y = h->lay;
-    static const int on = [] { const char* e = getenv("SBR_GEMM_F16"); return e ? atoi(e) : 1; }();
-    if (!on || y.cfg.cell == SBR_CELL_VANILLA) return false;
+    if (!h->sw.gemm_f16 || y.cfg.cell == SBR_CELL_VANILLA) return false;
     return !with_gradient || (y.cfg.grad_clip > 0.0f && y.cfg.grad_clip <= 100.0f);
 }
 static inline void layer_gemm_hint(const sbr_handle* h, bool grad_a, bool grad_b) {
@@ -718,7 +670,7 @@ static inline bool simple_gemm(const sbr_handle* h) { return h->lay.cfg.flags & 
 // Does a step over `rows` batch rows take the one-launch sampled head (head_sampled_kernel)?  Asked by the step and by sbr_query.
 static bool head_sampled_taken(const sbr_handle* h, int rows) {
     const Layout& y = h->lay;
-    return h->head_fuse && !simple_gemm(h) && y.D == 1 && !(y.cfg.flags & SBR_FLAG_F32_MFMA) &&
+    return h->sw.head_fuse && !simple_gemm(h) && y.D == 1 && !(y.cfg.flags & SBR_FLAG_F32_MFMA) &&
            sbr_head_sampled_ok(rows, y.C, y.HLt, y.cfg.loss);
 }
 // Overlapped step tail: time chunks for this step (0 = not taken) and steps per chunk.  Taken for a single index-input layer
@@ -726,15 +678,15 @@ static bool head_sampled_taken(const sbr_handle* h, int rows) {
 static int tail_plan(sbr_handle* h, int* ch_out) {
     const Layout& y = h->lay;
     *ch_out = 0;
-    if (!h->tail_overlap || y.tail_keys < 2 || y.n_sparse || h->bwd_chunks != 1 || !h->wgrad_x6) return 0;
+    if (!h->sw.tail_overlap || y.tail_keys < 2 || y.n_sparse || h->sw.bwd_chunks != 1) return 0;
     if (simple_rec(h) || simple_gemm(h) || (y.cfg.flags & (SBR_FLAG_F32_MFMA | SBR_FLAG_ATOMIC_SCATTER))) return 0;
     RecArgs a; memset(&a, 0, sizeof(a));
     a.cell = y.cfg.cell; a.T = y.T; a.Bp = y.Bp; a.H = y.layer[0].H; a.Hp = y.layer[0].Hp; a.G = y.G; a.clip = y.cfg.grad_clip;
-    a.rpt = h->rpt; a.x6_split = h->x6_split; a.x6_pipe = h->x6_pipe; a.n_in = y.layer[0].n_in_p;
+    rec_switches(h, a); a.n_in = y.layer[0].n_in_p;
     a.hs = h->A(y.layer[0].a_hs); a.cs = h->A(y.layer[0].a_cs);
     for (int k = 0; k < 4; ++k) a.g[k] = h->A(y.layer[0].a_g[k]);
     if (!sbr_rec_x6p_tail_ok(a)) return 0;
-    int nc = std::min(std::min(y.tail_keys, h->tail_chunks_max), y.T / 16);
+    int nc = std::min(std::min(y.tail_keys, kTailChunksMax), y.T / 16);
     if (nc < 2) return 0;
     const int ch = (y.T + nc - 1) / nc;
     nc = (y.T + ch - 1) / ch;
@@ -742,18 +694,18 @@ static int tail_plan(sbr_handle* h, int* ch_out) {
     *ch_out = ch;
     // Chunk bounds.  The scatter-add of a time chunk can start when the chain has left it, and the chain leaves chunk 0 last:
     // with equal chunks an eighth of the step's entries waits for the chain's end (30 - 45 us of polling waves behind it,
-    // profiles/round3_c_timeline.txt).  So the chunks near t = 0 are small -- 1, 3, 7, 18 ... steps (powers of SBR_TAIL_GEOM,
-    // default 2.6; <= 1: equal chunks) -- until a power exceeds the equal share of what is left, which the remaining chunks then
+    // profiles/round3_c_timeline.txt).  So the chunks near t = 0 are small -- 1, 3, 7, 18 ... steps (powers of sbr_tail_geom,
+    // 2.6; <= 1: equal chunks) -- until a power exceeds the equal share of what is left, which the remaining chunks then
     // take: at T = 200 and eight chunks 1, 3, 7, 18, 42, 43, 43, 43 steps (the consumers still start after a fifth of the chain).
     // At most half of the chunks are small ones.
-    const double geom = h->tail_geom;
+    const double geom = sbr_tail_geom(h->sw.tail_scatter_lds);
     SbrTChunks& tc = h->tail_bounds;
     tc.n = nc;
     tc.lo[0] = 0;
     // LDS-row scatter-add (launch_scatter_lds_poll): a unit walks the chunks one after the other, so what counts is that chunk c is
-    // done when chunk c - 1 is released and that ONE round of rows is left behind the chain: the last chunk has SBR_TAIL_FIRST
-    // steps (default 6: ~8 entries per unit) and the sizes grow by SBR_TAIL_GEOM (default 1.6 here): 6, 10, 15, 25, then equal shares.
-    double pw = h->tail_scatter_lds ? (double)h->tail_first : 1.0;
+    // done when chunk c - 1 is released and that ONE round of rows is left behind the chain: the last chunk has kTailFirst
+    // steps (6: ~8 entries per unit) and the sizes grow by sbr_tail_geom (1.6 here): 6, 10, 15, 25, then equal shares.
+    double pw = h->sw.tail_scatter_lds ? (double)kTailFirst : 1.0;
     for (int c = 0; c < nc; ++c) {
         const int rem = y.T - tc.lo[c], left = nc - c;
         const int share = (rem + left - 1) / left;
@@ -772,10 +724,10 @@ static int tail_plan(sbr_handle* h, int* ch_out) {
 static int tail_cost_scan(sbr_handle* h) {
     const Layout& y = h->lay;
     h->tail_cost_scanned = false;
-    if (!h->tail_scatter_lds) return SBR_OK;
+    if (!h->sw.tail_scatter_lds) return SBR_OK;
     hipError_t e = hipSuccess;
     if (launch_scatter_cost_scan(h->side2, (const int*)h->A(y.a_soff), (int*)h->A(y.a_sP), y.cfg.input_size, h->tail_nc, y.T * y.Bp * y.F,
-                                 y.G * y.layer[0].Hp, h->tail_scatter_units, &e)) {
+                                 y.G * y.layer[0].Hp, kTailScatterUnits, &e)) {
         if (e != hipSuccess) { sbr_set_error("HIP launch failed: %s", hipGetErrorString(e)); return SBR_EHIP; }
         h->tail_cost_scanned = true;
     }
@@ -849,7 +801,7 @@ static int forward_bi(sbr_handle* h) {
             RecArgs ra = rec_args(h, pl);
             if (l == 0 && !y.E) {
                 const int* idx = d ? Xr : h->bX;
-                if (y.F == 1 && h->fuse_gather && sbr_rec_fwd_can_fuse_gather(ra, simple_rec(h))) {
+                if (y.F == 1 && h->sw.fuse_gather && sbr_rec_fwd_can_fuse_gather(ra, simple_rec(h))) {
                     ra.gX = idx; ra.gWin = h->P(ly.p_Win); ra.gbias = h->P(ly.p_b);
                 } else {
                     SBR_LAUNCH(launch_gather_xt(s, h->P(ly.p_Win), h->P(ly.p_b), idx, h->A(ly.a_xt), y.T, y.Bp, y.F, GHp, h->n_rows));
@@ -966,7 +918,7 @@ extern "C" int sbr_forward(sbr_handle* h) {
     // its event (long complete by then).  SBR_SPARSE_OUT_EARLY=0: as before.
     h->cells_early = false;
     bool forked = false;
-    if (training && h->sparse_out_early && sparse_lazy(h) && y.S > 0 && y.cfg.loss != SBR_LOSS_CCE && !SBR_LOSS_IS_MARGIN(y.cfg.loss)) {
+    if (training && h->sw.sparse_out_early && sparse_lazy(h) && y.S > 0 && y.cfg.loss != SBR_LOSS_CCE && !SBR_LOSS_IS_MARGIN(y.cfg.loss)) {
         int kb = -1;
         for (int b = 0; b < y.n_sparse; ++b) if (y.sparse[b].kind == 1) kb = b;
         if (kb >= 0) {
@@ -985,9 +937,8 @@ extern "C" int sbr_forward(sbr_handle* h) {
     // fence below), so WHEN they start decides when the step ends -- and both waited behind work that does not need the chain:
     // the scatter-add behind the 45 us of the time-chunked sort.  The sort needs nothing but the batch: it runs now, beside the
     // forward chain, for one event record in front of it.  The forward chain claims its CUs' LDS while the sort (118 KB of LDS
-    // histogram per workgroup) runs beside it, so the two do not share CUs.  SBR_TAIL_EARLY_SORT=0: behind the output phase.
-    const bool tail_live = h->tail_nc >= 2 && h->tail_overlap == 1;
-    if (tail_live && h->tail_early_sort) {
+    // histogram per workgroup) runs beside it, so the two do not share CUs.
+    if (h->tail_nc >= 2 && h->sw.tail_overlap == 1) {
         if (!forked) SBR_HIP(hipEventRecord(h->ev_fork, s));
         SBR_HIP(hipStreamWaitEvent(h->side2, h->ev_fork, 0));
         SBR_LAUNCH(launch_scatter_sort(h->side2, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, (int*)h->A(y.a_scnt),
@@ -1007,7 +958,7 @@ extern "C" int sbr_forward(sbr_handle* h) {
                                    ly.n_in_p, h->P(ly.p_b), nullptr, 0, simple_gemm(h)));
             mark(h, 1);
         } else if (l == 0) {
-            if (y.F == 1 && h->fuse_gather && sbr_rec_fwd_can_fuse_gather(ra, simple_rec(h))) {
+            if (y.F == 1 && h->sw.fuse_gather && sbr_rec_fwd_can_fuse_gather(ra, simple_rec(h))) {
                 ra.gX = h->bX; ra.gWin = h->P(ly.p_Win); ra.gbias = h->P(ly.p_b);   // gathered inside the forward kernel
             } else {
                 SBR_LAUNCH(launch_gather_xt(s, h->P(ly.p_Win), h->P(ly.p_b), h->bX, h->A(ly.a_xt), y.T, y.Bp,
@@ -1020,7 +971,7 @@ extern "C" int sbr_forward(sbr_handle* h) {
             SBR_LAUNCH(launch_gemm(s, h->A(lo.a_hs) + (size_t)y.Bp * lo.Hp, lo.Hp, 1, h->P(ly.p_Win), GHp, 1, h->A(ly.a_xt), GHp,
                                    y.T * y.Bp, GHp, lo.Hp, h->P(ly.p_b), nullptr, 0, simple_gemm(h)));
         }
-        if (l == 0 && h->tail_sorted) ra.fence_kb = h->tail_fence_kb;
+        if (l == 0 && h->tail_sorted) ra.fence_kb = kTailFenceKb;
         SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, simple_rec(h)));
     }
     mark(h, 2);
@@ -1067,7 +1018,6 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
     if (R < y.Bp) SBR_HIP(hipMemsetAsync(h->A(y.a_dhlast), 0, (size_t)y.Bp * Hp * sizeof(float), s));   // padded rows carry no gradient
     h->side_pending = true;
     h->fill_done = false;
-    h->out3 = false;
     // Work on the side stream that needs only the batch: the sentinel fill of the cluster BPTT kernels' exchange arrays and
     // the sort for the embedding scatter-add (the scatter kernel waits for ev_sort).  With cluster kernels it starts now,
     // beside the output phase (its own fork event); otherwise it rides behind the ev_lg wait the side stream needs anyway
@@ -1124,19 +1074,18 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         int keep = 0;
         bool fold = false;
         if (!sg && y.D == 1 && R == y.Bp && !simple_rec(h)) {
-            const bool fold_on = h->fold_dh;
             RecArgs ra = rec_args(h, y.L - 1);
-            fold = fold_on && sbr_rec_x6p_ok(ra) && !sbr_rec_cluster_ok(ra);
+            fold = sbr_rec_x6p_ok(ra) && !sbr_rec_cluster_ok(ra);
         }
         // Round 5: logits, softmax + CCE and dh in ONE launch whose workgroups exchange the row statistics inside the kernel
         // (sbr_head.hip; exact-f32 products); its dh leaves as split-K slabs -- folded into the chain's prologue as above, or
         // reduced here.  Shapes it does not serve (and SBR_HEAD_FUSE=0) keep the three launches below.
         bool head_done = false;
-        if (h->head_fuse && y.cfg.loss == SBR_LOSS_CCE && !sg && !bf16p && !(y.cfg.flags & SBR_FLAG_F32_MFMA) && y.D == 1 && R == y.Bp) {
+        if (h->sw.head_fuse && y.cfg.loss == SBR_LOSS_CCE && !sg && !bf16p && !(y.cfg.flags & SBR_FLAG_F32_MFMA) && y.D == 1 && R == y.Bp) {
             int nsl = 0; hipError_t he = hipSuccess;
             h->head_epoch += 1; if (!h->head_epoch) h->head_epoch = 1;
             if (launch_head_cce(s, hl, h->P(y.p_WoutT), h->P(y.p_bout), tgt, h->bpop, lg, h->A(y.a_rowcost), ws, y.ws_floats,
-                                (unsigned*)h->A(y.a_hstat), (int*)h->A(y.a_fault), y.Bp, N, Nl, Hp, y.Bg, h->head_epoch, &nsl, &he,
+                                (unsigned*)h->A(y.a_hstat), (int*)h->A(y.a_fault), y.Bp, N, Nl, Hp, y.Bg, h->head_epoch, h->sw.head_wait_ticks, &nsl, &he,
                                 (y.cfg.flags & SBR_FLAG_PROFILE_REC) && (size_t)y.Bp * 16 >= 256 * 8 ? (unsigned long long*)h->A(y.a_prof) + (size_t)2 * (y.Bp / 16) * 16 * 8 : nullptr)) {
                 SBR_LAUNCH(he);
                 head_done = true;
@@ -1164,18 +1113,6 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         h->ev_lg_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
         SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
         if (!fill_needed) { const int rc = side_batch_work(); if (rc != SBR_OK) return rc; }
-        // Overlapped tail, single-call step: the output layer's gradient kernels and its update (five launches, 50 - 60 us on one
-        // stream with its gaps) go to the SECOND side stream, in front of the scatter-add, so that the polling weight-gradient
-        // GEMM on `sd` starts with the chain instead of a third of it late (profiles/round3_l_timeline.txt, round3_z_timeline0.txt):
-        // the scatter-add's units catch up with what was released meanwhile in one pass, the GEMM's groups would carry the backlog
-        // to the end.  (A stream of their own was tried: with main, two side streams and the monitor's that is a fifth hardware
-        // queue, and two of them then share one -- profiles/round3_A_variants.txt.)  No split-K workspace for dW_out there: the
-        // polling GEMM owns ws2 meanwhile.
-        h->out3 = h->in_train_step && h->tail_nc >= 2 && h->tail_overlap == 1 && h->tail_out_stream;
-        // SBR_TAIL_OUT_STREAM=2: ... or the monitor's stream, which is idle while the scatter-add launch carries the monitor
-        h->out3_stream = (h->tail_out_stream == 2 && h->tail_mon_units && h->tail_cost_scanned) ? h->side3 : h->side2;
-        hipStream_t so = h->out3 ? h->out3_stream : sd;
-        if (h->out3) SBR_HIP(hipStreamWaitEvent(so, h->ev_lg_rec, 0));
         // Single-call step without a bias regulariser: the output layer's gradient, its step and the batch cost in ONE launch
         // (launch_out_grad_step, sbr_misc.hip) instead of the five or six below -- the polling weight-gradient GEMM of the overlapped
         // tail, next on this stream, then starts with the chain instead of 68 us into it.  SBR_OUT_FUSE=0: as before.
@@ -1184,10 +1121,10 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         // then starts 9 us earlier and ends where it did, it is throughput-bound beside the chain; C1: 0.3156 -> 0.3035 together with
         // the one-launch head: profiles/round5_variants.txt call b)
         const bool will_step_here = h->in_train_step && !y.n_sparse && !sg && h->tail_nc == 0;
-        if (h->out_fuse && will_step_here && y.cfg.regularization == 0.0f && y.D == 1) {
+        if (h->sw.out_fuse && will_step_here && y.cfg.regularization == 0.0f && y.D == 1) {
             hipError_t oe = hipSuccess;
             float* s1e = y.n_state_arrays > 1 ? h->St(1, 0) : nullptr;
-            if (launch_out_grad_step(so, lg, hl, h->A(y.a_rowcost), h->cost_ptr(), y.cfg.updater, h->P(y.p_WoutT), h->St(0, y.p_WoutT),
+            if (launch_out_grad_step(sd, lg, hl, h->A(y.a_rowcost), h->cost_ptr(), y.cfg.updater, h->P(y.p_WoutT), h->St(0, y.p_WoutT),
                                      s1e ? s1e + y.p_WoutT : nullptr, h->P(y.p_bout), h->St(0, y.p_bout), s1e ? s1e + y.p_bout : nullptr,
                                      R, N, Nl, Hp, y.cfg.learning_rate, y.cfg.rho, y.cfg.beta1, y.cfg.beta2, (long)h->step_count + 1, &oe)) {
                 SBR_LAUNCH(oe);
@@ -1195,14 +1132,13 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
             }
         }
         if (!h->out_stepped) {
-        SBR_LAUNCH(launch_sum_cost(so, h->A(y.a_rowcost), R, h->cost_ptr()));
+        SBR_LAUNCH(launch_sum_cost(sd, h->A(y.a_rowcost), R, h->cost_ptr()));
         // data-parallel: every rank adds its share of the bias regulariser, shares sum to reg
         const float reg = y.cfg.regularization * (float)R / (float)y.Bg;
-        SBR_LAUNCH(launch_colsum_bias(so, lg, R, N, Nl, h->Gd(y.p_bout), h->P(y.p_bout), reg, h->cost_ptr(), h->A(y.a_csum)));
-        SBR_LAUNCH(launch_gemm(so, lg, 1, Nl, hl, Hp, 1, h->Gd(y.p_WoutT), Hp, N, Hp, R, nullptr, h->out3 ? h->A(y.a_ws3) : ws2,
-                               h->out3 ? y.ws3_floats : y.ws2_floats, sg));
+        SBR_LAUNCH(launch_colsum_bias(sd, lg, R, N, Nl, h->Gd(y.p_bout), h->P(y.p_bout), reg, h->cost_ptr(), h->A(y.a_csum)));
+        SBR_LAUNCH(launch_gemm(sd, lg, 1, Nl, hl, Hp, 1, h->Gd(y.p_WoutT), Hp, N, Hp, R, nullptr, ws2, y.ws2_floats, sg));
         }
-        SBR_HIP(hipEventRecord(h->ev_og, so)); h->og_recorded = true;   // output-layer gradients + cost complete
+        SBR_HIP(hipEventRecord(h->ev_og, sd)); h->og_recorded = true;   // output-layer gradients + cost complete
         // Single-call step, dense updates: the output layer is stepped right here, beside the BPTT chain (nothing reads W_out
         // any more: dh was computed in front of the record the side stream waited on); sbr_apply_update leaves the range
         // out.  C4: 46 us off the end of the step.  (The overlapped tail does the same itself; phase-by-phase callers --
@@ -1245,33 +1181,26 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         }
         // Round 5: dh feeds the BPTT chain, everything else here only feeds the optimizer -- cost sum, bias column sums, the dWc GEMM
         // and the scatter of the cells' gradients (5 launches, ~75 us at C3 beside the side stream's sort) leave the main stream: dh
-        // first, one record, the rest on the side stream beside the chain (as the dense heads always did).  SBR_SAMPLED_SIDE=0: rounds 1 - 4.
-        const int sampled_side = 1;
-        hipStream_t sg_s = sampled_side ? sd : s;
-        if (sampled_side) {
-            if (!head1) SBR_LAUNCH(launch_gemm(s, act, C, 1, Wc, Hp, 1, h->A(y.a_dhlast), Hp, R, Hp, C, nullptr, nullptr, 0, sg));
-            h->ev_lg_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
-            SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
-        }
-        SBR_LAUNCH(launch_sum_cost(sg_s, h->A(y.a_rowcost), R, h->cost_ptr()));
-        SBR_LAUNCH(launch_colsum_bias(sg_s, act, R, C, C, dbc, nullptr, 0.0f, nullptr, h->A(y.a_csum)));
-        SBR_LAUNCH(launch_gemm(sg_s, act, 1, C, hl, Hp, 1, dWc, Hp, C, Hp, R, nullptr, nullptr, 0, sg));
-        if (!sampled_side) SBR_LAUNCH(launch_gemm(s, act, C, 1, Wc, Hp, 1, h->A(y.a_dhlast), Hp, R, Hp, C, nullptr, nullptr, 0, sg));
-        SBR_LAUNCH(launch_scatter_cells(sg_s, h->Gd(y.p_WoutT), h->Gd(y.p_bout), dWc, dbc, cells, C, Hp));
-        SBR_HIP(hipEventRecord(h->ev_og, sg_s)); h->og_recorded = true;
-        if (!sampled_side) h->ev_lg_rec = h->ev_og;
+        // first, one record, the rest on the side stream beside the chain (as the dense heads always did).
+        if (!head1) SBR_LAUNCH(launch_gemm(s, act, C, 1, Wc, Hp, 1, h->A(y.a_dhlast), Hp, R, Hp, C, nullptr, nullptr, 0, sg));
+        h->ev_lg_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
+        SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
+        SBR_LAUNCH(launch_sum_cost(sd, h->A(y.a_rowcost), R, h->cost_ptr()));
+        SBR_LAUNCH(launch_colsum_bias(sd, act, R, C, C, dbc, nullptr, 0.0f, nullptr, h->A(y.a_csum)));
+        SBR_LAUNCH(launch_gemm(sd, act, 1, C, hl, Hp, 1, dWc, Hp, C, Hp, R, nullptr, nullptr, 0, sg));
+        SBR_LAUNCH(launch_scatter_cells(sd, h->Gd(y.p_WoutT), h->Gd(y.p_bout), dWc, dbc, cells, C, Hp));
+        SBR_HIP(hipEventRecord(h->ev_og, sd)); h->og_recorded = true;
         if (!fill_needed) {      // the batch-only side work follows (the side stream has waited for this phase's record)
-            if (!sampled_side) SBR_HIP(hipStreamWaitEvent(sd, h->ev_og, 0));
             const int rc = side_batch_work(); if (rc != SBR_OK) return rc;
         }
         // Single-call step: the head's row-sparse block (W_out^T rows + b_out of the sampled cells) has its complete gradient now
         // and nothing reads those rows any more (dh is computed): its step runs on the side stream beside the BPTT chain instead
         // of at the end of the step (C3: 35 us, C5: 41 us); sbr_apply_update leaves the block out.
         h->wout_early = false;
-        if (h->in_train_step && h->sparse_out_early)
+        if (h->in_train_step && h->sw.sparse_out_early)
             for (int b = 0; b < y.n_sparse; ++b)
                 if (y.sparse[b].kind == 1 && !h->sp_exchanged[b]) {
-                    SBR_HIP(hipStreamWaitEvent(sd, h->ev_og, 0));      // (recorded on this very stream unless SBR_SAMPLED_SIDE=0)
+                    SBR_HIP(hipStreamWaitEvent(sd, h->ev_og, 0));      // (recorded on this very stream)
                     SBR_LAUNCH(launch_sparse_step_list(sd, sparse_rows(h, b), sparse_upd(h), (const int*)h->A(y.a_cells), nullptr, C, C,
                                                        (int)h->step_count + 1));
                     h->wout_early = true;
@@ -1317,26 +1246,24 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
         // BPTT in time chunks when the bf16x6 kernel runs: dW_hid of a finished chunk is computed on the side
         // stream (190 idle CUs) while the chain continues
         const size_t slab = (size_t)ly.Hp * GHp;
-        int nc = (sbr_rec_bwd_chunkable(a, simple_rec(h)) && y.T >= 64 && !sg) ? h->bwd_chunks : 1;
-        int nsl = (int)std::min<size_t>(h->wgrad_slices / nc, y.ws2_floats / (slab * nc));   // K-slices (= workgroups of the wgrad kernel)
+        int nc = (sbr_rec_bwd_chunkable(a, simple_rec(h)) && y.T >= 64 && !sg) ? h->sw.bwd_chunks : 1;
+        int nsl = (int)std::min<size_t>(kWgradSlices / nc, y.ws2_floats / (slab * nc));   // K-slices (= workgroups of the wgrad kernel)
         if (nsl < 1) nc = 1;
         const bool side_wgrad = !simple_rec(h) && !sg && nsl >= 1;   // weight gradients on the side stream
         // the bf16x6 GEMM covers the slab with 128x128 tiles: ~512 workgroups in all is enough (the dedicated f32
         // kernel, one workgroup per slab, wants many thin slabs)
-        const bool wg_gemm = (h->wgrad_x6 && !(y.cfg.flags & SBR_FLAG_F32_MFMA) && ly.Hp >= 96) || !(ly.Hp == 32 || ly.Hp == 64 || ly.Hp == 128);
+        const bool wg_gemm = (!(y.cfg.flags & SBR_FLAG_F32_MFMA) && ly.Hp >= 96) || !(ly.Hp == 32 || ly.Hp == 64 || ly.Hp == 128);
         // fp16 x3 products for that GEMM: its operands are hidden states (|h| <= 1 behind tanh / sigmoid gates) and gradients
         // that have passed the clip at +-100 (scaled by 2^9 into fp16's range), see gemm_x6_kernel NP = 2
-        const int wgf = h->wgrad_f16;
-        const bool wg_f16 = wgf && !a.relu && y.cfg.grad_clip > 0.0f && y.cfg.grad_clip <= 100.0f;
+        const bool wg_f16 = h->sw.wgrad_f16 && !a.relu && y.cfg.grad_clip > 0.0f && y.cfg.grad_clip <= 100.0f;
         if (wg_gemm && nsl > 1) {
-            const int wgs = h->wgrad_x6_wgs;
-            nsl = std::max(1, std::min(nsl, wgs / (((ly.Hp + 127) / 128) * ((GHp + 127) / 128)) / nc));
+            nsl = std::max(1, std::min(nsl, kWgradX6Wgs / (((ly.Hp + 127) / 128) * ((GHp + 127) / 128)) / nc));
         }
         // Tail of a single-layer step with one BPTT launch: the main stream keeps the longer branch (dW_hid GEMM + slab
         // reduction + its updates) and the side stream takes the bias partials, the embedding scatter-add and their
         // updates -- the main stream then ends the step without waiting ~13 us for a cross-stream event behind the
         // branch that finishes last (profiles/round1_i_timeline.txt).
-        const bool swap = h->swap_tail && side_wgrad && nc == 1 && y.L == 1 && !y.E && !y.n_sparse &&
+        const bool swap = side_wgrad && nc == 1 && y.L == 1 && !y.E && !y.n_sparse &&
                           y.n_params <= ((size_t)4 << 20) &&      // large models (C4: 34 M parameters) measured 2 % slower this way
                           !(y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER);   // phase-by-phase callers (data parallel) join the side stream
                                                                       // before their collective: same split of the tail
@@ -1360,7 +1287,7 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
             const int tnc = h->tail_nc, CH = h->tail_ch;
             // SBR_TAIL_OVERLAP=2: the same kernels, all on the main stream behind the chain (nothing has to run concurrently):
             // for tools that serialise kernels (rocprofv3 --pmc) and for triage
-            const bool serial = h->tail_overlap == 2;
+            const bool serial = h->sw.tail_overlap == 2;
             hipStream_t s2 = serial ? s : h->side2;
             if (serial) {
                 sd = s;
@@ -1373,38 +1300,35 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
             const int nwaves = (y.Bp / a.rpt) * 8;
             int* done = (int*)h->A(y.a_done);
             h->prog_epoch = (h->prog_epoch + 1) & 0x7FFFF; if (!h->prog_epoch) h->prog_epoch = 1;
-            a.progress = words; a.prog_every = h->tail_pub_every; a.prog_epoch = h->prog_epoch;
+            a.progress = words; a.prog_every = kTailPubEvery; a.prog_epoch = h->prog_epoch;
             const int K = y.T * y.Bp;
             const int cap = (int)std::min<size_t>(256, y.ws2_floats / slab);
             SbrPoll pl{words, nwaves, done, a.prog_epoch, y.Bp, a.fault, 0, 0, h->tail_trace, nullptr, 0};
             if (h->tail_slab_key[0] != K || h->tail_slab_key[1] != cap || !h->tail_slab_dev) {      // (first step of this shape)
-                sbr_tail_slab_table(K, y.Bp, 255, h->tail_slab_growth, h->tail_slab_max, h->tail_slab_host);
+                sbr_tail_slab_table(K, y.Bp, 255, kTailSlabGrowth, kTailSlabMax, h->tail_slab_host);
                 if (!h->tail_slab_dev) SBR_HIP(hipMalloc(&h->tail_slab_dev, 260 * sizeof(int)));
                 SBR_HIP(hipMemcpy(h->tail_slab_dev, h->tail_slab_host.data(), h->tail_slab_host.size() * sizeof(int), hipMemcpyHostToDevice));
                 h->tail_slab_key[0] = K; h->tail_slab_key[1] = cap;
             }
             pl.slab_lo = h->tail_slab_dev;
             pl.n_slabs = (int)h->tail_slab_host.size() - 1;
-            const int n_slabs = std::max(1, std::min(std::min(h->tail_gemm_groups, cap), pl.n_slabs));      // partials = persistent groups
+            const int n_slabs = std::max(1, std::min(std::min(kTailGemmGroups, cap), pl.n_slabs));      // partials = persistent groups
             const bool upd_here = h->in_train_step;
             float* s1a = y.n_state_arrays > 1 ? h->St(1, 0) : nullptr;
             auto upd_on = [&](hipStream_t st, size_t lo, size_t hi, size_t gap_at = (size_t)-1, size_t gap_len = 0) -> hipError_t {
                 return launch_update(st, y.cfg.updater, h->P(lo), h->Gd(lo), h->St(0, lo), s1a ? s1a + lo : nullptr, hi - lo - gap_len,
                                      y.cfg.learning_rate, y.cfg.rho, y.cfg.beta1, y.cfg.beta2, (long)h->step_count + 1, gap_at, gap_len);
             };
-            if (!serial) a.fence_kb = h->tail_fence_kb;              // the chain's CUs are its own: the consumers take the other 192
+            if (!serial) a.fence_kb = kTailFenceKb;              // the chain's CUs are its own: the consumers take the other 192
             SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, false));
             mark(h, 4);
             // side stream: output layer first (its gradients are complete on this stream: dW_out GEMM, bias sums)
             const bool out_early = upd_here && (y.cfg.loss == SBR_LOSS_CCE || SBR_LOSS_IS_MARGIN(y.cfg.loss));
-            if (out_early) {
-                if (!h->out_stepped)       // (else: launch_out_grad_step has stepped the output layer with its gradient, sbr_loss_backward_output)
-                SBR_LAUNCH(upd_on(h->out3 ? h->out3_stream : sd, y.p_split, y.n_params));
-                if (h->out3) SBR_HIP(hipEventRecord(h->ev_tail3, h->out3_stream));
-            }
+            if (out_early && !h->out_stepped)       // (else: launch_out_grad_step has stepped the output layer with its gradient, sbr_loss_backward_output)
+                SBR_LAUNCH(upd_on(sd, y.p_split, y.n_params));
             // the monitor: on a stream of its own behind nothing but the chain's first progress words (its own loop waits for them)
             // ... unless the scatter-add launch carries it (default where that launch is the LDS-row one and has its own stream)
-            const bool mon_in_units = !serial && h->tail_mon_units && h->tail_cost_scanned;
+            const bool mon_in_units = !serial && h->tail_cost_scanned;
             if (!mon_in_units) SBR_LAUNCH(launch_tail_monitor(serial ? s : h->side3, pl, a.t_lo));
             SBR_LAUNCH(launch_tail_gate(sd, words, nwaves, a.prog_epoch, y.T, a.fault));
             {
@@ -1421,21 +1345,20 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
             hipError_t se = hipSuccess;
             if (h->tail_cost_scanned && launch_scatter_lds_poll(s2, h->Gd(ly.p_Win), a.dxt, (const int*)h->A(y.a_sid), (const int*)h->A(y.a_spos),
                                                                (const int*)h->A(y.a_soff), (const int*)h->A(y.a_sP), y.cfg.input_size, tnc,
-                                                               y.T * y.Bp * y.F, GHp, pl, h->tail_bounds, h->tail_scatter_units, &se,
+                                                               y.T * y.Bp * y.F, GHp, pl, h->tail_bounds, kTailScatterUnits, &se,
                                                                mon_in_units, a.t_lo)) {
                 SBR_LAUNCH(se); h->last_scatter_form = 5;
             } else {
             h->last_scatter_form = 4;
             SBR_LAUNCH(launch_scatter_reduce_poll(s2, h->Gd(ly.p_Win), a.dxt, (const int*)h->A(y.a_sid), (const int*)h->A(y.a_spos),
                                                   (const int*)h->A(y.a_soff), y.cfg.input_size, tnc, CH, y.T * y.Bp * y.F, GHp, y.Bp, pl,
-                                                  0, &h->tail_bounds, h->tail_short_chunks, !serial && h->tail_fence_kb > 0));
+                                                  0, &h->tail_bounds, kTailShortChunks, !serial && kTailFenceKb > 0));
             }
             if (upd_here) SBR_LAUNCH(upd_on(s2, ly.p_Win, ly.p_b));
             SBR_HIP(hipEventRecord(h->ev_tail2, s2));
             // single-call step: the slab reduction IS the W_hid update (one launch, one pass less behind the chain); phase-by-phase
             // callers (data parallel) need the reduced gradient
-            const int fuse_slabs = h->tail_fuse_slabs;
-            if (upd_here && fuse_slabs && ly.p_peep - ly.p_Whid == slab && (slab & 3) == 0) {
+            if (upd_here && ly.p_peep - ly.p_Whid == slab && (slab & 3) == 0) {
                 SBR_LAUNCH(launch_update_from_slabs(sd, y.cfg.updater, ws2, n_slabs, h->P(ly.p_Whid), h->St(0, ly.p_Whid),
                                                     s1a ? s1a + ly.p_Whid : nullptr, slab, y.cfg.learning_rate, y.cfg.rho, y.cfg.beta1,
                                                     y.cfg.beta2, (long)h->step_count + 1));
@@ -1449,7 +1372,7 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                                                   h->Gd(ly.p_cinit), h->Gd(ly.p_hinit)));
             mark(h, 5);
             if (upd_here) {      // b, then (behind the gap that is W_hid) peepholes / initial states, and the output layer unless done
-                // (a sampled head's gradient kernels run on the side stream since round 5 -- SBR_SAMPLED_SIDE -- and this launch reads
+                // (a sampled head's gradient kernels run on the side stream since round 5, and this launch reads
                 // and clears their output: order it behind them.  Without the wait the chain's length hid the race.)
                 if (!out_early && h->og_recorded) SBR_HIP(hipStreamWaitEvent(s, h->ev_og, 0));
                 SBR_LAUNCH(upd_on(s, ly.p_b, out_early ? y.p_split : y.n_params, ly.p_Whid - ly.p_b, ly.p_peep - ly.p_Whid));
@@ -1465,9 +1388,6 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
             SBR_HIP(hipStreamWaitEvent(s, h->ev_tail2, 0));
             mark(h, 6);
             SBR_HIP(hipStreamWaitEvent(s, h->ev_tail, 0));
-            if (h->out3 && out_early) SBR_HIP(hipStreamWaitEvent(s, h->ev_tail3, 0));
-            else if (h->out3) SBR_HIP(hipStreamWaitEvent(s, h->ev_og, 0));
-            h->out3 = false;
             h->side_pending = false;
             continue;
         }
@@ -1542,9 +1462,7 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
             } else {
                 if (sm == s) SBR_HIP(hipStreamWaitEvent(s, h->ev_sort, 0));      // (the sort ran on the side stream)
                 hipError_t se = hipSuccess;
-                static const int range_on = [] { const char* e = getenv("SBR_SCAT_RANGE"); return e ? atoi(e) : 1; }();
-                // SBR_SCAT_RANGE: 1 (default) = the range form up to 1024-float rows, the atomic kernel beyond (C5: measured 8.35 against
-                // 8.44 - 8.48 ms with either new form); 2 = the segment-parallel form; 0 = the atomic kernel everywhere
+                const int range_on = h->sw.scat_range;      // (SbrSwitches: 1 the range form up to 1024-float rows, 2 the segment-parallel form, 0 neither)
                 if (range_on == 1 && y.a_srpart && GHp <= 1024 &&
                     launch_scatter_range(sm, h->Gd(ly.p_Win), a.dxt, (const int*)h->A(y.a_sid), (const int*)h->A(y.a_spos), (const int*)h->A(y.a_soff),
                                          y.cfg.input_size, GHp, h->A(y.a_srpart), (int*)h->A(y.a_srid), SBR_SCAT_RANGES, &se)) {
@@ -1703,7 +1621,7 @@ extern "C" int sbr_apply_update(sbr_handle* h) {
     // [0, hi) of the parameter section.
     // Single-call step, dense wide index-input block, the step's plain-key sort at hand (a_soff: this batch's segment offsets): the pass
     // over W_in reads / clears the gradient of the touched rows only (launch_update_rows_aware).  SBR_ROW_AWARE_UPDATE=0: update_kernel.
-    const bool row_aware = h->row_aware && h->in_train_step && y.a_srpart && !y.n_sparse && !y.E && y.D == 1 && h->tail_nc < 2 &&
+    const bool row_aware = h->sw.row_aware && h->in_train_step && y.a_srpart && !y.n_sparse && !y.E && y.D == 1 && h->tail_nc < 2 &&
                            !(y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) && !simple_gemm(h) && !simple_rec(h) && ((y.G * y.layer[0].Hp) & 3) == 0;
     h->last_row_aware = row_aware;
     auto upd_front = [&](size_t hi) -> hipError_t {
@@ -2023,7 +1941,6 @@ extern "C" int sbr_debug_gemm(void* stream, const float* A, int64_t sam, int64_t
                               size_t ws_floats, int32_t exact_f32) {
     CHECK_ARG(A && B && C, "null operand");
     sbr_gemm_set_exact_f32(exact_f32 == 1);
-    sbr_gemm_set_planes(exact_f32 == 2 ? 1 : 3);
     sbr_gemm_set_planes((exact_f32 == 2 || exact_f32 == 5) ? 1 : 3);
     if (exact_f32 == 3 || exact_f32 == 4) sbr_gemm_hint(2, 1.0f, 1.0f);      // the two-plane fp16 split (three MFMAs): what the step's logits GEMM takes
     sbr_gemm_x6_no_wide(exact_f32 == 4 || exact_f32 == 5);
@@ -2070,7 +1987,7 @@ extern "C" int sbr_debug_scatter(sbr_handle* h, int reps, float* us, int64_t* en
     SBR_HIP(hipEventCreate(&e0)); SBR_HIP(hipEventCreate(&e1));
     float* dW = h->Gd(ly.p_Win);
     const float* dxt = h->A(ly.a_dxt);
-    static const int range_on = [] { const char* e = getenv("SBR_SCAT_RANGE"); return e ? atoi(e) : 1; }();
+    const int range_on = h->sw.scat_range;
     auto one = [&]() -> int {
         hipError_t se = hipSuccess;
         if (range_on == 1 && y.a_srpart && GHp <= 1024 &&
@@ -2112,11 +2029,11 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     const Layout& y = h->lay; const std::string w(what);
     if (w == "fused_gather") {
         RecArgs a = rec_args(h, 0);
-        *value = (y.E == 0 && y.F == 1 && h->fuse_gather && sbr_rec_fwd_can_fuse_gather(a, simple_rec(h))) ? 1 : 0;
+        *value = (y.E == 0 && y.F == 1 && h->sw.fuse_gather && sbr_rec_fwd_can_fuse_gather(a, simple_rec(h))) ? 1 : 0;
     } else if (w == "rows_per_workgroup") *value = h->rpt;
     else if (w == "head_fused") {      // would a full batch of a training step take the one-launch head (sbr_head.hip)?  (its column chunks, or 0)
         int cc = 0, cw = 0; size_t lds = 0;
-        *value = (h->head_fuse && y.cfg.loss == SBR_LOSS_CCE && !simple_gemm(h) && !(y.cfg.flags & (SBR_FLAG_BF16_PROJECTION | SBR_FLAG_F32_MFMA)) &&
+        *value = (h->sw.head_fuse && y.cfg.loss == SBR_LOSS_CCE && !simple_gemm(h) && !(y.cfg.flags & (SBR_FLAG_BF16_PROJECTION | SBR_FLAG_F32_MFMA)) &&
                   y.D == 1 && y.B == y.Bp && sbr_head_plan(y.Bp, y.N, y.HLt, &cc, &cw, &lds) && (size_t)cc * y.Bp * y.HLt <= y.ws_floats) ? cc : 0;
     }
     else if (w == "head_sampled") *value = head_sampled_taken(h, y.B) ? 1 : 0;      // a full batch of a training step: head_sampled_kernel, or the four launches
@@ -2139,8 +2056,7 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
         const bool x6 = cl || xp || xq || (!a.f32_mfma && (a.Hp == 32 || a.Hp == 64 || a.Hp == 128));
         int products = 0, rows = 16, wgs = y.Bp / 16;
         if (!simple_rec(h) && x6) {
-            const char* fe = getenv(bwd ? "SBR_X6_F16_BWD" : "SBR_X6_F16");      // the launchers' own conditions (sbr_rec_p.hip)
-            const bool f16 = (xp || cl || xq) && (fe ? atoi(fe) != 0 : true) && (bwd ? (a.clip > 0.0f && a.clip <= 100.0f) : !a.relu);
+            const bool f16 = (xp || cl || xq) && (bwd ? sbr_rec_f16_bwd(a) : sbr_rec_f16_fwd(a));
             products = f16 ? (xp && !cl ? sbr_rec_x6p_f16_terms() : 3) : 6;
             if (cl && sbr_rec_c16_ok(a)) { rows = 16; wgs = (y.Bp / 16) * (a.Hp / 16); }
             else if (cl) { rows = bwd ? sbr_rec_cluster_bwd_rows(a) : SBR_CL_ROWS; wgs = (y.Bp / rows) * (a.Hp == 256 ? 8 : 32); }
@@ -2151,7 +2067,7 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "tail_chunks") { int ch = 0; *value = tail_plan(h, &ch); }      // time chunks of the overlapped step tail (0: not taken)
     // ... whose consumers really run on the side streams (SBR_TAIL_OVERLAP=2 keeps them on the main stream: a data-parallel driver
     // must then not order a collective behind a side stream that produces nothing)
-    else if (w == "tail_streams") { int ch = 0; *value = (tail_plan(h, &ch) >= 2 && h->tail_overlap == 1) ? 1 : 0; }
+    else if (w == "tail_streams") { int ch = 0; *value = (tail_plan(h, &ch) >= 2 && h->sw.tail_overlap == 1) ? 1 : 0; }
     else if (w == "tail_last_steps") { int ch = 0; *value = tail_plan(h, &ch) >= 2 ? h->tail_bounds.lo[1] : 0; }   // time steps of chunk 0 (behind the chain)
     else if (w == "side_stream2") *value = (int64_t)(intptr_t)h->side2;
     else if (w == "tail_chain_cycles" || w == "tail_chain_ticks") {      // last overlapped-tail BPTT launch: shader cycles / 100 MHz ticks

@@ -106,7 +106,6 @@ struct Layout {
     size_t a_Wc, a_bc, a_act, a_dWc, a_dbc; // sampled heads: [C][HLp], [C], [Bp][C], [C][HLp], [C]
     size_t a_ws; size_t ws_floats;        // split-K workspace (main stream)
     size_t a_ws2; size_t ws2_floats;      // split-K workspace of the side stream (output-layer + weight gradients)
-    size_t a_ws3; size_t ws3_floats;      // split-K workspace of the output layer's dW_out GEMM when it runs on a stream of its own (SBR_TAIL_OUT_STREAM)
     size_t a_csum;                        // [16][max(N,C)] column-sum partials
     size_t a_prof;                        // [2][nblk][16][4] uint64 in-kernel cycle counters (fwd, bwd)
     size_t a_fault;                       // int: a cluster exchange wait timed out
@@ -138,111 +137,136 @@ static inline SbrTChunks sbr_uniform_tchunks(int tch, int n) {
     for (int c = 0; c <= SBR_TCHUNKS_MAX; ++c) tc.lo[c] = tch * (c < n ? c : n);
     return tc;
 }
+// ---------------------------------------------------------------------------------------
+// Tuned constants of the step.  Each was an environment switch while it was being measured (rounds 1 - 5) and is fixed since
+// round 6; the A/B numbers are in profiles/round2_b_tail_variants.txt, round3_*_variants.txt, round4_variants.txt,
+// round5_variants.txt and DESIGN.md sections 3, 3a, 3d.  The variants that measured slower are gone with their switches: the
+// output layer's gradient kernels on a stream of their own (round 4, calls n, q), the unsplit gate math on 4-row tiles, the
+// f32 weight-gradient kernel at 128 units, the sort behind the output phase, dh_last reduced in front of rec_bwd_x6p, the
+// W_hid slab reduction apart from its update, the unswapped tail of a single-layer step.
+// ---------------------------------------------------------------------------------------
+constexpr int kWgradSlices = 256;         // K-slices of the weight-gradient kernel (total over the BPTT chunks)
+constexpr int kWgradX6Wgs = 512;          // ... of which the bf16x6 GEMM (128 x 128 tiles) takes as many as give ~512 workgroups in all
+constexpr int kTailChunksMax = 8;         // overlapped tail: time chunks of the sort's keys, at most
+constexpr int kTailPubEvery = 2;          // time steps between two progress words of a chain wave
+constexpr int kTailShortChunks = 3;       // time chunks (from t = 0) whose scatter-add entries are cut into short pieces (polling range form)
+constexpr int kTailFenceKb = 124;         // LDS the chains claim while consumers / the sort run beside them
+constexpr int kTailFirst = 6;             // LDS-row scatter-add: time steps of the last time chunk (~8 entries per unit)
+constexpr int kTailScatterUnits = 192;    // ... and its workgroups (the CUs the chain leaves free at C2)
+constexpr int kTailGemmGroups = 64;       // persistent groups of the polling dW_hid GEMM (one partial each)
+constexpr int kTailSlabMax = 512;         // rows of its largest K slab
+constexpr double kTailSlabGrowth = 0.35;  // k steps of a slab per time step of lead (sbr_tail_slab_table)
+// growth of the small time chunks near t = 0 (tail_plan, sbr_api.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
+// walks them one after the other; 1, 3, 7, 18 for the polling range form
+static inline double sbr_tail_geom(int scatter_lds) { return scatter_lds ? 1.6 : 2.6; }
+
+// Every environment switch the library reads (README.md "Switches"), with its default.  sbr_read_switches (sbr_api.hip) fills one
+// per engine, inside sbr_create, and nothing reads the environment afterwards: an engine keeps the values it was created under.
+#define HEAD_WAIT_TICKS 6000ull      // 60 us of the 100 MHz clock: how long a chunk's statistics are waited for before they are recomputed
+struct SbrSwitches {
+    int rpt = 0;                 // SBR_RPT=1,2,4,8,16: rows per workgroup of the bf16x6 recurrent kernels (else: chosen by the batch size)
+    int bwd_chunks = 1;          // SBR_BWD_CHUNKS: BPTT launches per layer (1..SBR_BWD_CHUNKS)
+    int cluster = 1;             // SBR_CLUSTER: cluster recurrent kernels for wide layers
+    int cl_linear = 0;           // SBR_CL_LINEAR: (experiment) cluster members on consecutive workgroup ids = different XCDs
+    int cl16 = 1;                // SBR_CL16: the 16-row cluster kernels (sbr_rec_c16.hip); 0: the 8-row ones
+    int c16_two_level = 1;       // SBR_C16_TWO_LEVEL: Hp = 512, the backward exchange in two levels (rec_bwd_c16t)
+    int x6_pipe = 1;             // SBR_X6_PIPE: per-k-block publish counters instead of a workgroup barrier per step (0: the barrier kernels, x6s)
+    int x6_f16 = 1;              // SBR_X6_F16: forward chains on the two-plane fp16 split (sbr_rec_f16_fwd)
+    int x6_f16_bwd = 1;          // SBR_X6_F16_BWD: ... and the BPTT chains (sbr_rec_f16_bwd)
+    int fuse_gather = 1;         // SBR_FUSE_GATHER: the embedding gather inside the forward kernel
+    int gemm_f16 = 1;            // SBR_GEMM_F16: the dense GEMMs around the recurrent layers on the two-plane fp16 split
+    int wgrad_f16 = 1;           // SBR_WGRAD_F16: ... and the dW_hid GEMM
+    int tail_overlap = 1;        // SBR_TAIL_OVERLAP: weight-gradient GEMM and scatter-add of finished time chunks run beside the BPTT chain
+                                 // (2: the same kernels on the main stream behind the chain)
+    int tail_scatter_lds = 1;    // SBR_TAIL_SCATTER_LDS: its scatter-add in LDS rows; 0: the polling range form (also the way out when the LDS rows run out)
+    int tail_trace = 0;          // SBR_TAIL_TRACE: the consumers' wait stamps (SbrPoll.trace, tools/tail_trace.py)
+    int scat_range = 1;          // SBR_SCAT_RANGE: scatter-add of wide rows -- 1 the range form up to 1024-float rows, the atomic kernel beyond (C5:
+                                 // measured 8.35 against 8.44 - 8.48 ms with either new form); 2 the segment-parallel form; 0 the atomic kernel everywhere
+    int sparse_out_early = 1;    // SBR_SPARSE_OUT_EARLY: the sampled head's row-sparse block is caught up beside the forward chain and stepped
+                                 // beside the BPTT chain (side stream) instead of in front of / behind them
+    int head_fuse = 1;           // SBR_HEAD_FUSE: the full-softmax / sampled head in one launch (sbr_head.hip)
+    unsigned long long head_wait_ticks = HEAD_WAIT_TICKS;   // SBR_HEAD_WAIT_TICKS (tests: 0 = every foreign chunk is recomputed)
+    int out_fuse = 1;            // SBR_OUT_FUSE: the dense head's gradient and step in one launch (launch_out_grad_step)
+    int row_aware = 1;           // SBR_ROW_AWARE_UPDATE: the dense pass over a wide index-input block skips the gradient traffic of the rows the batch did not touch
+};
+
 struct sbr_handle {
     Layout lay;
-    float* arena; bool own_arena;
-    hipStream_t stream;
-    hipStream_t side;            // batch-only preprocessing (scatter sort) overlapped with the chain
-    hipEvent_t ev_fork, ev_join;
-    hipEvent_t ev_sort, ev_lg, ev_fill, ev_og, ev_chunk[SBR_BWD_CHUNKS];
-    bool in_train_step;  // phases called from sbr_train_step: the side stream joins only before the update
-    bool side_pending;   // side-stream work issued and not yet joined by the main stream
-    bool deferred_join;  // phases called one by one do not join the side stream (sbr_set_deferred_join)
-    bool og_recorded;    // ev_og marks the output-layer gradients of this step complete
-    bool fill_done;      // the cluster BPTT sentinel fill of this step was issued on the side stream (ev_fill)
-    bool out_early;      // this step's output-layer parameters were stepped on the side stream beside the BPTT chain
-    int sparse_out_early;    // SBR_SPARSE_OUT_EARLY (default 1): the sampled head's row-sparse block is caught up beside the forward
-                             // chain and stepped beside the BPTT chain (side stream) instead of in front of / behind them
-    bool cells_early;    // this step: cells built + their rows caught up on the side stream by sbr_forward (ev_cells)
-    bool wout_early;     // this step: the sampled head's rows were stepped beside the BPTT chain
-    hipEvent_t ev_cells;
-    int head_fuse;       // SBR_HEAD_FUSE (default 1): the full-softmax head in one launch (sbr_head.hip)
-    unsigned head_epoch;
-    int row_aware;       // SBR_ROW_AWARE_UPDATE (default 1): the dense pass over a wide index-input block skips the gradient traffic of the rows the batch did not touch
-    int out_fuse;        // SBR_OUT_FUSE (default 1): the dense head's gradient and step in one launch (launch_out_grad_step)
-    bool out_stepped;    // this step: done, the output layer's range needs no update launch
-    int dh_slabs_n;      // > 0: dh_last of this step sits in the main workspace as that many unreduced split-K slabs
+    SbrSwitches sw;
+    float* arena = nullptr; bool own_arena = false;
+    hipStream_t stream = nullptr;
+    // Priority side streams and disable-timing events: sbr_create / sbr_destroy walk handle_streams() / handle_events() (sbr_api.hip)
+    hipStream_t side = nullptr;      // batch-only preprocessing (scatter sort) overlapped with the chain
+    hipStream_t side2 = nullptr;     // second consumer stream of the overlapped tail (scatter-add)
+    hipStream_t side3 = nullptr;     // the overlapped tail's monitor where it is a launch of its own (tail_monitor_kernel), and s_bb
+    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+    hipEvent_t ev_sort = nullptr, ev_lg = nullptr, ev_fill = nullptr, ev_og = nullptr, ev_chunk[SBR_BWD_CHUNKS] = {};
+    hipEvent_t ev_cells = nullptr, ev_tail = nullptr, ev_tail2 = nullptr, ev_bb = nullptr, ev_bbw = nullptr;
+    bool in_train_step = false;  // phases called from sbr_train_step: the side stream joins only before the update
+    bool side_pending = false;   // side-stream work issued and not yet joined by the main stream
+    bool deferred_join = false;  // phases called one by one do not join the side stream (sbr_set_deferred_join)
+    bool og_recorded = false;    // ev_og marks the output-layer gradients of this step complete
+    bool fill_done = false;      // the cluster BPTT sentinel fill of this step was issued on the side stream (ev_fill)
+    bool out_early = false;      // this step's output-layer parameters were stepped on the side stream beside the BPTT chain
+    bool cells_early = false;    // this step: cells built + their rows caught up on the side stream by sbr_forward (ev_cells)
+    bool wout_early = false;     // this step: the sampled head's rows were stepped beside the BPTT chain
+    unsigned head_epoch = 0;
+    bool out_stepped = false;    // this step: done, the output layer's range needs no update launch
+    int dh_slabs_n = 0;          // > 0: dh_last of this step sits in the main workspace as that many unreduced split-K slabs
     std::vector<ParamDesc> descs;
-    int rpt;             // rows per workgroup for the bf16x6 recurrent kernels
-    int bwd_chunks;      // BPTT launches per layer (1..SBR_BWD_CHUNKS)
-    int wgrad_slices;    // K-slices of the weight-gradient kernel (total over the chunks)
-    int cluster, cl_linear; // cluster recurrent kernels for wide layers (SBR_CLUSTER, SBR_CL_LINEAR)
-    int cl_epoch;
-    int x6_split, fuse_gather;
-    int sp_exchanged[2]; // data-parallel step: rows of block b were packed / gathered (candidates = a_cand[0 .. sp_ncand[b]))
-    int sp_ncand[2];
-    int sp_epoch;        // pack epoch
-    float* lag_host;     // pinned: [2] cost, [2] fault flag, [2] sequence number (sbr_train_step_lagged: lag_report_kernel)
-    unsigned lag_seq[2], lag_counter;
-    int lag_slot, lag_pending;
-    int x6_pipe;         // per-k-block publish counters instead of a workgroup barrier per step (SBR_X6_PIPE, default 1; Hp = 128)
-    int wgrad_x6;        // weight gradients through the bf16x6 GEMM instead of the dedicated f32 kernel (SBR_WGRAD_X6, default 1; the f32 kernel serves Hp < 96 and SBR_FLAG_F32_MFMA)
+    int rpt = 16;                // rows per workgroup for the bf16x6 recurrent kernels (SbrSwitches.rpt, or chosen by the batch size)
+    int cl_epoch = 0;
+    int sp_exchanged[2] = {0, 0}; // data-parallel step: rows of block b were packed / gathered (candidates = a_cand[0 .. sp_ncand[b]))
+    int sp_ncand[2] = {0, 0};
+    int sp_epoch = 0;            // pack epoch
+    float* lag_host = nullptr;   // pinned: [2] cost, [2] fault flag, [2] sequence number (sbr_train_step_lagged: lag_report_kernel)
+    unsigned lag_seq[2] = {0, 0}, lag_counter = 0;
+    int lag_slot = 0, lag_pending = -1;
     // current batch: the arena's own buffers, or (device-resident inputs covering all Bp rows) the caller's
-    const int *bX, *blen, *btgt, *bsmp; const float* bpop;
+    const int *bX = nullptr, *blen = nullptr, *btgt = nullptr, *bsmp = nullptr; const float* bpop = nullptr;
     // sbr_build_batch beside the step in flight (sbr_batch.hip): its own stream, the set the current batch sits in, and what
     // tells it that the set it is about to overwrite is no longer read
 #ifndef SBR_BB_STREAM
 #define SBR_BB_STREAM 0      // (probe builds: 1 = a stream of its own, 2 = ... at low priority)
 #endif
-    hipStream_t s_bb; hipEvent_t ev_bb, ev_bbw;
-    int bb_set;                 // arena set of the current batch (0: also what sbr_set_batch fills)
-    uint64_t batch_seq;         // sbr_forward calls so far
-    uint64_t set_use[2];        // batch_seq of the last forward that read set i
-    uint64_t lg_seq;            // batch_seq when ev_lg_rec was last recorded (a main-stream record in the middle of a training step)
-    bool bb_unread;             // the current batch was built and no forward has read it yet
-    bool train_fwd_open;        // a training forward whose step has not reached sbr_apply_update
-    int bb_slow;                // builds left that wait for all of the engine's streams (a step was abandoned: its side streams were not joined)
-    int n_rows;          // rows of the current batch (<= local_batch)
-    int64_t step_count;  // adam t
-    bool have_batch, fwd_done;
-    bool grads_clean;    // the gradient section is all zero (fresh arena, or the update kernel cleared it)
-    bool timing;
-    unsigned timing_marks;   // which of the SBR_N_PHASES event marks a step records (sbr_enable_timing)
-    int tail_overlap;    // SBR_TAIL_OVERLAP (default 1): weight-gradient GEMM and scatter-add of finished time chunks run beside the BPTT chain
-    int tail_chunks_max; // SBR_TAIL_CHUNKS (default 8)
-    int tail_pub_every;  // SBR_TAIL_PUBLISH_EVERY: time steps between two progress words of a chain wave (default 2)
-    int tail_nc, tail_ch;   // this step: time chunks of the sort's keys / steps per chunk (0: plain keys)
-    SbrTChunks tail_bounds; // ... and their bounds (tail_plan)
-    unsigned long long* tail_trace = nullptr;    // SBR_TAIL_TRACE=1: SbrPoll.trace
-    int tail_fence_kb;      // SBR_TAIL_FENCE_KB: LDS the chains claim while consumers / the sort run beside them (0: none)
-    int tail_early_sort;    // SBR_TAIL_EARLY_SORT: the time-chunked sort beside the forward chain
-    int tail_out_stream;    // SBR_TAIL_OUT_STREAM: output-layer gradients + update on a third side stream (single-call steps)
-    bool tail_sorted, out3; // this step: the sort already ran (sbr_forward) / the output layer's work is on side3
-    hipStream_t out3_stream;   // this step: the stream of the output layer's gradient kernels when they left the side stream (out3)
-    hipStream_t side3; hipEvent_t ev_tail3;      // side3: the overlapped tail's monitor (tail_monitor_kernel)
-    int tail_short_chunks;  // time chunks (from t = 0) whose scatter-add entries are cut into short pieces (SBR_TAIL_SHORT_CHUNKS)
-    double tail_geom;       // SBR_TAIL_GEOM: growth of the small time chunks near t = 0 (<= 1: equal chunks)
+    hipStream_t s_bb = nullptr;
+    int bb_set = 0;             // arena set of the current batch (0: also what sbr_set_batch fills)
+    uint64_t batch_seq = 0;     // sbr_forward calls so far
+    uint64_t set_use[2] = {0, 0};   // batch_seq of the last forward that read set i
+    uint64_t lg_seq = 0;        // batch_seq when ev_lg_rec was last recorded (a main-stream record in the middle of a training step)
+    bool bb_unread = false;     // the current batch was built and no forward has read it yet
+    bool train_fwd_open = false;    // a training forward whose step has not reached sbr_apply_update
+    int bb_slow = 0;            // builds left that wait for all of the engine's streams (a step was abandoned: its side streams were not joined)
+    int n_rows = 0;          // rows of the current batch (<= local_batch)
+    int64_t step_count = 0;  // adam t
+    bool have_batch = false, fwd_done = false;
+    bool grads_clean = false;    // the gradient section is all zero (fresh arena, or the update kernel cleared it)
+    bool timing = false;
+    unsigned timing_marks = 0;   // which of the SBR_N_PHASES event marks a step records (sbr_enable_timing)
+    int tail_nc = 0, tail_ch = 0;   // this step: time chunks of the sort's keys / steps per chunk (0: plain keys)
+    SbrTChunks tail_bounds = {};    // ... and their bounds (tail_plan)
+    unsigned long long* tail_trace = nullptr;    // SbrSwitches.tail_trace: SbrPoll.trace
+    bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
     bool tail_cost_scanned = false;                                       // this step's sort was followed by launch_scatter_cost_scan
     int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
-    int tail_mon_units;                                                   // SBR_TAIL_MONITOR_IN_UNITS: the monitor is a workgroup of the scatter-add launch
-    int tail_first;                                                       // SBR_TAIL_FIRST: time steps of the last time chunk (LDS-row scatter-add)
-    int tail_scatter_lds, tail_scatter_units;                             // SBR_TAIL_SCATTER_LDS / SBR_TAIL_SCATTER_UNITS
-    int tail_gemm_groups;                                                 // SBR_TAIL_GEMM_GROUPS: persistent groups of the polling dW_hid GEMM
-    int tail_fuse_slabs, tail_slab_max;                                   // SBR_TAIL_FUSE_SLABS / SBR_TAIL_SLAB_MAX (rows)
-    double tail_slab_growth;                                              // SBR_TAIL_SLAB_GROWTH (k steps of a slab per time step of lead)
     std::vector<int> tail_slab_host; int* tail_slab_dev = nullptr; int tail_slab_key[2] = {0, 0};   // the table of the last plan
-    bool fold_dh;           // SBR_FOLD_DH
-    int wgrad_f16, wgrad_x6_wgs;                                          // SBR_WGRAD_F16, SBR_WGRAD_X6_WGS
-    int prog_epoch;
-    bool tail_updated;      // this step: the overlapped tail has applied the optimizer itself (single-call step)
-    hipEvent_t ev_tail, ev_tail2;
-    bool tail_join_pending; // overlapped tail of a phase-by-phase step: the main stream has not joined the consumer streams yet
-    bool step_open;         // sbr_zero_grads has opened a training step (cleared by sbr_forward)
-    hipEvent_t ev_lg_rec;   // this step: the main-stream record that released the side stream (sbr_loss_backward_output)
-    hipStream_t side2;      // second consumer stream of the overlapped tail (scatter-add)
-    bool swap_tail;      // SBR_SWAP_TAIL: after the BPTT chain the main stream keeps dW_hid, the side stream takes the scatter
-    bool tail_swapped;   // ... done for this step (sbr_apply_update splits its ranges accordingly)
-    unsigned marks_shared;   // marks of this step already recorded as a cross-stream event (record_shared)
+    int prog_epoch = 0;
+    bool tail_updated = false;   // this step: the overlapped tail has applied the optimizer itself (single-call step)
+    bool tail_join_pending = false; // overlapped tail of a phase-by-phase step: the main stream has not joined the consumer streams yet
+    bool step_open = false;      // sbr_zero_grads has opened a training step (cleared by sbr_forward)
+    hipEvent_t ev_lg_rec = nullptr; // this step: the main-stream record that released the side stream (sbr_loss_backward_output); one of the events above
+    bool tail_swapped = false;   // this step: after the BPTT chain the main stream kept dW_hid, the side stream took the scatter (sbr_apply_update splits its ranges accordingly)
+    unsigned marks_shared = 0;   // marks of this step already recorded as a cross-stream event (record_shared)
     // ring of per-step event sets, read back after the timed region (no per-step sync)
     static const int kRing = 64;
-    hipEvent_t ev[kRing][SBR_N_PHASES];
-    int ring_used;       // train steps recorded since timing was enabled
-    int ring_cur;        // set used by the step in flight
+    hipEvent_t ev[kRing][SBR_N_PHASES] = {};
+    int ring_used = 0;       // train steps recorded since timing was enabled
+    int ring_cur = 0;        // set used by the step in flight
     // chain-only timing (sbr_chain_times): an event pair around every launch of a recurrent chain kernel, any layer, either direction
     static const int kChain = 256;
-    hipEvent_t ev_ch[kChain][2];
-    unsigned char ch_dir[kChain];
+    hipEvent_t ev_ch[kChain][2] = {};
+    unsigned char ch_dir[kChain] = {};
     int ch_n = 0;
     bool chain_timing = false;
     float* P(size_t off) const { return arena + lay.s_params + off; }
@@ -278,7 +302,7 @@ void sbr_set_error(const char* fmt, ...);
 #define SBR_DONE_COPIES 32
 #define SBR_DONE_STRIDE 1088
 struct SbrPoll { const int* words; int n; int* done; int epoch; int rows_per_step; int* fault; int n_small, k_small;
-                 unsigned long long* trace; const int* slab_lo; int n_slabs; };    // trace (SBR_TAIL_TRACE=1, tools/tail_trace.py): 100 MHz stamps of the consumers' waits and ends
+                 unsigned long long* trace; const int* slab_lo; int n_slabs; };    // trace (sbr_handle.tail_trace, tools/tail_trace.py): 100 MHz stamps of the consumers' waits and ends
 
 // ---------------------------------------------------------------------------------------
 // Kernel launchers (each returns hipGetLastError())
@@ -373,8 +397,9 @@ struct RecArgs {
     float* part;            // [chunks][nblk][G*Hp + 5*Hp]
     int rpt;                // live batch rows per workgroup of the bf16x6 kernels (16, 8, 4, 2, 1); part[] has Bp/rpt blocks
     int xt_blocked;         // xt is tile-blocked (layer 0: written by the gather) or row-major (GEMM output)
-    int x6_split;           // 4-row tiles use the split-gate-math kernels (SBR_X6_SPLIT, default 1)
-    int x6_pipe;            // Hp = 128: waves synchronise per k-block through LDS counters, no per-step barrier (SBR_X6_PIPE)
+    int x6_pipe;            // Hp = 128: waves synchronise per k-block through LDS counters, no per-step barrier (SbrSwitches.x6_pipe)
+    int x6_f16, x6_f16_bwd; // fp16 planes allowed for the forward / the BPTT chain (SbrSwitches; what a launch takes: sbr_rec_f16_fwd / _bwd)
+    int cl16, c16_two_level; // the 16-row cluster kernels allowed / their two-level backward exchange at Hp = 512 (SbrSwitches)
     // layer 0, one index per step: the embedding gather is fused into the forward kernel (xt is never written)
     const int* gX;          // [Bp][T] item ids, or NULL: read xt
     const float* gWin;      // [input_size][G*Hp]
@@ -383,8 +408,8 @@ struct RecArgs {
     int f32_mfma;           // SBR_FLAG_F32_MFMA: exact-f32 v_mfma_f32_16x16x4_f32 kernels instead of bf16x6
     unsigned long long* prof; // SBR_FLAG_PROFILE_REC: [nblk][waves][4] cycle counters, else NULL
     // cluster kernels (sbr_rec_cl.hip): several workgroups per row tile for layers too wide for one CU
-    int cluster;            // allowed (SBR_CLUSTER != 0)
-    int cl_linear;          // (experiment, SBR_CL_LINEAR=1) cluster members on consecutive workgroup ids = different XCDs
+    int cluster;            // allowed (SbrSwitches.cluster)
+    int cl_linear;          // (experiment, SbrSwitches.cl_linear) cluster members on consecutive workgroup ids = different XCDs
     int* fault;             // set to 1 when a cluster exchange wait gave up (bounded spin)
     int sentinel_done;      // the backward exchange arrays were already filled with the sentinel (side stream)
     int* clx;               // [tiles][C] start-of-launch handshake: (epoch << 4) | XCC id of every member
@@ -399,6 +424,12 @@ struct RecArgs {
     int fence_kb;           // rec_*_x6p: the workgroup claims this much of its CU's LDS (KiB; 0: what it needs) so that kernels which
                             // run BESIDE the chain and use LDS themselves are placed on other CUs (overlapped step tail)
 };
+// Operand planes of the recurrent chains (128-unit, small-layer and cluster kernels alike): the two-plane fp16 split unless it is
+// switched off or its operand is unbounded -- forward: a rectified state (the split needs |h| < 65504); backward: the operand that
+// carries gradients is bounded by the reference's own gradient clip at +-100.  The forward and the backward launch of a step must
+// agree on the kernel family (they share the saved gates' layout): both values come from the engine's SbrSwitches.
+static inline bool sbr_rec_f16_fwd(const RecArgs& a) { return a.x6_f16 && !a.relu; }
+static inline bool sbr_rec_f16_bwd(const RecArgs& a) { return a.x6_f16_bwd && a.clip > 0.0f && a.clip <= 100.0f; }
 #define SBR_CL_ROWS 8       // batch rows per cluster tile
 #define SBR_C16_RING 2      // rec_bwd_c16: slots of the ring of partial-sum blocks (blocks carry the lap's parity: sbr_rec_c16.hip)
 #define SBR_X6P_FUSE_MAX_T 4096      // fused gather of rec_fwd_x6p: 4 rows x T row offsets in LDS
@@ -486,7 +517,7 @@ bool launch_head_sampled(hipStream_t s, const float* h, const float* Wc, const f
                          unsigned long long* prof = nullptr);
 bool launch_head_cce(hipStream_t s, const float* h, const float* WoutT, const float* bout, const int* tgt, const float* pop, float* dlogits,
                      float* rowcost, float* slabs, size_t slab_floats, unsigned* stats, int* fault, int Bp, int N, int Nl, int Hp, int Bglobal,
-                     unsigned epoch, int* n_slabs, hipError_t* err, unsigned long long* prof = nullptr);
+                     unsigned epoch, unsigned long long wait_ticks, int* n_slabs, hipError_t* err, unsigned long long* prof = nullptr);
 // full softmax + categorical cross-entropy (rnn_one_hot.py:65-77): logits (rows,N), row stride ld, in; dlogits out in place
 hipError_t launch_softmax_cce(hipStream_t s, float* logits, const float* bout, const int* target, const float* pop,
                               float* rowcost, int rows, int N, long ld, int Bglobal);

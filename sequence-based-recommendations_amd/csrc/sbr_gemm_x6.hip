@@ -337,7 +337,7 @@ __global__ void __launch_bounds__(256, PL ? 1 : 2) gemm_x6_kernel(GemmX6Args g) 
 // Two operand elements -> their fp16 planes, packed (low half = the first): h1 = fp16(x s), h2 = fp16((x s - h1) 2048), three VALU
 // instructions per element (the mixed-precision FMA reads an fp16 half as a source and writes one as a result: no conversion back, no
 // pack) where the C form below takes five or six.  Same values bit for bit: x s is exact (s a power of two), so is x s - h1.
-__device__ __forceinline__ void x6_split_pair(float x0, float x1, float s, float k2048, unsigned& h1, unsigned& h2) {
+__device__ __forceinline__ void x6_pair_split(float x0, float x1, float s, float k2048, unsigned& h1, unsigned& h2) {
     unsigned d1, d2; float r0, r1;
     asm("v_fma_mixlo_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "=v"(d1) : "v"(x0), "v"(s));
     asm("v_fma_mixhi_f16 %0, %1, %2, 0 op_sel_hi:[0,0,0]" : "+v"(d1) : "v"(x1), "v"(s));
@@ -419,7 +419,7 @@ __global__ void __launch_bounds__(512, 1) gemm_x6w_kernel(GemmX6Args g) {
 #pragma unroll
                     for (int c = 0; c < 4; ++c) {
                         unsigned p1, p2;
-                        x6_split_pair(ra[2 * hh + (c >> 1)][2 * (c & 1)], ra[2 * hh + (c >> 1)][2 * (c & 1) + 1], g.sa, 2048.0f, p1, p2);
+                        x6_pair_split(ra[2 * hh + (c >> 1)][2 * (c & 1)], ra[2 * hh + (c >> 1)][2 * (c & 1) + 1], g.sa, 2048.0f, p1, p2);
                         w1[c] = p1; w2[c] = p2;
                     }
                     *(u32x4*)(A0 + hh * 16) = w1;
@@ -437,7 +437,7 @@ __global__ void __launch_bounds__(512, 1) gemm_x6w_kernel(GemmX6Args g) {
             for (int e = 0; e < 4; ++e) {
                 if constexpr (NP == 2) {
                     unsigned p1, p2;
-                    x6_split_pair(rb[0][e], rb[1][e], g.sb, 2048.0f, p1, p2);
+                    x6_pair_split(rb[0][e], rb[1][e], g.sb, 2048.0f, p1, p2);
                     *(unsigned*)(B0 + e * ROW) = p1;
                     *(unsigned*)(B0 + e * ROW + PB) = p2;
                 } else {
@@ -453,7 +453,7 @@ __global__ void __launch_bounds__(512, 1) gemm_x6w_kernel(GemmX6Args g) {
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     unsigned p1, p2;
-                    x6_split_pair(rb[c >> 1][2 * (c & 1)], rb[c >> 1][2 * (c & 1) + 1], g.sb, 2048.0f, p1, p2);
+                    x6_pair_split(rb[c >> 1][2 * (c & 1)], rb[c >> 1][2 * (c & 1) + 1], g.sb, 2048.0f, p1, p2);
                     w1[c] = p1; w2[c] = p2;
                 }
                 *(u32x4*)B0 = w1;

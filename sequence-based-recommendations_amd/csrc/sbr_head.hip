@@ -47,7 +47,7 @@ struct HeadArgs {
     const float* pop;      // [Bp]
     float* dlog;           // [Bp][Nl]
     float* rowcost;        // [Bp]
-    unsigned long long wait_ticks;   // HEAD_WAIT_TICKS, or SBR_HEAD_WAIT_TICKS (tests: 0 = every foreign chunk is recomputed)
+    unsigned long long wait_ticks;   // SbrSwitches.head_wait_ticks: HEAD_WAIT_TICKS (sbr_common.h), or what SBR_HEAD_WAIT_TICKS said (tests: 0 = every foreign chunk is recomputed)
     float* slabs;          // [CC][Bp][HP]
     unsigned* stats;       // [RB][CC][16][4]
     int* fault;
@@ -76,7 +76,6 @@ __device__ __forceinline__ void head_logits(const float* __restrict__ wr, const 
     }
 }
 
-#define HEAD_WAIT_TICKS 6000ull      // 60 us of the 100 MHz clock: how long a chunk's statistics are waited for before they are recomputed
 
 // rows [n_lo, n_lo + CW) of W_out^T -> the LDS image (rows beyond the catalogue: zeros).  Rounds of 16 pieces per thread in flight
 // (C2's chunk of 240 rows x 128 floats is 30 pieces per thread; in rounds of 6 the fill was five dependent round trips to L2)
@@ -337,17 +336,14 @@ bool sbr_head_plan(int Bp, int N, int Hp, int* CC, int* CW, size_t* lds_bytes) {
 // slabs: CC * Bp * Hp floats; stats: (Bp / 16) * CC * 64 unsigned; false: shape not served, nothing launched
 bool launch_head_cce(hipStream_t s, const float* h, const float* WoutT, const float* bout, const int* tgt, const float* pop, float* dlogits,
                      float* rowcost, float* slabs, size_t slab_floats, unsigned* stats, int* fault, int Bp, int N, int Nl, int Hp, int Bglobal,
-                     unsigned epoch, int* n_slabs, hipError_t* err, unsigned long long* prof) {
+                     unsigned epoch, unsigned long long wait_ticks, int* n_slabs, hipError_t* err, unsigned long long* prof) {
     int CC = 0, CW = 0; size_t lds = 0;
     if (!sbr_head_plan(Bp, N, Hp, &CC, &CW, &lds) || (size_t)CC * Bp * Hp > slab_floats || epoch == 0) return false;
     HeadArgs a;
     a.h = h; a.W = WoutT; a.b = bout; a.tgt = tgt; a.pop = pop; a.dlog = dlogits; a.rowcost = rowcost; a.slabs = slabs; a.stats = stats;
     a.fault = fault; a.N = N; a.Nl = Nl; a.CW = CW; a.CC = CC; a.RB = Bp / 16; a.Bp = Bp; a.inv_Bg = 1.0f / (float)Bglobal; a.epoch = epoch;
     a.prof = prof;
-    {   // read per launch: the tests flip it (0: nobody is waited for -- the recompute path serves every foreign chunk)
-        const char* e = getenv("SBR_HEAD_WAIT_TICKS");
-        a.wait_ticks = e ? strtoull(e, nullptr, 10) : HEAD_WAIT_TICKS;
-    }
+    a.wait_ticks = wait_ticks;      // (0: nobody is waited for -- the recompute path serves every foreign chunk)
     const int grid = a.RB * CC;
     if (Hp == 128) { SBR_DYN_LDS(head_cce_kernel<128>, lds); head_cce_kernel<128><<<grid, 256, lds, s>>>(a); }
     else if (Hp == 64) { SBR_DYN_LDS(head_cce_kernel<64>, lds); head_cce_kernel<64><<<grid, 256, lds, s>>>(a); }

@@ -1313,7 +1313,7 @@ static hipError_t launch_fwd_cell(hipStream_t s, const RecArgs& a, bool simple) 
         const size_t l6 = (size_t)Gates<CELL>::G * (Hp / 32) * (Hp / 16) * 1024 + 2 * 3 * 16 * (size_t)(Hp * 2 + 32);
         if (l6 <= 160 * 1024) {
             const int nb6 = a.Bp / a.rpt;
-            if (a.rpt == 4 && a.x6_split) {   // 4-row tiles: one (row, unit) pair per lane
+            if (a.rpt == 4) {   // 4-row tiles: one (row, unit) pair per lane
                 const size_t l4 = (size_t)Gates<CELL>::G * (Hp / 32) * (Hp / 16) * 1024 + 2 * 3 * 4 * (size_t)(Hp * 2 + 32);
                 if (Hp == 32) LAUNCH_DYN((rec_fwd_x6s<CELL, 32>), nb6, Hp * 4, l4, a);
                 else if (Hp == 64) LAUNCH_DYN((rec_fwd_x6s<CELL, 64>), nb6, Hp * 4, l4, a);
@@ -1350,7 +1350,7 @@ bool sbr_rec_fwd_can_fuse_gather(const RecArgs& a, bool simple) {
     if (!(Hp == 32 || Hp == 64 || Hp == 128)) return false;
     if (sbr_rec_x6p_ok(a) && !sbr_rec_x6p_fuse_ok(a)) return false;    // rec_fwd_x6p: row offsets in LDS (T), 32-bit offsets into W_in (n_in)
     const size_t l4 = (size_t)a.G * (Hp / 32) * (Hp / 16) * 1024 + 2 * 3 * 4 * (size_t)(Hp * 2 + 32);
-    return a.rpt == 4 && a.x6_split && l4 <= 160 * 1024;
+    return a.rpt == 4 && l4 <= 160 * 1024;
 }
 
 hipError_t launch_rec_forward(hipStream_t s, const RecArgs& a, bool simple) {
@@ -1392,7 +1392,7 @@ static hipError_t launch_bwd_cell(hipStream_t s, const RecArgs& a, bool simple) 
         const size_t l6 = w3b + (db6 ? 2 : 1) * one6;
         if (l6 <= 160 * 1024) {
             const int nb6 = a.Bp / a.rpt;
-            if (a.rpt == 4 && a.x6_split) {
+            if (a.rpt == 4) {
                 if (Hp == 32) LAUNCH_DYN((rec_bwd_x6s<CELL, 32>), nb6, Hp * 4, l6, a, db6);
                 else if (Hp == 64) LAUNCH_DYN((rec_bwd_x6s<CELL, 64>), nb6, Hp * 4, l6, a, db6);
                 else LAUNCH_DYN((rec_bwd_x6s<CELL, 128>), nb6, Hp * 4, l6, a, db6);

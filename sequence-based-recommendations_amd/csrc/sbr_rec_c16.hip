@@ -791,11 +791,6 @@ __global__ void __launch_bounds__(256, 2) rec_bwd_c16(RecArgs a) {
 // ---------------------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------------------
-// Hp = 512: the backward exchange in two levels (rec_bwd_c16t); SBR_C16_TWO_LEVEL=0: one level, as at Hp = 256
-static bool c16_two_level() {
-    static const int two = [] { const char* e = getenv("SBR_C16_TWO_LEVEL"); return e ? atoi(e) : 1; }();
-    return two != 0;
-}
 template <int CELL, int HP>
 static hipError_t fwd_c16(hipStream_t s, const RecArgs& a) {
     constexpr int G = Gates<CELL>::G;
@@ -813,7 +808,7 @@ static hipError_t bwd_c16(hipStream_t s, const RecArgs& a_in) {
     a.dhe_on = a.dh_ext != nullptr;
     if (!a.dh_ext) a.dh_ext = a.hs;                      // requested every step, used only under dhe_on (no pointer select in the kernel)
     if constexpr (HP == 512) {
-        if (c16_two_level()) {
+        if (a.c16_two_level) {      // the backward exchange in two levels (rec_bwd_c16t); SBR_C16_TWO_LEVEL=0: one level, as at Hp = 256
             const size_t lds2 = (size_t)4 * (G == 1 ? 1 : 2) * 2048 + 4 * 1024;
             CL_LAUNCH((rec_bwd_c16t<CELL>), 32, 16, lds2);
             return hipGetLastError();
@@ -836,6 +831,6 @@ hipError_t launch_rec_backward_c16(hipStream_t s, const RecArgs& a) { C16_DISPAT
 // (two levels: + the sentinel of the level-1 images behind them; 1 MB per tile instead of 2)
 hipError_t sbr_rec_c16_fill(hipStream_t s, const RecArgs& a) {
     size_t bytes = sbr_rec_c16_ring_floats(a.Bp, a.Hp) * sizeof(float);
-    if (a.Hp == 512 && c16_two_level()) bytes = (size_t)(a.Bp / 16) * (SBR_C16_RING * 32 * 8 * 1024 + 4 * 8 * 16384);
+    if (a.Hp == 512 && a.c16_two_level) bytes = (size_t)(a.Bp / 16) * (SBR_C16_RING * 32 * 8 * 1024 + 4 * 8 * 16384);
     return hipMemsetAsync(a.pring, 0xFF, bytes, s);
 }

@@ -21,16 +21,6 @@
 // Cell math: sbr_cell.h (sparse_lstm.py:377-425, :764-805, :1120-1152); BPTT pinned by oracle/rnn_oracle.py.
 #include "sbr_rec_cl.h"
 
-// bool switches of the two chains, read per launch (the tests flip them); the same conditions as the 128-unit kernels
-static bool cl_f16_fwd(const RecArgs& a) {
-    const char* fe = getenv("SBR_X6_F16");
-    return (fe ? atoi(fe) != 0 : true) && !a.relu;
-}
-static bool cl_f16_bwd(const RecArgs& a) {
-    const char* fe = getenv("SBR_X6_F16_BWD");
-    return (fe ? atoi(fe) != 0 : true) && a.clip > 0.0f && a.clip <= 100.0f;
-}
-
 // ---------------------------------------------------------------------------------------
 // forward
 // ---------------------------------------------------------------------------------------
@@ -1017,16 +1007,14 @@ bool sbr_rec_cluster_ok(const RecArgs& a) {
 // the 16-row kernels: both chains on fp16 planes (one answer for the forward and the backward launch of a step: they share
 // the exchange arrays' and the partial sums' layout), SBR_CL16=0 keeps the 8-row kernels
 bool sbr_rec_c16_ok(const RecArgs& a) {
-    const char* ce = getenv("SBR_CL16");                           // read per launch: the tests flip it
-    const bool on = ce ? atoi(ce) != 0 : true;
-    if (!(on && sbr_rec_cluster_ok(a) && a.xh && a.pring && a.Bp % 16 == 0 && cl_f16_fwd(a) && cl_f16_bwd(a))) return false;
+    if (!(a.cl16 && sbr_rec_cluster_ok(a) && a.xh && a.pring && a.Bp % 16 == 0 && sbr_rec_f16_fwd(a) && sbr_rec_f16_bwd(a))) return false;
     if (a.cell != SBR_CELL_VANILLA && a.g[0])             // the saved gates are ONE region [T][Bp][Hp][4] under the four arrays
         for (int k = 1; k < 4; ++k) if (a.g[k] != a.g[0] + (size_t)k * a.T * a.Bp * a.Hp) return false;
     return true;
 }
 int sbr_rec_cluster_bwd_rows(const RecArgs& a) {
     if (sbr_rec_c16_ok(a)) return 16;
-    return a.Hp == 512 && !cl_f16_bwd(a) ? 4 : SBR_CL_ROWS;
+    return a.Hp == 512 && !sbr_rec_f16_bwd(a) ? 4 : SBR_CL_ROWS;
 }
 size_t sbr_rec_c16_ring_floats(int Bp, int Hp) { return (size_t)SBR_C16_RING * (Bp / 16) * (Hp / 16) * (Hp / 16) * 256; }
 
@@ -1037,7 +1025,7 @@ static hipError_t fwd_cl(hipStream_t s, const RecArgs& a) {
     hipError_t e = hipMemsetAsync(a.hs, 0xFF, (size_t)(a.T + 1) * a.Bp * HP * sizeof(float), s);   // sentinel: see the header
     if (e != hipSuccess) return e;
     if (HP == 256) {
-        if (cl_f16_fwd(a)) {
+        if (sbr_rec_f16_fwd(a)) {
             const size_t lds = 2 * (size_t)R * (HP * 2 + 32) + 2 * G * 1024;
             CL_LAUNCH((rec_fwd_cl<CELL, 256, R, true>), 256 / 32, R, lds);
         } else {
@@ -1045,7 +1033,7 @@ static hipError_t fwd_cl(hipStream_t s, const RecArgs& a) {
             CL_LAUNCH((rec_fwd_cl<CELL, 256, R, false>), 256 / 32, R, lds);
         }
     } else {   // 512: one unit tile per workgroup, K in four parts, a cluster = 32 workgroups
-        if (cl_f16_fwd(a)) {
+        if (sbr_rec_f16_fwd(a)) {
             const size_t lds = 2 * (size_t)R * (HP * 2 + 32) + 3 * G * 1024;
             CL_LAUNCH((rec_fwd_clg<CELL, 512, 1, 4, R, true>), 512 / 16, R, lds);
         } else {
@@ -1065,7 +1053,7 @@ static hipError_t bwd_cl(hipStream_t s, const RecArgs& a) {
     if (sbr_rec_c16_ok(a)) return launch_rec_backward_c16(s, a);
     if (HP == 256) {
         constexpr int R = SBR_CL_ROWS;
-        if (cl_f16_bwd(a)) {
+        if (sbr_rec_f16_bwd(a)) {
             const size_t lds = 2 * (size_t)R * (GHP * 2 + 32) + 2 * 1024;
             CL_LAUNCH((rec_bwd_cl<CELL, 256, R, true>), 256 / 32, R, lds);
         } else {
@@ -1073,7 +1061,7 @@ static hipError_t bwd_cl(hipStream_t s, const RecArgs& a) {
             CL_LAUNCH((rec_bwd_cl<CELL, 256, R, false>), 256 / 32, R, lds);
         }
     } else {
-        if (cl_f16_bwd(a)) {     // two fp16 planes and no W plane in LDS: 8-row tiles fit (66 KB), half the workgroup rounds
+        if (sbr_rec_f16_bwd(a)) {     // two fp16 planes and no W plane in LDS: 8-row tiles fit (66 KB), half the workgroup rounds
             constexpr int R = 8;
             const size_t lds = 2 * (size_t)R * (GHP * 2 + 32) + 3 * 1024;
             CL_LAUNCH((rec_bwd_clg<CELL, 512, 1, 4, R, true>), 512 / 16, R, lds);

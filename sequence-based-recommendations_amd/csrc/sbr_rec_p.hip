@@ -1113,22 +1113,13 @@ __global__ void __launch_bounds__(512) rec_bwd_x6p(RecArgs a) {
 // ---------------------------------------------------------------------------------------
 static size_t fwd_lds_bytes() { return 2 * 3 * R * (size_t)(HP * 2 + 32) + 64; }
 
-static bool x6p_f16_fwd(const RecArgs& a) {                        // forward products as fp16 x3 (see split2_f16); a rectified
-    const char* fe = getenv("SBR_X6_F16");                         // state is unbounded, the fp16 split needs |h| < 65504
-    return (fe ? atoi(fe) != 0 : true) && !a.relu;                 // (read per launch: the tests flip it)
-}
-static bool x6p_f16_bwd(const RecArgs& a) {     // the operand that carries gradients is bounded by the reference's own gradient clip
-    const char* fe = getenv("SBR_X6_F16_BWD");
-    return (fe ? atoi(fe) != 0 : true) && a.clip > 0.0f && a.clip <= 100.0f;
-}
-
 int sbr_rec_x6p_f16_terms() { return X6P_PACK ? (X6P_SPARSE ? 1 : 2) : 3; }
 
 bool sbr_rec_x6p_ok(const RecArgs& a) {
-    if (!a.x6_pipe || a.f32_mfma || a.Hp != HP || a.rpt != R || !a.x6_split) return false;
+    if (!a.x6_pipe || a.f32_mfma || a.Hp != HP || a.rpt != R) return false;
     // four gates: W_hid fits the register file as two fp16 planes only, so an LSTM runs here while BOTH directions take their
     // fp16 forms (one answer for the forward and the backward launch of a step: they share the saved activations' layout)
-    if (a.G > 3 && !(x6p_f16_fwd(a) && x6p_f16_bwd(a))) return false;
+    if (a.G > 3 && !(sbr_rec_f16_fwd(a) && sbr_rec_f16_bwd(a))) return false;
     if ((size_t)a.Bp * a.G * HP * 4 >= ((size_t)1 << 32)) return false;          // 32-bit per-lane byte offsets
     // (NOT a function of a.gX: the forward and the backward launch of a step must get the same answer -- they share the saved
     // gates' layout (X6P_G4).  Whether the gather can be fused is sbr_rec_fwd_can_fuse_gather's decision, made before gX is set;
@@ -1159,7 +1150,7 @@ static hipError_t launch_fwd_p(hipStream_t s, const RecArgs& a) {
         KERNEL<<<nb, 512, lds, s>>>(a); } while (0)
     const bool fuse = a.gX != nullptr;
     if (fuse && !sbr_rec_x6p_fuse_ok(a)) return hipErrorInvalidValue;          // (sbr_rec_fwd_can_fuse_gather says when)
-    const bool f16 = x6p_f16_fwd(a);
+    const bool f16 = sbr_rec_f16_fwd(a);
     if constexpr (CELL == CELL_LSTM) {
         if (!f16) return hipErrorInvalidValue;                     // (sbr_rec_x6p_ok says when)
         if (a.prof) { if (fuse) X6P_LAUNCH((rec_fwd_x6p<CELL, true, true, true>)); else X6P_LAUNCH((rec_fwd_x6p<CELL, false, true, true>)); }
@@ -1182,7 +1173,7 @@ static hipError_t launch_bwd_p(hipStream_t s, const RecArgs& a) {
     // Overlapped tail: the chain's workgroup claims most of its CU's LDS, so that the consumers that run beside it -- the polling
     // weight-gradient GEMM (40 KB of LDS per workgroup, MFMAs on the same SIMDs) and the scatter-add (which asks for LDS it does not
     // use, for this purpose) -- are placed on the other 192 CUs instead of sharing the chain's matrix pipes, issue slots and L1
-    // path.  SBR_TAIL_FENCE_KB=0: no fence (round 2).
+    // path.  (fence_kb = 0: no fence, as in round 2.)
     if (a.fence_kb > 0 && a.Bp / R <= 192) {      // (one workgroup per CU must still leave CUs to the consumers: up to B = 768)
         const size_t fence = (size_t)a.fence_kb * 1024;
         if (fence > lds && fence <= 160 * 1024) lds = fence;
@@ -1192,7 +1183,7 @@ static hipError_t launch_bwd_p(hipStream_t s, const RecArgs& a) {
         SBR_DYN_LDS(KERNEL, lds); \
         KERNEL<<<nb, 512, lds, s>>>(a); } while (0)
     const bool ext = a.dh_ext != nullptr;
-    const bool f16 = x6p_f16_bwd(a);                               // fp16 x3 products for the BPTT chain
+    const bool f16 = sbr_rec_f16_bwd(a);                               // fp16 x3 products for the BPTT chain
     if (a.progress && (ext || !f16)) return hipErrorInvalidValue;               // (sbr_rec_x6p_tail_ok says when)
     if (CELL == CELL_LSTM && !f16) return hipErrorInvalidValue;                 // (sbr_rec_x6p_ok)
     if (a.prof && f16 && !ext) {      // in-kernel counters for the fp16x3 forms too (tools/tail_prof.py)
@@ -1211,7 +1202,7 @@ static hipError_t launch_bwd_p(hipStream_t s, const RecArgs& a) {
 
 // the write-through / progress form of the backward kernel exists for the fp16x3 products of a top (single) layer
 bool sbr_rec_x6p_tail_ok(const RecArgs& a) {
-    const bool f16 = x6p_f16_bwd(a);
+    const bool f16 = sbr_rec_f16_bwd(a);
     const char* sbase = a.cell == SBR_CELL_LSTM ? (const char*)a.cs : (const char*)a.hs;
     for (int k = 0; k < 4 && a.cell != SBR_CELL_VANILLA; ++k) {      // one scalar base serves hs (cs) and the gate arrays (LDS-DMA loads)
         const ptrdiff_t d = (const char*)a.g[k] - sbase;

@@ -494,7 +494,7 @@ __global__ void __launch_bounds__(HQ * 4) rec_bwd_x6q(RecArgs a) {
 // launchers
 // ---------------------------------------------------------------------------------------
 bool sbr_rec_x6q_ok(const RecArgs& a) {
-    if (!a.x6_pipe || a.f32_mfma || !(a.Hp == 32 || a.Hp == 64) || a.rpt != RQ || !a.x6_split || a.prof) return false;
+    if (!a.x6_pipe || a.f32_mfma || !(a.Hp == 32 || a.Hp == 64) || a.rpt != RQ || a.prof) return false;
     if ((size_t)a.Bp * a.G * a.Hp * 4 >= ((size_t)1 << 32)) return false;               // 32-bit per-lane byte offsets
     if (a.gX && (size_t)a.n_in * a.G * a.Hp * 4 >= ((size_t)1 << 32)) return false;     // ... also into W_in (fused gather)
     return true;
@@ -508,8 +508,7 @@ template <int CELL, int HQ>
 static hipError_t launch_fwd_q(hipStream_t s, const RecArgs& a) {
     const size_t lds = 2 * 3 * RQ * (size_t)(HQ * 2 + 32) + 64;
     const int nb = a.Bp / RQ;
-    const char* fe = getenv("SBR_X6_F16");                         // read per launch: the tests flip it
-    const bool f16 = (fe ? atoi(fe) != 0 : true) && !a.relu;       // (a rectified state is unbounded)
+    const bool f16 = sbr_rec_f16_fwd(a);
     if (f16) { if (a.gX) X6Q_LAUNCH((rec_fwd_x6q<CELL, HQ, true, true>), HQ * 4, lds); else X6Q_LAUNCH((rec_fwd_x6q<CELL, HQ, false, true>), HQ * 4, lds); }
     else { if (a.gX) X6Q_LAUNCH((rec_fwd_x6q<CELL, HQ, true, false>), HQ * 4, lds); else X6Q_LAUNCH((rec_fwd_x6q<CELL, HQ, false, false>), HQ * 4, lds); }
     return hipGetLastError();
@@ -518,8 +517,7 @@ template <int CELL, int HQ>
 static hipError_t launch_bwd_q(hipStream_t s, const RecArgs& a) {
     const size_t lds = 2 * 3 * RQ * (size_t)(Gates<CELL>::G * HQ * 2 + 32) + 64;
     const int nb = a.Bp / RQ;
-    const char* fe = getenv("SBR_X6_F16_BWD");                     // read per launch: the tests flip it
-    const bool f16 = (fe ? atoi(fe) != 0 : true) && a.clip > 0.0f && a.clip <= 100.0f;      // the clip bounds the gradient operand
+    const bool f16 = sbr_rec_f16_bwd(a);
     if (f16) { if (a.dh_ext) X6Q_LAUNCH((rec_bwd_x6q<CELL, HQ, true, true>), HQ * 4, lds); else X6Q_LAUNCH((rec_bwd_x6q<CELL, HQ, false, true>), HQ * 4, lds); }
     else { if (a.dh_ext) X6Q_LAUNCH((rec_bwd_x6q<CELL, HQ, true, false>), HQ * 4, lds); else X6Q_LAUNCH((rec_bwd_x6q<CELL, HQ, false, false>), HQ * 4, lds); }
     return hipGetLastError();

@@ -1,6 +1,7 @@
 """The non-default forms of the step tail of a wide index-input layer (G*Hp >= 512 floats per row: LSTM-128 and wider) -- each a switch
-that is read once per process, so each runs in a child: the atomic scatter-add of rounds 1 - 3 (SBR_SCAT_RANGE=0) -- what rows wider
-than 1024 floats take -- and the segment-parallel form (2), and the plain dense pass over W_in (SBR_ROW_AWARE_UPDATE=0).
+that is read once per engine, when it is created; each form runs in a child process of its own here: the atomic scatter-add of rounds
+1 - 3 (SBR_SCAT_RANGE=0) -- what rows wider than 1024 floats take -- and the segment-parallel form (2), and the plain dense pass over
+W_in (SBR_ROW_AWARE_UPDATE=0).
 Same bars as the default form (the range scatter-add, every other wide-layer test): cost, hidden state and gradients against the float64
 oracle, parameters after two Adam steps; and after three steps the same parameters as the default form up to what Adam makes of
 summation-order roundings (an element whose gradient is ~0 moves by ~lr whatever the gradient's size: 5e-5 of the largest parameter)."""
