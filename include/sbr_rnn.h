@@ -28,7 +28,7 @@ extern "C" {
 #endif
 
 #define SBR_MAX_LAYERS 4
-#define SBR_ABI_VERSION 10
+#define SBR_ABI_VERSION 11
 
 typedef enum { SBR_OK = 0, SBR_EINVAL = -1, SBR_ENOMEM = -2, SBR_EHIP = -3, SBR_ESTATE = -4,
                SBR_EUNSUPPORTED = -5 } sbr_status;
@@ -267,6 +267,25 @@ int sbr_predict_scores(sbr_handle* h, int probs, float* out_host);
  * (interactions_are_unique, rnn_base.py:200-201).  Ties break to the lowest id.  A row with fewer than k rankable items
  * (more than N - k items excluded, or NaN scores) gets -1 in the places it cannot fill. */
 int sbr_topk(sbr_handle* h, int k, int exclude_seen, int32_t* ids_host);
+/* The same ranking without sbr_topk's limits (ABI 11): any depth 1 <= k <= N, and per-row exclusion lists -- the batched form of
+ * top_k_recommendations(sequence, k, exclude=...) (rnn_base.py:140-165), for users whose history is longer than max_length (all of
+ * it is excluded, only its end is fed) and for metrics deeper than 64.  The scores ranked are the ones sbr_topk ranks (the exact-f32
+ * projection plus bias, no softmax: monotone), so the two calls agree id for id.
+ *   exclude_input != 0   the items of each row's input window are never ranked (sbr_topk's exclude_seen = 1)
+ *   excl_ids / excl_off  HOST arrays, a CSR over the batch's rows: excl_off has n_rows + 1 non-decreasing entries, row r's further
+ *                        excluded ids are excl_ids[excl_off[r] .. excl_off[r + 1]) -- any length, duplicates and empty lists
+ *                        allowed; both NULL: no lists.  An id outside [0, N), decreasing offsets, or exactly one of the two NULL
+ *                        is SBR_EINVAL, found before anything is launched: the engine stays usable.
+ *   ids_host             [n_rows][k], score descending, ties to the lowest id (-0.0 and +0.0 tie).  Finite scores and +inf are
+ *                        ranked; NaN, -inf and excluded items never; the places a row cannot fill hold -1
+ *   scores_host          NULL, or [n_rows][k]: the score of each ranked id (-inf in the unfilled places); softmax is NOT applied
+ * No batch set: SBR_ESTATE.  The call needs scratch that grows with n_rows * k and the lists; it is the handle's own device
+ * allocation (made on first use, grown on demand, freed by sbr_destroy), never part of the arena -- sbr_arena_bytes does not change.
+ * A failed allocation is SBR_ENOMEM with the byte count in sbr_last_error().  Parameters, gradients and optimizer state are not
+ * touched (beyond bringing lazily stepped rows up to date, as sbr_topk does).  sbr_query "rank_select" / "rank_sort" tell what the
+ * last call ran: the select with the row in LDS (1) or streamed (2), the sort in LDS (1) or as a radix sort in scratch (2). */
+int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
+             int32_t* ids_host, float* scores_host);
 
 /* The dense GEMM of the hot path on caller-provided DEVICE buffers (parity tests of the kernels themselves):
  * C[m][n] = sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n]); ws: split-K workspace (may be NULL).

@@ -459,6 +459,7 @@ extern "C" void sbr_destroy(sbr_handle* h) {
     if (h->own_arena && h->arena) (void)hipFree(h->arena);
     if (h->tail_trace) (void)hipFree(h->tail_trace);
     if (h->tail_slab_dev) (void)hipFree(h->tail_slab_dev);
+    if (h->rank_scratch) (void)hipFree(h->rank_scratch);
     delete h;
 }
 
@@ -1889,6 +1890,71 @@ extern "C" int sbr_topk(sbr_handle* h, int k, int exclude_seen, int32_t* ids_hos
     return check_fault(h);          // ... nor rankings (test.py, validation)
 }
 
+// Ordered top-k of any depth with per-row exclusion lists (top_k_recommendations' k and exclude=, rnn_base.py:140-165, for a
+// whole batch): sbr_rank.hip.  Its scratch -- the device copies of the lists, the selected (key, id) pairs, the radix sort's
+// second pair, the results -- is the handle's own allocation and not part of the arena: its size follows k and the lists.
+static int rank_scratch(sbr_handle* h, size_t bytes) {
+    if (bytes <= h->rank_scratch_bytes) return SBR_OK;
+    if (h->rank_scratch) { (void)hipFree(h->rank_scratch); h->rank_scratch = nullptr; h->rank_scratch_bytes = 0; }
+    if (hipMalloc(&h->rank_scratch, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->rank_scratch = nullptr;
+        sbr_set_error("sbr_rank: hipMalloc(%zu) of the ranking scratch failed", bytes);
+        return SBR_ENOMEM;
+    }
+    h->rank_scratch_bytes = bytes;
+    return SBR_OK;
+}
+
+extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
+                        int32_t* ids_host, float* scores_host) {
+    CHECK_ARG(h && ids_host, "null argument");
+    if (!h->have_batch) { sbr_set_error("sbr_rank: no batch set"); return SBR_ESTATE; }
+    const Layout& y = h->lay;
+    const int rows = h->n_rows;
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    CHECK_ARG((excl_ids == nullptr) == (excl_off == nullptr), "excl_ids and excl_off: both or neither");
+    int64_t n_excl = 0;
+    if (excl_off) {         // everything about the lists is checked here, before anything is launched
+        CHECK_ARG(excl_off[0] >= 0, "excl_off[0] = %lld is negative", (long long)excl_off[0]);
+        for (int r = 0; r < rows; ++r)
+            CHECK_ARG(excl_off[r + 1] >= excl_off[r], "excl_off decreases at row %d (%lld -> %lld)", r, (long long)excl_off[r], (long long)excl_off[r + 1]);
+        for (int64_t j = excl_off[0]; j < excl_off[rows]; ++j)
+            CHECK_ARG(excl_ids[j] >= 0 && excl_ids[j] < y.N, "excluded id %d outside [0,%d)", excl_ids[j], y.N);
+        n_excl = excl_off[rows] - excl_off[0];
+    }
+    const bool radix = k > kRankSortLds;
+    const size_t rk = (size_t)rows * k;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_off = take((size_t)(rows + 1) * sizeof(long long)), o_eid = take((size_t)n_excl * sizeof(int));
+    const size_t o_nsel = take((size_t)rows * sizeof(int));
+    const size_t o_k0 = take(rk * sizeof(unsigned)), o_i0 = take(rk * sizeof(int));
+    const size_t o_k1 = take(radix ? rk * sizeof(unsigned) : 0), o_i1 = take(radix ? rk * sizeof(int) : 0);
+    const size_t o_oid = take(rk * sizeof(int)), o_osc = take(rk * sizeof(float));
+    int rc;
+    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_topk ranks (and flushes lazily stepped rows)
+    float* lg = h->A(y.a_logits);
+    if (excl_off) {
+        std::vector<long long> off((size_t)rows + 1);
+        for (int r = 0; r <= rows; ++r) off[r] = (long long)(excl_off[r] - excl_off[0]);
+        // (pageable host memory: both copies have left the host buffers when they return)
+        SBR_HIP(hipMemcpyAsync(S + o_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        if (n_excl) SBR_HIP(hipMemcpyAsync(S + o_eid, excl_ids + excl_off[0], (size_t)n_excl * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        SBR_HIP(hipStreamSynchronize(h->stream));           // `off` goes out of scope
+    }
+    SBR_LAUNCH(launch_rank_exclude(h->stream, lg, rows, y.N, excl_off ? (const int*)(S + o_eid) : nullptr,
+                                   excl_off ? (const long long*)(S + o_off) : nullptr, exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
+    SBR_LAUNCH(launch_rank_select(h->stream, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
+    SBR_LAUNCH(launch_rank_sort(h->stream, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
+                                (const int*)(S + o_nsel), (int*)(S + o_oid), (float*)(S + o_osc), &h->last_rank_sort));
+    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    return check_fault(h);          // a forward that gave up must not hand out rankings
+}
+
 // ---------------------------------------------------------------------------------------
 // debug / timing
 // ---------------------------------------------------------------------------------------
@@ -2040,6 +2106,9 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     // what the LAST step launched for the gradient of layer 0's index-input rows (-1: no step yet): 0 sorted segment reduce, 1 range form,
     // 2 segment-parallel form, 3 per-element atomics (SBR_FLAG_ATOMIC_SCATTER), 4 / 5 the overlapped tail's polling reduce / LDS-row kernel
     else if (w == "scatter_form") *value = h->last_scatter_form;
+    // what the LAST sbr_rank ran (0: none yet): its select with the row's keys in LDS (1) or streamed (2), its sort in LDS (1) or in scratch (2)
+    else if (w == "rank_select") *value = h->last_rank_select;
+    else if (w == "rank_sort") *value = h->last_rank_sort;
     else if (w == "row_aware_update") *value = h->last_row_aware ? 1 : 0;      // ... and whether its optimizer pass over W_in was the row-aware one
     else if (w == "cluster") { RecArgs a = rec_args(h, (y.L - 1) * y.D); *value = (!simple_rec(h) && sbr_rec_cluster_ok(a)) ? 1 : 0; }
     else if (w == "rec_kernel") {   // family serving the top layer: 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other

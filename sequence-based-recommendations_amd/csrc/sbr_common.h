@@ -159,6 +159,10 @@ constexpr double kTailSlabGrowth = 0.35;  // k steps of a slab per time step of 
 // growth of the small time chunks near t = 0 (tail_plan, sbr_api.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
 // walks them one after the other; 1, 3, 7, 18 for the polling range form
 static inline double sbr_tail_geom(int scatter_lds) { return scatter_lds ? 1.6 : 2.6; }
+// sbr_rank (sbr_rank.hip): where its two pairs of regimes change
+constexpr int kRankThreads = 1024;        // threads of a row's workgroup in the select and sort kernels (16 waves: one id segment each)
+constexpr int kRankLdsRow = 32768;        // longest row whose keys stay in LDS during the select (128 KB of the CU's 160 KB; C4's 26 744 fits)
+constexpr int kRankSortLds = 2048;        // largest k the LDS bitonic sort takes (16 KB of 64-bit composites); above: the LSD radix sort in scratch
 
 // Every environment switch the library reads (README.md "Switches"), with its default.  sbr_read_switches (sbr_api.hip) fills one
 // per engine, inside sbr_create, and nothing reads the environment afterwards: an engine keeps the values it was created under.
@@ -247,6 +251,8 @@ struct sbr_handle {
     SbrTChunks tail_bounds = {};    // ... and their bounds (tail_plan)
     unsigned long long* tail_trace = nullptr;    // SbrSwitches.tail_trace: SbrPoll.trace
     bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
+    // sbr_rank: scratch outside the arena (grown on demand, freed by sbr_destroy) and what the last call ran (sbr_query "rank_select" / "rank_sort")
+    void* rank_scratch = nullptr; size_t rank_scratch_bytes = 0; int last_rank_select = 0, last_rank_sort = 0;
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
     bool tail_cost_scanned = false;                                       // this step's sort was followed by launch_scatter_cost_scan
     int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
@@ -572,3 +578,14 @@ hipError_t launch_exclude_seen(hipStream_t s, float* scores, const int* X, const
                                int N, float value);
 hipError_t launch_topk(hipStream_t s, float* scores, int rows, int N, int k, int* ids);
 hipError_t launch_fill(hipStream_t s, float* p, float v, size_t n);
+// sbr_rank.hip: ordered top-k of any k with per-row exclusion lists (include/sbr_rnn.h: sbr_rank)
+// -inf into scores[r][id] for the ids of row r's CSR list (excl_off NULL: none) and, with X, of its input window
+hipError_t launch_rank_exclude(hipStream_t s, float* scores, int rows, int N, const int* excl_ids, const long long* excl_off,
+                               const int* X, const int* len, int T, int F);
+// the (at most k) entries of every row that a ranking to depth k holds, in id order: keys / ids [rows][k], n_sel [rows]; returns the
+// regime in *select (1: the row's keys in LDS, 2: streamed)
+hipError_t launch_rank_select(hipStream_t s, const float* scores, int rows, int N, int k, unsigned* keys, int* ids, int* n_sel, int* select);
+// ... sorted by key descending, id ascending, into out_ids / out_scores [rows][k] (-1 / -inf behind a row's n_sel); keys2 / ids2: the
+// radix sort's second buffer pair (not read when k <= kRankSortLds); returns the regime in *sort (1: LDS bitonic, 2: radix in scratch)
+hipError_t launch_rank_sort(hipStream_t s, const float* scores, int rows, int N, int k, unsigned* keys, int* ids, unsigned* keys2, int* ids2,
+                            const int* n_sel, int* out_ids, float* out_scores, int* sort);

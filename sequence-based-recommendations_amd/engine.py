@@ -21,7 +21,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libsbr_rnn.so")
 
 SBR_MAX_LAYERS = 4
-SBR_ABI_VERSION = 10
+SBR_ABI_VERSION = 11
 SBR_N_PHASES = 8
 PHASE_NAMES = ("gather", "rec_fwd", "output", "rec_bwd", "wgrad", "scatter", "update", "total")
 
@@ -60,7 +60,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_param_shape", "sbr_describe_param", "sbr_set_params", "sbr_get_params", "sbr_get_grads", "sbr_section", "sbr_set_batch",
            "sbr_set_default_target",
            "sbr_train_step", "sbr_train_step_lagged", "sbr_lagged_flush", "sbr_zero_grads", "sbr_forward", "sbr_loss_backward_output", "sbr_backward_recurrent",
-           "sbr_apply_update", "sbr_read_cost", "sbr_predict_scores", "sbr_topk", "sbr_debug_buffer",
+           "sbr_apply_update", "sbr_read_cost", "sbr_predict_scores", "sbr_topk", "sbr_rank", "sbr_debug_buffer",
            "sbr_copy_to_host", "sbr_synchronize", "sbr_enable_timing", "sbr_phase_times", "sbr_chain_times", "sbr_query",
            "sbr_set_deferred_join", "sbr_join_side", "sbr_debug_gemm", "sbr_debug_scatter", "sbr_debug_occupy", "sbr_flush_lazy", "sbr_sparse_info", "sbr_sparse_pack",
            "sbr_sparse_unpack_add", "sbr_dense_ranges", "sbr_sparse_pack_device", "sbr_sparse_unpack_add_all",
@@ -113,6 +113,7 @@ def load_library(path=None):
     lib.sbr_read_cost.argtypes = [vp, f32p]
     lib.sbr_predict_scores.argtypes = [vp, ctypes.c_int, vp]
     lib.sbr_topk.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
+    lib.sbr_rank.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     lib.sbr_debug_buffer.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     lib.sbr_copy_to_host.argtypes = [vp, vp, vp, ctypes.c_size_t]
     lib.sbr_enable_timing.argtypes = [vp, ctypes.c_int]
@@ -678,6 +679,43 @@ class RNNEngine(object):
         # test function's scores * (1 - exclude) (:201-202): the same ranking except for RNNMargin's raw outputs
         self._check(self.lib.sbr_topk(self.h, int(k), int(exclude_seen), ctypes.c_void_p(ids.ctypes.data)))
         return ids
+
+    def rank(self, X, mask, k, exclude=None, exclude_input=True, return_scores=False):
+        """Ordered top-k of any depth 1 <= k <= n_items for every row (sbr_rank): ids (rows, k) int32, score descending, ties to
+        the lowest id, -1 where a row runs out of rankable items; with return_scores also their float32 scores (raw activations,
+        no softmax; -inf in the unfilled places).  exclude: per row, the ids never to rank (any length, duplicates allowed, None
+        or empty for none) -- top_k_recommendations' exclude= and the part of a history that no longer fits the input window;
+        exclude_input: also the items of the row's input window, as test_function(exclude_seen=True) does."""
+        self._rank_local_flush("rank")
+        n = self.set_batch(X, mask)
+        ids_arr = off_arr = None
+        if exclude is not None:
+            lists = [np.zeros(0, dtype=np.int32) if e is None else np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+            if len(lists) != n:
+                raise ValueError("exclude must hold one id list per row: %d lists for %d rows" % (len(lists), n))
+            off_arr = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum([len(e) for e in lists], out=off_arr[1:])
+            ids_arr = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]))   # (never empty: its pointer is not NULL)
+        return self.rank_csr(n, k, ids_arr, off_arr, exclude_input=exclude_input, return_scores=return_scores)
+
+    def rank_csr(self, rows, k, excl_ids=None, excl_off=None, exclude_input=True, return_scores=False):
+        """sbr_rank on the batch already set (`rows` rows); the lists as the C-ABI takes them: int32 ids and int64 offsets
+        (rows + 1 of them), or None for both."""
+        self._rank_local_flush("rank")
+        k = int(k)
+        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
+            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
+        ids = np.empty((rows, k), dtype=np.int32)
+        scores = np.empty((rows, k), dtype=np.float32) if return_scores else None
+        if excl_ids is not None:
+            excl_ids = np.ascontiguousarray(np.asarray(excl_ids, dtype=np.int32))
+        if excl_off is not None:
+            excl_off = np.ascontiguousarray(np.asarray(excl_off, dtype=np.int64))
+            if excl_off.shape != (rows + 1,):
+                raise ValueError("excl_off must have %d entries (rows + 1), got %r" % (rows + 1, excl_off.shape))
+        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        self._check(self.lib.sbr_rank(self.h, k, int(bool(exclude_input)), p(excl_ids), p(excl_off), p(ids), p(scores)))
+        return (ids, scores) if return_scores else ids
 
     # ---------------------------------------------------------------- debug / timing
     def debug_buffer(self, name):

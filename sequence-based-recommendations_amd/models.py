@@ -211,6 +211,41 @@ class RNNBase(object):
         output[exclude] = -np.inf
         return list(np.argpartition(-output, range(k))[:k])
 
+    batched_top_k = True        # top_k_batch ranks what top_k_recommendations ranks (RNNCluster: no, it scores inside a cluster on the host)
+
+    def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
+        """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)], batch_size rows per engine
+        call (engine.rank): per sequence the last max_length items go in; every item of the WHOLE sequence is excluded when
+        interactions are unique -- also the part that no longer fits the window -- plus the row's own exclude list; any
+        1 <= k <= n_items.  Returns a list of id lists, best first; a row with fewer than k rankable items returns only
+        those (top_k_recommendations would go on with excluded ids, in no defined order)."""
+        n = len(sequences)
+        if user_ids is None:
+            user_ids = [None] * n
+        if exclude is None:
+            exclude = [None] * n
+        if len(user_ids) != n or len(exclude) != n:
+            raise ValueError("user_ids and exclude must have one entry per sequence")
+        out = []
+        for lo in range(0, n, self.batch_size):
+            hi = min(n, lo + self.batch_size)
+            X = np.zeros((hi - lo, self.max_length, self._input_size()), dtype=np.int32)
+            mask = np.zeros((hi - lo, self.max_length), dtype=np.float32)
+            lists = []
+            for i in range(lo, hi):
+                seq = sequences[i][-min(self.max_length, len(sequences[i])):]
+                if len(seq):
+                    X[i - lo, :len(seq), :] = np.array([self._get_features(x, user_ids[i]) for x in seq], dtype=np.int32)
+                mask[i - lo, :len(seq)] = 1
+                ex = [x[0] for x in sequences[i]] if self.interactions_are_unique else []
+                if exclude[i] is not None:
+                    ex = ex + [int(e) for e in exclude[i]]
+                lists.append(np.asarray(ex, dtype=np.int32))
+            # the lists carry every viewed item already: the engine need not derive them from its input window again
+            ids = self._rd().rank(X, mask, k, exclude=lists, exclude_input=False)
+            out.extend([int(j) for j in row[row >= 0]] for row in ids)
+        return out
+
     # ------------------------------------------------------------------ training loop (rnn_base.py:215-356)
     def get_pareto_front(self, metrics, metrics_names):
         costs = np.zeros((len(metrics[metrics_names[0]]), len(metrics_names)))
@@ -791,6 +826,12 @@ class RNNCluster(RNNBase):
         scores = u.dot(params[-2]) + params[-1]
         scores[exclude] = -np.inf
         return list(np.argpartition(-scores, range(k))[:k]), self.n_items
+
+    batched_top_k = False
+
+    def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
+        raise NotImplementedError("RNNCluster ranks inside the user's hard cluster on the host (predict_function, rnn_cluster.py:302-325): "
+                                  "the engine's batched ranking would rank the whole catalogue instead; call top_k_recommendations per user")
 
     def top_k_recommendations(self, sequence, user_id=None, k=10, exclude=None):
         if exclude is None:

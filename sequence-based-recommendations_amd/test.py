@@ -37,14 +37,18 @@ def save_file_name(predictor, dataset, args):                         # test.py:
 def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list=False, k=10):
     """test.py:43-77: the first half of every test sequence is viewed, the rest is the goal;
     `top_k_recommendations` feeds the last max_length viewed items and excludes EVERY viewed item (rnn_base.py:132-159).
-    Users whose viewed half fits the window (the engine derives the exclusion from its input) are ranked batch_size at a
-    time; longer ones, and full rankings (--save_rank), go through top_k_recommendations one by one."""
+    Users are ranked batch_size at a time: those whose viewed half fits the window, at k <= 64, by the engine's test function
+    (it derives the exclusion from its input); deeper rankings and longer histories by RNNBase.top_k_batch, which hands the
+    engine the whole viewed half as an exclusion list."""
     predictor.load(model_file)
     evaluator = Evaluator(dataset, k=k)
     if get_full_recommendation_list:
         k = dataset.n_items
     start = time.perf_counter()
-    pending, results, order = [], {}, []
+    pending, deep, results, order = [], [], {}, []
+    # RNNCluster scores inside the user's cluster on the host and has no batched ranking; nor has a stand-in engine that offers
+    # the reference's three callables only (tests/test_cli_reference_golden.py)
+    batched_deep = getattr(predictor, "batched_top_k", False) and hasattr(predictor.engine, "rank")
 
     def flush():
         if not pending:
@@ -58,18 +62,35 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
         for (n, _, _), row in zip(pending, ids):
             results[n] = list(row[row >= 0])      # -1 = a place the row had no rankable item for (include/sbr_rnn.h)
         del pending[:]
+
+    def flush_deep():
+        if not deep:
+            return
+        ranked = predictor.top_k_batch([viewed for _, viewed, _ in deep], user_ids=[u for _, _, u in deep], k=k)
+        for (n, _, _), row in zip(deep, ranked):
+            results[n] = row
+        del deep[:]
     for n, (sequence, user_id) in enumerate(dataset.test_set(epochs=1)):
         num_viewed = int(len(sequence) / 2)
         viewed, goal = sequence[:num_viewed], [i[0] for i in sequence[num_viewed:]]
         if len(goal) == 0:
             raise ValueError
         order.append((n, goal))
-        if get_full_recommendation_list or k > 64 or len(viewed) > predictor.max_length or len(viewed) == 0:
+        # Two cases stay on the host, one user per call.  --save_rank: the reference's full list also holds the excluded ids, behind
+        # the ranked ones in numpy's partition order, and the rank comparison reads them; the engine never ranks an excluded id.
+        # An empty viewed half (a sequence of one item): a row of length 0 has only ever been scored by this one-row call, and a
+        # test set holds at most a handful of them.
+        if get_full_recommendation_list or len(viewed) == 0 or ((k > 64 or len(viewed) > predictor.max_length) and not batched_deep):
             results[n] = list(predictor.top_k_recommendations(viewed, user_id=user_id, k=k))
+        elif k > 64 or len(viewed) > predictor.max_length:
+            deep.append((n, viewed, user_id))
+            if len(deep) == predictor.batch_size:
+                flush_deep()
         else:
             pending.append((n, viewed, user_id))
             if len(pending) == predictor.batch_size:
                 flush()
+    flush_deep()
     flush()
     for n, goal in order:
         evaluator.add_instance(goal, results[n])

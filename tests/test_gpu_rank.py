@@ -1,0 +1,279 @@
+"""sbr_rank through RNNEngine.rank: ordered top-k of any depth with per-row exclusion lists, against (1) the existing
+sbr_topk call, id for id, and (2) a stable host sort of the very scores predict_function returns for a raw-score head.
+Every expected list is exact: np.lexsort((ids, -scores)) over the items that are neither excluded, NaN nor -inf."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+import parity_util as PU
+
+pytestmark = pytest.mark.gpu
+
+_SRC = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "sequence-based-recommendations_amd", "csrc",
+                         "sbr_common.h")).read()
+LDS_ROW = int(re.search(r"constexpr int kRankLdsRow = (\d+);", _SRC).group(1))
+SORT_LDS = int(re.search(r"constexpr int kRankSortLds = (\d+);", _SRC).group(1))
+
+
+def select_regime(N):
+    return 1 if N <= LDS_ROW else 2
+
+
+def sort_regime(k):
+    return 1 if k <= SORT_LDS else 2
+
+
+def make_engine(cell, layers, loss, N, B, T, S=0, seed=0, edit=None):
+    params, cfg, batch = PU.build_case(cell, layers, loss, N, B, T, S=S, seed=seed)
+    if edit is not None:
+        edit(params)
+    eng = PU.engine_for(cfg, N, B, T, S=S)
+    eng.set_all_param_values(params)
+    return eng, params, batch
+
+
+def window(batch, b):
+    return [int(i) for i in batch["X"][b, :int(batch["mask"][b].sum()), 0]]
+
+
+def expected_row(scores, excluded, k):
+    """(ids, scores) of the row's ranking to depth k, -1 / -inf behind the rankable items"""
+    ok = ~np.isnan(scores) & (scores > -np.inf)
+    ok[np.asarray(sorted(set(excluded)), dtype=np.int64)] = False
+    ids = np.nonzero(ok)[0]
+    ids = ids[np.lexsort((ids, -scores[ids]))][:k]
+    out_i = -np.ones(k, dtype=np.int32); out_s = np.full(k, -np.inf, dtype=np.float32)
+    out_i[:len(ids)] = ids; out_s[:len(ids)] = scores[ids]
+    return out_i, out_s
+
+
+def check_rank(eng, batch, scores, k, lists=None, exclude_input=True, N=None):
+    ids, sc = eng.rank(batch["X"], batch["mask"], k, exclude=lists, exclude_input=exclude_input, return_scores=True)
+    assert eng.query("rank_select") == select_regime(N) and eng.query("rank_sort") == sort_regime(k)
+    assert ids.shape == sc.shape == (scores.shape[0], k) and ids.dtype == np.int32 and sc.dtype == np.float32
+    for b in range(scores.shape[0]):
+        excl = (window(batch, b) if exclude_input else []) + ([] if lists is None or lists[b] is None else [int(i) for i in lists[b]])
+        ei, es = expected_row(scores[b], excl, k)
+        assert np.array_equal(ids[b], ei), (b, k, np.nonzero(ids[b] != ei)[0][:5], ids[b][:8], ei[:8])
+        assert np.array_equal(sc[b], es), (b, k)
+        assert not set(ids[b][ids[b] >= 0]) & set(excl)
+    return ids, sc
+
+
+# ------------------------------------------------------------------ 1. the same answer as sbr_topk
+SAME_CASES = [("GRU", [16], "CCE", 50, 19, 8, 0), ("LSTM", [20], "Blackout", 1000, 5, 6, 8),
+              ("GRU", [128], "CCE", 3706, 16, 4, 0), ("GRU", [8], "TOP1", 70001, 3, 2, 8)]
+
+
+@pytest.mark.parametrize("case", SAME_CASES, ids=lambda c: "%s%d-%s-N%d" % (c[0], c[1][0], c[2], c[3]))
+def test_same_ids_as_topk(case):
+    cell, layers, loss, N, B, T, S = case
+    eng, _, batch = make_engine(cell, layers, loss, N, B, T, S=S)
+    try:
+        for k in (1, 5, 64):
+            for excl in (True, False):
+                if k > N:       # neither call can rank deeper than the catalogue
+                    with pytest.raises(ValueError):
+                        eng.test_function((batch["X"], batch["mask"]), k=k, exclude_seen=excl)
+                    with pytest.raises(ValueError):
+                        eng.rank(batch["X"], batch["mask"], k, exclude_input=excl)
+                    continue
+                old = eng.test_function((batch["X"], batch["mask"]), k=k, exclude_seen=excl)
+                new = eng.rank(batch["X"], batch["mask"], k, exclude_input=excl)
+                assert eng.query("rank_select") == select_regime(N) and eng.query("rank_sort") == 1
+                assert np.array_equal(old, new), (k, excl, np.argwhere(old != new)[:5])
+    finally:
+        eng.close()
+
+
+def test_same_ids_as_topk_when_a_row_runs_out():
+    # the -1 places: a row that has seen 10 of 12 items (tests/test_gpu_edge_shapes.py)
+    N, B, T = 12, 3, 10
+    eng, _, _ = make_engine("GRU", [8], "CCE", N, B, T, seed=2)
+    try:
+        X = np.zeros((B, T, 1), np.int32); mask = np.zeros((B, T), np.float32)
+        X[0, :10, 0] = np.arange(10); mask[0, :10] = 1
+        X[1, :3, 0] = [4, 4, 5]; mask[1, :3] = 1
+        X[2, :1, 0] = [0]; mask[2, :1] = 1
+        for k in (1, 5, 12):
+            old = eng.test_function((X, mask), k=k)
+            new = eng.rank(X, mask, k)
+            assert np.array_equal(old, new), (k, old, new)
+        assert list(new[0][2:]) == [-1] * 10
+    finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------ 2. exact ranking beyond 64
+DEEP_CASES = [("LSTM", [20], "Blackout", 1000, 5, 6, 8), ("GRU", [16], "TOP1", 3706, 5, 4, 8), ("GRU", [8], "TOP1", 70001, 3, 2, 8)]
+
+
+def deep_ks(N):
+    return (65, 257, 1000, N)
+
+
+def test_deep_cases_reach_every_regime():
+    assert {select_regime(c[3]) for c in DEEP_CASES} == {1, 2}
+    assert {sort_regime(k) for c in DEEP_CASES for k in deep_ks(c[3])} == {1, 2}
+    assert 70001 > 65536 and 70001 % 2 == 1
+
+
+@pytest.mark.parametrize("case", DEEP_CASES, ids=lambda c: "%s-N%d" % (c[2], c[3]))
+def test_exact_ranking_beyond_64(case):
+    cell, layers, loss, N, B, T, S = case
+    eng, _, batch = make_engine(cell, layers, loss, N, B, T, S=S, seed=3)
+    try:
+        scores = eng.predict_function(batch["X"], batch["mask"])      # raw activations: the floats that are ranked
+        for k in deep_ks(N):
+            check_rank(eng, batch, scores, k, N=N)
+        check_rank(eng, batch, scores, N, exclude_input=False, N=N)
+    finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------ 3. ties
+@pytest.mark.parametrize("N", [1000, 40000])
+def test_ties_come_out_adjacent_in_ascending_id(N):
+    assert select_regime(1000) == 1 and select_regime(40000) == 2
+    B, T = 2, 4
+
+    def tie(params):
+        for j in (7, 900):
+            params[-2][:, j] = params[-2][:, 3]
+            params[-1][j] = params[-1][3]
+    eng, _, batch = make_engine("GRU", [8], "TOP1", N, B, T, S=8, seed=5, edit=tie)
+    try:
+        scores = eng.predict_function(batch["X"], batch["mask"])
+        for b in range(B):
+            s3, s7, s900 = (scores[b, j:j + 1].view(np.uint32)[0] for j in (3, 7, 900))
+            assert s3 == s7 == s900                                   # bitwise equal scores: what the test is about
+            full, _ = expected_row(scores[b], [], N)
+            p = int(np.nonzero(full == 3)[0][0])
+            assert list(full[p:p + 3]) == [3, 7, 900]
+            for k, inside in ((p + 1, [3]), (p + 2, [3, 7]), (p + 3, [3, 7, 900])):      # the cut falls inside the group
+                ids, _ = check_rank(eng, batch, scores, k, exclude_input=False, N=N)
+                assert list(ids[b][p:]) == inside
+                assert not (set((3, 7, 900)) - set(inside)) & set(ids[b])
+    finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------ 4. exclusion lists
+@pytest.mark.parametrize("N", [1000, 40000])
+def test_exclusion_lists(N):
+    B, T, k = 6, 6, 20
+    nan_item = 11
+
+    def nan_bias(params):
+        params[-1][nan_item] = np.nan                                 # a NaN score of that item in every row
+    eng, _, batch = make_engine("GRU", [8], "TOP1", N, B, T, S=8, seed=7, edit=nan_bias)
+    try:
+        scores = eng.predict_function(batch["X"], batch["mask"])
+        assert np.isnan(scores[:, nan_item]).all()
+        rng = np.random.default_rng(0)
+        keep = np.array([1, nan_item, 17, 29, 333, 640, N - 1])      # row 4: all but these seven are excluded
+        lists = [rng.permutation(N)[:300].astype(np.int32),           # 300 distinct ids
+                 np.array([5, 5, 9, 9, 9, 5, N - 1, 0], dtype=np.int32),      # duplicates
+                 np.zeros(0, dtype=np.int32),                         # empty
+                 np.arange(N, dtype=np.int32),                        # everything
+                 np.setdiff1d(np.arange(N), keep).astype(np.int32),   # fewer than k left
+                 None]
+        for excl_in in (True, False):
+            ids, sc = check_rank(eng, batch, scores, k, lists=lists, exclude_input=excl_in, N=N)
+            assert not (ids == nan_item).any()
+            assert (ids[3] == -1).all() and np.all(sc[3] == -np.inf)
+            left = [i for i in keep if i != nan_item and not (excl_in and i in window(batch, 4))]
+            assert sorted(ids[4][:len(left)]) == sorted(left) and (ids[4][len(left):] == -1).all()
+            assert (ids[[0, 1, 2, 5]] >= 0).all()
+        # far deeper than what rows 3 and 4 have left (N = 40000: in the scratch sort)
+        check_rank(eng, batch, scores, min(N, SORT_LDS + 100), lists=lists, N=N)
+    finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------ 5. errors leave a working engine
+def test_errors_leave_a_working_engine():
+    N, B, T = 1000, 4, 6
+    eng, _, batch = make_engine("GRU", [8], "TOP1", N, B, T, S=8, seed=8)
+    try:
+        scores = eng.predict_function(batch["X"], batch["mask"])
+        X, mask = batch["X"], batch["mask"]
+        good = [np.array([1, 2, 3], dtype=np.int32)] * B
+        bad_calls = [
+            lambda: eng.rank(X, mask, 0),
+            lambda: eng.rank(X, mask, N + 1),
+            lambda: eng.rank(X, mask, 10, exclude=[np.array([1, N], dtype=np.int32)] + good[1:]),
+            lambda: eng.rank(X, mask, 10, exclude=[np.array([-1], dtype=np.int32)] + good[1:]),
+            lambda: eng.rank_csr(B, 10, np.arange(8, dtype=np.int32), np.array([0, 4, 2, 6, 8], dtype=np.int64)),      # decreasing offsets
+            lambda: eng.rank_csr(B, 10, np.arange(8, dtype=np.int32), None),                                         # one pointer NULL
+            lambda: eng.rank_csr(B, 10, None, np.array([0, 1, 2, 3, 4], dtype=np.int64)),
+        ]
+        for i, call in enumerate(bad_calls):
+            with pytest.raises(ValueError):
+                call()
+            check_rank(eng, batch, scores, 70, lists=good, N=N)
+        import ctypes
+        out = np.empty((B, 10), dtype=np.int32)      # the library's own range check of k (the binding checks it first)
+        for k in (0, N + 1):
+            assert eng.lib.sbr_rank(eng.h, k, 1, None, None, ctypes.c_void_p(out.ctypes.data), None) == -1
+        check_rank(eng, batch, scores, 70, lists=good, N=N)
+    finally:
+        eng.close()
+
+
+def test_no_batch_is_a_state_error():
+    import ctypes
+    from sbr_amd.engine import SbrError
+    N, B, T = 50, 4, 4
+    eng, _, batch = make_engine("GRU", [8], "CCE", N, B, T)
+    try:
+        out = np.empty((B, 5), dtype=np.int32)
+        assert eng.lib.sbr_rank(eng.h, 5, 1, None, None, ctypes.c_void_p(out.ctypes.data), None) == -4      # SBR_ESTATE
+        with pytest.raises(SbrError):
+            eng.rank_csr(B, 5)
+    finally:
+        eng.close()
+
+
+# ------------------------------------------------------------------ 6. no side effects
+@pytest.mark.parametrize("case", [("GRU", [16], "CCE", 200, 19, 8, 0), ("GRU", [16], "TOP1", 1000, 8, 6, 8)], ids=["CCE", "TOP1"])
+def test_rank_changes_nothing(case):
+    """rank(), then a training step: the cost and every parameter bitwise equal to those of an engine that never ranked.
+
+    The comparison is bitwise, so the step itself has to be repeatable bit for bit, and on a batch in which an item repeats it is
+    not: the input-weight gradient rows of a repeated item are added with float atomics in an order that is not fixed (DESIGN.md,
+    "deterministic up to the order of those few additions"), and two engines that never ranked then differ in the last bit of a
+    few of those rows -- measured on GRU[16] CCE N=50 B=19 T=8, where 152 positions share 50 items.  So no item occurs twice in
+    this batch (inputs, targets and samples are cut from one permutation of the catalogue, N >= B*T + B + S): every destination
+    then gets a single addition and the step has one result, which a ranking call before it must not change."""
+    cell, layers, loss, N, B, T, S = case
+
+    def train(eng, batch):
+        if loss == "CCE":
+            return eng.train_function(batch["X"], batch["mask"], batch["target"], batch["pop"])
+        return eng.train_function(batch["X"], batch["mask"], batch["target"], batch["samples"], batch["pop"])
+    ranked, params, batch = make_engine(cell, layers, loss, N, B, T, S=S, seed=9)
+    plain, _, _ = make_engine(cell, layers, loss, N, B, T, S=S, seed=9)
+    perm = np.random.default_rng(9).permutation(N).astype(np.int32)
+    batch["X"][:, :, 0] = perm[:B * T].reshape(B, T)
+    if S:
+        batch["target"][:] = perm[B * T:B * T + B]
+        batch["samples"][:] = perm[B * T + B:B * T + B + S]
+    used = np.concatenate([batch["X"].ravel()] + ([batch["target"], batch["samples"]] if S else []))
+    assert len(set(used.tolist())) == len(used) and batch["mask"].sum() > B
+    try:
+        lists = [np.arange(b, b + 20, dtype=np.int32) for b in range(B)]
+        a = ranked.rank(batch["X"], batch["mask"], 30, exclude=lists, return_scores=True)
+        b = ranked.rank(batch["X"], batch["mask"], 30, exclude=lists, return_scores=True)
+        assert np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])
+        ranked.rank(batch["X"], batch["mask"], N)
+        for p, q in zip(ranked.get_all_param_values(), plain.get_all_param_values()):
+            assert np.array_equal(p, q)
+        cost_r, cost_p = train(ranked, batch), train(plain, batch)
+        assert np.float32(cost_r).tobytes() == np.float32(cost_p).tobytes()
+        for p, q in zip(ranked.get_all_param_values(), plain.get_all_param_values()):
+            assert p.tobytes() == q.tobytes()
+    finally:
+        ranked.close(); plain.close()
