@@ -721,6 +721,18 @@ static int tail_plan(sbr_handle* h, int* ch_out) {
     return nc;
 }
 
+// The one place where the epoch of the chain's progress words advances: once per step, in front of whatever is launched first
+// with it -- the gate at the head of the side stream (sbr_loss_backward_output) or the chain (sbr_backward_recurrent).
+static int tail_next_epoch(sbr_handle* h) {
+    h->prog_epoch = (h->prog_epoch + 1) & 0x7FFFF; if (!h->prog_epoch) h->prog_epoch = 1;
+    return h->prog_epoch;
+}
+// the chain's progress words of this step's overlapped tail, one per wave of rec_bwd_x6p
+static int* tail_words(sbr_handle* h, int* nwaves) {
+    *nwaves = (h->lay.Bp / rec_args(h, 0).rpt) * 8;
+    return (int*)h->A(h->lay.a_prog);
+}
+
 // behind the time-chunked sort of an overlapped tail (second side stream): the running cost of the ids, for the LDS-row scatter-add
 static int tail_cost_scan(sbr_handle* h) {
     const Layout& y = h->lay;
@@ -1019,6 +1031,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
     if (R < y.Bp) SBR_HIP(hipMemsetAsync(h->A(y.a_dhlast), 0, (size_t)y.Bp * Hp * sizeof(float), s));   // padded rows carry no gradient
     h->side_pending = true;
     h->fill_done = false;
+    h->tail_gated = false; h->last_tail_gated = 0;
     // Work on the side stream that needs only the batch: the sentinel fill of the cluster BPTT kernels' exchange arrays and
     // the sort for the embedding scatter-add (the scatter kernel waits for ev_sort).  With cluster kernels it starts now,
     // beside the output phase (its own fork event); otherwise it rides behind the ev_lg wait the side stream needs anyway
@@ -1040,7 +1053,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         if (h->tail_nc >= 2) {
             // overlapped tail: the time-chunked sort runs on the SECOND side stream, which consumes it (scatter-add beside the
             // chain); that stream is released by the same record as the first one
-            if (h->ev_lg_rec) SBR_HIP(hipStreamWaitEvent(h->side2, h->ev_lg_rec, 0));      // (NULL: the head's flag form -- the sort ran
+            if (h->ev_lg_rec) SBR_HIP(hipStreamWaitEvent(h->side2, h->ev_lg_rec, 0));      // (NULL: released by the gate -- the sort ran
                                                                                         // beside the forward chain, the consumers wait for the chain's progress words)
             if (!h->tail_sorted) {
                 SBR_LAUNCH(launch_scatter_sort(h->side2, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, (int*)h->A(y.a_scnt),
@@ -1065,6 +1078,26 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         SBR_HIP(hipStreamWaitEvent(sd, h->ev_fork, 0));
         const int rc = side_batch_work(); if (rc != SBR_OK) return rc;
     }
+    // What releases the side stream once this phase's main-stream work (the head, dh) is enqueued: one record at the end of it,
+    // which is also the timing mark in front of rec_bwd.  Single-call step with the overlapped tail: no record.  The BPTT chain is
+    // ordered behind this phase on the main stream and publishes progress words of this step's epoch, so a gate on those words
+    // at the HEAD of the side stream releases it once the head is complete (tail_gate_wave_kernel, sbr_misc.hip) -- what the
+    // second side stream does anyway -- and the chain starts without the record's 10 us in front of it.  The
+    // record stays for phase-by-phase callers, SBR_TAIL_OVERLAP=2, steps without the overlapped tail and a timing mark there.
+    auto release_side = [&]() -> int {
+        const bool mark3 = h->timing && ((h->timing_marks >> 3) & 1) && h->ev[h->ring_cur][3];
+        if (kTailGateFirst && h->in_train_step && h->tail_nc >= 2 && h->sw.tail_overlap == 1 && h->tail_sorted && y.L == 1 && y.D == 1 && !fill_needed && !mark3) {
+            int nwaves = 0;
+            int* words = tail_words(h, &nwaves);
+            SBR_LAUNCH(launch_tail_gate_wave(sd, words, nwaves, tail_next_epoch(h), y.T, (int*)h->A(y.a_fault)));
+            h->tail_gated = true;
+            h->ev_lg_rec = nullptr; h->ev_step_rec = h->ev_fork; h->lg_seq = h->batch_seq;      // (ev_fork: sbr_forward, in front of the sort)
+        } else {
+            h->ev_lg_rec = h->ev_step_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
+            SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
+        }
+        return SBR_OK;
+    };
     if (y.cfg.loss == SBR_LOSS_CCE || SBR_LOSS_IS_MARGIN(y.cfg.loss)) {      // dense heads: full softmax, or RNNMargin's linear layer
         float* lg = h->A(y.a_logits);
         const int Nl = (N + 3) & ~3;               // row stride of the logits / dlogits buffer
@@ -1109,10 +1142,8 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
                                fold ? &keep : nullptr));
         }
         h->dh_slabs_n = keep;
-        // beside the BPTT chain: cost, db_out (+ bias regulariser), dW_out^T [N][Hp] = dlogits^T . h.  One record at the end
-        // of this phase's main-stream work releases the side stream and is the timing mark in front of rec_bwd.
-        h->ev_lg_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
-        SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
+        // beside the BPTT chain: cost, db_out (+ bias regulariser), dW_out^T [N][Hp] = dlogits^T . h
+        { const int rc = release_side(); if (rc != SBR_OK) return rc; }
         if (!fill_needed) { const int rc = side_batch_work(); if (rc != SBR_OK) return rc; }
         // Single-call step without a bias regulariser: the output layer's gradient, its step and the batch cost in ONE launch
         // (launch_out_grad_step, sbr_misc.hip) instead of the five or six below -- the polling weight-gradient GEMM of the overlapped
@@ -1184,8 +1215,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
         // and the scatter of the cells' gradients (5 launches, ~75 us at C3 beside the side stream's sort) leave the main stream: dh
         // first, one record, the rest on the side stream beside the chain (as the dense heads always did).
         if (!head1) SBR_LAUNCH(launch_gemm(s, act, C, 1, Wc, Hp, 1, h->A(y.a_dhlast), Hp, R, Hp, C, nullptr, nullptr, 0, sg));
-        h->ev_lg_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
-        SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
+        { const int rc = release_side(); if (rc != SBR_OK) return rc; }
         SBR_LAUNCH(launch_sum_cost(sd, h->A(y.a_rowcost), R, h->cost_ptr()));
         SBR_LAUNCH(launch_colsum_bias(sd, act, R, C, C, dbc, nullptr, 0.0f, nullptr, h->A(y.a_csum)));
         SBR_LAUNCH(launch_gemm(sd, act, 1, C, hl, Hp, 1, dWc, Hp, C, Hp, R, nullptr, nullptr, 0, sg));
@@ -1297,11 +1327,13 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                 SBR_HIP(hipStreamWaitEvent(s, h->ev_tail2, 0));
             }
             const bool gru = y.cfg.cell == SBR_CELL_GRU;
-            int* words = (int*)h->A(y.a_prog);
-            const int nwaves = (y.Bp / a.rpt) * 8;
+            int nwaves = 0;
+            int* words = tail_words(h, &nwaves);
             int* done = (int*)h->A(y.a_done);
-            h->prog_epoch = (h->prog_epoch + 1) & 0x7FFFF; if (!h->prog_epoch) h->prog_epoch = 1;
-            a.progress = words; a.prog_every = kTailPubEvery; a.prog_epoch = h->prog_epoch;
+            // (the side stream's gate of this step may already wait for the epoch: sbr_loss_backward_output)
+            const bool gated = h->tail_gated && !serial;
+            h->tail_gated = false; h->last_tail_gated = gated;
+            a.progress = words; a.prog_every = kTailPubEvery; a.prog_epoch = gated ? h->prog_epoch : tail_next_epoch(h);
             const int K = y.T * y.Bp;
             const int cap = (int)std::min<size_t>(256, y.ws2_floats / slab);
             SbrPoll pl{words, nwaves, done, a.prog_epoch, y.Bp, a.fault, 0, 0, h->tail_trace, nullptr, 0};
@@ -1331,7 +1363,7 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
             // ... unless the scatter-add launch carries it (default where that launch is the LDS-row one and has its own stream)
             const bool mon_in_units = !serial && h->tail_cost_scanned;
             if (!mon_in_units) SBR_LAUNCH(launch_tail_monitor(serial ? s : h->side3, pl, a.t_lo));
-            SBR_LAUNCH(launch_tail_gate(sd, words, nwaves, a.prog_epoch, y.T, a.fault));
+            if (!gated) SBR_LAUNCH(launch_tail_gate(sd, words, nwaves, a.prog_epoch, y.T, a.fault));      // (else: at the head of this stream)
             {
                 hipError_t we = hipSuccess;
                 if (!launch_gemm_slabs_x6_poll(sd, h->A(ly.a_hs), 1, ly.Hp, a.dxt, GHp, 1, ly.Hp, GHp, K, ws2, n_slabs, GHp, slab,
@@ -1340,7 +1372,10 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                 }
                 SBR_LAUNCH(we);
             }
-            if (!serial) SBR_LAUNCH(launch_tail_gate(s2, words, nwaves, a.prog_epoch, y.T, a.fault));
+            // (the second side stream: behind the record where there is one; without it this gate is on the chip from the sort's
+            // end on, beside the forward chain and the head -- the one-wave form there too)
+            if (gated) SBR_LAUNCH(launch_tail_gate_wave(s2, words, nwaves, a.prog_epoch, y.T, a.fault));
+            else if (!serial) SBR_LAUNCH(launch_tail_gate(s2, words, nwaves, a.prog_epoch, y.T, a.fault));
             // (tried and dropped: the last time chunk as a launch of its own behind the polling one, one wave per 16 entries on the
             // then idle chip -- the hot rows' atomics serialise there: 23 us for 6400 entries, profiles/round3_variants.txt call d)
             hipError_t se = hipSuccess;
@@ -2106,6 +2141,7 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     // what the LAST step launched for the gradient of layer 0's index-input rows (-1: no step yet): 0 sorted segment reduce, 1 range form,
     // 2 segment-parallel form, 3 per-element atomics (SBR_FLAG_ATOMIC_SCATTER), 4 / 5 the overlapped tail's polling reduce / LDS-row kernel
     else if (w == "scatter_form") *value = h->last_scatter_form;
+    else if (w == "tail_gate_first") *value = h->last_tail_gated;      // the last step's side stream: 1 released by the gate at its head, 0 by a record
     // what the LAST sbr_rank ran (0: none yet): its select with the row's keys in LDS (1) or streamed (2), its sort in LDS (1) or in scratch (2)
     else if (w == "rank_select") *value = h->last_rank_select;
     else if (w == "rank_sort") *value = h->last_rank_sort;

@@ -640,7 +640,7 @@ extern "C" int sbr_build_batch(sbr_handle* h, sbr_dataset* d, int64_t batch, uin
     // batch i+1 while step i runs and the device packs it beside the step (two small launches, 20 - 30 us that used to sit between
     // two steps; tools/bench_train_loop.py).  Order: (1) the set it overwrites was read by the step before the one in flight --
     // every stream of a completed step is joined into the main stream by sbr_apply_update, so any main-stream record made DURING
-    // the step in flight is behind it: the step records one anyway (ev_lg, in front of the BPTT chain), no extra record on the
+    // the step in flight is behind it: the step records one anyway (ev_lg in front of the BPTT chain, or the forward's fork: sbr_handle.ev_step_rec), no extra record on the
     // main stream; (2) without such a record (first batches, evaluation between steps, a step abandoned half way) the build
     // waits for a fresh record on each of the engine's streams; (3) the main stream waits for the build (long complete by then).
     // The dataset's own arrays change only inside calls that synchronise d->stream first and last, i.e. behind (3).
@@ -648,8 +648,8 @@ extern "C" int sbr_build_batch(sbr_handle* h, sbr_dataset* d, int64_t batch, uin
     const int set = h->bb_set ^ 1;
     if (h->train_fwd_open) h->bb_slow = 2;
     if (h->bb_unread && h->bb_slow == 0) h->bb_slow = 1;      // two builds and no forward between them: whoever read the first did it outside a step
-    if (h->bb_slow == 0 && h->ev_lg_rec && h->lg_seq > h->set_use[set]) {
-        SBR_HIP(hipStreamWaitEvent(s, h->ev_lg_rec, 0));
+    if (h->bb_slow == 0 && h->ev_step_rec && h->lg_seq > h->set_use[set]) {
+        SBR_HIP(hipStreamWaitEvent(s, h->ev_step_rec, 0));
     } else {
         hipStream_t all[4] = {h->stream, h->side, h->side2, h->side3};
         for (hipStream_t q : all) { SBR_HIP(hipEventRecord(h->ev_bbw, q)); SBR_HIP(hipStreamWaitEvent(s, h->ev_bbw, 0)); }

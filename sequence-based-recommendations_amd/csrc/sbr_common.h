@@ -156,6 +156,9 @@ constexpr int kTailScatterUnits = 192;    // ... and its workgroups (the CUs the
 constexpr int kTailGemmGroups = 64;       // persistent groups of the polling dW_hid GEMM (one partial each)
 constexpr int kTailSlabMax = 512;         // rows of its largest K slab
 constexpr double kTailSlabGrowth = 0.35;  // k steps of a slab per time step of lead (sbr_tail_slab_table)
+// the side stream of a single-call step (profiles/tail_release_variants.txt):
+constexpr bool kTailGateFirst = true;     // released by the chain's progress words (a one-wave gate at its head) instead of a main-stream record
+constexpr int kTailGateSleep = 32;        // ... whose polls of ONE word are this many s_sleep units (64 clocks each) apart until the chain appears
 // growth of the small time chunks near t = 0 (tail_plan, sbr_api.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
 // walks them one after the other; 1, 3, 7, 18 for the polling range form
 static inline double sbr_tail_geom(int scatter_lds) { return scatter_lds ? 1.6 : 2.6; }
@@ -253,11 +256,14 @@ struct sbr_handle {
     bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
     // sbr_rank: scratch outside the arena (grown on demand, freed by sbr_destroy) and what the last call ran (sbr_query "rank_select" / "rank_sort")
     void* rank_scratch = nullptr; size_t rank_scratch_bytes = 0; int last_rank_select = 0, last_rank_sort = 0;
+    int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
     bool tail_cost_scanned = false;                                       // this step's sort was followed by launch_scatter_cost_scan
     int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
     std::vector<int> tail_slab_host; int* tail_slab_dev = nullptr; int tail_slab_key[2] = {0, 0};   // the table of the last plan
-    int prog_epoch = 0;
+    int prog_epoch = 0;          // epoch of the chain's progress words: advanced once per step by tail_next_epoch (sbr_api.hip)
+    bool tail_gated = false;     // this step: the side stream is already behind a gate on this step's epoch (sbr_loss_backward_output)
+    hipEvent_t ev_step_rec = nullptr; // a main-stream record made DURING the step in flight, for sbr_build_batch: ev_lg_rec, or the forward's fork
     bool tail_updated = false;   // this step: the overlapped tail has applied the optimizer itself (single-call step)
     bool tail_join_pending = false; // overlapped tail of a phase-by-phase step: the main stream has not joined the consumer streams yet
     bool step_open = false;      // sbr_zero_grads has opened a training step (cleared by sbr_forward)
@@ -330,6 +336,8 @@ hipError_t launch_scatter_sort(hipStream_t s, const int* X, const int* len, int 
 int sbr_scatter_lds_ids();     // largest key space the LDS-histogram sort takes
 // overlapped step tail: wait (bounded) until every progress word of the running BPTT chain is (epoch, <= target)
 hipError_t launch_tail_gate(hipStream_t s, const int* progress, int n, int epoch, int target, int* fault);
+// ... the same wait as ONE wave that may be launched long before the chain (it sits beside the forward chain and the head)
+hipError_t launch_tail_gate_wave(hipStream_t s, const int* progress, int n, int epoch, int target, int* fault);
 // emb[t][b][f*Ep + e] = W_emb[X[b][t][f]][e]          (lasagne EmbeddingLayer + flatten(outdim=3), recurrent_layers.py:48)
 hipError_t launch_gather_concat(hipStream_t s, const float* Wemb, const int* X, float* out, int T, int Bp, int F, int Ep);
 // --r_bi helpers (sbr_misc.hip).  rev(t, len) = t < len ? len-1-t : t (padding stays in place).

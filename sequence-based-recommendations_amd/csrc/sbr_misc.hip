@@ -1362,6 +1362,37 @@ hipError_t launch_tail_gate(hipStream_t s, const int* progress, int n, int epoch
     return hipGetLastError();
 }
 
+// The same gate for the HEAD of the side stream of a single-call step (sbr_loss_backward_output): it is launched in front of the
+// chain and is on the chip while the forward chain and the head run, so it is one wave without LDS.  Until the chain appears
+// it polls ONE word, kTailGateSleep sleep units apart (a load per microsecond); then its lanes read all n words at once,
+// eight loads in flight each, until every one is of this epoch.  A word of this epoch means that the chain has started, i.e. that
+// everything in front of it on the main stream is complete and written back; a word the step before left carries the epoch
+// before.  The bound and the fault bit are tail_gate_kernel's: a chain that never comes (an error return between the two
+// phases) ends the wait by itself.
+__global__ void __launch_bounds__(64) tail_gate_wave_kernel(const int* __restrict__ progress, int n, int epoch, int target, int* __restrict__ fault) {
+    const unsigned long long t0 = wall_clock64();
+    auto passed = [&](int v) { return (v >> 12) == epoch && (v & 0xfff) <= target; };
+    for (;;) {
+        if (passed(__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) break;
+        if (wall_clock64() - t0 > SBR_POLL_TICKS) { if (threadIdx.x == 0) atomicOr(fault, 8); return; }
+        __builtin_amdgcn_s_sleep(kTailGateSleep);
+    }
+    for (;;) {
+        bool ok = true;
+#pragma unroll 8
+        for (int i = 0; i < n; i += 64)      // (uniform trip count, the index clamped: nothing between the loads)
+            ok = passed(__hip_atomic_load(progress + min(i + (int)threadIdx.x, n - 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) && ok;
+        if (__all(ok)) break;
+        if (wall_clock64() - t0 > SBR_POLL_TICKS) { if (threadIdx.x == 0) atomicOr(fault, 8); return; }
+        __builtin_amdgcn_s_sleep(8);
+    }
+}
+hipError_t launch_tail_gate_wave(hipStream_t s, const int* progress, int n, int epoch, int target, int* fault) {
+    if (n < 1) return hipErrorInvalidValue;
+    tail_gate_wave_kernel<<<1, 64, 0, s>>>(progress, n, epoch, target, fault);
+    return hipGetLastError();
+}
+
 // triage fallback: per-element float atomics (SBR_FLAG_ATOMIC_SCATTER)
 __global__ void scatter_rows_kernel(float* __restrict__ dWin, const f32x4* __restrict__ dxt, const int* __restrict__ X,
                                     const int* __restrict__ len, int T, int Bp, int F, int R4) {
