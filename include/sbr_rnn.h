@@ -256,6 +256,30 @@ int sbr_cluster_select(sbr_cluster* c, const float* h_dev, int ld_h, int off2, i
 /* scores_dev[r][n] *= hard[n][csel[r]] (NULL: skip), n_used_dev[r] = sum_n hard[n][csel[r]] (NULL: skip) */
 int sbr_cluster_mask_scores(sbr_cluster* c, float* scores_dev, int ld, int rows, const int32_t* csel_dev, float* n_used_dev);
 int sbr_cluster_hard(sbr_cluster* c, float* hard_host);                                          /* [N][C] = _get_hard_clusters() */
+/* Ranking inside each row's item cluster on the device (added under ABI 11: two symbols, no struct change) -- the batched form of
+ * RNNCluster.predict_function / top_k_recommendations (rnn_cluster.py:302-325, :461-487; test.py:61-76).
+ * sbr_cluster_lists: the hard clusters of prepare_tests (rnn_cluster.py:440-466; NOT the f(100 R) of sbr_cluster_hard) as a CSR over
+ * the clusters.  members(c) holds every item i with R[i][c] > 0, and every item without a positive entry whose fallback cluster is c:
+ * the reference's scan (best = 0, best_val = R[i][0]; in order, only R[i][j] > best_val replaces it; NaN compares false).  Lists are
+ * ascending in id; an item may sit in several, a list may be empty.  Built on the device from R on first use and kept until R changes
+ * (sbr_cluster_set_params, sbr_cluster_apply_update).  sizes_host [C]; members_host NULL, or [sum of sizes]: list 0, list 1, ... */
+int sbr_cluster_lists(sbr_cluster* c, int32_t* sizes_host, int32_t* members_host);
+/* For every row r < n_rows of the batch set on engine h (a forward is run if none has been): the row's cluster
+ * c = argmax_j (u_r . Wc)[j] (what sbr_cluster_select returns), the scores h_last[r] . W_out^T[i] + b_out[i] of i in members(c) only,
+ * and their ordered top-k.  Exclusion (exclude_input, excl_ids / excl_off), validation, k, the order of the result, its -1 / -inf
+ * places (also k above the cluster's size, and an empty cluster) and the scratch are those of sbr_rank above; an excluded id outside the
+ * row's cluster is ignored.  On the default projection a score is the very float sbr_rank ranks for (r, i), so the result equals
+ * sbr_rank's filtered to members(c) -- bit for bit.
+ *   ids_host      [n_rows][k];  scores_host  NULL or [n_rows][k]
+ *   cluster_host  NULL or [n_rows]: the selected cluster;  size_host  NULL or [n_rows]: len(members(c)) before exclusion (the reference's
+ *                 number of scored items, test.py:73-76)
+ * c and h must agree in n_items, in the width and split of the user representation and in the stream (SBR_EINVAL); no batch set:
+ * SBR_ESTATE.  Parameters, gradients and optimizer state stay untouched beyond bringing lazily stepped output rows up to date.
+ * Two forms: 1 scores only the members (default); 2 runs the full projection and picks the members' scores out of it -- taken with
+ * SBR_CLUSTER_RANK=0 in the environment at the engine's creation, with SBR_FLAG_BF16_PROJECTION and with SBR_FLAG_SIMPLE_GEMM.
+ * sbr_query "cluster_rank_form" tells which the last call took (0: none yet), "rank_select" / "rank_sort" its regimes. */
+int sbr_cluster_rank(sbr_cluster* c, sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
+                     int32_t* ids_host, float* scores_host, int32_t* cluster_host, int32_t* size_host);
 
 /* predict_function(X, mask) (rnn_base.py:188-194) on the current batch: scores (rows,N);
  * softmax probabilities for CCE (DenseLayer softmax, rnn_one_hot.py:65), raw activations

@@ -357,6 +357,7 @@ static SbrSwitches sbr_read_switches() {
     if (const char* e = getenv("SBR_HEAD_WAIT_TICKS")) sw.head_wait_ticks = strtoull(e, nullptr, 10);
     sw.out_fuse = flag("SBR_OUT_FUSE", sw.out_fuse);
     sw.row_aware = flag("SBR_ROW_AWARE_UPDATE", sw.row_aware);
+    sw.cluster_rank = flag("SBR_CLUSTER_RANK", sw.cluster_rank);
     return sw;
 }
 
@@ -1990,6 +1991,85 @@ extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* 
     return check_fault(h);          // a forward that gave up must not hand out rankings
 }
 
+// Ranking inside each row's item cluster (RNNCluster.predict_function for a whole batch, rnn_cluster.py:302-325; kernels and the
+// accumulation-order argument: sbr_cluster_rank.hip).  The member lists are the cluster object's, everything a call needs beyond
+// them sits in the handle's ranking scratch.
+extern "C" int sbr_cluster_rank(sbr_cluster* c, sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
+                                int32_t* ids_host, float* scores_host, int32_t* cluster_host, int32_t* size_host) {
+    CHECK_ARG(c && h && ids_host, "null argument");
+    if (!h->have_batch) { sbr_set_error("sbr_cluster_rank: no batch set"); return SBR_ESTATE; }
+    const Layout& y = h->lay;
+    const int rows = h->n_rows, C = c->cfg.n_clusters, HL = y.cfg.layers[y.L - 1];
+    CHECK_ARG(c->cfg.n_items == y.N, "the cluster head has %d items, the engine %d", c->cfg.n_items, y.N);
+    CHECK_ARG(c->cfg.n_hidden == y.D * HL && c->cfg.hidden_split == HL, "the cluster head reads %d features (split %d), the engine's user representation has %d (split %d)",
+              c->cfg.n_hidden, c->cfg.hidden_split, y.D * HL, HL);
+    CHECK_ARG(c->stream == h->stream, "the cluster head and the engine are on different streams");
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    CHECK_ARG((excl_ids == nullptr) == (excl_off == nullptr), "excl_ids and excl_off: both or neither");
+    int64_t n_excl = 0;
+    if (excl_off) {         // everything about the lists is checked here, before anything is launched
+        CHECK_ARG(excl_off[0] >= 0, "excl_off[0] = %lld is negative", (long long)excl_off[0]);
+        for (int r = 0; r < rows; ++r)
+            CHECK_ARG(excl_off[r + 1] >= excl_off[r], "excl_off decreases at row %d (%lld -> %lld)", r, (long long)excl_off[r], (long long)excl_off[r + 1]);
+        for (int64_t j = excl_off[0]; j < excl_off[rows]; ++j)
+            CHECK_ARG(excl_ids[j] >= 0 && excl_ids[j] < y.N, "excluded id %d outside [0,%d)", excl_ids[j], y.N);
+        n_excl = excl_off[rows] - excl_off[0];
+    }
+    int rc;
+    if ((rc = sbr_cluster_build_lists(c)) != SBR_OK) return rc;      // (cached until R changes: sizes and Lmax are host values)
+    const int lmax = c->lmax, kk = std::min(k, lmax);
+    const bool radix = kk > kRankSortLds;
+    const size_t rk = (size_t)rows * k, rkk = (size_t)rows * kk;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_off = take((size_t)(rows + 1) * sizeof(long long)), o_eid = take((size_t)n_excl * sizeof(int));
+    const size_t o_csel = take((size_t)rows * sizeof(int)), o_grp = take(sbr_crk_group_words(rows, C) * sizeof(int));
+    const size_t o_cs = take((size_t)rows * lmax * sizeof(float));
+    const size_t o_nsel = take((size_t)rows * sizeof(int));
+    const size_t o_k0 = take(rkk * sizeof(unsigned)), o_i0 = take(rkk * sizeof(int));
+    const size_t o_k1 = take(radix ? rkk * sizeof(unsigned) : 0), o_i1 = take(radix ? rkk * sizeof(int) : 0);
+    const size_t o_pos = take(rkk * sizeof(int)), o_psc = take(rkk * sizeof(float));
+    const size_t o_oid = take(rk * sizeof(int)), o_osc = take(rk * sizeof(float)), o_size = take((size_t)rows * sizeof(int));
+    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    int* csel = (int*)(S + o_csel);
+    float* cs = (float*)(S + o_cs);
+    // the restricted kernel restates the exact-f32 projection; the bf16 and the triage projections round differently, and their
+    // scores are gathered from the matrix those kernels write
+    const bool restricted = h->sw.cluster_rank && !(y.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
+    if (restricted) {
+        if (!h->fwd_done && (rc = sbr_forward(h)) != SBR_OK) return rc;
+        if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;      // the sampled heads step W_out^T / b_out rows lazily: every member row must be current
+    } else if ((rc = full_scores(h, 0)) != SBR_OK) return rc;
+    if (excl_off) {
+        std::vector<long long> off((size_t)rows + 1);
+        for (int r = 0; r <= rows; ++r) off[r] = (long long)(excl_off[r] - excl_off[0]);
+        SBR_HIP(hipMemcpyAsync(S + o_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+        if (n_excl) SBR_HIP(hipMemcpyAsync(S + o_eid, excl_ids + excl_off[0], (size_t)n_excl * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        SBR_HIP(hipStreamSynchronize(h->stream));           // `off` goes out of scope
+    }
+    if ((rc = sbr_cluster_select(c, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, rows, csel, nullptr)) != SBR_OK) return rc;
+    if (restricted) {
+        SBR_LAUNCH(launch_crk_group(h->stream, csel, rows, C, (int*)(S + o_grp)));
+        SBR_LAUNCH(launch_crk_score(h->stream, h_last(h), y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, c->mem_ids, c->mem_off,
+                                    (const int*)(S + o_grp), rows, C, lmax, cs));
+    } else
+        SBR_LAUNCH(launch_crk_gather(h->stream, h->A(y.a_logits), y.N, csel, c->mem_ids, c->mem_off, rows, lmax, cs));
+    h->last_cluster_rank_form = restricted ? 1 : 2;
+    SBR_LAUNCH(launch_crk_exclude(h->stream, cs, lmax, csel, c->mem_ids, c->mem_off, rows, y.N, excl_off ? (const int*)(S + o_eid) : nullptr,
+                                  excl_off ? (const long long*)(S + o_off) : nullptr, exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
+    SBR_LAUNCH(launch_rank_select(h->stream, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
+    SBR_LAUNCH(launch_rank_sort(h->stream, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
+                                (const int*)(S + o_nsel), (int*)(S + o_pos), (float*)(S + o_psc), &h->last_rank_sort));
+    SBR_LAUNCH(launch_crk_translate(h->stream, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
+                                    (int*)(S + o_oid), (float*)(S + o_osc), (int*)(S + o_size)));
+    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (cluster_host) SBR_HIP(hipMemcpyAsync(cluster_host, csel, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (size_host) SBR_HIP(hipMemcpyAsync(size_host, S + o_size, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return check_fault(h);          // a forward that gave up must not hand out rankings
+}
+
 // ---------------------------------------------------------------------------------------
 // debug / timing
 // ---------------------------------------------------------------------------------------
@@ -2145,6 +2225,8 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     // what the LAST sbr_rank ran (0: none yet): its select with the row's keys in LDS (1) or streamed (2), its sort in LDS (1) or in scratch (2)
     else if (w == "rank_select") *value = h->last_rank_select;
     else if (w == "rank_sort") *value = h->last_rank_sort;
+    // the LAST sbr_cluster_rank: 0 none yet, 1 only the members of each row's cluster were scored, 2 they were gathered from the full scores
+    else if (w == "cluster_rank_form") *value = h->last_cluster_rank_form;
     else if (w == "row_aware_update") *value = h->last_row_aware ? 1 : 0;      // ... and whether its optimizer pass over W_in was the row-aware one
     else if (w == "cluster") { RecArgs a = rec_args(h, (y.L - 1) * y.D); *value = (!simple_rec(h) && sbr_rec_cluster_ok(a)) ? 1 : 0; }
     else if (w == "rec_kernel") {   // family serving the top layer: 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other

@@ -18,20 +18,6 @@
 #include <new>
 #include "sbr_common.h"
 
-struct sbr_cluster {
-    sbr_cluster_config cfg;
-    hipStream_t stream;
-    float *R, *Wc, *dR, *dWc, *sR[2], *sWc[2];       // parameters, gradients, optimizer state
-    float *z, *p, *M, *sm, *sg, *score, *dz, *rowcost, *ones, *cost, *hard, *nused;
-    int* ids;
-    long step;
-    float scale;
-    unsigned long long noise_ctr;
-    int J;                                           // cells of the last forward (B + samples)
-    int hard_valid;
-    int dR_clean;                                    // dR is all zeros: the optimizer kernel clears every gradient it consumes (no N x C memset per step)
-};
-
 extern void sbr_set_error(const char* fmt, ...);
 #define CL_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { sbr_set_error("%s: %s", #x, hipGetErrorString(e_)); return SBR_EHIP; } } while (0)
 #define CL_ARG(c, ...) do { if (!(c)) { sbr_set_error(__VA_ARGS__); return SBR_EINVAL; } } while (0)
@@ -232,6 +218,7 @@ extern "C" sbr_cluster* sbr_cluster_create(const sbr_cluster_config* cfg, void* 
     sbr_cluster* k = new (std::nothrow) sbr_cluster();
     if (!k) return nullptr;
     k->cfg = c; k->stream = (hipStream_t)stream; k->step = 0; k->scale = c.scale; k->noise_ctr = 0; k->J = 0; k->hard_valid = 0; k->dR_clean = 0;
+    k->lists_valid = 0; k->mem_ids = nullptr; k->mem_cap = 0; k->mem_off = nullptr; k->mem_work = nullptr; k->mem_work_n = 0; k->lmax = 0;
     const size_t N = c.n_items, C = c.n_clusters, H = c.n_hidden, B = c.batch_size, J = B + c.max_samples;
     const size_t nR = N * C, nW = H * C;
     float** f[] = {&k->R, &k->Wc, &k->dR, &k->dWc, &k->sR[0], &k->sR[1], &k->sWc[0], &k->sWc[1], &k->z, &k->p, &k->M, &k->sm, &k->sg,
@@ -256,6 +243,7 @@ extern "C" void sbr_cluster_destroy(sbr_cluster* k) {
     (void)hipStreamSynchronize(k->stream);
     for (float* q : f) if (q) (void)hipFree(q);
     if (k->ids) (void)hipFree(k->ids);
+    for (int* q : {k->mem_ids, k->mem_off, k->mem_work}) if (q) (void)hipFree(q);
     delete k;
 }
 
@@ -264,7 +252,7 @@ extern "C" int sbr_cluster_set_params(sbr_cluster* k, const float* R, const floa
     CL_HIP(hipMemcpyAsync(k->R, R, (size_t)k->cfg.n_items * k->cfg.n_clusters * sizeof(float), hipMemcpyHostToDevice, k->stream));
     CL_HIP(hipMemcpyAsync(k->Wc, Wc, (size_t)k->cfg.n_hidden * k->cfg.n_clusters * sizeof(float), hipMemcpyHostToDevice, k->stream));
     CL_HIP(hipStreamSynchronize(k->stream));
-    k->hard_valid = 0;
+    k->hard_valid = 0; k->lists_valid = 0;
     return SBR_OK;
 }
 static int cl_get(sbr_cluster* k, float* R, float* Wc, const float* dR, const float* dW) {
@@ -315,7 +303,7 @@ extern "C" int sbr_cluster_apply_update(sbr_cluster* k) {      // self.updater(c
                          c.learning_rate, c.rho, c.beta1, c.beta2, k->step));
     CL_HIP(launch_update(k->stream, c.updater, k->R, k->dR, k->sR[0], two ? k->sR[1] : nullptr, (size_t)c.n_items * c.n_clusters,
                          c.learning_rate, c.rho, c.beta1, c.beta2, k->step));
-    k->hard_valid = 0;
+    k->hard_valid = 0; k->lists_valid = 0;
     k->dR_clean = 1;                                 // update_kernel has cleared dR (and dWc)
     return SBR_OK;
 }

@@ -195,6 +195,8 @@ struct SbrSwitches {
     unsigned long long head_wait_ticks = HEAD_WAIT_TICKS;   // SBR_HEAD_WAIT_TICKS (tests: 0 = every foreign chunk is recomputed)
     int out_fuse = 1;            // SBR_OUT_FUSE: the dense head's gradient and step in one launch (launch_out_grad_step)
     int row_aware = 1;           // SBR_ROW_AWARE_UPDATE: the dense pass over a wide index-input block skips the gradient traffic of the rows the batch did not touch
+    int cluster_rank = 1;        // SBR_CLUSTER_RANK: sbr_cluster_rank scores only the members of each row's cluster (sbr_cluster_rank.hip); 0: it
+                                 // gathers them from the full score matrix (also the road of the bf16 / triage projections)
 };
 
 struct sbr_handle {
@@ -256,6 +258,7 @@ struct sbr_handle {
     bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
     // sbr_rank: scratch outside the arena (grown on demand, freed by sbr_destroy) and what the last call ran (sbr_query "rank_select" / "rank_sort")
     void* rank_scratch = nullptr; size_t rank_scratch_bytes = 0; int last_rank_select = 0, last_rank_sort = 0;
+    int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
     bool tail_cost_scanned = false;                                       // this step's sort was followed by launch_scatter_cost_scan
@@ -286,6 +289,29 @@ struct sbr_handle {
     float* St(int k, size_t off) const { return arena + lay.s_state + (size_t)k * lay.n_params + off; }
     float* A(size_t off) const { return arena + lay.s_act + off; }
     float* cost_ptr() const { return arena + lay.s_grads + lay.n_params; }
+};
+
+// The cluster head (sbr_cluster.hip; include/sbr_rnn.h "The cluster head of RNNCluster")
+struct sbr_cluster {
+    sbr_cluster_config cfg;
+    hipStream_t stream;
+    float *R, *Wc, *dR, *dWc, *sR[2], *sWc[2];       // parameters, gradients, optimizer state
+    float *z, *p, *M, *sm, *sg, *score, *dz, *rowcost, *ones, *cost, *hard, *nused;
+    int* ids;
+    long step;
+    float scale;
+    unsigned long long noise_ctr;
+    int J;                                           // cells of the last forward (B + samples)
+    int hard_valid;
+    int dR_clean;                                    // dR is all zeros: the optimizer kernel clears every gradient it consumes (no N x C memset per step)
+    // sbr_cluster_lists / sbr_cluster_rank (sbr_cluster_rank.hip): the hard clusters of prepare_tests as a CSR over clusters.  Own
+    // allocations, made on first use and freed by sbr_cluster_destroy; valid until R changes (set_params, apply_update)
+    int lists_valid;
+    int* mem_ids; size_t mem_cap;                    // [sum of sizes] item ids, every list ascending
+    int* mem_off;                                    // [C + 1] first entry of every list
+    int* mem_work; size_t mem_work_n;                // [C][blocks] per-block counts, then exclusive offsets inside a list
+    std::vector<int> mem_sizes;                      // host copy of the sizes, read back once per version of R
+    int lmax;                                        // the longest list, padded to a multiple of 4
 };
 
 void sbr_set_error(const char* fmt, ...);
@@ -597,3 +623,25 @@ hipError_t launch_rank_select(hipStream_t s, const float* scores, int rows, int 
 // radix sort's second buffer pair (not read when k <= kRankSortLds); returns the regime in *sort (1: LDS bitonic, 2: radix in scratch)
 hipError_t launch_rank_sort(hipStream_t s, const float* scores, int rows, int N, int k, unsigned* keys, int* ids, unsigned* keys2, int* ids2,
                             const int* n_sel, int* out_ids, float* out_scores, int* sort);
+// sbr_cluster_rank.hip: ranking inside each row's item cluster (include/sbr_rnn.h: sbr_cluster_lists, sbr_cluster_rank)
+// builds c's member lists if R changed since they were built (synchronises the stream once then); SBR_OK or a negative sbr_status
+int sbr_cluster_build_lists(sbr_cluster* c);
+// words of int scratch launch_crk_group needs behind its csel [rows]: counts [C], offsets [C + 1], row order [rows], the tile
+// table [3][max_tiles] and the tile count [1]
+static inline int sbr_crk_max_tiles(int rows, int C) { return rows / 16 + C; }
+static inline size_t sbr_crk_group_words(int rows, int C) { return (size_t)C + (C + 1) + rows + 3 * (size_t)sbr_crk_max_tiles(rows, C) + 1; }
+// counting sort of the rows by csel and the table of 16-row tiles (cluster, first place in `order`, rows)
+hipError_t launch_crk_group(hipStream_t s, const int* csel, int rows, int C, int* work);
+// cs[row][j] = h[row] . WoutT[members(c)[j]] + bout[...] for the tiles of `work`, -inf behind a row's list: the accumulation
+// order of gemm_f32_mfma + softmax_rows_kernel, bit for bit
+hipError_t launch_crk_score(hipStream_t s, const float* h, int ldh, const float* WoutT, const float* bout, int K, const int* mem_ids,
+                            const int* mem_off, const int* work, int rows, int C, int lmax, float* cs);
+// the second form: cs[row][j] = logits[row][members(c)[j]]
+hipError_t launch_crk_gather(hipStream_t s, const float* logits, int N, const int* csel, const int* mem_ids, const int* mem_off,
+                             int rows, int lmax, float* cs);
+// -inf at the places of the row's excluded ids that its cluster holds (binary search in the ascending list)
+hipError_t launch_crk_exclude(hipStream_t s, float* cs, int lmax, const int* csel, const int* mem_ids, const int* mem_off, int rows, int N,
+                              const int* excl_ids, const long long* excl_off, const int* X, const int* len, int T, int F);
+// places -> item ids, widened from kk to k columns (-1 / -inf); clu / size (nullable) [rows]: the row's cluster and its list's length
+hipError_t launch_crk_translate(hipStream_t s, const int* pos, const float* psc, int kk, int k, const int* csel, const int* mem_ids,
+                                const int* mem_off, int rows, int* out_ids, float* out_scores, int* size);

@@ -66,7 +66,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_sparse_unpack_add", "sbr_dense_ranges", "sbr_sparse_pack_device", "sbr_sparse_unpack_add_all",
            "sbr_cluster_create", "sbr_cluster_destroy", "sbr_cluster_set_params", "sbr_cluster_get_params", "sbr_cluster_get_grads",
            "sbr_cluster_set_scale", "sbr_cluster_forward_backward", "sbr_cluster_apply_update", "sbr_cluster_select",
-           "sbr_cluster_mask_scores", "sbr_cluster_hard",
+           "sbr_cluster_mask_scores", "sbr_cluster_hard", "sbr_cluster_lists", "sbr_cluster_rank",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
            "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch"]
@@ -144,6 +144,8 @@ def load_library(path=None):
     lib.sbr_cluster_select.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, vp, vp]
     lib.sbr_cluster_mask_scores.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
     lib.sbr_cluster_hard.argtypes = [vp, vp]
+    lib.sbr_cluster_lists.argtypes = [vp, vp, vp]
+    lib.sbr_cluster_rank.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
     lib.sbr_dataset_create.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.POINTER(vp)]
     lib.sbr_dataset_destroy.argtypes = [vp]
     lib.sbr_dataset_set_tables.argtypes = [vp, vp, vp]
@@ -893,6 +895,7 @@ class ClusterHead(object):
         self._smp = self.torch.empty(self.max_samples, dtype=self.torch.int32, device=dev)
         self._csel = self.torch.empty(max(self.batch_size, 16), dtype=self.torch.int32, device=dev)
         self._hard = None
+        self._lists = None
 
     def _check(self, rc):
         if rc != 0:
@@ -923,6 +926,7 @@ class ClusterHead(object):
             raise ValueError("mismatch: cluster arrays have shapes %r, %r" % (R.shape, Wc.shape))
         self._check(self.lib.sbr_cluster_set_params(self.h, ctypes.c_void_p(R.ctypes.data), ctypes.c_void_p(Wc.ctypes.data)))
         self._hard = None
+        self._lists = None
 
     def _get(self, fn):
         R = np.empty((self.n_items, self.n_clusters), dtype=np.float32); Wc = np.empty((self.n_hidden, self.n_clusters), dtype=np.float32)
@@ -954,6 +958,7 @@ class ClusterHead(object):
     def apply_update(self):
         self._check(self.lib.sbr_cluster_apply_update(self.h))
         self._hard = None
+        self._lists = None
 
     def select(self, rows, with_activations=False):
         """argmax cluster of the first `rows` user representations (rnn_cluster.py:334) [, the selection activations]"""
@@ -981,3 +986,56 @@ class ClusterHead(object):
                                                      ctypes.c_void_p(self._csel.data_ptr()),
                                                      ctypes.c_void_p(used.data_ptr()) if used is not None else None))
         return used.cpu().numpy() if used is not None else None
+
+    def cluster_lists(self):
+        """The hard clusters of prepare_tests (rnn_cluster.py:440-466) as a list of C ascending int32 id arrays, built on the device
+        (sbr_cluster_lists): cluster j holds every item whose membership R[i][j] is positive, and every item without a positive
+        membership whose largest one -- the first of them -- is R[i][j].  Cached until the arrays change."""
+        if self._lists is None:
+            sizes = np.empty(self.n_clusters, dtype=np.int32)
+            self._check(self.lib.sbr_cluster_lists(self.h, ctypes.c_void_p(sizes.ctypes.data), None))
+            members = np.empty(max(int(sizes.sum()), 1), dtype=np.int32)
+            self._check(self.lib.sbr_cluster_lists(self.h, ctypes.c_void_p(sizes.ctypes.data), ctypes.c_void_p(members.ctypes.data)))
+            bounds = np.concatenate([[0], np.cumsum(sizes, dtype=np.int64)])
+            self._lists = [members[bounds[j]:bounds[j + 1]].copy() for j in range(self.n_clusters)]
+        return self._lists
+
+    def rank(self, X, mask, k, exclude=None, exclude_input=True, return_scores=False):
+        """RNNEngine.rank inside each row's cluster (sbr_cluster_rank): the row's cluster is the arg-max of its selection activations,
+        only that cluster's items (cluster_lists) are scored and ranked.  Returns (ids (rows, k) int32, [scores (rows, k) float32,]
+        clusters (rows,) int32, sizes (rows,) int32): ids score descending, ties to the lowest id, -1 (-inf) where the row runs out
+        of rankable members -- k may exceed the cluster's size; sizes = items in the row's cluster before any exclusion.  `exclude`,
+        `exclude_input` as in RNNEngine.rank; an excluded id outside the row's cluster changes nothing."""
+        eng = self.engine
+        eng._rank_local_flush("rank")
+        n = eng.set_batch(X, mask)
+        ids_arr = off_arr = None
+        if exclude is not None:
+            lists = [np.zeros(0, dtype=np.int32) if e is None else np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+            if len(lists) != n:
+                raise ValueError("exclude must hold one id list per row: %d lists for %d rows" % (len(lists), n))
+            off_arr = np.zeros(n + 1, dtype=np.int64)
+            np.cumsum([len(e) for e in lists], out=off_arr[1:])
+            ids_arr = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]))   # (never empty: its pointer is not NULL)
+        return self.rank_csr(n, k, ids_arr, off_arr, exclude_input=exclude_input, return_scores=return_scores)
+
+    def rank_csr(self, rows, k, excl_ids=None, excl_off=None, exclude_input=True, return_scores=False):
+        """sbr_cluster_rank on the batch already set on the engine (`rows` rows); the lists as the C-ABI takes them"""
+        self.engine._rank_local_flush("rank")
+        k = int(k)
+        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
+            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
+        ids = np.empty((rows, k), dtype=np.int32)
+        scores = np.empty((rows, k), dtype=np.float32) if return_scores else None
+        clusters, sizes = np.empty(rows, dtype=np.int32), np.empty(rows, dtype=np.int32)
+        if excl_ids is not None:
+            excl_ids = np.ascontiguousarray(np.asarray(excl_ids, dtype=np.int32))
+        if excl_off is not None:
+            excl_off = np.ascontiguousarray(np.asarray(excl_off, dtype=np.int64))
+            if excl_off.shape != (rows + 1,):
+                raise ValueError("excl_off must have %d entries (rows + 1), got %r" % (rows + 1, excl_off.shape))
+        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        # (the engine's mapping of the status: SBR_EINVAL is a ValueError, as RNNEngine.rank raises it)
+        self.engine._check(self.lib.sbr_cluster_rank(self.h, self.engine.h, k, int(bool(exclude_input)), p(excl_ids), p(excl_off), p(ids),
+                                                     p(scores), p(clusters), p(sizes)))
+        return (ids, scores, clusters, sizes) if return_scores else (ids, clusters, sizes)

@@ -211,7 +211,7 @@ class RNNBase(object):
         output[exclude] = -np.inf
         return list(np.argpartition(-output, range(k))[:k])
 
-    batched_top_k = True        # top_k_batch ranks what top_k_recommendations ranks (RNNCluster: no, it scores inside a cluster on the host)
+    batched_top_k = True        # top_k_batch ranks what top_k_recommendations ranks (RNNCluster: inside the user's cluster, and it returns (ids, n_scored))
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)], batch_size rows per engine
@@ -827,11 +827,44 @@ class RNNCluster(RNNBase):
         scores[exclude] = -np.inf
         return list(np.argpartition(-scores, range(k))[:k]), self.n_items
 
-    batched_top_k = False
+    batched_top_k = True
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
-        raise NotImplementedError("RNNCluster ranks inside the user's hard cluster on the host (predict_function, rnn_cluster.py:302-325): "
-                                  "the engine's batched ranking would rank the whole catalogue instead; call top_k_recommendations per user")
+        """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per
+        call (ClusterHead.rank): one (ids, n_scored) per sequence -- the ranked ids inside the user's cluster, best first, and the
+        number of items in that cluster.  Per sequence the last max_length items go in; with unique interactions the WHOLE sequence
+        is excluded, plus the row's own list; any 1 <= k <= n_items.  A row with fewer than k rankable members returns only those
+        (the host road goes on with excluded ids, in numpy's partition order).  --ignore_clusters: the whole catalogue, as
+        RNNBase.top_k_batch ranks it, with n_scored = n_items."""
+        n = len(sequences)
+        if not self.predict_with_clusters:
+            ranked = super(RNNCluster, self).top_k_batch(sequences, user_ids=user_ids, k=k, exclude=exclude)
+            return [(ids, self.n_items) for ids in ranked]
+        if user_ids is None:
+            user_ids = [None] * n
+        if exclude is None:
+            exclude = [None] * n
+        if len(user_ids) != n or len(exclude) != n:
+            raise ValueError("user_ids and exclude must have one entry per sequence")
+        out = []
+        for lo in range(0, n, self.batch_size):
+            hi = min(n, lo + self.batch_size)
+            X = np.zeros((hi - lo, self.max_length, self._input_size()), dtype=np.int32)
+            mask = np.zeros((hi - lo, self.max_length), dtype=np.float32)
+            lists = []
+            for i in range(lo, hi):
+                seq = sequences[i][-min(self.max_length, len(sequences[i])):]
+                if len(seq):
+                    X[i - lo, :len(seq), :] = np.array([self._get_features(x, user_ids[i]) for x in seq], dtype=np.int32)
+                mask[i - lo, :len(seq)] = 1
+                ex = [x[0] for x in sequences[i]] if self.interactions_are_unique else []
+                if exclude[i] is not None:
+                    ex = ex + [int(e) for e in exclude[i]]
+                lists.append(np.asarray(ex, dtype=np.int32))
+            # the lists carry every viewed item already: the engine need not derive them from its input window again
+            ids, _, sizes = self.head.rank(X, mask, k, exclude=lists, exclude_input=False)
+            out.extend(([int(j) for j in row[row >= 0]], int(m)) for row, m in zip(ids, sizes))
+        return out
 
     def top_k_recommendations(self, sequence, user_id=None, k=10, exclude=None):
         if exclude is None:

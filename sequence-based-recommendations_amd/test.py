@@ -39,16 +39,21 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
     `top_k_recommendations` feeds the last max_length viewed items and excludes EVERY viewed item (rnn_base.py:132-159).
     Users are ranked batch_size at a time: those whose viewed half fits the window, at k <= 64, by the engine's test function
     (it derives the exclusion from its input); deeper rankings and longer histories by RNNBase.top_k_batch, which hands the
-    engine the whole viewed half as an exclusion list."""
+    engine the whole viewed half as an exclusion list.
+    A cluster model (`--clusters C`, test.py:61-76) ranks inside each user's item cluster: every user with a viewed half goes
+    through RNNCluster.top_k_batch at any k -- never through the engine's whole-catalogue test function -- and nb_of_dp is the
+    mean number of items scored per user, the size of the user's cluster."""
     predictor.load(model_file)
     evaluator = Evaluator(dataset, k=k)
     if get_full_recommendation_list:
         k = dataset.n_items
     start = time.perf_counter()
     pending, deep, results, order = [], [], {}, []
-    # RNNCluster scores inside the user's cluster on the host and has no batched ranking; nor has a stand-in engine that offers
-    # the reference's three callables only (tests/test_cli_reference_golden.py)
+    # a stand-in engine that offers the reference's three callables only has no batched ranking (tests/test_cli_reference_golden.py)
     batched_deep = getattr(predictor, "batched_top_k", False) and hasattr(predictor.engine, "rank")
+    # the reference tests a model as a cluster model on args.clusters > 0 (test.py:61): its recommendation calls return (ids, n)
+    clustered = getattr(args, "clusters", 0) > 0
+    scored = {}
 
     def flush():
         if not pending:
@@ -68,7 +73,10 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
             return
         ranked = predictor.top_k_batch([viewed for _, viewed, _ in deep], user_ids=[u for _, _, u in deep], k=k)
         for (n, _, _), row in zip(deep, ranked):
-            results[n] = row
+            if clustered:
+                results[n], scored[n] = row
+            else:
+                results[n] = row
         del deep[:]
     for n, (sequence, user_id) in enumerate(dataset.test_set(epochs=1)):
         num_viewed = int(len(sequence) / 2)
@@ -80,7 +88,15 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
         # the ranked ones in numpy's partition order, and the rank comparison reads them; the engine never ranks an excluded id.
         # An empty viewed half (a sequence of one item): a row of length 0 has only ever been scored by this one-row call, and a
         # test set holds at most a handful of them.
-        if get_full_recommendation_list or len(viewed) == 0 or ((k > 64 or len(viewed) > predictor.max_length) and not batched_deep):
+        if clustered:
+            if get_full_recommendation_list or len(viewed) == 0:
+                ids, scored[n] = predictor.top_k_recommendations(viewed, user_id=user_id, k=k)
+                results[n] = list(ids)
+            else:
+                deep.append((n, viewed, user_id))
+                if len(deep) == predictor.batch_size:
+                    flush_deep()
+        elif get_full_recommendation_list or len(viewed) == 0 or ((k > 64 or len(viewed) > predictor.max_length) and not batched_deep):
             results[n] = list(predictor.top_k_recommendations(viewed, user_id=user_id, k=k))
         elif k > 64 or len(viewed) > predictor.max_length:
             deep.append((n, viewed, user_id))
@@ -95,7 +111,7 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
     for n, goal in order:
         evaluator.add_instance(goal, results[n])
     print("Timer: ", time.perf_counter() - start)
-    evaluator.nb_of_dp = dataset.n_items
+    evaluator.nb_of_dp = np.mean([scored[n] for n, _ in order]) if clustered else dataset.n_items      # test.py:73-76
     return evaluator
 
 
