@@ -442,6 +442,33 @@ int sbr_plan_pass_host(const int64_t* lengths, const int32_t* order, int64_t n_u
  * makes it the current batch, as sbr_set_batch does.  Entirely on the handle's stream; no host sync. */
 int sbr_build_batch(sbr_handle* h, sbr_dataset* d, int64_t batch, uint64_t seed);
 
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation of whole users on the device (added under ABI 11: one symbol, no struct change) -- the per-user loops of test.py:43-77
+ * and of the validation inside train() (rnn_base.py:358-371; evaluation.py:16-216) for a list of users in ONE call.  User
+ * u = users[j] is sequence u of d as uploaded (never the noised copy; no planned pass is touched): L = its length, half = L / 2, the
+ * viewed half is items[0 .. half), the goal items[half .. L) (test.py:81-83, _gen_mini_batch(test=True)); the row fed is the last
+ * min(T, half) viewed items, left-aligned and padded with index 0 (+ n_items + rating index with n_feat == 2, ratings attached by
+ * sbr_dataset_set_options).  local_batch users at a time are packed into the engine's batch buffers (the handle is left as
+ * sbr_set_batch leaves it), scored (the very floats sbr_rank ranks), excluded straight from the dataset's device CSR, ranked by
+ * sbr_rank's kernels (sbr_query "rank_select" / "rank_sort" report them) and compared with the goal; everything is enqueued on the
+ * engine's stream without a host wait in between, and the call waits for the device once, at its end.
+ * users may repeat, in any order.  SBR_EINVAL, found before anything is launched (the engine stays usable): a user outside
+ * [0, n_users) or with L < 2, n < 1, k outside [1, N], an unknown mode, n_feat == 2 without ratings attached, items or stream of h and
+ * d that differ.  Parameters, gradients and optimizer state are touched only by bringing lazily stepped rows up to date, as sbr_rank
+ * does.  Scratch: the handle's ranking scratch (see sbr_rank), grown once per call. */
+#define SBR_EVAL_EXCL_NONE 0         /* --repeated_interactions */
+#define SBR_EVAL_EXCL_VIEWED 1       /* the whole viewed half is never ranked, also the part that no longer fits the window
+                                        (top_k_recommendations, rnn_base.py:132-159; test.py:43-77) */
+#define SBR_EVAL_EXCL_WINDOW 2       /* only the items fed are never ranked (the compiled test function, rnn_base.py:196-209: validation) */
+#define SBR_EVAL_EXCL_WINDOW_ZERO 3  /* the items fed score 0.0 and stay rankable (the same function on RNNMargin's raw outputs: sbr_topk's exclude_seen = 2) */
+int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int exclude_mode,
+                 int32_t* ids_host,        /* NULL, or [n][k]: exactly sbr_rank's ids (-1 in unfilled places) */
+                 int32_t* n_pred_host,     /* [n] places filled (ids >= 0) */
+                 int32_t* hits_host,       /* [n] |set(goal) & set(top-k)| */
+                 int32_t* first_hit_host,  /* [n] 1 when goal[0] is among the top-k (sps) */
+                 uint32_t* hitmask_host,   /* NULL, or [n][(k + 31) / 32]: bit p of a row = the id at place p is a goal item */
+                 int32_t* item_hits_host); /* NULL, or [N]: over all n users, how often item i was a correct prediction */
+
 #ifdef __cplusplus
 }
 #endif

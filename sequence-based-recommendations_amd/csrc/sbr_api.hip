@@ -1991,6 +1991,77 @@ extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* 
     return check_fault(h);          // a forward that gave up must not hand out rankings
 }
 
+// Whole users evaluated on the device (include/sbr_rnn.h: sbr_evaluate; kernels: sbr_eval.hip).  Per chunk of local_batch users:
+// pack -> forward + projection (full_scores) -> exclusion from the dataset's CSR -> sbr_rank's select and sort -> hits, all on the
+// main stream; the per-user results of every chunk land at the chunk's offset of arrays sized for the whole call, and the host
+// waits once, in check_fault.  The pack writes batch set 0 on the main stream like sbr_set_batch's device-to-device copies, behind every
+// reader of the set (sbr_build_batch's comment, sbr_batch.hip), and leaves the handle as that call does.
+extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int exclude_mode, int32_t* ids_host,
+                            int32_t* n_pred_host, int32_t* hits_host, int32_t* first_hit_host, uint32_t* hitmask_host, int32_t* item_hits_host) {
+    CHECK_ARG(h && d && users && n_pred_host && hits_host && first_hit_host, "null argument");
+    const Layout& y = h->lay;
+    SbrEvalView v;
+    int rc;
+    if ((rc = sbr_dataset_eval_view(d, &v, 0)) != SBR_OK) return rc;
+    CHECK_ARG(n >= 1, "n=%lld users: at least one", (long long)n);
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW_ZERO, "unknown exclusion mode %d", exclude_mode);
+    CHECK_ARG(y.F == 1 || (y.F == 2 && v.rate && y.cfg.input_size == y.N + 10),
+              "a model with two indices per step needs the ratings attached to the dataset (sbr_dataset_set_options)");
+    CHECK_ARG(v.n_items == y.N && (y.cfg.input_size == y.N || y.F == 2), "dataset has %d items, the model %d", v.n_items, y.N);
+    CHECK_ARG(v.stream == h->stream, "dataset and engine must share one stream");
+    for (int64_t j = 0; j < n; ++j) {
+        CHECK_ARG(users[j] >= 0 && users[j] < v.n_users, "users[%lld] = %d outside [0,%lld)", (long long)j, users[j], (long long)v.n_users);
+        CHECK_ARG(v.h_off[users[j] + 1] - v.h_off[users[j]] >= 2, "user %d has fewer than two items: nothing to view or no goal", users[j]);
+    }
+    if ((rc = sbr_dataset_eval_view(d, &v, 1)) != SBR_OK) return rc;      // (first call for this dataset: sorts and uploads the goals)
+    const int B = y.B, words = (k + 31) / 32;
+    const bool radix = k > kRankSortLds, margin = SBR_LOSS_IS_MARGIN(y.cfg.loss);
+    const size_t bk = (size_t)B * k, nk = (size_t)n * k;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    const size_t o_users = take((size_t)n * sizeof(int)), o_npred = take((size_t)n * sizeof(int)), o_hits = take((size_t)n * sizeof(int));
+    const size_t o_first = take((size_t)n * sizeof(int)), o_mask = take(hitmask_host ? (size_t)n * words * sizeof(unsigned) : 0);
+    const size_t o_ihits = take(item_hits_host ? (size_t)y.N * sizeof(int) : 0);
+    const size_t o_oid = take((ids_host ? nk : bk) * sizeof(int));      // the ids of every user only when the caller fetches them
+    const size_t o_nsel = take((size_t)B * sizeof(int)), o_k0 = take(bk * sizeof(unsigned)), o_i0 = take(bk * sizeof(int));
+    const size_t o_k1 = take(radix ? bk * sizeof(unsigned) : 0), o_i1 = take(radix ? bk * sizeof(int) : 0), o_osc = take(bk * sizeof(float));
+    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    // (pageable host memory: the copy has left the caller's array when it returns)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (item_hits_host) SBR_HIP(hipMemsetAsync(S + o_ihits, 0, (size_t)y.N * sizeof(int), s));
+    for (int64_t c0 = 0; c0 < n; c0 += B) {
+        const int rows = (int)std::min<int64_t>(B, n - c0);
+        // --- the chunk becomes the current batch, in set 0, as sbr_set_batch would leave it
+        h->bX = (const int*)h->A(y.a_X); h->blen = (const int*)h->A(y.a_len); h->btgt = (const int*)h->A(y.a_tgt);
+        h->bsmp = (const int*)h->A(y.a_smp); h->bpop = h->A(y.a_pop);
+        h->bb_set = 0; h->bb_unread = false;
+        if (rows < y.Bp && margin) SBR_HIP(hipMemsetAsync(h->A(y.a_tgt), 0xFF, (size_t)y.Bp * y.NT * sizeof(int), s));   // no positives
+        SBR_LAUNCH(launch_ev_pack(s, v, dusers + c0, rows, y.Bp, y.T, y.F, (int*)h->A(y.a_X), (int*)h->A(y.a_len), h->A(y.a_pop)));
+        h->n_rows = rows; h->have_batch = true; h->fwd_done = false;
+        if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_rank ranks (and flushes lazily stepped rows)
+        float* lg = h->A(y.a_logits);
+        SBR_LAUNCH(launch_ev_exclude(s, v, dusers + c0, rows, y.T, y.N, exclude_mode, lg));
+        int* oid = (int*)(S + o_oid) + (ids_host ? (size_t)c0 * k : 0);
+        SBR_LAUNCH(launch_rank_select(s, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
+        SBR_LAUNCH(launch_rank_sort(s, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
+                                    (const int*)(S + o_nsel), oid, (float*)(S + o_osc), &h->last_rank_sort));
+        SBR_LAUNCH(launch_ev_hits(s, v, dusers + c0, rows, k, oid, (int*)(S + o_npred) + c0, (int*)(S + o_hits) + c0, (int*)(S + o_first) + c0,
+                                  hitmask_host ? (unsigned*)(S + o_mask) + (size_t)c0 * words : nullptr,
+                                  item_hits_host ? (int*)(S + o_ihits) : nullptr));
+    }
+    if (ids_host) SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, nk * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(n_pred_host, S + o_npred, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(hits_host, S + o_hits, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(first_hit_host, S + o_first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (hitmask_host) SBR_HIP(hipMemcpyAsync(hitmask_host, S + o_mask, (size_t)n * words * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (item_hits_host) SBR_HIP(hipMemcpyAsync(item_hits_host, S + o_ihits, (size_t)y.N * sizeof(int), hipMemcpyDeviceToHost, s));
+    return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
+}
+
 // Ranking inside each row's item cluster (RNNCluster.predict_function for a whole batch, rnn_cluster.py:302-325; kernels and the
 // accumulation-order argument: sbr_cluster_rank.hip).  The member lists are the cluster object's, everything a call needs beyond
 // them sits in the handle's ranking scratch.

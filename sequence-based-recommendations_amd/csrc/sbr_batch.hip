@@ -32,6 +32,7 @@ struct sbr_dataset {
     int *d_seg_user, *d_seg_k, *d_seg_row0, *d_batch_begin; size_t cap_su, cap_sk, cap_sr, cap_bb;
     int *d_split, *d_rowuser; size_t cap_rows;      // per-row scratch of the batch being built
     int64_t n_batches; int batch_size;
+    int* d_goal;                                    // sbr_evaluate: every user's goal half sorted ascending (sbr_dataset_eval_view), or NULL
 };
 
 
@@ -415,6 +416,7 @@ extern "C" int sbr_dataset_create(const int32_t* items, const int64_t* offsets, 
     d->h_items.assign(items, items + nnz); d->h_off.assign(offsets, offsets + n_users + 1);
     d->d_seg_user = d->d_seg_k = d->d_seg_row0 = d->d_batch_begin = nullptr; d->cap_su = d->cap_sk = d->cap_sr = d->cap_bb = 0;
     d->d_split = d->d_rowuser = nullptr; d->cap_rows = 0; d->n_batches = 0; d->batch_size = 0;
+    d->d_goal = nullptr;
     d->len.resize(n_users);
     for (int64_t u = 0; u < n_users; ++u) {
         d->len[u] = offsets[u + 1] - offsets[u];
@@ -442,6 +444,7 @@ extern "C" int sbr_dataset_destroy(sbr_dataset* d) {
     (void)hipFree(d->d_split); (void)hipFree(d->d_rowuser);
     (void)hipFree(d->d_items_n); (void)hipFree(d->d_rate_n); (void)hipFree(d->d_len_n);
     (void)hipFree(d->d_hr_user); (void)hipFree(d->d_hr_split); (void)hipFree(d->d_hr_tgt);
+    (void)hipFree(d->d_goal);
     delete d;
     return SBR_OK;
 }
@@ -534,6 +537,30 @@ extern "C" int sbr_dataset_set_tables(sbr_dataset* d, const float* pop_db, const
         SBR_HIP(hipMemcpyAsync(d->d_cdf, cdf, d->n_items * sizeof(double), hipMemcpyHostToDevice, d->stream));
     }
     SBR_HIP(hipStreamSynchronize(d->stream));
+    return SBR_OK;
+}
+
+// What sbr_evaluate reads (sbr_common.h).  The sorted goals come from the host copy of the sequences: one std::sort per user and one
+// upload, on the first call for this dataset
+// (with_goal = 0: the view without them, for the argument checks -- nothing is allocated or copied).
+int sbr_dataset_eval_view(sbr_dataset* d, SbrEvalView* v, int with_goal) {
+    if (with_goal && !d->d_goal) {
+        std::vector<int> g(d->h_items);
+        g.resize((size_t)std::max<int64_t>(d->nnz, 1));
+        for (int64_t u = 0; u < d->n_users; ++u) {
+            const int64_t o = d->h_off[u], L = d->h_off[u + 1] - o;
+            std::sort(g.begin() + o + L / 2, g.begin() + o + L);
+        }
+        if (hipMalloc(&d->d_goal, g.size() * sizeof(int)) != hipSuccess) {
+            (void)hipGetLastError(); d->d_goal = nullptr;
+            sbr_set_error("sbr_evaluate: hipMalloc(%zu) of the sorted goals failed", g.size() * sizeof(int));
+            return SBR_ENOMEM;
+        }
+        SBR_HIP(hipMemcpyAsync(d->d_goal, g.data(), g.size() * sizeof(int), hipMemcpyHostToDevice, d->stream));
+        SBR_HIP(hipStreamSynchronize(d->stream));           // `g` goes out of scope
+    }
+    v->n_users = d->n_users; v->n_items = d->n_items; v->stream = d->stream;
+    v->items = d->d_items; v->rate = d->d_rate; v->goal = d->d_goal; v->off = d->d_off; v->h_off = d->h_off.data();
     return SBR_OK;
 }
 

@@ -645,3 +645,22 @@ hipError_t launch_crk_exclude(hipStream_t s, float* cs, int lmax, const int* cse
 // places -> item ids, widened from kk to k columns (-1 / -inf); clu / size (nullable) [rows]: the row's cluster and its list's length
 hipError_t launch_crk_translate(hipStream_t s, const int* pos, const float* psc, int kk, int k, const int* csel, const int* mem_ids,
                                 const int* mem_off, int rows, int* out_ids, float* out_scores, int* size);
+// sbr_eval.hip: evaluation of whole users on the device (include/sbr_rnn.h: sbr_evaluate).  A user's sequence is split in the middle
+// (test.py:81-83, _gen_mini_batch(test=True)): half = L / 2 viewed items, the rest is the goal.
+// What sbr_evaluate reads of a dataset (sbr_batch.hip owns the struct): the sequences as uploaded -- never the noised copy --, the
+// host copy of the offsets for the argument checks, and `goal`: per user the goal items[off + half .. off + L) sorted ascending, at
+// the same places of a second array (its viewed places are not written).  Built on the first call, freed with the dataset.
+struct SbrEvalView {
+    int64_t n_users; int n_items; hipStream_t stream;
+    const int *items, *rate, *goal; const long long* off; const int64_t* h_off;
+};
+int sbr_dataset_eval_view(sbr_dataset* d, SbrEvalView* v, int with_goal);      // with_goal = 0: no `goal`, nothing allocated or copied
+// rows [0, rows) of the batch buffers from users[0 .. rows): the last min(T, half) viewed items left-aligned (+ n_items + rating index
+// with F == 2, as bb_pack_kernel writes it), the length, popularity 1; rows [rows, Bp): index 0, length 0, popularity 1
+hipError_t launch_ev_pack(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop);
+// mode SBR_EVAL_EXCL_*: -inf (WINDOW_ZERO: 0.0f) into scores[r][id] for the viewed items of users[r] (VIEWED: all of them; WINDOW*: the ones fed)
+hipError_t launch_ev_exclude(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int mode, float* scores);
+// per row r of ids [rows][k] (ordered top-k, -1 behind the filled places): n_pred, hits, first_hit [rows], mask [rows][(k + 31) / 32]
+// (NULL: not written), item_hits [N] += 1 per hit (NULL: not counted)
+hipError_t launch_ev_hits(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int k, const int* ids, int* n_pred, int* hits,
+                          int* first_hit, unsigned* mask, int* item_hits);

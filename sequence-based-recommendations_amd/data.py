@@ -149,6 +149,30 @@ class NativeBatchBuilder(object):
         self.ds.close()
 
 
+def sequences_csr(sequence_set):
+    """(items int32 (nnz,), offsets int64 (n_users + 1,), ratings float64 (nnz,)) of a SequenceGenerator's file: the CSR form
+    DeviceDataset takes, users in file order."""
+    if not hasattr(sequence_set, "users"):
+        sequence_set.load()
+    lengths = np.array([len(x) for x in sequence_set.items], dtype=np.int64)
+    offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+    items = np.concatenate(sequence_set.items).astype(np.int32) if len(lengths) else np.zeros(0, np.int32)
+    ratings = np.concatenate(sequence_set.ratings) if len(lengths) else np.zeros(0)
+    return items, offsets, ratings
+
+
+def make_device_dataset(engine, sequence_set, n_items, ratings=False):
+    """A SequenceGenerator's sequences in HBM, as NativeBatchBuilder uploads the training set: items, offsets, and with --rf the
+    ratings beside them (set_options).  What RNNEngine.evaluate reads for a validation or test set."""
+    from .engine import DeviceDataset
+    items, offsets, r = sequences_csr(sequence_set)
+    ds = DeviceDataset(engine, items, offsets, n_items)
+    if ratings:
+        ds.set_options(r, False)
+    ds.items, ds.offsets = items, offsets       # host copies: the goals of the users come from them
+    return ds
+
+
 class DataHandler(object):
     """Directory resolver + `stats` loader + item popularity cache (data_handling.py:12-102)."""
 
@@ -160,6 +184,18 @@ class DataHandler(object):
         self.validation_set = SequenceGenerator(self.dirname + "data/val_set_sequences")
         self.test_set = SequenceGenerator(self.dirname + "data/test_set_sequences")
         self._load_stats()
+
+    def device_set(self, which, engine, ratings=False):
+        """The DeviceDataset of the "validation" or "test" set for `engine` (data.make_device_dataset), made on first use and
+        kept: one per set.  Another engine, or another --rf setting, replaces it."""
+        cache = self.__dict__.setdefault("_device_sets", {})
+        hit = cache.get(which)
+        if hit is None or hit[0] is not engine or hit[1] != bool(ratings):
+            if hit is not None:
+                hit[2].close()
+            source = {"validation": self.validation_set, "test": self.test_set, "training": self.training_set}[which]
+            hit = cache[which] = (engine, bool(ratings), make_device_dataset(engine, source, self.n_items, ratings=ratings))
+        return hit[2]
 
     @property
     def item_popularity(self):
@@ -280,3 +316,117 @@ class Evaluator(object):
         if len(correct) == 0:
             return 0
         return len([i for i in correct if i in pop_items]) / len(correct)
+
+
+class NativeEvaluator(Evaluator):
+    """Evaluator over the per-user records RNNEngine.evaluate brings back from the device (include/sbr_rnn.h: sbr_evaluate)
+    instead of (goal, predictions) lists: sps, recall, precision, user_coverage, item_coverage, blockbuster_share and ndcg come
+    from the integer counts and the hit mask and equal, with ==, what Evaluator computes from the same ids -- the ratios are the
+    same int / int divisions, added in user order by the same sequential sums.  `instances` is built on first use from the ids
+    when they were fetched (want_ids); every other metric (novelty, get_rank_comparison, ...) is the base class's on them.
+    add_instance still works: the instance's record is computed on the host and takes its place in the order."""
+
+    def __init__(self, dataset, k=10):
+        self._seg, self._inst, self._n = [], None, 0
+        self._item_hits = None
+        super(NativeEvaluator, self).__init__(dataset, k=k)      # (its metrics table binds the methods below)
+
+    # ------------------------------------------------------------------ records in
+    def add_records(self, rec, goal_len, goals=None, rows=None, item_hits=True):
+        """rec: what RNNEngine.evaluate returned at this evaluator's k; goal_len (n,): len(goal) of every user; goals: their
+        goal lists (only `instances` needs them); rows: the users of rec that take the next places (slice or index array; None =
+        all of them, in order); item_hits=False: rec's per-item counts were already added with an earlier slice."""
+        sel = slice(None) if rows is None else rows
+        pick = lambda a: None if a is None else np.asarray(a)[sel]
+        seg = {"n_pred": pick(rec["n_pred"]).astype(np.int64), "hits": pick(rec["hits"]).astype(np.int64),
+               "first": pick(rec["first_hit"]).astype(np.int64), "glen": np.asarray(goal_len, dtype=np.int64).reshape(-1),
+               "mask": pick(rec.get("hitmask")), "ids": pick(rec.get("ids")), "goals": goals}
+        if len(seg["glen"]) != len(seg["n_pred"]):
+            raise ValueError("goal_len must have one entry per user")
+        if item_hits:
+            ih = np.asarray(rec["item_hits"], dtype=np.int64)
+            self._item_hits = ih.copy() if self._item_hits is None else self._item_hits + ih
+        self._seg.append(seg)
+        self._n += len(seg["n_pred"])
+        self._inst = None
+
+    def add_instance(self, goal, predictions):
+        goal, top = list(goal), list(predictions)[:self.k]
+        correct = set(goal) & set(top)
+        bits = np.zeros((1, (self.k + 31) // 32), dtype=np.uint32)
+        for i, p in enumerate(top):
+            if p in goal:
+                bits[0, i // 32] |= np.uint32(1 << (i % 32))
+        if self._item_hits is None:
+            self._item_hits = np.zeros(self.dataset.n_items, dtype=np.int64)
+        for i in correct:
+            self._item_hits[i] += 1
+        self._seg.append({"n_pred": np.array([len(top)], np.int64), "hits": np.array([len(correct)], np.int64),
+                          "first": np.array([int(len(goal) > 0 and goal[0] in top)], np.int64), "glen": np.array([len(goal)], np.int64),
+                          "mask": bits, "ids": None, "goals": [goal], "host": [goal, list(predictions)]})
+        self._n += 1
+        self._inst = None
+
+    # ------------------------------------------------------------------ instances, for everything the records do not carry
+    @property
+    def instances(self):
+        if self._inst is None:
+            out = []
+            for seg in self._seg:
+                if "host" in seg:
+                    out.append(seg["host"])
+                    continue
+                if seg["ids"] is None or seg["goals"] is None:
+                    raise RuntimeError("this metric needs the recommended ids: evaluate with want_ids=True and hand the goals over")
+                out.extend([list(g), list(row[row >= 0])] for g, row in zip(seg["goals"], seg["ids"]))
+            self._inst = out
+        return self._inst
+
+    @instances.setter
+    def instances(self, value):      # (Evaluator.__init__ starts from an empty list)
+        self._inst = None
+
+    def _col(self, name):
+        return np.concatenate([seg[name] for seg in self._seg]).tolist() if self._seg else []
+
+    # ------------------------------------------------------------------ evaluation.py:37-88, 118-194 from the records
+    def average_precision(self):
+        return sum(h / p for h, p in zip(self._col("hits"), self._col("n_pred")) if p > 0) / self._n
+
+    def average_recall(self):
+        return sum(h / g for h, g in zip(self._col("hits"), self._col("glen")) if g > 0) / self._n
+
+    def sps(self):
+        return sum(self._col("first")) / self._n
+
+    def user_coverage(self):
+        return sum(int(h > 0) for h in self._col("hits")) / self._n
+
+    def item_coverage(self):
+        return 0 if self._item_hits is None else int(np.count_nonzero(self._item_hits))
+
+    def blockbuster_share(self):
+        nb_pop = self.dataset.n_items // 100
+        pop_items = np.argpartition(-self.dataset.item_popularity, nb_pop)[:nb_pop]
+        total = 0 if self._item_hits is None else int(self._item_hits.sum())
+        if total == 0:
+            return 0
+        return int(self._item_hits[np.unique(pop_items)].sum()) / total
+
+    def average_ndcg(self):
+        # the discount of place i exactly as the base class computes it, one scalar call each; np.cumsum adds in order, and the
+        # 0.0 of a place without a hit leaves the running sum as it is: dcg and max_dcg are the base class's sequential sums
+        k = self.k
+        disc = np.array([1.0 / np.log2(2 + i) for i in range(k)], dtype=np.float64)
+        run = np.cumsum(disc)
+        ndcg = 0.0
+        for seg in self._seg:
+            if seg["mask"] is None:
+                raise RuntimeError("ndcg needs the hit mask: evaluate with want_mask=True")
+            n = len(seg["n_pred"])
+            bits = ((seg["mask"].astype(np.uint32)[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(n, -1)[:, :k]
+            dcg = np.cumsum(np.where(bits != 0, disc[None, :], 0.0), axis=1)[:, -1]
+            m = np.minimum(seg["n_pred"], seg["glen"])
+            for i in np.nonzero(seg["n_pred"] > 0)[0].tolist():
+                ndcg += dcg[i] / (run[m[i] - 1] if m[i] > 0 else 0.0)
+        return ndcg / self._n

@@ -41,6 +41,8 @@ FLAG_SPARSE_UPDATE = 32      # row-sparse optimizer steps for every block that e
 FLAG_DENSE_UPDATE = 64       # never: lasagne's dense pass over every parameter
 FLAG_BF16_PROJECTION = 128   # output projection on plain bf16 operands (one MFMA per block) -- training forward of CCE, predict, top-k
 FLAG_BF16_LAYERS = 256       # the dense GEMMs between stacked layers (input projection of layer >= 2 and its backward pair) on plain bf16 operands
+# sbr_evaluate's exclusion modes (include/sbr_rnn.h)
+EVAL_EXCL_NONE, EVAL_EXCL_VIEWED, EVAL_EXCL_WINDOW, EVAL_EXCL_WINDOW_ZERO = 0, 1, 2, 3
 
 
 class SbrConfig(ctypes.Structure):
@@ -69,7 +71,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_cluster_mask_scores", "sbr_cluster_hard", "sbr_cluster_lists", "sbr_cluster_rank",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
-           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch"]
+           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate"]
 
 _lib = None
 
@@ -160,6 +162,7 @@ def load_library(path=None):
                                               ctypes.POINTER(i32p)]
     lib.sbr_plan_pass_host.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, vp, vp, i32p, vp, vp, vp, vp, i64p, i64p]
     lib.sbr_build_batch.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint64]
+    lib.sbr_evaluate.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -458,6 +461,7 @@ class RNNEngine(object):
             self._check(self.lib.sbr_param_shape(self.h, i, dims, ctypes.byref(nd)))
             self.param_shapes.append(tuple(int(d) for d in dims[:nd.value]))
         self._sections = {}
+        self.evaluate_calls = 0      # calls of evaluate() so far (tests: which road an evaluation took)
 
     # ---------------------------------------------------------------- plumbing
     def _check(self, rc):
@@ -718,6 +722,30 @@ class RNNEngine(object):
         p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
         self._check(self.lib.sbr_rank(self.h, k, int(bool(exclude_input)), p(excl_ids), p(excl_off), p(ids), p(scores)))
         return (ids, scores) if return_scores else ids
+
+    def evaluate(self, dataset, users, k, exclude_mode, want_ids=False, want_mask=True):
+        """Whole users of a DeviceDataset evaluated on the device (sbr_evaluate): each user's sequence is split in the middle, the
+        last max_length items of the viewed half go in, the ranking to depth k is compared with the rest.  exclude_mode: one of
+        EVAL_EXCL_*.  Returns a dict of int32 arrays over the n users, in the order given: "n_pred" (places filled), "hits"
+        (|set(goal) & set(top-k)|), "first_hit" (goal[0] among the top-k), "item_hits" (n_items,: how often an item was a correct
+        prediction), "hitmask" (uint32 (n, ceil(k / 32)): bit p = the id at place p is a goal item; None without want_mask) and
+        "ids" ((n, k), exactly rank()'s, -1 in the unfilled places; None without want_ids)."""
+        self._rank_local_flush("evaluate")
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        n, k = len(users), int(k)
+        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
+            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
+        out = {"n_pred": np.empty(n, np.int32), "hits": np.empty(n, np.int32), "first_hit": np.empty(n, np.int32),
+               "item_hits": np.empty(self.n_items, np.int32),
+               "hitmask": np.empty((n, (k + 31) // 32), np.uint32) if want_mask else None,
+               "ids": np.empty((n, k), np.int32) if want_ids else None}
+        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        self.evaluate_calls += 1
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.sbr_evaluate(self.h, dataset.d, ctypes.c_void_p(users.ctypes.data) if n else None, n, k, int(exclude_mode),
+                                              p(out["ids"]), p(out["n_pred"]), p(out["hits"]), p(out["first_hit"]), p(out["hitmask"]),
+                                              p(out["item_hits"])))
+        return out
 
     # ---------------------------------------------------------------- debug / timing
     def debug_buffer(self, name):

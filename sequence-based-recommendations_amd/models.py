@@ -382,12 +382,42 @@ class RNNBase(object):
                                              if ts.bias >= 0.0 else None),
                                   n_targets=self._engine_targets() if multi else 1)
 
+    native_eval = True          # evaluate() ranks what this model's test function / top_k_recommendations rank (RNNCluster: no, it ranks inside a cluster)
+
+    def native_evaluator(self, dataset, which, k, mode, want_ids=False):
+        """Every user of dataset's "validation" / "test" set evaluated by ONE engine call (RNNEngine.evaluate: split in the middle,
+        the last max_length viewed items in, the rest as goal -- what _gen_mini_batch(test=True) and test.run_tests do per user),
+        as a data.NativeEvaluator; mode: engine.EVAL_EXCL_*.  None -> the per-user host road: SBR_NATIVE_EVAL=0, a data-parallel
+        wrapper (its collectives own the ranking calls), a cluster model, a stand-in engine without evaluate(), or a target
+        selection that may drop a test row (--rand_test_target with --target_bias)."""
+        ts = self.target_selection
+        if os.environ.get("SBR_NATIVE_EVAL", "1") == "0" or self.dp is not None or not self.native_eval or not hasattr(self.engine, "evaluate"):
+            return None
+        if getattr(dataset, which + "_set").shuffle or (which == "validation" and not ts.determinist_test and ts.bias >= 0.0):
+            return None      # (users in file order only; a validation row without a target is skipped by the host road)
+        from .data import NativeEvaluator
+        ds = dataset.device_set(which, self.engine, ratings=self.use_ratings_features)
+        print("Opening file (1)")                            # (the line the set's generator prints for its one pass)
+        lens = ds.offsets[1:] - ds.offsets[:-1]
+        users = np.nonzero(lens >= 2)[0].astype(np.int32)    # SequenceGenerator's min_length = 2 (data_handling.py:143)
+        rec = self.engine.evaluate(ds, users, k, mode, want_ids=want_ids, want_mask=True)
+        goals = None
+        if want_ids:
+            goals = [ds.items[ds.offsets[u] + lens[u] // 2:ds.offsets[u + 1]].tolist() for u in users.tolist()]
+        ev = NativeEvaluator(dataset, k=k)
+        ev.add_records(rec, (lens - lens // 2)[users], goals=goals)
+        return ev
+
     def _compute_validation_metrics(self, metrics):
         from .data import Evaluator
-        ev = Evaluator(self.dataset, k=10)
-        for goals, ids in self.batched_test_predictions(self.dataset.validation_set(epochs=1), k=10):
-            for goal, row in zip(goals, ids):
-                ev.add_instance(goal, row)
+        from .engine import EVAL_EXCL_NONE, EVAL_EXCL_WINDOW, EVAL_EXCL_WINDOW_ZERO
+        mode = {0: EVAL_EXCL_NONE, 1: EVAL_EXCL_WINDOW, 2: EVAL_EXCL_WINDOW_ZERO}[int(self._exclude_mode())]
+        ev = self.native_evaluator(self.dataset, "validation", 10, mode)
+        if ev is None:
+            ev = Evaluator(self.dataset, k=10)
+            for goals, ids in self.batched_test_predictions(self.dataset.validation_set(epochs=1), k=10):
+                for goal, row in zip(goals, ids):
+                    ev.add_instance(goal, row)
         metrics["recall"].append(ev.average_recall())
         metrics["sps"].append(ev.sps())
         metrics["ndcg"].append(ev.average_ndcg())
@@ -828,6 +858,7 @@ class RNNCluster(RNNBase):
         return list(np.argpartition(-scores, range(k))[:k]), self.n_items
 
     batched_top_k = True
+    native_eval = False         # evaluation stays on the per-user road: a cluster model ranks inside each user's item cluster
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per

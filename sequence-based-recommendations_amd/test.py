@@ -42,8 +42,22 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
     engine the whole viewed half as an exclusion list.
     A cluster model (`--clusters C`, test.py:61-76) ranks inside each user's item cluster: every user with a viewed half goes
     through RNNCluster.top_k_batch at any k -- never through the engine's whole-catalogue test function -- and nb_of_dp is the
-    mean number of items scored per user, the size of the user's cluster."""
+    mean number of items scored per user, the size of the user's cluster.
+    By default none of that loop runs: the whole set is evaluated by one engine call (RNNBase.native_evaluator, sbr_evaluate) and
+    the returned evaluator is a data.NativeEvaluator with the same metrics, equal with ==."""
     predictor.load(model_file)
+    # the whole test set in one engine call (RNNBase.native_evaluator): every user here has a viewed half -- the set's generator
+    # skips sequences of fewer than two items -- and the engine excludes all of it, also what no longer fits the window.  Not
+    # with --save_rank, not for a cluster model, not with SBR_NATIVE_EVAL=0: those take the per-user road below.
+    if not get_full_recommendation_list and getattr(args, "clusters", 0) <= 0 and hasattr(predictor, "native_evaluator"):
+        from .engine import EVAL_EXCL_NONE, EVAL_EXCL_VIEWED
+        start = time.perf_counter()
+        evaluator = predictor.native_evaluator(dataset, "test", k, EVAL_EXCL_VIEWED if predictor.interactions_are_unique else EVAL_EXCL_NONE,
+                                               want_ids=True)
+        if evaluator is not None:
+            print("Timer: ", time.perf_counter() - start)
+            evaluator.nb_of_dp = dataset.n_items                                                       # test.py:73-76
+            return evaluator
     evaluator = Evaluator(dataset, k=k)
     if get_full_recommendation_list:
         k = dataset.n_items
