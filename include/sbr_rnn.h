@@ -349,7 +349,9 @@ int sbr_enable_timing(sbr_handle* h, int on);
  * "scatter_form" (the scatter-add of layer 0's index-input gradient rows: -1 no step yet, 0 sorted segment reduce, 1 range form,
  * 2 segment-parallel form, 3 per-element atomics of SBR_FLAG_ATOMIC_SCATTER, 4 / 5 the overlapped tail's polling reduce / its
  * LDS-row kernel), "row_aware_update" (1: its optimizer pass over layer 0's W_in was the row-aware one), "tail_gate_first" (1: the side
- * stream of its overlapped tail was released by the gate on the BPTT chain's progress words at its head, 0: by a main-stream record). */
+ * stream of its overlapped tail was released by the gate on the BPTT chain's progress words at its head, 0: by a main-stream record),
+ * "step_join_gate" / "step_fork_gate" (1: the step's end joined its consumer streams through the gate on their completion words /
+ * its start released the second side stream by the forward chain's start word; 0: by events on the main stream). */
 int sbr_query(sbr_handle* h, const char* what, int64_t* value);
 int sbr_phase_times(sbr_handle* h, float us[SBR_N_PHASES]);
 /* Chain-only timing (ABI 8; tooling: bench.py prices the recurrent chain kernels of stacked layers apart from the dense GEMMs

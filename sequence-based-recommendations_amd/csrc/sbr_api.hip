@@ -425,6 +425,9 @@ extern "C" int sbr_create(const sbr_config* cfg, void* arena, size_t arena_bytes
                              //  main stream and the step takes 0.76 ms instead of 0.33 -- profiles/round6_variants.txt, call m)
 #endif
     memset(h->lag_host, 0, 8 * sizeof(float));
+    if (hipMalloc(&h->step_words, 160 * sizeof(int)) != hipSuccess || hipMemset(h->step_words, 0, 160 * sizeof(int)) != hipSuccess) {
+        sbr_set_error("step boundary words: allocation failed"); sbr_destroy(h); return SBR_EHIP;
+    }
     // parameters, gradients, optimizer state and batch buffers start as zeros
     // (activations too: one-off, keeps every later GEMM operand finite)
     hipError_t e = hipMemsetAsync(h->arena, 0, h->lay.s_end * sizeof(float), h->stream);
@@ -460,6 +463,7 @@ extern "C" void sbr_destroy(sbr_handle* h) {
     if (h->own_arena && h->arena) (void)hipFree(h->arena);
     if (h->tail_trace) (void)hipFree(h->tail_trace);
     if (h->tail_slab_dev) (void)hipFree(h->tail_slab_dev);
+    if (h->step_words) (void)hipFree(h->step_words);
     if (h->rank_scratch) (void)hipFree(h->rank_scratch);
     delete h;
 }
@@ -728,6 +732,12 @@ static int tail_next_epoch(sbr_handle* h) {
     h->prog_epoch = (h->prog_epoch + 1) & 0x7FFFF; if (!h->prog_epoch) h->prog_epoch = 1;
     return h->prog_epoch;
 }
+// Step boundary (kStepJoinGate / kStepForkGate): the epoch of the completion words / of the start word advances once per step that
+// publishes them, by the same rule -- a word the step before left carries the epoch before, never this one, and never 0 (the
+// words start as zeros).  Both timing marks of the boundary (0: in front of the forward, 6: between the two joins) are event
+// records on the main stream at the very points the gates take the events from: with either of them on, the events stay.
+static int step_next_epoch(int* e) { *e = (*e + 1) & 0x7FFFFFFF; if (!*e) *e = 1; return *e; }
+static bool step_boundary_marks(const sbr_handle* h) { return h->timing && (h->timing_marks & ((1u << 0) | (1u << 6))); }
 // the chain's progress words of this step's overlapped tail, one per wave of rec_bwd_x6p
 static int* tail_words(sbr_handle* h, int* nwaves) {
     *nwaves = (h->lay.Bp / rec_args(h, 0).rpt) * 8;
@@ -952,15 +962,31 @@ extern "C" int sbr_forward(sbr_handle* h) {
     // the scatter-add behind the 45 us of the time-chunked sort.  The sort needs nothing but the batch: it runs now, beside the
     // forward chain, for one event record in front of it.  The forward chain claims its CUs' LDS while the sort (118 KB of LDS
     // histogram per workgroup) runs beside it, so the two do not share CUs.
-    if (h->tail_nc >= 2 && h->sw.tail_overlap == 1) {
-        if (!forked) SBR_HIP(hipEventRecord(h->ev_fork, s));
-        SBR_HIP(hipStreamWaitEvent(h->side2, h->ev_fork, 0));
+    // Step start without an event (kStepForkGate; single-call step, one layer, one direction, rec_fwd_x6p): the forward chain stores a
+    // start word of this step's epoch at its entry, and a one-wave gate on that word stands at the head of the second side stream
+    // where the record / wait pair stood -- a word of this epoch means that everything in front of the chain on the main stream is
+    // complete and written back, the batch included.  The chain is launched FIRST: a gate is only ever enqueued behind the kernel
+    // that releases it, so a forward launch that fails leaves no gate waiting.  
+    auto early_sort = [&]() -> int {
         SBR_LAUNCH(launch_scatter_sort(h->side2, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, (int*)h->A(y.a_scnt),
                                        (int*)h->A(y.a_soff), (int*)h->A(y.a_scur), (int*)h->A(y.a_sid), (int*)h->A(y.a_spos), 0,
                                        h->tail_ch, h->tail_nc, &h->tail_bounds, &h->scnt_zero_n));
         h->tail_sorted = true;
-        { const int rc = tail_cost_scan(h); if (rc != SBR_OK) return rc; }
+        return tail_cost_scan(h);
+    };
+    h->fork_gated = false; h->step_word_epoch = 0;
+    const bool sort_early = h->tail_nc >= 2 && h->sw.tail_overlap == 1;
+    bool fork_gate = false;
+    if (kStepForkGate && sort_early && h->in_train_step && y.L == 1 && y.D == 1 && !forked && !step_boundary_marks(h) && !simple_rec(h)) {
+        const RecArgs r0 = rec_args(h, 0);
+        fork_gate = sbr_rec_x6p_ok(r0) && !sbr_rec_cluster_ok(r0);
     }
+    if (sort_early && !fork_gate) {
+        if (!forked) SBR_HIP(hipEventRecord(h->ev_fork, s));
+        SBR_HIP(hipStreamWaitEvent(h->side2, h->ev_fork, 0));
+        { const int rc = early_sort(); if (rc != SBR_OK) return rc; }
+    }
+    if (training) h->last_fork_gate = fork_gate;
     if (y.D == 2) return forward_bi(h);
     for (int l = 0; l < y.L; ++l) {
         const LayerLayout& ly = y.layer[l];
@@ -985,8 +1011,14 @@ extern "C" int sbr_forward(sbr_handle* h) {
             SBR_LAUNCH(launch_gemm(s, h->A(lo.a_hs) + (size_t)y.Bp * lo.Hp, lo.Hp, 1, h->P(ly.p_Win), GHp, 1, h->A(ly.a_xt), GHp,
                                    y.T * y.Bp, GHp, lo.Hp, h->P(ly.p_b), nullptr, 0, simple_gemm(h)));
         }
-        if (l == 0 && h->tail_sorted) ra.fence_kb = kTailFenceKb;
+        if (l == 0 && (h->tail_sorted || fork_gate)) ra.fence_kb = kTailFenceKb;
+        if (fork_gate) { ra.start_word = h->step_words + 128; ra.start_epoch = step_next_epoch(&h->fork_epoch); }
         SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, simple_rec(h)));
+        if (fork_gate) {
+            h->fork_gated = true; h->step_word_epoch = h->fork_epoch;
+            SBR_LAUNCH(launch_step_gate(h->side2, h->step_words + 128, nullptr, h->fork_epoch, (int*)h->A(y.a_fault)));
+            { const int rc = early_sort(); if (rc != SBR_OK) return rc; }
+        }
     }
     mark(h, 2);
     h->fwd_done = true;
@@ -1033,6 +1065,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
     h->side_pending = true;
     h->fill_done = false;
     h->tail_gated = false; h->last_tail_gated = 0;
+    h->last_join_gate = 0;
     // Work on the side stream that needs only the batch: the sentinel fill of the cluster BPTT kernels' exchange arrays and
     // the sort for the embedding scatter-add (the scatter kernel waits for ev_sort).  With cluster kernels it starts now,
     // beside the output phase (its own fork event); otherwise it rides behind the ev_lg wait the side stream needs anyway
@@ -1092,9 +1125,11 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
             int* words = tail_words(h, &nwaves);
             SBR_LAUNCH(launch_tail_gate_wave(sd, words, nwaves, tail_next_epoch(h), y.T, (int*)h->A(y.a_fault)));
             h->tail_gated = true;
-            h->ev_lg_rec = nullptr; h->ev_step_rec = h->ev_fork; h->lg_seq = h->batch_seq;      // (ev_fork: sbr_forward, in front of the sort)
+            // (what sbr_build_batch orders itself behind: sbr_forward's fork -- its record, or the chain's start word where there is none)
+            h->ev_lg_rec = nullptr; h->ev_step_rec = h->fork_gated ? nullptr : h->ev_fork; h->lg_seq = h->batch_seq;
         } else {
             h->ev_lg_rec = h->ev_step_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
+            h->step_word_epoch = 0;      // (the record is the later point of the step: the builder takes it)
             SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
         }
         return SBR_OK;
@@ -1391,7 +1426,16 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                                                   (const int*)h->A(y.a_soff), y.cfg.input_size, tnc, CH, y.T * y.Bp * y.F, GHp, y.Bp, pl,
                                                   0, &h->tail_bounds, kTailShortChunks, !serial && kTailFenceKb > 0));
             }
+            // Step end without an event wait (kStepJoinGate; single-call step): behind the last kernel of either consumer stream a
+            // one-lane kernel stores a completion word of this step's epoch at its entry (kernel to kernel on one queue: no gap), and
+            // ONE gate on both words, behind this stream's own last kernel, is the join.  The events are still recorded on their
+            // streams (sbr_join_side, the data-parallel driver and callers that restore or read parameters from another stream use
+            // them).  DESIGN.md section 3f.
+            const bool join_gate = kStepJoinGate && upd_here && !serial && !step_boundary_marks(h);
+            if (join_gate) step_next_epoch(&h->join_epoch);
+            h->last_join_gate = join_gate;
             if (upd_here) SBR_LAUNCH(upd_on(s2, ly.p_Win, ly.p_b));
+            if (join_gate) SBR_LAUNCH(launch_step_word(s2, h->step_words + 96, h->join_epoch));
             SBR_HIP(hipEventRecord(h->ev_tail2, s2));
             // single-call step: the slab reduction IS the W_hid update (one launch, one pass less behind the chain); phase-by-phase
             // callers (data parallel) need the reduced gradient
@@ -1403,6 +1447,7 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                 SBR_LAUNCH(launch_splitk_reduce(sd, ws2, n_slabs, ly.Hp, GHp, h->Gd(ly.p_Whid), GHp, nullptr));
                 if (upd_here) SBR_LAUNCH(upd_on(sd, ly.p_Whid, ly.p_peep));
             }
+            if (join_gate) SBR_LAUNCH(launch_step_word(sd, h->step_words + 32, h->join_epoch));
             SBR_HIP(hipEventRecord(h->ev_tail, sd));
             // main stream, behind the chain
             SBR_LAUNCH(launch_rec_reduce_partials(s, a.part, nblk, y.G, ly.Hp, y.cfg.cell, h->Gd(ly.p_b), h->Gd(ly.p_peep),
@@ -1420,6 +1465,11 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
                 // W_hid: side stream, the rest: this stream) and joins through sbr_join_side / sbr_apply_update
                 h->tail_join_pending = true;
                 mark(h, 6);
+                continue;
+            }
+            if (join_gate) {      // (no mark 6 here: step_boundary_marks)
+                SBR_LAUNCH(launch_step_gate(s, h->step_words + 32, h->step_words + 96, h->join_epoch, a.fault));
+                h->side_pending = false;
                 continue;
             }
             SBR_HIP(hipStreamWaitEvent(s, h->ev_tail2, 0));
@@ -2292,6 +2342,8 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     // what the LAST step launched for the gradient of layer 0's index-input rows (-1: no step yet): 0 sorted segment reduce, 1 range form,
     // 2 segment-parallel form, 3 per-element atomics (SBR_FLAG_ATOMIC_SCATTER), 4 / 5 the overlapped tail's polling reduce / LDS-row kernel
     else if (w == "scatter_form") *value = h->last_scatter_form;
+    else if (w == "step_join_gate") *value = h->last_join_gate;        // the last step's end: 1 joined by the gate on the consumers' completion words, 0 by events
+    else if (w == "step_fork_gate") *value = h->last_fork_gate;        // ... its start: 1 the second side stream released by the forward chain's start word, 0 by a record
     else if (w == "tail_gate_first") *value = h->last_tail_gated;      // the last step's side stream: 1 released by the gate at its head, 0 by a record
     // what the LAST sbr_rank ran (0: none yet): its select with the row's keys in LDS (1) or streamed (2), its sort in LDS (1) or in scratch (2)
     else if (w == "rank_select") *value = h->last_rank_select;

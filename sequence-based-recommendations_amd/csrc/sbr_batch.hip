@@ -668,7 +668,7 @@ extern "C" int sbr_build_batch(sbr_handle* h, sbr_dataset* d, int64_t batch, uin
     // two steps; tools/bench_train_loop.py).  Order: (1) the set it overwrites was read by the step before the one in flight --
     // every stream of a completed step is joined into the main stream by sbr_apply_update, so any main-stream record made DURING
     // the step in flight is behind it: the step records one anyway (ev_lg in front of the BPTT chain, or the forward's fork: sbr_handle.ev_step_rec), no extra record on the
-    // main stream; (2) without such a record (first batches, evaluation between steps, a step abandoned half way) the build
+    // main stream -- or, where the step forks without a record, its forward chain's start word says the same (step_word_epoch); (2) without such a record (first batches, evaluation between steps, a step abandoned half way) the build
     // waits for a fresh record on each of the engine's streams; (3) the main stream waits for the build (long complete by then).
     // The dataset's own arrays change only inside calls that synchronise d->stream first and last, i.e. behind (3).
     hipStream_t s = h->s_bb;
@@ -677,6 +677,10 @@ extern "C" int sbr_build_batch(sbr_handle* h, sbr_dataset* d, int64_t batch, uin
     if (h->bb_unread && h->bb_slow == 0) h->bb_slow = 1;      // two builds and no forward between them: whoever read the first did it outside a step
     if (h->bb_slow == 0 && h->ev_step_rec && h->lg_seq > h->set_use[set]) {
         SBR_HIP(hipStreamWaitEvent(s, h->ev_step_rec, 0));
+    } else if (h->bb_slow == 0 && h->step_word_epoch && h->step_words && h->lg_seq > h->set_use[set]) {
+        // the step in flight made no record: its forward chain publishes a start word instead (kStepForkGate, sbr_forward), and "the
+        // forward chain of the step in flight has started" is what the record meant -- the same one-wave gate the second side stream has
+        SBR_LAUNCH(launch_step_gate(s, h->step_words + 128, nullptr, h->step_word_epoch, (int*)h->A(y.a_fault)));
     } else {
         hipStream_t all[4] = {h->stream, h->side, h->side2, h->side3};
         for (hipStream_t q : all) { SBR_HIP(hipEventRecord(h->ev_bbw, q)); SBR_HIP(hipStreamWaitEvent(s, h->ev_bbw, 0)); }

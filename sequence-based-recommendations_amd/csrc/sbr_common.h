@@ -159,6 +159,9 @@ constexpr double kTailSlabGrowth = 0.35;  // k steps of a slab per time step of 
 // the side stream of a single-call step (profiles/tail_release_variants.txt):
 constexpr bool kTailGateFirst = true;     // released by the chain's progress words (a one-wave gate at its head) instead of a main-stream record
 constexpr int kTailGateSleep = 32;        // ... whose polls of ONE word are this many s_sleep units (64 clocks each) apart until the chain appears
+// the boundary between two such steps (profiles/step_boundary_variants.txt): no event on the main stream
+constexpr bool kStepJoinGate = true;      // step end: a one-wave gate on the completion words of the two consumer streams joins them
+constexpr bool kStepForkGate = true;      // step start: the second side stream (and the batch builder) wait for the forward chain's start word
 // growth of the small time chunks near t = 0 (tail_plan, sbr_api.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
 // walks them one after the other; 1, 3, 7, 18 for the polling range form
 static inline double sbr_tail_geom(int scatter_lds) { return scatter_lds ? 1.6 : 2.6; }
@@ -266,6 +269,15 @@ struct sbr_handle {
     std::vector<int> tail_slab_host; int* tail_slab_dev = nullptr; int tail_slab_key[2] = {0, 0};   // the table of the last plan
     int prog_epoch = 0;          // epoch of the chain's progress words: advanced once per step by tail_next_epoch (sbr_api.hip)
     bool tail_gated = false;     // this step: the side stream is already behind a gate on this step's epoch (sbr_loss_backward_output)
+    // Words of the step boundary (kStepJoinGate / kStepForkGate): an allocation of its own, made and zeroed on first use and freed by
+    // sbr_destroy; each word on a 128-byte line of its own.  [32]: completion word of the side stream, [96]: of the second side
+    // stream, [128]: the forward chain's start word.
+    int* step_words = nullptr;
+    int join_epoch = 0, fork_epoch = 0;   // epochs of the completion words / the start word: advanced by step_next_epoch (sbr_api.hip), never 0
+    bool fork_gated = false;              // this step: the second side stream was released by the start word (sbr_forward)
+    int last_join_gate = -1, last_fork_gate = -1;                         // what the last step took: sbr_query "step_join_gate" / "step_fork_gate"
+    int step_word_epoch = 0;     // != 0: the forward chain of the step in flight publishes this epoch in its start word (sbr_build_batch waits for it
+                                 // where it waited for ev_step_rec)
     hipEvent_t ev_step_rec = nullptr; // a main-stream record made DURING the step in flight, for sbr_build_batch: ev_lg_rec, or the forward's fork
     bool tail_updated = false;   // this step: the overlapped tail has applied the optimizer itself (single-call step)
     bool tail_join_pending = false; // overlapped tail of a phase-by-phase step: the main stream has not joined the consumer streams yet
@@ -364,6 +376,11 @@ int sbr_scatter_lds_ids();     // largest key space the LDS-histogram sort takes
 hipError_t launch_tail_gate(hipStream_t s, const int* progress, int n, int epoch, int target, int* fault);
 // ... the same wait as ONE wave that may be launched long before the chain (it sits beside the forward chain and the head)
 hipError_t launch_tail_gate_wave(hipStream_t s, const int* progress, int n, int epoch, int target, int* fault);
+// step boundary: ONE wave waits (bounded: SBR_POLL_TICKS, fault bit 3) until w0[0] == epoch and, where w1 is given, w1[0] == epoch
+hipError_t launch_step_gate(hipStream_t s, const int* w0, const int* w1, int epoch, int* fault);
+// ... and what it waits for at the end of a stream: a one-lane kernel that stores `epoch` into `word` at its entry, i.e. once
+// everything in front of it on stream s is complete and written back
+hipError_t launch_step_word(hipStream_t s, int* word, int epoch);
 // emb[t][b][f*Ep + e] = W_emb[X[b][t][f]][e]          (lasagne EmbeddingLayer + flatten(outdim=3), recurrent_layers.py:48)
 hipError_t launch_gather_concat(hipStream_t s, const float* Wemb, const int* X, float* out, int T, int Bp, int F, int Ep);
 // --r_bi helpers (sbr_misc.hip).  rev(t, len) = t < len ? len-1-t : t (padding stays in place).
@@ -461,6 +478,9 @@ struct RecArgs {
     // (prog_epoch << 12) | t in progress[block * 8 + wave] once all its time steps >= t are complete: at launch (t = first
     // live step + 1 ...), whenever t is a multiple of prog_every, and t_lo at the end.  NULL: plain stores, no progress
     int* progress; int prog_every; int prog_epoch;
+    // step boundary (rec_fwd_x6p only): one lane of workgroup 0 stores start_epoch here at kernel entry, write-through -- whoever polls it
+    // learns that everything in front of this launch on its stream is complete and written back.  NULL: nothing is stored
+    int* start_word; int start_epoch;
     int fence_kb;           // rec_*_x6p: the workgroup claims this much of its CU's LDS (KiB; 0: what it needs) so that kernels which
                             // run BESIDE the chain and use LDS themselves are placed on other CUs (overlapped step tail)
 };

@@ -1393,6 +1393,39 @@ hipError_t launch_tail_gate_wave(hipStream_t s, const int* progress, int n, int 
     return hipGetLastError();
 }
 
+// Gate of the step boundary (sbr_api.hip: the join of the consumer streams at the end of a single-call step with the overlapped
+// tail, the release of the second side stream and of the batch builder at its start): one wave, no LDS, returns once w0[0] (and
+// w1[0], where given) hold `epoch`.  The words are stored write-through by kernels that were enqueued BEFORE this one
+// (step_word_kernel behind the last kernel of a consumer stream; the forward chain's entry: RecArgs.start_word), so the wait ends
+// by itself; the bound and the fault bit are tail_gate_kernel's all the same.  Relaxed agent-scope loads, s_sleep between polls;
+// what is enqueued behind the gate sees the publishers' data through its own kernel-start acquire.
+__global__ void __launch_bounds__(64) step_gate_kernel(const int* __restrict__ w0, const int* __restrict__ w1, int epoch, int* __restrict__ fault) {
+    const unsigned long long t0 = wall_clock64();
+    for (;;) {
+        const int a = __hip_atomic_load(w0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const int b = w1 ? __hip_atomic_load(w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : epoch;
+        if (a == epoch && b == epoch) break;
+        if (wall_clock64() - t0 > SBR_POLL_TICKS) { if (threadIdx.x == 0) atomicOr(fault, 8); return; }
+        __builtin_amdgcn_s_sleep(8);
+    }
+}
+hipError_t launch_step_gate(hipStream_t s, const int* w0, const int* w1, int epoch, int* fault) {
+    if (!w0 || !epoch) return hipErrorInvalidValue;
+    step_gate_kernel<<<1, 64, 0, s>>>(w0, w1, epoch, fault);
+    return hipGetLastError();
+}
+// The completion word of a stream: one lane stores `epoch`, write-through, as the first thing it does.  That this kernel has
+// started means that everything in front of it on its stream is complete and written back (the argument of tail_gate_wave_kernel
+// above and of RecArgs.start_word) -- the release is the one the queue makes at the end of every kernel, once, for all XCDs.
+__global__ void __launch_bounds__(64) step_word_kernel(int* __restrict__ word, int epoch) {
+    if (threadIdx.x == 0) __hip_atomic_store(word, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+hipError_t launch_step_word(hipStream_t s, int* word, int epoch) {
+    if (!word || !epoch) return hipErrorInvalidValue;
+    step_word_kernel<<<1, 64, 0, s>>>(word, epoch);
+    return hipGetLastError();
+}
+
 // triage fallback: per-element float atomics (SBR_FLAG_ATOMIC_SCATTER)
 __global__ void scatter_rows_kernel(float* __restrict__ dWin, const f32x4* __restrict__ dxt, const int* __restrict__ X,
                                     const int* __restrict__ len, int T, int Bp, int F, int R4) {

@@ -173,6 +173,9 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
     const int u = wave * 16 + j;
     const int T = a.T, Bp = a.Bp;
     if (threadIdx.x < 8) cnt[threadIdx.x] = 0;
+    // step boundary (RecArgs.start_word): this launch has started, i.e. everything in front of it on its stream is complete
+    if (a.start_word && blockIdx.x == 0 && threadIdx.x == 0)
+        __hip_atomic_store(a.start_word, a.start_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (write-through: pollers sit on other XCDs)
     const bool roleA = wave < 4;                         // waves w and w + 4 share a SIMD; the older one owns the pipe
     int spin_limit = X6P_SPIN_LIMIT;                     // (drops to 64 once this wave has raised the fault flag)
     const unsigned lds_tok = (unsigned)(size_t)(tok + (wave & 3));
