@@ -471,6 +471,52 @@ int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n,
                  uint32_t* hitmask_host,   /* NULL, or [n][(k + 31) / 32]: bit p of a row = the id at place p is a goal item */
                  int32_t* item_hits_host); /* NULL, or [N]: over all n users, how often item i was a correct prediction */
 
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation of whole users of a cluster model on the device (added under ABI 11: one symbol and one struct, nothing existing
+ * changes) -- sbr_evaluate for `--clusters C`: RNNCluster._compute_validation_metrics (rnn_cluster.py:409-438, one compiled test
+ * function call per user) and test.py:61-76 (one top_k_recommendations call per user).  Users are split, fed, chunked
+ * (local_batch per chunk) and compared with the goal exactly as by sbr_evaluate; the handle is left as sbr_set_batch leaves it;
+ * everything is enqueued on the engine's stream and the host waits once, at the end of the call.  A row's cluster is what
+ * sbr_cluster_select returns for it.
+ *   whole    when given: exactly what sbr_evaluate returns for the same users, k and exclude_mode -- from the same forward pass.  (On
+ *            the PRODUCT road of a margin loss, SBR_EVAL_EXCL_WINDOW ranks the whole catalogue as SBR_EVAL_EXCL_WINDOW_ZERO, the
+ *            compiled test function's arithmetic on raw outputs.)
+ *   inside, SBR_CEVAL_LISTS    per chunk exactly sbr_cluster_rank's ids for the packed rows: only the members of the row's cluster
+ *            are ranked, score descending, ties to the lowest id, -1 behind the rankable members (k may exceed a cluster's size; a
+ *            cluster may be empty), n_pred < k then.  SBR_EVAL_EXCL_VIEWED: the whole viewed half is never ranked; _WINDOW: the
+ *            items fed; _NONE: nothing; read from the dataset's device CSR, no list is built or uploaded.  Both forms of
+ *            sbr_cluster_rank stay, chosen by the same switches; sbr_query "cluster_rank_form" reports the one taken.
+ *   inside, SBR_CEVAL_PRODUCT  the N scores p * m of a row are ranked by sbr_rank's kernels, p the float sbr_predict_scores with
+ *            probs = 1 writes for (row, item) -- the same device code computes it --, m the float sbr_cluster_hard holds at
+ *            [item][cluster of the row], the product one f32 multiply.  SBR_EVAL_EXCL_WINDOW: the items fed score +0.0 and stay
+ *            rankable; _NONE: every score as it is.  size_host must be NULL.
+ * The hits of both rankings follow sbr_evaluate's rule.  SBR_EINVAL, found before anything is launched (engine and head stay usable):
+ * everything sbr_evaluate rejects, everything sbr_cluster_rank rejects about c against h (items, width and split, stream), a mode
+ * the road does not take (LISTS: _WINDOW_ZERO; PRODUCT: _VIEWED, _WINDOW_ZERO), inside == NULL, a NULL n_pred / hits / first_hit in
+ * a given sbr_eval_out, size_host on the PRODUCT road.  Parameters, gradients and optimizer state of engine and head are touched
+ * only by bringing lazily stepped output rows up to date and by building the member lists (LISTS) or the membership matrix and its
+ * transposed copy (PRODUCT) for the current R.  Scratch: the handle's ranking scratch, sized once per call.
+ * Host waits besides the one at the end, all BEFORE the first chunk is enqueued and none between chunks: the ranking scratch growing
+ * (hipFree / hipMalloc), the first call for a dataset (its sorted goals are uploaded), and once per version of R the member lists
+ * (LISTS: their sizes are read back) or, on the first PRODUCT call of a head, the hipMalloc of the transposed copy (N * C floats). */
+typedef struct sbr_eval_out {          /* one ranking's results, as the host outputs of sbr_evaluate */
+    int32_t* ids;        /* NULL or [n][k] */
+    int32_t* n_pred;     /* [n] */
+    int32_t* hits;       /* [n] */
+    int32_t* first_hit;  /* [n] */
+    uint32_t* hitmask;   /* NULL or [n][(k+31)/32] */
+    int32_t* item_hits;  /* NULL or [N] */
+} sbr_eval_out;
+#define SBR_CEVAL_LISTS   0   /* test.py:61-76 / top_k_recommendations: rank inside members(c), the lists of sbr_cluster_lists */
+#define SBR_CEVAL_PRODUCT 1   /* the compiled test function, rnn_cluster.py:327-352: rank softmax * f(100 R)[:, c] over the catalogue */
+int sbr_cluster_evaluate(sbr_cluster* c, sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k,
+                         int road, int exclude_mode,
+                         const sbr_eval_out* whole,    /* NULL, or the whole-catalogue ranking of the same forward pass */
+                         const sbr_eval_out* inside,   /* required: the cluster ranking */
+                         int32_t* cluster_host,        /* [n] selected cluster */
+                         int32_t* size_host,           /* NULL or [n]: len(members(c)) (LISTS road) */
+                         int32_t* cluster_use_host);   /* NULL or [C]: users per selected cluster */
+
 #ifdef __cplusplus
 }
 #endif

@@ -2041,21 +2041,13 @@ extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* 
     return check_fault(h);          // a forward that gave up must not hand out rankings
 }
 
-// Whole users evaluated on the device (include/sbr_rnn.h: sbr_evaluate; kernels: sbr_eval.hip).  Per chunk of local_batch users:
-// pack -> forward + projection (full_scores) -> exclusion from the dataset's CSR -> sbr_rank's select and sort -> hits, all on the
-// main stream; the per-user results of every chunk land at the chunk's offset of arrays sized for the whole call, and the host
-// waits once, in check_fault.  The pack writes batch set 0 on the main stream like sbr_set_batch's device-to-device copies, behind every
-// reader of the set (sbr_build_batch's comment, sbr_batch.hip), and leaves the handle as that call does.
-extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int exclude_mode, int32_t* ids_host,
-                            int32_t* n_pred_host, int32_t* hits_host, int32_t* first_hit_host, uint32_t* hitmask_host, int32_t* item_hits_host) {
-    CHECK_ARG(h && d && users && n_pred_host && hits_host && first_hit_host, "null argument");
+// what sbr_evaluate and sbr_cluster_evaluate check about the users, k and the dataset against the engine; on SBR_OK v holds the sorted goals
+static int eval_check_args(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, SbrEvalView& v) {
     const Layout& y = h->lay;
-    SbrEvalView v;
     int rc;
     if ((rc = sbr_dataset_eval_view(d, &v, 0)) != SBR_OK) return rc;
     CHECK_ARG(n >= 1, "n=%lld users: at least one", (long long)n);
     CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
-    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW_ZERO, "unknown exclusion mode %d", exclude_mode);
     CHECK_ARG(y.F == 1 || (y.F == 2 && v.rate && y.cfg.input_size == y.N + 10),
               "a model with two indices per step needs the ratings attached to the dataset (sbr_dataset_set_options)");
     CHECK_ARG(v.n_items == y.N && (y.cfg.input_size == y.N || y.F == 2), "dataset has %d items, the model %d", v.n_items, y.N);
@@ -2064,9 +2056,37 @@ extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users,
         CHECK_ARG(users[j] >= 0 && users[j] < v.n_users, "users[%lld] = %d outside [0,%lld)", (long long)j, users[j], (long long)v.n_users);
         CHECK_ARG(v.h_off[users[j] + 1] - v.h_off[users[j]] >= 2, "user %d has fewer than two items: nothing to view or no goal", users[j]);
     }
-    if ((rc = sbr_dataset_eval_view(d, &v, 1)) != SBR_OK) return rc;      // (first call for this dataset: sorts and uploads the goals)
+    return sbr_dataset_eval_view(d, &v, 1);      // (first call for this dataset: sorts and uploads the goals)
+}
+
+// a chunk's rows become the current batch, in set 0, as sbr_set_batch would leave it
+static int eval_pack_chunk(sbr_handle* h, const SbrEvalView& v, const int* dusers, int rows) {
+    const Layout& y = h->lay;
+    hipStream_t s = h->stream;
+    h->bX = (const int*)h->A(y.a_X); h->blen = (const int*)h->A(y.a_len); h->btgt = (const int*)h->A(y.a_tgt);
+    h->bsmp = (const int*)h->A(y.a_smp); h->bpop = h->A(y.a_pop);
+    h->bb_set = 0; h->bb_unread = false;
+    if (rows < y.Bp && SBR_LOSS_IS_MARGIN(y.cfg.loss)) SBR_HIP(hipMemsetAsync(h->A(y.a_tgt), 0xFF, (size_t)y.Bp * y.NT * sizeof(int), s));   // no positives
+    SBR_LAUNCH(launch_ev_pack(s, v, dusers, rows, y.Bp, y.T, y.F, (int*)h->A(y.a_X), (int*)h->A(y.a_len), h->A(y.a_pop)));
+    h->n_rows = rows; h->have_batch = true; h->fwd_done = false;
+    return SBR_OK;
+}
+
+// Whole users evaluated on the device (include/sbr_rnn.h: sbr_evaluate; kernels: sbr_eval.hip).  Per chunk of local_batch users:
+// pack -> forward + projection (full_scores) -> exclusion from the dataset's CSR -> sbr_rank's select and sort -> hits, all on the
+// main stream; the per-user results of every chunk land at the chunk's offset of arrays sized for the whole call, and the host
+// waits once, in check_fault.  The pack writes batch set 0 on the main stream like sbr_set_batch's device-to-device copies, behind every
+// reader of the set (sbr_build_batch's comment, sbr_batch.hip), and leaves the handle as that call does.
+extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int exclude_mode, int32_t* ids_host,
+                            int32_t* n_pred_host, int32_t* hits_host, int32_t* first_hit_host, uint32_t* hitmask_host, int32_t* item_hits_host) {
+    CHECK_ARG(h && d && users && n_pred_host && hits_host && first_hit_host, "null argument");
+    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW_ZERO, "unknown exclusion mode %d", exclude_mode);
+    const Layout& y = h->lay;
+    SbrEvalView v;
+    int rc;
+    if ((rc = eval_check_args(h, d, users, n, k, v)) != SBR_OK) return rc;
     const int B = y.B, words = (k + 31) / 32;
-    const bool radix = k > kRankSortLds, margin = SBR_LOSS_IS_MARGIN(y.cfg.loss);
+    const bool radix = k > kRankSortLds;
     const size_t bk = (size_t)B * k, nk = (size_t)n * k;
     size_t at = 0;
     auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
@@ -2085,13 +2105,7 @@ extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users,
     if (item_hits_host) SBR_HIP(hipMemsetAsync(S + o_ihits, 0, (size_t)y.N * sizeof(int), s));
     for (int64_t c0 = 0; c0 < n; c0 += B) {
         const int rows = (int)std::min<int64_t>(B, n - c0);
-        // --- the chunk becomes the current batch, in set 0, as sbr_set_batch would leave it
-        h->bX = (const int*)h->A(y.a_X); h->blen = (const int*)h->A(y.a_len); h->btgt = (const int*)h->A(y.a_tgt);
-        h->bsmp = (const int*)h->A(y.a_smp); h->bpop = h->A(y.a_pop);
-        h->bb_set = 0; h->bb_unread = false;
-        if (rows < y.Bp && margin) SBR_HIP(hipMemsetAsync(h->A(y.a_tgt), 0xFF, (size_t)y.Bp * y.NT * sizeof(int), s));   // no positives
-        SBR_LAUNCH(launch_ev_pack(s, v, dusers + c0, rows, y.Bp, y.T, y.F, (int*)h->A(y.a_X), (int*)h->A(y.a_len), h->A(y.a_pop)));
-        h->n_rows = rows; h->have_batch = true; h->fwd_done = false;
+        if ((rc = eval_pack_chunk(h, v, dusers + c0, rows)) != SBR_OK) return rc;
         if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_rank ranks (and flushes lazily stepped rows)
         float* lg = h->A(y.a_logits);
         SBR_LAUNCH(launch_ev_exclude(s, v, dusers + c0, rows, y.T, y.N, exclude_mode, lg));
@@ -2189,6 +2203,146 @@ extern "C" int sbr_cluster_rank(sbr_cluster* c, sbr_handle* h, int k, int exclud
     if (cluster_host) SBR_HIP(hipMemcpyAsync(cluster_host, csel, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (size_host) SBR_HIP(hipMemcpyAsync(size_host, S + o_size, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return check_fault(h);          // a forward that gave up must not hand out rankings
+}
+
+// Whole users of a cluster model evaluated on the device (include/sbr_rnn.h: sbr_cluster_evaluate; kernels: sbr_cluster_eval.hip and
+// the ones sbr_evaluate and sbr_cluster_rank launch).  Per chunk of local_batch users: pack -> forward (+ projection where a full score
+// row is read) -> cluster selection -> the cluster ranking's score matrix, taken BEFORE any exclusion touches the full scores ->
+// [the whole-catalogue ranking, as sbr_evaluate runs it] -> exclusion, select, sort[, translate], hits of the cluster ranking.  All on
+// the main stream; results land at the chunk's offset of arrays sized for the whole call and the host waits once, in check_fault.
+struct CevRecords { size_t npred, hits, first, mask, ihits, oid; };
+static bool cev_out_ok(const sbr_eval_out* o) { return o->n_pred && o->hits && o->first_hit; }
+extern "C" int sbr_cluster_evaluate(sbr_cluster* c, sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int road,
+                                    int exclude_mode, const sbr_eval_out* whole, const sbr_eval_out* inside, int32_t* cluster_host,
+                                    int32_t* size_host, int32_t* cluster_use_host) {
+    CHECK_ARG(c && h && d && users && inside && cluster_host, "null argument");
+    CHECK_ARG(cev_out_ok(inside) && (!whole || cev_out_ok(whole)), "n_pred, hits and first_hit of a given sbr_eval_out are required");
+    CHECK_ARG(road == SBR_CEVAL_LISTS || road == SBR_CEVAL_PRODUCT, "unknown road %d", road);
+    const bool product = road == SBR_CEVAL_PRODUCT;
+    if (product) {
+        CHECK_ARG(exclude_mode == SBR_EVAL_EXCL_NONE || exclude_mode == SBR_EVAL_EXCL_WINDOW,
+                  "the PRODUCT road takes SBR_EVAL_EXCL_NONE or SBR_EVAL_EXCL_WINDOW, not mode %d", exclude_mode);
+        CHECK_ARG(!size_host, "size_host is the LISTS road's: the PRODUCT road ranks the whole catalogue");
+    } else
+        CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW,
+                  "the LISTS road takes SBR_EVAL_EXCL_NONE, _VIEWED or _WINDOW, not mode %d", exclude_mode);
+    const Layout& y = h->lay;
+    const int C = c->cfg.n_clusters, HL = y.cfg.layers[y.L - 1];
+    CHECK_ARG(c->cfg.n_items == y.N, "the cluster head has %d items, the engine %d", c->cfg.n_items, y.N);
+    CHECK_ARG(c->cfg.n_hidden == y.D * HL && c->cfg.hidden_split == HL, "the cluster head reads %d features (split %d), the engine's user representation has %d (split %d)",
+              c->cfg.n_hidden, c->cfg.hidden_split, y.D * HL, HL);
+    CHECK_ARG(c->stream == h->stream, "the cluster head and the engine are on different streams");
+    SbrEvalView v;
+    int rc;
+    if ((rc = eval_check_args(h, d, users, n, k, v)) != SBR_OK) return rc;
+    // once per call, before the chunk loop: the member lists (host sizes, Lmax) or the membership matrix of the current R
+    if ((rc = product ? sbr_cluster_build_hard(c, 1) : sbr_cluster_build_lists(c)) != SBR_OK) return rc;
+    const int B = y.B, words = (k + 31) / 32, N = y.N;
+    const int lmax = product ? 0 : c->lmax, kk = product ? k : std::min(k, lmax);      // kk: the depth ranked in the cluster matrix
+    // the restricted kernel restates the exact-f32 projection (sbr_cluster_rank's comment); every other case reads full score rows
+    const bool restricted = !product && h->sw.cluster_rank && !(y.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
+    const bool full = whole || !restricted;
+    const bool radix = k > kRankSortLds;                                                // (kk <= k: sized for the deeper one)
+    // the whole-catalogue ranking scores the items fed 0.0 where the compiled test function of a margin model does (_exclude_mode)
+    const int whole_mode = (product && exclude_mode == SBR_EVAL_EXCL_WINDOW && SBR_LOSS_IS_MARGIN(y.cfg.loss)) ? SBR_EVAL_EXCL_WINDOW_ZERO : exclude_mode;
+    const size_t bk = (size_t)B * k, nk = (size_t)n * k;
+    size_t at = 0;
+    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
+    auto records = [&](const sbr_eval_out* o) {
+        CevRecords r{};
+        if (!o) return r;
+        r.npred = take((size_t)n * sizeof(int)); r.hits = take((size_t)n * sizeof(int)); r.first = take((size_t)n * sizeof(int));
+        r.mask = take(o->hitmask ? (size_t)n * words * sizeof(unsigned) : 0); r.ihits = take(o->item_hits ? (size_t)N * sizeof(int) : 0);
+        r.oid = take((o->ids ? nk : bk) * sizeof(int));      // the ids of every user only when the caller fetches them
+        return r;
+    };
+    const size_t o_users = take((size_t)n * sizeof(int)), o_csel = take((size_t)n * sizeof(int)), o_size = take((size_t)n * sizeof(int));
+    const size_t o_use = take((size_t)C * sizeof(int));
+    const CevRecords rw = records(whole), ri = records(inside);
+    const size_t o_grp = take(restricted ? sbr_crk_group_words(B, C) * sizeof(int) : 0);
+    const size_t o_cs = take((size_t)B * (product ? N : lmax) * sizeof(float));
+    const size_t o_nsel = take((size_t)B * sizeof(int)), o_k0 = take(bk * sizeof(unsigned)), o_i0 = take(bk * sizeof(int));
+    const size_t o_k1 = take(radix ? bk * sizeof(unsigned) : 0), o_i1 = take(radix ? bk * sizeof(int) : 0), o_osc = take(bk * sizeof(float));
+    const size_t o_pos = take(product ? 0 : (size_t)B * kk * sizeof(int)), o_psc = take(product ? 0 : (size_t)B * kk * sizeof(float));
+    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    int* dcsel = (int*)(S + o_csel);
+    float* cs = (float*)(S + o_cs);
+    // (pageable host memory: the copy has left the caller's array when it returns)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if (whole && whole->item_hits) SBR_HIP(hipMemsetAsync(S + rw.ihits, 0, (size_t)N * sizeof(int), s));
+    if (inside->item_hits) SBR_HIP(hipMemsetAsync(S + ri.ihits, 0, (size_t)N * sizeof(int), s));
+    if (cluster_use_host) SBR_HIP(hipMemsetAsync(S + o_use, 0, (size_t)C * sizeof(int), s));
+    auto hits = [&](const sbr_eval_out* o, const CevRecords& r, int64_t c0, int rows, const int* oid) {
+        return launch_ev_hits(s, v, dusers + c0, rows, k, oid, (int*)(S + r.npred) + c0, (int*)(S + r.hits) + c0, (int*)(S + r.first) + c0,
+                              o->hitmask ? (unsigned*)(S + r.mask) + (size_t)c0 * words : nullptr, o->item_hits ? (int*)(S + r.ihits) : nullptr);
+    };
+    for (int64_t c0 = 0; c0 < n; c0 += B) {
+        const int rows = (int)std::min<int64_t>(B, n - c0);
+        const int* cu = dusers + c0;
+        int* csel = dcsel + c0;
+        if ((rc = eval_pack_chunk(h, v, cu, rows)) != SBR_OK) return rc;
+        if (full) {
+            if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_rank ranks (and flushes lazily stepped rows)
+        } else {
+            if ((rc = sbr_forward(h)) != SBR_OK) return rc;
+            if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;       // every member row of W_out^T / b_out must be current
+        }
+        float* lg = h->A(y.a_logits);
+        if ((rc = sbr_cluster_select(c, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, rows, csel, nullptr)) != SBR_OK) return rc;
+        // --- the cluster ranking's scores, while the full scores are as the projection left them
+        if (product)
+            SBR_LAUNCH(launch_cev_product(s, v, cu, rows, y.T, N, C, exclude_mode == SBR_EVAL_EXCL_WINDOW, lg, csel, c->hardT, cs));
+        else if (restricted) {
+            SBR_LAUNCH(launch_crk_group(s, csel, rows, C, (int*)(S + o_grp)));
+            SBR_LAUNCH(launch_crk_score(s, h_last(h), y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, c->mem_ids, c->mem_off,
+                                        (const int*)(S + o_grp), rows, C, lmax, cs));
+        } else
+            SBR_LAUNCH(launch_crk_gather(s, lg, N, csel, c->mem_ids, c->mem_off, rows, lmax, cs));
+        if (!product) h->last_cluster_rank_form = restricted ? 1 : 2;
+        // --- the whole-catalogue ranking of the same forward pass: sbr_evaluate's chunk
+        if (whole) {
+            int* oid = (int*)(S + rw.oid) + (whole->ids ? (size_t)c0 * k : 0);
+            SBR_LAUNCH(launch_ev_exclude(s, v, cu, rows, y.T, N, whole_mode, lg));
+            SBR_LAUNCH(launch_rank_select(s, lg, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
+            SBR_LAUNCH(launch_rank_sort(s, lg, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
+                                        (const int*)(S + o_nsel), oid, (float*)(S + o_osc), &h->last_rank_sort));
+            SBR_LAUNCH(hits(whole, rw, c0, rows, oid));
+        }
+        // --- the cluster ranking
+        int* oid = (int*)(S + ri.oid) + (inside->ids ? (size_t)c0 * k : 0);
+        if (product) {
+            SBR_LAUNCH(launch_rank_select(s, cs, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
+            SBR_LAUNCH(launch_rank_sort(s, cs, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
+                                        (const int*)(S + o_nsel), oid, (float*)(S + o_osc), &h->last_rank_sort));
+        } else {
+            SBR_LAUNCH(launch_cev_exclude(s, v, cu, rows, y.T, N, exclude_mode, cs, lmax, csel, C, c->mem_ids, c->mem_off));
+            SBR_LAUNCH(launch_rank_select(s, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
+            SBR_LAUNCH(launch_rank_sort(s, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
+                                        (const int*)(S + o_nsel), (int*)(S + o_pos), (float*)(S + o_psc), &h->last_rank_sort));
+            SBR_LAUNCH(launch_crk_translate(s, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
+                                            oid, (float*)(S + o_osc), (int*)(S + o_size) + c0));
+        }
+        SBR_LAUNCH(hits(inside, ri, c0, rows, oid));
+    }
+    if (cluster_use_host) SBR_LAUNCH(launch_cev_use(s, dcsel, (long long)n, C, (int*)(S + o_use)));
+    auto fetch = [&](const sbr_eval_out* o, const CevRecords& r) -> int {
+        if (o->ids) SBR_HIP(hipMemcpyAsync(o->ids, S + r.oid, nk * sizeof(int), hipMemcpyDeviceToHost, s));
+        SBR_HIP(hipMemcpyAsync(o->n_pred, S + r.npred, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        SBR_HIP(hipMemcpyAsync(o->hits, S + r.hits, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        SBR_HIP(hipMemcpyAsync(o->first_hit, S + r.first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (o->hitmask) SBR_HIP(hipMemcpyAsync(o->hitmask, S + r.mask, (size_t)n * words * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        if (o->item_hits) SBR_HIP(hipMemcpyAsync(o->item_hits, S + r.ihits, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
+        return SBR_OK;
+    };
+    if (whole && (rc = fetch(whole, rw)) != SBR_OK) return rc;
+    if ((rc = fetch(inside, ri)) != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(cluster_host, dcsel, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (size_host) SBR_HIP(hipMemcpyAsync(size_host, S + o_size, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (cluster_use_host) SBR_HIP(hipMemcpyAsync(cluster_use_host, S + o_use, (size_t)C * sizeof(int), hipMemcpyDeviceToHost, s));
+    return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
 }
 
 // ---------------------------------------------------------------------------------------

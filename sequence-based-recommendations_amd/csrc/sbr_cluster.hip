@@ -217,7 +217,7 @@ extern "C" sbr_cluster* sbr_cluster_create(const sbr_cluster_config* cfg, void* 
     if (c.updater < 0 || c.updater > SBR_UPD_ADAM) { sbr_set_error("Unknown update option"); return nullptr; }
     sbr_cluster* k = new (std::nothrow) sbr_cluster();
     if (!k) return nullptr;
-    k->cfg = c; k->stream = (hipStream_t)stream; k->step = 0; k->scale = c.scale; k->noise_ctr = 0; k->J = 0; k->hard_valid = 0; k->dR_clean = 0;
+    k->cfg = c; k->stream = (hipStream_t)stream; k->step = 0; k->scale = c.scale; k->noise_ctr = 0; k->J = 0; k->hard_valid = 0; k->hardT = nullptr; k->hardT_valid = 0; k->dR_clean = 0;
     k->lists_valid = 0; k->mem_ids = nullptr; k->mem_cap = 0; k->mem_off = nullptr; k->mem_work = nullptr; k->mem_work_n = 0; k->lmax = 0;
     const size_t N = c.n_items, C = c.n_clusters, H = c.n_hidden, B = c.batch_size, J = B + c.max_samples;
     const size_t nR = N * C, nW = H * C;
@@ -243,6 +243,7 @@ extern "C" void sbr_cluster_destroy(sbr_cluster* k) {
     (void)hipStreamSynchronize(k->stream);
     for (float* q : f) if (q) (void)hipFree(q);
     if (k->ids) (void)hipFree(k->ids);
+    if (k->hardT) (void)hipFree(k->hardT);
     for (int* q : {k->mem_ids, k->mem_off, k->mem_work}) if (q) (void)hipFree(q);
     delete k;
 }
@@ -252,7 +253,7 @@ extern "C" int sbr_cluster_set_params(sbr_cluster* k, const float* R, const floa
     CL_HIP(hipMemcpyAsync(k->R, R, (size_t)k->cfg.n_items * k->cfg.n_clusters * sizeof(float), hipMemcpyHostToDevice, k->stream));
     CL_HIP(hipMemcpyAsync(k->Wc, Wc, (size_t)k->cfg.n_hidden * k->cfg.n_clusters * sizeof(float), hipMemcpyHostToDevice, k->stream));
     CL_HIP(hipStreamSynchronize(k->stream));
-    k->hard_valid = 0; k->lists_valid = 0;
+    k->hard_valid = 0; k->hardT_valid = 0; k->lists_valid = 0;
     return SBR_OK;
 }
 static int cl_get(sbr_cluster* k, float* R, float* Wc, const float* dR, const float* dW) {
@@ -303,7 +304,7 @@ extern "C" int sbr_cluster_apply_update(sbr_cluster* k) {      // self.updater(c
                          c.learning_rate, c.rho, c.beta1, c.beta2, k->step));
     CL_HIP(launch_update(k->stream, c.updater, k->R, k->dR, k->sR[0], two ? k->sR[1] : nullptr, (size_t)c.n_items * c.n_clusters,
                          c.learning_rate, c.rho, c.beta1, c.beta2, k->step));
-    k->hard_valid = 0; k->lists_valid = 0;
+    k->hard_valid = 0; k->hardT_valid = 0; k->lists_valid = 0;
     k->dR_clean = 1;                                 // update_kernel has cleared dR (and dWc)
     return SBR_OK;
 }
@@ -318,13 +319,32 @@ extern "C" int sbr_cluster_select(sbr_cluster* k, const float* h_dev, int ld_h, 
     return SBR_OK;
 }
 
-extern "C" int sbr_cluster_mask_scores(sbr_cluster* k, float* scores_dev, int ld, int rows, const int32_t* csel_dev, float* n_used_dev) {
-    CL_ARG(k && csel_dev && rows >= 1 && (scores_dev || n_used_dev), "bad argument");
+// The one place `hard` (and its transposed copy) is made: whoever clears hard_valid clears hardT_valid with it.
+int sbr_cluster_build_hard(sbr_cluster* k, int transposed) {
     const sbr_cluster_config& c = k->cfg;
     if (!k->hard_valid) {        // _get_hard_clusters: f(100 R), the mix clipped to [0, 1]
         cl_members_kernel<<<c.n_items, 64, 0, k->stream>>>(k->R, nullptr, c.n_clusters, 100.0f, c.cluster_type, k->hard, nullptr, nullptr, 1);
-        k->hard_valid = 1;
+        CL_HIP(hipGetLastError());
+        k->hard_valid = 1; k->hardT_valid = 0;
     }
+    if (transposed && !k->hardT_valid) {
+        if (!k->hardT && hipMalloc((void**)&k->hardT, (size_t)c.n_items * c.n_clusters * sizeof(float)) != hipSuccess) {
+            (void)hipGetLastError();
+            k->hardT = nullptr;
+            sbr_set_error("sbr_cluster_evaluate: hipMalloc of the transposed membership matrix failed");
+            return SBR_ENOMEM;
+        }
+        CL_HIP(launch_cev_transpose(k->stream, k->hard, c.n_items, c.n_clusters, k->hardT));
+        k->hardT_valid = 1;
+    }
+    return SBR_OK;
+}
+
+extern "C" int sbr_cluster_mask_scores(sbr_cluster* k, float* scores_dev, int ld, int rows, const int32_t* csel_dev, float* n_used_dev) {
+    CL_ARG(k && csel_dev && rows >= 1 && (scores_dev || n_used_dev), "bad argument");
+    const sbr_cluster_config& c = k->cfg;
+    int rc;
+    if ((rc = sbr_cluster_build_hard(k, 0)) != SBR_OK) return rc;
     if (scores_dev) {
         CL_ARG(ld >= c.n_items, "row stride %d < %d items", ld, c.n_items);
         const dim3 grid((unsigned)std::min(256, (c.n_items + 255) / 256), (unsigned)rows);
@@ -338,8 +358,8 @@ extern "C" int sbr_cluster_mask_scores(sbr_cluster* k, float* scores_dev, int ld
 extern "C" int sbr_cluster_hard(sbr_cluster* k, float* hard_host) {      // [N][C]: what prepare_tests / the metrics read (host copy)
     CL_ARG(k && hard_host, "null argument");
     const sbr_cluster_config& c = k->cfg;
-    cl_members_kernel<<<c.n_items, 64, 0, k->stream>>>(k->R, nullptr, c.n_clusters, 100.0f, c.cluster_type, k->hard, nullptr, nullptr, 1);
-    k->hard_valid = 1;
+    int rc;
+    if ((rc = sbr_cluster_build_hard(k, 0)) != SBR_OK) return rc;
     CL_HIP(hipMemcpyAsync(hard_host, k->hard, (size_t)c.n_items * c.n_clusters * sizeof(float), hipMemcpyDeviceToHost, k->stream));
     CL_HIP(hipStreamSynchronize(k->stream));
     return SBR_OK;

@@ -19,6 +19,7 @@
 // roles in the same k order and ends in the same two adds, so a score here is the very float sbr_rank ranks: an output element of
 // the instruction depends on its own row of A and column of B only, not on which rows or items share the tile.
 #include "sbr_common.h"
+#include "sbr_device.h"
 #include <math.h>
 #include <algorithm>
 #include <new>
@@ -228,11 +229,7 @@ __global__ void __launch_bounds__(256) crk_gather_kernel(const float* __restrict
         cs[(size_t)r * lmax + p] = p < len ? lg[(size_t)r * N + mem[base + p]] : -INFINITY;
 }
 
-__device__ __forceinline__ void crk_exclude_one(float* __restrict__ row, const int* __restrict__ list, int len, int id) {
-    int lo = 0, hi = len;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (list[mid] < id) lo = mid + 1; else hi = mid; }
-    if (lo < len && list[lo] == id) row[lo] = -INFINITY;
-}
+// (crk_exclude_one: sbr_device.h)
 __global__ void __launch_bounds__(256) crk_exclude_kernel(float* __restrict__ cs, int lmax, const int* __restrict__ csel, const int* __restrict__ mem,
                                                           const int* __restrict__ moff, int N, const int* __restrict__ excl_ids,
                                                           const long long* __restrict__ excl_off, const int* __restrict__ X,

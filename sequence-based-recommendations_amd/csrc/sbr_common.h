@@ -315,6 +315,9 @@ struct sbr_cluster {
     unsigned long long noise_ctr;
     int J;                                           // cells of the last forward (B + samples)
     int hard_valid;
+    // sbr_cluster_evaluate's PRODUCT road (sbr_cluster_eval.hip): the same floats as `hard`, [C][N], so that a row's membership column
+    // is a contiguous stream.  Own allocation, made on first use; valid only while hard_valid is (every site that clears one clears both)
+    float* hardT; int hardT_valid;
     int dR_clean;                                    // dR is all zeros: the optimizer kernel clears every gradient it consumes (no N x C memset per step)
     // sbr_cluster_lists / sbr_cluster_rank (sbr_cluster_rank.hip): the hard clusters of prepare_tests as a CSR over clusters.  Own
     // allocations, made on first use and freed by sbr_cluster_destroy; valid until R changes (set_params, apply_update)
@@ -665,6 +668,8 @@ hipError_t launch_crk_exclude(hipStream_t s, float* cs, int lmax, const int* cse
 // places -> item ids, widened from kk to k columns (-1 / -inf); clu / size (nullable) [rows]: the row's cluster and its list's length
 hipError_t launch_crk_translate(hipStream_t s, const int* pos, const float* psc, int kk, int k, const int* csel, const int* mem_ids,
                                 const int* mem_off, int rows, int* out_ids, float* out_scores, int* size);
+// makes c->hard = f(100 R) if R changed since it was made and, with transposed, c->hardT from it; SBR_OK or a negative sbr_status
+int sbr_cluster_build_hard(sbr_cluster* c, int transposed);
 // sbr_eval.hip: evaluation of whole users on the device (include/sbr_rnn.h: sbr_evaluate).  A user's sequence is split in the middle
 // (test.py:81-83, _gen_mini_batch(test=True)): half = L / 2 viewed items, the rest is the goal.
 // What sbr_evaluate reads of a dataset (sbr_batch.hip owns the struct): the sequences as uploaded -- never the noised copy --, the
@@ -684,3 +689,14 @@ hipError_t launch_ev_exclude(hipStream_t s, const SbrEvalView& v, const int* use
 // (NULL: not written), item_hits [N] += 1 per hit (NULL: not counted)
 hipError_t launch_ev_hits(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int k, const int* ids, int* n_pred, int* hits,
                           int* first_hit, unsigned* mask, int* item_hits);
+// sbr_cluster_eval.hip: what sbr_cluster_evaluate needs beyond the kernels above (include/sbr_rnn.h)
+// -inf at the places of the viewed (mode VIEWED) / fed (WINDOW) items of users[r] that the row's cluster holds; cs [rows][lmax]
+hipError_t launch_cev_exclude(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int mode, float* cs, int lmax,
+                              const int* csel, int C, const int* mem_ids, const int* mem_off);
+hipError_t launch_cev_transpose(hipStream_t s, const float* hard, int N, int C, float* hardT);
+// prod[r][i] = softmax(logits[r])[i] * hardT[csel[r]][i] (logits: biased, untouched by any exclusion), then with zero_fed +0.0 at the
+// items fed of users[r]
+hipError_t launch_cev_product(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int C, int zero_fed,
+                              const float* logits, const int* csel, const float* hardT, float* prod);
+// use[c] += rows of csel[0 .. n) that selected c (integer atomics)
+hipError_t launch_cev_use(hipStream_t s, const int* csel, long long n, int C, int* use);

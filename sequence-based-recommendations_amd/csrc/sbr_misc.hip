@@ -3,41 +3,12 @@
 // optimizers (K13), test-path exclusion + top-k (K14).
 #include "sbr_common.h"
 #include "sbr_rec_p.h"
+#include "sbr_device.h"
 #include <math.h>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-// ---------------------------------------------------------------------------------------
-// block-wide reductions (256 threads = 4 waves)
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-    v = wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = 0.0f;
-    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) s += red[w];
-    return s;
-}
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float s = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) s = fmaxf(s, red[w]);
-    return s;
-}
+// block-wide reductions (256 threads = 4 waves): sbr_device.h
 
 // ---------------------------------------------------------------------------------------
 // K1 embedding-bag gather: xt[t][b][:] = sum_f W_in[X[b][t][f]][:] + bias
@@ -1615,12 +1586,8 @@ __global__ void __launch_bounds__(256) softmax_rows_kernel(float* __restrict__ l
     float mx = -INFINITY;
     for (int n = threadIdx.x; n < N; n += 256) { const float v = x[n] + bout[n]; x[n] = v; mx = fmaxf(mx, v); }
     if (!do_softmax) return;
-    mx = block_max(mx, red);
-    float se = 0.0f;
-    for (int n = threadIdx.x; n < N; n += 256) se += expf(x[n] - mx);
-    se = block_sum(se, red);
-    const float inv = 1.0f / se;
-    for (int n = threadIdx.x; n < N; n += 256) x[n] = expf(x[n] - mx) * inv;
+    const float inv = softmax_row_scale(x, N, mx, red, mx);      // (sbr_device.h: cev_product_kernel takes the same two calls)
+    for (int n = threadIdx.x; n < N; n += 256) x[n] = softmax_row_value(x[n], mx, inv);
 }
 
 hipError_t launch_softmax_rows(hipStream_t s, float* logits, const float* bout, int rows, int N, int do_softmax) {

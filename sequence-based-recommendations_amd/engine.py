@@ -43,6 +43,14 @@ FLAG_BF16_PROJECTION = 128   # output projection on plain bf16 operands (one MFM
 FLAG_BF16_LAYERS = 256       # the dense GEMMs between stacked layers (input projection of layer >= 2 and its backward pair) on plain bf16 operands
 # sbr_evaluate's exclusion modes (include/sbr_rnn.h)
 EVAL_EXCL_NONE, EVAL_EXCL_VIEWED, EVAL_EXCL_WINDOW, EVAL_EXCL_WINDOW_ZERO = 0, 1, 2, 3
+# sbr_cluster_evaluate's roads (include/sbr_rnn.h)
+CEVAL_LISTS, CEVAL_PRODUCT = 0, 1
+
+
+class SbrEvalOut(ctypes.Structure):
+    """sbr_eval_out: the host arrays of one ranking's results (sbr_cluster_evaluate)"""
+    _fields_ = [("ids", ctypes.c_void_p), ("n_pred", ctypes.c_void_p), ("hits", ctypes.c_void_p), ("first_hit", ctypes.c_void_p),
+                ("hitmask", ctypes.c_void_p), ("item_hits", ctypes.c_void_p)]
 
 
 class SbrConfig(ctypes.Structure):
@@ -71,7 +79,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_cluster_mask_scores", "sbr_cluster_hard", "sbr_cluster_lists", "sbr_cluster_rank",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
-           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate"]
+           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate"]
 
 _lib = None
 
@@ -163,6 +171,8 @@ def load_library(path=None):
     lib.sbr_plan_pass_host.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, vp, vp, i32p, vp, vp, vp, vp, i64p, i64p]
     lib.sbr_build_batch.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint64]
     lib.sbr_evaluate.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+    lib.sbr_cluster_evaluate.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SbrEvalOut),
+                                         ctypes.POINTER(SbrEvalOut), vp, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -924,6 +934,7 @@ class ClusterHead(object):
         self._csel = self.torch.empty(max(self.batch_size, 16), dtype=self.torch.int32, device=dev)
         self._hard = None
         self._lists = None
+        self.evaluate_calls = 0      # calls of evaluate() so far (tests: which road an evaluation took)
 
     def _check(self, rc):
         if rc != 0:
@@ -1067,3 +1078,37 @@ class ClusterHead(object):
         self.engine._check(self.lib.sbr_cluster_rank(self.h, self.engine.h, k, int(bool(exclude_input)), p(excl_ids), p(excl_off), p(ids),
                                                      p(scores), p(clusters), p(sizes)))
         return (ids, scores, clusters, sizes) if return_scores else (ids, clusters, sizes)
+
+    def evaluate(self, dataset, users, k, road, exclude_mode, want_ids=False, want_mask=True, want_whole=False):
+        """Whole users of a DeviceDataset evaluated inside their item clusters on the device (sbr_cluster_evaluate), split and fed
+        as by RNNEngine.evaluate.  road: CEVAL_LISTS (only the members of the user's cluster are ranked: top_k_recommendations)
+        or CEVAL_PRODUCT (softmax probability times hard membership over the catalogue: the compiled test function);
+        exclude_mode: EVAL_EXCL_* (LISTS: NONE, VIEWED, WINDOW; PRODUCT: NONE, WINDOW -- the items fed score 0.0).  Returns
+        {"inside": rec, "whole": rec or None, "cluster": (n,) int32, "size": (n,) int32 items in the user's cluster (None on the
+        PRODUCT road), "cluster_use": (C,) int32 users per cluster}; rec is RNNEngine.evaluate's dict, "whole" (want_whole) the
+        whole-catalogue ranking of the same forward pass."""
+        eng = self.engine
+        eng._rank_local_flush("evaluate")
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        n, k = len(users), int(k)
+        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
+            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
+        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+        def record():
+            rec = {"n_pred": np.empty(n, np.int32), "hits": np.empty(n, np.int32), "first_hit": np.empty(n, np.int32),
+                   "item_hits": np.empty(self.n_items, np.int32),
+                   "hitmask": np.empty((n, (k + 31) // 32), np.uint32) if want_mask else None,
+                   "ids": np.empty((n, k), np.int32) if want_ids else None}
+            return rec, SbrEvalOut(p(rec["ids"]), p(rec["n_pred"]), p(rec["hits"]), p(rec["first_hit"]), p(rec["hitmask"]), p(rec["item_hits"]))
+        inside, c_inside = record()
+        whole, c_whole = record() if want_whole else (None, None)
+        out = {"inside": inside, "whole": whole, "cluster": np.empty(n, np.int32),
+               "size": np.empty(n, np.int32) if int(road) == CEVAL_LISTS else None, "cluster_use": np.empty(self.n_clusters, np.int32)}
+        self.evaluate_calls += 1
+        with self.torch.cuda.device(eng.device):
+            # (the engine's mapping of the status: SBR_EINVAL is a ValueError, as RNNEngine.evaluate raises it)
+            eng._check(self.lib.sbr_cluster_evaluate(self.h, eng.h, dataset.d, ctypes.c_void_p(users.ctypes.data) if n else None, n, k, int(road),
+                                                     int(exclude_mode), ctypes.byref(c_whole) if want_whole else None, ctypes.byref(c_inside),
+                                                     p(out["cluster"]), p(out["size"]), p(out["cluster_use"])))
+        return out

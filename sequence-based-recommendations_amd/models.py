@@ -384,29 +384,47 @@ class RNNBase(object):
 
     native_eval = True          # evaluate() ranks what this model's test function / top_k_recommendations rank (RNNCluster: no, it ranks inside a cluster)
 
-    def native_evaluator(self, dataset, which, k, mode, want_ids=False):
-        """Every user of dataset's "validation" / "test" set evaluated by ONE engine call (RNNEngine.evaluate: split in the middle,
-        the last max_length viewed items in, the rest as goal -- what _gen_mini_batch(test=True) and test.run_tests do per user),
-        as a data.NativeEvaluator; mode: engine.EVAL_EXCL_*.  None -> the per-user host road: SBR_NATIVE_EVAL=0, a data-parallel
-        wrapper (its collectives own the ranking calls), a cluster model, a stand-in engine without evaluate(), or a target
-        selection that may drop a test row (--rand_test_target with --target_bias)."""
+    def _native_eval_users(self, dataset, which, evaluate_on=None):
+        """(DeviceDataset, users, lengths) of dataset's "validation" / "test" set for one native evaluation call, or None where the
+        per-user host road must run: SBR_NATIVE_EVAL=0, a data-parallel wrapper (its collectives own the ranking calls), a
+        stand-in without evaluate() (evaluate_on: the object that must offer it, the engine by default), a shuffled set, or a
+        target selection that may drop a test row (--rand_test_target with --target_bias)."""
         ts = self.target_selection
-        if os.environ.get("SBR_NATIVE_EVAL", "1") == "0" or self.dp is not None or not self.native_eval or not hasattr(self.engine, "evaluate"):
+        if os.environ.get("SBR_NATIVE_EVAL", "1") == "0" or self.dp is not None or not hasattr(self.engine if evaluate_on is None else evaluate_on, "evaluate"):
             return None
         if getattr(dataset, which + "_set").shuffle or (which == "validation" and not ts.determinist_test and ts.bias >= 0.0):
             return None      # (users in file order only; a validation row without a target is skipped by the host road)
-        from .data import NativeEvaluator
         ds = dataset.device_set(which, self.engine, ratings=self.use_ratings_features)
         print("Opening file (1)")                            # (the line the set's generator prints for its one pass)
         lens = ds.offsets[1:] - ds.offsets[:-1]
         users = np.nonzero(lens >= 2)[0].astype(np.int32)    # SequenceGenerator's min_length = 2 (data_handling.py:143)
-        rec = self.engine.evaluate(ds, users, k, mode, want_ids=want_ids, want_mask=True)
+        return ds, users, lens
+
+    @staticmethod
+    def _evaluator_of_records(dataset, ds, users, lens, rec, k, want_ids):
+        from .data import NativeEvaluator
         goals = None
         if want_ids:
             goals = [ds.items[ds.offsets[u] + lens[u] // 2:ds.offsets[u + 1]].tolist() for u in users.tolist()]
         ev = NativeEvaluator(dataset, k=k)
         ev.add_records(rec, (lens - lens // 2)[users], goals=goals)
         return ev
+
+    def _whole_catalogue_evaluator(self, dataset, which, k, mode, want_ids=False):
+        found = self._native_eval_users(dataset, which)
+        if found is None:
+            return None
+        ds, users, lens = found
+        rec = self.engine.evaluate(ds, users, k, mode, want_ids=want_ids, want_mask=True)
+        return self._evaluator_of_records(dataset, ds, users, lens, rec, k, want_ids)
+
+    def native_evaluator(self, dataset, which, k, mode, want_ids=False):
+        """Every user of dataset's "validation" / "test" set evaluated by ONE engine call (RNNEngine.evaluate: split in the middle,
+        the last max_length viewed items in, the rest as goal -- what _gen_mini_batch(test=True) and test.run_tests do per user),
+        as a data.NativeEvaluator; mode: engine.EVAL_EXCL_*.  None -> the per-user host road (_native_eval_users names the cases)."""
+        if not self.native_eval:
+            return None
+        return self._whole_catalogue_evaluator(dataset, which, k, mode, want_ids=want_ids)
 
     def _compute_validation_metrics(self, metrics):
         from .data import Evaluator
@@ -770,17 +788,46 @@ class RNNCluster(RNNBase):
                 s1[b, seen] = 0.0; s2[b, seen] = 0.0
         return self._ranked(s1, k)[0], self._ranked(s2, k)[0], int(csel[0]), float(used[0].sum())
 
+    def _native_validation(self):
+        """The loop of _compute_validation_metrics as ONE call of the head (ClusterHead.evaluate, PRODUCT road, both rankings of the
+        same forward pass): (ev, ev_clusters, clusters, used_items), or None where the loop must run (_native_eval_users)."""
+        from .engine import CEVAL_PRODUCT, EVAL_EXCL_NONE, EVAL_EXCL_WINDOW
+        found = self._native_eval_users(self.dataset, "validation", evaluate_on=self.head)
+        if found is None:
+            return None
+        ds, users, lens = found
+        out = self.head.evaluate(ds, users, 10, CEVAL_PRODUCT, EVAL_EXCL_WINDOW if self.interactions_are_unique else EVAL_EXCL_NONE,
+                                 want_ids=False, want_mask=True, want_whole=True)
+        return self._validation_parts(self.dataset, ds, users, lens, out, self.head.hard_clusters(), self.n_clusters)
+
+    @classmethod
+    def _validation_parts(cls, dataset, ds, users, lens, out, hard, n_clusters):
+        """what the host loop accumulates, from the records of one ClusterHead.evaluate call and the host copy of the hard clusters"""
+        ev = cls._evaluator_of_records(dataset, ds, users, lens, out["whole"], 10, False)
+        ev_clusters = cls._evaluator_of_records(dataset, ds, users, lens, out["inside"], 10, False)
+        clusters = np.zeros(n_clusters, dtype="int")
+        clusters[:] = out["cluster_use"]
+        # items in a user's cluster: the host road's own expression per distinct cluster (numpy's pairwise sum over the N
+        # memberships; a device sum would round in another order), then one entry per user in user order
+        per_cluster = {int(c): float(hard[:, [int(c)]].T[0].sum()) for c in np.unique(out["cluster"])}
+        used_items = [per_cluster[int(c)] for c in out["cluster"]]
+        return ev, ev_clusters, clusters, used_items
+
     def _compute_validation_metrics(self, metrics):
         from .data import Evaluator
-        clusters = np.zeros(self.n_clusters, dtype="int")
-        used_items = []
-        ev, ev_clusters = Evaluator(self.dataset, k=10), Evaluator(self.dataset, k=10)
-        for batch, goal in self._gen_mini_batch(self.dataset.validation_set(epochs=1), test=True):
-            pred1, pred2, cl, n_used = self.test_function(batch)
-            ev.add_instance(goal, pred1)
-            ev_clusters.add_instance(goal, pred2)
-            clusters[cl] += 1
-            used_items.append(n_used)
+        native = self._native_validation()
+        if native is not None:
+            ev, ev_clusters, clusters, used_items = native
+        else:
+            clusters = np.zeros(self.n_clusters, dtype="int")
+            used_items = []
+            ev, ev_clusters = Evaluator(self.dataset, k=10), Evaluator(self.dataset, k=10)
+            for batch, goal in self._gen_mini_batch(self.dataset.validation_set(epochs=1), test=True):
+                pred1, pred2, cl, n_used = self.test_function(batch)
+                ev.add_instance(goal, pred1)
+                ev_clusters.add_instance(goal, pred2)
+                clusters[cl] += 1
+                used_items.append(n_used)
         R = self.head.get_params()[0]
         if self.cluster_type == "softmax":
             ignored_items = 0
@@ -858,7 +905,27 @@ class RNNCluster(RNNBase):
         return list(np.argpartition(-scores, range(k))[:k]), self.n_items
 
     batched_top_k = True
-    native_eval = False         # evaluation stays on the per-user road: a cluster model ranks inside each user's item cluster
+    native_eval = False         # RNNEngine.evaluate does not rank what this model ranks: its native road is ClusterHead.evaluate
+
+    def native_evaluator(self, dataset, which, k, mode, want_ids=False):
+        """test.run_tests' users in ONE call of the head (ClusterHead.evaluate, LISTS road: each user ranked inside the member list
+        of their cluster, what top_k_batch does batch_size users at a time) as a data.NativeEvaluator with nb_of_dp = the mean
+        number of items scored per user; --ignore_clusters: RNNBase's whole-catalogue road, nb_of_dp = n_items.  None -> the
+        per-user host road (_native_eval_users names the cases)."""
+        if not self.predict_with_clusters:
+            ev = self._whole_catalogue_evaluator(dataset, which, k, mode, want_ids=want_ids)
+            if ev is not None:
+                ev.nb_of_dp = self.n_items
+            return ev
+        from .engine import CEVAL_LISTS
+        found = self._native_eval_users(dataset, which, evaluate_on=self.head)
+        if found is None:
+            return None
+        ds, users, lens = found
+        out = self.head.evaluate(ds, users, k, CEVAL_LISTS, mode, want_ids=want_ids, want_mask=True)
+        ev = self._evaluator_of_records(dataset, ds, users, lens, out["inside"], k, want_ids)
+        ev.nb_of_dp = np.mean(out["size"])
+        return ev
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per

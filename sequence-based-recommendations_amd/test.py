@@ -43,20 +43,25 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
     A cluster model (`--clusters C`, test.py:61-76) ranks inside each user's item cluster: every user with a viewed half goes
     through RNNCluster.top_k_batch at any k -- never through the engine's whole-catalogue test function -- and nb_of_dp is the
     mean number of items scored per user, the size of the user's cluster.
-    By default none of that loop runs: the whole set is evaluated by one engine call (RNNBase.native_evaluator, sbr_evaluate) and
-    the returned evaluator is a data.NativeEvaluator with the same metrics, equal with ==."""
+    By default none of that loop runs: the whole set is evaluated by one engine call (RNNBase.native_evaluator, sbr_evaluate; for a
+    cluster model RNNCluster.native_evaluator, sbr_cluster_evaluate) and the returned evaluator is a data.NativeEvaluator with the
+    same metrics, equal with ==."""
     predictor.load(model_file)
     # the whole test set in one engine call (RNNBase.native_evaluator): every user here has a viewed half -- the set's generator
     # skips sequences of fewer than two items -- and the engine excludes all of it, also what no longer fits the window.  Not
-    # with --save_rank, not for a cluster model, not with SBR_NATIVE_EVAL=0: those take the per-user road below.
-    if not get_full_recommendation_list and getattr(args, "clusters", 0) <= 0 and hasattr(predictor, "native_evaluator"):
+    # with --save_rank, not with SBR_NATIVE_EVAL=0: those take the per-user road below.  A cluster model's call is the head's
+    # (RNNCluster.native_evaluator, sbr_cluster_evaluate): inside each user's cluster, nb_of_dp the mean cluster size.
+    # the reference tests a model as a cluster model on args.clusters > 0 (test.py:61): its recommendation calls return (ids, n)
+    clustered = getattr(args, "clusters", 0) > 0
+    if not get_full_recommendation_list and hasattr(predictor, "native_evaluator"):
         from .engine import EVAL_EXCL_NONE, EVAL_EXCL_VIEWED
         start = time.perf_counter()
         evaluator = predictor.native_evaluator(dataset, "test", k, EVAL_EXCL_VIEWED if predictor.interactions_are_unique else EVAL_EXCL_NONE,
                                                want_ids=True)
         if evaluator is not None:
             print("Timer: ", time.perf_counter() - start)
-            evaluator.nb_of_dp = dataset.n_items                                                       # test.py:73-76
+            if not clustered:
+                evaluator.nb_of_dp = dataset.n_items                                                   # test.py:73-76
             return evaluator
     evaluator = Evaluator(dataset, k=k)
     if get_full_recommendation_list:
@@ -65,8 +70,6 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
     pending, deep, results, order = [], [], {}, []
     # a stand-in engine that offers the reference's three callables only has no batched ranking (tests/test_cli_reference_golden.py)
     batched_deep = getattr(predictor, "batched_top_k", False) and hasattr(predictor.engine, "rank")
-    # the reference tests a model as a cluster model on args.clusters > 0 (test.py:61): its recommendation calls return (ids, n)
-    clustered = getattr(args, "clusters", 0) > 0
     scored = {}
 
     def flush():
