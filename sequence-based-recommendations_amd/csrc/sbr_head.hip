@@ -9,26 +9,35 @@
 // Here a workgroup owns 16 batch rows x one CHUNK of the catalogue (CW columns, a multiple of 16), and the grid -- row blocks x
 // column chunks, at most one workgroup per CU: at most 256 -- is co-resident, so the softmax's row statistics cross the chunks
 // inside the kernel:
-//   0. the chunk's rows of W_out^T [CW][HP] (item-major: a row is contiguous) go to LDS once, f32, row stride HP + 4 floats;
-//      every wave keeps its 16 rows of h_last in registers as the MFMA's B operand.
+//   0. everything the launch reads is requested at its top: the h rows (every wave keeps its 16 rows of h_last in registers as the
+//      MFMA's B operand), the rows' targets and popularities, the bias of the wave's tiles (one 16-byte piece per tile), and the
+//      chunk's rows of W_out^T [CW][HP] (item-major: a row is contiguous), which go to LDS once, f32, row stride HP + 4 floats.
 //   1. logits tile by tile (a wave takes the 16-column tiles wave, wave + 4, ...): D[item][row] = sum_k W[item][k] h[row][k] on
 //      v_mfma_f32_16x16x4_f32 (exact f32 products -- no operand split, nothing to bound), one ds_read_b128 per four
 //      instructions (k slot q of instruction m is k0 + 4 q + m).  A lane ends with four consecutive items of one batch row, the
 //      tile stays in registers.
 //   2. row max / sum of exponentials over the chunk (lanes -> waves through LDS), published as one 16-byte piece per (row block,
 //      chunk, row) whose dwords validate themselves against this launch's epoch (value, value ^ epoch: no ordering needed, a
-//      torn piece is simply not valid yet); every workgroup of the row block polls the CC pieces of its rows (agent-scope loads)
-//      and combines them in chunk order -- every workgroup the same bits.  A chunk whose workgroup has not published within
-//      60 us is not waited for: its statistics are recomputed by whoever misses them (its W rows through the same LDS image,
-//      the same code), so every workgroup can always finish on its own -- two processes on one GPU can interleave two such
-//      grids so that neither is ever co-resident.
-//   3. dlogits = (softmax - onehot) / (pop B) from the registers, stored once (the output layer's gradient kernels on the side
-//      stream read them); the row's cost by the lane that holds its target column.
-//   4. dh[row][k] = sum_items dlogits[row][item] W[item][k] with the SAME LDS image (item = reduction index: one ds_read_b32 per
-//      instruction, conflict-free at stride HP + 4) and the dlogits registers as the B operand exactly as phase 3 left them
-//      (k slot q of instruction e of tile t is item 16 t + 4 q + e); the four waves' partial sums meet in LDS and leave as ONE
-//      split-K slab [Bp][HP] per chunk -- what rec_bwd_x6p's prologue already adds up (RecArgs.dh_slabs), else
-//      gemm_splitk_reduce follows.
+//      torn piece is simply not valid yet).
+//   3. UNDER the exchange (one trip to the memory side and back: 5 us in which the workgroup did nothing): the chunk's dh partial from
+//      un-normalised numerators p~ = exp2((l - m_c) log2e), m_c the chunk's own row maximum, the target's column left out --
+//      dh[row][k] = sum_items p~[row][item] W[item][k] with the SAME LDS image (item = reduction index: one ds_read_b32 per
+//      instruction, conflict-free at stride HP + 4) and the numerators as the B operand in the layout phase 1 left (k slot q of
+//      instruction e of tile t is item 16 t + 4 q + e); the target's row of the image goes to registers.
+//   4. every workgroup of the row block polls the CC pieces of its rows (agent-scope loads) and combines them in chunk order --
+//      every workgroup the same bits.  A chunk whose workgroup has not published within 60 us is not waited for: its statistics
+//      are recomputed by whoever misses them (its W rows through the same LDS image -- free by then: dh is in registers -- and the
+//      same code), so every workgroup can always finish on its own -- two processes on one GPU can interleave two such grids so
+//      that neither is ever co-resident.
+//   5. dlogits = (softmax - onehot) / (pop B) from the logits in registers, stored once (the output layer's gradient kernels on the
+//      side stream read them); the row's cost by the lane that holds its target column.
+//   6. a lane's dh accumulators all belong to one batch row: scaled by exp2((m_c - M) log2e) / S / (pop B) -- 0 for a chunk beyond the
+//      catalogue or more than ~104 below M -- plus (p_y - 1) / (pop B) W[y][.] with p_y - 1 as phase 5 formed it (no sum(p W) - W_y
+//      cancellation); the four waves' partial sums meet in LDS and leave as ONE split-K slab [Bp][HP] per chunk -- what
+//      rec_bwd_x6p's prologue already adds up (RecArgs.dh_slabs), else gemm_splitk_reduce follows.
+// (profiles/head_stream_variants.txt: what this order gained over "fill, logits, exchange, dlogits, dh", and the two forms measured
+// with it that showed no gain of their own and are not here: logits straight from the pieces a wave streams for itself, and the
+// first poll's loads in flight under the dh MFMAs.)
 // Served: CCE, one direction, full batches (rows == Bp), HP in {32, 64, 128}, and a catalogue whose chunk fits LDS
 // (CW (HP + 4) 4 bytes + 3 KB <= 160 KB with CC = min(16, 256 / (Bp / 16)) chunks: N <= 4 864 at B = 256, HP = 128: C1, C2).  Everything
 // else keeps the three launches.  SBR_HEAD_FUSE=0 switches it off.
@@ -76,7 +85,6 @@ __device__ __forceinline__ void head_logits(const float* __restrict__ wr, const 
     }
 }
 
-
 // rows [n_lo, n_lo + CW) of W_out^T -> the LDS image (rows beyond the catalogue: zeros).  Rounds of 16 pieces per thread in flight
 // (C2's chunk of 240 rows x 128 floats is 30 pieces per thread; in rounds of 6 the fill was five dependent round trips to L2)
 template <int HP>
@@ -98,42 +106,32 @@ __device__ __forceinline__ void head_fill(const HeadArgs& a, float* __restrict__
     }
 }
 
-// this wave's tiles of the chunk whose rows are in the LDS image: logits (+ bias; -inf beyond the catalogue) into lg, the wave's
-// row maximum and sum of exponentials into red_w[wave][row]
-template <int HP>
-__device__ __forceinline__ void head_wave_stats(const HeadArgs& a, const float* __restrict__ Wl, const f32x4 (&hb)[HP / 16], int n_lo, int ntiles,
+// The bias of a lane's four columns of every tile of its wave, one 16-byte request per tile, issued in front of the fill with no branch
+// around it (one dword load per column behind the MFMAs, each in its own exec-guarded block with its own vmcnt(0), was 16 - 20
+// serialised round trips per wave on the critical path: what made a logits MFMA look like 86 cycles).  The
+// request starts at most at the last 16-byte piece that holds a column of the catalogue and so ends at most at b[N + 2]: the bias is
+// carved from the parameter arena, whose every buffer starts on a 256-byte boundary and is padded to one (sbr_api.hip: lay.p_bout =
+// take(N), sbr_align), so those floats are the arena's own.  Columns beyond the catalogue are replaced by -inf in head_tile_stats
+// whatever was read for them.
+__device__ __forceinline__ void head_bias(const HeadArgs& a, int n_lo, int wave, int q, f32x4 (&bv)[HEAD_NT]) {
+    const int c_last = (a.N - 1) & ~3;
+#pragma unroll
+    for (int i = 0; i < HEAD_NT; ++i) bv[i] = *(const f32x4*)(a.b + min(n_lo + 16 * (wave + 4 * i) + 4 * q, c_last));
+}
+
+// a wave's accumulators -> logits (+ bias; -inf beyond the catalogue) into lg, the wave's row maximum and sum of exponentials into
+// red_w[wave][row]
+__device__ __forceinline__ void head_tile_stats(const HeadArgs& a, const f32x4 (&acc)[HEAD_NT], const f32x4 (&bv)[HEAD_NT], int n_lo, int ntiles,
                                                 int wave, int j, int q, f32x4 (&lg)[HEAD_NT], float* __restrict__ red_w) {
-    constexpr int LDW = HP + 4;
     float mx = -INFINITY;
-    {
-        f32x4 acc[HEAD_NT];
 #pragma unroll
-        for (int i = 0; i < HEAD_NT; ++i) acc[i] = f32x4{0, 0, 0, 0};
-        const float* wr = Wl + (16 * wave + j) * LDW + 4 * q;          // tile wave + 4 i: + 64 i rows
-        const int ntw = ntiles > wave ? (ntiles - wave + 3) >> 2 : 0;   // tiles of this wave (wave-uniform)
-        // the tiles advance TOGETHER through k, one accumulator chain each; straight-line code per tile count (guards inside the
-        // loops made 160 basic blocks of it: 4.7 -> 24.7 us, profiles/round5_variants.txt call d)
-        switch (ntw) {
-            case 5: head_logits<HP, 5>(wr, hb, acc); break;
-            case 4: head_logits<HP, 4>(wr, hb, acc); break;
-            case 3: head_logits<HP, 3>(wr, hb, acc); break;
-            case 2: head_logits<HP, 2>(wr, hb, acc); break;
-            case 1: head_logits<HP, 1>(wr, hb, acc); break;
-            default: break;
-        }
-        asm volatile("s_nop 15");                                      // MFMA D -> VALU read (see sbr_gemm.hip)
+    for (int i = 0; i < HEAD_NT; ++i) {
+        const int t = wave + 4 * i;
+        const int c0 = n_lo + 16 * t + 4 * q;
 #pragma unroll
-        for (int i = 0; i < HEAD_NT; ++i) {
-            const int t = wave + 4 * i;
-            lg[i] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-            if (t < ntiles) {
-                const int c0 = n_lo + 16 * t + 4 * q;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float v = (c0 + r < a.N) ? acc[i][r] + a.b[c0 + r] : -INFINITY;
-                    lg[i][r] = v; mx = fmaxf(mx, v);
-                }
-            }
+        for (int r = 0; r < 4; ++r) {
+            const float v = (t < ntiles && c0 + r < a.N) ? acc[i][r] + bv[i][r] : -INFINITY;
+            lg[i][r] = v; mx = fmaxf(mx, v);
         }
     }
     mx = fmaxf(mx, __shfl_xor(mx, 16)); mx = fmaxf(mx, __shfl_xor(mx, 32));      // the lanes of a row: q = 0 .. 3
@@ -147,6 +145,31 @@ __device__ __forceinline__ void head_wave_stats(const HeadArgs& a, const float* 
     se += __shfl_xor(se, 16); se += __shfl_xor(se, 32);
     if (q == 0) { red_w[(wave * 16 + j) * 2] = mx; red_w[(wave * 16 + j) * 2 + 1] = se; }
 }
+
+// this wave's tiles of the chunk whose rows are in the LDS image: logits and statistics (bv: head_bias of the chunk, requested by the
+// caller in front of the chunk's fill)
+template <int HP>
+__device__ __forceinline__ void head_wave_stats(const HeadArgs& a, const float* __restrict__ Wl, const f32x4 (&hb)[HP / 16], const f32x4 (&bv)[HEAD_NT],
+                                                int n_lo, int ntiles, int wave, int j, int q, f32x4 (&lg)[HEAD_NT], float* __restrict__ red_w) {
+    constexpr int LDW = HP + 4;
+    f32x4 acc[HEAD_NT];
+#pragma unroll
+    for (int i = 0; i < HEAD_NT; ++i) acc[i] = f32x4{0, 0, 0, 0};
+    const float* wr = Wl + (16 * wave + j) * LDW + 4 * q;          // tile wave + 4 i: + 64 i rows
+    const int ntw = ntiles > wave ? (ntiles - wave + 3) >> 2 : 0;   // tiles of this wave (wave-uniform)
+    // the tiles advance TOGETHER through k, one accumulator chain each; straight-line code per tile count (guards inside the
+    // loops made 160 basic blocks of it: 4.7 -> 24.7 us, profiles/round5_variants.txt call d)
+    switch (ntw) {
+        case 5: head_logits<HP, 5>(wr, hb, acc); break;
+        case 4: head_logits<HP, 4>(wr, hb, acc); break;
+        case 3: head_logits<HP, 3>(wr, hb, acc); break;
+        case 2: head_logits<HP, 2>(wr, hb, acc); break;
+        case 1: head_logits<HP, 1>(wr, hb, acc); break;
+        default: break;
+    }
+    asm volatile("s_nop 15");                                      // MFMA D -> VALU read (see sbr_gemm.hip)
+    head_tile_stats(a, acc, bv, n_lo, ntiles, wave, j, q, lg, red_w);
+}
 // the four waves' statistics of row r -> the chunk's (fixed order)
 __device__ __forceinline__ void head_chunk_combine(const float* __restrict__ red_w, int r, float& m, float& s) {
     m = -INFINITY; s = 0.0f;
@@ -157,6 +180,29 @@ __device__ __forceinline__ void head_chunk_combine(const float* __restrict__ red
         const float mw = red_w[(w * 16 + r) * 2];
         if (mw > -INFINITY) s += red_w[(w * 16 + r) * 2 + 1] * __builtin_amdgcn_exp2f((mw - m) * HEAD_LOG2E);
     }
+}
+
+// dh partial of this wave's tiles: da[k tile] += sum over the tiles' items of W[item][k] g[row][item] with the LDS image (item =
+// reduction index: one ds_read_b32 per instruction, conflict-free at stride HP + 4) and g as the B operand in the layout the logits
+// left (k slot q of instruction e of tile t is item 16 t + 4 q + e)
+template <int HP>
+__device__ __forceinline__ void head_dh(const float* __restrict__ Wl, const f32x4 (&g)[HEAD_NT], int ntiles, int wave, int j, int q, f32x4 (&da)[HP / 16]) {
+    constexpr int LDW = HP + 4, KG = HP / 16;
+#pragma unroll
+    for (int kt = 0; kt < KG; ++kt) da[kt] = f32x4{0, 0, 0, 0};
+#pragma unroll
+    for (int i = 0; i < HEAD_NT; ++i) {
+        const int t = wave + 4 * i;
+        if (t < ntiles) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float* wr = Wl + (16 * t + 4 * q + e) * LDW + j;
+#pragma unroll
+                for (int kt = 0; kt < KG; ++kt) da[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * kt], g[i][e], da[kt], 0, 0, 0);
+            }
+        }
+    }
+    asm volatile("s_nop 15");                                          // MFMA D -> VALU read
 }
 
 template <int HP>
@@ -176,23 +222,29 @@ __global__ void __launch_bounds__(256) head_cce_kernel(HeadArgs a) {
     float* red_w = lds + wl_floats;                                    // [4][16][2] the waves' statistics of the chunk in LDS
     float* cst = red_w + 128;                                          // [CC <= 16][16][2] every chunk's statistics of this row block
     int* miss = (int*)(cst + 512);                                     // [16] chunks whose workgroup did not publish in time
-    // ---- 0. W chunk -> LDS (rows beyond the catalogue: zeros), h rows -> registers
+    // ---- 0. everything the launch reads is requested here, in one go: the h rows (every wave keeps them as the MFMA's B operand), the
+    //      row's target and popularity, the bias of the wave's tiles, the W chunk -> LDS (rows beyond the catalogue: zeros).  Nothing
+    //      in front of the fill waits for a load: the store that needs the target comes behind the logits.
     const int row = rb * 16 + j;
     f32x4 hb[KG];
 #pragma unroll
     for (int g = 0; g < KG; ++g) hb[g] = *(const f32x4*)(a.h + (size_t)row * HP + 16 * g + 4 * q);
     const int y = a.tgt[row];
-    const float scale = a.inv_Bg / a.pop[row];
+    const float popr = a.pop[row];
+    f32x4 lg[HEAD_NT];
+    {
+        f32x4 bv[HEAD_NT];
+        head_bias(a, n_lo, wave, q, bv);
+        if (tid < 16) miss[tid] = 0;
+        head_fill<HP>(a, Wl, n_lo, tid);
+        __syncthreads();
+        HEAD_STAMP(1);
+        // ---- 1. logits of this wave's tiles, 2. the waves' row statistics
+        head_wave_stats<HP>(a, Wl, hb, bv, n_lo, ntiles, wave, j, q, lg, red_w);
+    }
+    const float scale = a.inv_Bg / popr;
     // (a target outside the catalogue hits no column: the row's cost is written here, or last step's value would be summed again)
     if (cc == 0 && wave == 0 && q == 0 && (unsigned)y >= (unsigned)a.N) a.rowcost[row] = 0.0f;
-    if (tid < 16) miss[tid] = 0;
-    head_fill<HP>(a, Wl, n_lo, tid);
-    __syncthreads();
-    HEAD_STAMP(1);
-    // ---- 1. logits of this wave's tiles, 2. the waves' row statistics
-    f32x4 lg[HEAD_NT];
-    head_wave_stats<HP>(a, Wl, hb, n_lo, ntiles, wave, j, q, lg, red_w);
-    HEAD_STAMP(2);
     __syncthreads();
     if (tid < 16) {                                                    // this chunk's (max, sum) of row tid: kept, and published
         float m, sx;
@@ -204,6 +256,30 @@ __global__ void __launch_bounds__(256) head_cce_kernel(HeadArgs a) {
         __hip_atomic_store(p + 1, mb ^ a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(p + 2, sb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __hip_atomic_store(p + 3, sb ^ a.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    HEAD_STAMP(2);
+    // ---- 3. dh partial of this chunk UNDER the exchange: dh is linear in the softmax numerators, so it is formed from the
+    //      un-normalised p~ = exp2((l - m_c) log2e) with m_c the CHUNK's row maximum (<= 1: no overflow; a chunk wholly beyond the
+    //      catalogue has m_c = -inf and numerators 0, not NaN), the target's column left out, and scaled once M and S are known.
+    f32x4 da[KG], wy[KG];
+    float mc = -INFINITY;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) mc = fmaxf(mc, red_w[(w * 16 + j) * 2]);      // (head_chunk_combine's m of row j)
+    {
+        f32x4 pt[HEAD_NT];
+#pragma unroll
+        for (int i = 0; i < HEAD_NT; ++i) {
+            const int c0 = n_lo + 16 * (wave + 4 * i) + 4 * q;
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+                pt[i][r] = (mc > -INFINITY && c0 + r != y) ? __builtin_amdgcn_exp2f((lg[i][r] - mc) * HEAD_LOG2E) : 0.0f;      // (-inf -> 0)
+        }
+        head_dh<HP>(Wl, pt, ntiles, wave, j, q, da);
+        // the target's row of the image (any row where the target is not a column of this chunk: its factor is 0 then)
+        const int ly = y - n_lo;
+        const float* wr = Wl + (((unsigned)ly < (unsigned)a.CW && (unsigned)y < (unsigned)a.N) ? ly : 0) * LDW + 4 * q;
+#pragma unroll
+        for (int kt = 0; kt < KG; ++kt) wy[kt] = *(const f32x4*)(wr + 16 * kt);
     }
     HEAD_STAMP(3);
     // The other chunks' statistics.  A workgroup that has not published within HEAD_WAIT_TICKS is not waited for: its chunk's
@@ -229,17 +305,19 @@ __global__ void __launch_bounds__(256) head_cce_kernel(HeadArgs a) {
         if (ok) { cst[(c * 16 + r) * 2] = __uint_as_float(d0); cst[(c * 16 + r) * 2 + 1] = __uint_as_float(d2); }
         else miss[c] = 1;
     }
-    __syncthreads();
+    __syncthreads();                                                   // (every wave is through with the image, too: dh is in registers)
     {
         bool any = false;
         for (int c = 0; c < a.CC; ++c) {
             if (!miss[c]) continue;                                    // (LDS word: the same answer in every thread)
             any = true;
             __syncthreads();                                           // everyone has read miss[c] / finished with the image
+            f32x4 bx[HEAD_NT];
+            head_bias(a, c * a.CW, wave, q, bx);
             head_fill<HP>(a, Wl, c * a.CW, tid);
             __syncthreads();
             f32x4 lgx[HEAD_NT];
-            head_wave_stats<HP>(a, Wl, hb, c * a.CW, ntiles, wave, j, q, lgx, red_w);
+            head_wave_stats<HP>(a, Wl, hb, bx, c * a.CW, ntiles, wave, j, q, lgx, red_w);
             __syncthreads();
             if (tid < 16) {
                 float m, sx;
@@ -247,21 +325,19 @@ __global__ void __launch_bounds__(256) head_cce_kernel(HeadArgs a) {
                 cst[(c * 16 + tid) * 2] = m; cst[(c * 16 + tid) * 2 + 1] = sx;
             }
         }
-        if (any) {                                                     // this chunk's own rows again: phase 4 multiplies with them
-            __syncthreads();
-            head_fill<HP>(a, Wl, n_lo, tid);
-            __syncthreads();
-        }
+        if (any) __syncthreads();                                      // cst complete (the own rows are not filled again: dh is in registers)
     }
     float M = -INFINITY, S = 0.0f;
     for (int c = 0; c < a.CC; ++c) M = fmaxf(M, cst[(c * 16 + j) * 2]);
     for (int c = 0; c < a.CC; ++c) {                                   // chunk order: the same bits in every workgroup of the row block
-        const float mc = cst[(c * 16 + j) * 2];
-        if (mc > -INFINITY) S += cst[(c * 16 + j) * 2 + 1] * __builtin_amdgcn_exp2f((mc - M) * HEAD_LOG2E);
+        const float mc_c = cst[(c * 16 + j) * 2];
+        if (mc_c > -INFINITY) S += cst[(c * 16 + j) * 2 + 1] * __builtin_amdgcn_exp2f((mc_c - M) * HEAD_LOG2E);
     }
     const float inv = 1.0f / S;
     HEAD_STAMP(4);
-    // ---- 3. dlogits (in the registers of the tile), the row's cost
+    // ---- 4. dlogits from the logits kept in registers (the expressions, and the bits, of the form that multiplied them afterwards), the
+    //      row's cost
+    float dy = 0.0f;                                                   // the target's dlogit, in the lane that holds its column
 #pragma unroll
     for (int i = 0; i < HEAD_NT; ++i) {
         const int t = wave + 4 * i;
@@ -274,31 +350,19 @@ __global__ void __launch_bounds__(256) head_cce_kernel(HeadArgs a) {
                 const float p = __builtin_amdgcn_exp2f((v - M) * HEAD_LOG2E) * inv;      // (column beyond the catalogue: 0)
                 const bool hit = c0 + r == y;
                 d[r] = (p - (hit ? 1.0f : 0.0f)) * scale;
-                if (hit) a.rowcost[row] = (logf(S) + M - v) * scale;
+                if (hit) { a.rowcost[row] = (logf(S) + M - v) * scale; dy = d[r]; }
             }
-            lg[i] = d;
             if (c0 < a.N) *(f32x4*)(a.dlog + (size_t)row * a.Nl + c0) = d;
-        } else lg[i] = f32x4{0, 0, 0, 0};
-    }
-    HEAD_STAMP(5);
-    // ---- 4. dh partial of this chunk
-    f32x4 da[KG];
-#pragma unroll
-    for (int kt = 0; kt < KG; ++kt) da[kt] = f32x4{0, 0, 0, 0};
-#pragma unroll
-    for (int i = 0; i < HEAD_NT; ++i) {
-        const int t = wave + 4 * i;
-        if (t < ntiles) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float* wr = Wl + (16 * t + 4 * q + e) * LDW + j;
-#pragma unroll
-                for (int kt = 0; kt < KG; ++kt) da[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wr[16 * kt], lg[i][e], da[kt], 0, 0, 0);
-            }
         }
     }
-    asm volatile("s_nop 15");
-    __syncthreads();                                                   // every wave has read its W rows: the image becomes the partials
+    HEAD_STAMP(5);
+    // ---- 5. the accumulators of a lane all belong to batch row j: scaled by exp2((m_c - M) log2e) / S / (pop B) (0 where the chunk lies
+    //      too far below M to count, or beyond the catalogue), plus the target's term (p_y - 1) / (pop B) W[y][.] with p_y - 1 as the
+    //      dlogits form it -- no sum(p W) - W_y cancellation
+    dy += __shfl_xor(dy, 16); dy += __shfl_xor(dy, 32);                // (one lane of the row holds it, in one wave; the others add 0)
+    const float f = __builtin_amdgcn_exp2f((mc - M) * HEAD_LOG2E) * inv * scale;
+#pragma unroll
+    for (int kt = 0; kt < KG; ++kt) da[kt] = da[kt] * f + dy * wy[kt];
     HEAD_STAMP(6);
     float* part = Wl + (size_t)wave * 16 * HP;
 #pragma unroll

@@ -1,6 +1,7 @@
 """Phase stamps of the one-launch head (csrc/sbr_head.hip, SBR_FLAG_PROFILE_REC): per workgroup the 100 MHz clock at
-  0 start | 1 W chunk in LDS, h in registers | 2 logits done | 3 chunk statistics published | 4 all chunks' statistics read and
-  combined | 5 dlogits stored | 6 dh MFMAs done | 7 slab stored
+  0 start | 1 W chunk in LDS (every request of the launch issued in front of it) | 2 logits done, chunk statistics published |
+  3 dh MFMAs done (un-normalised, under the exchange) | 4 all chunks' statistics read and combined | 5 dlogits stored |
+  6 dh scaled, the target's term added | 7 slab stored
 printed relative to the launch's first stamp, mean / min / max over the workgroups, in microseconds.
     python tools/head_prof.py [c2|c1]"""
 import os, sys
@@ -22,7 +23,7 @@ for _ in range(4):
 raw = eng.debug_buffer("prof_head").view(np.uint64)[:256 * 8].reshape(256, 8).astype(np.int64)
 raw = raw[: (B // 16) * cc]
 t0 = raw[:, 0].min()
-names = ["start", "W chunk in LDS", "logits", "stats published", "stats combined", "dlogits stored", "dh MFMAs", "slab stored"]
+names = ["start", "W chunk in LDS", "stats published", "dh MFMAs", "stats combined", "dlogits stored", "dh scaled", "slab stored"]
 for i, nm in enumerate(names):
     v = (raw[:, i] - t0) / 100.0
     print("%-18s mean %6.2f  min %6.2f  max %6.2f us" % (nm, v.mean(), v.min(), v.max()))
