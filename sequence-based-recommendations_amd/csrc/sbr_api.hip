@@ -499,7 +499,7 @@ static SbrSparseUpd sparse_upd(sbr_handle* h) {
 static inline bool sparse_lazy(const sbr_handle* h) { return h->lay.n_sparse > 0 && h->lay.cfg.updater != SBR_UPD_ADAGRAD; }
 
 // every row of every sparse block current through the last applied step (before parameters are read as a whole)
-static int flush_lazy(sbr_handle* h, int only_kind = -1) {
+int flush_lazy(sbr_handle* h, int only_kind) {
     if (!sparse_lazy(h)) return SBR_OK;
     for (int b = 0; b < h->lay.n_sparse; ++b)
         if (only_kind < 0 || h->lay.sparse[b].kind == only_kind)
@@ -672,7 +672,7 @@ static inline void layer_gemm_hint(const sbr_handle* h, bool grad_a, bool grad_b
     if (h->lay.cfg.flags & SBR_FLAG_BF16_LAYERS) sbr_gemm_hint(1, 1.0f, 1.0f);
     else if (layer_gemm_f16(h, grad_a || grad_b)) sbr_gemm_hint(2, grad_a ? 512.0f : 1.0f, grad_b ? 512.0f : 1.0f);
 }
-static inline bool simple_gemm(const sbr_handle* h) { return h->lay.cfg.flags & SBR_FLAG_SIMPLE_GEMM; }
+bool simple_gemm(const sbr_handle* h) { return h->lay.cfg.flags & SBR_FLAG_SIMPLE_GEMM; }
 // Does a step over `rows` batch rows take the one-launch sampled head (head_sampled_kernel)?  Asked by the step and by sbr_query.
 static bool head_sampled_taken(const sbr_handle* h, int rows) {
     const Layout& y = h->lay;
@@ -1025,7 +1025,7 @@ extern "C" int sbr_forward(sbr_handle* h) {
     return SBR_OK;
 }
 
-static float* h_last(sbr_handle* h) {   // hid_out[-1] (sparse_lstm.py:485-486) = slot T of the top layer
+float* h_last(sbr_handle* h) {   // hid_out[-1] (sparse_lstm.py:485-486) = slot T of the top layer
     const Layout& y = h->lay; const LayerLayout& ly = y.layer[(y.L - 1) * y.D];
     if (y.D == 2) return h->A(y.a_hcat);                 // [forward final | backwards final], filled by forward_bi
     return h->A(ly.a_hs) + (size_t)y.T * y.Bp * ly.Hp;
@@ -1837,7 +1837,7 @@ static int report_fault(sbr_handle* h, int fault) {
                   (fault & 1) ? "SBR_CLUSTER=0" : (fault & 8) ? "SBR_TAIL_OVERLAP=0" : "SBR_X6_PIPE=0");
     return SBR_EHIP;
 }
-static int check_fault(sbr_handle* h) {        // synchronises the stream
+int check_fault(sbr_handle* h) {        // synchronises the stream
     int fault = 0;
     SBR_HIP(hipMemcpyAsync(&fault, h->A(h->lay.a_fault), sizeof(int), hipMemcpyDeviceToHost, h->stream));
     SBR_HIP(hipStreamSynchronize(h->stream));
@@ -1921,11 +1921,10 @@ extern "C" int sbr_lagged_flush(sbr_handle* h, float* cost, int* have) {
 // ---------------------------------------------------------------------------------------
 // predict / top-k
 // ---------------------------------------------------------------------------------------
-static int full_scores(sbr_handle* h, int do_softmax) {
+int full_scores(sbr_handle* h, int do_softmax) {
     const Layout& y = h->lay;
     int rc;
-    if (!h->fwd_done && (rc = sbr_forward(h)) != SBR_OK) return rc;
-    if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;      // every item is scored: all of W_out^T / b_out must be current
+    if ((rc = forward_current(h)) != SBR_OK) return rc;    // every item is scored: all of W_out^T / b_out must be current
     float* lg = h->A(y.a_logits);
     // scoring always runs the exact-f32 kernel: a row's scores (hence its ranked ids) must not depend on how many rows
     // share the call (the bf16x6 kernel takes over at >= 96 rows and rounds differently)
@@ -1974,375 +1973,6 @@ extern "C" int sbr_topk(sbr_handle* h, int k, int exclude_seen, int32_t* ids_hos
     SBR_LAUNCH(launch_topk(h->stream, lg, h->n_rows, y.N, k, ids));
     SBR_HIP(hipMemcpyAsync(ids_host, ids, (size_t)h->n_rows * k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     return check_fault(h);          // ... nor rankings (test.py, validation)
-}
-
-// Ordered top-k of any depth with per-row exclusion lists (top_k_recommendations' k and exclude=, rnn_base.py:140-165, for a
-// whole batch): sbr_rank.hip.  Its scratch -- the device copies of the lists, the selected (key, id) pairs, the radix sort's
-// second pair, the results -- is the handle's own allocation and not part of the arena: its size follows k and the lists.
-static int rank_scratch(sbr_handle* h, size_t bytes) {
-    if (bytes <= h->rank_scratch_bytes) return SBR_OK;
-    if (h->rank_scratch) { (void)hipFree(h->rank_scratch); h->rank_scratch = nullptr; h->rank_scratch_bytes = 0; }
-    if (hipMalloc(&h->rank_scratch, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        h->rank_scratch = nullptr;
-        sbr_set_error("sbr_rank: hipMalloc(%zu) of the ranking scratch failed", bytes);
-        return SBR_ENOMEM;
-    }
-    h->rank_scratch_bytes = bytes;
-    return SBR_OK;
-}
-
-extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
-                        int32_t* ids_host, float* scores_host) {
-    CHECK_ARG(h && ids_host, "null argument");
-    if (!h->have_batch) { sbr_set_error("sbr_rank: no batch set"); return SBR_ESTATE; }
-    const Layout& y = h->lay;
-    const int rows = h->n_rows;
-    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
-    CHECK_ARG((excl_ids == nullptr) == (excl_off == nullptr), "excl_ids and excl_off: both or neither");
-    int64_t n_excl = 0;
-    if (excl_off) {         // everything about the lists is checked here, before anything is launched
-        CHECK_ARG(excl_off[0] >= 0, "excl_off[0] = %lld is negative", (long long)excl_off[0]);
-        for (int r = 0; r < rows; ++r)
-            CHECK_ARG(excl_off[r + 1] >= excl_off[r], "excl_off decreases at row %d (%lld -> %lld)", r, (long long)excl_off[r], (long long)excl_off[r + 1]);
-        for (int64_t j = excl_off[0]; j < excl_off[rows]; ++j)
-            CHECK_ARG(excl_ids[j] >= 0 && excl_ids[j] < y.N, "excluded id %d outside [0,%d)", excl_ids[j], y.N);
-        n_excl = excl_off[rows] - excl_off[0];
-    }
-    const bool radix = k > kRankSortLds;
-    const size_t rk = (size_t)rows * k;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_off = take((size_t)(rows + 1) * sizeof(long long)), o_eid = take((size_t)n_excl * sizeof(int));
-    const size_t o_nsel = take((size_t)rows * sizeof(int));
-    const size_t o_k0 = take(rk * sizeof(unsigned)), o_i0 = take(rk * sizeof(int));
-    const size_t o_k1 = take(radix ? rk * sizeof(unsigned) : 0), o_i1 = take(radix ? rk * sizeof(int) : 0);
-    const size_t o_oid = take(rk * sizeof(int)), o_osc = take(rk * sizeof(float));
-    int rc;
-    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
-    char* S = (char*)h->rank_scratch;
-    if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_topk ranks (and flushes lazily stepped rows)
-    float* lg = h->A(y.a_logits);
-    if (excl_off) {
-        std::vector<long long> off((size_t)rows + 1);
-        for (int r = 0; r <= rows; ++r) off[r] = (long long)(excl_off[r] - excl_off[0]);
-        // (pageable host memory: both copies have left the host buffers when they return)
-        SBR_HIP(hipMemcpyAsync(S + o_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        if (n_excl) SBR_HIP(hipMemcpyAsync(S + o_eid, excl_ids + excl_off[0], (size_t)n_excl * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        SBR_HIP(hipStreamSynchronize(h->stream));           // `off` goes out of scope
-    }
-    SBR_LAUNCH(launch_rank_exclude(h->stream, lg, rows, y.N, excl_off ? (const int*)(S + o_eid) : nullptr,
-                                   excl_off ? (const long long*)(S + o_off) : nullptr, exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
-    SBR_LAUNCH(launch_rank_select(h->stream, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
-    SBR_LAUNCH(launch_rank_sort(h->stream, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
-                                (const int*)(S + o_nsel), (int*)(S + o_oid), (float*)(S + o_osc), &h->last_rank_sort));
-    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    return check_fault(h);          // a forward that gave up must not hand out rankings
-}
-
-// what sbr_evaluate and sbr_cluster_evaluate check about the users, k and the dataset against the engine; on SBR_OK v holds the sorted goals
-static int eval_check_args(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, SbrEvalView& v) {
-    const Layout& y = h->lay;
-    int rc;
-    if ((rc = sbr_dataset_eval_view(d, &v, 0)) != SBR_OK) return rc;
-    CHECK_ARG(n >= 1, "n=%lld users: at least one", (long long)n);
-    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
-    CHECK_ARG(y.F == 1 || (y.F == 2 && v.rate && y.cfg.input_size == y.N + 10),
-              "a model with two indices per step needs the ratings attached to the dataset (sbr_dataset_set_options)");
-    CHECK_ARG(v.n_items == y.N && (y.cfg.input_size == y.N || y.F == 2), "dataset has %d items, the model %d", v.n_items, y.N);
-    CHECK_ARG(v.stream == h->stream, "dataset and engine must share one stream");
-    for (int64_t j = 0; j < n; ++j) {
-        CHECK_ARG(users[j] >= 0 && users[j] < v.n_users, "users[%lld] = %d outside [0,%lld)", (long long)j, users[j], (long long)v.n_users);
-        CHECK_ARG(v.h_off[users[j] + 1] - v.h_off[users[j]] >= 2, "user %d has fewer than two items: nothing to view or no goal", users[j]);
-    }
-    return sbr_dataset_eval_view(d, &v, 1);      // (first call for this dataset: sorts and uploads the goals)
-}
-
-// a chunk's rows become the current batch, in set 0, as sbr_set_batch would leave it
-static int eval_pack_chunk(sbr_handle* h, const SbrEvalView& v, const int* dusers, int rows) {
-    const Layout& y = h->lay;
-    hipStream_t s = h->stream;
-    h->bX = (const int*)h->A(y.a_X); h->blen = (const int*)h->A(y.a_len); h->btgt = (const int*)h->A(y.a_tgt);
-    h->bsmp = (const int*)h->A(y.a_smp); h->bpop = h->A(y.a_pop);
-    h->bb_set = 0; h->bb_unread = false;
-    if (rows < y.Bp && SBR_LOSS_IS_MARGIN(y.cfg.loss)) SBR_HIP(hipMemsetAsync(h->A(y.a_tgt), 0xFF, (size_t)y.Bp * y.NT * sizeof(int), s));   // no positives
-    SBR_LAUNCH(launch_ev_pack(s, v, dusers, rows, y.Bp, y.T, y.F, (int*)h->A(y.a_X), (int*)h->A(y.a_len), h->A(y.a_pop)));
-    h->n_rows = rows; h->have_batch = true; h->fwd_done = false;
-    return SBR_OK;
-}
-
-// Whole users evaluated on the device (include/sbr_rnn.h: sbr_evaluate; kernels: sbr_eval.hip).  Per chunk of local_batch users:
-// pack -> forward + projection (full_scores) -> exclusion from the dataset's CSR -> sbr_rank's select and sort -> hits, all on the
-// main stream; the per-user results of every chunk land at the chunk's offset of arrays sized for the whole call, and the host
-// waits once, in check_fault.  The pack writes batch set 0 on the main stream like sbr_set_batch's device-to-device copies, behind every
-// reader of the set (sbr_build_batch's comment, sbr_batch.hip), and leaves the handle as that call does.
-extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int exclude_mode, int32_t* ids_host,
-                            int32_t* n_pred_host, int32_t* hits_host, int32_t* first_hit_host, uint32_t* hitmask_host, int32_t* item_hits_host) {
-    CHECK_ARG(h && d && users && n_pred_host && hits_host && first_hit_host, "null argument");
-    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW_ZERO, "unknown exclusion mode %d", exclude_mode);
-    const Layout& y = h->lay;
-    SbrEvalView v;
-    int rc;
-    if ((rc = eval_check_args(h, d, users, n, k, v)) != SBR_OK) return rc;
-    const int B = y.B, words = (k + 31) / 32;
-    const bool radix = k > kRankSortLds;
-    const size_t bk = (size_t)B * k, nk = (size_t)n * k;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_users = take((size_t)n * sizeof(int)), o_npred = take((size_t)n * sizeof(int)), o_hits = take((size_t)n * sizeof(int));
-    const size_t o_first = take((size_t)n * sizeof(int)), o_mask = take(hitmask_host ? (size_t)n * words * sizeof(unsigned) : 0);
-    const size_t o_ihits = take(item_hits_host ? (size_t)y.N * sizeof(int) : 0);
-    const size_t o_oid = take((ids_host ? nk : bk) * sizeof(int));      // the ids of every user only when the caller fetches them
-    const size_t o_nsel = take((size_t)B * sizeof(int)), o_k0 = take(bk * sizeof(unsigned)), o_i0 = take(bk * sizeof(int));
-    const size_t o_k1 = take(radix ? bk * sizeof(unsigned) : 0), o_i1 = take(radix ? bk * sizeof(int) : 0), o_osc = take(bk * sizeof(float));
-    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
-    char* S = (char*)h->rank_scratch;
-    hipStream_t s = h->stream;
-    const int* dusers = (const int*)(S + o_users);
-    // (pageable host memory: the copy has left the caller's array when it returns)
-    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    if (item_hits_host) SBR_HIP(hipMemsetAsync(S + o_ihits, 0, (size_t)y.N * sizeof(int), s));
-    for (int64_t c0 = 0; c0 < n; c0 += B) {
-        const int rows = (int)std::min<int64_t>(B, n - c0);
-        if ((rc = eval_pack_chunk(h, v, dusers + c0, rows)) != SBR_OK) return rc;
-        if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_rank ranks (and flushes lazily stepped rows)
-        float* lg = h->A(y.a_logits);
-        SBR_LAUNCH(launch_ev_exclude(s, v, dusers + c0, rows, y.T, y.N, exclude_mode, lg));
-        int* oid = (int*)(S + o_oid) + (ids_host ? (size_t)c0 * k : 0);
-        SBR_LAUNCH(launch_rank_select(s, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
-        SBR_LAUNCH(launch_rank_sort(s, lg, rows, y.N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
-                                    (const int*)(S + o_nsel), oid, (float*)(S + o_osc), &h->last_rank_sort));
-        SBR_LAUNCH(launch_ev_hits(s, v, dusers + c0, rows, k, oid, (int*)(S + o_npred) + c0, (int*)(S + o_hits) + c0, (int*)(S + o_first) + c0,
-                                  hitmask_host ? (unsigned*)(S + o_mask) + (size_t)c0 * words : nullptr,
-                                  item_hits_host ? (int*)(S + o_ihits) : nullptr));
-    }
-    if (ids_host) SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, nk * sizeof(int), hipMemcpyDeviceToHost, s));
-    SBR_HIP(hipMemcpyAsync(n_pred_host, S + o_npred, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    SBR_HIP(hipMemcpyAsync(hits_host, S + o_hits, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    SBR_HIP(hipMemcpyAsync(first_hit_host, S + o_first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (hitmask_host) SBR_HIP(hipMemcpyAsync(hitmask_host, S + o_mask, (size_t)n * words * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    if (item_hits_host) SBR_HIP(hipMemcpyAsync(item_hits_host, S + o_ihits, (size_t)y.N * sizeof(int), hipMemcpyDeviceToHost, s));
-    return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
-}
-
-// Ranking inside each row's item cluster (RNNCluster.predict_function for a whole batch, rnn_cluster.py:302-325; kernels and the
-// accumulation-order argument: sbr_cluster_rank.hip).  The member lists are the cluster object's, everything a call needs beyond
-// them sits in the handle's ranking scratch.
-extern "C" int sbr_cluster_rank(sbr_cluster* c, sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
-                                int32_t* ids_host, float* scores_host, int32_t* cluster_host, int32_t* size_host) {
-    CHECK_ARG(c && h && ids_host, "null argument");
-    if (!h->have_batch) { sbr_set_error("sbr_cluster_rank: no batch set"); return SBR_ESTATE; }
-    const Layout& y = h->lay;
-    const int rows = h->n_rows, C = c->cfg.n_clusters, HL = y.cfg.layers[y.L - 1];
-    CHECK_ARG(c->cfg.n_items == y.N, "the cluster head has %d items, the engine %d", c->cfg.n_items, y.N);
-    CHECK_ARG(c->cfg.n_hidden == y.D * HL && c->cfg.hidden_split == HL, "the cluster head reads %d features (split %d), the engine's user representation has %d (split %d)",
-              c->cfg.n_hidden, c->cfg.hidden_split, y.D * HL, HL);
-    CHECK_ARG(c->stream == h->stream, "the cluster head and the engine are on different streams");
-    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
-    CHECK_ARG((excl_ids == nullptr) == (excl_off == nullptr), "excl_ids and excl_off: both or neither");
-    int64_t n_excl = 0;
-    if (excl_off) {         // everything about the lists is checked here, before anything is launched
-        CHECK_ARG(excl_off[0] >= 0, "excl_off[0] = %lld is negative", (long long)excl_off[0]);
-        for (int r = 0; r < rows; ++r)
-            CHECK_ARG(excl_off[r + 1] >= excl_off[r], "excl_off decreases at row %d (%lld -> %lld)", r, (long long)excl_off[r], (long long)excl_off[r + 1]);
-        for (int64_t j = excl_off[0]; j < excl_off[rows]; ++j)
-            CHECK_ARG(excl_ids[j] >= 0 && excl_ids[j] < y.N, "excluded id %d outside [0,%d)", excl_ids[j], y.N);
-        n_excl = excl_off[rows] - excl_off[0];
-    }
-    int rc;
-    if ((rc = sbr_cluster_build_lists(c)) != SBR_OK) return rc;      // (cached until R changes: sizes and Lmax are host values)
-    const int lmax = c->lmax, kk = std::min(k, lmax);
-    const bool radix = kk > kRankSortLds;
-    const size_t rk = (size_t)rows * k, rkk = (size_t)rows * kk;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-    const size_t o_off = take((size_t)(rows + 1) * sizeof(long long)), o_eid = take((size_t)n_excl * sizeof(int));
-    const size_t o_csel = take((size_t)rows * sizeof(int)), o_grp = take(sbr_crk_group_words(rows, C) * sizeof(int));
-    const size_t o_cs = take((size_t)rows * lmax * sizeof(float));
-    const size_t o_nsel = take((size_t)rows * sizeof(int));
-    const size_t o_k0 = take(rkk * sizeof(unsigned)), o_i0 = take(rkk * sizeof(int));
-    const size_t o_k1 = take(radix ? rkk * sizeof(unsigned) : 0), o_i1 = take(radix ? rkk * sizeof(int) : 0);
-    const size_t o_pos = take(rkk * sizeof(int)), o_psc = take(rkk * sizeof(float));
-    const size_t o_oid = take(rk * sizeof(int)), o_osc = take(rk * sizeof(float)), o_size = take((size_t)rows * sizeof(int));
-    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
-    char* S = (char*)h->rank_scratch;
-    int* csel = (int*)(S + o_csel);
-    float* cs = (float*)(S + o_cs);
-    // the restricted kernel restates the exact-f32 projection; the bf16 and the triage projections round differently, and their
-    // scores are gathered from the matrix those kernels write
-    const bool restricted = h->sw.cluster_rank && !(y.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
-    if (restricted) {
-        if (!h->fwd_done && (rc = sbr_forward(h)) != SBR_OK) return rc;
-        if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;      // the sampled heads step W_out^T / b_out rows lazily: every member row must be current
-    } else if ((rc = full_scores(h, 0)) != SBR_OK) return rc;
-    if (excl_off) {
-        std::vector<long long> off((size_t)rows + 1);
-        for (int r = 0; r <= rows; ++r) off[r] = (long long)(excl_off[r] - excl_off[0]);
-        SBR_HIP(hipMemcpyAsync(S + o_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
-        if (n_excl) SBR_HIP(hipMemcpyAsync(S + o_eid, excl_ids + excl_off[0], (size_t)n_excl * sizeof(int), hipMemcpyHostToDevice, h->stream));
-        SBR_HIP(hipStreamSynchronize(h->stream));           // `off` goes out of scope
-    }
-    if ((rc = sbr_cluster_select(c, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, rows, csel, nullptr)) != SBR_OK) return rc;
-    if (restricted) {
-        SBR_LAUNCH(launch_crk_group(h->stream, csel, rows, C, (int*)(S + o_grp)));
-        SBR_LAUNCH(launch_crk_score(h->stream, h_last(h), y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, c->mem_ids, c->mem_off,
-                                    (const int*)(S + o_grp), rows, C, lmax, cs));
-    } else
-        SBR_LAUNCH(launch_crk_gather(h->stream, h->A(y.a_logits), y.N, csel, c->mem_ids, c->mem_off, rows, lmax, cs));
-    h->last_cluster_rank_form = restricted ? 1 : 2;
-    SBR_LAUNCH(launch_crk_exclude(h->stream, cs, lmax, csel, c->mem_ids, c->mem_off, rows, y.N, excl_off ? (const int*)(S + o_eid) : nullptr,
-                                  excl_off ? (const long long*)(S + o_off) : nullptr, exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
-    SBR_LAUNCH(launch_rank_select(h->stream, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
-    SBR_LAUNCH(launch_rank_sort(h->stream, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
-                                (const int*)(S + o_nsel), (int*)(S + o_pos), (float*)(S + o_psc), &h->last_rank_sort));
-    SBR_LAUNCH(launch_crk_translate(h->stream, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
-                                    (int*)(S + o_oid), (float*)(S + o_osc), (int*)(S + o_size)));
-    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
-    if (cluster_host) SBR_HIP(hipMemcpyAsync(cluster_host, csel, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    if (size_host) SBR_HIP(hipMemcpyAsync(size_host, S + o_size, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return check_fault(h);          // a forward that gave up must not hand out rankings
-}
-
-// Whole users of a cluster model evaluated on the device (include/sbr_rnn.h: sbr_cluster_evaluate; kernels: sbr_cluster_eval.hip and
-// the ones sbr_evaluate and sbr_cluster_rank launch).  Per chunk of local_batch users: pack -> forward (+ projection where a full score
-// row is read) -> cluster selection -> the cluster ranking's score matrix, taken BEFORE any exclusion touches the full scores ->
-// [the whole-catalogue ranking, as sbr_evaluate runs it] -> exclusion, select, sort[, translate], hits of the cluster ranking.  All on
-// the main stream; results land at the chunk's offset of arrays sized for the whole call and the host waits once, in check_fault.
-struct CevRecords { size_t npred, hits, first, mask, ihits, oid; };
-static bool cev_out_ok(const sbr_eval_out* o) { return o->n_pred && o->hits && o->first_hit; }
-extern "C" int sbr_cluster_evaluate(sbr_cluster* c, sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int road,
-                                    int exclude_mode, const sbr_eval_out* whole, const sbr_eval_out* inside, int32_t* cluster_host,
-                                    int32_t* size_host, int32_t* cluster_use_host) {
-    CHECK_ARG(c && h && d && users && inside && cluster_host, "null argument");
-    CHECK_ARG(cev_out_ok(inside) && (!whole || cev_out_ok(whole)), "n_pred, hits and first_hit of a given sbr_eval_out are required");
-    CHECK_ARG(road == SBR_CEVAL_LISTS || road == SBR_CEVAL_PRODUCT, "unknown road %d", road);
-    const bool product = road == SBR_CEVAL_PRODUCT;
-    if (product) {
-        CHECK_ARG(exclude_mode == SBR_EVAL_EXCL_NONE || exclude_mode == SBR_EVAL_EXCL_WINDOW,
-                  "the PRODUCT road takes SBR_EVAL_EXCL_NONE or SBR_EVAL_EXCL_WINDOW, not mode %d", exclude_mode);
-        CHECK_ARG(!size_host, "size_host is the LISTS road's: the PRODUCT road ranks the whole catalogue");
-    } else
-        CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW,
-                  "the LISTS road takes SBR_EVAL_EXCL_NONE, _VIEWED or _WINDOW, not mode %d", exclude_mode);
-    const Layout& y = h->lay;
-    const int C = c->cfg.n_clusters, HL = y.cfg.layers[y.L - 1];
-    CHECK_ARG(c->cfg.n_items == y.N, "the cluster head has %d items, the engine %d", c->cfg.n_items, y.N);
-    CHECK_ARG(c->cfg.n_hidden == y.D * HL && c->cfg.hidden_split == HL, "the cluster head reads %d features (split %d), the engine's user representation has %d (split %d)",
-              c->cfg.n_hidden, c->cfg.hidden_split, y.D * HL, HL);
-    CHECK_ARG(c->stream == h->stream, "the cluster head and the engine are on different streams");
-    SbrEvalView v;
-    int rc;
-    if ((rc = eval_check_args(h, d, users, n, k, v)) != SBR_OK) return rc;
-    // once per call, before the chunk loop: the member lists (host sizes, Lmax) or the membership matrix of the current R
-    if ((rc = product ? sbr_cluster_build_hard(c, 1) : sbr_cluster_build_lists(c)) != SBR_OK) return rc;
-    const int B = y.B, words = (k + 31) / 32, N = y.N;
-    const int lmax = product ? 0 : c->lmax, kk = product ? k : std::min(k, lmax);      // kk: the depth ranked in the cluster matrix
-    // the restricted kernel restates the exact-f32 projection (sbr_cluster_rank's comment); every other case reads full score rows
-    const bool restricted = !product && h->sw.cluster_rank && !(y.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
-    const bool full = whole || !restricted;
-    const bool radix = k > kRankSortLds;                                                // (kk <= k: sized for the deeper one)
-    // the whole-catalogue ranking scores the items fed 0.0 where the compiled test function of a margin model does (_exclude_mode)
-    const int whole_mode = (product && exclude_mode == SBR_EVAL_EXCL_WINDOW && SBR_LOSS_IS_MARGIN(y.cfg.loss)) ? SBR_EVAL_EXCL_WINDOW_ZERO : exclude_mode;
-    const size_t bk = (size_t)B * k, nk = (size_t)n * k;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; };
-    auto records = [&](const sbr_eval_out* o) {
-        CevRecords r{};
-        if (!o) return r;
-        r.npred = take((size_t)n * sizeof(int)); r.hits = take((size_t)n * sizeof(int)); r.first = take((size_t)n * sizeof(int));
-        r.mask = take(o->hitmask ? (size_t)n * words * sizeof(unsigned) : 0); r.ihits = take(o->item_hits ? (size_t)N * sizeof(int) : 0);
-        r.oid = take((o->ids ? nk : bk) * sizeof(int));      // the ids of every user only when the caller fetches them
-        return r;
-    };
-    const size_t o_users = take((size_t)n * sizeof(int)), o_csel = take((size_t)n * sizeof(int)), o_size = take((size_t)n * sizeof(int));
-    const size_t o_use = take((size_t)C * sizeof(int));
-    const CevRecords rw = records(whole), ri = records(inside);
-    const size_t o_grp = take(restricted ? sbr_crk_group_words(B, C) * sizeof(int) : 0);
-    const size_t o_cs = take((size_t)B * (product ? N : lmax) * sizeof(float));
-    const size_t o_nsel = take((size_t)B * sizeof(int)), o_k0 = take(bk * sizeof(unsigned)), o_i0 = take(bk * sizeof(int));
-    const size_t o_k1 = take(radix ? bk * sizeof(unsigned) : 0), o_i1 = take(radix ? bk * sizeof(int) : 0), o_osc = take(bk * sizeof(float));
-    const size_t o_pos = take(product ? 0 : (size_t)B * kk * sizeof(int)), o_psc = take(product ? 0 : (size_t)B * kk * sizeof(float));
-    if ((rc = rank_scratch(h, at)) != SBR_OK) return rc;
-    char* S = (char*)h->rank_scratch;
-    hipStream_t s = h->stream;
-    const int* dusers = (const int*)(S + o_users);
-    int* dcsel = (int*)(S + o_csel);
-    float* cs = (float*)(S + o_cs);
-    // (pageable host memory: the copy has left the caller's array when it returns)
-    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
-    if (whole && whole->item_hits) SBR_HIP(hipMemsetAsync(S + rw.ihits, 0, (size_t)N * sizeof(int), s));
-    if (inside->item_hits) SBR_HIP(hipMemsetAsync(S + ri.ihits, 0, (size_t)N * sizeof(int), s));
-    if (cluster_use_host) SBR_HIP(hipMemsetAsync(S + o_use, 0, (size_t)C * sizeof(int), s));
-    auto hits = [&](const sbr_eval_out* o, const CevRecords& r, int64_t c0, int rows, const int* oid) {
-        return launch_ev_hits(s, v, dusers + c0, rows, k, oid, (int*)(S + r.npred) + c0, (int*)(S + r.hits) + c0, (int*)(S + r.first) + c0,
-                              o->hitmask ? (unsigned*)(S + r.mask) + (size_t)c0 * words : nullptr, o->item_hits ? (int*)(S + r.ihits) : nullptr);
-    };
-    for (int64_t c0 = 0; c0 < n; c0 += B) {
-        const int rows = (int)std::min<int64_t>(B, n - c0);
-        const int* cu = dusers + c0;
-        int* csel = dcsel + c0;
-        if ((rc = eval_pack_chunk(h, v, cu, rows)) != SBR_OK) return rc;
-        if (full) {
-            if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_rank ranks (and flushes lazily stepped rows)
-        } else {
-            if ((rc = sbr_forward(h)) != SBR_OK) return rc;
-            if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;       // every member row of W_out^T / b_out must be current
-        }
-        float* lg = h->A(y.a_logits);
-        if ((rc = sbr_cluster_select(c, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, rows, csel, nullptr)) != SBR_OK) return rc;
-        // --- the cluster ranking's scores, while the full scores are as the projection left them
-        if (product)
-            SBR_LAUNCH(launch_cev_product(s, v, cu, rows, y.T, N, C, exclude_mode == SBR_EVAL_EXCL_WINDOW, lg, csel, c->hardT, cs));
-        else if (restricted) {
-            SBR_LAUNCH(launch_crk_group(s, csel, rows, C, (int*)(S + o_grp)));
-            SBR_LAUNCH(launch_crk_score(s, h_last(h), y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, c->mem_ids, c->mem_off,
-                                        (const int*)(S + o_grp), rows, C, lmax, cs));
-        } else
-            SBR_LAUNCH(launch_crk_gather(s, lg, N, csel, c->mem_ids, c->mem_off, rows, lmax, cs));
-        if (!product) h->last_cluster_rank_form = restricted ? 1 : 2;
-        // --- the whole-catalogue ranking of the same forward pass: sbr_evaluate's chunk
-        if (whole) {
-            int* oid = (int*)(S + rw.oid) + (whole->ids ? (size_t)c0 * k : 0);
-            SBR_LAUNCH(launch_ev_exclude(s, v, cu, rows, y.T, N, whole_mode, lg));
-            SBR_LAUNCH(launch_rank_select(s, lg, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
-            SBR_LAUNCH(launch_rank_sort(s, lg, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
-                                        (const int*)(S + o_nsel), oid, (float*)(S + o_osc), &h->last_rank_sort));
-            SBR_LAUNCH(hits(whole, rw, c0, rows, oid));
-        }
-        // --- the cluster ranking
-        int* oid = (int*)(S + ri.oid) + (inside->ids ? (size_t)c0 * k : 0);
-        if (product) {
-            SBR_LAUNCH(launch_rank_select(s, cs, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
-            SBR_LAUNCH(launch_rank_sort(s, cs, rows, N, k, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
-                                        (const int*)(S + o_nsel), oid, (float*)(S + o_osc), &h->last_rank_sort));
-        } else {
-            SBR_LAUNCH(launch_cev_exclude(s, v, cu, rows, y.T, N, exclude_mode, cs, lmax, csel, C, c->mem_ids, c->mem_off));
-            SBR_LAUNCH(launch_rank_select(s, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (int*)(S + o_nsel), &h->last_rank_select));
-            SBR_LAUNCH(launch_rank_sort(s, cs, rows, lmax, kk, (unsigned*)(S + o_k0), (int*)(S + o_i0), (unsigned*)(S + o_k1), (int*)(S + o_i1),
-                                        (const int*)(S + o_nsel), (int*)(S + o_pos), (float*)(S + o_psc), &h->last_rank_sort));
-            SBR_LAUNCH(launch_crk_translate(s, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
-                                            oid, (float*)(S + o_osc), (int*)(S + o_size) + c0));
-        }
-        SBR_LAUNCH(hits(inside, ri, c0, rows, oid));
-    }
-    if (cluster_use_host) SBR_LAUNCH(launch_cev_use(s, dcsel, (long long)n, C, (int*)(S + o_use)));
-    auto fetch = [&](const sbr_eval_out* o, const CevRecords& r) -> int {
-        if (o->ids) SBR_HIP(hipMemcpyAsync(o->ids, S + r.oid, nk * sizeof(int), hipMemcpyDeviceToHost, s));
-        SBR_HIP(hipMemcpyAsync(o->n_pred, S + r.npred, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        SBR_HIP(hipMemcpyAsync(o->hits, S + r.hits, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        SBR_HIP(hipMemcpyAsync(o->first_hit, S + r.first, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (o->hitmask) SBR_HIP(hipMemcpyAsync(o->hitmask, S + r.mask, (size_t)n * words * sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        if (o->item_hits) SBR_HIP(hipMemcpyAsync(o->item_hits, S + r.ihits, (size_t)N * sizeof(int), hipMemcpyDeviceToHost, s));
-        return SBR_OK;
-    };
-    if (whole && (rc = fetch(whole, rw)) != SBR_OK) return rc;
-    if ((rc = fetch(inside, ri)) != SBR_OK) return rc;
-    SBR_HIP(hipMemcpyAsync(cluster_host, dcsel, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (size_host) SBR_HIP(hipMemcpyAsync(size_host, S + o_size, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (cluster_use_host) SBR_HIP(hipMemcpyAsync(cluster_use_host, S + o_use, (size_t)C * sizeof(int), hipMemcpyDeviceToHost, s));
-    return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
 }
 
 // ---------------------------------------------------------------------------------------

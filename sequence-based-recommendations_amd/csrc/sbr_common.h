@@ -337,6 +337,14 @@ void sbr_set_error(const char* fmt, ...);
 #define SBR_LAUNCH(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     sbr_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return SBR_EHIP; } } while (0)
 
+// What the ranking and evaluation calls (sbr_rank_api.hip) need of the engine (sbr_api.hip)
+int flush_lazy(sbr_handle* h, int only_kind = -1);   // every row of every sparse block (of that kind) current through the last applied step
+bool simple_gemm(const sbr_handle* h);               // SBR_FLAG_SIMPLE_GEMM: the triage projection
+float* h_last(sbr_handle* h);                        // the user representation of the current batch, [Bp][HLt]
+int check_fault(sbr_handle* h);                      // synchronises the stream; fails the call if a bounded wait of its kernels gave up
+int full_scores(sbr_handle* h, int do_softmax);      // forward_current + the projection into a_logits: the scores of every item
+int forward_current(sbr_handle* h);                  // (sbr_rank_api.hip) forward pass if the batch has none yet + lazily stepped output rows flushed
+
 // Consumers of a RUNNING BPTT chain (overlapped step tail): the chain's waves publish (epoch << 12) | t in words[0 .. n) once
 // all their time steps >= t are complete and written through (RecArgs.progress); ONE workgroup -- the MONITOR: workgroup 0 of
 // the scatter-add launch, or tail_monitor_kernel -- folds them into `done` = (epoch << 12) | max t, which every consumer polls.  rows_per_step: K rows per time step.

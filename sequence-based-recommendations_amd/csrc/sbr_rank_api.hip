@@ -1,0 +1,397 @@
+// The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_rank, sbr_evaluate, sbr_cluster_rank, sbr_cluster_evaluate.
+// Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_cluster_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
+// sbr_api.hip), built from the shared pieces below.  Every call waits for the device once, in check_fault.
+#include "sbr_common.h"
+#include <algorithm>
+
+// The scratch of these calls -- the device copies of the lists, the selected (key, id) pairs, the radix sort's second pair, the
+// results -- is the handle's own allocation and not part of the arena: its size follows k and the lists.
+static int rank_scratch(sbr_handle* h, size_t bytes) {
+    if (bytes <= h->rank_scratch_bytes) return SBR_OK;
+    if (h->rank_scratch) { (void)hipFree(h->rank_scratch); h->rank_scratch = nullptr; h->rank_scratch_bytes = 0; }
+    if (hipMalloc(&h->rank_scratch, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        h->rank_scratch = nullptr;
+        sbr_set_error("sbr_rank: hipMalloc(%zu) of the ranking scratch failed", bytes);
+        return SBR_ENOMEM;
+    }
+    h->rank_scratch_bytes = bytes;
+    return SBR_OK;
+}
+
+// byte offsets into the scratch, every region on a 256-byte boundary; `at` ends as the size to allocate
+struct Carver {
+    size_t at = 0;
+    size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; }
+};
+
+// what select + sort of `rows` rows to `depth` places work in: the selected count, the (key, id) pairs and, with radix, the second pair
+struct RankWork { size_t nsel, k0, i0, k1, i1; };
+static RankWork carve_rank_work(Carver& cv, int rows, int depth, bool radix) {
+    const size_t n = (size_t)rows * depth;
+    RankWork w;
+    w.nsel = cv.take((size_t)rows * sizeof(int));
+    w.k0 = cv.take(n * sizeof(unsigned)); w.i0 = cv.take(n * sizeof(int));
+    w.k1 = cv.take(radix ? n * sizeof(unsigned) : 0); w.i1 = cv.take(radix ? n * sizeof(int) : 0);
+    return w;
+}
+
+// the ordered top `depth` of every row of scores [rows][width] into out_ids / out_scores [rows][depth]
+static int rank_rows(sbr_handle* h, char* S, const RankWork& w, const float* scores, int rows, int width, int depth, int* out_ids, float* out_scores) {
+    SBR_LAUNCH(launch_rank_select(h->stream, scores, rows, width, depth, (unsigned*)(S + w.k0), (int*)(S + w.i0), (int*)(S + w.nsel), &h->last_rank_select));
+    SBR_LAUNCH(launch_rank_sort(h->stream, scores, rows, width, depth, (unsigned*)(S + w.k0), (int*)(S + w.i0), (unsigned*)(S + w.k1), (int*)(S + w.i1),
+                                (const int*)(S + w.nsel), out_ids, out_scores, &h->last_rank_sort));
+    return SBR_OK;
+}
+
+// The per-row exclusion lists of sbr_rank and sbr_cluster_rank: the caller's CSR, and where its device copy sits in the scratch
+struct ExclLists {
+    const int32_t* ids; const int64_t* off; int rows; int64_t n;      // n: ids in all
+    size_t o_off, o_ids;
+    const long long* dev_off(const char* S) const { return off ? (const long long*)(S + o_off) : nullptr; }
+    const int* dev_ids(const char* S) const { return off ? (const int*)(S + o_ids) : nullptr; }
+};
+// everything about the lists is checked here, before anything is launched
+static int excl_check(const int32_t* excl_ids, const int64_t* excl_off, int rows, int N, ExclLists& x) {
+    CHECK_ARG((excl_ids == nullptr) == (excl_off == nullptr), "excl_ids and excl_off: both or neither");
+    x = ExclLists{excl_ids, excl_off, rows, 0, 0, 0};
+    if (!excl_off) return SBR_OK;
+    CHECK_ARG(excl_off[0] >= 0, "excl_off[0] = %lld is negative", (long long)excl_off[0]);
+    for (int r = 0; r < rows; ++r)
+        CHECK_ARG(excl_off[r + 1] >= excl_off[r], "excl_off decreases at row %d (%lld -> %lld)", r, (long long)excl_off[r], (long long)excl_off[r + 1]);
+    for (int64_t j = excl_off[0]; j < excl_off[rows]; ++j)
+        CHECK_ARG(excl_ids[j] >= 0 && excl_ids[j] < N, "excluded id %d outside [0,%d)", excl_ids[j], N);
+    x.n = excl_off[rows] - excl_off[0];
+    return SBR_OK;
+}
+static void excl_carve(Carver& cv, ExclLists& x) {
+    x.o_off = cv.take((size_t)(x.rows + 1) * sizeof(long long)); x.o_ids = cv.take((size_t)x.n * sizeof(int));
+}
+static int excl_upload(sbr_handle* h, char* S, const ExclLists& x) {
+    if (!x.off) return SBR_OK;
+    std::vector<long long> off((size_t)x.rows + 1);
+    for (int r = 0; r <= x.rows; ++r) off[r] = (long long)(x.off[r] - x.off[0]);
+    // (pageable host memory: both copies have left the host buffers when they return)
+    SBR_HIP(hipMemcpyAsync(S + x.o_off, off.data(), off.size() * sizeof(long long), hipMemcpyHostToDevice, h->stream));
+    if (x.n) SBR_HIP(hipMemcpyAsync(S + x.o_ids, x.ids + x.off[0], (size_t)x.n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    SBR_HIP(hipStreamSynchronize(h->stream));           // `off` goes out of scope
+    return SBR_OK;
+}
+
+// the hidden state of the current batch with every output row current: full_scores minus its projection
+int forward_current(sbr_handle* h) {
+    int rc;
+    if (!h->fwd_done && (rc = sbr_forward(h)) != SBR_OK) return rc;
+    return flush_lazy(h, 1);      // the sampled heads step W_out^T / b_out rows lazily: every row that is scored must be current
+}
+
+// Ordered top-k of any depth with per-row exclusion lists (top_k_recommendations' k and exclude=, rnn_base.py:140-165, for a
+// whole batch): sbr_rank.hip.
+extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
+                        int32_t* ids_host, float* scores_host) {
+    CHECK_ARG(h && ids_host, "null argument");
+    if (!h->have_batch) { sbr_set_error("sbr_rank: no batch set"); return SBR_ESTATE; }
+    const Layout& y = h->lay;
+    const int rows = h->n_rows;
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    ExclLists x;
+    int rc;
+    if ((rc = excl_check(excl_ids, excl_off, rows, y.N, x)) != SBR_OK) return rc;
+    const size_t rk = (size_t)rows * k;
+    Carver cv;
+    excl_carve(cv, x);
+    const RankWork w = carve_rank_work(cv, rows, k, k > kRankSortLds);
+    const size_t o_oid = cv.take(rk * sizeof(int)), o_osc = cv.take(rk * sizeof(float));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_topk ranks (and flushes lazily stepped rows)
+    float* lg = h->A(y.a_logits);
+    if ((rc = excl_upload(h, S, x)) != SBR_OK) return rc;
+    SBR_LAUNCH(launch_rank_exclude(h->stream, lg, rows, y.N, x.dev_ids(S), x.dev_off(S), exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
+    if ((rc = rank_rows(h, S, w, lg, rows, y.N, k, (int*)(S + o_oid), (float*)(S + o_osc))) != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    return check_fault(h);          // a forward that gave up must not hand out rankings
+}
+
+// what sbr_evaluate and sbr_cluster_evaluate check about the users, k and the dataset against the engine; on SBR_OK v holds the sorted goals
+static int eval_check_args(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, SbrEvalView& v) {
+    const Layout& y = h->lay;
+    int rc;
+    if ((rc = sbr_dataset_eval_view(d, &v, 0)) != SBR_OK) return rc;
+    CHECK_ARG(n >= 1, "n=%lld users: at least one", (long long)n);
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    CHECK_ARG(y.F == 1 || (y.F == 2 && v.rate && y.cfg.input_size == y.N + 10),
+              "a model with two indices per step needs the ratings attached to the dataset (sbr_dataset_set_options)");
+    CHECK_ARG(v.n_items == y.N && (y.cfg.input_size == y.N || y.F == 2), "dataset has %d items, the model %d", v.n_items, y.N);
+    CHECK_ARG(v.stream == h->stream, "dataset and engine must share one stream");
+    for (int64_t j = 0; j < n; ++j) {
+        CHECK_ARG(users[j] >= 0 && users[j] < v.n_users, "users[%lld] = %d outside [0,%lld)", (long long)j, users[j], (long long)v.n_users);
+        CHECK_ARG(v.h_off[users[j] + 1] - v.h_off[users[j]] >= 2, "user %d has fewer than two items: nothing to view or no goal", users[j]);
+    }
+    return sbr_dataset_eval_view(d, &v, 1);      // (first call for this dataset: sorts and uploads the goals)
+}
+
+// a chunk's rows become the current batch, in set 0, as sbr_set_batch would leave it
+static int eval_pack_chunk(sbr_handle* h, const SbrEvalView& v, const int* dusers, int rows) {
+    const Layout& y = h->lay;
+    hipStream_t s = h->stream;
+    h->bX = (const int*)h->A(y.a_X); h->blen = (const int*)h->A(y.a_len); h->btgt = (const int*)h->A(y.a_tgt);
+    h->bsmp = (const int*)h->A(y.a_smp); h->bpop = h->A(y.a_pop);
+    h->bb_set = 0; h->bb_unread = false;
+    if (rows < y.Bp && SBR_LOSS_IS_MARGIN(y.cfg.loss)) SBR_HIP(hipMemsetAsync(h->A(y.a_tgt), 0xFF, (size_t)y.Bp * y.NT * sizeof(int), s));   // no positives
+    SBR_LAUNCH(launch_ev_pack(s, v, dusers, rows, y.Bp, y.T, y.F, (int*)h->A(y.a_X), (int*)h->A(y.a_len), h->A(y.a_pop)));
+    h->n_rows = rows; h->have_batch = true; h->fwd_done = false;
+    return SBR_OK;
+}
+
+// One ranking's per-user records of an evaluation call (an sbr_eval_out's device side): sized for all n users of the call, every chunk
+// writes at its offset; `oid` holds the ids of every user only when the caller fetches them, otherwise one chunk's
+struct EvalRecords {
+    const sbr_eval_out* o; int64_t n; int k, words, N;
+    size_t npred, hits, first, mask, ihits, oid;
+    int* ids_at(char* S, int64_t c0) const { return (int*)(S + oid) + (o->ids ? (size_t)c0 * k : 0); }
+};
+static bool eval_out_ok(const sbr_eval_out* o) { return o->n_pred && o->hits && o->first_hit; }
+static EvalRecords carve_records(Carver& cv, const sbr_eval_out* o, int64_t n, int k, int N, int B) {
+    EvalRecords r{o, n, k, (k + 31) / 32, N, 0, 0, 0, 0, 0, 0};
+    if (!o) return r;
+    r.npred = cv.take((size_t)n * sizeof(int)); r.hits = cv.take((size_t)n * sizeof(int)); r.first = cv.take((size_t)n * sizeof(int));
+    r.mask = cv.take(o->hitmask ? (size_t)n * r.words * sizeof(unsigned) : 0); r.ihits = cv.take(o->item_hits ? (size_t)N * sizeof(int) : 0);
+    r.oid = cv.take((o->ids ? (size_t)n * k : (size_t)B * k) * sizeof(int));
+    return r;
+}
+// before the chunk loop: item_hits is the one record the chunks add to
+static int clear_records(sbr_handle* h, char* S, const EvalRecords& r) {
+    if (r.o && r.o->item_hits) SBR_HIP(hipMemsetAsync(S + r.ihits, 0, (size_t)r.N * sizeof(int), h->stream));
+    return SBR_OK;
+}
+// the records of the chunk's users [c0, c0 + rows) from their ranked ids
+static int launch_hits(sbr_handle* h, char* S, const EvalRecords& r, const SbrEvalView& v, const int* users, int64_t c0, int rows, const int* ids) {
+    SBR_LAUNCH(launch_ev_hits(h->stream, v, users + c0, rows, r.k, ids, (int*)(S + r.npred) + c0, (int*)(S + r.hits) + c0, (int*)(S + r.first) + c0,
+                              r.o->hitmask ? (unsigned*)(S + r.mask) + (size_t)c0 * r.words : nullptr, r.o->item_hits ? (int*)(S + r.ihits) : nullptr));
+    return SBR_OK;
+}
+static int fetch_records(sbr_handle* h, const char* S, const EvalRecords& r) {
+    const sbr_eval_out* o = r.o;
+    hipStream_t s = h->stream;
+    const size_t n = (size_t)r.n;
+    if (o->ids) SBR_HIP(hipMemcpyAsync(o->ids, S + r.oid, n * r.k * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(o->n_pred, S + r.npred, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(o->hits, S + r.hits, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(o->first_hit, S + r.first, n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (o->hitmask) SBR_HIP(hipMemcpyAsync(o->hitmask, S + r.mask, n * r.words * sizeof(unsigned), hipMemcpyDeviceToHost, s));
+    if (o->item_hits) SBR_HIP(hipMemcpyAsync(o->item_hits, S + r.ihits, (size_t)r.N * sizeof(int), hipMemcpyDeviceToHost, s));
+    return SBR_OK;
+}
+
+// Whole users evaluated on the device (include/sbr_rnn.h: sbr_evaluate; kernels: sbr_eval.hip).  Per chunk of local_batch users:
+// pack -> forward + projection (full_scores) -> exclusion from the dataset's CSR -> sbr_rank's select and sort -> hits, all on the
+// main stream; the per-user results of every chunk land at the chunk's offset of arrays sized for the whole call, and the host
+// waits once, in check_fault.  The pack writes batch set 0 on the main stream like sbr_set_batch's device-to-device copies, behind every
+// reader of the set (sbr_build_batch's comment, sbr_batch.hip), and leaves the handle as that call does.
+extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int exclude_mode, int32_t* ids_host,
+                            int32_t* n_pred_host, int32_t* hits_host, int32_t* first_hit_host, uint32_t* hitmask_host, int32_t* item_hits_host) {
+    CHECK_ARG(h && d && users && n_pred_host && hits_host && first_hit_host, "null argument");
+    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW_ZERO, "unknown exclusion mode %d", exclude_mode);
+    const Layout& y = h->lay;
+    SbrEvalView v;
+    int rc;
+    if ((rc = eval_check_args(h, d, users, n, k, v)) != SBR_OK) return rc;
+    const sbr_eval_out out{ids_host, n_pred_host, hits_host, first_hit_host, hitmask_host, item_hits_host};
+    const int B = y.B;
+    Carver cv;
+    const size_t o_users = cv.take((size_t)n * sizeof(int));
+    const EvalRecords rec = carve_records(cv, &out, n, k, y.N, B);
+    const RankWork w = carve_rank_work(cv, B, k, k > kRankSortLds);
+    const size_t o_osc = cv.take((size_t)B * k * sizeof(float));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    // (pageable host memory: the copy has left the caller's array when it returns)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if ((rc = clear_records(h, S, rec)) != SBR_OK) return rc;
+    for (int64_t c0 = 0; c0 < n; c0 += B) {
+        const int rows = (int)std::min<int64_t>(B, n - c0);
+        if ((rc = eval_pack_chunk(h, v, dusers + c0, rows)) != SBR_OK) return rc;
+        if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_rank ranks (and flushes lazily stepped rows)
+        float* lg = h->A(y.a_logits);
+        SBR_LAUNCH(launch_ev_exclude(s, v, dusers + c0, rows, y.T, y.N, exclude_mode, lg));
+        int* oid = rec.ids_at(S, c0);
+        if ((rc = rank_rows(h, S, w, lg, rows, y.N, k, oid, (float*)(S + o_osc))) != SBR_OK) return rc;
+        if ((rc = launch_hits(h, S, rec, v, dusers, c0, rows, oid)) != SBR_OK) return rc;
+    }
+    if ((rc = fetch_records(h, S, rec)) != SBR_OK) return rc;
+    return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
+}
+
+static int cluster_fits_engine(const sbr_cluster* c, const sbr_handle* h) {
+    const Layout& y = h->lay;
+    const int HL = y.cfg.layers[y.L - 1];
+    CHECK_ARG(c->cfg.n_items == y.N, "the cluster head has %d items, the engine %d", c->cfg.n_items, y.N);
+    CHECK_ARG(c->cfg.n_hidden == y.D * HL && c->cfg.hidden_split == HL, "the cluster head reads %d features (split %d), the engine's user representation has %d (split %d)",
+              c->cfg.n_hidden, c->cfg.hidden_split, y.D * HL, HL);
+    CHECK_ARG(c->stream == h->stream, "the cluster head and the engine are on different streams");
+    return SBR_OK;
+}
+
+// the restricted kernel restates the exact-f32 projection; the bf16 and the triage projections round differently, and their
+// scores are gathered from the matrix those kernels write
+static bool cluster_rank_restricted(const sbr_handle* h) {
+    return h->sw.cluster_rank && !(h->lay.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
+}
+
+// cs [rows][lmax]: the scores of the members of every row's cluster csel[row], restricted (scored from h_last; o_grp: launch_crk_group's
+// words in the scratch) or gathered from the full scores
+static int cluster_scores(sbr_cluster* c, sbr_handle* h, char* S, size_t o_grp, const int* csel, int rows, int lmax, float* cs, bool restricted) {
+    const Layout& y = h->lay;
+    const int C = c->cfg.n_clusters;
+    if (restricted) {
+        SBR_LAUNCH(launch_crk_group(h->stream, csel, rows, C, (int*)(S + o_grp)));
+        SBR_LAUNCH(launch_crk_score(h->stream, h_last(h), y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, c->mem_ids, c->mem_off,
+                                    (const int*)(S + o_grp), rows, C, lmax, cs));
+    } else
+        SBR_LAUNCH(launch_crk_gather(h->stream, h->A(y.a_logits), y.N, csel, c->mem_ids, c->mem_off, rows, lmax, cs));
+    h->last_cluster_rank_form = restricted ? 1 : 2;
+    return SBR_OK;
+}
+
+// Ranking inside each row's item cluster (RNNCluster.predict_function for a whole batch, rnn_cluster.py:302-325; kernels and the
+// accumulation-order argument: sbr_cluster_rank.hip).  The member lists are the cluster object's, everything a call needs beyond
+// them sits in the handle's ranking scratch.
+extern "C" int sbr_cluster_rank(sbr_cluster* c, sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
+                                int32_t* ids_host, float* scores_host, int32_t* cluster_host, int32_t* size_host) {
+    CHECK_ARG(c && h && ids_host, "null argument");
+    if (!h->have_batch) { sbr_set_error("sbr_cluster_rank: no batch set"); return SBR_ESTATE; }
+    const Layout& y = h->lay;
+    const int rows = h->n_rows, C = c->cfg.n_clusters;
+    int rc;
+    if ((rc = cluster_fits_engine(c, h)) != SBR_OK) return rc;
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    ExclLists x;
+    if ((rc = excl_check(excl_ids, excl_off, rows, y.N, x)) != SBR_OK) return rc;
+    if ((rc = sbr_cluster_build_lists(c)) != SBR_OK) return rc;      // (cached until R changes: sizes and Lmax are host values)
+    const int lmax = c->lmax, kk = std::min(k, lmax);
+    const size_t rk = (size_t)rows * k, rkk = (size_t)rows * kk;
+    Carver cv;
+    excl_carve(cv, x);
+    const size_t o_csel = cv.take((size_t)rows * sizeof(int)), o_grp = cv.take(sbr_crk_group_words(rows, C) * sizeof(int));
+    const size_t o_cs = cv.take((size_t)rows * lmax * sizeof(float));
+    const RankWork w = carve_rank_work(cv, rows, kk, kk > kRankSortLds);      // the cluster matrix is ranked to kk places
+    const size_t o_pos = cv.take(rkk * sizeof(int)), o_psc = cv.take(rkk * sizeof(float));
+    const size_t o_oid = cv.take(rk * sizeof(int)), o_osc = cv.take(rk * sizeof(float)), o_size = cv.take((size_t)rows * sizeof(int));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    int* csel = (int*)(S + o_csel);
+    float* cs = (float*)(S + o_cs);
+    const bool restricted = cluster_rank_restricted(h);
+    if ((rc = restricted ? forward_current(h) : full_scores(h, 0)) != SBR_OK) return rc;
+    if ((rc = excl_upload(h, S, x)) != SBR_OK) return rc;
+    if ((rc = sbr_cluster_select(c, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, rows, csel, nullptr)) != SBR_OK) return rc;
+    if ((rc = cluster_scores(c, h, S, o_grp, csel, rows, lmax, cs, restricted)) != SBR_OK) return rc;
+    SBR_LAUNCH(launch_crk_exclude(h->stream, cs, lmax, csel, c->mem_ids, c->mem_off, rows, y.N, x.dev_ids(S), x.dev_off(S),
+                                  exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
+    if ((rc = rank_rows(h, S, w, cs, rows, lmax, kk, (int*)(S + o_pos), (float*)(S + o_psc))) != SBR_OK) return rc;
+    SBR_LAUNCH(launch_crk_translate(h->stream, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
+                                    (int*)(S + o_oid), (float*)(S + o_osc), (int*)(S + o_size)));
+    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    if (cluster_host) SBR_HIP(hipMemcpyAsync(cluster_host, csel, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (size_host) SBR_HIP(hipMemcpyAsync(size_host, S + o_size, (size_t)rows * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return check_fault(h);          // a forward that gave up must not hand out rankings
+}
+
+// Whole users of a cluster model evaluated on the device (include/sbr_rnn.h: sbr_cluster_evaluate; kernels: sbr_cluster_eval.hip and
+// the ones sbr_evaluate and sbr_cluster_rank launch).  Per chunk of local_batch users: pack -> forward (+ projection where a full score
+// row is read) -> cluster selection -> the cluster ranking's score matrix, taken BEFORE any exclusion touches the full scores ->
+// [the whole-catalogue ranking, as sbr_evaluate runs it] -> exclusion, select, sort[, translate], hits of the cluster ranking.  All on
+// the main stream; results land at the chunk's offset of arrays sized for the whole call and the host waits once, in check_fault.
+extern "C" int sbr_cluster_evaluate(sbr_cluster* c, sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, int road,
+                                    int exclude_mode, const sbr_eval_out* whole, const sbr_eval_out* inside, int32_t* cluster_host,
+                                    int32_t* size_host, int32_t* cluster_use_host) {
+    CHECK_ARG(c && h && d && users && inside && cluster_host, "null argument");
+    CHECK_ARG(eval_out_ok(inside) && (!whole || eval_out_ok(whole)), "n_pred, hits and first_hit of a given sbr_eval_out are required");
+    CHECK_ARG(road == SBR_CEVAL_LISTS || road == SBR_CEVAL_PRODUCT, "unknown road %d", road);
+    const bool product = road == SBR_CEVAL_PRODUCT;
+    if (product) {
+        CHECK_ARG(exclude_mode == SBR_EVAL_EXCL_NONE || exclude_mode == SBR_EVAL_EXCL_WINDOW,
+                  "the PRODUCT road takes SBR_EVAL_EXCL_NONE or SBR_EVAL_EXCL_WINDOW, not mode %d", exclude_mode);
+        CHECK_ARG(!size_host, "size_host is the LISTS road's: the PRODUCT road ranks the whole catalogue");
+    } else
+        CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW,
+                  "the LISTS road takes SBR_EVAL_EXCL_NONE, _VIEWED or _WINDOW, not mode %d", exclude_mode);
+    const Layout& y = h->lay;
+    const int C = c->cfg.n_clusters;
+    SbrEvalView v;
+    int rc;
+    if ((rc = cluster_fits_engine(c, h)) != SBR_OK) return rc;
+    if ((rc = eval_check_args(h, d, users, n, k, v)) != SBR_OK) return rc;
+    // once per call, before the chunk loop: the member lists (host sizes, Lmax) or the membership matrix of the current R
+    if ((rc = product ? sbr_cluster_build_hard(c, 1) : sbr_cluster_build_lists(c)) != SBR_OK) return rc;
+    const int B = y.B, N = y.N;
+    const int lmax = product ? 0 : c->lmax, kk = product ? k : std::min(k, lmax);      // kk: the depth ranked in the cluster matrix
+    // the restricted kernel applies to the LISTS road only; every other case reads full score rows
+    const bool restricted = !product && cluster_rank_restricted(h);
+    const bool full = whole || !restricted;
+    // the whole-catalogue ranking scores the items fed 0.0 where the compiled test function of a margin model does (_exclude_mode)
+    const int whole_mode = (product && exclude_mode == SBR_EVAL_EXCL_WINDOW && SBR_LOSS_IS_MARGIN(y.cfg.loss)) ? SBR_EVAL_EXCL_WINDOW_ZERO : exclude_mode;
+    Carver cv;
+    const size_t o_users = cv.take((size_t)n * sizeof(int)), o_csel = cv.take((size_t)n * sizeof(int)), o_size = cv.take((size_t)n * sizeof(int));
+    const size_t o_use = cv.take((size_t)C * sizeof(int));
+    const EvalRecords rw = carve_records(cv, whole, n, k, N, B), ri = carve_records(cv, inside, n, k, N, B);
+    const size_t o_grp = cv.take(restricted ? sbr_crk_group_words(B, C) * sizeof(int) : 0);
+    const size_t o_cs = cv.take((size_t)B * (product ? N : lmax) * sizeof(float));
+    const RankWork w = carve_rank_work(cv, B, k, k > kRankSortLds);      // one working set for both rankings (kk <= k: sized for the deeper one)
+    const size_t o_osc = cv.take((size_t)B * k * sizeof(float));
+    const size_t o_pos = cv.take(product ? 0 : (size_t)B * kk * sizeof(int)), o_psc = cv.take(product ? 0 : (size_t)B * kk * sizeof(float));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    int* dcsel = (int*)(S + o_csel);
+    float *cs = (float*)(S + o_cs), *osc = (float*)(S + o_osc);
+    // (pageable host memory: the copy has left the caller's array when it returns)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if ((rc = clear_records(h, S, rw)) != SBR_OK || (rc = clear_records(h, S, ri)) != SBR_OK) return rc;
+    if (cluster_use_host) SBR_HIP(hipMemsetAsync(S + o_use, 0, (size_t)C * sizeof(int), s));
+    for (int64_t c0 = 0; c0 < n; c0 += B) {
+        const int rows = (int)std::min<int64_t>(B, n - c0);
+        const int* cu = dusers + c0;
+        int* csel = dcsel + c0;
+        if ((rc = eval_pack_chunk(h, v, cu, rows)) != SBR_OK) return rc;
+        // (full: the very floats sbr_rank ranks)
+        if ((rc = full ? full_scores(h, 0) : forward_current(h)) != SBR_OK) return rc;
+        float* lg = h->A(y.a_logits);
+        if ((rc = sbr_cluster_select(c, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, rows, csel, nullptr)) != SBR_OK) return rc;
+        // --- the cluster ranking's scores, while the full scores are as the projection left them
+        if (product)
+            SBR_LAUNCH(launch_cev_product(s, v, cu, rows, y.T, N, C, exclude_mode == SBR_EVAL_EXCL_WINDOW, lg, csel, c->hardT, cs));
+        else if ((rc = cluster_scores(c, h, S, o_grp, csel, rows, lmax, cs, restricted)) != SBR_OK) return rc;
+        // --- the whole-catalogue ranking of the same forward pass: sbr_evaluate's chunk
+        if (whole) {
+            int* oid = rw.ids_at(S, c0);
+            SBR_LAUNCH(launch_ev_exclude(s, v, cu, rows, y.T, N, whole_mode, lg));
+            if ((rc = rank_rows(h, S, w, lg, rows, N, k, oid, osc)) != SBR_OK) return rc;
+            if ((rc = launch_hits(h, S, rw, v, dusers, c0, rows, oid)) != SBR_OK) return rc;
+        }
+        // --- the cluster ranking
+        int* oid = ri.ids_at(S, c0);
+        if (product) {
+            if ((rc = rank_rows(h, S, w, cs, rows, N, k, oid, osc)) != SBR_OK) return rc;
+        } else {
+            SBR_LAUNCH(launch_cev_exclude(s, v, cu, rows, y.T, N, exclude_mode, cs, lmax, csel, C, c->mem_ids, c->mem_off));
+            if ((rc = rank_rows(h, S, w, cs, rows, lmax, kk, (int*)(S + o_pos), (float*)(S + o_psc))) != SBR_OK) return rc;
+            SBR_LAUNCH(launch_crk_translate(s, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
+                                            oid, osc, (int*)(S + o_size) + c0));
+        }
+        if ((rc = launch_hits(h, S, ri, v, dusers, c0, rows, oid)) != SBR_OK) return rc;
+    }
+    if (cluster_use_host) SBR_LAUNCH(launch_cev_use(s, dcsel, (long long)n, C, (int*)(S + o_use)));
+    if (whole && (rc = fetch_records(h, S, rw)) != SBR_OK) return rc;
+    if ((rc = fetch_records(h, S, ri)) != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(cluster_host, dcsel, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (size_host) SBR_HIP(hipMemcpyAsync(size_host, S + o_size, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (cluster_use_host) SBR_HIP(hipMemcpyAsync(cluster_use_host, S + o_use, (size_t)C * sizeof(int), hipMemcpyDeviceToHost, s));
+    return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
+}

@@ -52,6 +52,11 @@ class SbrEvalOut(ctypes.Structure):
     _fields_ = [("ids", ctypes.c_void_p), ("n_pred", ctypes.c_void_p), ("hits", ctypes.c_void_p), ("first_hit", ctypes.c_void_p),
                 ("hitmask", ctypes.c_void_p), ("item_hits", ctypes.c_void_p)]
 
+    @classmethod
+    def of(cls, rec):
+        """over the arrays of an _eval_record dict (which must outlive the call)"""
+        return cls(*[_ptr(rec[name]) for name, _ in cls._fields_])
+
 
 class SbrConfig(ctypes.Structure):
     _fields_ = [("abi_version", ctypes.c_int32), ("cell", ctypes.c_int32), ("n_layers", ctypes.c_int32),
@@ -180,6 +185,49 @@ def load_library(path=None):
 
 class SbrError(RuntimeError):
     pass
+
+
+def _ptr(a):
+    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def _check_k(k, n_items):
+    k = int(k)
+    if not 1 <= k <= n_items:       # (the library checks it too: here before the result arrays are sized by k)
+        raise ValueError("k=%d outside [1,N=%d]" % (k, n_items))
+    return k
+
+
+def _excl_csr(exclude, n):
+    """rank()'s per-row `exclude` lists as the CSR sbr_rank takes: (int32 ids, int64 offsets), or (None, None)"""
+    if exclude is None:
+        return None, None
+    lists = [np.zeros(0, dtype=np.int32) if e is None else np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
+    if len(lists) != n:
+        raise ValueError("exclude must hold one id list per row: %d lists for %d rows" % (len(lists), n))
+    off_arr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum([len(e) for e in lists], out=off_arr[1:])
+    ids_arr = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]))   # (never empty: its pointer is not NULL)
+    return ids_arr, off_arr
+
+
+def _csr_args(excl_ids, excl_off, rows):
+    """rank_csr()'s lists in the C-ABI's types"""
+    if excl_ids is not None:
+        excl_ids = np.ascontiguousarray(np.asarray(excl_ids, dtype=np.int32))
+    if excl_off is not None:
+        excl_off = np.ascontiguousarray(np.asarray(excl_off, dtype=np.int64))
+        if excl_off.shape != (rows + 1,):
+            raise ValueError("excl_off must have %d entries (rows + 1), got %r" % (rows + 1, excl_off.shape))
+    return excl_ids, excl_off
+
+
+def _eval_record(n, k, n_items, want_mask, want_ids):
+    """the host arrays of one ranking's per-user results (RNNEngine.evaluate's return value)"""
+    return {"n_pred": np.empty(n, np.int32), "hits": np.empty(n, np.int32), "first_hit": np.empty(n, np.int32),
+            "item_hits": np.empty(n_items, np.int32),
+            "hitmask": np.empty((n, (k + 31) // 32), np.uint32) if want_mask else None,
+            "ids": np.empty((n, k), np.int32) if want_ids else None}
 
 
 def mask_to_lengths(mask):
@@ -591,8 +639,7 @@ class RNNEngine(object):
                 raise ValueError("target must have %d entries, got %d" % (need, tgt.shape[0]))
         if self.loss in SAMPLED_LOSSES and smp is not None and smp.shape[0] != self.n_samples:
             raise ValueError("samples must have %d entries" % self.n_samples)
-        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-        self._check(self.lib.sbr_set_batch(self.h, p(X), p(lengths), p(tgt), p(smp), p(pop), n_rows, 0))
+        self._check(self.lib.sbr_set_batch(self.h, _ptr(X), _ptr(lengths), _ptr(tgt), _ptr(smp), _ptr(pop), n_rows, 0))
         return n_rows
 
     def set_default_target(self, default_target=None):
@@ -704,33 +751,18 @@ class RNNEngine(object):
         exclude_input: also the items of the row's input window, as test_function(exclude_seen=True) does."""
         self._rank_local_flush("rank")
         n = self.set_batch(X, mask)
-        ids_arr = off_arr = None
-        if exclude is not None:
-            lists = [np.zeros(0, dtype=np.int32) if e is None else np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
-            if len(lists) != n:
-                raise ValueError("exclude must hold one id list per row: %d lists for %d rows" % (len(lists), n))
-            off_arr = np.zeros(n + 1, dtype=np.int64)
-            np.cumsum([len(e) for e in lists], out=off_arr[1:])
-            ids_arr = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]))   # (never empty: its pointer is not NULL)
+        ids_arr, off_arr = _excl_csr(exclude, n)
         return self.rank_csr(n, k, ids_arr, off_arr, exclude_input=exclude_input, return_scores=return_scores)
 
     def rank_csr(self, rows, k, excl_ids=None, excl_off=None, exclude_input=True, return_scores=False):
         """sbr_rank on the batch already set (`rows` rows); the lists as the C-ABI takes them: int32 ids and int64 offsets
         (rows + 1 of them), or None for both."""
         self._rank_local_flush("rank")
-        k = int(k)
-        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
-            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
+        k = _check_k(k, self.n_items)
         ids = np.empty((rows, k), dtype=np.int32)
         scores = np.empty((rows, k), dtype=np.float32) if return_scores else None
-        if excl_ids is not None:
-            excl_ids = np.ascontiguousarray(np.asarray(excl_ids, dtype=np.int32))
-        if excl_off is not None:
-            excl_off = np.ascontiguousarray(np.asarray(excl_off, dtype=np.int64))
-            if excl_off.shape != (rows + 1,):
-                raise ValueError("excl_off must have %d entries (rows + 1), got %r" % (rows + 1, excl_off.shape))
-        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-        self._check(self.lib.sbr_rank(self.h, k, int(bool(exclude_input)), p(excl_ids), p(excl_off), p(ids), p(scores)))
+        excl_ids, excl_off = _csr_args(excl_ids, excl_off, rows)
+        self._check(self.lib.sbr_rank(self.h, k, int(bool(exclude_input)), _ptr(excl_ids), _ptr(excl_off), _ptr(ids), _ptr(scores)))
         return (ids, scores) if return_scores else ids
 
     def evaluate(self, dataset, users, k, exclude_mode, want_ids=False, want_mask=True):
@@ -742,19 +774,13 @@ class RNNEngine(object):
         "ids" ((n, k), exactly rank()'s, -1 in the unfilled places; None without want_ids)."""
         self._rank_local_flush("evaluate")
         users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
-        n, k = len(users), int(k)
-        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
-            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
-        out = {"n_pred": np.empty(n, np.int32), "hits": np.empty(n, np.int32), "first_hit": np.empty(n, np.int32),
-               "item_hits": np.empty(self.n_items, np.int32),
-               "hitmask": np.empty((n, (k + 31) // 32), np.uint32) if want_mask else None,
-               "ids": np.empty((n, k), np.int32) if want_ids else None}
-        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        n, k = len(users), _check_k(k, self.n_items)
+        out = _eval_record(n, k, self.n_items, want_mask, want_ids)
         self.evaluate_calls += 1
         with self.torch.cuda.device(self.device):
-            self._check(self.lib.sbr_evaluate(self.h, dataset.d, ctypes.c_void_p(users.ctypes.data) if n else None, n, k, int(exclude_mode),
-                                              p(out["ids"]), p(out["n_pred"]), p(out["hits"]), p(out["first_hit"]), p(out["hitmask"]),
-                                              p(out["item_hits"])))
+            rec = SbrEvalOut.of(out)
+            self._check(self.lib.sbr_evaluate(self.h, dataset.d, _ptr(users) if n else None, n, k, int(exclude_mode),
+                                              rec.ids, rec.n_pred, rec.hits, rec.first_hit, rec.hitmask, rec.item_hits))
         return out
 
     # ---------------------------------------------------------------- debug / timing
@@ -1048,35 +1074,20 @@ class ClusterHead(object):
         eng = self.engine
         eng._rank_local_flush("rank")
         n = eng.set_batch(X, mask)
-        ids_arr = off_arr = None
-        if exclude is not None:
-            lists = [np.zeros(0, dtype=np.int32) if e is None else np.asarray(e, dtype=np.int32).reshape(-1) for e in exclude]
-            if len(lists) != n:
-                raise ValueError("exclude must hold one id list per row: %d lists for %d rows" % (len(lists), n))
-            off_arr = np.zeros(n + 1, dtype=np.int64)
-            np.cumsum([len(e) for e in lists], out=off_arr[1:])
-            ids_arr = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]))   # (never empty: its pointer is not NULL)
+        ids_arr, off_arr = _excl_csr(exclude, n)
         return self.rank_csr(n, k, ids_arr, off_arr, exclude_input=exclude_input, return_scores=return_scores)
 
     def rank_csr(self, rows, k, excl_ids=None, excl_off=None, exclude_input=True, return_scores=False):
         """sbr_cluster_rank on the batch already set on the engine (`rows` rows); the lists as the C-ABI takes them"""
         self.engine._rank_local_flush("rank")
-        k = int(k)
-        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
-            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
+        k = _check_k(k, self.n_items)
         ids = np.empty((rows, k), dtype=np.int32)
         scores = np.empty((rows, k), dtype=np.float32) if return_scores else None
         clusters, sizes = np.empty(rows, dtype=np.int32), np.empty(rows, dtype=np.int32)
-        if excl_ids is not None:
-            excl_ids = np.ascontiguousarray(np.asarray(excl_ids, dtype=np.int32))
-        if excl_off is not None:
-            excl_off = np.ascontiguousarray(np.asarray(excl_off, dtype=np.int64))
-            if excl_off.shape != (rows + 1,):
-                raise ValueError("excl_off must have %d entries (rows + 1), got %r" % (rows + 1, excl_off.shape))
-        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        excl_ids, excl_off = _csr_args(excl_ids, excl_off, rows)
         # (the engine's mapping of the status: SBR_EINVAL is a ValueError, as RNNEngine.rank raises it)
-        self.engine._check(self.lib.sbr_cluster_rank(self.h, self.engine.h, k, int(bool(exclude_input)), p(excl_ids), p(excl_off), p(ids),
-                                                     p(scores), p(clusters), p(sizes)))
+        self.engine._check(self.lib.sbr_cluster_rank(self.h, self.engine.h, k, int(bool(exclude_input)), _ptr(excl_ids), _ptr(excl_off),
+                                                     _ptr(ids), _ptr(scores), _ptr(clusters), _ptr(sizes)))
         return (ids, scores, clusters, sizes) if return_scores else (ids, clusters, sizes)
 
     def evaluate(self, dataset, users, k, road, exclude_mode, want_ids=False, want_mask=True, want_whole=False):
@@ -1090,25 +1101,15 @@ class ClusterHead(object):
         eng = self.engine
         eng._rank_local_flush("evaluate")
         users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
-        n, k = len(users), int(k)
-        if not 1 <= k <= self.n_items:       # (the library checks it too: here before the result arrays are sized by k)
-            raise ValueError("k=%d outside [1,N=%d]" % (k, self.n_items))
-        p = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
-
-        def record():
-            rec = {"n_pred": np.empty(n, np.int32), "hits": np.empty(n, np.int32), "first_hit": np.empty(n, np.int32),
-                   "item_hits": np.empty(self.n_items, np.int32),
-                   "hitmask": np.empty((n, (k + 31) // 32), np.uint32) if want_mask else None,
-                   "ids": np.empty((n, k), np.int32) if want_ids else None}
-            return rec, SbrEvalOut(p(rec["ids"]), p(rec["n_pred"]), p(rec["hits"]), p(rec["first_hit"]), p(rec["hitmask"]), p(rec["item_hits"]))
-        inside, c_inside = record()
-        whole, c_whole = record() if want_whole else (None, None)
+        n, k = len(users), _check_k(k, self.n_items)
+        inside = _eval_record(n, k, self.n_items, want_mask, want_ids)
+        whole = _eval_record(n, k, self.n_items, want_mask, want_ids) if want_whole else None
         out = {"inside": inside, "whole": whole, "cluster": np.empty(n, np.int32),
                "size": np.empty(n, np.int32) if int(road) == CEVAL_LISTS else None, "cluster_use": np.empty(self.n_clusters, np.int32)}
         self.evaluate_calls += 1
         with self.torch.cuda.device(eng.device):
             # (the engine's mapping of the status: SBR_EINVAL is a ValueError, as RNNEngine.evaluate raises it)
-            eng._check(self.lib.sbr_cluster_evaluate(self.h, eng.h, dataset.d, ctypes.c_void_p(users.ctypes.data) if n else None, n, k, int(road),
-                                                     int(exclude_mode), ctypes.byref(c_whole) if want_whole else None, ctypes.byref(c_inside),
-                                                     p(out["cluster"]), p(out["size"]), p(out["cluster_use"])))
+            eng._check(self.lib.sbr_cluster_evaluate(self.h, eng.h, dataset.d, _ptr(users) if n else None, n, k, int(road), int(exclude_mode),
+                                                     ctypes.byref(SbrEvalOut.of(whole)) if want_whole else None, ctypes.byref(SbrEvalOut.of(inside)),
+                                                     _ptr(out["cluster"]), _ptr(out["size"]), _ptr(out["cluster_use"])))
         return out

@@ -219,6 +219,15 @@ class RNNBase(object):
         interactions are unique -- also the part that no longer fits the window -- plus the row's own exclude list; any
         1 <= k <= n_items.  Returns a list of id lists, best first; a row with fewer than k rankable items returns only
         those (top_k_recommendations would go on with excluded ids, in no defined order)."""
+        out = []
+        for X, mask, lists in self._rank_chunks(sequences, user_ids, exclude):
+            ids = self._rd().rank(X, mask, k, exclude=lists, exclude_input=False)
+            out.extend([int(j) for j in row[row >= 0]] for row in ids)
+        return out
+
+    def _rank_chunks(self, sequences, user_ids, exclude):
+        """top_k_batch's engine calls: (X, mask, lists) per batch_size sequences; lists: per row the ids never to rank, which carry
+        every viewed item already -- the engine need not derive them from its input window again (exclude_input=False)"""
         n = len(sequences)
         if user_ids is None:
             user_ids = [None] * n
@@ -226,7 +235,6 @@ class RNNBase(object):
             exclude = [None] * n
         if len(user_ids) != n or len(exclude) != n:
             raise ValueError("user_ids and exclude must have one entry per sequence")
-        out = []
         for lo in range(0, n, self.batch_size):
             hi = min(n, lo + self.batch_size)
             X = np.zeros((hi - lo, self.max_length, self._input_size()), dtype=np.int32)
@@ -241,10 +249,7 @@ class RNNBase(object):
                 if exclude[i] is not None:
                     ex = ex + [int(e) for e in exclude[i]]
                 lists.append(np.asarray(ex, dtype=np.int32))
-            # the lists carry every viewed item already: the engine need not derive them from its input window again
-            ids = self._rd().rank(X, mask, k, exclude=lists, exclude_input=False)
-            out.extend([int(j) for j in row[row >= 0]] for row in ids)
-        return out
+            yield X, mask, lists
 
     # ------------------------------------------------------------------ training loop (rnn_base.py:215-356)
     def get_pareto_front(self, metrics, metrics_names):
@@ -934,32 +939,11 @@ class RNNCluster(RNNBase):
         is excluded, plus the row's own list; any 1 <= k <= n_items.  A row with fewer than k rankable members returns only those
         (the host road goes on with excluded ids, in numpy's partition order).  --ignore_clusters: the whole catalogue, as
         RNNBase.top_k_batch ranks it, with n_scored = n_items."""
-        n = len(sequences)
         if not self.predict_with_clusters:
             ranked = super(RNNCluster, self).top_k_batch(sequences, user_ids=user_ids, k=k, exclude=exclude)
             return [(ids, self.n_items) for ids in ranked]
-        if user_ids is None:
-            user_ids = [None] * n
-        if exclude is None:
-            exclude = [None] * n
-        if len(user_ids) != n or len(exclude) != n:
-            raise ValueError("user_ids and exclude must have one entry per sequence")
         out = []
-        for lo in range(0, n, self.batch_size):
-            hi = min(n, lo + self.batch_size)
-            X = np.zeros((hi - lo, self.max_length, self._input_size()), dtype=np.int32)
-            mask = np.zeros((hi - lo, self.max_length), dtype=np.float32)
-            lists = []
-            for i in range(lo, hi):
-                seq = sequences[i][-min(self.max_length, len(sequences[i])):]
-                if len(seq):
-                    X[i - lo, :len(seq), :] = np.array([self._get_features(x, user_ids[i]) for x in seq], dtype=np.int32)
-                mask[i - lo, :len(seq)] = 1
-                ex = [x[0] for x in sequences[i]] if self.interactions_are_unique else []
-                if exclude[i] is not None:
-                    ex = ex + [int(e) for e in exclude[i]]
-                lists.append(np.asarray(ex, dtype=np.int32))
-            # the lists carry every viewed item already: the engine need not derive them from its input window again
+        for X, mask, lists in self._rank_chunks(sequences, user_ids, exclude):
             ids, _, sizes = self.head.rank(X, mask, k, exclude=lists, exclude_input=False)
             out.extend(([int(j) for j in row[row >= 0]], int(m)) for row, m in zip(ids, sizes))
         return out

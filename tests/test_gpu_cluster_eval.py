@@ -100,29 +100,29 @@ def spread_selection(eng, head, R, X, mask, n_clusters, rng, chunk):
 
 class Case(object):
     def __init__(self, cell="GRU", layers=(16,), loss="TOP1", S=8, cluster_type="mix", R="planted", seed=0, bi=False, F=1, n_opt=0, flags=0,
-                 batch=B, n_clusters=C, lengths=LENGTHS, users=USERS, ratings=None, updater="adam", edit=None):
+                 batch=B, n_clusters=C, lengths=LENGTHS, users=USERS, ratings=None, updater="adam", edit=None, n_items=N):
         from sbr_amd.engine import ClusterHead, DeviceDataset
         self.B, self.C, self.F, self.ratings, self.users = batch, n_clusters, F, ratings, np.asarray(users, dtype=np.int32)
-        params, cfg, self.batch = PU.build_case(cell, list(layers), loss, N, batch, T, S=S, seed=seed, F=F, n_opt=n_opt, bi=bi,
+        params, cfg, self.batch = PU.build_case(cell, list(layers), loss, n_items, batch, T, S=S, seed=seed, F=F, n_opt=n_opt, bi=bi,
                                                 clusters=dict(n=n_clusters))
         if edit is not None:
             edit(params)
-        self.eng = PU.engine_for(cfg, N, batch, T, S=S, F=F, n_opt=n_opt, flags=flags, updater=updater)
+        self.eng = PU.engine_for(cfg, n_items, batch, T, S=S, F=F, n_opt=n_opt, flags=flags, updater=updater)
         from sbr_amd.engine import SAMPLED_LOSSES                    # (the head's own loss is a sampled one whatever the engine trains with)
         self.head = ClusterHead(self.eng, n_clusters, cluster_type, loss=loss if loss in SAMPLED_LOSSES else "SCCE", max_samples=max(S, 1),
                                 updater=updater)
         self.eng.set_all_param_values(params[:-2])
         self.head.set_params(params[-2], params[-1])
-        self.seqs, items, offsets = make_sequences(lengths)
-        self.ds = DeviceDataset(self.eng, items, offsets, N)
+        self.seqs, items, offsets = make_sequences(lengths, n_items=n_items)
+        self.ds = DeviceDataset(self.eng, items, offsets, n_items)
         if ratings is not None:
             self.ds.set_options(np.concatenate(ratings), False)
         rng = np.random.default_rng(100 + seed)
         if isinstance(R, str) and R == "planted":
-            R = plant_R(rng, N, n_clusters, empty=EMPTY if n_clusters > EMPTY else None)
+            R = plant_R(rng, n_items, n_clusters, empty=EMPTY if n_clusters > EMPTY else None)
         elif isinstance(R, str):                 # "fractional": 100 R of order 1, memberships strictly between 0 and 1
-            R = rng.normal(0, 0.012, size=(N, n_clusters)).astype(np.float32)
-        self.X, self.mask, self.viewed, self.goals = host_rows(self.seqs, self.users, F=F, ratings=ratings)
+            R = rng.normal(0, 0.012, size=(n_items, n_clusters)).astype(np.float32)
+        self.X, self.mask, self.viewed, self.goals = host_rows(self.seqs, self.users, F=F, ratings=ratings, n_items=n_items)
         spread_selection(self.eng, self.head, R, self.X, self.mask, n_clusters, rng, batch)
 
     def close(self):
@@ -470,3 +470,52 @@ def test_bad_arguments_leave_engine_and_head_usable(top1):
         assert np.array_equal(case.head.evaluate(case.ds, USERS, 5, LISTS, VIEWED, want_ids=True)["inside"]["ids"], want)
     finally:
         other_head.close(); other_n.close()
+
+
+# ------------------------------------------------------------------ calls of different shapes on one handle
+def test_calls_of_different_shapes_share_one_scratch():
+    """The four calls carve one scratch allocation of the handle, each in its own layout: rank, evaluate, ClusterHead.rank and both
+    roads of ClusterHead.evaluate follow each other on ONE engine and head, at depths on both sides of the LDS sort's limit (k = N =
+    2100 > 2048: the radix sort's second pair is carved) and with kk = Lmax < k on the LISTS road, three chunks with a partial last
+    one.  Every array of every result is the one the same call returns as the ONLY ranking call of a freshly built engine and head."""
+    n_items, lengths = 2100, [2, 3, 5, 8, 11, 14, 4, 7, 12]
+    make = lambda: Case(layers=(8,), batch=4, n_clusters=3, lengths=lengths, users=np.arange(9), n_items=n_items, seed=11)
+    calls = [
+        lambda c: c.eng.rank(c.X[:4], c.mask[:4], 5, return_scores=True),
+        lambda c: c.eng.evaluate(c.ds, c.users, n_items, VIEWED, want_ids=True, want_mask=True),
+        lambda c: c.head.rank(c.X[:4], c.mask[:4], 3, exclude=c.viewed[:4], return_scores=True),
+        lambda c: c.head.evaluate(c.ds, c.users, 70, PRODUCT, WINDOW, want_ids=True, want_whole=True),
+        lambda c: c.head.evaluate(c.ds, c.users, n_items, LISTS, VIEWED, want_ids=True),
+        lambda c: c.eng.rank(c.X[:4], c.mask[:4], 5, return_scores=True),
+    ]
+
+    def arrays(res, name=""):
+        if isinstance(res, dict):
+            return [a for key in sorted(res) for a in arrays(res[key], name + "/" + key)]
+        if isinstance(res, tuple):
+            return [a for i, r in enumerate(res) for a in arrays(r, "%s/%d" % (name, i))]
+        return [(name, res)]
+
+    def same(a, b, what):
+        a, b = arrays(a), arrays(b)
+        assert [n for n, _ in a] == [n for n, _ in b] and len(a) >= 2, what
+        for (name, x), (_, y) in zip(a, b):
+            assert (x is None and y is None) or (x.dtype == y.dtype and np.array_equal(x, y)), (what, name)
+
+    shared = make()
+    try:
+        got = []
+        for call in calls:
+            got.append(call(shared))
+            assert shared.eng.query("rank_sort") == (2 if len(got) == 2 else 1)                          # radix in scratch only at k = 2100 over the catalogue
+        assert np.all(got[1]["n_pred"] > 2048)
+        assert 0 < got[4]["size"].max() < n_items and np.all(got[4]["inside"]["ids"][:, -1] == -1)      # kk = Lmax < k
+    finally:
+        shared.close()
+    same(got[5], got[0], "rank again")
+    for i, call in enumerate(calls[:5]):
+        fresh = make()
+        try:
+            same(got[i], call(fresh), "call %d" % (i + 1))
+        finally:
+            fresh.close()
