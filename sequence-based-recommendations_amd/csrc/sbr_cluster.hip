@@ -2,7 +2,7 @@
 // :327-352): a second, small model that reads the user representation h (the recurrent stack's final state) and trains ONLY its own
 // two arrays -- the cluster-selection weights Wc (H, C) (a DenseLayer without bias, :239) and the item / cluster repartition
 // R (N, C) (:244) -- with its own call of the update manager (:282-285); nothing of it reaches the recurrent network, whose
-// sampled head and loss stay in the engine (sbr_api.hip, losses SBR_LOSS_BLACKOUT .. SBR_LOSS_LIN).
+// sampled head and loss stay in the engine (sbr_step.hip, losses SBR_LOSS_BLACKOUT .. SBR_LOSS_LIN).
 //
 //   z = h . Wc (+ noise);  p = softmax(scale z)                                          cluster selection        :240-243
 //   M = f(R[targets ++ cluster_samples]),  f = softmax(scale .) | + sigmoid(scale .) | sigmoid(scale .)          :245-253

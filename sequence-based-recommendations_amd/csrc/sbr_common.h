@@ -162,7 +162,7 @@ constexpr int kTailGateSleep = 32;        // ... whose polls of ONE word are thi
 // the boundary between two such steps (profiles/step_boundary_variants.txt): no event on the main stream
 constexpr bool kStepJoinGate = true;      // step end: a one-wave gate on the completion words of the two consumer streams joins them
 constexpr bool kStepForkGate = true;      // step start: the second side stream (and the batch builder) wait for the forward chain's start word
-// growth of the small time chunks near t = 0 (tail_plan, sbr_api.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
+// growth of the small time chunks near t = 0 (tail_plan, sbr_step.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
 // walks them one after the other; 1, 3, 7, 18 for the polling range form
 static inline double sbr_tail_geom(int scatter_lds) { return scatter_lds ? 1.6 : 2.6; }
 // sbr_rank (sbr_rank.hip): where its two pairs of regimes change
@@ -267,13 +267,13 @@ struct sbr_handle {
     bool tail_cost_scanned = false;                                       // this step's sort was followed by launch_scatter_cost_scan
     int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
     std::vector<int> tail_slab_host; int* tail_slab_dev = nullptr; int tail_slab_key[2] = {0, 0};   // the table of the last plan
-    int prog_epoch = 0;          // epoch of the chain's progress words: advanced once per step by tail_next_epoch (sbr_api.hip)
+    int prog_epoch = 0;          // epoch of the chain's progress words: advanced once per step by tail_next_epoch (sbr_step.hip)
     bool tail_gated = false;     // this step: the side stream is already behind a gate on this step's epoch (sbr_loss_backward_output)
     // Words of the step boundary (kStepJoinGate / kStepForkGate): an allocation of its own, made and zeroed on first use and freed by
     // sbr_destroy; each word on a 128-byte line of its own.  [32]: completion word of the side stream, [96]: of the second side
     // stream, [128]: the forward chain's start word.
     int* step_words = nullptr;
-    int join_epoch = 0, fork_epoch = 0;   // epochs of the completion words / the start word: advanced by step_next_epoch (sbr_api.hip), never 0
+    int join_epoch = 0, fork_epoch = 0;   // epochs of the completion words / the start word: advanced by step_next_epoch (sbr_step.hip), never 0
     bool fork_gated = false;              // this step: the second side stream was released by the start word (sbr_forward)
     int last_join_gate = -1, last_fork_gate = -1;                         // what the last step took: sbr_query "step_join_gate" / "step_fork_gate"
     int step_word_epoch = 0;     // != 0: the forward chain of the step in flight publishes this epoch in its start word (sbr_build_batch waits for it
@@ -337,13 +337,33 @@ void sbr_set_error(const char* fmt, ...);
 #define SBR_LAUNCH(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     sbr_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return SBR_EHIP; } } while (0)
 
-// What the ranking and evaluation calls (sbr_rank_api.hip) need of the engine (sbr_api.hip)
+// What the ranking and evaluation calls (sbr_rank_api.hip) need of the engine (sbr_api.hip, sbr_step.hip)
 int flush_lazy(sbr_handle* h, int only_kind = -1);   // every row of every sparse block (of that kind) current through the last applied step
 bool simple_gemm(const sbr_handle* h);               // SBR_FLAG_SIMPLE_GEMM: the triage projection
 float* h_last(sbr_handle* h);                        // the user representation of the current batch, [Bp][HLt]
 int check_fault(sbr_handle* h);                      // synchronises the stream; fails the call if a bounded wait of its kernels gave up
 int full_scores(sbr_handle* h, int do_softmax);      // forward_current + the projection into a_logits: the scores of every item
 int forward_current(sbr_handle* h);                  // (sbr_rank_api.hip) forward pass if the batch has none yet + lazily stepped output rows flushed
+
+// What the rest of the engine (sbr_api.hip: sbr_query, sbr_zero_grads, the sparse exchange, the debug calls) needs of the training
+// step (sbr_step.hip), and the one layout piece the step takes from there
+struct RecArgs; struct SbrSparseRows; struct SbrSparseUpd;
+RecArgs rec_args(sbr_handle* h, int l);              // layer l's kernel arguments for the current batch; advances the cluster kernels' exchange epoch
+bool simple_rec(const sbr_handle* h);                // SBR_FLAG_SIMPLE_REC: the triage recurrent kernels
+int tail_plan(sbr_handle* h, int* ch_out);           // overlapped step tail: time chunks of a step (0: not taken), steps per chunk; fills h->tail_bounds
+bool head_sampled_taken(const sbr_handle* h, int rows);   // does a step over `rows` rows take the one-launch sampled head?
+void mark(sbr_handle* h, int i);                     // timing mark i of the step in flight, on the main stream
+SbrSparseRows sparse_rows(sbr_handle* h, int b);     // row-sparse block b: where its rows, gradients, state and last-step words are
+SbrSparseUpd sparse_upd(sbr_handle* h);              // ... and the optimizer's constants for the row kernels
+int side_join(sbr_handle* h);                        // the main stream joins whatever the step left pending on the side streams
+// adagrad's zero-gradient step is a no-op: nothing is ever pending
+static inline bool sparse_lazy(const sbr_handle* h) { return h->lay.n_sparse > 0 && h->lay.cfg.updater != SBR_UPD_ADAGRAD; }
+// one direction's counting-sort arrays of the batch's ids (dir 0: a_s*, 1: the reversed ids of --r_bi, a_s2*): counters, segment
+// offsets (off[n_ids]: the entry count), cursors, and the sorted entries' ids and positions
+struct SbrSortKeys { int *cnt, *off, *cur, *sid, *pos; };
+SbrSortKeys sort_keys(const sbr_handle* h, int dir);
+// (sbr_api.hip) the float ranges of the parameter section that the row-sparse blocks own, ascending
+std::vector<std::pair<size_t, size_t>> sparse_float_ranges(const Layout& lay);
 
 // Consumers of a RUNNING BPTT chain (overlapped step tail): the chain's waves publish (epoch << 12) | t in words[0 .. n) once
 // all their time steps >= t are complete and written through (RecArgs.progress); ONE workgroup -- the MONITOR: workgroup 0 of

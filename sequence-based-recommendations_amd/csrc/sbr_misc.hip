@@ -1364,7 +1364,7 @@ hipError_t launch_tail_gate_wave(hipStream_t s, const int* progress, int n, int 
     return hipGetLastError();
 }
 
-// Gate of the step boundary (sbr_api.hip: the join of the consumer streams at the end of a single-call step with the overlapped
+// Gate of the step boundary (sbr_step.hip: the join of the consumer streams at the end of a single-call step with the overlapped
 // tail, the release of the second side stream and of the batch builder at its start): one wave, no LDS, returns once w0[0] (and
 // w1[0], where given) hold `epoch`.  The words are stored write-through by kernels that were enqueued BEFORE this one
 // (step_word_kernel behind the last kernel of a consumer stream; the forward chain's entry: RecArgs.start_word), so the wait ends

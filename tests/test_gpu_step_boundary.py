@@ -1,4 +1,4 @@
-"""The boundary between two single-call steps with the overlapped tail carries no event on the main stream (csrc/sbr_api.hip):
+"""The boundary between two single-call steps with the overlapped tail carries no event on the main stream (csrc/sbr_step.hip):
 
   step end    behind the last kernel of either consumer stream (update_kernel behind the scatter-add, update_from_slabs_kernel behind
               the dW_hid GEMM) a one-lane kernel stores a completion word of the step's epoch, and ONE gate on both words

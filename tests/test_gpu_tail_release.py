@@ -1,5 +1,5 @@
 """The side stream of a single-call step with the overlapped tail is released by the BPTT chain's progress words (a one-wave gate
-at its head, launched in the loss phase) instead of a main-stream record (csrc/sbr_api.hip sbr_loss_backward_output, csrc/sbr_misc.hip
+at its head, launched in the loss phase) instead of a main-stream record (csrc/sbr_step.hip sbr_loss_backward_output, csrc/sbr_misc.hip
 tail_gate_wave_kernel), and the second gate in front of the polling GEMM is gone.
 
 What can go wrong: a gate that passes on the words the step BEFORE left (the epoch) lets the output layer's gradient kernels read
