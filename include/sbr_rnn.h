@@ -472,6 +472,35 @@ int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n,
                  int32_t* item_hits_host); /* NULL, or [N]: over all n users, how often item i was a correct prediction */
 
 /* ------------------------------------------------------------------------------------------------
+ * The rank of every goal item on the device (added under ABI 11: one symbol, no struct change) -- what test.py:42-77 with
+ * get_full_recommendation_list and evaluation.py:198-206 (get_rank_comparison) obtain per user from a ranking to depth N, and what
+ * the metrics at ANY depth follow from.  Users are split, fed, chunked (local_batch per chunk) and excluded exactly as by
+ * sbr_evaluate, in all four SBR_EVAL_EXCL_* modes (WINDOW_ZERO leaves the items fed at 0.0 and rankable); users may repeat; the
+ * handle is left as sbr_set_batch leaves it.  For user users[j] and goal place p (sequence order, p < L - L / 2), with g the item there:
+ *   ranks[goal_off[j] + p]   the place of g in sbr_rank's result at k = N for that row: the number of rankable items i with a better
+ *                            score, or an equal score and i < g; -1 when g itself is never ranked (excluded, NaN, -inf, outside
+ *                            the catalogue).  A goal that repeats an item holds the same rank at each of its places.
+ *   n_rankable[j]            the rankable items of the row = sbr_evaluate's n_pred at k = N.
+ * A rank is a count (ev_goal_rank_kernel, sbr_eval.hip): one pass over the score row per 1024 goal items (sbr_query "goal_rank_tile"),
+ * no select, no sort, no k; integer arithmetic only.  sbr_query "goal_rank_form": 1 the row's keys stayed in LDS, 2 every pass streamed
+ * the row (N > 32768), 0 no call yet.  Every chunk is enqueued on the engine's stream without a host wait in between; the call waits
+ * once, at its end.  goal_off is computed on the host from the lengths and written before anything is launched.
+ * SBR_EINVAL, found before anything is launched (the engine stays usable): everything sbr_evaluate rejects (k does not exist here), an
+ * unknown mode, a NULL output, cap < goal_off[n] (sbr_last_error names the count needed).  Parameters, gradients and optimizer state
+ * are the same bits after the call as before it: lazily stepped rows are brought up to date for the call as by sbr_evaluate, and
+ * -- since where the replay of their missed steps is split changes float32 roundings -- put back behind the last chunk, so that
+ * training goes on exactly as if the call had not been made (also when a chunk fails to launch; not when one of these copies itself
+ * fails, SBR_EHIP: the rows are then left up to date, which is valid state).  That copy is (1 + optimizer state arrays) x parameters
+ * floats of ranking scratch and twice that in device traffic per call, only on an engine that steps rows lazily and has trained
+ * (LSTM-256 on 100 000 items with Adam: 1.5 GB, one millisecond per call -- profiles/eval_ranks_bench.json).  Scratch: the handle's ranking scratch (users, n + 1 offsets,
+ * goal_off[n] ranks, n counts; with lazily stepped rows and steps applied, the copy of parameters and optimizer state). */
+int sbr_evaluate_ranks(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int exclude_mode,
+                       int64_t* goal_off_host,     /* [n + 1]: user j's goal places are [goal_off[j], goal_off[j + 1]); goal_off[0] = 0 */
+                       int32_t* ranks_host,        /* [cap] */
+                       int64_t cap,                /* must be >= goal_off[n] = sum over users of L - L / 2 */
+                       int32_t* n_rankable_host);  /* [n] */
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation of whole users of a cluster model on the device (added under ABI 11: one symbol and one struct, nothing existing
  * changes) -- sbr_evaluate for `--clusters C`: RNNCluster._compute_validation_metrics (rnn_cluster.py:409-438, one compiled test
  * function call per user) and test.py:61-76 (one top_k_recommendations call per user).  Users are split, fed, chunked

@@ -945,6 +945,9 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "rank_sort") *value = h->last_rank_sort;
     // the LAST sbr_cluster_rank: 0 none yet, 1 only the members of each row's cluster were scored, 2 they were gathered from the full scores
     else if (w == "cluster_rank_form") *value = h->last_cluster_rank_form;
+    // the LAST sbr_evaluate_ranks: 0 none yet, 1 the row's keys stayed in LDS, 2 every pass streamed the row; and the goal items of a pass
+    else if (w == "goal_rank_form") *value = h->last_goal_rank_form;
+    else if (w == "goal_rank_tile") *value = kGoalRankTile;
     else if (w == "row_aware_update") *value = h->last_row_aware ? 1 : 0;      // ... and whether its optimizer pass over W_in was the row-aware one
     else if (w == "cluster") { RecArgs a = rec_args(h, (y.L - 1) * y.D); *value = (!simple_rec(h) && sbr_rec_cluster_ok(a)) ? 1 : 0; }
     else if (w == "rec_kernel") {   // family serving the top layer: 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <math.h>
 #include <string>
 #include <vector>
 #include "../../include/sbr_rnn.h"
@@ -169,6 +170,18 @@ static inline double sbr_tail_geom(int scatter_lds) { return scatter_lds ? 1.6 :
 constexpr int kRankThreads = 1024;        // threads of a row's workgroup in the select and sort kernels (16 waves: one id segment each)
 constexpr int kRankLdsRow = 32768;        // longest row whose keys stay in LDS during the select (128 KB of the CU's 160 KB; C4's 26 744 fits)
 constexpr int kRankSortLds = 2048;        // largest k the LDS bitonic sort takes (16 KB of 64-bit composites); above: the LSD radix sort in scratch
+constexpr int kGoalRankTile = 1024;       // goal items ev_goal_rank_kernel ranks per pass over the row (sbr_eval.hip): one per thread; 8 KB of composites
+                                          // + 4 KB of counts beside the 128 KB row = 140.1 KB of the CU's 160 KB
+static_assert(kGoalRankTile == kRankThreads, "ev_goal_rank_kernel: a thread owns one goal item of the tile and one word of its scan");
+
+// The order-preserving 32-bit image of a score (sbr_rank.hip's KEY; read by the select kernels there and by ev_goal_rank_kernel):
+// sign-flip transform of the float's bits, -0.0 canonicalised to +0.0, NaN and -inf -> 0 = never ranked.
+__device__ __forceinline__ unsigned rank_key(float v) {
+    if (!(v > -INFINITY)) return 0u;              // NaN, -inf
+    unsigned u = __float_as_uint(v);
+    if (v == 0.0f) u = 0u;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
 
 // Every environment switch the library reads (README.md "Switches"), with its default.  sbr_read_switches (sbr_api.hip) fills one
 // per engine, inside sbr_create, and nothing reads the environment afterwards: an engine keeps the values it was created under.
@@ -261,6 +274,7 @@ struct sbr_handle {
     bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
     // sbr_rank: scratch outside the arena (grown on demand, freed by sbr_destroy) and what the last call ran (sbr_query "rank_select" / "rank_sort")
     void* rank_scratch = nullptr; size_t rank_scratch_bytes = 0; int last_rank_select = 0, last_rank_sort = 0;
+    int last_goal_rank_form = 0;                                          // sbr_evaluate_ranks: 0 none yet, 1 the row's keys in LDS, 2 streamed
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
@@ -717,6 +731,11 @@ hipError_t launch_ev_exclude(hipStream_t s, const SbrEvalView& v, const int* use
 // (NULL: not written), item_hits [N] += 1 per hit (NULL: not counted)
 hipError_t launch_ev_hits(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int k, const int* ids, int* n_pred, int* hits,
                           int* first_hit, unsigned* mask, int* item_hits);
+// rank[r][j] of goal item j of users[r] in the complete ranking of scores[r] (include/sbr_rnn.h: sbr_evaluate_ranks) at
+// ranks[goal_off[r] + j], -1 for an item that is never ranked; n_rankable [rows]; returns the regime in *form (1: the row's keys in LDS,
+// 2: streamed)
+hipError_t launch_ev_goal_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* goal_off, int rows, int N,
+                               const float* scores, int* ranks, int* n_rankable, int* form);
 // sbr_cluster_eval.hip: what sbr_cluster_evaluate needs beyond the kernels above (include/sbr_rnn.h)
 // -inf at the places of the viewed (mode VIEWED) / fed (WINDOW) items of users[r] that the row's cluster holds; cs [rows][lmax]
 hipError_t launch_cev_exclude(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int mode, float* cs, int lmax,

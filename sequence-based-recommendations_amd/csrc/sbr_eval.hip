@@ -4,6 +4,8 @@
 //   1. ev_pack_kernel      the rows fed: the last min(T, half) viewed items of every user of the chunk
 //   2. ev_exclude_kernel   the viewed items out of the score rows
 //   3. ev_hits_kernel      the ordered top-k against the goal: counts, the hit mask, per-item hit counts
+// and, for sbr_evaluate_ranks, in place of select + sort + 3:
+//   4. ev_goal_rank_kernel the place of every goal item in the row's complete ranking, counted and never sorted out
 // A user's sequence of L items is split at half = L / 2 (test.py:81-83): items[0 .. half) viewed, items[half .. L) the goal.
 // Rows are independent in every kernel; nothing waits on another workgroup.
 #include "sbr_common.h"
@@ -92,6 +94,114 @@ __global__ void __launch_bounds__(kHitThreads) ev_hits_kernel(const int* __restr
     if (tid == 0) { n_pred[r] = s_cnt[0]; hits[r] = s_cnt[1]; first_hit[r] = s_cnt[2] > 0 ? 1 : 0; }
 }
 
+// ---- sbr_evaluate_ranks: the place of every goal item in the complete ranking of its row
+// An item's place is a count: the rankable items whose composite key << 32 | ~id is larger than its own (sbr_rank's order: key
+// descending, ties to the lowest id).  One workgroup per row; the goal is taken kGoalRankTile items at a time, and per tile the row
+// is read once: the tile's composites are sorted descending in LDS, every rankable item of the row finds by binary search how many of
+// them are >= its own composite (p) and adds 1 to cnt[p] (integer LDS atomics: the sums do not depend on the order), and after an
+// inclusive scan the goal item whose composite first stands at place q of the sorted tile has scan[q] items in front of it.
+// O((N + tile) log tile) per tile whatever the goals hold; a repeated goal item finds the same q at each of its places.
+constexpr int kGoalWaves = kRankThreads / 64;
+constexpr int kGoalCntWords = kGoalRankTile + 4;                                   // cnt[p], p in [0, tile]; 16-byte multiple
+constexpr int kGoalFixedBytes = kGoalRankTile * 8 + (kGoalCntWords + kGoalWaves + 4) * 4;   // composites, counts, scan partials, n_rankable
+static_assert(kGoalFixedBytes % 16 == 0, "the LDS row starts on a 16-byte boundary");
+static_assert(kGoalFixedBytes + kRankLdsRow * 4 <= 160 * 1024, "the row's keys and a tile's state share the CU's 160 KB");
+
+// LDSROW: the row's keys are computed once into LDS (N <= kRankLdsRow); otherwise every tile streams the row from memory.
+template <bool LDSROW>
+__global__ void __launch_bounds__(kRankThreads) ev_goal_rank_kernel(const int* __restrict__ items, const long long* __restrict__ off,
+                                                                    const int* __restrict__ users, const long long* __restrict__ goal_off,
+                                                                    const float* __restrict__ scores, int N, int* __restrict__ ranks,
+                                                                    int* __restrict__ n_rankable) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned long long* c = (unsigned long long*)smem;             // [kGoalRankTile] the tile's composites, sorted descending
+    unsigned* cnt = (unsigned*)(c + kGoalRankTile);                // [kGoalCntWords] items per p, then its inclusive scan
+    unsigned* ws = cnt + kGoalCntWords;                            // [kGoalWaves]
+    unsigned* nrk = ws + kGoalWaves;                               // [1] rankable items of the row
+    unsigned* lrow = (unsigned*)(smem + kGoalFixedBytes);
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int u = users[r];
+    const long long o = off[u];
+    const int L = (int)(off[u + 1] - o), half = L / 2, ng = L - half;
+    const int* g = items + o + half;                               // the goal in sequence order
+    int* out = ranks + goal_off[r];
+    const float* row = scores + (size_t)r * N;
+    if (tid == 0) nrk[0] = 0;
+    if (LDSROW)
+        for (int i = tid; i < N; i += kRankThreads) lrow[i] = rank_key(row[i]);
+    __syncthreads();
+    auto key_at = [&](int i) -> unsigned { return LDSROW ? lrow[i] : rank_key(row[i]); };
+
+    for (int j0 = 0; j0 < ng; j0 += kGoalRankTile) {               // (ng >= 1: the call takes users of two items or more)
+        const int tn = min(kGoalRankTile, ng - j0);
+        int P = 64;                                                // the sorted length: tn rounded up to a power of two, zero padded
+        while (P < tn) P <<= 1;
+        // --- 1. composites: thread t owns goal item j0 + t; an id outside the catalogue is never ranked
+        unsigned long long mine = 0ull;
+        if (tid < tn) {
+            const int gid = g[j0 + tid];
+            const unsigned key = (unsigned)gid < (unsigned)N ? key_at(gid) : 0u;
+            mine = ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (unsigned)gid);
+        }
+        if (tid < P) c[tid] = mine;
+        cnt[tid] = 0;
+        if (tid < kGoalCntWords - kGoalRankTile) cnt[kGoalRankTile + tid] = 0;
+        __syncthreads();
+        // --- 2. bitonic sort, descending (rank_sort_lds_kernel's network)
+        for (int size = 2; size <= P; size <<= 1)
+            for (int stride = size >> 1; stride > 0; stride >>= 1) {
+                if (tid < P / 2) {
+                    const int i = 2 * tid - (tid & (stride - 1)), j = i + stride;
+                    const unsigned long long a = c[i], b = c[j];
+                    if ((a < b) == ((i & size) == 0)) { c[i] = b; c[j] = a; }
+                }
+                __syncthreads();
+            }
+        // --- 3. one pass over the row: p = #{ composites of the tile >= the item's own }; an item behind the whole tile (p == tn) is
+        // in front of none of its goal items and is not counted.  A thread adds a run of equal p at once.
+        unsigned cur = 0, run = 0, nr = 0;
+        for (int i = tid; i < N; i += kRankThreads) {
+            const unsigned key = key_at(i);
+            if (key == 0u) continue;
+            ++nr;
+            const unsigned long long comp = ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
+            int lo = 0, hi = tn;                                   // first place with c[place] < comp
+            while (lo < hi) { const int mid = (lo + hi) >> 1; if (c[mid] >= comp) lo = mid + 1; else hi = mid; }
+            if (lo == tn) continue;
+            if (run && (unsigned)lo == cur) ++run;
+            else { if (run) atomicAdd(&cnt[cur], run); cur = (unsigned)lo; run = 1; }
+        }
+        if (run) atomicAdd(&cnt[cur], run);
+        if (j0 == 0) {
+#pragma unroll
+            for (int o2 = 32; o2 > 0; o2 >>= 1) nr += __shfl_xor(nr, o2);
+            if (lane == 0) atomicAdd(&nrk[0], nr);
+        }
+        __syncthreads();
+        // --- 4. inclusive scan of cnt[0 .. kGoalRankTile): one word per thread
+        unsigned v = cnt[tid];
+#pragma unroll
+        for (int o2 = 1; o2 < 64; o2 <<= 1) { const unsigned t = __shfl_up(v, o2); if (lane >= o2) v += t; }
+        if (lane == 63) ws[w] = v;
+        __syncthreads();
+        for (int i = 0; i < w; ++i) v += ws[i];
+        cnt[tid] = v;
+        __syncthreads();
+        // --- 5. the first place q of the item's own composite: everything counted at p <= q stands in front of it
+        if (tid < tn) {
+            int rank = -1;
+            if ((unsigned)(mine >> 32) != 0u) {
+                int lo = 0, hi = tn;                               // first place with c[place] <= mine
+                while (lo < hi) { const int mid = (lo + hi) >> 1; if (c[mid] > mine) lo = mid + 1; else hi = mid; }
+                rank = (int)cnt[lo];
+            }
+            out[j0 + tid] = rank;
+        }
+        __syncthreads();                                           // c, cnt and ws are the next tile's
+    }
+    if (tid == 0) n_rankable[r] = (int)nrk[0];
+}
+
 }  // namespace
 
 hipError_t launch_ev_pack(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop) {
@@ -110,5 +220,18 @@ hipError_t launch_ev_hits(hipStream_t s, const SbrEvalView& v, const int* users,
                           int* first_hit, unsigned* mask, int* item_hits) {
     if (rows <= 0) return hipSuccess;
     ev_hits_kernel<<<rows, kHitThreads, 0, s>>>(v.items, v.goal, v.off, users, k, ids, n_pred, hits, first_hit, mask, item_hits);
+    return hipGetLastError();
+}
+
+hipError_t launch_ev_goal_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* goal_off, int rows, int N,
+                               const float* scores, int* ranks, int* n_rankable, int* form) {
+    *form = N <= kRankLdsRow ? 1 : 2;
+    if (rows <= 0) return hipSuccess;
+    if (N <= kRankLdsRow) {
+        const size_t lds = (size_t)kGoalFixedBytes + ((size_t)N * sizeof(unsigned) + 15) / 16 * 16;
+        SBR_DYN_LDS(ev_goal_rank_kernel<true>, lds);
+        ev_goal_rank_kernel<true><<<rows, kRankThreads, lds, s>>>(v.items, v.off, users, goal_off, scores, N, ranks, n_rankable);
+    } else
+        ev_goal_rank_kernel<false><<<rows, kRankThreads, kGoalFixedBytes, s>>>(v.items, v.off, users, goal_off, scores, N, ranks, n_rankable);
     return hipGetLastError();
 }

@@ -23,13 +23,6 @@ constexpr int kSelFixedWords = kBins + 4 * kWaves;   // histogram, scan partials
 static_assert(kBins == 2 * kRankThreads, "the suffix scan of the select gives every thread two bins");
 static_assert((kSelFixedWords * 4) % 16 == 0, "the LDS row starts on a 16-byte boundary");
 
-__device__ __forceinline__ unsigned rank_key(float v) {
-    if (!(v > -INFINITY)) return 0u;              // NaN, -inf
-    unsigned u = __float_as_uint(v);
-    if (v == 0.0f) u = 0u;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // inclusive scan over the workgroup's kRankThreads values (ws: kWaves words of LDS, free again on return)
 __device__ __forceinline__ unsigned block_incl_scan(unsigned v, unsigned* ws) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;

@@ -1,4 +1,5 @@
-// The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_rank, sbr_evaluate, sbr_cluster_rank, sbr_cluster_evaluate.
+// The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_rank, sbr_evaluate, sbr_evaluate_ranks, sbr_cluster_rank,
+// sbr_cluster_evaluate.
 // Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_cluster_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
 // sbr_api.hip), built from the shared pieces below.  Every call waits for the device once, in check_fault.
 #include "sbr_common.h"
@@ -145,6 +146,24 @@ static int eval_pack_chunk(sbr_handle* h, const SbrEvalView& v, const int* duser
     return SBR_OK;
 }
 
+// The chunk loop of the whole-catalogue evaluations: local_batch users at a time are packed, scored (the very floats sbr_rank ranks;
+// lazily stepped rows are flushed) and excluded from the dataset's CSR, then `ranked(c0, rows, scores)` enqueues what the call makes of
+// the chunk's score rows.  Everything on the main stream, no host wait.
+template <class Ranked>
+static int eval_chunks(sbr_handle* h, const SbrEvalView& v, const int* dusers, int64_t n, int exclude_mode, Ranked&& ranked) {
+    const Layout& y = h->lay;
+    int rc;
+    for (int64_t c0 = 0; c0 < n; c0 += y.B) {
+        const int rows = (int)std::min<int64_t>(y.B, n - c0);
+        if ((rc = eval_pack_chunk(h, v, dusers + c0, rows)) != SBR_OK) return rc;
+        if ((rc = full_scores(h, 0)) != SBR_OK) return rc;
+        float* lg = h->A(y.a_logits);
+        SBR_LAUNCH(launch_ev_exclude(h->stream, v, dusers + c0, rows, y.T, y.N, exclude_mode, lg));
+        if ((rc = ranked(c0, rows, lg)) != SBR_OK) return rc;
+    }
+    return SBR_OK;
+}
+
 // One ranking's per-user records of an evaluation call (an sbr_eval_out's device side): sized for all n users of the call, every chunk
 // writes at its offset; `oid` holds the ids of every user only when the caller fetches them, otherwise one chunk's
 struct EvalRecords {
@@ -212,18 +231,73 @@ extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users,
     // (pageable host memory: the copy has left the caller's array when it returns)
     SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     if ((rc = clear_records(h, S, rec)) != SBR_OK) return rc;
-    for (int64_t c0 = 0; c0 < n; c0 += B) {
-        const int rows = (int)std::min<int64_t>(B, n - c0);
-        if ((rc = eval_pack_chunk(h, v, dusers + c0, rows)) != SBR_OK) return rc;
-        if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_rank ranks (and flushes lazily stepped rows)
-        float* lg = h->A(y.a_logits);
-        SBR_LAUNCH(launch_ev_exclude(s, v, dusers + c0, rows, y.T, y.N, exclude_mode, lg));
+    rc = eval_chunks(h, v, dusers, n, exclude_mode, [&](int64_t c0, int rows, float* lg) -> int {
         int* oid = rec.ids_at(S, c0);
-        if ((rc = rank_rows(h, S, w, lg, rows, y.N, k, oid, (float*)(S + o_osc))) != SBR_OK) return rc;
-        if ((rc = launch_hits(h, S, rec, v, dusers, c0, rows, oid)) != SBR_OK) return rc;
-    }
+        int rc2;
+        if ((rc2 = rank_rows(h, S, w, lg, rows, y.N, k, oid, (float*)(S + o_osc))) != SBR_OK) return rc2;
+        return launch_hits(h, S, rec, v, dusers, c0, rows, oid);
+    });
+    if (rc != SBR_OK) return rc;
     if ((rc = fetch_records(h, S, rec)) != SBR_OK) return rc;
     return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
+}
+
+// The place of every goal item in the complete ranking of its user (include/sbr_rnn.h: sbr_evaluate_ranks): sbr_evaluate's chunks with
+// one counting kernel (ev_goal_rank_kernel, sbr_eval.hip) where that call selects, sorts and compares.  The offsets of the users' goal
+// places follow from the lengths alone: they are written for the caller, and uploaded, before anything is launched.
+extern "C" int sbr_evaluate_ranks(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int exclude_mode, int64_t* goal_off_host,
+                                  int32_t* ranks_host, int64_t cap, int32_t* n_rankable_host) {
+    CHECK_ARG(h && d && users && goal_off_host && ranks_host && n_rankable_host, "null argument");
+    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW_ZERO, "unknown exclusion mode %d", exclude_mode);
+    const Layout& y = h->lay;
+    SbrEvalView v;
+    int rc;
+    if ((rc = eval_check_args(h, d, users, n, 1, v)) != SBR_OK) return rc;      // (no k here: 1 is inside every catalogue)
+    int64_t total = 0;
+    for (int64_t j = 0; j < n; ++j) { const int64_t L = v.h_off[users[j] + 1] - v.h_off[users[j]]; total += L - L / 2; }
+    CHECK_ARG(cap >= total, "cap=%lld: the goals of these users hold %lld items", (long long)cap, (long long)total);
+    goal_off_host[0] = 0;
+    for (int64_t j = 0; j < n; ++j) { const int64_t L = v.h_off[users[j] + 1] - v.h_off[users[j]]; goal_off_host[j + 1] = goal_off_host[j] + (L - L / 2); }
+    Carver cv;
+    const size_t o_users = cv.take((size_t)n * sizeof(int)), o_goff = cv.take((size_t)(n + 1) * sizeof(long long));
+    const size_t o_ranks = cv.take((size_t)total * sizeof(int)), o_nrk = cv.take((size_t)n * sizeof(int));
+    // Lazily stepped rows are brought up to date where the call reads them, and WHERE a replay of missed steps is split changes float32
+    // roundings (sbr_sparse.hip): a training run with this call in its middle would differ in the last bit from one without.  So once
+    // steps have been applied, the parameters, the optimizer state and the rows' last-step words are kept and put back behind the last chunk.
+    const bool keep = sparse_lazy(h) && h->step_count > 0;
+    const size_t np_bytes = y.n_params * sizeof(float);
+    const size_t o_kp = cv.take(keep ? np_bytes : 0), o_ks = cv.take(keep ? y.n_state_arrays * np_bytes : 0);
+    size_t o_kl[2] = {0, 0};
+    for (int b = 0; b < y.n_sparse; ++b) o_kl[b] = cv.take(keep ? (size_t)y.sparse[b].n_rows * sizeof(int) : 0);
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    const long long* dgoff = (const long long*)(S + o_goff);
+    static_assert(sizeof(long long) == sizeof(int64_t), "the offsets are uploaded as they are");
+    // (pageable host memory: the copies have left the caller's arrays when they return)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    SBR_HIP(hipMemcpyAsync(S + o_goff, goal_off_host, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    if (keep) {
+        SBR_HIP(hipMemcpyAsync(S + o_kp, h->P(0), np_bytes, hipMemcpyDeviceToDevice, s));
+        SBR_HIP(hipMemcpyAsync(S + o_ks, h->St(0, 0), y.n_state_arrays * np_bytes, hipMemcpyDeviceToDevice, s));
+        for (int b = 0; b < y.n_sparse; ++b)
+            SBR_HIP(hipMemcpyAsync(S + o_kl[b], h->A(y.sparse[b].a_last), (size_t)y.sparse[b].n_rows * sizeof(int), hipMemcpyDeviceToDevice, s));
+    }
+    rc = eval_chunks(h, v, dusers, n, exclude_mode, [&](int64_t c0, int rows, float* lg) -> int {
+        SBR_LAUNCH(launch_ev_goal_rank(s, v, dusers + c0, dgoff + c0, rows, y.N, lg, (int*)(S + o_ranks), (int*)(S + o_nrk) + c0, &h->last_goal_rank_form));
+        return SBR_OK;
+    });
+    if (keep) {      // (also behind a chunk that failed: the call leaves the bits it found)
+        SBR_HIP(hipMemcpyAsync(h->P(0), S + o_kp, np_bytes, hipMemcpyDeviceToDevice, s));
+        SBR_HIP(hipMemcpyAsync(h->St(0, 0), S + o_ks, y.n_state_arrays * np_bytes, hipMemcpyDeviceToDevice, s));
+        for (int b = 0; b < y.n_sparse; ++b)
+            SBR_HIP(hipMemcpyAsync(h->A(y.sparse[b].a_last), S + o_kl[b], (size_t)y.sparse[b].n_rows * sizeof(int), hipMemcpyDeviceToDevice, s));
+    }
+    if (rc != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    return check_fault(h);          // a forward that gave up must not hand out ranks; the call's one wait for the device
 }
 
 static int cluster_fits_engine(const sbr_cluster* c, const sbr_handle* h) {

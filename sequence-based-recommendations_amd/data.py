@@ -169,7 +169,7 @@ def make_device_dataset(engine, sequence_set, n_items, ratings=False):
     ds = DeviceDataset(engine, items, offsets, n_items)
     if ratings:
         ds.set_options(r, False)
-    ds.items, ds.offsets = items, offsets       # host copies: the goals of the users come from them
+    ds.items = items       # host copy: the goals of the users come from it (ds.offsets is the dataset's own)
     return ds
 
 
@@ -430,3 +430,117 @@ class NativeEvaluator(Evaluator):
             for i in np.nonzero(seg["n_pred"] > 0)[0].tolist():
                 ndcg += dcg[i] / (run[m[i] - 1] if m[i] > 0 else 0.0)
         return ndcg / self._n
+
+
+class RankEvaluator(Evaluator):
+    """Evaluator over the PLACE of every goal item in the complete ranking of its user (RNNEngine.evaluate_ranks, include/sbr_rnn.h:
+    sbr_evaluate_ranks) instead of recommendation lists: one number per goal item answers every depth at once.  at(k) is the
+    NativeEvaluator of depth k -- its records are derived from the ranks and equal what RNNEngine.evaluate returns at that k, so
+    the seven record-based metrics equal, with ==, the ones of that call; the metrics table binds them at this evaluator's own k
+    and adds "mrr".  get_rank_comparison() gives what the base class computes from full recommendation lists (test.py
+    --save_rank), mrr() the mean reciprocal rank of the first goal item.  The ranks carry no ids: novelty and `instances`, which
+    need the recommended ids, come from fetch_ids(k) -- a callable returning what RNNEngine.evaluate(k, want_ids=True) returns for
+    the same users (RNNBase.native_rank_evaluator hands one over), called on first use; without one they raise RuntimeError."""
+
+    RECORD_METRICS = ("sps", "recall", "precision", "ndcg", "item_coverage", "user_coverage", "blockbuster_share")
+
+    def __init__(self, dataset, k=10, fetch_ids=None):
+        super(RankEvaluator, self).__init__(dataset, k=k)
+        self._rk, self._items, self._glen, self._nrk, self._at = [], [], [], [], {}
+        self._fetch_ids, self._goals, self._ids_at = fetch_ids, [], {}
+        table = {name: (lambda name=name: self.at(self.k).metrics[name]()) for name in self.RECORD_METRICS}
+        table.update({"assr": self.assr, "novelty": self.average_novelty, "mrr": self.mrr})
+        self.metrics = table
+
+    # ------------------------------------------------------------------ ranks in
+    def add_ranks(self, rec, goal_items):
+        """rec: what RNNEngine.evaluate_ranks returned; goal_items: per user of rec, in order, the goal ids in sequence order
+        (the DeviceDataset's host copy: items[off + L // 2 : off + L])."""
+        off = np.asarray(rec["goal_off"], dtype=np.int64)
+        glen = off[1:] - off[:-1]
+        flat = np.concatenate([np.asarray(g, dtype=np.int64).reshape(-1) for g in goal_items]) if len(goal_items) else np.zeros(0, np.int64)
+        if len(goal_items) != len(glen) or [len(g) for g in goal_items] != glen.tolist() or len(rec["ranks"]) != len(flat):
+            raise ValueError("goal_items must hold the goal of every user of rec, as long as its ranks")
+        self._rk.append(np.asarray(rec["ranks"], dtype=np.int64)); self._items.append(flat)
+        self._glen.append(glen); self._nrk.append(np.asarray(rec["n_rankable"], dtype=np.int64))
+        self._goals.extend(np.asarray(g).reshape(-1).tolist() for g in goal_items)
+        self._at, self._ids_at = {}, {}
+
+    def _flat(self):
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        glen = cat(self._glen)
+        return cat(self._rk), cat(self._items), glen, cat(self._nrk), np.concatenate([[0], np.cumsum(glen)]).astype(np.int64)
+
+    def n_unrankable(self):
+        """goal places whose item is never ranked (rank -1: excluded, NaN or -inf score)"""
+        return int(sum(int(np.count_nonzero(r < 0)) for r in self._rk))
+
+    # ------------------------------------------------------------------ any depth
+    def at(self, k):
+        """The NativeEvaluator of depth k: n_pred = min(k, n_rankable), hits = the distinct goal items with 0 <= rank < k,
+        first_hit = goal[0] among them, hitmask bit `rank` per such item, item_hits their per-item counts."""
+        k = int(k)
+        if k not in self._at:
+            rank, items, glen, nrk, off = self._flat()
+            n = len(glen)
+            user = np.repeat(np.arange(n, dtype=np.int64), glen)
+            first_place = np.zeros(len(rank), dtype=bool)      # one place per distinct (user, item): a repeated item holds one rank
+            first_place[np.unique(user * int(self.dataset.n_items) + items, return_index=True)[1]] = True
+            sel = first_place & (rank >= 0) & (rank < k)
+            mask = np.zeros((n, (k + 31) // 32), dtype=np.uint32)
+            np.bitwise_or.at(mask, (user[sel], rank[sel] // 32), (np.uint32(1) << (rank[sel] % 32).astype(np.uint32)))
+            head = rank[off[:-1]] if n else rank
+            rec = {"n_pred": np.minimum(k, nrk).astype(np.int32), "hits": np.bincount(user[sel], minlength=n).astype(np.int32),
+                   "first_hit": ((head >= 0) & (head < k)).astype(np.int32), "hitmask": mask, "ids": None,
+                   "item_hits": np.bincount(items[sel], minlength=int(self.dataset.n_items)).astype(np.int32)}
+            ev = NativeEvaluator(self.dataset, k=k)
+            ev.add_records(rec, glen)
+            self._at[k] = ev
+        return self._at[k]
+
+    def records(self, k):
+        """the record dict at(k) is built from (what RNNEngine.evaluate returns at k, without ids)"""
+        seg = self.at(k)._seg[0]
+        return {"n_pred": seg["n_pred"].astype(np.int32), "hits": seg["hits"].astype(np.int32), "first_hit": seg["first"].astype(np.int32),
+                "hitmask": seg["mask"], "item_hits": self.at(k)._item_hits.astype(np.int32)}
+
+    # ------------------------------------------------------------------ the full ranking
+    def get_rank_comparison(self):
+        rank, _, glen, _, off = self._flat()
+        return [(j, int(rank[off[u] + j])) for u in range(len(glen)) for j in range(int(glen[u]))]
+
+    def mrr(self):
+        rank, _, glen, _, off = self._flat()
+        head = rank[off[:-1]].tolist()
+        return sum(1.0 / (1 + r) if r >= 0 else 0.0 for r in head) / len(glen)
+
+    def with_ids(self, k):
+        """The NativeEvaluator of depth k over the ids themselves (fetch_ids(k)): what the ranks cannot serve -- novelty, instances."""
+        k = int(k)
+        if k not in self._ids_at:
+            if self._fetch_ids is None:
+                raise RuntimeError("this metric needs the recommended ids, which ranks do not carry: hand RankEvaluator a fetch_ids")
+            ev = NativeEvaluator(self.dataset, k=k)
+            ev.add_records(self._fetch_ids(k), self._flat()[2], goals=self._goals)
+            self._ids_at[k] = ev
+        return self._ids_at[k]
+
+    def average_novelty(self):
+        return self.with_ids(self.k).average_novelty()
+
+    @property
+    def instances(self):
+        return self.with_ids(self.k).instances
+
+    @instances.setter
+    def instances(self, value):      # (Evaluator.__init__ starts from an empty list)
+        pass
+
+    # the base class's methods of the record-based metrics, at this evaluator's own k
+    def sps(self): return self.at(self.k).sps()
+    def average_recall(self): return self.at(self.k).average_recall()
+    def average_precision(self): return self.at(self.k).average_precision()
+    def average_ndcg(self): return self.at(self.k).average_ndcg()
+    def user_coverage(self): return self.at(self.k).user_coverage()
+    def item_coverage(self): return self.at(self.k).item_coverage()
+    def blockbuster_share(self): return self.at(self.k).blockbuster_share()

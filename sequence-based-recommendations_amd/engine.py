@@ -84,7 +84,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_cluster_mask_scores", "sbr_cluster_hard", "sbr_cluster_lists", "sbr_cluster_rank",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
-           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate"]
+           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks"]
 
 _lib = None
 
@@ -176,6 +176,7 @@ def load_library(path=None):
     lib.sbr_plan_pass_host.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, vp, vp, i32p, vp, vp, vp, vp, i64p, i64p]
     lib.sbr_build_batch.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint64]
     lib.sbr_evaluate.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+    lib.sbr_evaluate_ranks.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, vp]
     lib.sbr_cluster_evaluate.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SbrEvalOut),
                                          ctypes.POINTER(SbrEvalOut), vp, vp, vp]
     if path == LIB_PATH:
@@ -308,6 +309,7 @@ class DeviceDataset(object):
         items = np.ascontiguousarray(items, dtype=np.int32)
         offsets = np.ascontiguousarray(offsets, dtype=np.int64)
         self.n_users, self.n_batches = len(offsets) - 1, 0
+        self.offsets = offsets      # host copy (n_users + 1 words): sizes evaluate_ranks' result
         d = ctypes.c_void_p()
         with engine.torch.cuda.device(engine.device):
             engine._check(self.lib.sbr_dataset_create(items.ctypes.data, offsets.ctypes.data, self.n_users, int(n_items),
@@ -781,6 +783,25 @@ class RNNEngine(object):
             rec = SbrEvalOut.of(out)
             self._check(self.lib.sbr_evaluate(self.h, dataset.d, _ptr(users) if n else None, n, k, int(exclude_mode),
                                               rec.ids, rec.n_pred, rec.hits, rec.first_hit, rec.hitmask, rec.item_hits))
+        return out
+
+    def evaluate_ranks(self, dataset, users, exclude_mode):
+        """The place of every goal item in the complete ranking of its user (sbr_evaluate_ranks): users are split, fed and excluded
+        as by evaluate(); no k.  Returns a dict: "goal_off" (int64 (n + 1,): user j's goal places are [goal_off[j], goal_off[j + 1]),
+        in sequence order), "ranks" (int32 (goal_off[-1],): the index of the goal item in evaluate(k=n_items)'s ids of that user,
+        -1 for an item that is never ranked) and "n_rankable" (int32 (n,): that call's n_pred)."""
+        self._rank_local_flush("evaluate_ranks")
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        n = len(users)
+        off, cap = np.asarray(dataset.offsets, dtype=np.int64), 0      # the dataset's host offsets size the result
+        if n and users.min() >= 0 and users.max() < len(off) - 1:      # (otherwise the library rejects the users: nothing is written)
+            lens = off[1:][users] - off[:-1][users]
+            cap = int((lens - lens // 2).sum())
+        out = {"ranks": np.empty(cap, dtype=np.int32), "goal_off": np.zeros(n + 1, dtype=np.int64), "n_rankable": np.empty(n, dtype=np.int32)}
+        self.evaluate_calls += 1
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.sbr_evaluate_ranks(self.h, dataset.d, _ptr(users) if n else None, n, int(exclude_mode), _ptr(out["goal_off"]),
+                                                    _ptr(out["ranks"]), cap, _ptr(out["n_rankable"])))
         return out
 
     # ---------------------------------------------------------------- debug / timing

@@ -389,13 +389,13 @@ class RNNBase(object):
 
     native_eval = True          # evaluate() ranks what this model's test function / top_k_recommendations rank (RNNCluster: no, it ranks inside a cluster)
 
-    def _native_eval_users(self, dataset, which, evaluate_on=None):
+    def _native_eval_users(self, dataset, which, evaluate_on=None, method="evaluate"):
         """(DeviceDataset, users, lengths) of dataset's "validation" / "test" set for one native evaluation call, or None where the
         per-user host road must run: SBR_NATIVE_EVAL=0, a data-parallel wrapper (its collectives own the ranking calls), a
-        stand-in without evaluate() (evaluate_on: the object that must offer it, the engine by default), a shuffled set, or a
+        stand-in without evaluate() (evaluate_on: the object that must offer `method`, the engine by default), a shuffled set, or a
         target selection that may drop a test row (--rand_test_target with --target_bias)."""
         ts = self.target_selection
-        if os.environ.get("SBR_NATIVE_EVAL", "1") == "0" or self.dp is not None or not hasattr(self.engine if evaluate_on is None else evaluate_on, "evaluate"):
+        if os.environ.get("SBR_NATIVE_EVAL", "1") == "0" or self.dp is not None or not hasattr(self.engine if evaluate_on is None else evaluate_on, method):
             return None
         if getattr(dataset, which + "_set").shuffle or (which == "validation" and not ts.determinist_test and ts.bias >= 0.0):
             return None      # (users in file order only; a validation row without a target is skipped by the host road)
@@ -430,6 +430,26 @@ class RNNBase(object):
         if not self.native_eval:
             return None
         return self._whole_catalogue_evaluator(dataset, which, k, mode, want_ids=want_ids)
+
+    def _whole_catalogue_rank_evaluator(self, dataset, which, mode, k):
+        from .data import RankEvaluator
+        found = self._native_eval_users(dataset, which, method="evaluate_ranks")
+        if found is None:
+            return None
+        ds, users, lens = found
+        rec = self.engine.evaluate_ranks(ds, users, mode)
+        # (novelty and `instances` need the ids: one more engine call at the depth asked for, only if they are asked for)
+        ev = RankEvaluator(dataset, k=k, fetch_ids=lambda depth: self.engine.evaluate(ds, users, depth, mode, want_ids=True, want_mask=True))
+        ev.add_ranks(rec, [ds.items[ds.offsets[u] + lens[u] // 2:ds.offsets[u + 1]] for u in users.tolist()])
+        return ev
+
+    def native_rank_evaluator(self, dataset, which, mode, k=10):
+        """The place of every goal item of dataset's "validation" / "test" set in the complete ranking of its user, from ONE engine
+        call (RNNEngine.evaluate_ranks), as a data.RankEvaluator: the metrics at any depth, the rank comparison of test.py
+        --save_rank, mrr.  mode: engine.EVAL_EXCL_*.  None -> the per-user host road (_native_eval_users names the cases)."""
+        if not self.native_eval:
+            return None
+        return self._whole_catalogue_rank_evaluator(dataset, which, mode, k)
 
     def _compute_validation_metrics(self, metrics):
         from .data import Evaluator
@@ -930,6 +950,16 @@ class RNNCluster(RNNBase):
         out = self.head.evaluate(ds, users, k, CEVAL_LISTS, mode, want_ids=want_ids, want_mask=True)
         ev = self._evaluator_of_records(dataset, ds, users, lens, out["inside"], k, want_ids)
         ev.nb_of_dp = np.mean(out["size"])
+        return ev
+
+    def native_rank_evaluator(self, dataset, which, mode, k=10):
+        """--ignore_clusters: RNNBase's whole-catalogue ranks, nb_of_dp = n_items; None otherwise -- the place of a goal item inside
+        its user's cluster is not what evaluate_ranks counts, the per-user host road serves it."""
+        if self.predict_with_clusters:
+            return None
+        ev = self._whole_catalogue_rank_evaluator(dataset, which, mode, k)
+        if ev is not None:
+            ev.nb_of_dp = self.n_items
         return ev
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):

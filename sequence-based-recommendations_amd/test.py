@@ -45,11 +45,16 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
     mean number of items scored per user, the size of the user's cluster.
     By default none of that loop runs: the whole set is evaluated by one engine call (RNNBase.native_evaluator, sbr_evaluate; for a
     cluster model RNNCluster.native_evaluator, sbr_cluster_evaluate) and the returned evaluator is a data.NativeEvaluator with the
-    same metrics, equal with ==."""
+    same metrics, equal with ==.
+    get_full_recommendation_list (--save_rank) needs the place of every goal item in the complete ranking, not the ranking: one
+    engine call counts them (RNNBase.native_rank_evaluator, sbr_evaluate_ranks) and the returned data.RankEvaluator derives the
+    metrics at k and the rank comparison from them.  Deliberate difference: those places are sbr_rank's on the raw scores, ties
+    to the lowest id; the per-user road ranks predict_function's output -- for CCE softmax probabilities, which can tie where
+    the raw scores do not.  On a sampled-head model without ties the two full_rank files are equal."""
     predictor.load(model_file)
     # the whole test set in one engine call (RNNBase.native_evaluator): every user here has a viewed half -- the set's generator
     # skips sequences of fewer than two items -- and the engine excludes all of it, also what no longer fits the window.  Not
-    # with --save_rank, not with SBR_NATIVE_EVAL=0: those take the per-user road below.  A cluster model's call is the head's
+    # with SBR_NATIVE_EVAL=0: that takes the per-user road below; --save_rank has a native road of its own (further down).  A cluster model's call is the head's
     # (RNNCluster.native_evaluator, sbr_cluster_evaluate): inside each user's cluster, nb_of_dp the mean cluster size.
     # the reference tests a model as a cluster model on args.clusters > 0 (test.py:61): its recommendation calls return (ids, n)
     clustered = getattr(args, "clusters", 0) > 0
@@ -62,6 +67,18 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
             print("Timer: ", time.perf_counter() - start)
             if not clustered:
                 evaluator.nb_of_dp = dataset.n_items                                                   # test.py:73-76
+            return evaluator
+    # --save_rank: the ranks of the goal items from one engine call.  Not for a cluster model (a place inside a cluster is another
+    # count), and not when a goal item of the set is unrankable (rank -1: with unique interactions, a goal item that was also viewed):
+    # the reference places such an item behind the ranked ones in numpy's partition order, which is no defined rank -- the whole set
+    # then takes the per-user road below, as it does with SBR_NATIVE_EVAL=0.
+    if get_full_recommendation_list and not clustered and hasattr(predictor, "native_rank_evaluator"):
+        from .engine import EVAL_EXCL_NONE, EVAL_EXCL_VIEWED
+        start = time.perf_counter()
+        evaluator = predictor.native_rank_evaluator(dataset, "test", EVAL_EXCL_VIEWED if predictor.interactions_are_unique else EVAL_EXCL_NONE, k=k)
+        if evaluator is not None and evaluator.n_unrankable() == 0:
+            print("Timer: ", time.perf_counter() - start)
+            evaluator.nb_of_dp = dataset.n_items                                                       # test.py:73-76
             return evaluator
     evaluator = Evaluator(dataset, k=k)
     if get_full_recommendation_list:
@@ -101,8 +118,9 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
         if len(goal) == 0:
             raise ValueError
         order.append((n, goal))
-        # Two cases stay on the host, one user per call.  --save_rank: the reference's full list also holds the excluded ids, behind
-        # the ranked ones in numpy's partition order, and the rank comparison reads them; the engine never ranks an excluded id.
+        # Two cases stay on the host, one user per call.  --save_rank where the ranks could not come from the engine (above): the
+        # reference's full list also holds the excluded ids, behind the ranked ones in numpy's partition order, and the rank
+        # comparison reads them; the engine never ranks an excluded id.
         # An empty viewed half (a sequence of one item): a row of length 0 has only ever been scored by this one-row call, and a
         # test set holds at most a handful of them.
         if clustered:
