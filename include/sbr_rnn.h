@@ -289,9 +289,17 @@ int sbr_predict_scores(sbr_handle* h, int probs, float* out_host);
 /* test_function(theano_inputs, k) (rnn_base.py:196-211): ordered top-k ids per row of
  * softmax * (1 - exclude) where exclude = the row's own input items when exclude_seen
  * (interactions_are_unique, rnn_base.py:200-201).  Ties break to the lowest id.  A row with fewer than k rankable items
- * (more than N - k items excluded, or NaN scores) gets -1 in the places it cannot fill. */
+ * (more than N - k items excluded, or NaN scores) gets -1 in the places it cannot fill.
+ *   k             1 <= k <= min(64, N)
+ *   exclude_seen  0: nothing; 1: the items of the row's input window are never ranked (top_k_recommendations, rnn_base.py:154-155);
+ *                 2: the compiled function's scores * (1 - exclude) (:201-202) -- 1's ranking for every loss but RNNMargin's, whose
+ *                 raw outputs it ranks with the window items at 0.0 and still rankable
+ * No batch set: SBR_ESTATE.  This is an entry to sbr_rank's pipeline (exclusion, radix select, sort) with the contract above: it
+ * takes its select / sort working set from the handle's ranking scratch (see sbr_rank; SBR_ENOMEM when that cannot grow), an input
+ * id outside [0, N) is skipped, the scores it ranks are left as the exclusion left them, and sbr_query "rank_select" / "rank_sort"
+ * tell what it ran. */
 int sbr_topk(sbr_handle* h, int k, int exclude_seen, int32_t* ids_host);
-/* The same ranking without sbr_topk's limits (ABI 11): any depth 1 <= k <= N, and per-row exclusion lists -- the batched form of
+/* The same ranking, by the same kernels, without sbr_topk's limits (ABI 11): any depth 1 <= k <= N, and per-row exclusion lists -- the batched form of
  * top_k_recommendations(sequence, k, exclude=...) (rnn_base.py:140-165), for users whose history is longer than max_length (all of
  * it is excluded, only its end is fed) and for metrics deeper than 64.  The scores ranked are the ones sbr_topk ranks (the exact-f32
  * projection plus bias, no softmax: monotone), so the two calls agree id for id.

@@ -732,7 +732,7 @@ extern "C" int sbr_dense_ranges(sbr_handle* h, int cap, int64_t* lo, int64_t* hi
 }
 
 // ---------------------------------------------------------------------------------------
-// predict / top-k
+// predict (the ranking calls, sbr_topk among them: sbr_rank_api.hip)
 // ---------------------------------------------------------------------------------------
 int full_scores(sbr_handle* h, int do_softmax) {
     const Layout& y = h->lay;
@@ -764,28 +764,6 @@ extern "C" int sbr_predict_scores(sbr_handle* h, int probs, float* out_host) {
         return check_fault(h);      // a forward that gave up must not hand out scores
     }
     return SBR_OK;
-}
-
-extern "C" int sbr_topk(sbr_handle* h, int k, int exclude_seen, int32_t* ids_host) {
-    CHECK_ARG(h && ids_host, "null argument");
-    if (!h->have_batch) { sbr_set_error("sbr_topk: no batch set"); return SBR_ESTATE; }
-    const Layout& y = h->lay;
-    CHECK_ARG(k >= 1 && k <= 64 && k <= y.N, "k=%d outside [1,min(64,N)]", k);
-    // softmax is monotone: ranking the biased logits == ranking softmax(logits)*(1-exclude)
-    // (rnn_base.py:200-207) whenever at least k items are not excluded.
-    const int rc = full_scores(h, 0);
-    if (rc != SBR_OK) return rc;
-    float* lg = h->A(y.a_logits);
-    // exclude_seen 1: viewed items can never be ranked (top_k_recommendations, rnn_base.py:154-155); 2: the compiled test
-    // function's scores * (1 - exclude) (:201-202) -- the same ranking for probabilities, NOT for RNNMargin's raw outputs,
-    // where a viewed item then scores 0 and outranks every negative one
-    if (exclude_seen)
-        SBR_LAUNCH(launch_exclude_seen(h->stream, lg, h->bX, h->blen, h->n_rows, y.T, y.F, y.N,
-                                       (exclude_seen == 2 && SBR_LOSS_IS_MARGIN(y.cfg.loss)) ? 0.0f : -INFINITY));
-    int* ids = (int*)h->A(y.a_topk);
-    SBR_LAUNCH(launch_topk(h->stream, lg, h->n_rows, y.N, k, ids));
-    SBR_HIP(hipMemcpyAsync(ids_host, ids, (size_t)h->n_rows * k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    return check_fault(h);          // ... nor rankings (test.py, validation)
 }
 
 // ---------------------------------------------------------------------------------------

@@ -548,8 +548,9 @@ int sbr_dataset_eval_view(sbr_dataset* d, SbrEvalView* v, int with_goal) {
         std::vector<int> g(d->h_items);
         g.resize((size_t)std::max<int64_t>(d->nnz, 1));
         for (int64_t u = 0; u < d->n_users; ++u) {
-            const int64_t o = d->h_off[u], L = d->h_off[u + 1] - o;
-            std::sort(g.begin() + o + L / 2, g.begin() + o + L);
+            const int64_t o = d->h_off[u];
+            const UserSplit sp(o, d->h_off[u + 1], 0);              // (no window here)
+            std::sort(g.begin() + o + sp.half, g.begin() + o + sp.half + sp.goal_len());
         }
         if (hipMalloc(&d->d_goal, g.size() * sizeof(int)) != hipSuccess) {
             (void)hipGetLastError(); d->d_goal = nullptr;

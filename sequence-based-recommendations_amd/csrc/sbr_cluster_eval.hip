@@ -1,12 +1,10 @@
 // sbr_cluster_evaluate: whole test / validation users of a cluster model on the device (include/sbr_rnn.h; the chunk loop is in
-// sbr_api.hip next to sbr_evaluate).  Pack, whole-catalogue exclusion and hits are sbr_eval.hip's kernels, grouping, member scoring,
-// gathering and translation sbr_cluster_rank.hip's, select and sort sbr_rank.hip's.  What those do not do:
-//   1. cev_exclude_kernel    the viewed / fed items of a user, read from the dataset's CSR, out of the row of the compact cluster
-//                            matrix (LISTS road; sbr_cluster_rank takes them from an uploaded list or from the input window)
-//   2. cev_transpose_kernel  hard [N][C] -> hardT [C][N], once per version of R
-//   3. cev_product_kernel    softmax probability times hard membership of the row's cluster over the catalogue (PRODUCT road: the
+// sbr_rank_api.hip next to sbr_evaluate).  Pack and hits are sbr_eval.hip's kernels, grouping, member scoring, gathering and
+// translation sbr_cluster_rank.hip's, exclusion (of both rankings), select and sort sbr_rank.hip's.  What those do not do:
+//   1. cev_transpose_kernel  hard [N][C] -> hardT [C][N], once per version of R
+//   2. cev_product_kernel    softmax probability times hard membership of the row's cluster over the catalogue (PRODUCT road: the
 //                            compiled test function, rnn_cluster.py:327-352), then +0.0 at the items fed
-//   4. cev_use_kernel        users per selected cluster
+//   3. cev_use_kernel        users per selected cluster
 // Rows are independent in every kernel; nothing waits on another workgroup.
 #include "sbr_common.h"
 #include "sbr_device.h"
@@ -14,25 +12,6 @@
 #include <algorithm>
 
 namespace {
-
-// One workgroup per row.  VIEWED: every viewed item; WINDOW: the items fed (the last min(T, half) of them).
-__global__ void __launch_bounds__(256) cev_exclude_kernel(float* __restrict__ cs, int lmax, const int* __restrict__ csel, int C,
-                                                          const int* __restrict__ mem, const int* __restrict__ moff, int N,
-                                                          const int* __restrict__ items, const long long* __restrict__ off,
-                                                          const int* __restrict__ users, int T, int mode) {
-    const int r = blockIdx.x, c = csel[r];
-    if ((unsigned)c >= (unsigned)C) return;
-    const int base = moff[c], n = min(moff[c + 1] - base, lmax);
-    const int u = users[r];
-    const long long o = off[u];
-    const int half = (int)(off[u + 1] - o) / 2;
-    const int start = mode == SBR_EVAL_EXCL_VIEWED ? 0 : half - min(T, half);
-    float* row = cs + (size_t)r * lmax;
-    for (int t = start + threadIdx.x; t < half; t += blockDim.x) {
-        const int id = items[o + t];
-        if ((unsigned)id < (unsigned)N) crk_exclude_one(row, mem + base, n, id);
-    }
-}
 
 // 32 x 32 tiles through LDS: reads and writes are both rows of 32 consecutive floats
 __global__ void __launch_bounds__(256) cev_transpose_kernel(const float* __restrict__ in, int N, int C, float* __restrict__ out) {
@@ -74,8 +53,8 @@ __global__ void __launch_bounds__(256) cev_product_kernel(const float* __restric
     __syncthreads();                                 // the row is written before a fed item is overwritten by another thread
     const int u = users[r];
     const long long o = off[u];
-    const int half = (int)(off[u + 1] - o) / 2;
-    for (int t = half - min(T, half) + threadIdx.x; t < half; t += 256) {
+    const UserSplit sp(o, off[u + 1], T);
+    for (int t = sp.window_begin() + threadIdx.x; t < sp.window_end(); t += 256) {
         const int id = items[o + t];
         if ((unsigned)id < (unsigned)N) out[id] = 0.0f;
     }
@@ -89,13 +68,6 @@ __global__ void __launch_bounds__(256) cev_use_kernel(const int* __restrict__ cs
 }
 
 }  // namespace
-
-hipError_t launch_cev_exclude(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int mode, float* cs, int lmax,
-                              const int* csel, int C, const int* mem_ids, const int* mem_off) {
-    if (rows <= 0 || mode == SBR_EVAL_EXCL_NONE) return hipSuccess;
-    cev_exclude_kernel<<<rows, 256, 0, s>>>(cs, lmax, csel, C, mem_ids, mem_off, N, v.items, v.off, users, T, mode);
-    return hipGetLastError();
-}
 
 hipError_t launch_cev_transpose(hipStream_t s, const float* hard, int N, int C, float* hardT) {
     cev_transpose_kernel<<<dim3((unsigned)((N + 31) / 32), (unsigned)((C + 31) / 32)), 256, 0, s>>>(hard, N, C, hardT);

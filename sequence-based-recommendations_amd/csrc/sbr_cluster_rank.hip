@@ -8,8 +8,8 @@
 //   per call  crk_group_kernel (counting sort of the rows by cluster, table of 16-row tiles), then either
 //             crk_score_kernel  (form 1) the scores of the members only, into a compact matrix cs [rows][Lmax], or
 //             crk_gather_kernel (form 2) the same places picked out of the full score matrix,
-//             crk_exclude_kernel (binary search of every excluded id in the row's ascending list), the select and sort of
-//             sbr_rank.hip on cs (they return PLACES; place order inside a list is id order, so their tie rule carries over),
+//             the exclusion (sbr_rank.hip's exclude_kernel on ExclCluster rows: binary search of every excluded id in the row's
+//             ascending list), the select and sort of sbr_rank.hip on cs (they return PLACES; place order inside a list is id order, so their tie rule carries over),
 //             crk_translate_kernel (place -> item id).
 //
 // Accumulation order of form 1.  full_scores runs gemm_f32_mfma (sbr_gemm.hip) without split-K: for an output element one chain of
@@ -19,7 +19,6 @@
 // roles in the same k order and ends in the same two adds, so a score here is the very float sbr_rank ranks: an output element of
 // the instruction depends on its own row of A and column of B only, not on which rows or items share the tile.
 #include "sbr_common.h"
-#include "sbr_device.h"
 #include <math.h>
 #include <algorithm>
 #include <new>
@@ -229,28 +228,6 @@ __global__ void __launch_bounds__(256) crk_gather_kernel(const float* __restrict
         cs[(size_t)r * lmax + p] = p < len ? lg[(size_t)r * N + mem[base + p]] : -INFINITY;
 }
 
-// (crk_exclude_one: sbr_device.h)
-__global__ void __launch_bounds__(256) crk_exclude_kernel(float* __restrict__ cs, int lmax, const int* __restrict__ csel, const int* __restrict__ mem,
-                                                          const int* __restrict__ moff, int N, const int* __restrict__ excl_ids,
-                                                          const long long* __restrict__ excl_off, const int* __restrict__ X,
-                                                          const int* __restrict__ len, int T, int F) {
-    const int r = blockIdx.x, c = csel[r];
-    const int base = moff[c], n = moff[c + 1] - base;
-    float* row = cs + (size_t)r * lmax;
-    if (excl_off)
-        for (long long e = excl_off[r] + threadIdx.x; e < excl_off[r + 1]; e += blockDim.x) {
-            const int id = excl_ids[e];
-            if ((unsigned)id < (unsigned)N) crk_exclude_one(row, mem + base, n, id);
-        }
-    if (X) {
-        const int L = min(len[r], T);
-        for (int t = threadIdx.x; t < L; t += blockDim.x) {
-            const int id = X[((size_t)r * T + t) * F];
-            if ((unsigned)id < (unsigned)N) crk_exclude_one(row, mem + base, n, id);
-        }
-    }
-}
-
 __global__ void __launch_bounds__(256) crk_translate_kernel(const int* __restrict__ pos, const float* __restrict__ psc, int kk, int k,
                                                             const int* __restrict__ csel, const int* __restrict__ mem, const int* __restrict__ moff,
                                                             int* __restrict__ out_ids, float* __restrict__ out_scores, int* __restrict__ size) {
@@ -350,13 +327,6 @@ hipError_t launch_crk_gather(hipStream_t s, const float* logits, int N, const in
                              int rows, int lmax, float* cs) {
     if (rows <= 0) return hipSuccess;
     crk_gather_kernel<<<dim3((unsigned)std::min(64, (lmax + 255) / 256), (unsigned)rows), 256, 0, s>>>(logits, N, csel, mem_ids, mem_off, lmax, cs);
-    return hipGetLastError();
-}
-
-hipError_t launch_crk_exclude(hipStream_t s, float* cs, int lmax, const int* csel, const int* mem_ids, const int* mem_off, int rows, int N,
-                              const int* excl_ids, const long long* excl_off, const int* X, const int* len, int T, int F) {
-    if (rows <= 0 || (!excl_off && !X)) return hipSuccess;
-    crk_exclude_kernel<<<rows, 256, 0, s>>>(cs, lmax, csel, mem_ids, mem_off, N, excl_ids, excl_off, X, len, T, F);
     return hipGetLastError();
 }
 

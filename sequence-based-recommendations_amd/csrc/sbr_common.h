@@ -183,6 +183,27 @@ __device__ __forceinline__ unsigned rank_key(float v) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
+// How the evaluation reads a user's sequence of L items (test.py:81-83, rnn_base.py:410), the one statement of the rule: items
+// [0, half) are viewed, [half, L) are the goal, and the row fed is the window of the last min(T, half) viewed items.  Places count
+// from the user's first item; built from the user's two offsets into the dataset's CSR and the engine's T.
+struct UserSplit {
+    int L, half, fed;
+    __host__ __device__ constexpr UserSplit(long long off_lo, long long off_hi, int T)
+        : L((int)(off_hi - off_lo)), half(L / 2), fed(T < half ? T : half) {}
+    __host__ __device__ constexpr int goal_len() const { return L - half; }
+    __host__ __device__ constexpr int viewed_begin() const { return 0; }
+    __host__ __device__ constexpr int viewed_end() const { return half; }
+    __host__ __device__ constexpr int window_begin() const { return half - fed; }
+    __host__ __device__ constexpr int window_end() const { return half; }
+};
+#define SBR_SPLIT_IS(L, T, H, G, WB) (UserSplit(100, 100 + (L), (T)).half == (H) && UserSplit(100, 100 + (L), (T)).goal_len() == (G) && \
+                                      UserSplit(100, 100 + (L), (T)).window_begin() == (WB) && UserSplit(100, 100 + (L), (T)).window_end() == (H))
+// (L, T) -> half, goal length, first place of the window; T shorter than, equal to and longer than half
+static_assert(SBR_SPLIT_IS(2, 0, 1, 1, 1) && SBR_SPLIT_IS(2, 1, 1, 1, 0) && SBR_SPLIT_IS(2, 5, 1, 1, 0), "L = 2: one item viewed, one the goal");
+static_assert(SBR_SPLIT_IS(3, 0, 1, 2, 1) && SBR_SPLIT_IS(3, 1, 1, 2, 0) && SBR_SPLIT_IS(3, 2, 1, 2, 0), "L = 3: the odd item belongs to the goal");
+static_assert(SBR_SPLIT_IS(7, 2, 3, 4, 1) && SBR_SPLIT_IS(7, 3, 3, 4, 0) && SBR_SPLIT_IS(7, 4, 3, 4, 0), "L = 7: the window is the END of the viewed half");
+#undef SBR_SPLIT_IS
+
 // Every environment switch the library reads (README.md "Switches"), with its default.  sbr_read_switches (sbr_api.hip) fills one
 // per engine, inside sbr_create, and nothing reads the environment afterwards: an engine keeps the values it was created under.
 #define HEAD_WAIT_TICKS 6000ull      // 60 us of the 100 MHz clock: how long a chunk's statistics are waited for before they are recomputed
@@ -671,16 +692,13 @@ hipError_t launch_sparse_pack(hipStream_t s, const SbrSparseRows& r, const int* 
                               int epoch, int* ids_out, float* rows_out, int W, int* count);
 hipError_t launch_sparse_unpack_add(hipStream_t s, const SbrSparseRows& r, const int* ids, const float* rows, int n, int W, int* cand);
 hipError_t launch_sparse_unpack_add_dev(hipStream_t s, const SbrSparseRows& r, const int* ids, const float* rows, int cap, int W, int* cand);
-// top-k (rnn_base.py:196-211)
-// value: -inf (top_k_recommendations, rnn_base.py:154-155) or 0 (the compiled test function's scores * (1 - exclude), :201-202)
-hipError_t launch_exclude_seen(hipStream_t s, float* scores, const int* X, const int* len, int rows, int T, int F,
-                               int N, float value);
-hipError_t launch_topk(hipStream_t s, float* scores, int rows, int N, int k, int* ids);
 hipError_t launch_fill(hipStream_t s, float* p, float v, size_t n);
-// sbr_rank.hip: ordered top-k of any k with per-row exclusion lists (include/sbr_rnn.h: sbr_rank)
-// -inf into scores[r][id] for the ids of row r's CSR list (excl_off NULL: none) and, with X, of its input window
-hipError_t launch_rank_exclude(hipStream_t s, float* scores, int rows, int N, const int* excl_ids, const long long* excl_off,
-                               const int* X, const int* len, int T, int F);
+// sbr_rank.hip: ordered top-k of any k with per-row exclusion (include/sbr_rnn.h: sbr_topk, sbr_rank)
+// The one exclusion of every ranking call: the ids that `src` names for row r (sbr_device.h: ExclSources -- the caller's CSR lists,
+// the row's input window, the viewed half of the row's user) leave row r of `to` (ExclCatalogue: a value at scores[r][id];
+// ExclCluster: -inf at the id's place of a compact cluster row).  One workgroup of 256 per row; no source, no launch.
+struct ExclSources;
+template <class Sink> hipError_t launch_exclude(hipStream_t s, int rows, const ExclSources& src, const Sink& to);
 // the (at most k) entries of every row that a ranking to depth k holds, in id order: keys / ids [rows][k], n_sel [rows]; returns the
 // regime in *select (1: the row's keys in LDS, 2: streamed)
 hipError_t launch_rank_select(hipStream_t s, const float* scores, int rows, int N, int k, unsigned* keys, int* ids, int* n_sel, int* select);
@@ -704,16 +722,13 @@ hipError_t launch_crk_score(hipStream_t s, const float* h, int ldh, const float*
 // the second form: cs[row][j] = logits[row][members(c)[j]]
 hipError_t launch_crk_gather(hipStream_t s, const float* logits, int N, const int* csel, const int* mem_ids, const int* mem_off,
                              int rows, int lmax, float* cs);
-// -inf at the places of the row's excluded ids that its cluster holds (binary search in the ascending list)
-hipError_t launch_crk_exclude(hipStream_t s, float* cs, int lmax, const int* csel, const int* mem_ids, const int* mem_off, int rows, int N,
-                              const int* excl_ids, const long long* excl_off, const int* X, const int* len, int T, int F);
 // places -> item ids, widened from kk to k columns (-1 / -inf); clu / size (nullable) [rows]: the row's cluster and its list's length
 hipError_t launch_crk_translate(hipStream_t s, const int* pos, const float* psc, int kk, int k, const int* csel, const int* mem_ids,
                                 const int* mem_off, int rows, int* out_ids, float* out_scores, int* size);
 // makes c->hard = f(100 R) if R changed since it was made and, with transposed, c->hardT from it; SBR_OK or a negative sbr_status
 int sbr_cluster_build_hard(sbr_cluster* c, int transposed);
 // sbr_eval.hip: evaluation of whole users on the device (include/sbr_rnn.h: sbr_evaluate).  A user's sequence is split in the middle
-// (test.py:81-83, _gen_mini_batch(test=True)): half = L / 2 viewed items, the rest is the goal.
+// (UserSplit above): the viewed half, the rest is the goal.
 // What sbr_evaluate reads of a dataset (sbr_batch.hip owns the struct): the sequences as uploaded -- never the noised copy --, the
 // host copy of the offsets for the argument checks, and `goal`: per user the goal items[off + half .. off + L) sorted ascending, at
 // the same places of a second array (its viewed places are not written).  Built on the first call, freed with the dataset.
@@ -725,8 +740,6 @@ int sbr_dataset_eval_view(sbr_dataset* d, SbrEvalView* v, int with_goal);      /
 // rows [0, rows) of the batch buffers from users[0 .. rows): the last min(T, half) viewed items left-aligned (+ n_items + rating index
 // with F == 2, as bb_pack_kernel writes it), the length, popularity 1; rows [rows, Bp): index 0, length 0, popularity 1
 hipError_t launch_ev_pack(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop);
-// mode SBR_EVAL_EXCL_*: -inf (WINDOW_ZERO: 0.0f) into scores[r][id] for the viewed items of users[r] (VIEWED: all of them; WINDOW*: the ones fed)
-hipError_t launch_ev_exclude(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int mode, float* scores);
 // per row r of ids [rows][k] (ordered top-k, -1 behind the filled places): n_pred, hits, first_hit [rows], mask [rows][(k + 31) / 32]
 // (NULL: not written), item_hits [N] += 1 per hit (NULL: not counted)
 hipError_t launch_ev_hits(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int k, const int* ids, int* n_pred, int* hits,
@@ -737,9 +750,6 @@ hipError_t launch_ev_hits(hipStream_t s, const SbrEvalView& v, const int* users,
 hipError_t launch_ev_goal_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* goal_off, int rows, int N,
                                const float* scores, int* ranks, int* n_rankable, int* form);
 // sbr_cluster_eval.hip: what sbr_cluster_evaluate needs beyond the kernels above (include/sbr_rnn.h)
-// -inf at the places of the viewed (mode VIEWED) / fed (WINDOW) items of users[r] that the row's cluster holds; cs [rows][lmax]
-hipError_t launch_cev_exclude(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int mode, float* cs, int lmax,
-                              const int* csel, int C, const int* mem_ids, const int* mem_off);
 hipError_t launch_cev_transpose(hipStream_t s, const float* hard, int N, int C, float* hardT);
 // prod[r][i] = softmax(logits[r])[i] * hardT[csel[r]][i] (logits: biased, untouched by any exclusion), then with zero_fed +0.0 at the
 // items fed of users[r]

@@ -1,12 +1,12 @@
 // sbr_evaluate: whole test / validation users on the device (include/sbr_rnn.h; test.py:43-77, rnn_base.py:358-371 and the set
-// algebra of evaluation.py:16-216).  Between the forward and the ranking kernels the call already has (sbr_rank.hip) it needs three
-// small kernels, all reading the dataset's CSR (sbr_batch.hip) where it lies:
-//   1. ev_pack_kernel      the rows fed: the last min(T, half) viewed items of every user of the chunk
-//   2. ev_exclude_kernel   the viewed items out of the score rows
-//   3. ev_hits_kernel      the ordered top-k against the goal: counts, the hit mask, per-item hit counts
-// and, for sbr_evaluate_ranks, in place of select + sort + 3:
-//   4. ev_goal_rank_kernel the place of every goal item in the row's complete ranking, counted and never sorted out
-// A user's sequence of L items is split at half = L / 2 (test.py:81-83): items[0 .. half) viewed, items[half .. L) the goal.
+// algebra of evaluation.py:16-216).  Between the forward and the ranking kernels the call already has (sbr_rank.hip: exclusion --
+// here of the viewed items, read from the dataset's CSR --, select, sort) it needs two small kernels, both reading the dataset's CSR
+// (sbr_batch.hip) where it lies:
+//   1. ev_pack_kernel      the rows fed: the window of every user of the chunk
+//   2. ev_hits_kernel      the ordered top-k against the goal: counts, the hit mask, per-item hit counts
+// and, for sbr_evaluate_ranks, in place of select + sort + 2:
+//   3. ev_goal_rank_kernel the place of every goal item in the row's complete ranking, counted and never sorted out
+// What of a user's sequence is viewed, fed (the window) and the goal: UserSplit (sbr_common.h).
 // Rows are independent in every kernel; nothing waits on another workgroup.
 #include "sbr_common.h"
 #include <math.h>
@@ -25,29 +25,13 @@ __global__ void __launch_bounds__(64) ev_pack_kernel(const int* __restrict__ ite
     }
     const int u = users[b];
     const long long o = off[u];
-    const int half = (int)(off[u + 1] - o) / 2;
-    const int n_in = min(T, half), start = half - n_in;            // rnn_base.py:410: at most max_length items before the split
+    const UserSplit sp(o, off[u + 1], T);
+    const int start = sp.window_begin(), n_in = sp.window_end() - start;   // rnn_base.py:410: at most max_length items before the split
     for (int t = lane; t < T; t += 64) {
         X[((size_t)b * T + t) * F] = t < n_in ? items[o + start + t] : 0;
         if (F == 2) X[((size_t)b * T + t) * F + 1] = t < n_in ? n_items + rate[o + start + t] : 0;   // rnn_base.py:637-642
     }
     if (lane == 0) { lengths[b] = n_in; pop[b] = 1.0f; }
-}
-
-// One workgroup per row.  VIEWED: every viewed item, also the ones in front of the window (top_k_recommendations, rnn_base.py:154-155);
-// WINDOW / WINDOW_ZERO: the items fed (the compiled test function's exclude, rnn_base.py:200-202) -- removed / scored 0.
-__global__ void __launch_bounds__(256) ev_exclude_kernel(const int* __restrict__ items, const long long* __restrict__ off,
-                                                         const int* __restrict__ users, int T, int N, int mode, float* __restrict__ scores) {
-    const int r = blockIdx.x, u = users[r];
-    const long long o = off[u];
-    const int half = (int)(off[u + 1] - o) / 2;
-    const int start = mode == SBR_EVAL_EXCL_VIEWED ? 0 : half - min(T, half);
-    const float value = mode == SBR_EVAL_EXCL_WINDOW_ZERO ? 0.0f : -INFINITY;
-    float* row = scores + (size_t)r * N;
-    for (int t = start + threadIdx.x; t < half; t += blockDim.x) {
-        const int id = items[o + t];
-        if ((unsigned)id < (unsigned)N) row[id] = value;
-    }
 }
 
 constexpr int kHitThreads = 256;
@@ -63,7 +47,8 @@ __global__ void __launch_bounds__(kHitThreads) ev_hits_kernel(const int* __restr
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int u = users[r];
     const long long o = off[u];
-    const int L = (int)(off[u + 1] - o), half = L / 2, ng = L - half;
+    const UserSplit sp(o, off[u + 1], 0);                          // (no window here)
+    const int half = sp.half, ng = sp.goal_len();
     const int* g = goal + o + half;
     const int first = items[o + half];                             // goal[0] of the sequence as it is, not of the sorted copy
     const int* irow = ids + (size_t)r * k;
@@ -122,8 +107,9 @@ __global__ void __launch_bounds__(kRankThreads) ev_goal_rank_kernel(const int* _
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int u = users[r];
     const long long o = off[u];
-    const int L = (int)(off[u + 1] - o), half = L / 2, ng = L - half;
-    const int* g = items + o + half;                               // the goal in sequence order
+    const UserSplit sp(o, off[u + 1], 0);                          // (no window here)
+    const int ng = sp.goal_len();
+    const int* g = items + o + sp.half;                            // the goal in sequence order
     int* out = ranks + goal_off[r];
     const float* row = scores + (size_t)r * N;
     if (tid == 0) nrk[0] = 0;
@@ -207,12 +193,6 @@ __global__ void __launch_bounds__(kRankThreads) ev_goal_rank_kernel(const int* _
 hipError_t launch_ev_pack(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop) {
     if (Bp <= 0) return hipSuccess;
     ev_pack_kernel<<<Bp, 64, 0, s>>>(v.items, v.rate, v.off, users, v.n_items, rows, T, F, X, lengths, pop);
-    return hipGetLastError();
-}
-
-hipError_t launch_ev_exclude(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int T, int N, int mode, float* scores) {
-    if (rows <= 0 || mode == SBR_EVAL_EXCL_NONE) return hipSuccess;
-    ev_exclude_kernel<<<rows, 256, 0, s>>>(v.items, v.off, users, T, N, mode, scores);
     return hipGetLastError();
 }
 

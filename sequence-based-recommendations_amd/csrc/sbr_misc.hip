@@ -2004,59 +2004,6 @@ hipError_t launch_update(hipStream_t s, int updater, float* p, float* g, float* 
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------------------------------
-// K14 test path: exclude seen items, ordered top-k (rnn_base.py:196-211)
-// ---------------------------------------------------------------------------------------
-__global__ void exclude_seen_kernel(float* __restrict__ scores, const int* __restrict__ X, const int* __restrict__ len,
-                                    int rows, int T, int F, int N, float value) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= rows * T) return;
-    const int r = i / T, t = i % T;
-    if (t < len[r]) scores[(size_t)r * N + X[((size_t)r * T + t) * F]] = value;   // exclude[i, item ids] = 1
-}
-hipError_t launch_exclude_seen(hipStream_t s, float* scores, const int* X, const int* len, int rows, int T, int F, int N, float value) {
-    if (rows <= 0) return hipSuccess;
-    exclude_seen_kernel<<<(rows * T + 255) / 256, 256, 0, s>>>(scores, X, len, rows, T, F, N, value);
-    return hipGetLastError();
-}
-
-// k rounds of arg-max per row; ties -> lowest id; destroys the row (winners set to -inf).  Only finite scores and +inf are
-// candidates (NaN never wins a comparison and -inf is an excluded or already emitted item): when a row runs out of
-// candidates -- a user who has seen more than N - k items with exclude_seen, or NaN scores -- the remaining places are
-// filled with -1 instead of re-emitting an excluded id or an out-of-range one.
-__global__ void __launch_bounds__(256) topk_kernel(float* __restrict__ scores, int N, int k, int* __restrict__ ids) {
-    __shared__ float rv[4];
-    __shared__ int ri[4];
-    float* x = scores + (size_t)blockIdx.x * N;
-    for (int it = 0; it < k; ++it) {
-        float bv = -INFINITY; int bi = 0x7fffffff;
-        for (int n = threadIdx.x; n < N; n += 256) {
-            const float v = x[n];
-            if (v > bv || (v == bv && n < bi && v > -INFINITY)) { bv = v; bi = n; }
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float ov = __shfl_xor(bv, o); const int oi = __shfl_xor(bi, o);
-            if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-        }
-        __syncthreads();
-        if ((threadIdx.x & 63) == 0) { rv[threadIdx.x >> 6] = bv; ri[threadIdx.x >> 6] = bi; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int w = 1; w < 4; ++w)
-                if (rv[w] > bv || (rv[w] == bv && ri[w] < bi)) { bv = rv[w]; bi = ri[w]; }
-            ids[(size_t)blockIdx.x * k + it] = bi < N ? bi : -1;
-            if (bi < N) x[bi] = -INFINITY;
-        }
-        __syncthreads();
-    }
-}
-hipError_t launch_topk(hipStream_t s, float* scores, int rows, int N, int k, int* ids) {
-    if (rows <= 0) return hipSuccess;
-    topk_kernel<<<rows, 256, 0, s>>>(scores, N, k, ids);
-    return hipGetLastError();
-}
-
 __global__ void fill_kernel(float* p, float v, size_t n) {
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }

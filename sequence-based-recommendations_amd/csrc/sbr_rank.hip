@@ -1,8 +1,9 @@
-// sbr_rank: ordered top-k of ANY depth with per-row exclusion lists (include/sbr_rnn.h; the batched form of
-// top_k_recommendations, rnn_base.py:140-165, whose exclude= list and k the arg-max passes of topk_kernel cannot serve).
+// The kernels of every ranking call (include/sbr_rnn.h: sbr_topk, sbr_rank, sbr_evaluate, sbr_cluster_rank, sbr_cluster_evaluate):
+// ordered top-k of ANY depth with per-row exclusion (the batched form of top_k_recommendations, rnn_base.py:140-165).
 //
 // A row is read a bounded number of times, whatever k is:
-//   1. rank_exclude_kernel   -inf into the row at the ids of its CSR list and, when asked, of its input window
+//   1. exclude_kernel        the row's excluded ids -- whatever list, window or dataset names them -- leave a catalogue row or a
+//                            compact cluster row (sources, sinks and the visiting loop: sbr_device.h)
 //   2. rank_select_kernel    radix select of the k-th largest KEY (three digits: 11 + 11 + 10 bits, one LDS histogram each), then
 //                            an ordered compaction: every candidate above that key, and the lowest ids among those equal to it
 //                            until k is reached, leave the row IN ID ORDER -- which is the order equal keys must keep
@@ -10,9 +11,10 @@
 // One workgroup of kRankThreads threads per row in every kernel: rows are independent, nothing waits on another workgroup.
 //
 // KEY: the order-preserving 32-bit image of a score -- sign-flip transform of the float's bits, -0.0 canonicalised to +0.0 (the
-// two compare equal in topk_kernel, so they must tie here), NaN and -inf (never ranked: an excluded or unusable item) mapped to
+// two compare equal as floats, so they must tie here), NaN and -inf (never ranked: an excluded or unusable item) mapped to
 // 0, below every candidate (the smallest candidate, -FLT_MAX, has key 0x00800000).
 #include "sbr_common.h"
+#include "sbr_device.h"
 #include <math.h>
 
 namespace {
@@ -36,24 +38,8 @@ __device__ __forceinline__ unsigned block_incl_scan(unsigned v, unsigned* ws) {
     return v + base;
 }
 
-__global__ void __launch_bounds__(256) rank_exclude_kernel(float* __restrict__ scores, int N, const int* __restrict__ excl_ids,
-                                                           const long long* __restrict__ excl_off, const int* __restrict__ X,
-                                                           const int* __restrict__ len, int T, int F) {
-    const int r = blockIdx.x;
-    float* row = scores + (size_t)r * N;
-    if (excl_off)
-        for (long long j = excl_off[r] + threadIdx.x; j < excl_off[r + 1]; j += blockDim.x) {
-            const int id = excl_ids[j];
-            if ((unsigned)id < (unsigned)N) row[id] = -INFINITY;
-        }
-    if (X) {
-        const int L = min(len[r], T);
-        for (int t = threadIdx.x; t < L; t += blockDim.x) {
-            const int id = X[((size_t)r * T + t) * F];
-            if ((unsigned)id < (unsigned)N) row[id] = -INFINITY;
-        }
-    }
-}
+template <class Sink>
+__global__ void __launch_bounds__(256) exclude_kernel(ExclSources src, Sink to) { to.exclude_row(src, blockIdx.x); }
 
 // LDSROW: the row's keys are computed once into LDS and every pass reads them there (N <= kRankLdsRow); otherwise every pass
 // streams the row from memory (one read per pass: 3 digits, the per-wave counts, the compaction).
@@ -244,12 +230,14 @@ __global__ void __launch_bounds__(kRankThreads) rank_sort_radix_kernel(const flo
 
 }  // namespace
 
-hipError_t launch_rank_exclude(hipStream_t s, float* scores, int rows, int N, const int* excl_ids, const long long* excl_off,
-                               const int* X, const int* len, int T, int F) {
-    if (rows <= 0 || (!excl_off && !X)) return hipSuccess;
-    rank_exclude_kernel<<<rows, 256, 0, s>>>(scores, N, excl_ids, excl_off, X, len, T, F);
+template <class Sink>
+hipError_t launch_exclude(hipStream_t s, int rows, const ExclSources& src, const Sink& to) {
+    if (rows <= 0 || !src.any()) return hipSuccess;
+    exclude_kernel<<<rows, 256, 0, s>>>(src, to);
     return hipGetLastError();
 }
+template hipError_t launch_exclude<ExclCatalogue>(hipStream_t, int, const ExclSources&, const ExclCatalogue&);
+template hipError_t launch_exclude<ExclCluster>(hipStream_t, int, const ExclSources&, const ExclCluster&);
 
 hipError_t launch_rank_select(hipStream_t s, const float* scores, int rows, int N, int k, unsigned* keys, int* ids, int* n_sel, int* select) {
     *select = N <= kRankLdsRow ? 1 : 2;

@@ -1,8 +1,11 @@
-// The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_rank, sbr_evaluate, sbr_evaluate_ranks, sbr_cluster_rank,
-// sbr_cluster_evaluate.
+// The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_topk, sbr_rank, sbr_evaluate, sbr_evaluate_ranks,
+// sbr_cluster_rank, sbr_cluster_evaluate.
 // Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_cluster_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
-// sbr_api.hip), built from the shared pieces below.  Every call waits for the device once, in check_fault.
+// sbr_api.hip), built from the shared pieces below: scores, ONE exclusion launch per ranking (launch_exclude: what
+// is excluded is an ExclSources, where it lands an ExclCatalogue or ExclCluster, sbr_device.h), select and sort (rank_rows).
+// Every call waits for the device once, in check_fault.
 #include "sbr_common.h"
+#include "sbr_device.h"
 #include <algorithm>
 
 // The scratch of these calls -- the device copies of the lists, the selected (key, id) pairs, the radix sort's second pair, the
@@ -79,11 +82,53 @@ static int excl_upload(sbr_handle* h, char* S, const ExclLists& x) {
     return SBR_OK;
 }
 
+// what sbr_rank and sbr_cluster_rank exclude from a row: its uploaded list and, when asked, its input window
+static ExclSources excl_sources(const sbr_handle* h, const char* S, const ExclLists& x, int exclude_input) {
+    ExclSources src;
+    src.lists(x.dev_ids(S), x.dev_off(S));
+    if (exclude_input) src.window(h->bX, h->blen, h->lay.T, h->lay.F);
+    return src;
+}
+
 // the hidden state of the current batch with every output row current: full_scores minus its projection
 int forward_current(sbr_handle* h) {
     int rc;
     if (!h->fwd_done && (rc = sbr_forward(h)) != SBR_OK) return rc;
     return flush_lazy(h, 1);      // the sampled heads step W_out^T / b_out rows lazily: every row that is scored must be current
+}
+
+// The compiled test function's ranking (rnn_base.py:196-211), the oldest call: a second entry to sbr_rank's pipeline with its own
+// contract -- k <= 64, the result in the arena's a_topk (the Layout keeps the buffer, so every arena offset is what it was), and
+// exclude_seen in place of the lists.  Softmax is monotone: ranking the biased logits == ranking softmax(logits) * (1 - exclude)
+// (:200-207) whenever at least k items are not excluded.
+// Against the k arg-max passes this call used to run, the ids are the same (tests/test_gpu_rank.py) and three things differ: the
+// score row is no longer overwritten with -inf at the winners; an id outside [0, N) in a device-resident batch is skipped where it
+// used to be written through; and sbr_query "rank_select" / "rank_sort" now also tell what an sbr_topk call ran.
+extern "C" int sbr_topk(sbr_handle* h, int k, int exclude_seen, int32_t* ids_host) {
+    CHECK_ARG(h && ids_host, "null argument");
+    if (!h->have_batch) { sbr_set_error("sbr_topk: no batch set"); return SBR_ESTATE; }
+    const Layout& y = h->lay;
+    const int rows = h->n_rows;
+    CHECK_ARG(k >= 1 && k <= 64 && k <= y.N, "k=%d outside [1,min(64,N)]", k);
+    Carver cv;
+    const RankWork w = carve_rank_work(cv, rows, k, k > kRankSortLds);
+    const size_t o_osc = cv.take((size_t)rows * k * sizeof(float));
+    int rc;
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    if ((rc = full_scores(h, 0)) != SBR_OK) return rc;
+    float* lg = h->A(y.a_logits);
+    // exclude_seen 1: viewed items can never be ranked (top_k_recommendations, rnn_base.py:154-155); 2: the compiled test
+    // function's scores * (1 - exclude) (:201-202) -- the same ranking for probabilities, NOT for RNNMargin's raw outputs,
+    // where a viewed item then scores 0 and outranks every negative one
+    ExclSources seen;
+    if (exclude_seen) seen.window(h->bX, h->blen, y.T, y.F);
+    const float value = (exclude_seen == 2 && SBR_LOSS_IS_MARGIN(y.cfg.loss)) ? 0.0f : -INFINITY;
+    SBR_LAUNCH(launch_exclude(h->stream, rows, seen, ExclCatalogue{lg, y.N, value}));
+    int* ids = (int*)h->A(y.a_topk);
+    if ((rc = rank_rows(h, S, w, lg, rows, y.N, k, ids, (float*)(S + o_osc))) != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(ids_host, ids, (size_t)rows * k * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    return check_fault(h);          // a forward that gave up must not hand out rankings (test.py, validation)
 }
 
 // Ordered top-k of any depth with per-row exclusion lists (top_k_recommendations' k and exclude=, rnn_base.py:140-165, for a
@@ -108,7 +153,7 @@ extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* 
     if ((rc = full_scores(h, 0)) != SBR_OK) return rc;      // the very floats sbr_topk ranks (and flushes lazily stepped rows)
     float* lg = h->A(y.a_logits);
     if ((rc = excl_upload(h, S, x)) != SBR_OK) return rc;
-    SBR_LAUNCH(launch_rank_exclude(h->stream, lg, rows, y.N, x.dev_ids(S), x.dev_off(S), exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
+    SBR_LAUNCH(launch_exclude(h->stream, rows, excl_sources(h, S, x, exclude_input), ExclCatalogue{lg, y.N, -INFINITY}));
     if ((rc = rank_rows(h, S, w, lg, rows, y.N, k, (int*)(S + o_oid), (float*)(S + o_osc))) != SBR_OK) return rc;
     SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
     if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
@@ -146,6 +191,11 @@ static int eval_pack_chunk(sbr_handle* h, const SbrEvalView& v, const int* duser
     return SBR_OK;
 }
 
+// where an evaluation's exclusion lands in the whole-catalogue scores: WINDOW_ZERO scores the items fed 0.0 and keeps them rankable
+static ExclCatalogue eval_sink(float* scores, int N, int exclude_mode) {
+    return ExclCatalogue{scores, N, exclude_mode == SBR_EVAL_EXCL_WINDOW_ZERO ? 0.0f : -INFINITY};
+}
+
 // The chunk loop of the whole-catalogue evaluations: local_batch users at a time are packed, scored (the very floats sbr_rank ranks;
 // lazily stepped rows are flushed) and excluded from the dataset's CSR, then `ranked(c0, rows, scores)` enqueues what the call makes of
 // the chunk's score rows.  Everything on the main stream, no host wait.
@@ -158,7 +208,7 @@ static int eval_chunks(sbr_handle* h, const SbrEvalView& v, const int* dusers, i
         if ((rc = eval_pack_chunk(h, v, dusers + c0, rows)) != SBR_OK) return rc;
         if ((rc = full_scores(h, 0)) != SBR_OK) return rc;
         float* lg = h->A(y.a_logits);
-        SBR_LAUNCH(launch_ev_exclude(h->stream, v, dusers + c0, rows, y.T, y.N, exclude_mode, lg));
+        SBR_LAUNCH(launch_exclude(h->stream, rows, ExclSources().dataset(v, dusers + c0, y.T, exclude_mode), eval_sink(lg, y.N, exclude_mode)));
         if ((rc = ranked(c0, rows, lg)) != SBR_OK) return rc;
     }
     return SBR_OK;
@@ -254,10 +304,11 @@ extern "C" int sbr_evaluate_ranks(sbr_handle* h, sbr_dataset* d, const int32_t* 
     int rc;
     if ((rc = eval_check_args(h, d, users, n, 1, v)) != SBR_OK) return rc;      // (no k here: 1 is inside every catalogue)
     int64_t total = 0;
-    for (int64_t j = 0; j < n; ++j) { const int64_t L = v.h_off[users[j] + 1] - v.h_off[users[j]]; total += L - L / 2; }
+    auto goal_len = [&](int64_t j) -> int64_t { return UserSplit(v.h_off[users[j]], v.h_off[users[j] + 1], y.T).goal_len(); };
+    for (int64_t j = 0; j < n; ++j) total += goal_len(j);
     CHECK_ARG(cap >= total, "cap=%lld: the goals of these users hold %lld items", (long long)cap, (long long)total);
     goal_off_host[0] = 0;
-    for (int64_t j = 0; j < n; ++j) { const int64_t L = v.h_off[users[j] + 1] - v.h_off[users[j]]; goal_off_host[j + 1] = goal_off_host[j] + (L - L / 2); }
+    for (int64_t j = 0; j < n; ++j) goal_off_host[j + 1] = goal_off_host[j] + goal_len(j);
     Carver cv;
     const size_t o_users = cv.take((size_t)n * sizeof(int)), o_goff = cv.take((size_t)(n + 1) * sizeof(long long));
     const size_t o_ranks = cv.take((size_t)total * sizeof(int)), o_nrk = cv.take((size_t)n * sizeof(int));
@@ -364,8 +415,7 @@ extern "C" int sbr_cluster_rank(sbr_cluster* c, sbr_handle* h, int k, int exclud
     if ((rc = excl_upload(h, S, x)) != SBR_OK) return rc;
     if ((rc = sbr_cluster_select(c, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, rows, csel, nullptr)) != SBR_OK) return rc;
     if ((rc = cluster_scores(c, h, S, o_grp, csel, rows, lmax, cs, restricted)) != SBR_OK) return rc;
-    SBR_LAUNCH(launch_crk_exclude(h->stream, cs, lmax, csel, c->mem_ids, c->mem_off, rows, y.N, x.dev_ids(S), x.dev_off(S),
-                                  exclude_input ? h->bX : nullptr, h->blen, y.T, y.F));
+    SBR_LAUNCH(launch_exclude(h->stream, rows, excl_sources(h, S, x, exclude_input), ExclCluster{cs, lmax, csel, C, c->mem_ids, c->mem_off, y.N}));
     if ((rc = rank_rows(h, S, w, cs, rows, lmax, kk, (int*)(S + o_pos), (float*)(S + o_psc))) != SBR_OK) return rc;
     SBR_LAUNCH(launch_crk_translate(h->stream, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
                                     (int*)(S + o_oid), (float*)(S + o_osc), (int*)(S + o_size)));
@@ -445,7 +495,7 @@ extern "C" int sbr_cluster_evaluate(sbr_cluster* c, sbr_handle* h, sbr_dataset* 
         // --- the whole-catalogue ranking of the same forward pass: sbr_evaluate's chunk
         if (whole) {
             int* oid = rw.ids_at(S, c0);
-            SBR_LAUNCH(launch_ev_exclude(s, v, cu, rows, y.T, N, whole_mode, lg));
+            SBR_LAUNCH(launch_exclude(s, rows, ExclSources().dataset(v, cu, y.T, whole_mode), eval_sink(lg, N, whole_mode)));
             if ((rc = rank_rows(h, S, w, lg, rows, N, k, oid, osc)) != SBR_OK) return rc;
             if ((rc = launch_hits(h, S, rw, v, dusers, c0, rows, oid)) != SBR_OK) return rc;
         }
@@ -454,7 +504,7 @@ extern "C" int sbr_cluster_evaluate(sbr_cluster* c, sbr_handle* h, sbr_dataset* 
         if (product) {
             if ((rc = rank_rows(h, S, w, cs, rows, N, k, oid, osc)) != SBR_OK) return rc;
         } else {
-            SBR_LAUNCH(launch_cev_exclude(s, v, cu, rows, y.T, N, exclude_mode, cs, lmax, csel, C, c->mem_ids, c->mem_off));
+            SBR_LAUNCH(launch_exclude(s, rows, ExclSources().dataset(v, cu, y.T, exclude_mode), ExclCluster{cs, lmax, csel, C, c->mem_ids, c->mem_off, N}));
             if ((rc = rank_rows(h, S, w, cs, rows, lmax, kk, (int*)(S + o_pos), (float*)(S + o_psc))) != SBR_OK) return rc;
             SBR_LAUNCH(launch_crk_translate(s, (const int*)(S + o_pos), (const float*)(S + o_psc), kk, k, csel, c->mem_ids, c->mem_off, rows,
                                             oid, osc, (int*)(S + o_size) + c0));

@@ -106,6 +106,52 @@ def test_same_ids_as_topk_when_a_row_runs_out():
         eng.close()
 
 
+def test_window_longer_than_the_exclusion_workgroup():
+    # T = 300 > 256 threads: the window loop of the shared exclusion strides, and so does the list loop on a 300-id list.  Row 0 is
+    # full length (make_batch); its list holds its whole window, so window and list together exclude exactly 300 of the 400 items
+    # and every row keeps at least 100 rankable ones: no place is -1.
+    N, B, T = 400, 3, 300
+    eng, _, batch = make_engine("GRU", [8], "TOP1", N, B, T, S=8, seed=11)
+    try:
+        assert int(batch["mask"][0].sum()) == T > 256
+        scores = eng.predict_function(batch["X"], batch["mask"])      # raw activations: the floats that are ranked
+        seen0 = sorted(set(window(batch, 0)))
+        rest = np.setdiff1d(np.arange(N), seen0)
+        lists = [np.random.default_rng(11).permutation(np.concatenate([seen0, rest[:300 - len(seen0)]])).astype(np.int32), None, None]
+        assert len(lists[0]) == 300 == len(set(lists[0].tolist()) | set(seen0))
+        for k in (1, 5, 64):
+            for excl in (False, True):
+                ids = eng.test_function((batch["X"], batch["mask"]), k=k, exclude_seen=excl)
+                for b in range(B):
+                    ei, _ = expected_row(scores[b], window(batch, b) if excl else [], k)
+                    assert np.array_equal(ids[b], ei) and (ei >= 0).all(), (k, excl, b, ids[b][:8], ei[:8])
+            ids, _ = check_rank(eng, batch, scores, k, lists=lists, exclude_input=True, N=N)
+            assert (ids >= 0).all()
+    finally:
+        eng.close()
+
+
+def test_topk_modes_on_a_margin_head():
+    # exclude_seen 2 on a margin loss is the one exclusion VALUE that is not -inf: the window items score +0.0 and stay rankable
+    # (the compiled test function's scores * (1 - exclude) on raw outputs).  predict_function hands back hinge's raw outputs.
+    N, B, T, S = 60, 9, 8, 3
+    eng, _, batch = make_engine("GRU", [20], "hinge", N, B, T, S=S, seed=12)
+    try:
+        scores = eng.predict_function(batch["X"], batch["mask"])
+        assert (scores < 0).any() and (scores > 0).any()              # 0.0 lands inside the range of the scores
+        for k in (1, 5, 60):
+            for mode in (0, 1, 2):
+                ids = eng.test_function((batch["X"], batch["mask"]), k=k, exclude_seen=mode)
+                for b in range(B):
+                    row = scores[b].copy()
+                    if mode == 2:
+                        row[window(batch, b)] = 0.0
+                    ei, _ = expected_row(row, window(batch, b) if mode == 1 else [], k)
+                    assert np.array_equal(ids[b], ei), (k, mode, b, ids[b][:8], ei[:8])
+    finally:
+        eng.close()
+
+
 # ------------------------------------------------------------------ 2. exact ranking beyond 64
 DEEP_CASES = [("LSTM", [20], "Blackout", 1000, 5, 6, 8), ("GRU", [16], "TOP1", 3706, 5, 4, 8), ("GRU", [8], "TOP1", 70001, 3, 2, 8)]
 

@@ -1,12 +1,15 @@
-"""Times sbr_topk (k arg-max passes over the row, k <= 64) against sbr_rank (radix select + sort, any k) on ONE engine in one
-process, the two calls interleaved region by region:  python tools/rank_bench.py [--out profiles/rank_bench.json]
+"""Times the two entries to the one ranking pipeline (exclusion, radix select, sort) -- sbr_topk (k <= 64, the result through the
+arena) and sbr_rank (any k, per-row lists, the result through the ranking scratch) -- on ONE engine in one process, the two calls
+interleaved region by region:  python tools/rank_bench.py [--out profiles/rank_bench.json]
+(profiles/rank_bench.json itself is the record of sbr_topk's former k arg-max passes against sbr_rank; the same tool wrote it.)
 
 Per catalogue size N (3 706 and 100 000 by default) and B = 256 rows: both calls at k = 10 and k = 64 -- their ids are compared
 first, a timing of different answers is worth nothing --, then sbr_rank alone at k = 1000 and k = N.  A timed region is `--calls`
 calls on the batch already set (each ends in a stream synchronise inside the library: host clock around device work that
-ended); both calls score the rows with the same exact-f32 projection first, so the difference is the ranking.  Reported per
-case: the median over `--regions` regions (after `--warmup` untimed ones) of the time per call, and the regions' min / max as
-the run-to-run spread.  Needs the GPU; run it under a time limit of its own (a few minutes)."""
+ended); both calls score the rows with the same exact-f32 projection first, so what is left between them is the entry's own
+overhead ("entry_ratio": sbr_rank over sbr_topk, 1.0 up to the spread).  Reported per case: the median over `--regions` regions
+(after `--warmup` untimed ones) of the time per call, and the regions' min / max as the run-to-run spread.  Needs the GPU; run it
+under a time limit of its own (a few minutes)."""
 import argparse
 import ctypes
 import json
@@ -69,7 +72,7 @@ def main(argv=None):
                 case[name] = dict(median=float(np.median(ts)), min=float(min(ts)), max=float(max(ts)))
             if k <= 64:
                 case["ids_equal"] = same
-                case["rank_over_topk"] = case["sbr_rank"]["median"] / case["sbr_topk"]["median"]
+                case["entry_ratio"] =case["sbr_rank"]["median"] / case["sbr_topk"]["median"]
             out["cases"].append(case)
             print(json.dumps(case), flush=True)
         eng.close()
