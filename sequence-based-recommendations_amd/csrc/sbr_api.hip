@@ -402,6 +402,7 @@ extern "C" int sbr_create(const sbr_config* cfg, void* arena, size_t arena_bytes
     // 922k at 4 (two rounds) / 1047k at 16; B=4096 1380k at 16 vs 1124k at 8)
     h->rpt = sw.rpt;
     if (h->rpt != 1 && h->rpt != 2 && h->rpt != 4 && h->rpt != 8 && h->rpt != 16) { h->rpt = 4; while (h->rpt < 16 && h->lay.Bp / h->rpt > 256) h->rpt <<= 1; }
+    plan_layers(h);      // every layer's recurrent kernel: the layout, the switches, the flags and rpt are all it depends on
     if (sw.tail_trace) {      // tools/tail_trace.py
         if (hipMalloc(&h->tail_trace, 16384 * sizeof(unsigned long long)) != hipSuccess) h->tail_trace = nullptr;
         else (void)hipMemset(h->tail_trace, 0, 16384 * sizeof(unsigned long long));
@@ -902,10 +903,9 @@ extern "C" int sbr_debug_scatter(sbr_handle* h, int reps, float* us, int64_t* en
 extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     CHECK_ARG(h && what && value, "null argument");
     const Layout& y = h->lay; const std::string w(what);
-    if (w == "fused_gather") {
-        RecArgs a = rec_args(h, 0);
-        *value = (y.E == 0 && y.F == 1 && h->sw.fuse_gather && sbr_rec_fwd_can_fuse_gather(a, simple_rec(h))) ? 1 : 0;
-    } else if (w == "rows_per_workgroup") *value = h->rpt;
+    const RecPlan& top = h->plan[(y.L - 1) * y.D];      // the kernel-family keys speak of the TOP layer (RecPlan, sbr_common.h)
+    if (w == "fused_gather") *value = h->plan[0].fuse_gather ? 1 : 0;
+    else if (w == "rows_per_workgroup") *value = h->rpt;
     else if (w == "head_fused") {      // would a full batch of a training step take the one-launch head (sbr_head.hip)?  (its column chunks, or 0)
         int cc = 0, cw = 0; size_t lds = 0;
         *value = (h->sw.head_fuse && y.cfg.loss == SBR_LOSS_CCE && !simple_gemm(h) && !(y.cfg.flags & (SBR_FLAG_BF16_PROJECTION | SBR_FLAG_F32_MFMA)) &&
@@ -927,28 +927,15 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "goal_rank_form") *value = h->last_goal_rank_form;
     else if (w == "goal_rank_tile") *value = kGoalRankTile;
     else if (w == "row_aware_update") *value = h->last_row_aware ? 1 : 0;      // ... and whether its optimizer pass over W_in was the row-aware one
-    else if (w == "cluster") { RecArgs a = rec_args(h, (y.L - 1) * y.D); *value = (!simple_rec(h) && sbr_rec_cluster_ok(a)) ? 1 : 0; }
-    else if (w == "rec_kernel") {   // family serving the top layer: 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other
-        RecArgs a = rec_args(h, (y.L - 1) * y.D);
-        *value = simple_rec(h) ? 0 : sbr_rec_cluster_ok(a) ? 1 : sbr_rec_x6p_ok(a) ? 2 : sbr_rec_x6q_ok(a) ? 3 : 4;
-    }
+    else if (w == "cluster") *value = top.needs_fill ? 1 : 0;      // the cluster kernels (the family that wants the sentinel fill)
+    else if (w == "rec_kernel") *value = top.family;               // 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other
     else if (w.rfind("rec_products_", 0) == 0 || w.rfind("rec_rows_", 0) == 0 || w.rfind("rec_workgroups_", 0) == 0) {
-        // what the recurrent kernel of the TOP layer issues on the matrix pipe (bench.py: roofline.matrix_pipe / active_cus):
+        // what the recurrent kernel of the top layer issues on the matrix pipe (bench.py: roofline.matrix_pipe / active_cus):
         // products = low-precision MFMA terms per f32 product (bf16x6: 6, fp16x3: 3; 0 = the exact-f32 MFMA kernels, another
         // pipe rate); rows = live batch rows among the 16 columns of an MFMA tile; workgroups = workgroups of the launch
         const bool bwd = w.size() > 4 && w.compare(w.size() - 4, 4, "_bwd") == 0;
-        RecArgs a = rec_args(h, (y.L - 1) * y.D);
-        const bool cl = !simple_rec(h) && sbr_rec_cluster_ok(a), xp = sbr_rec_x6p_ok(a), xq = sbr_rec_x6q_ok(a);
-        const bool x6 = cl || xp || xq || (!a.f32_mfma && (a.Hp == 32 || a.Hp == 64 || a.Hp == 128));
-        int products = 0, rows = 16, wgs = y.Bp / 16;
-        if (!simple_rec(h) && x6) {
-            const bool f16 = (xp || cl || xq) && (bwd ? sbr_rec_f16_bwd(a) : sbr_rec_f16_fwd(a));
-            products = f16 ? (xp && !cl ? sbr_rec_x6p_f16_terms() : 3) : 6;
-            if (cl && sbr_rec_c16_ok(a)) { rows = 16; wgs = (y.Bp / 16) * (a.Hp / 16); }
-            else if (cl) { rows = bwd ? sbr_rec_cluster_bwd_rows(a) : SBR_CL_ROWS; wgs = (y.Bp / rows) * (a.Hp == 256 ? 8 : 32); }
-            else { rows = a.rpt; wgs = y.Bp / a.rpt; }
-        }
-        *value = w.rfind("rec_products_", 0) == 0 ? products : w.rfind("rec_rows_", 0) == 0 ? rows : wgs;
+        *value = w.rfind("rec_products_", 0) == 0 ? (bwd ? top.products_bwd : top.products_fwd)
+               : w.rfind("rec_rows_", 0) == 0 ? (bwd ? top.bwd_rows : top.fwd_rows) : (bwd ? top.bwd_wgs : top.fwd_wgs);
     }
     else if (w == "tail_chunks") { int ch = 0; *value = tail_plan(h, &ch); }      // time chunks of the overlapped step tail (0: not taken)
     // ... whose consumers really run on the side streams (SBR_TAIL_OVERLAP=2 keeps them on the main stream: a data-parallel driver

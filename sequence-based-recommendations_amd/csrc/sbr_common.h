@@ -236,9 +236,27 @@ struct SbrSwitches {
                                  // gathers them from the full score matrix (also the road of the bf16 / triage projections)
 };
 
+// Which recurrent kernel serves a layer, and everything the step and sbr_query derive from that choice.  Every input of the
+// decision is fixed when the engine is created, so sbr_rec_plan (sbr_rec.hip) makes it once per layer, inside sbr_create, and the
+// launchers, the step and the queries read the answer: this is what makes the forward and the backward launch of a step agree on the
+// layout of the saved activations they share.
+enum RecKernel { REC_TRIAGE, REC_C16, REC_CL8, REC_X6P, REC_X6Q, REC_X6S, REC_X6, REC_MFMA };
+struct RecPlan {
+    RecKernel fwd, bwd;          // what launch_rec_forward / launch_rec_backward run
+    int family;                  // sbr_query "rec_kernel": 0 triage, 1 cluster, 2 x6p, 3 x6q, 4 other
+    int fwd_rows, bwd_rows, fwd_wgs, bwd_wgs, products_fwd, products_bwd;   // sbr_query "rec_rows_*" / "rec_workgroups_*" / "rec_products_*"
+    int bwd_blocks;              // part[] blocks the backward launch writes
+    bool bwd_chunkable;          // the backward launch honours RecArgs.t_lo / t_hi / chunk (bf16x6 kernels)
+    bool fuse_gather;            // the forward launch gathers the rows of W_in itself: the step sets RecArgs.gX / gWin / gbias
+    bool tail_ok;                // rec_bwd_x6p's progress-publishing form can serve the layer (overlapped step tail)
+    bool needs_fill;             // cluster kernels: the backward exchange arrays want their sentinel fill (sbr_rec_bwd_cl_fill)
+    size_t fwd_lds, bwd_lds; int bwd_dbuf;   // REC_X6S / REC_X6 / REC_MFMA: dynamic LDS of the launch, the backward's double buffer
+};
+
 struct sbr_handle {
     Layout lay;
     SbrSwitches sw;
+    RecPlan plan[2 * SBR_MAX_LAYERS] = {};   // [l * D + d], like Layout.layer: filled by plan_layers at the end of sbr_create
     float* arena = nullptr; bool own_arena = false;
     hipStream_t stream = nullptr;
     // Priority side streams and disable-timing events: sbr_create / sbr_destroy walk handle_streams() / handle_events() (sbr_api.hip)
@@ -383,8 +401,7 @@ int forward_current(sbr_handle* h);                  // (sbr_rank_api.hip) forwa
 // What the rest of the engine (sbr_api.hip: sbr_query, sbr_zero_grads, the sparse exchange, the debug calls) needs of the training
 // step (sbr_step.hip), and the one layout piece the step takes from there
 struct RecArgs; struct SbrSparseRows; struct SbrSparseUpd;
-RecArgs rec_args(sbr_handle* h, int l);              // layer l's kernel arguments for the current batch; advances the cluster kernels' exchange epoch
-bool simple_rec(const sbr_handle* h);                // SBR_FLAG_SIMPLE_REC: the triage recurrent kernels
+void plan_layers(sbr_handle* h);                     // fills h->plan from the layout, the switches and the flags (sbr_create, once)
 int tail_plan(sbr_handle* h, int* ch_out);           // overlapped step tail: time chunks of a step (0: not taken), steps per chunk; fills h->tail_bounds
 bool head_sampled_taken(const sbr_handle* h, int rows);   // does a step over `rows` rows take the one-launch sampled head?
 void mark(sbr_handle* h, int i);                     // timing mark i of the step in flight, on the main stream
@@ -552,39 +569,36 @@ struct RecArgs {
 };
 // Operand planes of the recurrent chains (128-unit, small-layer and cluster kernels alike): the two-plane fp16 split unless it is
 // switched off or its operand is unbounded -- forward: a rectified state (the split needs |h| < 65504); backward: the operand that
-// carries gradients is bounded by the reference's own gradient clip at +-100.  The forward and the backward launch of a step must
-// agree on the kernel family (they share the saved gates' layout): both values come from the engine's SbrSwitches.
+// carries gradients is bounded by the reference's own gradient clip at +-100.  Both values come from the engine's SbrSwitches.
 static inline bool sbr_rec_f16_fwd(const RecArgs& a) { return a.x6_f16 && !a.relu; }
 static inline bool sbr_rec_f16_bwd(const RecArgs& a) { return a.x6_f16_bwd && a.clip > 0.0f && a.clip <= 100.0f; }
 #define SBR_CL_ROWS 8       // batch rows per cluster tile
 #define SBR_C16_RING 2      // rec_bwd_c16: slots of the ring of partial-sum blocks (blocks carry the lap's parity: sbr_rec_c16.hip)
 #define SBR_X6P_FUSE_MAX_T 4096      // fused gather of rec_fwd_x6p: 4 rows x T row offsets in LDS
-bool sbr_rec_cluster_ok(const RecArgs& a);
-int sbr_rec_cluster_bwd_rows(const RecArgs& a);
-hipError_t launch_rec_forward_cl(hipStream_t s, const RecArgs& a);
-hipError_t launch_rec_backward_cl(hipStream_t s, const RecArgs& a);
-// sbr_rec_p.hip: pipelined bf16x6 kernels for Hp = 128 on 4-row tiles
-bool sbr_rec_x6p_ok(const RecArgs& a);
+// The plan of a layer: `shape` = its RecArgs without the batch (gX null; dh_ext set where a layer above feeds it), simple =
+// SBR_FLAG_SIMPLE_REC, fused = the step would have the forward kernel gather W_in's rows (index input of one id per step, level 0,
+// SbrSwitches.fuse_gather).  Pure host code: no handle, no HIP call.  The only caller of the per-family predicates below, which
+// stay in the files that own their constants.
+RecPlan sbr_rec_plan(const RecArgs& shape, bool simple, bool fused);
+bool sbr_rec_cluster_ok(const RecArgs& a);    // sbr_rec_cl.hip: several workgroups per row tile, Hp = 256 / 512
+bool sbr_rec_c16_ok(const RecArgs& a);        // ... on 16-row tiles (sbr_rec_c16.hip)
+bool sbr_rec_x6p_ok(const RecArgs& a);        // sbr_rec_p.hip: pipelined bf16x6 kernels for Hp = 128 on 4-row tiles
 bool sbr_rec_x6p_fuse_ok(const RecArgs& a);   // ... and its forward kernel can gather the W_in rows itself (never part of sbr_rec_x6p_ok)
-int sbr_rec_x6p_f16_terms();              // MFMAs per f32 product of the x6p kernels' fp16 forms (2: packed planes, sbr_rec_p.hip)
 bool sbr_rec_x6p_tail_ok(const RecArgs& a);   // ... and its backward kernel can publish progress (RecArgs.progress)
+int sbr_rec_x6p_f16_terms();                  // MFMAs per f32 product of the x6p kernels' fp16 forms (2: packed planes, sbr_rec_p.hip)
+bool sbr_rec_x6q_ok(const RecArgs& a);        // sbr_rec_q.hip: the same step loop for Hp = 32 / 64 (one wave per SIMD)
+// The launches: the plan's kernel, taken as given.  The family launchers behind them (sbr_rec_cl.hip, sbr_rec_p.hip, sbr_rec_q.hip)
+// refuse only what their kernels cannot run (hipErrorInvalidValue).
+hipError_t launch_rec_forward(hipStream_t s, const RecArgs& a, const RecPlan& p);
+hipError_t launch_rec_backward(hipStream_t s, const RecArgs& a, const RecPlan& p);
+hipError_t launch_rec_forward_cl(hipStream_t s, const RecArgs& a, bool c16);
+hipError_t launch_rec_backward_cl(hipStream_t s, const RecArgs& a, bool c16);      // (fills the exchange arrays first unless a.sentinel_done)
+hipError_t sbr_rec_bwd_cl_fill(hipStream_t s, const RecArgs& a, bool c16);         // the sentinel fill of the backward exchange arrays
 hipError_t launch_rec_forward_x6p(hipStream_t s, const RecArgs& a);
 hipError_t launch_rec_backward_x6p(hipStream_t s, const RecArgs& a);
-// sbr_rec_q.hip: the same step loop for Hp = 32 / 64 (one wave per SIMD)
-bool sbr_rec_x6q_ok(const RecArgs& a);
 hipError_t launch_rec_forward_x6q(hipStream_t s, const RecArgs& a);
 hipError_t launch_rec_backward_x6q(hipStream_t s, const RecArgs& a);
-hipError_t sbr_rec_bwd_cl_fill(hipStream_t s, const RecArgs& a);
-bool sbr_rec_c16_ok(const RecArgs& a);
 size_t sbr_rec_c16_ring_floats(int Bp, int Hp);
-hipError_t launch_rec_forward(hipStream_t s, const RecArgs& a, bool simple);
-// true when the forward launch for these args can gather its input rows itself (RecArgs.gX/gWin/gbias)
-bool sbr_rec_fwd_can_fuse_gather(const RecArgs& a, bool simple);
-hipError_t launch_rec_backward(hipStream_t s, const RecArgs& a, bool simple);
-// number of part[] blocks the backward launch for these args writes
-int sbr_rec_bwd_blocks(const RecArgs& a, bool simple);
-// true when the backward launch honours RecArgs.t_lo/t_hi/chunk (bf16x6 kernels)
-bool sbr_rec_bwd_chunkable(const RecArgs& a, bool simple);
 // sums the per-workgroup partials into bias / peephole / init gradients
 hipError_t launch_rec_reduce_partials(hipStream_t s, const float* part, int nblk, int G, int Hp, int cell,
                                       float* db, float* dpeep, float* dcinit, float* dhinit);

@@ -224,15 +224,6 @@ __global__ void __launch_bounds__(SCAT_BLOCK) scat_fill_lds_kernel(const int* __
     }
 }
 
-__global__ void scat_count_kernel(const int* __restrict__ X, const int* __restrict__ len, int T, int Bp, int F,
-                                  int* __restrict__ cnt) {
-    const int total = T * Bp * F;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int f = i % F, pos = i / F, b = pos % Bp, t = pos / Bp;
-        if (t < len[b]) atomicAdd(&cnt[X[((size_t)b * T + t) * F + f]], 1);
-    }
-}
-
 // exclusive scan of cnt[0..n) -> offs[0..n], offs[n] = total; cur = copy of offs (fill cursors); one workgroup.
 // LDS (n <= SCAT_LDS_IDS, e.g. the ~30 k keys of the time-chunked sort): the counters are staged in LDS with coalesced loads,
 // every thread sums a contiguous run of ceil(n / 1024) of them, the 1024 run sums are scanned across the block once, every
@@ -347,22 +338,9 @@ __global__ void __launch_bounds__(1024) scat_scan_add_kernel(const int* __restri
         if (i0 + k < n) { const int v = offs[i0 + k] + carry; offs[i0 + k] = v; cur[i0 + k] = v; }
 }
 
-__global__ void scat_fill_kernel(const int* __restrict__ X, const int* __restrict__ len, int T, int Bp, int F,
-                                 int* __restrict__ cur, int* __restrict__ sid, int* __restrict__ spos, int concat) {
-    const int total = T * Bp * F;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int f = i % F, pos = i / F, b = pos % Bp, t = pos / Bp;
-        if (t < len[b]) {
-            const int id = X[((size_t)b * T + t) * F + f];
-            const int slot = atomicAdd(&cur[id], 1);
-            sid[slot] = id; spos[slot] = concat ? i : pos;
-        }
-    }
-}
-
 // The counting sort of catalogues beyond the LDS histogram, round 6: one global atomic per DISTINCT id of a workgroup's 1 024 entries
-// instead of one per entry.  The two kernels above send every entry's atomic to cnt[id] / cur[id]; atomics on one address serialise at
-// its L2 channel, and a step's hottest id holds thousands of its 51 200 entries (C5's batch: 3 612) -- ~50 us per kernel, all of it the
+// instead of one per entry.  The kernels this replaced sent every entry's atomic to cnt[id] / cur[id]; atomics on one address serialise
+// at its L2 channel, and a step's hottest id holds thousands of its 51 200 entries (C5's batch: 3 612) -- ~50 us per kernel, all of it the
 // hot counters, beside the head whose loads wait behind them (profiles/round6_variants.txt, calls s3 / a2).  Here a workgroup first
 // groups its entries in an LDS hash table (id -> count; LDS atomics), then adds each distinct id's count once; the fill takes a base slot
 // per distinct id the same way and every entry adds its rank inside the workgroup.
@@ -435,7 +413,6 @@ hipError_t launch_scatter_sort(hipStream_t s, const int* X, const int* len, int 
         scat_scan_kernel<true><<<1, 1024, lds, s>>>(cnt, n_ids, offs, cur);
         scat_fill_lds_kernel<<<grid, SCAT_BLOCK, lds, s>>>(X, len, T, Bp, F, n_ids, per_block, cur, sid, spos, concat, tc, ipc);
     } else {
-        const int grid = min(1024, (total + 255) / 256);
         const int agrid = (total + 1023) / 1024;
         scat_count_agg_kernel<<<agrid, 1024, 0, s>>>(X, len, T, Bp, F, cnt);
         const int nb = (n_ids + SCAN_BLK - 1) / SCAN_BLK;
@@ -445,7 +422,6 @@ hipError_t launch_scatter_sort(hipStream_t s, const int* X, const int* len, int 
             scat_scan_totals_kernel<<<1, 1024, 0, s>>>(cur, nb, cnt, offs + n_ids);
             scat_scan_add_kernel<<<nb, 1024, 0, s>>>(cnt, n_ids, offs, cur);
         }
-        (void)grid;
         scat_fill_agg_kernel<<<agrid, 1024, 0, s>>>(X, len, T, Bp, F, cur, sid, spos, concat);
     }
     return hipGetLastError();

@@ -1294,78 +1294,120 @@ hipError_t launch_rec_reduce_partials(hipStream_t s, const float* part, int nblk
 // ---------------------------------------------------------------------------------------
 // Launchers
 // ---------------------------------------------------------------------------------------
-template <int CELL>
-static hipError_t launch_fwd_cell(hipStream_t s, const RecArgs& a, bool simple) {
-    const int Hp = a.Hp;
-    if (simple) {
-        const int n = a.Bp * Hp, blk = 256, grid = (n + blk - 1) / blk;
-        for (int t = 0; t < a.T; ++t) rec_fwd_step_simple<CELL><<<grid, blk, 0, s>>>(a, t);
-        return hipGetLastError();
+// LDS bytes of the kernels of this file, each formula once: the plan sizes the launches with them and decides by them
+constexpr size_t kRecLdsMax = 160 * 1024;
+// rec_fwd_x6 / rec_fwd_x6s: W plane 3 + two buffers of three planes of `rows` state rows
+static size_t x6_fwd_lds(int G, int Hp, int rows) { return (size_t)G * (Hp / 32) * (Hp / 16) * 1024 + 2 * 3 * rows * (size_t)(Hp * 2 + 32); }
+// rec_bwd_x6 / rec_bwd_x6s: W plane 3 + `bufs` buffers of three planes of `rows` gradient rows
+static size_t x6_bwd_lds(int GHp, int Hp, int rows, int bufs) { return (size_t)(GHp / 32) * (Hp / 16) * 1024 + bufs * 3 * (size_t)rows * (GHp * 2 + 32); }
+// rec_fwd_mfma: two buffers of 16 rows of `cols` = Hp floats; rec_bwd_mfma: one or two of `cols` = G * Hp
+static size_t mfma_lds(int cols) { return 16 * (size_t)(4 * ((cols / 4 + 63) / 64 * 64) + 4) * sizeof(float); }
+
+// The plan of a layer (sbr_common.h): the one place where the kernel family is decided.  Precedence: triage, cluster, x6p, x6q, the
+// barrier kernels where their LDS fits (4-row tiles: x6s), rec_*_mfma.
+RecPlan sbr_rec_plan(const RecArgs& a, bool simple, bool fused) {
+    RecPlan p = {};
+    const int Hp = a.Hp, GHp = a.G * Hp;
+    const bool w6 = !a.f32_mfma && (Hp == 32 || Hp == 64 || Hp == 128);      // the widths of the single-workgroup bf16x6 kernels
+    const bool cl = !simple && sbr_rec_cluster_ok(a), c16 = cl && sbr_rec_c16_ok(a);
+    const bool xp = !simple && !cl && sbr_rec_x6p_ok(a), xq = !simple && !cl && !xp && sbr_rec_x6q_ok(a);
+    const bool bwd6 = w6 && x6_bwd_lds(GHp, Hp, a.rpt, 1) <= kRecLdsMax;     // the backward fits with one buffer at least
+    // the forward kernel gathers its rows itself: the cluster kernels, and the 4-row tiles of the bf16x6 ones (rec_fwd_x6p inside
+    // its bounds: row offsets in LDS (T), 32-bit offsets into W_in (n_in))
+    p.fuse_gather = fused && !simple && (cl || (w6 && !(xp && !sbr_rec_x6p_fuse_ok(a)) && a.rpt == 4 && x6_fwd_lds(a.G, Hp, 4) <= kRecLdsMax));
+    RecArgs af = a;
+    if (p.fuse_gather) af.gX = (const int*)a.hs;      // (only its being set is read: x6q's bound on the rows of W_in)
+    const bool xq_fwd = xq && sbr_rec_x6q_ok(af);
+
+    const RecKernel wide = c16 ? REC_C16 : REC_CL8, tile = a.rpt == 4 ? REC_X6S : REC_X6;
+    p.fwd = simple ? REC_TRIAGE : cl ? wide : xp ? REC_X6P : xq_fwd ? REC_X6Q : (w6 && x6_fwd_lds(a.G, Hp, 16) <= kRecLdsMax) ? tile : REC_MFMA;
+    p.bwd = simple ? REC_TRIAGE : cl ? wide : xp ? REC_X6P : xq ? REC_X6Q : bwd6 ? tile : REC_MFMA;
+    p.family = simple ? 0 : cl ? 1 : xp ? 2 : xq ? 3 : 4;
+    if (p.fwd == REC_X6S || p.fwd == REC_X6) p.fwd_lds = x6_fwd_lds(a.G, Hp, p.fwd == REC_X6S ? 4 : 16);
+    if (p.fwd == REC_MFMA) p.fwd_lds = 2 * mfma_lds(Hp);
+    if (p.bwd == REC_X6S || p.bwd == REC_X6) {
+        p.bwd_dbuf = x6_bwd_lds(GHp, Hp, a.rpt, 2) <= kRecLdsMax;
+        p.bwd_lds = x6_bwd_lds(GHp, Hp, a.rpt, p.bwd_dbuf ? 2 : 1);
     }
-    if (sbr_rec_cluster_ok(a)) return launch_rec_forward_cl(s, a);
-    if (sbr_rec_x6p_ok(a)) return launch_rec_forward_x6p(s, a);
-    if (sbr_rec_x6q_ok(a)) return launch_rec_forward_x6q(s, a);
-    const int nblk = a.Bp / 16;
+    if (p.bwd == REC_MFMA) {
+        p.bwd_dbuf = 2 * mfma_lds(GHp) <= 150 * 1024;
+        p.bwd_lds = (p.bwd_dbuf ? 2 : 1) * mfma_lds(GHp);
+    }
+    p.tail_ok = !simple && sbr_rec_x6p_tail_ok(a);
+    p.needs_fill = cl;
+    p.bwd_chunkable = !simple && bwd6;
+
+    // What sbr_query answers, as it always has -- by width, not by launch: a layer of 32 / 64 / 128 units counts as bf16x6 on
+    // rpt-row tiles even where its LDS does not fit and rec_*_mfma runs (DESIGN.md "What comes next").
+    p.products_fwd = p.products_bwd = 0; p.fwd_rows = p.bwd_rows = 16; p.fwd_wgs = p.bwd_wgs = a.Bp / 16;
+    if (!simple && (cl || w6)) {
+        const bool planes2 = cl || xp || xq;       // the families with fp16 forms
+        p.products_fwd = planes2 && sbr_rec_f16_fwd(a) ? (xp ? sbr_rec_x6p_f16_terms() : 3) : 6;
+        p.products_bwd = planes2 && sbr_rec_f16_bwd(a) ? (xp ? sbr_rec_x6p_f16_terms() : 3) : 6;
+        if (c16) p.fwd_wgs = p.bwd_wgs = (a.Bp / 16) * (Hp / 16);
+        else if (cl) {      // 8-row tiles; the backward at 512 units without fp16 planes: 4-row tiles (bwd_cl)
+            p.fwd_rows = SBR_CL_ROWS; p.bwd_rows = Hp == 512 && !sbr_rec_f16_bwd(a) ? 4 : SBR_CL_ROWS;
+            p.fwd_wgs = (a.Bp / p.fwd_rows) * (Hp == 256 ? 8 : 32); p.bwd_wgs = (a.Bp / p.bwd_rows) * (Hp == 256 ? 8 : 32);
+        } else { p.fwd_rows = p.bwd_rows = a.rpt; p.fwd_wgs = p.bwd_wgs = a.Bp / a.rpt; }
+    }
+    // (the triage kernels accumulate into block 0 of 16-row blocks, the others stay zero)
+    p.bwd_blocks = simple ? a.Bp / 16 : cl ? a.Bp / p.bwd_rows : bwd6 ? a.Bp / a.rpt : a.Bp / 16;
+    return p;
+}
+
 #define LAUNCH_DYN(KERNEL, GRID, BLOCK, LDS, ...) do { \
         SBR_DYN_LDS(KERNEL, (LDS)); \
         KERNEL<<<GRID, BLOCK, LDS, s>>>(__VA_ARGS__); } while (0)
-    if (!a.f32_mfma && (Hp == 32 || Hp == 64 || Hp == 128)) {
-        const size_t l6 = (size_t)Gates<CELL>::G * (Hp / 32) * (Hp / 16) * 1024 + 2 * 3 * 16 * (size_t)(Hp * 2 + 32);
-        if (l6 <= 160 * 1024) {
-            const int nb6 = a.Bp / a.rpt;
-            if (a.rpt == 4) {   // 4-row tiles: one (row, unit) pair per lane
-                const size_t l4 = (size_t)Gates<CELL>::G * (Hp / 32) * (Hp / 16) * 1024 + 2 * 3 * 4 * (size_t)(Hp * 2 + 32);
-                if (Hp == 32) LAUNCH_DYN((rec_fwd_x6s<CELL, 32>), nb6, Hp * 4, l4, a);
-                else if (Hp == 64) LAUNCH_DYN((rec_fwd_x6s<CELL, 64>), nb6, Hp * 4, l4, a);
-                else LAUNCH_DYN((rec_fwd_x6s<CELL, 128>), nb6, Hp * 4, l4, a);
-                return hipGetLastError();
-            }
-            if (Hp == 32) LAUNCH_DYN((rec_fwd_x6<CELL, 32>), nb6, Hp * 4, l6, a);
-            else if (Hp == 64) LAUNCH_DYN((rec_fwd_x6<CELL, 64>), nb6, Hp * 4, l6, a);
-            else LAUNCH_DYN((rec_fwd_x6<CELL, 128>), nb6, Hp * 4, l6, a);
-            return hipGetLastError();
+// the instance of a barrier kernel for the layer's width (32 / 64 / 128), on Bp / rpt tiles
+#define LAUNCH_X6_WIDTH(KERNEL, LDS, ...) do { \
+        const int nb6 = a.Bp / a.rpt; \
+        if (a.Hp == 32) LAUNCH_DYN((KERNEL<CELL, 32>), nb6, 32 * 4, LDS, __VA_ARGS__); \
+        else if (a.Hp == 64) LAUNCH_DYN((KERNEL<CELL, 64>), nb6, 64 * 4, LDS, __VA_ARGS__); \
+        else if (a.Hp == 128) LAUNCH_DYN((KERNEL<CELL, 128>), nb6, 128 * 4, LDS, __VA_ARGS__); \
+        else return hipErrorInvalidValue; } while (0)
+// ... of rec_*_mfma: W_hid resident up to 128 units, streamed above, with 1, 2 or 4 tiles per wave
+#define LAUNCH_MFMA_WIDTH(KERNEL, LDS, ...) do { \
+        const int nblk = a.Bp / 16, tiles = a.Hp / 16; \
+        if (a.Hp == 16) LAUNCH_DYN((KERNEL<CELL, 1, 4>), nblk, tiles * 64, LDS, __VA_ARGS__); \
+        else if (a.Hp == 32) LAUNCH_DYN((KERNEL<CELL, 1, 8>), nblk, tiles * 64, LDS, __VA_ARGS__); \
+        else if (a.Hp == 64) LAUNCH_DYN((KERNEL<CELL, 1, 16>), nblk, tiles * 64, LDS, __VA_ARGS__); \
+        else if (a.Hp == 128) LAUNCH_DYN((KERNEL<CELL, 1, 32>), nblk, tiles * 64, LDS, __VA_ARGS__); \
+        else if (tiles <= 16) LAUNCH_DYN((KERNEL<CELL, 1, 0>), nblk, tiles * 64, LDS, __VA_ARGS__); \
+        else if (tiles <= 32) LAUNCH_DYN((KERNEL<CELL, 2, 0>), nblk, (tiles / 2) * 64, LDS, __VA_ARGS__); \
+        else if (tiles <= 64) LAUNCH_DYN((KERNEL<CELL, 4, 0>), nblk, (tiles / 4) * 64, LDS, __VA_ARGS__); \
+        else return hipErrorInvalidValue; } while (0)
+
+template <int CELL>
+static hipError_t launch_fwd_cell(hipStream_t s, const RecArgs& a, const RecPlan& p) {
+    switch (p.fwd) {
+        case REC_TRIAGE: {
+            const int n = a.Bp * a.Hp, blk = 256, grid = (n + blk - 1) / blk;
+            for (int t = 0; t < a.T; ++t) rec_fwd_step_simple<CELL><<<grid, blk, 0, s>>>(a, t);
+            break;
         }
+        case REC_C16: case REC_CL8: return launch_rec_forward_cl(s, a, p.fwd == REC_C16);
+        case REC_X6P: return launch_rec_forward_x6p(s, a);
+        case REC_X6Q: return launch_rec_forward_x6q(s, a);
+        case REC_X6S: LAUNCH_X6_WIDTH(rec_fwd_x6s, p.fwd_lds, a); break;      // 4-row tiles: one (row, unit) pair per lane
+        case REC_X6: LAUNCH_X6_WIDTH(rec_fwd_x6, p.fwd_lds, a); break;
+        case REC_MFMA: LAUNCH_MFMA_WIDTH(rec_fwd_mfma, p.fwd_lds, a); break;
     }
-    const size_t lds = 2 * 16 * (size_t)(4 * ((Hp / 4 + 63) / 64 * 64) + 4) * sizeof(float);
-#define FWD_RES(KS) LAUNCH_DYN((rec_fwd_mfma<CELL, 1, KS>), nblk, (Hp / 16) * 64, lds, a)
-    if (Hp == 16) FWD_RES(4);
-    else if (Hp == 32) FWD_RES(8);
-    else if (Hp == 64) FWD_RES(16);
-    else if (Hp == 128) FWD_RES(32);
-    else {
-        const int tiles = Hp / 16;
-        if (tiles <= 16) LAUNCH_DYN((rec_fwd_mfma<CELL, 1, 0>), nblk, tiles * 64, lds, a);
-        else if (tiles <= 32) LAUNCH_DYN((rec_fwd_mfma<CELL, 2, 0>), nblk, (tiles / 2) * 64, lds, a);
-        else if (tiles <= 64) LAUNCH_DYN((rec_fwd_mfma<CELL, 4, 0>), nblk, (tiles / 4) * 64, lds, a);
-        else return hipErrorInvalidValue;
-    }
-#undef FWD_RES
     return hipGetLastError();
 }
 
-bool sbr_rec_fwd_can_fuse_gather(const RecArgs& a, bool simple) {
-    const int Hp = a.Hp;
-    if (simple || a.f32_mfma) return false;
-    if (sbr_rec_cluster_ok(a)) return true;               // rec_fwd_cl gathers its own rows too
-    if (!(Hp == 32 || Hp == 64 || Hp == 128)) return false;
-    if (sbr_rec_x6p_ok(a) && !sbr_rec_x6p_fuse_ok(a)) return false;    // rec_fwd_x6p: row offsets in LDS (T), 32-bit offsets into W_in (n_in)
-    const size_t l4 = (size_t)a.G * (Hp / 32) * (Hp / 16) * 1024 + 2 * 3 * 4 * (size_t)(Hp * 2 + 32);
-    return a.rpt == 4 && l4 <= 160 * 1024;
-}
-
-hipError_t launch_rec_forward(hipStream_t s, const RecArgs& a, bool simple) {
+hipError_t launch_rec_forward(hipStream_t s, const RecArgs& a, const RecPlan& p) {
     switch (a.cell) {
-        case SBR_CELL_LSTM: return launch_fwd_cell<CELL_LSTM>(s, a, simple);
-        case SBR_CELL_GRU: return launch_fwd_cell<CELL_GRU>(s, a, simple);
-        default: return launch_fwd_cell<CELL_VANILLA>(s, a, simple);
+        case SBR_CELL_LSTM: return launch_fwd_cell<CELL_LSTM>(s, a, p);
+        case SBR_CELL_GRU: return launch_fwd_cell<CELL_GRU>(s, a, p);
+        default: return launch_fwd_cell<CELL_VANILLA>(s, a, p);
     }
 }
 
 template <int CELL>
-static hipError_t launch_bwd_cell(hipStream_t s, const RecArgs& a, bool simple) {
+static hipError_t launch_bwd_cell(hipStream_t s, const RecArgs& a, const RecPlan& p) {
     const int Hp = a.Hp, G = Gates<CELL>::G, GHp = G * Hp;
     const int nblk = a.Bp / 16;
-    if (simple) {
+    if (p.bwd == REC_TRIAGE) {
         // part block 0 accumulates (atomics); other blocks stay zero
         hipError_t e = hipMemsetAsync(a.part, 0, (size_t)nblk * (GHp + 5 * Hp) * sizeof(float), s);
         if (e != hipSuccess) return e;
@@ -1383,64 +1425,22 @@ static hipError_t launch_bwd_cell(hipStream_t s, const RecArgs& a, bool simple) 
         (void)hipFree(st);
         return e;
     }
-    if (sbr_rec_cluster_ok(a)) return launch_rec_backward_cl(s, a);
-    if (sbr_rec_x6p_ok(a)) return launch_rec_backward_x6p(s, a);
-    if (sbr_rec_x6q_ok(a)) return launch_rec_backward_x6q(s, a);
-    if (!a.f32_mfma && (Hp == 32 || Hp == 64 || Hp == 128)) {
-        const size_t w3b = (size_t)(GHp / 32) * (Hp / 16) * 1024, one6 = 3 * (size_t)a.rpt * (GHp * 2 + 32);
-        const int db6 = (w3b + 2 * one6 <= 160 * 1024) ? 1 : 0;
-        const size_t l6 = w3b + (db6 ? 2 : 1) * one6;
-        if (l6 <= 160 * 1024) {
-            const int nb6 = a.Bp / a.rpt;
-            if (a.rpt == 4) {
-                if (Hp == 32) LAUNCH_DYN((rec_bwd_x6s<CELL, 32>), nb6, Hp * 4, l6, a, db6);
-                else if (Hp == 64) LAUNCH_DYN((rec_bwd_x6s<CELL, 64>), nb6, Hp * 4, l6, a, db6);
-                else LAUNCH_DYN((rec_bwd_x6s<CELL, 128>), nb6, Hp * 4, l6, a, db6);
-                return hipGetLastError();
-            }
-            if (Hp == 32) LAUNCH_DYN((rec_bwd_x6<CELL, 32>), nb6, Hp * 4, l6, a, db6);
-            else if (Hp == 64) LAUNCH_DYN((rec_bwd_x6<CELL, 64>), nb6, Hp * 4, l6, a, db6);
-            else LAUNCH_DYN((rec_bwd_x6<CELL, 128>), nb6, Hp * 4, l6, a, db6);
-            return hipGetLastError();
-        }
+    switch (p.bwd) {
+        case REC_TRIAGE: break;      // (above)
+        case REC_C16: case REC_CL8: return launch_rec_backward_cl(s, a, p.bwd == REC_C16);
+        case REC_X6P: return launch_rec_backward_x6p(s, a);
+        case REC_X6Q: return launch_rec_backward_x6q(s, a);
+        case REC_X6S: LAUNCH_X6_WIDTH(rec_bwd_x6s, p.bwd_lds, a, p.bwd_dbuf); break;
+        case REC_X6: LAUNCH_X6_WIDTH(rec_bwd_x6, p.bwd_lds, a, p.bwd_dbuf); break;
+        case REC_MFMA: LAUNCH_MFMA_WIDTH(rec_bwd_mfma, p.bwd_lds, a, p.bwd_dbuf); break;
     }
-    const size_t one = 16 * (size_t)(4 * ((GHp / 4 + 63) / 64 * 64) + 4) * sizeof(float);
-    const int dbuf = (2 * one <= 150 * 1024) ? 1 : 0;
-    const size_t lds = dbuf ? 2 * one : one;
-#define BWD_RES(KS) LAUNCH_DYN((rec_bwd_mfma<CELL, 1, KS>), nblk, (Hp / 16) * 64, lds, a, dbuf)
-    if (Hp == 16) BWD_RES(4);
-    else if (Hp == 32) BWD_RES(8);
-    else if (Hp == 64) BWD_RES(16);
-    else if (Hp == 128) BWD_RES(32);
-    else {
-        const int tiles = Hp / 16;
-        if (tiles <= 16) LAUNCH_DYN((rec_bwd_mfma<CELL, 1, 0>), nblk, tiles * 64, lds, a, dbuf);
-        else if (tiles <= 32) LAUNCH_DYN((rec_bwd_mfma<CELL, 2, 0>), nblk, (tiles / 2) * 64, lds, a, dbuf);
-        else if (tiles <= 64) LAUNCH_DYN((rec_bwd_mfma<CELL, 4, 0>), nblk, (tiles / 4) * 64, lds, a, dbuf);
-        else return hipErrorInvalidValue;
-    }
-#undef BWD_RES
     return hipGetLastError();
 }
 
-static bool uses_x6_bwd(const RecArgs& a) {
-    const int Hp = a.Hp, GHp = a.G * Hp;
-    if (a.f32_mfma || !(Hp == 32 || Hp == 64 || Hp == 128)) return false;
-    const size_t w3b = (size_t)(GHp / 32) * (Hp / 16) * 1024, one6 = 3 * (size_t)a.rpt * (GHp * 2 + 32);
-    return w3b + one6 <= 160 * 1024;
-}
-int sbr_rec_bwd_blocks(const RecArgs& a, bool simple) {
-    if (simple) return a.Bp / 16;                 // simple kernels accumulate into block 0, others zeroed
-    if (sbr_rec_cluster_ok(a)) return a.Bp / sbr_rec_cluster_bwd_rows(a);
-    return uses_x6_bwd(a) ? a.Bp / a.rpt : a.Bp / 16;
-}
-
-bool sbr_rec_bwd_chunkable(const RecArgs& a, bool simple) { return !simple && uses_x6_bwd(a); }
-
-hipError_t launch_rec_backward(hipStream_t s, const RecArgs& a, bool simple) {
+hipError_t launch_rec_backward(hipStream_t s, const RecArgs& a, const RecPlan& p) {
     switch (a.cell) {
-        case SBR_CELL_LSTM: return launch_bwd_cell<CELL_LSTM>(s, a, simple);
-        case SBR_CELL_GRU: return launch_bwd_cell<CELL_GRU>(s, a, simple);
-        default: return launch_bwd_cell<CELL_VANILLA>(s, a, simple);
+        case SBR_CELL_LSTM: return launch_bwd_cell<CELL_LSTM>(s, a, p);
+        case SBR_CELL_GRU: return launch_bwd_cell<CELL_GRU>(s, a, p);
+        default: return launch_bwd_cell<CELL_VANILLA>(s, a, p);
     }
 }

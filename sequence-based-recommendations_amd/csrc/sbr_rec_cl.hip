@@ -1003,25 +1003,19 @@ __global__ void __launch_bounds__(256) rec_bwd_clg(RecArgs a) {
 bool sbr_rec_cluster_ok(const RecArgs& a) {
     return a.cluster && !a.f32_mfma && (a.Hp == 256 || a.Hp == 512) && a.Bp % SBR_CL_ROWS == 0;
 }
-// rows per tile of the backward launch (part[] has Bp / rows blocks)
-// the 16-row kernels: both chains on fp16 planes (one answer for the forward and the backward launch of a step: they share
-// the exchange arrays' and the partial sums' layout), SBR_CL16=0 keeps the 8-row kernels
+// the 16-row kernels: both chains on fp16 planes (the forward and the backward launch share the exchange arrays' and the partial
+// sums' layout: sbr_rec_plan gives both the one answer), SBR_CL16=0 keeps the 8-row kernels
 bool sbr_rec_c16_ok(const RecArgs& a) {
     if (!(a.cl16 && sbr_rec_cluster_ok(a) && a.xh && a.pring && a.Bp % 16 == 0 && sbr_rec_f16_fwd(a) && sbr_rec_f16_bwd(a))) return false;
     if (a.cell != SBR_CELL_VANILLA && a.g[0])             // the saved gates are ONE region [T][Bp][Hp][4] under the four arrays
         for (int k = 1; k < 4; ++k) if (a.g[k] != a.g[0] + (size_t)k * a.T * a.Bp * a.Hp) return false;
     return true;
 }
-int sbr_rec_cluster_bwd_rows(const RecArgs& a) {
-    if (sbr_rec_c16_ok(a)) return 16;
-    return a.Hp == 512 && !sbr_rec_f16_bwd(a) ? 4 : SBR_CL_ROWS;
-}
 size_t sbr_rec_c16_ring_floats(int Bp, int Hp) { return (size_t)SBR_C16_RING * (Bp / 16) * (Hp / 16) * (Hp / 16) * 256; }
 
 template <int CELL, int HP>
 static hipError_t fwd_cl(hipStream_t s, const RecArgs& a) {
     constexpr int G = Gates<CELL>::G, R = SBR_CL_ROWS;
-    if (sbr_rec_c16_ok(a)) return launch_rec_forward_c16(s, a);
     hipError_t e = hipMemsetAsync(a.hs, 0xFF, (size_t)(a.T + 1) * a.Bp * HP * sizeof(float), s);   // sentinel: see the header
     if (e != hipSuccess) return e;
     if (HP == 256) {
@@ -1046,11 +1040,6 @@ static hipError_t fwd_cl(hipStream_t s, const RecArgs& a) {
 template <int CELL, int HP>
 static hipError_t bwd_cl(hipStream_t s, const RecArgs& a) {
     constexpr int G = Gates<CELL>::G, GHP = G * HP;
-    if (!a.sentinel_done) {                               // else: sbr_rec_bwd_cl_fill ran on the side stream during the output phase
-        const hipError_t e = sbr_rec_bwd_cl_fill(s, a);
-        if (e != hipSuccess) return e;
-    }
-    if (sbr_rec_c16_ok(a)) return launch_rec_backward_c16(s, a);
     if (HP == 256) {
         constexpr int R = SBR_CL_ROWS;
         if (sbr_rec_f16_bwd(a)) {
@@ -1060,7 +1049,7 @@ static hipError_t bwd_cl(hipStream_t s, const RecArgs& a) {
             const size_t lds = (size_t)(GHP / 64) * 4 * 1024 + 3 * (size_t)R * (GHP * 2 + 32) + 2 * 1024;
             CL_LAUNCH((rec_bwd_cl<CELL, 256, R, false>), 256 / 32, R, lds);
         }
-    } else {
+    } else {                          // (rows per tile here = RecPlan.bwd_rows: part[] has Bp / rows blocks)
         if (sbr_rec_f16_bwd(a)) {     // two fp16 planes and no W plane in LDS: 8-row tiles fit (66 KB), half the workgroup rounds
             constexpr int R = 8;
             const size_t lds = 2 * (size_t)R * (GHP * 2 + 32) + 3 * 1024;
@@ -1075,14 +1064,15 @@ static hipError_t bwd_cl(hipStream_t s, const RecArgs& a) {
 }
 
 // the sentinel fill of the backward exchange arrays (dxt, GRU: + the compact candidate slice)
-hipError_t sbr_rec_bwd_cl_fill(hipStream_t s, const RecArgs& a) {
-    if (sbr_rec_c16_ok(a)) return sbr_rec_c16_fill(s, a);
+hipError_t sbr_rec_bwd_cl_fill(hipStream_t s, const RecArgs& a, bool c16) {
+    if (c16) return sbr_rec_c16_fill(s, a);
     hipError_t e = hipMemsetAsync(a.dxt, 0xFF, (size_t)a.T * a.Bp * a.G * a.Hp * sizeof(float), s);
     if (e == hipSuccess && a.cell == SBR_CELL_GRU) e = hipMemsetAsync(a.dhi, 0xFF, (size_t)a.T * a.Bp * a.Hp * sizeof(float), s);
     return e;
 }
 
 #define CL_DISPATCH(FN) \
+    if (a.Hp != 256 && a.Hp != 512) return hipErrorInvalidValue; \
     if (a.Hp == 512) { \
         switch (a.cell) { case SBR_CELL_LSTM: return FN<CELL_LSTM, 512>(s, a); case SBR_CELL_GRU: return FN<CELL_GRU, 512>(s, a); \
                           default: return FN<CELL_VANILLA, 512>(s, a); } \
@@ -1090,5 +1080,15 @@ hipError_t sbr_rec_bwd_cl_fill(hipStream_t s, const RecArgs& a) {
     switch (a.cell) { case SBR_CELL_LSTM: return FN<CELL_LSTM, 256>(s, a); case SBR_CELL_GRU: return FN<CELL_GRU, 256>(s, a); \
                       default: return FN<CELL_VANILLA, 256>(s, a); }
 
-hipError_t launch_rec_forward_cl(hipStream_t s, const RecArgs& a) { CL_DISPATCH(fwd_cl) }
-hipError_t launch_rec_backward_cl(hipStream_t s, const RecArgs& a) { CL_DISPATCH(bwd_cl) }
+hipError_t launch_rec_forward_cl(hipStream_t s, const RecArgs& a, bool c16) {
+    if (c16) return launch_rec_forward_c16(s, a);
+    CL_DISPATCH(fwd_cl)
+}
+hipError_t launch_rec_backward_cl(hipStream_t s, const RecArgs& a, bool c16) {
+    if (!a.sentinel_done) {                               // else: sbr_rec_bwd_cl_fill ran on the side stream during the output phase
+        const hipError_t e = sbr_rec_bwd_cl_fill(s, a, c16);
+        if (e != hipSuccess) return e;
+    }
+    if (c16) return launch_rec_backward_c16(s, a);
+    CL_DISPATCH(bwd_cl)
+}

@@ -1121,12 +1121,11 @@ int sbr_rec_x6p_f16_terms() { return X6P_PACK ? (X6P_SPARSE ? 1 : 2) : 3; }
 bool sbr_rec_x6p_ok(const RecArgs& a) {
     if (!a.x6_pipe || a.f32_mfma || a.Hp != HP || a.rpt != R) return false;
     // four gates: W_hid fits the register file as two fp16 planes only, so an LSTM runs here while BOTH directions take their
-    // fp16 forms (one answer for the forward and the backward launch of a step: they share the saved activations' layout)
+    // fp16 forms
     if (a.G > 3 && !(sbr_rec_f16_fwd(a) && sbr_rec_f16_bwd(a))) return false;
     if ((size_t)a.Bp * a.G * HP * 4 >= ((size_t)1 << 32)) return false;          // 32-bit per-lane byte offsets
-    // (NOT a function of a.gX: the forward and the backward launch of a step must get the same answer -- they share the saved
-    // gates' layout (X6P_G4).  Whether the gather can be fused is sbr_rec_fwd_can_fuse_gather's decision, made before gX is set;
-    // launch_fwd_p refuses a fused launch outside those bounds instead of silently taking another kernel family.)
+    // (NOT a function of a.gX: the forward and the backward launch share the saved gates' layout (X6P_G4).  Whether the gather is
+    // fused is RecPlan.fuse_gather; launch_fwd_p refuses a fused launch outside sbr_rec_x6p_fuse_ok's bounds.)
     if (X6P_G4 && a.cell != SBR_CELL_VANILLA && a.g[0])                            // one region [T][Bp][HP][4] under the four arrays
         for (int k = 1; k < 4; ++k) if (a.g[k] != a.g[0] + (size_t)k * a.T * a.Bp * HP) return false;
     if (X6P_G4 && (size_t)a.Bp * HP * 16 >= ((size_t)1 << 32)) return false;
@@ -1152,7 +1151,7 @@ static hipError_t launch_fwd_p(hipStream_t s, const RecArgs& a) {
         SBR_DYN_LDS(KERNEL, lds); \
         KERNEL<<<nb, 512, lds, s>>>(a); } while (0)
     const bool fuse = a.gX != nullptr;
-    if (fuse && !sbr_rec_x6p_fuse_ok(a)) return hipErrorInvalidValue;          // (sbr_rec_fwd_can_fuse_gather says when)
+    if (fuse && !sbr_rec_x6p_fuse_ok(a)) return hipErrorInvalidValue;          // (RecPlan.fuse_gather says when)
     const bool f16 = sbr_rec_f16_fwd(a);
     if constexpr (CELL == CELL_LSTM) {
         if (!f16) return hipErrorInvalidValue;                     // (sbr_rec_x6p_ok says when)

@@ -13,44 +13,54 @@
 // ---------------------------------------------------------------------------------------
 // kernel arguments, plans, epochs
 // ---------------------------------------------------------------------------------------
-// what the kernel-family tests (sbr_rec_*_ok) and the launchers take from the engine's switches
-static inline void rec_switches(const sbr_handle* h, RecArgs& a) {
-    a.rpt = h->rpt; a.x6_pipe = h->sw.x6_pipe; a.x6_f16 = h->sw.x6_f16; a.x6_f16_bwd = h->sw.x6_f16_bwd;
-    a.cl16 = h->sw.cl16; a.c16_two_level = h->sw.c16_two_level;
-}
-// the shape of layer l and its forward activations: all that the kernel-family tests read, and all that tail_plan fills
-static void rec_shape(const sbr_handle* h, int l, RecArgs& a) {
-    const Layout& y = h->lay; const LayerLayout& ly = y.layer[l];
-    a.cell = y.cfg.cell; a.T = y.T; a.Bp = y.Bp; a.H = ly.H; a.Hp = ly.Hp; a.G = y.G;
-    a.n_in = ly.n_in_p;
-    a.clip = y.cfg.grad_clip;
-    rec_switches(h, a);
-    a.hs = h->A(ly.a_hs); a.cs = h->A(ly.a_cs);
-    for (int k = 0; k < 4; ++k) a.g[k] = h->A(ly.a_g[k]);
-}
 // slot k of the profile buffer: 0 the forward chain, 1 the backward chain, 2 the one-launch head (tools/rec_prof.py, cl_prof.py, head_prof.py)
 static inline unsigned long long* prof_slot(const sbr_handle* h, int k) {
     return (unsigned long long*)h->A(h->lay.a_prof) + (size_t)k * (h->lay.Bp / 16) * 16 * 8;
 }
-RecArgs rec_args(sbr_handle* h, int l) {
+// layer l without a batch: its sizes, the engine's switches and flags, where its activations lie -- what sbr_rec_plan reads
+static RecArgs rec_shape(const sbr_handle* h, int l) {
     const Layout& y = h->lay; const LayerLayout& ly = y.layer[l];
     RecArgs a; memset(&a, 0, sizeof(a));
-    rec_shape(h, l, a);
-    a.len = h->blen;
-    a.xt = h->A(ly.a_xt); a.Whid = h->P(ly.p_Whid); a.peep = h->P(ly.p_peep);
-    a.cinit = h->P(ly.p_cinit); a.hinit = h->P(ly.p_hinit);
+    a.cell = y.cfg.cell; a.T = y.T; a.Bp = y.Bp; a.H = ly.H; a.Hp = ly.Hp; a.G = y.G;
+    a.n_in = ly.n_in_p;
+    a.clip = y.cfg.grad_clip;
+    a.rpt = h->rpt; a.x6_pipe = h->sw.x6_pipe; a.x6_f16 = h->sw.x6_f16; a.x6_f16_bwd = h->sw.x6_f16_bwd;
+    a.cl16 = h->sw.cl16; a.c16_two_level = h->sw.c16_two_level;
+    a.hs = h->A(ly.a_hs); a.cs = h->A(ly.a_cs);
+    for (int k = 0; k < 4; ++k) a.g[k] = h->A(ly.a_g[k]);
     if (ly.Hp == 256 || ly.Hp == 512) { a.xh = h->A(ly.a_xh); a.pring = h->A(ly.a_pring); }
-    a.dxt = h->A(ly.a_dxt); a.dhi = h->A(ly.a_dhi); a.part = h->A(ly.a_part);
-    a.xt_blocked = 0;
-    a.t_lo = 0; a.t_hi = y.T; a.chunk = 0; a.state = h->A(ly.a_state);
     a.f32_mfma = (y.cfg.flags & SBR_FLAG_F32_MFMA) ? 1 : 0;
     a.prof = (y.cfg.flags & SBR_FLAG_PROFILE_REC) ? prof_slot(h, 0) : nullptr;
-    a.cluster = h->sw.cluster; a.cl_linear = h->sw.cl_linear; a.fault = (int*)h->A(y.a_fault);
-    a.clx = (int*)h->A(y.a_clx); a.epoch = (++h->cl_epoch) & 0x07FFFFFF;
+    a.cluster = h->sw.cluster; a.cl_linear = h->sw.cl_linear;
     a.relu = (y.cfg.cell == SBR_CELL_VANILLA && (l / y.D > 0 || y.E)) ? 1 : 0;   // stock RecurrentLayer: rectify [3P]
     return a;
 }
-bool simple_rec(const sbr_handle* h) { return h->lay.cfg.flags & SBR_FLAG_SIMPLE_REC; }
+// layer l's kernel arguments for the current batch; advances the cluster kernels' exchange epoch (unique per launch)
+static RecArgs rec_args(sbr_handle* h, int l) {
+    const Layout& y = h->lay; const LayerLayout& ly = y.layer[l];
+    RecArgs a = rec_shape(h, l);
+    a.len = h->blen;
+    a.xt = h->A(ly.a_xt); a.Whid = h->P(ly.p_Whid); a.peep = h->P(ly.p_peep);
+    a.cinit = h->P(ly.p_cinit); a.hinit = h->P(ly.p_hinit);
+    a.dxt = h->A(ly.a_dxt); a.dhi = h->A(ly.a_dhi); a.part = h->A(ly.a_part);
+    a.xt_blocked = 0;
+    a.t_lo = 0; a.t_hi = y.T; a.chunk = 0; a.state = h->A(ly.a_state);
+    a.fault = (int*)h->A(y.a_fault);
+    a.clx = (int*)h->A(y.a_clx); a.epoch = (++h->cl_epoch) & 0x07FFFFFF;
+    return a;
+}
+static bool simple_rec(const sbr_handle* h) { return h->lay.cfg.flags & SBR_FLAG_SIMPLE_REC; }
+// The plans of all layers, made once inside sbr_create.  dh_ext as the BPTT launch will have it (bptt_args); the step lets the
+// forward kernel gather W_in's rows where the input is one index per step without an embedding in front (layer0_input).
+void plan_layers(sbr_handle* h) {
+    const Layout& y = h->lay;
+    for (int l = 0; l < y.L * y.D; ++l) {
+        RecArgs a = rec_shape(h, l);
+        if (l / y.D < y.L - 1) a.dh_ext = h->A(y.layer[l].a_dhext);
+        h->plan[l] = sbr_rec_plan(a, simple_rec(h), l / y.D == 0 && !y.E && y.F == 1 && h->sw.fuse_gather);
+    }
+}
+static const RecPlan& plan_of(const sbr_handle* h, const LayerLayout& ly) { return h->plan[&ly - h->lay.layer]; }
 // Operand planes of the dense GEMMs around the recurrent layers (layer >= 2 input projection and its backward pair, the logits):
 // their operands are hidden states in [-1, 1] (not behind a rectifier), weights, and -- in the backward pair -- gate gradients
 // that have passed the reference's clip at +-100 (recurrent_layers.py:19): the two-plane fp16 split, three MFMAs per product, f32-class
@@ -77,10 +87,7 @@ int tail_plan(sbr_handle* h, int* ch_out) {
     const Layout& y = h->lay;
     *ch_out = 0;
     if (!h->sw.tail_overlap || y.tail_keys < 2 || y.n_sparse || h->sw.bwd_chunks != 1) return 0;
-    if (simple_rec(h) || simple_gemm(h) || (y.cfg.flags & (SBR_FLAG_F32_MFMA | SBR_FLAG_ATOMIC_SCATTER))) return 0;
-    RecArgs a; memset(&a, 0, sizeof(a));
-    rec_shape(h, 0, a);
-    if (!sbr_rec_x6p_tail_ok(a)) return 0;
+    if (!h->plan[0].tail_ok || simple_gemm(h) || (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER)) return 0;      // (tail_ok: never triage or exact-f32 kernels)
     int nc = std::min(std::min(y.tail_keys, kTailChunksMax), y.T / 16);
     if (nc < 2) return 0;
     const int ch = (y.T + nc - 1) / nc;
@@ -129,7 +136,7 @@ static int step_next_epoch(int* e) { *e = (*e + 1) & 0x7FFFFFFF; if (!*e) *e = 1
 static bool step_boundary_marks(const sbr_handle* h) { return h->timing && (h->timing_marks & ((1u << 0) | (1u << 6))); }
 // the chain's progress words of this step's overlapped tail, one per wave of rec_bwd_x6p
 static int* tail_words(sbr_handle* h, int* nwaves) {
-    *nwaves = (h->lay.Bp / rec_args(h, 0).rpt) * 8;
+    *nwaves = (h->lay.Bp / h->rpt) * 8;
     return (int*)h->A(h->lay.a_prog);
 }
 
@@ -283,7 +290,7 @@ static hipError_t input_projection(sbr_handle* h, const LayerLayout& ly, const f
 static int layer0_input(sbr_handle* h, RecArgs& ra, const LayerLayout& ly, const int* idx, const float* emb) {
     const Layout& y = h->lay;
     if (y.E) { SBR_LAUNCH(input_projection(h, ly, emb)); return SBR_OK; }
-    if (y.F == 1 && h->sw.fuse_gather && sbr_rec_fwd_can_fuse_gather(ra, simple_rec(h))) {
+    if (plan_of(h, ly).fuse_gather) {
         ra.gX = idx; ra.gWin = h->P(ly.p_Win); ra.gbias = h->P(ly.p_b);   // gathered inside the forward kernel
     } else {
         SBR_LAUNCH(launch_gather_xt(h->stream, h->P(ly.p_Win), h->P(ly.p_b), idx, h->A(ly.a_xt), y.T, y.Bp, y.F, y.G * ly.Hp, h->n_rows));
@@ -413,7 +420,7 @@ static int forward_uni(sbr_handle* h, bool fork_gate) {
         }
         if (l == 0 && (h->tail_sorted || fork_gate)) ra.fence_kb = kTailFenceKb;
         if (fork_gate) { ra.start_word = h->step_words + 128; ra.start_epoch = step_next_epoch(&h->fork_epoch); }
-        SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, simple_rec(h)));
+        SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, h->plan[l]));
         if (fork_gate) {
             h->fork_gated = true; h->step_word_epoch = h->fork_epoch;
             SBR_LAUNCH(launch_step_gate(h->side2, h->step_words + 128, nullptr, h->fork_epoch, (int*)h->A(y.a_fault)));
@@ -446,7 +453,7 @@ static int forward_bi(sbr_handle* h) {
                 SBR_LAUNCH(input_projection(h, ly, h->A(d ? y.a_catr[l - 1] : y.a_cat[l - 1])));
             }
             if (l == 0 && d == 1) mark(h, 1);
-            SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, simple_rec(h)));
+            SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, h->plan[pl]));
         }
         const LayerLayout& lf = y.layer[2 * l]; const LayerLayout& lb = y.layer[2 * l + 1];
         if (l + 1 < y.L) {
@@ -490,11 +497,8 @@ extern "C" int sbr_forward(sbr_handle* h) {
     // that releases it, so a forward launch that fails leaves no gate waiting.  
     h->fork_gated = false; h->step_word_epoch = 0;
     const bool sort_early = h->tail_nc >= 2 && h->sw.tail_overlap == 1;
-    bool fork_gate = false;
-    if (kStepForkGate && sort_early && h->in_train_step && y.L == 1 && y.D == 1 && !forked && !step_boundary_marks(h) && !simple_rec(h)) {
-        const RecArgs r0 = rec_args(h, 0);
-        fork_gate = sbr_rec_x6p_ok(r0) && !sbr_rec_cluster_ok(r0);
-    }
+    const bool fork_gate = kStepForkGate && sort_early && h->in_train_step && y.L == 1 && y.D == 1 && !forked && !step_boundary_marks(h) &&
+                           h->plan[0].fwd == REC_X6P;
     if (sort_early && !fork_gate) {
         if (!forked) SBR_HIP(hipEventRecord(h->ev_fork, s));
         SBR_HIP(hipStreamWaitEvent(h->side2, h->ev_fork, 0));
@@ -523,10 +527,8 @@ float* h_last(sbr_handle* h) {   // hid_out[-1] (sparse_lstm.py:485-486) = slot 
 static int side_batch_work(sbr_handle* h, bool fill_needed) {
     const Layout& y = h->lay; hipStream_t sd = h->side;
     if (fill_needed) {
-        for (int l = 0; l < y.L * y.D; ++l) {
-            RecArgs a = rec_args(h, l);
-            if (sbr_rec_cluster_ok(a)) SBR_LAUNCH(sbr_rec_bwd_cl_fill(sd, a));
-        }
+        for (int l = 0; l < y.L * y.D; ++l)
+            if (h->plan[l].needs_fill) SBR_LAUNCH(sbr_rec_bwd_cl_fill(sd, rec_args(h, l), h->plan[l].bwd == REC_C16));
         SBR_HIP(hipEventRecord(h->ev_fill, sd)); h->fill_done = true;
     }
     // (round 6, call s3: the sort BEHIND the head's record instead of beside the head lets the one-launch sampled head run in 26 us
@@ -666,11 +668,7 @@ static int loss_dense(sbr_handle* h, bool fill_needed) {
     // critical path: dh = dlogits . W_out^T feeds the BPTT chain.  Where the chain is rec_bwd_x6p, the split-K slabs of the dh
     // GEMM stay unreduced and the chain's prologue adds them: one launch (7 us + its gap) less in front of it
     int keep = 0;
-    bool fold = false;
-    if (!simple_gemm(h) && y.D == 1 && h->n_rows == y.Bp && !simple_rec(h)) {
-        RecArgs ra = rec_args(h, y.L - 1);
-        fold = sbr_rec_x6p_ok(ra) && !sbr_rec_cluster_ok(ra);
-    }
+    const bool fold = !simple_gemm(h) && y.D == 1 && h->n_rows == y.Bp && h->plan[y.L - 1].bwd == REC_X6P;
     bool head_done = false;
     int rc;
     if ((rc = dense_head_fused(h, fold, &keep, &head_done)) != SBR_OK) return rc;
@@ -763,8 +761,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
     h->last_join_gate = 0;
     // the batch-only side work (side_batch_work): beside the head where the cluster BPTT kernels need their sentinel fill, else behind it
     bool fill_needed = false;
-    if (!simple_rec(h))
-        for (int l = 0; l < y.L * y.D; ++l) fill_needed = fill_needed || sbr_rec_cluster_ok(rec_args(h, l));
+    for (int l = 0; l < y.L * y.D; ++l) fill_needed = fill_needed || h->plan[l].needs_fill;
     if (fill_needed) {
         SBR_HIP(hipEventRecord(h->ev_fork, s));
         SBR_HIP(hipStreamWaitEvent(sd, h->ev_fork, 0));
@@ -792,7 +789,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
 static int bptt_args(sbr_handle* h, int pl, const float* dh_last, bool wait_fill, RecArgs* out) {
     const Layout& y = h->lay; const LayerLayout& ly = y.layer[pl];
     RecArgs a = rec_args(h, pl);
-    if (h->fill_done && sbr_rec_cluster_ok(a)) {
+    if (h->fill_done && h->plan[pl].needs_fill) {
         a.sentinel_done = 1;
         if (wait_fill) SBR_HIP(hipStreamWaitEvent(h->stream, h->ev_fill, 0));
     }
@@ -820,7 +817,7 @@ static WgradPlan wgrad_plan(const sbr_handle* h, const LayerLayout& ly, const Re
     // BPTT in time chunks when the bf16x6 kernel runs: dW_hid of a finished chunk is computed on the side
     // stream (190 idle CUs) while the chain continues
     p.slab = (size_t)ly.Hp * GHp;
-    p.nc = (sbr_rec_bwd_chunkable(a, simple_rec(h)) && y.T >= 64 && !sg) ? h->sw.bwd_chunks : 1;
+    p.nc = (plan_of(h, ly).bwd_chunkable && y.T >= 64 && !sg) ? h->sw.bwd_chunks : 1;
     p.nsl = (int)std::min<size_t>(kWgradSlices / p.nc, y.ws2_floats / (p.slab * p.nc));   // K-slices (= workgroups of the wgrad kernel)
     if (p.nsl < 1) p.nc = 1;
     p.side = !simple_rec(h) && !sg && p.nsl >= 1;   // weight gradients on the side stream
@@ -904,7 +901,7 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
     const int n_slabs = std::max(1, std::min(std::min(kTailGemmGroups, cap), pl.n_slabs));      // partials = persistent groups
     const bool upd_here = h->in_train_step;
     if (!serial) a.fence_kb = kTailFenceKb;              // the chain's CUs are its own: the consumers take the other 192
-    SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, false));
+    SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, h->plan[0]));
     mark(h, 4);
     // side stream: output layer first (its gradients are complete on this stream: dW_out GEMM, bias sums)
     const bool out_early = upd_here && (y.cfg.loss == SBR_LOSS_CCE || SBR_LOSS_IS_MARGIN(y.cfg.loss));
@@ -999,7 +996,7 @@ static int backward_chunked(sbr_handle* h, int l, RecArgs& a, const WgradPlan& w
     float* ws2 = h->A(y.a_ws2);
     for (int c = 0; c < nc; ++c) {
         a.t_hi = (int)((long)y.T * (nc - c) / nc); a.t_lo = (int)((long)y.T * (nc - c - 1) / nc); a.chunk = c;
-        SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, false));
+        SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, h->plan[l]));
         // (this layer's main-stream record behind the BPTT launch)
         hipEvent_t ev_chain_end = record_shared(h, h->ev_chunk[c], (l == 0 && c == nc - 1) ? 4 : -1);
         SBR_HIP(hipStreamWaitEvent(sd, ev_chain_end, 0));
@@ -1073,7 +1070,7 @@ static int backward_layer(sbr_handle* h, int l) {
     { const int rc = bptt_args(h, l, top ? h->A(y.a_dhlast) : nullptr, top, &a); if (rc != SBR_OK) return rc; }
     if (top && h->dh_slabs_n > 0) { a.dh_slabs = h->A(y.a_ws); a.n_dh_slabs = h->dh_slabs_n; }      // (sbr_loss_backward_output)
     if (a.prof) a.prof = prof_slot(h, 1);
-    const int nblk = sbr_rec_bwd_blocks(a, simple_rec(h));
+    const int nblk = h->plan[l].bwd_blocks;
     const WgradPlan wp = wgrad_plan(h, ly, a);
     if (l == 0 && y.L == 1 && h->tail_nc >= 2) return backward_tail(h, a, wp, nblk);      // the whole of the layer
     hipStream_t sw = wp.swap ? s : sd;      // weight-gradient GEMM
@@ -1081,7 +1078,7 @@ static int backward_layer(sbr_handle* h, int l) {
     if (wp.nc > 1 || wp.side) {
         const int rc = backward_chunked(h, l, a, wp, nblk, sw, sm); if (rc != SBR_OK) return rc;
     } else {
-        SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, simple_rec(h)));
+        SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, h->plan[l]));
         if (l == 0) mark(h, 4);
         SBR_LAUNCH(reduce_partials(h, s, ly, a, nblk));
         { const int rc = whid_grad_gemm(h, ly, a); if (rc != SBR_OK) return rc; }
@@ -1122,8 +1119,8 @@ static int backward_bi(sbr_handle* h) {
             const int GHp = y.G * ly.Hp;
             RecArgs a;
             { const int rc = bptt_args(h, pl, l == y.L - 1 ? h->A(y.a_dhl[d]) : nullptr, true, &a); if (rc != SBR_OK) return rc; }
-            const int nblk = sbr_rec_bwd_blocks(a, simple_rec(h));
-            SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, simple_rec(h)));
+            const int nblk = h->plan[pl].bwd_blocks;
+            SBR_LAUNCH_CHAIN(1, s, launch_rec_backward(s, a, h->plan[pl]));
             if (l == 0 && d == 1) mark(h, 4);
             SBR_LAUNCH(reduce_partials(h, s, ly, a, nblk));
             { const int rc = whid_grad_gemm(h, ly, a); if (rc != SBR_OK) return rc; }

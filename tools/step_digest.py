@@ -21,9 +21,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "tests")]
 
-QUERIES = ("scatter_form", "step_join_gate", "step_fork_gate", "tail_gate_first", "row_aware_update", "tail_chunks", "rec_kernel")
+QUERIES = ("scatter_form", "step_join_gate", "step_fork_gate", "tail_gate_first", "row_aware_update", "tail_chunks", "rec_kernel",
+           # ... and every other key a layer's RecPlan answers (csrc/sbr_common.h)
+           "fused_gather", "cluster", "rec_rows_fwd", "rec_rows_bwd", "rec_workgroups_fwd", "rec_workgroups_bwd", "rec_products_fwd",
+           "rec_products_bwd")
 STEPS = 3
-FLAGS = dict(SIMPLE_REC=1, SIMPLE_GEMM=2, ATOMIC_SCATTER=4, F32_MFMA=16, SPARSE_UPDATE=32, BF16_PROJECTION=128, BF16_LAYERS=256)
+FLAGS = dict(SIMPLE_REC=1, SIMPLE_GEMM=2, ATOMIC_SCATTER=4, PROFILE_REC=8, F32_MFMA=16, SPARSE_UPDATE=32, BF16_PROJECTION=128, BF16_LAYERS=256)
 
 
 def case(name, family, cell, layers, loss, N, B, T, S=0, env=None, flags=0, updater="adam", reg=0.0, emb=0, bi=False, zipf=False,
@@ -90,6 +93,21 @@ def cases():
                    ("bf16layers", FLAGS["BF16_LAYERS"])):
         out.append(case("flag-%s-GRU128" % nm, "flags", cell="GRU", layers=[128], loss="CCE", N=300, B=64, T=70, scale=0.1, zipf=True, flags=fl, subset=True))
         out.append(case("flag-%s-LSTM-16-12" % nm, "flags", cell="LSTM", layers=[16, 12], loss="CCE", N=41, B=16, T=12, flags=fl))
+    # every recurrent kernel sbr_rec_plan can name (RecKernel, csrc/sbr_common.h) that the cases above do not reach
+    def rec(name, cell, layers, T=12, env=None, flags=0, subset=False):
+        out.append(case("rec-" + name, "rec_" + name.split("-")[0], cell=cell, layers=layers, loss="CCE", N=41, B=16, T=T, env=env, flags=flags,
+                        scale=0.05 if max(layers) > 128 else None, subset=subset))
+    rec("x6q-GRU32", "GRU", [32], subset=True); rec("x6q-LSTM64", "LSTM", [64]); rec("x6q-Vanilla20", "Vanilla", [20])
+    rec("x6s-GRU128", "GRU", [128], env={"SBR_X6_PIPE": "0"}, subset=True); rec("x6s-LSTM50", "LSTM", [50], env={"SBR_X6_PIPE": "0"})
+    rec("x6-GRU50-rpt16", "GRU", [50], env={"SBR_RPT": "16"}, subset=True); rec("x6-GRU50-rpt1", "GRU", [50], env={"SBR_RPT": "1"})
+    rec("x6-LSTM128-rpt16-bwd-mfma", "LSTM", [128], env={"SBR_RPT": "16", "SBR_X6_PIPE": "0"}, subset=True)   # forward rec_fwd_x6, backward rec_bwd_mfma
+    rec("cl8-GRU256", "GRU", [256], T=8, env={"SBR_CL16": "0"}, subset=True)
+    rec("cl8-LSTM512-rows4", "LSTM", [512], T=8, env={"SBR_X6_F16_BWD": "0"})                                  # 4-row backward tiles
+    rec("c16-GRU512", "GRU", [512], T=8, subset=True); rec("c16-GRU512-one-level", "GRU", [512], T=8, env={"SBR_C16_TWO_LEVEL": "0"})
+    rec("mfma-GRU256", "GRU", [256], env={"SBR_CLUSTER": "0"}, subset=True); rec("mfma-GRU300", "GRU", [300], env={"SBR_CLUSTER": "0"})   # 300: two tiles per wave
+    rec("relu-Vanilla-128-128", "Vanilla", [128, 128], subset=True)                                           # a rectifying upper layer
+    rec("prof-GRU32", "GRU", [32], flags=FLAGS["PROFILE_REC"])                                                # out of x6q
+    rec("unfused-GRU128", "GRU", [128], env={"SBR_FUSE_GATHER": "0"})
     names = [c["name"] for c in out]
     assert len(set(names)) == len(names)
     return out
