@@ -171,7 +171,7 @@ int sbr_build_layout(const sbr_config& cfg, Layout& lay, std::string& err) {
     lay.a_sid = take((size_t)T * Bp * lay.F); lay.a_spos = take((size_t)T * Bp * lay.F);
     {   // wide index-input rows: the partial rows of the long segments' pieces (launch_scatter_wide)
         const int ghp0 = G * lay.layer[0].Hp;
-        const bool wide0 = !lay.E && ghp0 >= 512 && ghp0 <= 8192;
+        const bool wide0 = sbr_scatter_wide_rows(lay.E ? lay.Ep : 0, ghp0);
         lay.sr_slots = wide0 ? std::max(sbr_scatter_wide_slots((size_t)T * Bp * lay.F), 2 * SBR_SCAT_RANGES) : 0;
         lay.a_srpart = wide0 ? take((size_t)lay.sr_slots * ghp0) : 0;
         lay.a_srid = wide0 ? take((size_t)lay.sr_slots * 4 + 8) : 0;
@@ -403,6 +403,10 @@ extern "C" int sbr_create(const sbr_config* cfg, void* arena, size_t arena_bytes
     h->rpt = sw.rpt;
     if (h->rpt != 1 && h->rpt != 2 && h->rpt != 4 && h->rpt != 8 && h->rpt != 16) { h->rpt = 4; while (h->rpt < 16 && h->lay.Bp / h->rpt > 256) h->rpt <<= 1; }
     plan_layers(h);      // every layer's recurrent kernel: the layout, the switches, the flags and rpt are all it depends on
+    plan_tail(h);        // ... the overlapped tail's time chunks, and the form of layer 0's scatter-add: the same inputs
+    const Layout& y = h->lay;
+    h->scat = sbr_scat_plan(y.G * y.layer[0].Hp, y.E ? y.Ep : 0, y.cfg.input_size, y.T * y.Bp * y.F, y.D, (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) != 0,
+                            sw.scat_range, sw.tail_scatter_lds, h->tail_chunks, kTailScatterUnits, y.sr_slots);
     if (sw.tail_trace) {      // tools/tail_trace.py
         if (hipMalloc(&h->tail_trace, 16384 * sizeof(unsigned long long)) != hipSuccess) h->tail_trace = nullptr;
         else (void)hipMemset(h->tail_trace, 0, 16384 * sizeof(unsigned long long));
@@ -850,56 +854,6 @@ extern "C" int sbr_debug_occupy(sbr_handle* h, int workgroups, int lds_kb, int m
     return SBR_OK;
 }
 
-// the stand-alone scatter-add of layer 0's embedding gradient over the current batch, timed on its own (include/sbr_rnn.h)
-extern "C" int sbr_debug_scatter(sbr_handle* h, int reps, float* us, int64_t* entries, int64_t* rows) {
-    CHECK_ARG(h && us && reps >= 1 && reps <= 1000, "bad argument");
-    const Layout& y = h->lay;
-    if (!h->have_batch || y.E || y.D != 1) { sbr_set_error("sbr_debug_scatter: needs a batch and an index-input, one-direction layer 0"); return SBR_ESTATE; }
-    const LayerLayout& ly = y.layer[0];
-    const int GHp = y.G * ly.Hp;
-    hipStream_t s = h->stream;
-    SBR_HIP(hipDeviceSynchronize());                      // nothing beside it
-    const SbrSortKeys k = sort_keys(h, 0);
-    SBR_LAUNCH(launch_scatter_sort(s, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, k.cnt, k.off, k.cur, k.sid, k.pos, 0, 0, 1, nullptr,
-                                   &h->scnt_zero_n));
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    SBR_HIP(hipEventCreate(&e0)); SBR_HIP(hipEventCreate(&e1));
-    float* dW = h->Gd(ly.p_Win);
-    const float* dxt = h->A(ly.a_dxt);
-    const int range_on = h->sw.scat_range;
-    auto one = [&]() -> int {
-        hipError_t se = hipSuccess;
-        if (range_on == 1 && y.a_srpart && GHp <= 1024 &&
-            launch_scatter_range(s, dW, dxt, k.sid, k.pos, k.off, y.cfg.input_size, GHp, h->A(y.a_srpart), (int*)h->A(y.a_srid), SBR_SCAT_RANGES, &se)) { SBR_LAUNCH(se); }
-        else if (range_on == 2 && y.a_srpart &&
-                 launch_scatter_wide(s, dW, dxt, k.sid, k.pos, k.off, y.cfg.input_size, y.T * y.Bp * y.F, GHp, h->A(y.a_srpart), (int*)h->A(y.a_srid), y.sr_slots, &se)) { SBR_LAUNCH(se); }
-        else SBR_LAUNCH(launch_scatter_reduce(s, dW, dxt, k.sid, k.pos, k.off, y.cfg.input_size, y.T * y.Bp * y.F, GHp, y.Bp));
-        return SBR_OK;
-    };
-    for (int i = 0; i < 2; ++i) { const int rc = one(); if (rc != SBR_OK) return rc; }
-    SBR_HIP(hipEventRecord(e0, s));
-    for (int i = 0; i < reps; ++i) { const int rc = one(); if (rc != SBR_OK) return rc; }
-    SBR_HIP(hipEventRecord(e1, s));
-    SBR_HIP(hipEventSynchronize(e1));
-    float ms = 0.f;
-    SBR_HIP(hipEventElapsedTime(&ms, e0, e1));
-    *us = ms * 1000.0f / (float)reps;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (entries || rows) {
-        std::vector<int> off((size_t)y.cfg.input_size + 1);
-        SBR_HIP(hipMemcpy(off.data(), k.off, off.size() * sizeof(int), hipMemcpyDeviceToHost));
-        int64_t nr = 0;
-        for (int i = 0; i < y.cfg.input_size; ++i) nr += off[i + 1] > off[i];
-        if (entries) *entries = off[y.cfg.input_size];
-        if (rows) *rows = nr;
-    }
-    // the gradient block as a step expects it: zero (the rows the scatter-add wrote, i.e. the whole block)
-    SBR_HIP(hipMemsetAsync(dW, 0, (size_t)y.cfg.input_size * GHp * sizeof(float), s));
-    SBR_HIP(hipStreamSynchronize(s));
-    h->tail_sorted = false;
-    return SBR_OK;
-}
-
 extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     CHECK_ARG(h && what && value, "null argument");
     const Layout& y = h->lay; const std::string w(what);
@@ -937,11 +891,11 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
         *value = w.rfind("rec_products_", 0) == 0 ? (bwd ? top.products_bwd : top.products_fwd)
                : w.rfind("rec_rows_", 0) == 0 ? (bwd ? top.bwd_rows : top.fwd_rows) : (bwd ? top.bwd_wgs : top.fwd_wgs);
     }
-    else if (w == "tail_chunks") { int ch = 0; *value = tail_plan(h, &ch); }      // time chunks of the overlapped step tail (0: not taken)
+    else if (w == "tail_chunks") *value = h->tail_chunks;      // time chunks of the overlapped step tail (0: not taken)
     // ... whose consumers really run on the side streams (SBR_TAIL_OVERLAP=2 keeps them on the main stream: a data-parallel driver
     // must then not order a collective behind a side stream that produces nothing)
-    else if (w == "tail_streams") { int ch = 0; *value = (tail_plan(h, &ch) >= 2 && h->sw.tail_overlap == 1) ? 1 : 0; }
-    else if (w == "tail_last_steps") { int ch = 0; *value = tail_plan(h, &ch) >= 2 ? h->tail_bounds.lo[1] : 0; }   // time steps of chunk 0 (behind the chain)
+    else if (w == "tail_streams") *value = (h->tail_chunks >= 2 && h->sw.tail_overlap == 1) ? 1 : 0;
+    else if (w == "tail_last_steps") *value = h->tail_chunks >= 2 ? h->tail_bounds.lo[1] : 0;   // time steps of chunk 0 (behind the chain)
     else if (w == "side_stream2") *value = (int64_t)(intptr_t)h->side2;
     else if (w == "tail_chain_cycles" || w == "tail_chain_ticks") {      // last overlapped-tail BPTT launch: shader cycles / 100 MHz ticks
         unsigned long long c[2] = {0, 0};

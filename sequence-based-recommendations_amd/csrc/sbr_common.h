@@ -133,11 +133,6 @@ void sbr_param_descs(const Layout& lay, std::vector<ParamDesc>& out);
 // belongs to it can only start at the chain's end -- so the chunks shrink geometrically towards t = 0.
 #define SBR_TCHUNKS_MAX 9
 struct SbrTChunks { int n; int lo[SBR_TCHUNKS_MAX + 1]; };
-static inline SbrTChunks sbr_uniform_tchunks(int tch, int n) {
-    SbrTChunks tc; tc.n = tch > 0 ? n : 0;
-    for (int c = 0; c <= SBR_TCHUNKS_MAX; ++c) tc.lo[c] = tch * (c < n ? c : n);
-    return tc;
-}
 // ---------------------------------------------------------------------------------------
 // Tuned constants of the step.  Each was an environment switch while it was being measured (rounds 1 - 5) and is fixed since
 // round 6; the A/B numbers are in profiles/round2_b_tail_variants.txt, round3_*_variants.txt, round4_variants.txt,
@@ -163,9 +158,30 @@ constexpr int kTailGateSleep = 32;        // ... whose polls of ONE word are thi
 // the boundary between two such steps (profiles/step_boundary_variants.txt): no event on the main stream
 constexpr bool kStepJoinGate = true;      // step end: a one-wave gate on the completion words of the two consumer streams joins them
 constexpr bool kStepForkGate = true;      // step start: the second side stream (and the batch builder) wait for the forward chain's start word
-// growth of the small time chunks near t = 0 (tail_plan, sbr_step.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
+// growth of the small time chunks near t = 0 (plan_tail, sbr_step.hip): 6, 10, 15, 25 steps for the LDS-row scatter-add, which
 // walks them one after the other; 1, 3, 7, 18 for the polling range form
 static inline double sbr_tail_geom(int scatter_lds) { return scatter_lds ? 1.6 : 2.6; }
+
+// ScatPlan: the form of the scatter-add of layer 0's index-input gradient and its launch recipe, chosen once per engine (sbr_scat_plan,
+// sbr_scatter.hip, called by sbr_create).  ScatForm's values are what sbr_query "scatter_form" reports: sorted
+// segment reduce, range form, segment-parallel form, per-element atomics; in an overlapped tail the polling reduce or the LDS rows.
+enum ScatForm { SCAT_REDUCE = 0, SCAT_RANGE = 1, SCAT_WIDE = 2, SCAT_ATOMIC = 3, SCAT_POLL = 4, SCAT_LDS = 5 };
+struct ScatReduce { int nv; bool comb; };      // form 0's recipe: 16-byte pieces per lane; the combining kernel or the walk (nv 0: no kernel)
+struct ScatPlan {
+    ScatForm plain = SCAT_REDUCE, tail = SCAT_POLL;      // over the plain-key sort (or without a sort): 0 .. 3; inside an overlapped tail: 4 or 5
+    ScatReduce reduce = {0, false};   // form 0, also for the rows of an embedding table in front of layer 0 (emb_grad_scatter)
+    int range_nv = 0, wide_nvw = 0, wide_nvb = 0;      // form 1: pieces per thread; form 2: per lane of the heads' waves, per thread of the other two kernels
+    int poll_nv = 0;                  // form 4: pieces per lane
+    int lds_nv = 0, floor_cost = 0, rows_lds = 0;      // form 5: pieces per lane, cost floor of an id, LDS rows of a unit
+    bool wide_rows = false;           // index-input rows of 512 .. 8192 floats with their partial-row slab (forms 1, 2; the row-aware update)
+};
+// index-input rows that get a partial-row slab (Layout.a_srpart, a_srid); Ep: width of an embedding table in front of layer 0, 0: none
+static inline bool sbr_scatter_wide_rows(int Ep, int GHp) { return !Ep && GHp >= 512 && GHp <= 8192; }
+// partial-row slots launch_scatter_wide can claim for max_entries sorted entries (the slab has at least as many)
+static inline int sbr_scatter_wide_slots(size_t max_entries) { return (int)(max_entries / 64 + max_entries / 65 + 2); }
+ScatReduce sbr_scat_reduce_recipe(int row_floats);
+ScatPlan sbr_scat_plan(int GHp, int Ep, int n_ids, int entries, int D, bool atomic, int scat_range, int tail_scatter_lds,
+                       int tail_chunks, int units, int part_slots);
 // sbr_rank (sbr_rank.hip): where its two pairs of regimes change
 constexpr int kRankThreads = 1024;        // threads of a row's workgroup in the select and sort kernels (16 waves: one id segment each)
 constexpr int kRankLdsRow = 32768;        // longest row whose keys stay in LDS during the select (128 KB of the CU's 160 KB; C4's 26 744 fits)
@@ -256,6 +272,7 @@ struct RecPlan {
 struct sbr_handle {
     Layout lay;
     SbrSwitches sw;
+    ScatPlan scat;                           // layer 0's scatter-add (sbr_scat_plan, behind plan_layers and plan_tail)
     RecPlan plan[2 * SBR_MAX_LAYERS] = {};   // [l * D + d], like Layout.layer: filled by plan_layers at the end of sbr_create
     float* arena = nullptr; bool own_arena = false;
     hipStream_t stream = nullptr;
@@ -307,8 +324,9 @@ struct sbr_handle {
     bool grads_clean = false;    // the gradient section is all zero (fresh arena, or the update kernel cleared it)
     bool timing = false;
     unsigned timing_marks = 0;   // which of the SBR_N_PHASES event marks a step records (sbr_enable_timing)
-    int tail_nc = 0, tail_ch = 0;   // this step: time chunks of the sort's keys / steps per chunk (0: plain keys)
-    SbrTChunks tail_bounds = {};    // ... and their bounds (tail_plan)
+    int tail_chunks = 0, tail_ch = 0;   // the overlapped tail as sbr_create planned it (plan_tail): time chunks of the sort's keys (0: not taken), steps per chunk
+    SbrTChunks tail_bounds = {};        // ... and their bounds
+    int tail_nc = 0;                    // this step: tail_chunks for a training step, 0 (plain keys) for any other forward
     unsigned long long* tail_trace = nullptr;    // SbrSwitches.tail_trace: SbrPoll.trace
     bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
     // sbr_rank: scratch outside the arena (grown on demand, freed by sbr_destroy) and what the last call ran (sbr_query "rank_select" / "rank_sort")
@@ -317,7 +335,6 @@ struct sbr_handle {
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
-    bool tail_cost_scanned = false;                                       // this step's sort was followed by launch_scatter_cost_scan
     int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
     std::vector<int> tail_slab_host; int* tail_slab_dev = nullptr; int tail_slab_key[2] = {0, 0};   // the table of the last plan
     int prog_epoch = 0;          // epoch of the chain's progress words: advanced once per step by tail_next_epoch (sbr_step.hip)
@@ -402,7 +419,7 @@ int forward_current(sbr_handle* h);                  // (sbr_rank_api.hip) forwa
 // step (sbr_step.hip), and the one layout piece the step takes from there
 struct RecArgs; struct SbrSparseRows; struct SbrSparseUpd;
 void plan_layers(sbr_handle* h);                     // fills h->plan from the layout, the switches and the flags (sbr_create, once)
-int tail_plan(sbr_handle* h, int* ch_out);           // overlapped step tail: time chunks of a step (0: not taken), steps per chunk; fills h->tail_bounds
+void plan_tail(sbr_handle* h);                       // overlapped step tail: fills h->tail_chunks / tail_ch / tail_bounds (sbr_create, once, behind plan_layers)
 bool head_sampled_taken(const sbr_handle* h, int rows);   // does a step over `rows` rows take the one-launch sampled head?
 void mark(sbr_handle* h, int i);                     // timing mark i of the step in flight, on the main stream
 SbrSparseRows sparse_rows(sbr_handle* h, int b);     // row-sparse block b: where its rows, gradients, state and last-step words are
@@ -450,7 +467,7 @@ hipError_t launch_scatter_rows(hipStream_t s, float* dWin, const float* dxt, con
 // chunk of 32 sorted entries reduces the dxt rows of equal id in registers
 // concat != 0: entry (pos, f) addresses row pos*F + f of the gradient array (embedding layer: the F embeddings of a step are
 // concatenated, not summed)
-// tch > 0: time-chunked keys (t / tch) * n_ids + id over n_tchunks chunks (cnt / offs / cur then hold n_tchunks * n_ids + 1 ints)
+// tch > 0: time-chunked keys chunk(t) * n_ids + id over the n_tchunks chunks of *bounds (cnt / offs / cur then hold n_tchunks * n_ids + 1 ints)
 hipError_t launch_scatter_sort(hipStream_t s, const int* X, const int* len, int T, int Bp, int F, int n_ids, int* cnt,
                                int* offs, int* cur, int* sid, int* spos, int concat = 0, int tch = 0, int n_tchunks = 1, const SbrTChunks* bounds = nullptr,
                                int* cnt_zero_n = nullptr);
@@ -477,33 +494,32 @@ hipError_t launch_split_cols(hipStream_t s, const float* src, float* a, float* b
 // (out_b == NULL: W arbitrary, only the sum d is written to out_f -- the embedding case)
 hipError_t launch_uncat(hipStream_t s, const float* f, const float* r, const int* len, float* out_f, float* out_b, int T, int Bp,
                         int W, int Hp);
-// wide rows (G*Hp >= 512), form 1: range scatter-add, two passes, no atomics (sbr_misc.hip); false: not served
-bool launch_scatter_range(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs, int n_ids,
-                          int GHp, float* part, int* part_id, int n_ranges, hipError_t* err);
+// The scatter-add of the sorted entries (sbr_scatter.hip): the launchers take the form's recipe from the engine's ScatPlan as given.
+// form 1, wide rows (512 .. 1024 floats): range scatter-add, two passes, no atomics
+hipError_t launch_scatter_range(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs, int n_ids,
+                                int GHp, float* part, int* part_id, int n_ranges, const ScatPlan& plan);
 #define SBR_SCAT_RANGES 512
-// form 2: segment-parallel scatter-add, no atomics on rows; false: not served
-bool launch_scatter_wide(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs, int n_ids,
-                         int max_entries, int GHp, float* part, int* aux, int n_slots, hipError_t* err);
+// form 2 (512 .. 2048 floats): segment-parallel scatter-add, no atomics on rows
+hipError_t launch_scatter_wide(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs, int n_ids,
+                               int max_entries, int GHp, float* part, int* aux, int n_slots, const ScatPlan& plan);
 // arguments of the optimizer step of a block's rows (update_rows_aware_kernel, out_grad_step_kernel): p / s0 / s1 = parameter and
 // optimizer-state rows (s1 NULL where the updater has one state array); the arithmetic is update_kernel's, element for element
 struct SbrScatStep { float* p; float* s0; float* s1; int* last; int updater, t_to; float lr, rho, b1, b2, a_t; };
-// partial-row slots launch_scatter_wide can claim for max_entries sorted entries (the caller's slab has at least as many)
-static inline int sbr_scatter_wide_slots(size_t max_entries) { return (int)(max_entries / 64 + max_entries / 65 + 2); }
-// key_lo / accumulate: the entries of the keys [key_lo, key_lo + n_ids) of a time-chunked sort, ADDED to dWin
+// form 0: one wave per 32 sorted entries sums the rows of equal id in registers
 hipError_t launch_scatter_reduce(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos,
-                                 const int* offs, int n_ids, int max_entries, int GHp, int Bp, int key_lo = 0, bool accumulate = false, int acc_chunk = 32);
-// all time chunks of a time-chunked sort in ONE launch beside the running chain: every wave waits for poll.done to reach the
-// time chunk of its entries (tch steps per chunk), rows are added with float atomics (an id may occur in every chunk)
-// the same without a global atomic per piece: `units` workgroups own id ranges of equal cost (P: n_ids + 1 ints of workspace, the
-// running cost) and accumulate their rows in LDS (sbr_misc.hip).  false = shape not supported, nothing launched.
-bool launch_scatter_cost_scan(hipStream_t s, const int* offs, int* P, int n_ids, int n_tchunks, int max_entries, int GHp, int units,
-                              hipError_t* err);
-hipError_t launch_tail_monitor(hipStream_t s, const SbrPoll& poll, int t_lo);
-bool launch_scatter_lds_poll(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs, const int* P,
-                             int n_ids, int n_tchunks, int max_entries, int GHp, const SbrPoll& poll, const SbrTChunks& bounds,
-                             int units, hipError_t* err, bool monitor = false, int t_lo = 0);      // monitor: one more workgroup, the tail's monitor
+                                 const int* offs, int n_ids, int max_entries, int GHp, int Bp, const ScatReduce& recipe);
+// form 4: all time chunks of a time-chunked sort in ONE launch beside the running chain: every wave waits for poll.done to reach the
+// time chunk of its entries, rows are added with float atomics (an id may occur in every chunk)
 hipError_t launch_scatter_reduce_poll(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs,
-                                      int n_ids, int n_tchunks, int tch, int max_entries, int GHp, int Bp, const SbrPoll& poll, int first_key = 0, const SbrTChunks* bounds = nullptr, int short_chunks = 0, bool fence_on = false);
+                                      int n_ids, int n_tchunks, int max_entries, int GHp, int Bp, const SbrPoll& poll,
+                                      const SbrTChunks& bounds, int short_chunks, bool fence_on, const ScatPlan& plan);
+// form 5: the same without a global atomic per piece: `units` workgroups own id ranges of equal cost (P: n_ids + 1 ints of workspace,
+// the running cost, which launch_scatter_cost_scan leaves behind the time-chunked sort) and accumulate their rows in LDS
+hipError_t launch_scatter_cost_scan(hipStream_t s, const int* offs, int* P, int n_ids, int n_tchunks, const ScatPlan& plan);
+hipError_t launch_scatter_lds_poll(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs, const int* P,
+                                   int n_ids, int n_tchunks, int GHp, const SbrPoll& poll, const SbrTChunks& bounds,
+                                   int units, const ScatPlan& plan, bool monitor = false, int t_lo = 0);      // monitor: one more workgroup, the tail's monitor
+hipError_t launch_tail_monitor(hipStream_t s, const SbrPoll& poll, int t_lo);
 
 // Tile-blocked activation layout [t][row tile of 16][column tile of 16][row 16][col 16] (floats):
 // the 16x16 tile one wave of the recurrent kernels owns is one contiguous KiB (8 full 128-B lines per

@@ -80,4 +80,32 @@ __device__ __forceinline__ void poll_sleep(int gap) {
     const int n = min(gap >> 2, 16);
     for (int i = 0; i < n; ++i) __builtin_amdgcn_s_sleep(32);
 }
+// the monitor's loop (one workgroup of 256 threads): tail_monitor_kernel (sbr_misc.hip, see there) and workgroup 0 of
+// scat_lds_kernel (sbr_scatter.hip) run this very code
+__device__ __forceinline__ void tail_monitor_loop(const SbrPoll& pl, int t_lo) {
+    __shared__ int s_part[4];
+    const int tid = threadIdx.x, tag = pl.epoch;
+    int last = 0x1000;
+    const unsigned long long t0 = wall_clock64();
+    for (;;) {
+        int m = 0;
+        for (int i = tid; i < pl.n; i += 256) {
+            const int v = __hip_atomic_load(pl.words + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            m = max(m, (v >> 12) == tag ? (v & 0xfff) : 0xfff);          // (a wave that has not published this step yet: nothing complete)
+        }
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) m = max(m, __shfl_xor(m, o));
+        if ((tid & 63) == 0) s_part[tid >> 6] = m;
+        __syncthreads();
+        m = max(max(s_part[0], s_part[1]), max(s_part[2], s_part[3]));
+        __syncthreads();
+        if (m != last && m != 0xfff) {
+            if (tid < SBR_DONE_COPIES) __hip_atomic_store(pl.done + tid * SBR_DONE_STRIDE, (tag << 12) | m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            last = m;
+        }
+        if (m <= t_lo) break;
+        if (wall_clock64() - t0 > SBR_POLL_TICKS) { if (tid == 0) atomicOr(pl.fault, 8); break; }
+        __builtin_amdgcn_s_sleep(4);
+    }
+}
 }  // namespace

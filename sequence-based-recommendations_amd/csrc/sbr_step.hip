@@ -81,19 +81,20 @@ bool head_sampled_taken(const sbr_handle* h, int rows) {
     return h->sw.head_fuse && !simple_gemm(h) && y.D == 1 && !(y.cfg.flags & SBR_FLAG_F32_MFMA) &&
            sbr_head_sampled_ok(rows, y.C, y.HLt, y.cfg.loss);
 }
-// Overlapped step tail: time chunks for this step (0 = not taken) and steps per chunk.  Taken for a single index-input layer
-// served by rec_bwd_x6p's progress-publishing form, dense updates, the bf16x6 weight-gradient GEMM and one BPTT launch.
-int tail_plan(sbr_handle* h, int* ch_out) {
+// Overlapped step tail, planned once inside sbr_create (behind plan_layers): time chunks of a training step (h->tail_chunks, 0 = not
+// taken), steps per chunk and the chunks' bounds.  Taken for a single index-input layer served by rec_bwd_x6p's progress-publishing
+// form, dense updates, the bf16x6 weight-gradient GEMM and one BPTT launch.
+void plan_tail(sbr_handle* h) {
     const Layout& y = h->lay;
-    *ch_out = 0;
-    if (!h->sw.tail_overlap || y.tail_keys < 2 || y.n_sparse || h->sw.bwd_chunks != 1) return 0;
-    if (!h->plan[0].tail_ok || simple_gemm(h) || (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER)) return 0;      // (tail_ok: never triage or exact-f32 kernels)
+    h->tail_chunks = h->tail_ch = 0;
+    if (!h->sw.tail_overlap || y.tail_keys < 2 || y.n_sparse || h->sw.bwd_chunks != 1) return;
+    if (!h->plan[0].tail_ok || simple_gemm(h) || (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER)) return;      // (tail_ok: never triage or exact-f32 kernels)
     int nc = std::min(std::min(y.tail_keys, kTailChunksMax), y.T / 16);
-    if (nc < 2) return 0;
+    if (nc < 2) return;
     const int ch = (y.T + nc - 1) / nc;
     nc = (y.T + ch - 1) / ch;
-    if (nc < 2) return 0;
-    *ch_out = ch;
+    if (nc < 2) return;
+    h->tail_chunks = nc; h->tail_ch = ch;
     // Chunk bounds.  The scatter-add of a time chunk can start when the chain has left it, and the chain leaves chunk 0 last:
     // with equal chunks an eighth of the step's entries waits for the chain's end (30 - 45 us of polling waves behind it,
     // profiles/round3_c_timeline.txt).  So the chunks near t = 0 are small -- 1, 3, 7, 18 ... steps (powers of sbr_tail_geom,
@@ -119,7 +120,6 @@ int tail_plan(sbr_handle* h, int* ch_out) {
         pw *= geom > 1.0 ? geom : 1.0;
     }
     for (int c = nc; c <= SBR_TCHUNKS_MAX; ++c) tc.lo[c] = y.T;
-    return nc;
 }
 
 // The one place where the epoch of the chain's progress words advances: once per step, in front of whatever is launched first
@@ -152,25 +152,14 @@ SbrSortKeys sort_keys(const sbr_handle* h, int dir) {
 // entries of the sort: every (position, feature) pair of the padded batch
 static inline int sort_entries(const Layout& y) { return y.T * y.Bp * y.F; }
 
-// behind the time-chunked sort of an overlapped tail (second side stream): the running cost of the ids, for the LDS-row scatter-add
-static int tail_cost_scan(sbr_handle* h) {
-    const Layout& y = h->lay;
-    h->tail_cost_scanned = false;
-    if (!h->sw.tail_scatter_lds) return SBR_OK;
-    hipError_t e = hipSuccess;
-    if (launch_scatter_cost_scan(h->side2, sort_keys(h, 0).off, (int*)h->A(y.a_sP), y.cfg.input_size, h->tail_nc, sort_entries(y),
-                                 y.G * y.layer[0].Hp, kTailScatterUnits, &e)) {
-        if (e != hipSuccess) { sbr_set_error("HIP launch failed: %s", hipGetErrorString(e)); return SBR_EHIP; }
-        h->tail_cost_scanned = true;
-    }
-    return SBR_OK;
-}
-// the time-chunked sort of an overlapped tail and the ids' running cost, on the second side stream, which consumes them
+// the time-chunked sort of an overlapped tail and (LDS-row scatter-add) the ids' running cost, on the second side stream, which consumes them
 static int tail_sort(sbr_handle* h) {
     const Layout& y = h->lay; const SbrSortKeys k = sort_keys(h, 0);
     SBR_LAUNCH(launch_scatter_sort(h->side2, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, k.cnt, k.off, k.cur, k.sid, k.pos, 0,
                                    h->tail_ch, h->tail_nc, &h->tail_bounds, &h->scnt_zero_n));
-    return tail_cost_scan(h);
+    if (h->scat.tail == SCAT_LDS)
+        SBR_LAUNCH(launch_scatter_cost_scan(h->side2, k.off, (int*)h->A(y.a_sP), y.cfg.input_size, h->tail_nc, h->scat));
+    return SBR_OK;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -338,7 +327,7 @@ static int emb_grad_scatter(sbr_handle* h) {
     const Layout& y = h->lay; const SbrSortKeys k = sort_keys(h, 0);
     SBR_HIP(hipStreamWaitEvent(h->stream, h->ev_sort, 0));
     SBR_LAUNCH(launch_scatter_reduce(h->stream, h->Gd(y.p_Emb), h->A(y.a_demb), k.sid, k.pos, k.off, y.cfg.input_size, sort_entries(y),
-                                     y.Ep, y.Bp));
+                                     y.Ep, y.Bp, h->scat.reduce));
     return SBR_OK;
 }
 
@@ -475,7 +464,7 @@ extern "C" int sbr_forward(sbr_handle* h) {
         for (int b = 0; b < y.n_sparse; ++b)
             if (y.sparse[b].kind == 0)
                 SBR_LAUNCH(launch_sparse_catch_up_batch(s, sparse_rows(h, b), sparse_upd(h), h->bX, h->blen, y.T, y.Bp, y.F, (int)h->step_count));
-    h->tail_nc = h->step_open ? tail_plan(h, &h->tail_ch) : 0;      // overlapped tail for this step? (never for predict / top-k)
+    h->tail_nc = h->step_open ? h->tail_chunks : 0;      // overlapped tail for this step? (never for predict / top-k)
     const bool training = h->step_open;
     h->step_open = false;
     h->tail_sorted = false;
@@ -875,7 +864,7 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
     const int GHp = y.G * ly.Hp;
     const size_t slab = wp.slab;
     float* ws2 = h->A(y.a_ws2);
-    const int tnc = h->tail_nc, CH = h->tail_ch;
+    const int tnc = h->tail_nc;
     // SBR_TAIL_OVERLAP=2: the same kernels, all on the main stream behind the chain (nothing has to run concurrently):
     // for tools that serialise kernels (rocprofv3 --pmc) and for triage
     const bool serial = h->sw.tail_overlap == 2;
@@ -909,7 +898,7 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
         SBR_LAUNCH(step_range(h, sd, y.p_split, y.n_params));
     // the monitor: on a stream of its own behind nothing but the chain's first progress words (its own loop waits for them)
     // ... unless the scatter-add launch carries it (default where that launch is the LDS-row one and has its own stream)
-    const bool mon_in_units = !serial && h->tail_cost_scanned;
+    const bool mon_in_units = !serial && h->scat.tail == SCAT_LDS;
     if (!mon_in_units) SBR_LAUNCH(launch_tail_monitor(serial ? s : h->side3, pl, a.t_lo));
     if (!gated) SBR_LAUNCH(launch_tail_gate(sd, words, nwaves, a.prog_epoch, y.T, a.fault));      // (else: at the head of this stream)
     {
@@ -927,16 +916,13 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
     // (tried and dropped: the last time chunk as a launch of its own behind the polling one, one wave per 16 entries on the
     // then idle chip -- the hot rows' atomics serialise there: 23 us for 6400 entries, profiles/round3_variants.txt call d)
     const SbrSortKeys k = sort_keys(h, 0);
-    hipError_t se = hipSuccess;
-    if (h->tail_cost_scanned && launch_scatter_lds_poll(s2, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, (const int*)h->A(y.a_sP),
-                                                       y.cfg.input_size, tnc, sort_entries(y), GHp, pl, h->tail_bounds, kTailScatterUnits, &se,
-                                                       mon_in_units, a.t_lo)) {
-        SBR_LAUNCH(se); h->last_scatter_form = 5;
-    } else {
-        h->last_scatter_form = 4;
-        SBR_LAUNCH(launch_scatter_reduce_poll(s2, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, y.cfg.input_size, tnc, CH, sort_entries(y),
-                                              GHp, y.Bp, pl, 0, &h->tail_bounds, kTailShortChunks, !serial && kTailFenceKb > 0));
-    }
+    h->last_scatter_form = h->scat.tail;
+    if (h->scat.tail == SCAT_LDS)
+        SBR_LAUNCH(launch_scatter_lds_poll(s2, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, (const int*)h->A(y.a_sP), y.cfg.input_size, tnc,
+                                           GHp, pl, h->tail_bounds, kTailScatterUnits, h->scat, mon_in_units, a.t_lo));
+    else
+        SBR_LAUNCH(launch_scatter_reduce_poll(s2, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, y.cfg.input_size, tnc, sort_entries(y),
+                                              GHp, y.Bp, pl, h->tail_bounds, kTailShortChunks, !serial && kTailFenceKb > 0, h->scat));
     // Step end without an event wait (kStepJoinGate; single-call step): behind the last kernel of either consumer stream a
     // one-lane kernel stores a completion word of this step's epoch at its entry (kernel to kernel on one queue: no gap), and
     // ONE gate on both words, behind this stream's own last kernel, is the join.  The events are still recorded on their
@@ -1031,33 +1017,67 @@ static int backward_chunked(sbr_handle* h, int l, RecArgs& a, const WgradPlan& w
     return SBR_OK;
 }
 
-// the gradient of layer 0's index-input rows on stream sm: per-element atomics, or one of the forms over the plain-key sort
-// (sbr_query "scatter_form": 3 / 1 the range form / 2 the segment-parallel form / 0 the sorted segment reduce)
+// The gradient of the index-input rows of layer 0 (direction dir: layer ly, its dxt) in the form h->scat.plain, on stream st: per-element
+// atomics over the ids themselves, or one of the forms over the plain-key sort of that direction's ids.  The one launch site of these
+// forms: the step (layer0_scatter, backward_bi) and sbr_debug_scatter.
+static int scatter_plain(sbr_handle* h, hipStream_t st, int dir, const LayerLayout& ly, const float* dxt) {
+    const Layout& y = h->lay; const ScatPlan& p = h->scat;
+    const int GHp = y.G * ly.Hp, n_ids = y.cfg.input_size;
+    float* dW = h->Gd(ly.p_Win);
+    const SbrSortKeys k = sort_keys(h, dir);
+    float* part = h->A(y.a_srpart); int* aux = (int*)h->A(y.a_srid);
+    if (p.plain == SCAT_ATOMIC) SBR_LAUNCH(launch_scatter_rows(st, dW, dxt, dir ? (const int*)h->A(y.a_Xr) : h->bX, h->blen, y.T, y.Bp, y.F, GHp));
+    else if (p.plain == SCAT_RANGE) SBR_LAUNCH(launch_scatter_range(st, dW, dxt, k.sid, k.pos, k.off, n_ids, GHp, part, aux, SBR_SCAT_RANGES, p));
+    else if (p.plain == SCAT_WIDE) SBR_LAUNCH(launch_scatter_wide(st, dW, dxt, k.sid, k.pos, k.off, n_ids, sort_entries(y), GHp, part, aux, y.sr_slots, p));
+    else SBR_LAUNCH(launch_scatter_reduce(st, dW, dxt, k.sid, k.pos, k.off, n_ids, sort_entries(y), GHp, y.Bp, p.reduce));
+    return SBR_OK;
+}
+// ... of a one-direction step: the sorted forms on stream sm (the atomics stay on the main stream); sbr_query "scatter_form"
 static int layer0_scatter(sbr_handle* h, const RecArgs& a, hipStream_t sm) {
-    const Layout& y = h->lay; const LayerLayout& ly = y.layer[0];
     hipStream_t s = h->stream;
+    const bool sorted = h->scat.plain != SCAT_ATOMIC;
+    if (sorted && sm == s) SBR_HIP(hipStreamWaitEvent(s, h->ev_sort, 0));      // (the sort ran on the side stream)
+    h->last_scatter_form = h->scat.plain;
+    return scatter_plain(h, sorted ? sm : s, 0, h->lay.layer[0], a.dxt);
+}
+
+// the stand-alone scatter-add of layer 0's embedding gradient over the current batch, timed on its own (include/sbr_rnn.h)
+extern "C" int sbr_debug_scatter(sbr_handle* h, int reps, float* us, int64_t* entries, int64_t* rows) {
+    CHECK_ARG(h && us && reps >= 1 && reps <= 1000, "bad argument");
+    const Layout& y = h->lay;
+    if (!h->have_batch || y.E || y.D != 1) { sbr_set_error("sbr_debug_scatter: needs a batch and an index-input, one-direction layer 0"); return SBR_ESTATE; }
+    const LayerLayout& ly = y.layer[0];
     const int GHp = y.G * ly.Hp;
-    if (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) {
-        SBR_LAUNCH(launch_scatter_rows(s, h->Gd(ly.p_Win), a.dxt, h->bX, a.len, y.T, y.Bp, y.F, GHp));
-        h->last_scatter_form = 3;
-        return SBR_OK;
-    }
-    if (sm == s) SBR_HIP(hipStreamWaitEvent(s, h->ev_sort, 0));      // (the sort ran on the side stream)
+    hipStream_t s = h->stream;
+    SBR_HIP(hipDeviceSynchronize());                      // nothing beside it
     const SbrSortKeys k = sort_keys(h, 0);
-    hipError_t se = hipSuccess;
-    const int range_on = h->sw.scat_range;      // (SbrSwitches: 1 the range form up to 1024-float rows, 2 the segment-parallel form, 0 neither)
-    if (range_on == 1 && y.a_srpart && GHp <= 1024 &&
-        launch_scatter_range(sm, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, y.cfg.input_size, GHp, h->A(y.a_srpart), (int*)h->A(y.a_srid),
-                             SBR_SCAT_RANGES, &se)) {
-        SBR_LAUNCH(se); h->last_scatter_form = 1;
-    } else if (range_on == 2 && y.a_srpart &&
-               launch_scatter_wide(sm, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, y.cfg.input_size, sort_entries(y), GHp,
-                                   h->A(y.a_srpart), (int*)h->A(y.a_srid), y.sr_slots, &se)) {
-        SBR_LAUNCH(se); h->last_scatter_form = 2;
-    } else {
-        h->last_scatter_form = 0;
-        SBR_LAUNCH(launch_scatter_reduce(sm, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, y.cfg.input_size, sort_entries(y), GHp, y.Bp));
+    SBR_LAUNCH(launch_scatter_sort(s, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, k.cnt, k.off, k.cur, k.sid, k.pos, 0, 0, 1, nullptr,
+                                   &h->scnt_zero_n));
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    SBR_HIP(hipEventCreate(&e0)); SBR_HIP(hipEventCreate(&e1));
+    const float* dxt = h->A(ly.a_dxt);
+    auto one = [&]() { return scatter_plain(h, s, 0, ly, dxt); };      // the step's own launch (layer0_scatter)
+    for (int i = 0; i < 2; ++i) { const int rc = one(); if (rc != SBR_OK) return rc; }
+    SBR_HIP(hipEventRecord(e0, s));
+    for (int i = 0; i < reps; ++i) { const int rc = one(); if (rc != SBR_OK) return rc; }
+    SBR_HIP(hipEventRecord(e1, s));
+    SBR_HIP(hipEventSynchronize(e1));
+    float ms = 0.f;
+    SBR_HIP(hipEventElapsedTime(&ms, e0, e1));
+    *us = ms * 1000.0f / (float)reps;
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+    if (entries || rows) {
+        std::vector<int> off((size_t)y.cfg.input_size + 1);
+        SBR_HIP(hipMemcpy(off.data(), k.off, off.size() * sizeof(int), hipMemcpyDeviceToHost));
+        int64_t nr = 0;
+        for (int i = 0; i < y.cfg.input_size; ++i) nr += off[i + 1] > off[i];
+        if (entries) *entries = off[y.cfg.input_size];
+        if (rows) *rows = nr;
     }
+    // the gradient block as a step expects it: zero (the rows the scatter-add wrote, i.e. the whole block)
+    SBR_HIP(hipMemsetAsync(h->Gd(ly.p_Win), 0, (size_t)y.cfg.input_size * GHp * sizeof(float), s));
+    SBR_HIP(hipStreamSynchronize(s));
+    h->tail_sorted = false;
     return SBR_OK;
 }
 
@@ -1116,7 +1136,6 @@ static int backward_bi(sbr_handle* h) {
         for (int d = 0; d < 2; ++d) {
             const int pl = 2 * l + d;
             const LayerLayout& ly = y.layer[pl];
-            const int GHp = y.G * ly.Hp;
             RecArgs a;
             { const int rc = bptt_args(h, pl, l == y.L - 1 ? h->A(y.a_dhl[d]) : nullptr, true, &a); if (rc != SBR_OK) return rc; }
             const int nblk = h->plan[pl].bwd_blocks;
@@ -1126,14 +1145,9 @@ static int backward_bi(sbr_handle* h) {
             { const int rc = whid_grad_gemm(h, ly, a); if (rc != SBR_OK) return rc; }
             if (l == 0 && !y.E) {   // index input: scatter-add with this direction's ids (the backwards one sorted its reversed ids)
                 if (d == 0) mark(h, 5);
-                const int* idx = d ? (const int*)h->A(y.a_Xr) : h->bX;
-                if (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) {
-                    SBR_LAUNCH(launch_scatter_rows(s, h->Gd(ly.p_Win), a.dxt, idx, a.len, y.T, y.Bp, y.F, GHp));
-                } else {
-                    const SbrSortKeys k = sort_keys(h, d);
-                    SBR_HIP(hipStreamWaitEvent(s, h->ev_sort, 0));
-                    SBR_LAUNCH(launch_scatter_reduce(s, h->Gd(ly.p_Win), a.dxt, k.sid, k.pos, k.off, y.cfg.input_size, sort_entries(y), GHp, y.Bp));
-                }
+                // (two directions: the plan says form 0 -- each with its own sort -- or the atomics; "scatter_form" is not set here)
+                if (h->scat.plain != SCAT_ATOMIC) SBR_HIP(hipStreamWaitEvent(s, h->ev_sort, 0));
+                { const int rc = scatter_plain(h, s, d, ly, a.dxt); if (rc != SBR_OK) return rc; }
             } else {                // dense input, in this direction's time order
                 const float* inp = l == 0 ? h->A(d ? y.a_embr : y.a_emb) : h->A(d ? y.a_catr[l - 1] : y.a_cat[l - 1]);
                 const int rc = input_grads_dense(h, ly, a, inp, h->A(y.a_dinp[d]), false); if (rc != SBR_OK) return rc;
@@ -1169,8 +1183,8 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
 // over W_in reads / clears the gradient of the touched rows only (launch_update_rows_aware).  SBR_ROW_AWARE_UPDATE=0: update_kernel.
 static bool row_aware_taken(const sbr_handle* h) {
     const Layout& y = h->lay;
-    return h->sw.row_aware && h->in_train_step && y.a_srpart && !y.n_sparse && !y.E && y.D == 1 && h->tail_nc < 2 &&
-           !(y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) && !simple_gemm(h) && !simple_rec(h) && ((y.G * y.layer[0].Hp) & 3) == 0;
+    return h->sw.row_aware && h->in_train_step && h->scat.wide_rows && !y.n_sparse && y.D == 1 && h->tail_nc < 2 &&
+           h->scat.plain != SCAT_ATOMIC && !simple_gemm(h) && !simple_rec(h);
 }
 // [0, hi) of the parameter section on the main stream; row_aware: with the row-aware pass over layer 0's W_in
 static hipError_t step_front(sbr_handle* h, size_t hi, bool row_aware) {

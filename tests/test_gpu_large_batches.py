@@ -251,7 +251,7 @@ def test_sampled_head_at_its_cell_limit(B, taken, loss, monkeypatch):
 # E. step tail at large entry counts
 # ----------------------------------------------------------------------------------------------------------------
 def test_overlapped_tail_at_528_rows():
-    """GRU-128, 300 Zipf ids, T = 70, 528 rows: tail_plan takes min(tail_keys = 8, 8, T / 16 = 4) = 4 time chunks (rec_bwd_x6p's
+    """GRU-128, 300 Zipf ids, T = 70, 528 rows: plan_tail takes min(tail_keys = 8, 8, T / 16 = 4) = 4 time chunks (rec_bwd_x6p's
     progress-publishing form on 4-row tiles); scat_lds_plan: 36 960 entries over 192 units = a cost floor of 13 entries per LDS row,
     19 rows of 384 floats = 29 KB -- the plan fits, scat_lds_kernel adds the hot ids' rows in LDS (sbr_query "scatter_form": what the
     last step launched, recorded at the launch)"""

@@ -282,6 +282,19 @@ def test_cluster_kernels_with_bf16x6_products(which, monkeypatch):
     check(PU.compare_step("GRU", [512], "CCE", N=61, B=37, T=7, scale=0.04), tol_h=2e-4)
 
 
+@pytest.mark.parametrize("H, scat_range", [(192, "0"), (768, None)], ids=["rows_of_576_floats", "rows_of_2304_floats"])
+def test_sorted_reduce_walk_of_odd_row_widths(H, scat_range, monkeypatch):
+    """The sorted segment reduce (scatter_form 0) on scat_reduce_kernel's walk, which serves the row widths whose 16-byte pieces do
+    not fill 1, 2, 4 or 8 times a wave: 576 floats = 3 pieces per lane on <4, 32> (with the range form switched off), 2 304 floats =
+    9 on <16, 32>; GRU [512] above is <8, 32>.  384 entries: three workgroups of 128, Zipf ids whose segments cross the seams of
+    the waves' 32-entry chunks and of the workgroups.  (Scale 0.04 as for the other layers of 512 units and more.)"""
+    if scat_range is not None:
+        monkeypatch.setenv("SBR_SCAT_RANGE", scat_range)
+    r = PU.compare_step("GRU", [H], "CCE", N=41, B=32, T=12, zipf=True, scale=0.04, queries_after=("scatter_form",))
+    assert r["q:scatter_form"] == 0
+    check(r, tol_h=2e-4)
+
+
 def test_cluster_kernels_fp16_products_with_active_clip_and_tiny_gradients():
     check(PU.compare_step("LSTM", [256], "CCE", N=61, B=21, T=9, popscale=1e-4), tol_h=2e-4)
     check(PU.compare_step("GRU", [256], "CCE", N=61, B=21, T=30, popscale=1e4, scale=0.05), tol_h=2e-4, tol_g=2e-4)
