@@ -31,6 +31,19 @@ __device__ __forceinline__ void st_s(const void* ubase, unsigned boff, float v) 
 __device__ __forceinline__ void st_s4(const void* ubase, unsigned boff, f32x4 v) {
     asm volatile("global_store_dwordx4 %0, %1, %2" :: "v"(boff), "v"(v), "s"(ubase) : "memory");
 }
+// ... with a cache policy: 0 plain (the line stays dirty in this XCD's L2 until the end-of-kernel release writes it back), 1 write-through
+// (sc1, as st_si<IMM, true>) -- for what the launch only leaves behind for the kernels after it.  (Non-temporal, nt, was measured too:
+// + 10 us per C2 step, profiles/chain_edges_variants.txt.)
+template <int POL>
+__device__ __forceinline__ void st_sp(const void* ubase, unsigned boff, float v) {
+    if constexpr (POL == 1) asm volatile("global_store_dword %0, %1, %2 sc1" :: "v"(boff), "v"(v), "s"(ubase) : "memory");
+    else st_s(ubase, boff, v);
+}
+template <int POL>
+__device__ __forceinline__ void st_sp4(const void* ubase, unsigned boff, f32x4 v) {
+    if constexpr (POL == 1) asm volatile("global_store_dwordx4 %0, %1, %2 sc1" :: "v"(boff), "v"(v), "s"(ubase) : "memory");
+    else st_s4(ubase, boff, v);
+}
 // WT: write-through (sc1) -- the value reaches memory that every XCD sees, for consumers that read it while this kernel
 // is still running (MI355X_MICROARCH.md, inter-workgroup visibility)
 template <int IMM, bool WT = false>

@@ -85,6 +85,15 @@
 #ifndef X6P_SPARSE
 #define X6P_SPARSE 1     // packed planes on the 2:4-sparse matrix instruction: ONE v_smfmac_f32_16x16x64_f16 per (gate, k-block), see
 #endif                   // "Sparse planes" below; 0: two dense MFMAs (round 3)
+#ifndef X6P_FWD_ST
+#define X6P_FWD_ST 1     // forward: cache policy of the saved activations' stores (hs, the gate element, cs; st_sp in sbr_rec_p.h): 0 plain,
+#endif                   // 1 write-through -- what the launch leaves dirty in L2 its end-of-kernel release has to write back before the head starts
+#ifndef X6P_FWD_PRO
+#define X6P_FWD_PRO 1    // forward, fused gather: 1 = the ids of steps 0 .. XPD are requested with the W_hid planes and the first XPD pieces of the
+#endif                   // ring leave from them directly; the table and the W_hid split run under the pieces' flight time, one barrier behind both
+#ifndef X6P_BWD_PRO
+#define X6P_BWD_PRO 1    // backward: 1 = every dh slab (up to 16) requested at once, the ring primed in front of the W_hid split, the first progress
+#endif                   // word published at the entry (0 / 0 / 0: the prologues and stores of before; -3.9, -3.7, -2.0 us per C2 step)
 #ifndef X6P_SP_INIT
 #define X6P_SP_INIT 1    // sparse forms: the accumulators' initial value (bias | zeros) comes from LDS (ds_read_b128 at the top of the step;
                          // bit 0: forward, bit 1: backward) or from VALU moves (0)
@@ -119,6 +128,14 @@ constexpr float F16_LO = 2048.0f;
 // {bias, 0, 0, 0} by moves (X6P_SP_INIT 0) or LDS reads (1).
 __device__ __forceinline__ f32x4 smfmac16(const f16x8& a, const f16x16& b, const f32x4& c, int idx) {
     return __builtin_amdgcn_smfmac_f32_16x16x64_f16(a, b, c, idx, 0, 0);
+}
+// a finished sparse plane pinned where it stands between the volatile asms around it (they keep their order; the compiler may otherwise
+// sink the split to the loop's door).  Device pass only: the host pass has no register class for a 32-byte "v" operand and drops the
+// instantiation without a word.
+__device__ __forceinline__ void pin_plane(f16x16& w) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(w));
+#endif
 }
 __device__ __forceinline__ f32x4 mfma16(const bf16x8& a, const bf16x8& b, const f32x4& c) { return MFMA_BF16(a, b, c); }
 [[maybe_unused]] __device__ __forceinline__ f32x4 mfma16(const f16x8& a, const f16x8& b, const f32x4& c) {
@@ -188,6 +205,20 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
 
     OPV W1[SP ? 1 : G][SP ? 1 : KB], W2[SP ? 1 : G][SP ? 1 : KB], W3[F16 ? 1 : G][F16 ? 1 : KB];   // B operands: lane (j, q) holds W[kb*32 + 8q + e][unit j]
     f16x16 WS[SP ? G : 1][SP ? KB : 1];                  // SP: both planes interleaved, lane (j, q) holds real k = 16 (e >> 3) + 4 q + ((e & 7) >> 1)
+    // PRO: the first trip to memory carries everything the prologue needs -- the W_hid elements (split further down, under the flight
+    // time of the ring's first pieces), this lane's ids of steps 0 .. XPD, the thread's share of the tile's ids for the table
+    constexpr bool PRO = FUSE && X6P_FWD_PRO, PROW = PRO && SP;
+    constexpr int XPD = 4, XTAB = 2;                     // ring depth (see below) | table entries a thread requests up front (R T <= 1024: T <= 256)
+    float wraw[PROW ? G : 1][PROW ? KB : 1][PROW ? 8 : 1];
+    int id_pro[XPD + 1], id_tab[XTAB];
+    auto split_ws = [&](int g, int kb, int r, float w) {
+        if constexpr (SP) {
+            _Float16 b1, b2;
+            asm("" : "+v"(w));                           // see split2_f16 (not volatile)
+            split2_f16(w, b1, b2);
+            WS[g][kb][2 * r] = b1; WS[g][kb][2 * r + 1] = b2;
+        }
+    };
     if constexpr (SP) {
 #pragma unroll
         for (int g = 0; g < G; ++g)
@@ -195,12 +226,9 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
             for (int kb = 0; kb < KB; ++kb)
 #pragma unroll
                 for (int r = 0; r < 8; ++r) {
-                    const float sc = (CELL == CELL_GRU && g < 2) ? X6P_NLOG2E : 1.0f;
-                    float w = sc * a.Whid[(size_t)(kb * 32 + 16 * (r >> 2) + 4 * q + (r & 3)) * GHP + g * HP + u];
-                    _Float16 b1, b2;
-                    asm("" : "+v"(w));                       // see split2_f16 (not volatile)
-                    split2_f16(w, b1, b2);
-                    WS[g][kb][2 * r] = b1; WS[g][kb][2 * r + 1] = b2;
+                    const float wv = a.Whid[(size_t)(kb * 32 + 16 * (r >> 2) + 4 * q + (r & 3)) * GHP + g * HP + u];
+                    if constexpr (PROW) wraw[g][kb][r] = wv;
+                    else split_ws(g, kb, r, ((CELL == CELL_GRU && g < 2) ? X6P_NLOG2E : 1.0f) * wv);
                 }
     } else
 #pragma unroll
@@ -225,17 +253,28 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
             }
 
     // per-lane byte offsets, computed once; the per-step part of every address is uniform and advances on the SALU
+    if constexpr (PRO) {      // the tile's ids are R T consecutive words: row r of the tile, step t at r T + t
+        const int* ids = a.gX + (size_t)blockIdx.x * R * T;
+        const int* idrow = ids + ((lane >> 2) & 3) * T;          // (the batch row this lane fetches for, see dma_x)
+#pragma unroll
+        for (int k = 0; k < XTAB; ++k) id_tab[k] = ids[min((int)threadIdx.x + 512 * k, R * T - 1)];
+#pragma unroll
+        for (int d = 0; d <= XPD; ++d) id_pro[d] = idrow[min(d, T - 1)];      // (requested last: when they are here, everything above is)
+    }
+    unsigned long long p_e0 = 0, p_e1 = 0;                       // PROF: kernel entry, table built (100 MHz clock)
+    if (PROF) p_e0 = wall_clock64();
+
     const unsigned bo_h = (unsigned)(row * HP + u) * 4u;                                       // hs rows
     const unsigned bo_g = X6P_G4 ? (unsigned)(row * HP + u) * 16u : (unsigned)sbr_blocked_index(0, row, u, Bp, HP) * 4u;   // saved activations
     const unsigned bo_x = (unsigned)(row * GHP + u) * 4u;                                      // xt rows (not fused)
     const size_t st_h = (size_t)Bp * HP * 4, st_x = (size_t)Bp * GHP * 4;                      // bytes per time step
 
     float h = a.hinit[u];
-    stf(a.hs, bo_h, h);
+    st_sp<X6P_FWD_ST>(a.hs, bo_h, h);
     float c = 0.f, pi = 0.f, pf = 0.f, po = 0.f;                 // LSTM: cell state and the peepholes of this lane's unit
     if (CELL == CELL_LSTM) {
         c = a.cinit[u]; pi = a.peep[u]; pf = a.peep[HP + u]; po = a.peep[2 * HP + u];
-        stf(a.cs, bo_h, c);
+        st_sp<X6P_FWD_ST>(a.cs, bo_h, c);
     }
     const unsigned lds_pub = (unsigned)(q * HROW + u * 2);            // where this lane's h goes inside a plane set
     // A operand: tile row m = j holds batch row j >> 2; PK: plane j & 1 of it (rows 4r + 2, 4r + 3 repeat rows 4r, 4r + 1)
@@ -283,7 +322,7 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
     // the address arithmetic (a 64-bit multiply-add, a 64-bit add) sat on the VALU beside the partner's MFMA stream:
     // 177 us against 153 us for the same kernel reading a pre-gathered xt.
     // Per iteration the wave issues: stores of step t (NSF) < the DMA piece of step t + XPD.
-    constexpr int XPD = 4, NSF = CELL == CELL_VANILLA ? 1 : (CELL == CELL_LSTM ? 2 : 1) + (X6P_G4 ? 1 : 4), XSTG = G * 256;
+    constexpr int NSF = CELL == CELL_VANILLA ? 1 : (CELL == CELL_LSTM ? 2 : 1) + (X6P_G4 ? 1 : 4), XSTG = G * 256;
     constexpr int XOFF_OFF = (2 * BUFB + 64 + 255) & ~255;
     const int xring_off = (XOFF_OFF + R * T * 4 + 255) & ~255;
     unsigned* xo_tab = (unsigned*)(smem_p + XOFF_OFF);
@@ -311,12 +350,44 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
             for (int g = 0; g < G; ++g) ((f32x4*)bz_lane)[g * HP] = biasv[g];
         }
     }
-    if constexpr (FUSE) {
+    if constexpr (PRO) {
+        // two trips to far memory instead of three, no barrier between them: the pieces of steps 0 .. XPD - 1 leave as soon as this
+        // lane's own ids are here (they came with the W_hid elements); the table (same contents, read from step 0 on for the
+        // pieces of steps > XPD) and the W_hid split follow while the pieces are in flight
+        // (every id is waited for HERE: a compiler-placed wait for one of them behind the pieces, which it cannot see, would wait for the
+        // pieces as well -- the vector memory counter retires in order)
+        static_assert(XPD == 4, "the pin below names XPD + 1 ids");
+        asm volatile("" : "+v"(id_pro[0]), "+v"(id_pro[1]), "+v"(id_pro[2]), "+v"(id_pro[3]), "+v"(id_pro[4]), "+v"(h), "+v"(bias_c));
+        if constexpr (CELL == CELL_LSTM) asm volatile("" : "+v"(c), "+v"(pi), "+v"(pf), "+v"(po));
+#pragma unroll
+        for (int d = 0; d < XPD; ++d) dma_x((unsigned)id_pro[d] * (unsigned)(GHP * 4) + bo_lane, d);
+        bo_nxt = (unsigned)id_pro[XPD] * (unsigned)(GHP * 4) + bo_lane;
+#pragma unroll
+        for (int k = 0; k < XTAB; ++k)
+            if ((int)threadIdx.x + 512 * k < R * T) xo_tab[threadIdx.x + 512 * k] = (unsigned)id_tab[k] * (unsigned)(GHP * 4);   // < 2^32: checked by the launcher
+        for (int i = threadIdx.x + 512 * XTAB; i < R * T; i += 512)
+            xo_tab[i] = (unsigned)a.gX[(size_t)blockIdx.x * R * T + i] * (unsigned)(GHP * 4);
+        if constexpr (PROW) {
+            // (pinned behind the pieces: volatile asms keep their order, so the split cannot be scheduled in front of them)
+#pragma unroll
+            for (int g = 0; g < G; ++g)
+#pragma unroll
+                for (int kb = 0; kb < KB; ++kb) {
+                    float (&w)[8] = wraw[g][kb];
+                    asm volatile("" : "+v"(w[0]), "+v"(w[1]), "+v"(w[2]), "+v"(w[3]), "+v"(w[4]), "+v"(w[5]), "+v"(w[6]), "+v"(w[7]));
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) split_ws(g, kb, r, ((CELL == CELL_GRU && g < 2) ? X6P_NLOG2E : 1.0f) * w[r]);
+                    pin_plane(WS[g][kb]);      // (... nor sunk behind the wait below)
+                }
+        }
+        wait_vm<0>();
+    } else if constexpr (FUSE) {
         for (int i = threadIdx.x; i < R * T; i += 512) {
             const int r = i / T;
             xo_tab[i] = (unsigned)a.gX[(size_t)(blockIdx.x * R + r) * T + (i - r * T)] * (unsigned)(GHP * 4);   // < 2^32: checked by the launcher
         }
         __syncthreads();
+        if (PROF) p_e1 = wall_clock64();
 #pragma unroll
         for (int d = 0; d < XPD; ++d) dma_x(xo_row[min(d, T - 1)] + bo_lane, d);
         bo_nxt = xo_row[min(XPD, T - 1)] + bo_lane;
@@ -325,6 +396,7 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
         load_x(0);
     }
     __syncthreads();
+    if (PROF && PRO) p_e1 = wall_clock64();                      // (one barrier: the table is built when the loop may start)
     unsigned long long p_c0 = 0, p_r0 = 0, p_spin = 0, p_tok = 0, p_seg[3] = {0, 0, 0}, p_ta = 0, p_tb = 0;
     if (PROF) { p_c0 = clock64(); p_r0 = wall_clock64(); }
     unsigned long long* tl = PROF && blockIdx.x == 0 && lane == 0 ? a.prof + (8 + wave) * 8 : nullptr;   // step-100 timeline
@@ -338,14 +410,14 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
     float sv_st[4] = {0.f, 0.f, 0.f, 0.f}, h_st = 0.f, c_st = 0.f;
     auto store_step = [&](size_t off, const float* svv, float hv, float cv) {
         if (CELL != CELL_VANILLA) {
-            if constexpr (X6P_G4) st_s4((const char*)a.g[0] + 4 * off, bo_g, f32x4{svv[0], svv[1], svv[2], svv[3]});
+            if constexpr (X6P_G4) st_sp4<X6P_FWD_ST>((const char*)a.g[0] + 4 * off, bo_g, f32x4{svv[0], svv[1], svv[2], svv[3]});
             else {
 #pragma unroll
-                for (int k = 0; k < 4; ++k) st_s((const char*)a.g[k] + off, bo_g, svv[k]);
+                for (int k = 0; k < 4; ++k) st_sp<X6P_FWD_ST>((const char*)a.g[k] + off, bo_g, svv[k]);
             }
         }
-        st_s((const char*)a.hs + off + st_h, bo_h, hv);
-        if (CELL == CELL_LSTM) st_s((const char*)a.cs + off + st_h, bo_h, cv);
+        st_sp<X6P_FWD_ST>((const char*)a.hs + off + st_h, bo_h, hv);
+        if (CELL == CELL_LSTM) st_sp<X6P_FWD_ST>((const char*)a.cs + off + st_h, bo_h, cv);
     };
     size_t off_t = 0;                                              // t * st_h
     int tmin = mylen;                                              // steps below it: no row of the tile is masked
@@ -604,11 +676,19 @@ __global__ void __launch_bounds__(512) rec_fwd_x6p(RecArgs a) {
     }
     };
     if (roleA && !X6P_SYNC && X6P_ROLES) steps(std::true_type{}); else steps(std::false_type{});
+    unsigned long long p_e3 = 0;
+    if (PROF) p_e3 = wall_clock64();                              // loop exit
     if (DEFER && tmax > 0) store_step(off_t - st_h, sv_st, h_st, c_st);      // the last step's
     for (int t = tmax; t < T; ++t) {                              // past the tile's longest row: the state is carried
-        stf((char*)a.hs + off_t + st_h, bo_h, h);
-        if (CELL == CELL_LSTM) stf((char*)a.cs + off_t + st_h, bo_h, c);
+        st_sp<X6P_FWD_ST>((char*)a.hs + off_t + st_h, bo_h, h);
+        if (CELL == CELL_LSTM) st_sp<X6P_FWD_ST>((char*)a.cs + off_t + st_h, bo_h, c);
         off_t += st_h;
+    }
+    // PROF: the chain's edges per workgroup on the chip-wide 100 MHz clock (tools/rec_prof.py): entry, table built, loop entry, loop exit,
+    // last store issued -- workgroup w at "wave" slot 8 + (w & 7) of block 1 + (w >> 3) (block 0's carry the step-100 timeline)
+    if (PROF && threadIdx.x == 0 && 1 + (blockIdx.x >> 3) < (unsigned)(a.Bp >> 4)) {
+        unsigned long long* e = a.prof + ((size_t)(1 + (blockIdx.x >> 3)) * 16 + 8 + (blockIdx.x & 7)) * 8;
+        e[0] = p_e0; e[1] = p_e1; e[2] = p_r0; e[3] = p_e3; e[4] = wall_clock64();
     }
     if (PROF && lane == 0 && blockIdx.x < (unsigned)(a.Bp >> 4)) {
         unsigned long long* o = a.prof + ((size_t)blockIdx.x * 16 + wave) * 8;
@@ -674,11 +754,14 @@ __global__ void __launch_bounds__(512) rec_bwd_x6p(RecArgs a) {
 
     OPV W1[SP ? 1 : KB], W2[SP ? 1 : KB], W3[F16 ? 1 : KB];               // B operands: lane (j, q) holds W_hid[unit j][kb*32 + 8q + e]
     f16x16 WS[SP ? KB : 1];                              // SP: both planes interleaved, columns kb*32 + 16 (e >> 3) + 4 q + ((e & 7) >> 1)
-    if constexpr (SP) {
-#pragma unroll
-        for (int kb = 0; kb < KB; ++kb) {
-            const float* src = a.Whid + (size_t)u * GHP + kb * 32 + 4 * q;
-            const f32x4 lo = *(const f32x4*)src, hi = *(const f32x4*)(src + 16);
+    // BPRO: every far load of the prologue is requested before anything waits -- the W_hid elements, dh (all slabs of a round at once),
+    // the ring's first PD stages (they need only sbase and the lane offsets) -- and the W_hid split runs while they are in flight
+    constexpr bool BPRO = X6P_BWD_PRO != 0, BPROW = BPRO && SP;
+    f32x4 wlo[BPROW ? KB : 1], whi[BPROW ? KB : 1];
+    unsigned long long p_e0 = 0, p_e1 = 0, p_e2 = 0;             // PROF: kernel entry, W_hid planes in registers, dh complete (100 MHz clock)
+    if (PROF) p_e0 = wall_clock64();
+    auto split_ws = [&](int kb, const f32x4& lo, const f32x4& hi) {
+        if constexpr (SP) {
 #pragma unroll
             for (int r = 0; r < 8; ++r) {
                 float w = r < 4 ? lo[r & 3] : hi[r & 3];
@@ -687,6 +770,15 @@ __global__ void __launch_bounds__(512) rec_bwd_x6p(RecArgs a) {
                 split2_f16(w, b1, b2);
                 WS[kb][2 * r] = b1; WS[kb][2 * r + 1] = b2;
             }
+        }
+    };
+    if constexpr (SP) {
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            const float* src = a.Whid + (size_t)u * GHP + kb * 32 + 4 * q;
+            const f32x4 lo = *(const f32x4*)src, hi = *(const f32x4*)(src + 16);
+            if constexpr (BPROW) { wlo[kb] = lo; whi[kb] = hi; }
+            else split_ws(kb, lo, hi);
         }
     } else
 #pragma unroll
@@ -718,21 +810,56 @@ __global__ void __launch_bounds__(512) rec_bwd_x6p(RecArgs a) {
     const int spidx = (j & 1) ? (int)0xDDDDDDDDu : (int)0x88888888u;      // SP: kept positions of every group of four, see rec_fwd_x6p
 
     const bool first = a.t_hi >= T, last = a.t_lo <= 0;          // first / last launch of the chunked chain
+    // dh of the chain's last step: dh_last arrives as unreduced split-K slabs of the dh GEMM (the one-launch head: 16), added z ascending
+    // into ONE running sum whatever the number in flight (one after the other: 6 us).  BPRO: the first round is requested here and
+    // added behind the W_hid split
     float dh = 0.f, dc = 0.f;
-    if (first) {
-        if (a.n_dh_slabs) {                                       // dh_last arrives as unreduced split-K slabs of the dh GEMM
-            const float* p = a.dh_slabs + (size_t)row * HP + u;
-            const size_t st = (size_t)Bp * HP;
-            int z = 0;
-            for (; z + 8 <= a.n_dh_slabs; z += 8) {               // eight loads in flight (one after the other: 6 us)
+    const float* const dh_p = a.dh_slabs + (size_t)row * HP + u;
+    const size_t dh_st = (size_t)Bp * HP;
+    // BPRO: the SAME sixteen loads (+ one for an LSTM's dc) whatever the source -- slabs, dh_last, the chunk hand-over, nothing: the
+    // compiler counts what is in flight once for all paths where they join, and a path with fewer loads made its waits for the
+    // W_hid elements (older than these) so strict that the split waited for the ring's pieces too.  Slots past the source's end read
+    // its last element again (nothing to read: a W_hid element); what is added, and in which order, is what it was.
+    const bool dh_slabs = first && a.n_dh_slabs > 0;
+    const float* const dh_one = first ? (a.dh_last ? a.dh_last + (size_t)row * HP + u : nullptr) : a.state + (size_t)row * HP + u;
+    const int dh_z = dh_slabs ? min(a.n_dh_slabs, 16) : 0;        // slabs requested ahead (uniform)
+    float dh_v[16], dc_v = 0.f;
+    auto dh_rest = [&]() {
+        if constexpr (BPRO) {
+            if (!dh_slabs) { if (dh_one) dh = dh_v[0]; }
+            else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) if (k < dh_z) dh += dh_v[k];
+            }
+            if (CELL == CELL_LSTM && !first) dc = dc_v;
+        }
+        if (dh_slabs) {
+            int z = BPRO ? dh_z : 0;
+            for (; BPRO && z + 16 <= a.n_dh_slabs; z += 16) {
+                float v[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) v[k] = dh_p[(size_t)(z + k) * dh_st];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) dh += v[k];
+            }
+            for (; z + 8 <= a.n_dh_slabs; z += 8) {
                 float v[8];
 #pragma unroll
-                for (int k = 0; k < 8; ++k) v[k] = p[(size_t)(z + k) * st];
+                for (int k = 0; k < 8; ++k) v[k] = dh_p[(size_t)(z + k) * dh_st];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) dh += v[k];
             }
-            for (; z < a.n_dh_slabs; ++z) dh += p[(size_t)z * st];
-        } else if (a.dh_last) dh = a.dh_last[(size_t)row * HP + u];
+            for (; z < a.n_dh_slabs; ++z) dh += dh_p[(size_t)z * dh_st];
+        }
+    };
+    if constexpr (BPRO) {
+        const float* const src = dh_slabs ? dh_p : dh_one ? dh_one : a.Whid + u;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) dh_v[k] = src[(size_t)min(k, max(dh_z - 1, 0)) * dh_st];
+        if (CELL == CELL_LSTM) dc_v = *(first ? a.Whid + u : a.state + (size_t)Bp * HP + (size_t)row * HP + u);
+    } else if (first) {
+        if (a.n_dh_slabs) dh_rest();
+        else if (a.dh_last) dh = a.dh_last[(size_t)row * HP + u];
     }
     else {
         dh = a.state[(size_t)row * HP + u];
@@ -818,13 +945,45 @@ __global__ void __launch_bounds__(512) rec_bwd_x6p(RecArgs a) {
         }
         if (EXT) dhe = ldf((const char*)a.dh_ext + o, bo_h);
     };
+    const int t_live = min(a.t_hi, tmax);                         // steps [t_live, t_hi) are masked for the whole tile
+    // fill the ring: steps t_live - 1 .. t_live - PD (clamped), all landed before the loop starts
+    auto prime_ring = [&]() {
+#pragma unroll
+        for (int d = 0; d < PD; ++d) dma_saved((size_t)max(t_live - 1 - d, a.t_lo) * st_h, d);
+    };
+    // WT: the first progress word says that every step >= max(t_live, t_lo) is complete.  BPRO: where no such step exists (no row of
+    // zeros to store first), it leaves HERE -- the loop's first counted wait retires in order behind this write-through store, whose
+    // acknowledgement is a trip to far memory; published behind the barrier, as it was, that trip stood in front of the loop
+    int* prog_slot = nullptr; int prog_next = 0; const int prog_tag = a.prog_epoch << 12;
+    const int prog_tl = max(t_live, a.t_lo);
+    const bool prog_early = BPRO && WT && a.t_hi <= prog_tl;      // (uniform)
+    if constexpr (WT) {
+        prog_slot = a.progress + blockIdx.x * 8 + wave;
+        if (prog_early) publish_word(prog_slot, prog_tag | prog_tl);
+    }
+    if constexpr (BPRO && RING) {
+        if (t_live > a.t_lo) prime_ring();
+    }
+    if constexpr (BPROW) {      // (pinned behind the ring's pieces: volatile asms keep their order)
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            asm volatile("" : "+v"(wlo[kb]), "+v"(whi[kb]));
+            split_ws(kb, wlo[kb], whi[kb]);
+            pin_plane(WS[kb]);      // ... nor sunk to the loop's door, behind the wait for the ring (where the split ran before)
+        }
+    }
+    if (PROF) {
+        if constexpr (SP) pin_plane(WS[KB - 1]); else asm volatile("" :: "v"(W1[KB - 1]));
+        p_e1 = wall_clock64();
+    }
+    if constexpr (BPRO) dh_rest();
+    if (PROF) { asm volatile("" :: "v"(dh)); p_e2 = wall_clock64(); }
     unsigned long long p_c0 = 0, p_r0 = 0, p_spin = 0, p_tok = 0, p_n = 0, p_m = 0, p_vm = 0;
     if (PROF) { p_c0 = clock64(); p_r0 = wall_clock64(); }
     unsigned long long wt_c0 = 0, wt_r0 = 0;
     if (WT) { wt_c0 = clock64(); wt_r0 = wall_clock64(); }
     __syncthreads();
 
-    const int t_live = min(a.t_hi, tmax);                         // steps [t_live, t_hi) are masked for the whole tile
     for (int t = a.t_hi - 1; t >= max(t_live, a.t_lo); --t) {     // zero rows; dh_ext still accumulates
         if (EXT) dh += a.dh_ext[((size_t)t * Bp + row) * HP + u];
 #pragma unroll
@@ -837,17 +996,13 @@ __global__ void __launch_bounds__(512) rec_bwd_x6p(RecArgs a) {
             if (WT) st_wt(p, 0.f); else *p = 0.f;
         }
     }
-    int* prog_slot = nullptr; int prog_next = 0; const int prog_tag = a.prog_epoch << 12;
     if constexpr (WT) {
-        prog_slot = a.progress + blockIdx.x * 8 + wave;
-        const int tl = max(t_live, a.t_lo);
-        publish_progress(prog_slot, prog_tag | tl);               // every step >= tl is complete (zero rows above)
-        prog_next = tl - a.prog_every;                            // publish again at or below this step
+        if (!prog_early) publish_progress(prog_slot, prog_tag | prog_tl);      // every step >= prog_tl is complete (zero rows above)
+        prog_next = prog_tl - a.prog_every;                       // publish again at or below this step
     }
     if (t_live > a.t_lo) {
-        if constexpr (RING) {    // fill the ring: steps t_live - 1 .. t_live - PD (clamped), all landed before the loop starts
-#pragma unroll
-            for (int d = 0; d < PD; ++d) dma_saved((size_t)max(t_live - 1 - d, a.t_lo) * st_h, d);
+        if constexpr (RING) {
+            if constexpr (!BPRO) prime_ring();
             wait_vm<0>();
             take_saved(0);                                        // the first step's values
         } else load_saved((size_t)(t_live - 1) * st_h);
@@ -1069,7 +1224,15 @@ __global__ void __launch_bounds__(512) rec_bwd_x6p(RecArgs a) {
         else dh += acc[0][0] + acc[1][0] + acc[2][0];
     }
     };
+    unsigned long long p_e3 = 0;                                  // PROF: loop entry
+    if (PROF) p_e3 = wall_clock64();
     if (roleA && !X6P_SYNC && X6P_ROLES) steps(std::true_type{}); else steps(std::false_type{});
+    // PROF: the chain's edges per workgroup (tools/rec_prof.py; the slots of rec_fwd_x6p): entry, W_hid planes in registers, dh complete,
+    // loop entry, loop exit
+    if (PROF && threadIdx.x == 0 && 1 + (blockIdx.x >> 3) < (unsigned)(a.Bp >> 4)) {
+        unsigned long long* e = a.prof + ((size_t)(1 + (blockIdx.x >> 3)) * 16 + 8 + (blockIdx.x & 7)) * 8;
+        e[0] = p_e0; e[1] = p_e1; e[2] = p_e2; e[3] = p_e3; e[4] = wall_clock64();
+    }
     if constexpr (WT) publish_progress(prog_slot, prog_tag | a.t_lo);
     if constexpr (WT) {      // shader cycles and 100 MHz wall-clock ticks of this launch (block 0, wave 0): the chain's effective clock
         if (blockIdx.x == 0 && wave == 0 && lane == 0) {

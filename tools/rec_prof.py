@@ -1,7 +1,9 @@
 """In-kernel cycle counters of the recurrent kernels (SBR_FLAG_PROFILE_REC): effective shader clock
 (s_memtime vs the 100 MHz s_memrealtime) and the split work / barrier-wait per wave.
 The profiling instances follow the product form the launch would take (fp16x3 by default, bf16x6 with SBR_X6_F16=0;
-profiles/round1_h_rec_phases_c2.txt is the bf16x6 forward of round 1)."""
+profiles/round1_h_rec_phases_c2.txt is the bf16x6 forward of round 1).
+For the 128-unit pipelined chains also their edges, per workgroup: prologue, loop and epilogue of each chain and the two boundaries
+around the one-launch head (profiles/chain_edges_stamps_*.txt).      python tools/rec_prof.py [c2 | l128 | ...]"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -17,6 +19,41 @@ eng.set_batch(hb["X"], None, hb["target"], hb["samples"] if loss != "CCE" else N
 for _ in range(3):
     eng.train_step(sync=True)
 raw = eng.debug_buffer("prof").view(np.uint64).reshape(2, B // 16, 16, 8)
+
+
+def chain_edges():
+    """The 128-unit pipelined kernels (csrc/sbr_rec_p.hip) stamp their edges per workgroup on the chip-wide 100 MHz clock: workgroup w
+    at [1 + w // 8][8 + w % 8][0..4]; the one-launch head its phases at prof_head[workgroup][0..7] (tools/head_prof.py)."""
+    nwg = B // 4
+    if int(eng.query("rec_kernel")) != 2 or 1 + (nwg - 1) // 8 >= B // 16:
+        return
+    e = np.array([[raw[k, 1 + w // 8, 8 + w % 8, :5] for w in range(nwg)] for k in range(2)]).astype(np.int64)
+    if not (e[:, :, 0] > 0).all():
+        return
+    us = lambda d: "min %6.2f  median %6.2f  max %6.2f us" % (d.min() / 100.0, np.median(d) / 100.0, d.max() / 100.0)
+    f, b = e[0], e[1]
+    print("chain edges, %d workgroups per chain (last of three steps)" % nwg)
+    print("  rec_fwd  entry -> table built        %s" % us(f[:, 1] - f[:, 0]))
+    print("  rec_fwd  prologue (entry -> loop)    %s" % us(f[:, 2] - f[:, 0]))
+    print("  rec_fwd  loop                        %s" % us(f[:, 3] - f[:, 2]))
+    print("  rec_fwd  epilogue (-> last store)    %s" % us(f[:, 4] - f[:, 3]))
+    print("  rec_fwd  first entry -> last store issued %.2f us" % ((f[:, 4].max() - f[:, 0].min()) / 100.0))
+    print("  rec_bwd  entry -> W_hid planes       %s" % us(b[:, 1] - b[:, 0]))
+    print("  rec_bwd  entry -> dh complete        %s" % us(b[:, 2] - b[:, 0]))
+    print("  rec_bwd  prologue (entry -> loop)    %s" % us(b[:, 3] - b[:, 0]))
+    print("  rec_bwd  loop                        %s" % us(b[:, 4] - b[:, 3]))
+    print("  rec_bwd  first entry -> last loop exit %.2f us" % ((b[:, 4].max() - b[:, 0].min()) / 100.0))
+    if int(eng.query("head_fused")) > 0:
+        hd = eng.debug_buffer("prof_head").view(np.uint64).reshape(-1, 8).astype(np.int64)
+        hd = hd[hd[:, 0] > 0]
+        if len(hd):
+            print("  last forward workgroup out of its loop -> first head workgroup in   %.2f us (last store issued -> : %.2f)" % (
+                (hd[:, 0].min() - f[:, 3].max()) / 100.0, (hd[:, 0].min() - f[:, 4].max()) / 100.0))
+            print("  head     first workgroup in -> last slab stored %.2f us" % ((hd[:, 7].max() - hd[:, 0].min()) / 100.0))
+            print("  last head slab stored -> first backward workgroup in                %.2f us" % ((b[:, 0].min() - hd[:, 7].max()) / 100.0))
+
+
+chain_edges()
 for k, name in enumerate(("rec_fwd", "rec_bwd")):
     p = raw[k].astype(np.float64)
     nw = min(8, int((p[0, :, 0] > 0).sum()))
