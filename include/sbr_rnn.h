@@ -169,6 +169,11 @@ int sbr_loss_backward_output(sbr_handle* h);
 int sbr_backward_recurrent(sbr_handle* h);
 int sbr_apply_update(sbr_handle* h);
 int sbr_read_cost(sbr_handle* h, float* cost_host);
+/* The lagged cost for the phase-by-phase form: call it behind sbr_apply_update.  It enqueues the report of the cost word at the
+ * end of the gradient section (after a data-parallel driver's all-reduce: the GLOBAL cost) and of the fault word on `stream`,
+ * and hands back the report of the previous call -- sbr_read_cost without the wait for the stream.  Same slots and sequence
+ * numbers as sbr_train_step_lagged, which is sbr_train_step + this call; sbr_lagged_flush serves both forms. */
+int sbr_cost_lagged(sbr_handle* h, float* prev_cost, int* have_prev);
 /* The phases put everything that only feeds the optimizer (output-layer weight/bias gradients, the cost, the
  * weight-gradient kernels) on an internal side stream.  Called one by one they join it at their end so that the
  * caller may read the gradients on `stream`.  A data-parallel driver that orders its collectives itself turns the

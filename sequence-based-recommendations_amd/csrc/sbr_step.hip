@@ -1,5 +1,5 @@
 // The training step of libsbr_rnn.so (include/sbr_rnn.h): sbr_forward, sbr_loss_backward_output, sbr_backward_recurrent,
-// sbr_apply_update and the single-call forms sbr_train_step / sbr_train_step_lagged.  Host code only: which kernel goes on which
+// sbr_apply_update, the single-call forms sbr_train_step / sbr_train_step_lagged and sbr_cost_lagged.  Host code only: which kernel goes on which
 // stream in which order; the arithmetic lives in the kernels.  Every launch recipe that more than one road of the step takes is
 // written once, in the first half of this file (kernel arguments, sort arrays, timing marks, optimizer steps, row-sparse blocks,
 // the GEMMs around a recurrent layer); the phases below are built from them.  What the rest of the engine (sbr_api.hip) needs of
@@ -1382,18 +1382,25 @@ static int lagged_collect(sbr_handle* h, float* cost, int* have) {
     return report_fault(h, fault);
 }
 
-extern "C" int sbr_train_step_lagged(sbr_handle* h, float* prev_cost, int* have_prev) {
+// The report of the step just applied, for either form of the step: behind sbr_apply_update of a phase-by-phase step (a data-parallel
+// driver: the cost word then holds the all-reduced, global cost) or behind sbr_train_step (sbr_train_step_lagged below).
+extern "C" int sbr_cost_lagged(sbr_handle* h, float* prev_cost, int* have_prev) {
     CHECK_ARG(h && prev_cost && have_prev, "null argument");
-    int rc = sbr_train_step(h, nullptr);
-    if (rc != SBR_OK) return rc;
     const int s = h->lag_slot;
     h->lag_seq[s] = ++h->lag_counter;
     lag_report_kernel<<<1, 1, 0, h->stream>>>(h->cost_ptr(), (const int*)h->A(h->lay.a_fault), h->lag_host, s, h->lag_seq[s]);
     SBR_LAUNCH(hipGetLastError());
-    rc = lagged_collect(h, prev_cost, have_prev);          // the step before this one: normally long finished
+    const int rc = lagged_collect(h, prev_cost, have_prev);          // the step before this one: normally long finished
     h->lag_pending = s;
     h->lag_slot = s ^ 1;
     return rc;
+}
+
+extern "C" int sbr_train_step_lagged(sbr_handle* h, float* prev_cost, int* have_prev) {
+    CHECK_ARG(h && prev_cost && have_prev, "null argument");
+    const int rc = sbr_train_step(h, nullptr);
+    if (rc != SBR_OK) return rc;
+    return sbr_cost_lagged(h, prev_cost, have_prev);
 }
 
 extern "C" int sbr_lagged_flush(sbr_handle* h, float* cost, int* have) {

@@ -80,10 +80,16 @@ class NativeBatchBuilder(object):
     The training file is parsed once (SequenceGenerator.load) and uploaded as CSR.  Per pass the users are walked in
     file order, or reshuffled like data_handling.py:139-141 with --tshuffle; the walk prints the reference's
     "Opening file (n)" line and keeps `training_set.epochs` (the fractional pass counter the training loop records,
-    rnn_base.py:312) up to date per batch.  `next()` makes the next batch the engine's current batch."""
+    rnn_base.py:312) up to date per batch.  `next()` makes the next batch the engine's current batch.
+
+    sync: the parallel.DataParallel of a multi-rank run.  `batch_size` stays the GLOBAL one: every rank plans the same pass and
+    its engine (local_batch, row_offset) builds its own rows of each batch -- plus all B targets and the S negatives of the
+    sampled heads.  Everything the plan and the draws depend on is rank 0's, broadcast: the builder's seed (the noise passes'
+    seeds derive from it), the --target_bias seed and the --tshuffle order of each pass.  Every rank draws from Python's generator
+    as the single-process run does and rank 0's draws are the ones used."""
 
     def __init__(self, engine, training_set, n_items, batch_size, pop_db=None, sample_cdf=None, seed=None, ratings=False,
-                 shuffle_targets=False, noise=None, keep_prob=None, n_targets=1):
+                 shuffle_targets=False, noise=None, keep_prob=None, n_targets=1, sync=None):
         from .engine import DeviceDataset
         if not hasattr(training_set, "users"):
             training_set.load()
@@ -96,21 +102,27 @@ class NativeBatchBuilder(object):
         if ratings or shuffle_targets:      # --rf: the rating index rides beside the item index; --shuffle_targets
             r = (np.concatenate(training_set.ratings) if len(lengths) else np.zeros(0)) if ratings else None
             self.ds.set_options(r, shuffle_targets)
+        self.sync = sync if (sync is not None and sync.world > 1) else None
+        shared = (lambda v: v) if self.sync is None else self.sync.broadcast_seed
         if keep_prob is not None:           # --target_bias: rows planned on the host (a row may run out of targets)
-            self.ds.set_target_bias(keep_prob, n_targets, seed=int(seed if seed is not None else random.getrandbits(62)))
+            self.ds.set_target_bias(keep_prob, n_targets, seed=shared(int(seed if seed is not None else random.getrandbits(62))))
         self.n_users = len(lengths)
         self.noise = noise if (noise is not None and getattr(noise, "name", "") != "") else None      # a SequenceNoise
-        self.seed = int(seed if seed is not None else random.getrandbits(63))
+        self.seed = shared(int(seed if seed is not None else random.getrandbits(63)))
         self.passes, self.cursor, self.n_batches, self.built = 0, 0, 0, 0
         self._frac = np.zeros(0)
 
     def _plan(self):
         self.passes += 1
-        print("Opening file ({})".format(self.passes))
+        if self.sync is None or self.sync.rank == 0:
+            print("Opening file ({})".format(self.passes))
         order = None
         if self.ts.shuffle:
             random.shuffle(self.ts.order)
             order = np.asarray(self.ts.order, dtype=np.int32)
+            if self.sync is not None:       # rank 0's order of this pass
+                order = self.sync.broadcast_array(order, order.shape, "int32")
+                self.ts.order = order.tolist()
         if self.noise is not None:      # this pass's noised copy of every sequence; the plan below sees its lengths
             nz = self.noise
             self.ds.noise_pass(nz.dropout, nz.swap, nz.shuf, nz.shuf_std, nz.ratings_perturb, seed=self.seed + 7919 * self.passes)

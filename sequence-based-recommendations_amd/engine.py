@@ -74,7 +74,7 @@ class SbrConfig(ctypes.Structure):
 EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create", "sbr_destroy", "sbr_num_params",
            "sbr_param_shape", "sbr_describe_param", "sbr_set_params", "sbr_get_params", "sbr_get_grads", "sbr_section", "sbr_set_batch",
            "sbr_set_default_target",
-           "sbr_train_step", "sbr_train_step_lagged", "sbr_lagged_flush", "sbr_zero_grads", "sbr_forward", "sbr_loss_backward_output", "sbr_backward_recurrent",
+           "sbr_train_step", "sbr_train_step_lagged", "sbr_cost_lagged", "sbr_lagged_flush", "sbr_zero_grads", "sbr_forward", "sbr_loss_backward_output", "sbr_backward_recurrent",
            "sbr_apply_update", "sbr_read_cost", "sbr_predict_scores", "sbr_topk", "sbr_rank", "sbr_debug_buffer",
            "sbr_copy_to_host", "sbr_synchronize", "sbr_enable_timing", "sbr_phase_times", "sbr_chain_times", "sbr_query",
            "sbr_set_deferred_join", "sbr_join_side", "sbr_debug_gemm", "sbr_debug_scatter", "sbr_debug_occupy", "sbr_flush_lazy", "sbr_sparse_info", "sbr_sparse_pack",
@@ -121,6 +121,7 @@ def load_library(path=None):
     lib.sbr_set_default_target.argtypes = [vp, vp]
     lib.sbr_train_step.argtypes = [vp, f32p]
     lib.sbr_train_step_lagged.argtypes = [vp, f32p, i32p]
+    lib.sbr_cost_lagged.argtypes = [vp, f32p, i32p]
     lib.sbr_lagged_flush.argtypes = [vp, f32p, i32p]
     for fn in (lib.sbr_zero_grads, lib.sbr_forward, lib.sbr_loss_backward_output, lib.sbr_backward_recurrent,
                lib.sbr_apply_update, lib.sbr_synchronize):
@@ -684,6 +685,14 @@ class RNNEngine(object):
         form, the host never waits for the step it has just enqueued.  flush_lagged() returns the last one."""
         cost, have = ctypes.c_float(), ctypes.c_int32()
         self._check(self.lib.sbr_train_step_lagged(self.h, ctypes.byref(cost), ctypes.byref(have)))
+        return float(cost.value) if have.value else None
+
+    def cost_lagged(self):
+        """Behind apply_update() of a phase-by-phase step (parallel.DataParallel.train_step): enqueues the report of that step's
+        cost -- the global one once the gradient section has been all-reduced -- and returns the cost the PREVIOUS lagged call
+        reported (None on the first); read_cost() without the wait for the stream.  flush_lagged() returns the last one."""
+        cost, have = ctypes.c_float(), ctypes.c_int32()
+        self._check(self.lib.sbr_cost_lagged(self.h, ctypes.byref(cost), ctypes.byref(have)))
         return float(cost.value) if have.value else None
 
     def flush_lagged(self):

@@ -52,6 +52,13 @@ class RNNBase(object):
                         "blockbuster_share": {"direction": -1}}
         self.engine = None
         self.dp = None          # parallel.DataParallel around self.engine in a multi-rank driver (attach_data_parallel)
+        self.dist = None        # the process group prepare_model builds that wrapper on (use_process_group)
+
+    def use_process_group(self, dist):
+        """Before prepare_model, on every rank of a launcher's job (train.main): the model then holds rows
+        [rank * B / world, (rank + 1) * B / world) of every batch, steps through a parallel.DataParallel and starts from rank 0's
+        parameters."""
+        self.dist = dist
 
     def attach_data_parallel(self, dp):
         """A multi-rank training driver hands over its parallel.DataParallel: from then on everything that reads parameters as a
@@ -89,16 +96,31 @@ class RNNBase(object):
                   embedding_size=self.recurrent_layer.embedding_size, bidirectional=self.recurrent_layer.bidirectional)
         kw.update(self.updater.engine_kwargs())
         kw.update(self._engine_kwargs())
-        self.engine = RNNEngine(**kw)
-        self._init_parameters()
+        if self.dist is None:
+            self.engine = RNNEngine(**kw)
+            self._init_parameters()
+            return
+        from .parallel import DataParallel
+        world, rank = self.dist.get_world_size(), self.dist.get_rank()
+        if self.batch_size % world:
+            raise ValueError("batch size %d does not divide by the world size %d" % (self.batch_size, world))
+        local = self.batch_size // world
+        self.engine = RNNEngine(local_batch=local, row_offset=rank * local, **kw)
+        self.attach_data_parallel(DataParallel(self.engine, self.dist))
+        # rank 0 draws exactly what a single process draws, in the same order; every other rank receives its arrays
+        values = self._initial_values() if rank == 0 else None
+        self.engine.set_all_param_values(self.dp.broadcast_params(values, self.engine.param_shapes))
 
-    def _init_parameters(self, seed=None):
+    def _initial_values(self, seed=None):
         """The initialisers the reference's layers name [3P] (engine.initial_values: gate weights and peepholes
         Normal(std 0.1), biases and initial states 0, stock RecurrentLayer weights U(-0.01, 0.01), embedding Normal(0.01),
         output W GlorotUniform(gain), output b 0), by parameter name."""
         from .engine import initial_values
         rng = np.random.RandomState(seed)
-        self.engine.set_all_param_values(initial_values(self.engine.param_descs, rng, getattr(self, "last_layer_init", 1.0)))
+        return initial_values(self.engine.param_descs, rng, getattr(self, "last_layer_init", 1.0))
+
+    def _init_parameters(self, seed=None):
+        self.engine.set_all_param_values(self._initial_values(seed))
 
     # ------------------------------------------------------------------ filenames (rnn_base.py:111-130)
     def _common_filename(self, epochs):
@@ -273,8 +295,25 @@ class RNNBase(object):
         if load_last_model:
             epochs_offset = self.load_last(save_dir)
         native = self._native_batch_builder(dataset)
+        # several ranks: the same loop on every rank, stepping through the data-parallel wrapper.  Iteration counts, costs (the
+        # all-reduced, global ones) and metrics are equal on all ranks by construction; the clock is not, so where the loop
+        # consults it (--max_time, --time_based_progress) rank 0's reading is used by all -- a broadcast made only then: with
+        # the default options the loop adds no collective of its own per iteration.  All ranks enter save together, rank 0 alone
+        # keeps and deletes files and prints.
+        dp = self.dp
+        ranks = dp.world if dp is not None else 1
+        rank0 = dp is None or dp.rank == 0
+        if dp is not None and native is None:
+            raise ValueError("data-parallel training runs on device-built batches only: " + str(self._native_batch_refusal(dataset)))
+        stepper = dp if dp is not None else self.engine
+        save = self.save if dp is None else (lambda f: self.save(f, write=rank0))
+        shared_clock = ranks > 1 and (max_time != np.inf or time_based_progress)
         batch_generator = native if native is not None else self._gen_mini_batch(self.sequence_noise(dataset.training_set()))
         start_time = time()
+
+        def now():
+            t = time() - start_time
+            return dp.broadcast_scalar(t) if shared_clock else t
         next_save = int(progress)
         train_costs, current_train_cost, epochs = [], [], []
         metrics = {name: [] for name in self.metrics.keys()}
@@ -286,37 +325,39 @@ class RNNBase(object):
                 current_train_cost.append(cost)
 
         try:
-            while time() - start_time < max_time and iterations < max_iter:
+            while now() < max_time and iterations < max_iter:
                 try:
                     batch = next(batch_generator)
                     # device batches: the step is enqueued and the PREVIOUS step's cost comes back (no wait for the step
                     # just enqueued); the last one is collected before anything reads the costs or the parameters
-                    take(self.engine.train_step_lagged() if native is not None else self.train_function(*batch))
+                    take(stepper.train_step_lagged() if native is not None else self.train_function(*batch))
                 except StopIteration:
                     break
                 iterations += 1
-                progress_indicator = int(time() - start_time) if time_based_progress else iterations
+                progress_indicator = int(now()) if time_based_progress else iterations
                 if progress_indicator >= next_save:
                     if native is not None:
-                        take(self.engine.flush_lagged())
+                        take(stepper.flush_lagged())
                     if progress_indicator >= min_iterations:
                         epochs.append(epochs_offset + dataset.training_set.epochs)
                         train_costs.append(np.mean(current_train_cost))
                         current_train_cost = []
                         metrics = self._compute_validation_metrics(metrics)
-                        self._print_progress(iterations, epochs[-1], start_time, train_costs, metrics, validation_metrics)
+                        if rank0:
+                            self._print_progress(iterations, epochs[-1], start_time, train_costs, metrics, validation_metrics)
                         run_nb = len(metrics[list(self.metrics.keys())[0]]) - 1
                         if autosave == "All":
                             filename[run_nb] = save_dir + self._get_model_filename(round(epochs[-1], 3))
-                            self.save(filename[run_nb])
+                            save(filename[run_nb])
                         elif autosave == "Best":
                             pareto_runs = self.get_pareto_front(metrics, validation_metrics)
                             if run_nb in pareto_runs:
                                 filename[run_nb] = save_dir + self._get_model_filename(round(epochs[-1], 3))
-                                self.save(filename[run_nb])
+                                save(filename[run_nb])
                                 for run in [r for r in filename if r not in pareto_runs]:
                                     try:
-                                        os.remove(filename[run])
+                                        if rank0:
+                                            os.remove(filename[run])
                                     except OSError:
                                         print("Warning : Previous model could not be deleted")
                                     del filename[run]
@@ -330,12 +371,15 @@ class RNNBase(object):
         except KeyboardInterrupt:
             print("Training interrupted")
         if native is not None:
-            take(self.engine.flush_lagged())
+            take(stepper.flush_lagged())
+        elapsed = time() - start_time
+        if ranks > 1:
+            elapsed = dp.broadcast_scalar(elapsed)       # (every rank returns rank 0's: once, behind the loop)
         if not metrics[validation_metrics[0]]:
-            return {}, time() - start_time, None
+            return {}, elapsed, None
         best_run = int(np.argmax(np.array(metrics[validation_metrics[0]]) * self.metrics[validation_metrics[0]]["direction"]))
         # the reference raises KeyError here when the best run was not saved (--save None): return None instead
-        return ({m: metrics[m][best_run] for m in self.metrics.keys()}, time() - start_time, filename.get(best_run))
+        return ({m: metrics[m][best_run] for m in self.metrics.keys()}, elapsed, filename.get(best_run))
 
     def batched_test_predictions(self, sequence_generator, k=10):
         """Batched form of the reference's per-user validation loop (rnn_base.py:358-371): the same
@@ -361,20 +405,13 @@ class RNNBase(object):
     def _native_batch_builder(self, dataset):
         """Device-side batch builder: item index, + rating index with --rf; next-item or shuffled targets, --n_targets of them
         for the multi-target losses; --db, --sampling_bias; the sequence noise; --target_bias (rows planned on the host by
-        the library).  None -> the reference-style host generator: SBR_NATIVE_BATCHES=0, or a case the builder refuses."""
-        if os.environ.get("SBR_NATIVE_BATCHES", "1") == "0":
+        the library).  None -> the reference-style host generator: SBR_NATIVE_BATCHES=0, or a case the builder refuses
+        (_native_batch_refusal names it).  With a data-parallel wrapper attached every rank plans the same passes -- what the
+        plan and the draws depend on is rank 0's (NativeBatchBuilder, sync=) -- and builds its own rows of each batch."""
+        if self._native_batch_refusal(dataset) is not None:
             return None
         ts = self.target_selection
         multi = isinstance(self, RNNMargin)                  # only the multi-target losses look past the first target
-        if self.sequence_noise.name != "":
-            if not hasattr(dataset.training_set, "users"):
-                dataset.training_set.load()
-            if max([len(x) for x in dataset.training_set.items] + [0]) > 8192:
-                return None  # (a sequence longer than the noise kernel's LDS staging)
-        if ts.shuffle and multi and self._engine_targets() > 16 and ts.bias < 0.0:
-            return None
-        if ts.bias >= 0.0 and multi and self._engine_targets() > 1024:
-            return None      # (the host row planner of --target_bias holds at most 1024 targets per row: sbr_dataset_set_target_bias)
         from .data import NativeBatchBuilder
         pop = np.asarray(dataset.item_popularity, dtype=np.float64)
         db = float(getattr(self, "diversity_bias", 0.0))
@@ -385,22 +422,45 @@ class RNNBase(object):
                                   ratings=self.use_ratings_features, shuffle_targets=ts.shuffle, noise=self.sequence_noise,
                                   keep_prob=(np.power(np.min(np.maximum(1, pop)) / np.maximum(1, pop), ts.bias).astype(np.float32)
                                              if ts.bias >= 0.0 else None),
-                                  n_targets=self._engine_targets() if multi else 1)
+                                  n_targets=self._engine_targets() if multi else 1, sync=self.dp)
+
+    def _native_batch_refusal(self, dataset):
+        """why this configuration trains on the reference-style host generator instead of device-built batches, or None; needs
+        neither an engine nor a device (train.main asks before it creates either)"""
+        if os.environ.get("SBR_NATIVE_BATCHES", "1") == "0":
+            return "SBR_NATIVE_BATCHES=0 selects the host batch generator"
+        ts = self.target_selection
+        multi = isinstance(self, RNNMargin)                  # only the multi-target losses look past the first target
+        if self.sequence_noise.name != "":
+            if not hasattr(dataset.training_set, "users"):
+                dataset.training_set.load()
+            if max([len(x) for x in dataset.training_set.items] + [0]) > 8192:
+                return "sequence noise over a sequence longer than 8192 items (the noise kernel's LDS staging)"
+        if ts.shuffle and multi and self._engine_targets() > 16 and ts.bias < 0.0:
+            return "--shuffle_targets with more than 16 targets per row"
+        if ts.bias >= 0.0 and multi and self._engine_targets() > 1024:
+            # (the host row planner of --target_bias holds at most 1024 targets per row: sbr_dataset_set_target_bias)
+            return "--target_bias with more than 1024 targets per row"
+        return None
 
     native_eval = True          # evaluate() ranks what this model's test function / top_k_recommendations rank (RNNCluster: no, it ranks inside a cluster)
 
     def _native_eval_users(self, dataset, which, evaluate_on=None, method="evaluate"):
         """(DeviceDataset, users, lengths) of dataset's "validation" / "test" set for one native evaluation call, or None where the
-        per-user host road must run: SBR_NATIVE_EVAL=0, a data-parallel wrapper (its collectives own the ranking calls), a
+        per-user host road must run: SBR_NATIVE_EVAL=0, under a data-parallel wrapper every call but evaluate() on the engine
+        (DataParallel.evaluate is the one sharded collective: evaluate_ranks and the cluster head's stay on the host road), a
         stand-in without evaluate() (evaluate_on: the object that must offer `method`, the engine by default), a shuffled set, or a
         target selection that may drop a test row (--rand_test_target with --target_bias)."""
         ts = self.target_selection
-        if os.environ.get("SBR_NATIVE_EVAL", "1") == "0" or self.dp is not None or not hasattr(self.engine if evaluate_on is None else evaluate_on, method):
+        if self.dp is not None and (method != "evaluate" or evaluate_on is not None):
+            return None
+        if os.environ.get("SBR_NATIVE_EVAL", "1") == "0" or not hasattr(self._rd() if evaluate_on is None else evaluate_on, method):
             return None
         if getattr(dataset, which + "_set").shuffle or (which == "validation" and not ts.determinist_test and ts.bias >= 0.0):
             return None      # (users in file order only; a validation row without a target is skipped by the host road)
         ds = dataset.device_set(which, self.engine, ratings=self.use_ratings_features)
-        print("Opening file (1)")                            # (the line the set's generator prints for its one pass)
+        if self.dp is None or self.dp.rank == 0:
+            print("Opening file (1)")                        # (the line the set's generator prints for its one pass)
         lens = ds.offsets[1:] - ds.offsets[:-1]
         users = np.nonzero(lens >= 2)[0].astype(np.int32)    # SequenceGenerator's min_length = 2 (data_handling.py:143)
         return ds, users, lens
@@ -420,7 +480,7 @@ class RNNBase(object):
         if found is None:
             return None
         ds, users, lens = found
-        rec = self.engine.evaluate(ds, users, k, mode, want_ids=want_ids, want_mask=True)
+        rec = self._rd().evaluate(ds, users, k, mode, want_ids=want_ids, want_mask=True)
         return self._evaluator_of_records(dataset, ds, users, lens, rec, k, want_ids)
 
     def native_evaluator(self, dataset, which, k, mode, want_ids=False):
@@ -762,6 +822,9 @@ class RNNCluster(RNNBase):
 
     def _native_batch_builder(self, dataset):
         return None          # the cluster samples and the growing scale are host state: the reference-style generator feeds this model
+
+    def _native_batch_refusal(self, dataset):
+        return "--clusters: the cluster samples and the growing scale are host state"
 
     # ------------------------------------------------------------------ the compiled-function seam
     def train_function(self, X, mask, target, samples, cluster_samples, exclude=None):

@@ -29,9 +29,62 @@ ordered on the stream it is issued under (this torch, 2.10, enqueues it there): 
 data when a DataParallel with more than one rank is built and otherwise falls back to the fully joined path (`stream_check`); no
 >1-GPU box was available to the builder to measure either placement.
 
+The training driver (`python -m sbr_amd.train` under a launcher: `init_from_env`, models.py) adds three things on top of the step:
+`train_step_lagged` / `flush_lagged` (the global cost one call late, through sbr_cost_lagged: no wait for the stream per iteration),
+`evaluate` (the validation users shared among the ranks behind ONE full flush, the records all-gathered: every rank returns the same
+dictionary) and the small broadcasts by which rank 0 decides what all ranks must agree on (initial parameters, seeds, the order of a
+pass, the clock where an option consults it).
+
 `engine` is anything with the RNNEngine phase methods -- the CPU tests pass an oracle-backed
 stand-in, production passes engine.RNNEngine.
 """
+
+
+BACKENDS = ("nccl", "gloo")
+
+
+def env_world(environ=None):
+    """WORLD_SIZE of a launcher's job (torch.distributed.run sets it); 1 without one"""
+    import os
+    return int((os.environ if environ is None else environ).get("WORLD_SIZE", "") or 1)
+
+
+def device_for_rank(local_rank, n_devices, backend):
+    """The device of a rank, as bench.py --dp-backend chooses it: LOCAL_RANK when that device exists; otherwise gloo lets several
+    ranks share a device (LOCAL_RANK % device_count) and nccl refuses (RCCL needs one GPU per rank)."""
+    if backend not in BACKENDS:
+        raise ValueError("SBR_DP_BACKEND=%r: must be one of %s" % (backend, "|".join(BACKENDS)))
+    if n_devices < 1:
+        raise RuntimeError("data-parallel training runs on the HIP engine: no GPU visible")
+    if local_rank < n_devices:
+        return local_rank
+    if backend == "nccl":
+        raise RuntimeError("LOCAL_RANK=%d but %d visible device(s): RCCL needs one GPU per rank (SBR_DP_BACKEND=gloo shares devices)"
+                           % (local_rank, n_devices))
+    return local_rank % n_devices
+
+
+def init_from_env(environ=None):
+    """The process group of a launcher's job, from RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT; the backend from
+    SBR_DP_BACKEND (nccl = RCCL, the default; gloo lets several ranks share one device).  Selects the rank's device and returns
+    torch.distributed; None when WORLD_SIZE is unset or 1 (nothing is initialised).  The caller destroys the group."""
+    import os
+    environ = os.environ if environ is None else environ
+    world = env_world(environ)
+    if world <= 1:
+        return None
+    import torch
+    import torch.distributed as dist
+    rank = int(environ["RANK"])
+    backend = environ.get("SBR_DP_BACKEND", "nccl")
+    index = device_for_rank(int(environ.get("LOCAL_RANK", rank)), torch.cuda.device_count(), backend)
+    torch.cuda.set_device(index)
+    init = "tcp://%s:%s" % (environ["MASTER_ADDR"], environ["MASTER_PORT"])
+    if backend == "nccl":
+        dist.init_process_group("nccl", init_method=init, rank=rank, world_size=world, device_id=torch.device("cuda", index))
+    else:
+        dist.init_process_group("gloo", init_method=init, rank=rank, world_size=world)
+    return dist
 
 
 class DataParallel(object):
@@ -273,6 +326,118 @@ class DataParallel(object):
             for b in range(self._nsparse):
                 self._exchange_sparse(b)
         e.apply_update()
+
+    # ---- the training loop's form of the step: the cost one call late, without a wait for the stream
+    def train_step_lagged(self):
+        """train_step() and the cost of the PREVIOUS lagged step (None on the first): after the all-reduce the cost word at the
+        end of the gradient section is the global cost, engine.cost_lagged() reports it through pinned memory one call late --
+        read_cost() would wait for the stream every iteration.  flush_lagged() returns the last one."""
+        self.train_step()
+        return self.engine.cost_lagged()
+
+    def flush_lagged(self):
+        return self.engine.flush_lagged()
+
+    # ---- what rank 0 decides for all: seeds, the order of a pass, its reading of the clock, the initial parameters
+    def _control_device(self):
+        """where the small tensors of the broadcasts below live: RCCL moves device memory only, gloo moves host memory"""
+        if not hasattr(self, "_ctl"):
+            nccl = getattr(self.dist, "get_backend", lambda g=None: "gloo")(self.group) == "nccl"
+            self._ctl = self.grads.device if nccl else "cpu"
+        return self._ctl
+
+    def broadcast_array(self, array, shape=None, dtype="float64"):
+        """rank 0's numpy array on every rank; the others pass None and the shape and dtype they expect"""
+        import numpy as np
+        if self.world == 1:
+            return array
+        import torch
+        a = np.ascontiguousarray(array) if self.rank == 0 else np.empty(shape, dtype=dtype)
+        t = torch.from_numpy(a.reshape(-1)).to(self._control_device())
+        self.dist.broadcast(t, src=0, group=self.group)
+        return t.cpu().numpy().reshape(a.shape)
+
+    def broadcast_scalar(self, value):
+        """rank 0's value (a float64: exact for seeds below 2**53 only -- see broadcast_seed) on every rank"""
+        import numpy as np
+        return float(self.broadcast_array(np.array([value], dtype=np.float64), (1,), "float64")[0])
+
+    def broadcast_seed(self, seed):
+        """rank 0's seed (any int below 2**64) on every rank"""
+        import numpy as np
+        return int(self.broadcast_array(np.array([int(seed or 0)], dtype=np.uint64).view(np.int64), (1,), "int64").view(np.uint64)[0])
+
+    def broadcast_params(self, values, shapes):
+        """rank 0's parameter list (float32 arrays in get_all_param_values order) on every rank: one flat broadcast"""
+        import numpy as np
+        sizes = [int(np.prod(s)) for s in shapes]
+        flat = None if self.rank != 0 else np.concatenate([np.asarray(v, dtype=np.float32).reshape(-1) for v in values])
+        flat = self.broadcast_array(flat, (sum(sizes),), "float32")
+        out, o = [], 0
+        for s, n in zip(shapes, sizes):
+            out.append(flat[o:o + n].reshape(s)); o += n
+        return out
+
+    # ---- validation: every rank evaluates a share of the users, the records are gathered into user order
+    def evaluate(self, dataset, users, k, exclude_mode, want_ids=False, want_mask=True):
+        """engine.evaluate(dataset, users, ...) as ONE collective: behind a barrier every rank makes a full flush_lazy, evaluates
+        users[lo:hi] of its shard and the per-user records are all-gathered into user order (padded to the largest share and
+        cut); item_hits is summed.  Every rank returns the same dictionary -- what engine.evaluate returns for the whole list.
+        The full flush is what keeps the replicas identical: sbr_evaluate brings current only what it reads (every output row,
+        but the W_in rows of its OWN users only), and where a replay of missed steps is split changes float32 roundings (module
+        docstring) -- ranks that evaluate different users would leave with different replicas.  After the flush nothing a share
+        reads has anything left to replay."""
+        import numpy as np
+        e = self.engine
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        self._collective("flush_lazy")                   # barrier + the full flush, on every rank
+        if self.world == 1:
+            e._dp_collective = True
+            try:
+                return e.evaluate(dataset, users, k, exclude_mode, want_ids=want_ids, want_mask=want_mask)
+            finally:
+                e._dp_collective = False
+        import torch
+        n = len(users)
+        spans = [self.shard(n, self.world, r) for r in range(self.world)]
+        lo, hi = spans[self.rank]
+        cap = max(b - a for a, b in spans)
+        k = int(k)
+        widths = [("n_pred", 1), ("hits", 1), ("first_hit", 1)]
+        if want_mask:
+            widths.append(("hitmask", (k + 31) // 32))
+        if want_ids:
+            widths.append(("ids", k))
+        n_items = int(e.n_items)
+        # one int32 message per rank: `cap` rows of the per-user records side by side, then item_hits
+        row = sum(w for _, w in widths)
+        msg = np.zeros(cap * row + n_items, dtype=np.int32)
+        if hi > lo:                                      # (an empty share makes no engine call: sbr_evaluate rejects n < 1)
+            e._dp_collective = True
+            try:
+                rec = e.evaluate(dataset, users[lo:hi], k, exclude_mode, want_ids=want_ids, want_mask=want_mask)
+            finally:
+                e._dp_collective = False
+            body, o = msg[:cap * row].reshape(cap, row), 0
+            for name, w in widths:
+                body[:hi - lo, o:o + w] = np.asarray(rec[name]).view(np.int32).reshape(hi - lo, w); o += w
+            msg[cap * row:] = rec["item_hits"]
+        dev = self._control_device()
+        mine = torch.from_numpy(msg).to(dev)
+        parts = [torch.empty_like(mine) for _ in range(self.world)]
+        self.dist.all_gather(parts, mine, group=self.group)
+        parts = [p.cpu().numpy() for p in parts]
+        out = {"item_hits": np.zeros(n_items, dtype=np.int32), "hitmask": None, "ids": None}
+        cols = {name: [] for name, _ in widths}
+        for (a, b), p in zip(spans, parts):
+            body, o = p[:cap * row].reshape(cap, row), 0
+            for name, w in widths:
+                cols[name].append(body[:b - a, o:o + w]); o += w
+            out["item_hits"] += p[cap * row:]
+        for name, w in widths:
+            a = np.ascontiguousarray(np.concatenate(cols[name], axis=0))
+            out[name] = a.reshape(n) if name in ("n_pred", "hits", "first_hit") else (a.view(np.uint32) if name == "hitmask" else a)
+        return out
 
     @staticmethod
     def exposed_us(exposed):

@@ -72,9 +72,33 @@ def get_early_stopper(args):                    # helpers/early_stopping.py:11-1
 def main(argv=None):
     args = parse.command_parser(parse.predictor_command_parser, parse.training_command_parser,
                                 early_stopping_command_parser, argv=argv)
+    from . import parallel
+    world = parallel.env_world()
+    if world > 1:
+        # one rank of a launcher's job (python -m torch.distributed.run --nproc-per-node N -m sbr_amd.train ...): every rank
+        # refuses the same configurations for the same reason, before a process group or an engine exists
+        if args.batch_size % world:
+            raise ValueError("data-parallel training: batch size %d does not divide by the world size %d" % (args.batch_size, world))
+        if args.clusters > 0:
+            raise ValueError("data-parallel training: --clusters is not supported (the cluster head is single-rank)")
     predictor = parse.get_predictor(args)
     dataset = DataHandler(dirname=args.dataset, extended_training_set=args.extended_set, shuffle_training=args.tshuffle)
-    predictor.prepare_model(dataset)
+    if world > 1:
+        reason = predictor._native_batch_refusal(dataset)
+        if reason is not None:
+            raise ValueError("data-parallel training runs on device-built batches only: " + reason)
+    dist = parallel.init_from_env()          # None without a launcher (WORLD_SIZE unset or 1): nothing below changes
+    try:
+        if dist is not None:
+            predictor.use_process_group(dist)
+        predictor.prepare_model(dataset)
+        return _train(predictor, dataset, args)
+    finally:
+        if dist is not None:
+            dist.destroy_process_group()
+
+
+def _train(predictor, dataset, args):
     return predictor.train(dataset,
                            save_dir=dataset.dirname + "models/" + args.dir,
                            time_based_progress=args.time_based_progress,
