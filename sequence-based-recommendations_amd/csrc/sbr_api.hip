@@ -221,13 +221,13 @@ int sbr_build_layout(const sbr_config& cfg, Layout& lay, std::string& err) {
             b.a_last = take(b.n_rows); b.a_mark = take(b.n_rows); b.a_cand = take(b.cand_cap); b.a_count = take(64);
         }
         if (lay.n_sparse && cfg.updater == SBR_UPD_ADAM) {
-            // a_t = lr sqrt(1 - b2^t) / (1 - b1^t) as the dense launch computes it (double, rounded to float), tabulated until
-            // it has been == (float)lr for a while; the catch-up replays missed steps with their own a_t
+            // a_t (sbr_adam_at: what the dense launches use), tabulated until it has been == (float)lr for a while; the catch-up
+            // replays missed steps with their own a_t
             const double lr = cfg.learning_rate, b1 = cfg.beta1, b2 = cfg.beta2;
             int t = 1, same = 0; double worst = 0.0, prev = 0.0;
             const int cap = 1 << 22;
             for (; t <= cap && same < 256; ++t) {
-                const double a = lr * sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t));
+                const double a = sbr_adam_at_d(lr, b1, b2, t);
                 same = ((float)a == (float)lr) ? same + 1 : 0;
                 if (t > 1) worst = std::max(worst, a / prev);
                 prev = a;
@@ -441,8 +441,7 @@ extern "C" int sbr_create(const sbr_config* cfg, void* arena, size_t arena_bytes
     if (e != hipSuccess) { sbr_set_error("arena initialisation failed: %s", hipGetErrorString(e)); sbr_destroy(h); return SBR_EHIP; }
     if (h->lay.n_at > 0) {
         std::vector<float> at(h->lay.n_at);
-        const double lr = cfg->learning_rate, b1 = cfg->beta1, b2 = cfg->beta2;
-        for (int t = 1; t <= h->lay.n_at; ++t) at[t - 1] = (float)(lr * sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t)));
+        for (int t = 1; t <= h->lay.n_at; ++t) at[t - 1] = sbr_adam_at(cfg->learning_rate, cfg->beta1, cfg->beta2, t);
         e = hipMemcpy(h->A(h->lay.a_at), at.data(), at.size() * sizeof(float), hipMemcpyHostToDevice);
         if (e != hipSuccess) { sbr_set_error("a_t table upload failed: %s", hipGetErrorString(e)); sbr_destroy(h); return SBR_EHIP; }
     }

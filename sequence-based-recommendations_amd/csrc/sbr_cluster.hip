@@ -300,10 +300,9 @@ extern "C" int sbr_cluster_apply_update(sbr_cluster* k) {      // self.updater(c
     const sbr_cluster_config& c = k->cfg;
     k->step += 1;
     const bool two = c.updater == SBR_UPD_ADAM || c.updater == SBR_UPD_ADADELTA;
-    CL_HIP(launch_update(k->stream, c.updater, k->Wc, k->dWc, k->sWc[0], two ? k->sWc[1] : nullptr, (size_t)c.n_hidden * c.n_clusters,
-                         c.learning_rate, c.rho, c.beta1, c.beta2, k->step));
-    CL_HIP(launch_update(k->stream, c.updater, k->R, k->dR, k->sR[0], two ? k->sR[1] : nullptr, (size_t)c.n_items * c.n_clusters,
-                         c.learning_rate, c.rho, c.beta1, c.beta2, k->step));
+    const SbrUpdRule st = sbr_upd_rule(c.updater, c.learning_rate, c.rho, c.beta1, c.beta2, k->step);
+    CL_HIP(launch_update(k->stream, st, k->Wc, k->dWc, k->sWc[0], two ? k->sWc[1] : nullptr, (size_t)c.n_hidden * c.n_clusters));
+    CL_HIP(launch_update(k->stream, st, k->R, k->dR, k->sR[0], two ? k->sR[1] : nullptr, (size_t)c.n_items * c.n_clusters));
     k->hard_valid = 0; k->hardT_valid = 0; k->lists_valid = 0;
     k->dR_clean = 1;                                 // update_kernel has cleared dR (and dWc)
     return SBR_OK;

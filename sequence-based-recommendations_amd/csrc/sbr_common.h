@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "../../include/sbr_rnn.h"
+#include "sbr_upd.h"
 
 #define SBR_BWD_CHUNKS 4       // BPTT launches per layer when T >= 64 (bf16x6 kernels)
 #define SBR_ALIGN_FLOATS 64   // every carved buffer starts on a 256-byte boundary
@@ -502,9 +503,6 @@ hipError_t launch_scatter_range(hipStream_t s, float* dWin, const float* dxt, co
 // form 2 (512 .. 2048 floats): segment-parallel scatter-add, no atomics on rows
 hipError_t launch_scatter_wide(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos, const int* offs, int n_ids,
                                int max_entries, int GHp, float* part, int* aux, int n_slots, const ScatPlan& plan);
-// arguments of the optimizer step of a block's rows (update_rows_aware_kernel, out_grad_step_kernel): p / s0 / s1 = parameter and
-// optimizer-state rows (s1 NULL where the updater has one state array); the arithmetic is update_kernel's, element for element
-struct SbrScatStep { float* p; float* s0; float* s1; int* last; int updater, t_to; float lr, rho, b1, b2, a_t; };
 // form 0: one wave per 32 sorted entries sums the rows of equal id in registers
 hipError_t launch_scatter_reduce(hipStream_t s, float* dWin, const float* dxt, const int* sid, const int* spos,
                                  const int* offs, int n_ids, int max_entries, int GHp, int Bp, const ScatReduce& recipe);
@@ -695,22 +693,26 @@ hipError_t launch_sampled_loss(hipStream_t s, float* act, const float* bc, const
                                int Bg, int S, int row_offset, int loss, int Bglobal);
 hipError_t launch_scatter_cells(hipStream_t s, float* dW, float* db, const float* dWc, const float* dbc,
                                 const int* cells, int C, int Hp);
-// optimizers (lasagne.updates.* [3P], update_manager.py:24-82)
+// optimizers (lasagne.updates.* [3P], update_manager.py:24-82): the dense step kernels (sbr_update.hip) take the step's rule
+// (sbr_upd.h); s1 NULL where the updater has one state array
 // n elements starting at p / g / s0 / s1, skipping gap_len elements after the first gap_at (two ranges, one launch)
-// the output layer's gradient + its step in one launch (sbr_misc.hip); false: shape not served
-bool launch_out_grad_step(hipStream_t s, const float* dlogits, const float* h_last, const float* rowcost, float* cost, int updater,
-                          float* W, float* Ws0, float* Ws1, float* b, float* bs0, float* bs1, int R, int N, int Nl, int Hp, float lr,
-                          float rho, float b1, float b2, long t, hipError_t* err);
-hipError_t launch_update_rows_aware(hipStream_t s, int updater, float* p, float* g, float* s0, float* s1, int n_rows, int row_floats,
-                                    const int* offs, float lr, float rho, float b1, float b2, long t);
-hipError_t launch_update(hipStream_t s, int updater, float* p, float* g, float* s0, float* s1, size_t n,
-                         float lr, float rho, float b1, float b2, long t, size_t gap_at = (size_t)-1, size_t gap_len = 0);
+hipError_t launch_update(hipStream_t s, const SbrUpdRule& st, float* p, float* g, float* s0, float* s1, size_t n,
+                         size_t gap_at = (size_t)-1, size_t gap_len = 0);
 // ... of a block whose gradient is still split-K slabs [nslabs][n] (16-byte aligned, n % 4 == 0): reduction + step in one launch
-hipError_t launch_update_from_slabs(hipStream_t s, int updater, const float* ws, int nslabs, float* p, float* s0, float* s1, size_t n,
-                                    float lr, float rho, float b1, float b2, long t);
+hipError_t launch_update_from_slabs(hipStream_t s, const SbrUpdRule& st, const float* ws, int nslabs, float* p, float* s0, float* s1,
+                                    size_t n);
+// ... of an item-indexed block of n_rows rows, reading / clearing the gradient of the rows with offs[r + 1] > offs[r] only
+hipError_t launch_update_rows_aware(hipStream_t s, const SbrUpdRule& st, float* p, float* g, float* s0, float* s1, int n_rows,
+                                    int row_floats, const int* offs);
+// the output layer's gradient + its step in one launch; false: shape not served
+bool launch_out_grad_step(hipStream_t s, const SbrUpdRule& st, const float* dlogits, const float* h_last, const float* rowcost,
+                          float* cost, float* W, float* Ws0, float* Ws1, float* b, float* bs0, float* bs1, int R, int N, int Nl, int Hp,
+                          hipError_t* err);
 // sbr_sparse.hip: row-sparse optimizer steps (lazy catch-up) and gradient exchange for the large-catalogue blocks
 struct SbrSparseRows { int npairs; size_t off[2]; int width[2]; int stride[2]; int n_rows; float *p, *g, *s0, *s1; int* last; };
-struct SbrSparseUpd { int updater; float lr, rho, b1, b2; const float* at; int n_at; int early_exit; };
+// rule.a_t is not used on this path: a row kernel replays steps of several numbers and reads each one's a_t from the table
+// at[t - 1], t = 1 .. n_at (sbr_adam_at; beyond it a_t == lr); early_exit: a missed Adam step's update shrinks monotonically
+struct SbrSparseUpd { SbrUpdRule rule; const float* at; int n_at; int early_exit; };
 hipError_t launch_sparse_catch_up_batch(hipStream_t s, const SbrSparseRows& r, const SbrSparseUpd& c, const int* X, const int* len, int T,
                                         int Bp, int F, int t_to);
 hipError_t launch_sparse_catch_up_list(hipStream_t s, const SbrSparseRows& r, const SbrSparseUpd& c, const int* list, const int* n_dev,

@@ -1,6 +1,6 @@
 // HBM-bound and small kernels of the hot path (gfx950, wave64): embedding-bag gather (K1; its
 // scatter-add gradient, K6: sbr_scatter.hip), softmax / cross-entropy (K8), sampled heads (K10-K12),
-// optimizers (K13), test-path exclusion + top-k (K14).
+// test-path exclusion + top-k (K14).  (The optimizers, K13: sbr_upd.h, sbr_update.hip.)
 #include "sbr_common.h"
 #include "sbr_rec_p.h"
 #include "sbr_device.h"
@@ -151,35 +151,6 @@ hipError_t launch_gather_xt(hipStream_t s, const float* Win, const float* bias, 
     const int grid = (int)min((size_t)256 * 16, (total + 255) / 256);
     gather_xt_kernel<<<grid, 256, 0, s>>>((const f32x4*)Win, (const f32x4*)bias, X, (f32x4*)xt, T, Bp, F, R4);
     return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// The optimizer step of one element / one 16-byte piece on registers (SbrScatStep in sbr_common.h): update_element's arithmetic,
-// for the kernels that hold a finished gradient in registers (update_rows_aware_kernel, out_grad_step_kernel).
-// (Round 5 also built a scatter-add that stepped the rows it completed -- launch_scatter_wide_step: correct, 20 % fewer bytes behind
-// the chain, and slower (C4 1.324 -> 1.375 ms): its waves held a row's optimizer state beside the dxt rows of a segment and ran at
-// 1.5 - 2.3 TB/s where the two-pass form streams at 3.6 - 6.2.  Removed in round 6; the numbers are in profiles/round5_a_*.)
-// ---------------------------------------------------------------------------------------
-__device__ __forceinline__ void scat_step1(const SbrScatStep& st, float g, float& p, float& s0, float& s1) {
-    switch (st.updater) {                                     // update_element's arithmetic (sbr_misc.hip K13), on registers
-        case SBR_UPD_ADAGRAD: { const float acc = s0 + g * g; s0 = acc; p -= st.lr * g / sqrtf(acc + 1e-6f); return; }
-        case SBR_UPD_RMSPROP: { const float acc = st.rho * s0 + (1.0f - st.rho) * g * g; s0 = acc; p -= st.lr * g / sqrtf(acc + 1e-6f); return; }
-        case SBR_UPD_ADADELTA: {
-            const float acc = st.rho * s0 + (1.0f - st.rho) * g * g;
-            const float upd = g * sqrtf(s1 + 1e-6f) / sqrtf(acc + 1e-6f);
-            s0 = acc; p -= st.lr * upd; s1 = st.rho * s1 + (1.0f - st.rho) * upd * upd; return;
-        }
-        case SBR_UPD_NESTEROV: { const float v = st.rho * s0 - st.lr * g; s0 = v; p += st.rho * v - st.lr * g; return; }
-        default: {
-            const float m = st.b1 * s0 + (1.0f - st.b1) * g;
-            const float v = st.b2 * s1 + (1.0f - st.b2) * g * g;
-            s0 = m; s1 = v; p -= st.a_t * m / (sqrtf(v) + 1e-8f); return;
-        }
-    }
-}
-__device__ __forceinline__ void scat_step4(const SbrScatStep& st, const f32x4& g, f32x4& p, f32x4& s0, f32x4& s1) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) { float pe = p[e], ae = s0[e], be = s1[e]; scat_step1(st, g[e], pe, ae, be); p[e] = pe; s0[e] = ae; s1[e] = be; }
 }
 
 // Gate of the overlapped step tail (sbr_backward_recurrent): returns once every wave of the running BPTT chain
@@ -630,232 +601,6 @@ __global__ void scatter_cells_kernel(float* __restrict__ dW, float* __restrict__
 hipError_t launch_scatter_cells(hipStream_t s, float* dW, float* db, const float* dWc, const float* dbc, const int* cells,
                                 int C, int Hp) {
     scatter_cells_kernel<<<(C * Hp + 255) / 256, 256, 0, s>>>(dW, db, dWc, dbc, cells, C, Hp);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// K13 optimizers: lasagne.updates.{adagrad,adadelta,rmsprop,nesterov_momentum,adam} [3P]
-// (update_manager.py:24-82), applied densely to the whole flat parameter section.
-// ---------------------------------------------------------------------------------------
-// one element's step: gi = its gradient; p, s0, s1 are read and written in place
-__device__ __forceinline__ void update_element(int updater, float gi, float* __restrict__ p, float* __restrict__ s0, float* __restrict__ s1,
-                                               size_t i, float lr, float rho, float b1, float b2, float a_t) {
-    float pi = p[i];
-    if (updater == SBR_UPD_ADAGRAD) {                 // eps 1e-6
-        const float acc = s0[i] + gi * gi;
-        s0[i] = acc; pi -= lr * gi / sqrtf(acc + 1e-6f);
-    } else if (updater == SBR_UPD_RMSPROP) {          // eps 1e-6
-        const float acc = rho * s0[i] + (1.0f - rho) * gi * gi;
-        s0[i] = acc; pi -= lr * gi / sqrtf(acc + 1e-6f);
-    } else if (updater == SBR_UPD_ADADELTA) {         // eps 1e-6
-        const float acc = rho * s0[i] + (1.0f - rho) * gi * gi;
-        const float upd = gi * sqrtf(s1[i] + 1e-6f) / sqrtf(acc + 1e-6f);
-        s0[i] = acc; pi -= lr * upd;
-        s1[i] = rho * s1[i] + (1.0f - rho) * upd * upd;
-    } else if (updater == SBR_UPD_NESTEROV) {         // sgd + apply_nesterov_momentum
-        const float v = rho * s0[i] - lr * gi;
-        s0[i] = v; pi += rho * v - lr * gi;
-    } else {                                          // adam, eps 1e-8
-        const float m = b1 * s0[i] + (1.0f - b1) * gi;
-        const float v = b2 * s1[i] + (1.0f - b2) * gi * gi;
-        s0[i] = m; s1[i] = v;
-        pi -= a_t * m / (sqrtf(v) + 1e-8f);
-    }
-    p[i] = pi;
-}
-
-__global__ void update_kernel(int updater, float* __restrict__ p, float* __restrict__ g, float* __restrict__ s0,
-                              float* __restrict__ s1, size_t n, float lr, float rho, float b1, float b2, float a_t,
-                              size_t gap_at, size_t gap_len) {
-    // n elements of [0, gap_at) u [gap_at + gap_len, ...): two parameter ranges in one launch
-    for (size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x; k < n; k += (size_t)gridDim.x * blockDim.x) {
-        const size_t i = k < gap_at ? k : k + gap_len;
-        const float gi = g[i];
-        g[i] = 0.0f;                                      // the gradient section is clean for the next step (no memset)
-        update_element(updater, gi, p, s0, s1, i, lr, rho, b1, b2, a_t);
-    }
-}
-
-// The optimizer step of a parameter block whose gradient still lies in split-K slabs (dW_hid of the overlapped step tail): the
-// slab reduction of gemm_splitk_reduce_v4 -- same grouping, same summation order, so the same gradient bits -- with the step
-// applied by the thread that holds the finished sum.  One launch and one pass over the block less at the end of the step; the
-// gradient array itself is not written (it stays as the last update left it: zero).
-__global__ void __launch_bounds__(256) update_from_slabs_kernel(int updater, const f32x4* __restrict__ ws, int nsplit, size_t n,
-                                                                float* __restrict__ p, float* __restrict__ s0, float* __restrict__ s1,
-                                                                float lr, float rho, float b1, float b2, float a_t) {
-    __shared__ f32x4 red[16][16];
-    const size_t n4 = n / 4;
-    const int j = threadIdx.x & 15, grp = threadIdx.x >> 4;
-    const size_t i4 = (size_t)blockIdx.x * 16 + j;
-    f32x4 a0 = {0, 0, 0, 0}, a1 = a0, a2 = a0, a3 = a0;
-    if (i4 < n4) {
-        int z = grp;
-        for (; z + 48 < nsplit; z += 64) {
-            a0 += ws[(size_t)z * n4 + i4]; a1 += ws[(size_t)(z + 16) * n4 + i4];
-            a2 += ws[(size_t)(z + 32) * n4 + i4]; a3 += ws[(size_t)(z + 48) * n4 + i4];
-        }
-        for (; z < nsplit; z += 16) a0 += ws[(size_t)z * n4 + i4];
-    }
-    red[grp][j] = (a0 + a1) + (a2 + a3);
-    __syncthreads();
-    if (threadIdx.x >= 64) return;
-    const int jj = threadIdx.x >> 2, e = threadIdx.x & 3;             // one element per thread
-    const size_t i = ((size_t)blockIdx.x * 16 + jj) * 4 + e;
-    if (i >= n) return;
-    float t = 0.f;
-#pragma unroll
-    for (int g = 0; g < 16; ++g) t += red[g][jj][e];
-    update_element(updater, t, p, s0, s1, i, lr, rho, b1, b2, a_t);
-}
-
-hipError_t launch_update_from_slabs(hipStream_t s, int updater, const float* ws, int nslabs, float* p, float* s0, float* s1, size_t n,
-                                    float lr, float rho, float b1, float b2, long t) {
-    if (n == 0) return hipSuccess;
-    if ((n & 3) || ((uintptr_t)ws & 15)) return hipErrorInvalidValue;
-    float a_t = 0.0f;
-    if (updater == SBR_UPD_ADAM)
-        a_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
-    update_from_slabs_kernel<<<(unsigned)((n / 4 + 15) / 16), 256, 0, s>>>(updater, (const f32x4*)ws, nslabs, n, p, s0, s1, lr, rho, b1, b2, a_t);
-    return hipGetLastError();
-}
-
-// The dense pass over an item-indexed block, aware of which rows the batch touched (offs = the scatter's segment offsets): an
-// untouched row's gradient is zero and stays zero, so its step reads and writes p, s0, s1 only (6 passes instead of 8: C4 touches 40 %
-// of its 26 744 rows per batch); a touched row's gradient is read and cleared as update_kernel does.  One streaming launch, 16
-// bytes per lane, update_element's arithmetic for both kinds of row.
-__global__ void __launch_bounds__(256) update_rows_aware_kernel(SbrScatStep st, float* __restrict__ gr, int n_rows, int R4,
-                                                                const int* __restrict__ offs) {
-    const size_t n4 = (size_t)n_rows * R4;
-    f32x4* __restrict__ p = (f32x4*)st.p; f32x4* __restrict__ s0 = (f32x4*)st.s0; f32x4* __restrict__ s1 = (f32x4*)st.s1;
-    f32x4* __restrict__ g = (f32x4*)gr;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (size_t)gridDim.x * blockDim.x) {
-        const int r = (int)(i / (unsigned)R4);
-        const bool touched = offs[r + 1] > offs[r];
-        f32x4 gv = {0, 0, 0, 0};
-        if (touched) { gv = g[i]; g[i] = f32x4{0, 0, 0, 0}; }
-        f32x4 pv = p[i], av = s0[i], bv = s1 ? s1[i] : f32x4{0, 0, 0, 0};
-        scat_step4(st, gv, pv, av, bv);
-        p[i] = pv; s0[i] = av;
-        if (s1) s1[i] = bv;
-    }
-}
-hipError_t launch_update_rows_aware(hipStream_t s, int updater, float* p, float* g, float* s0, float* s1, int n_rows, int row_floats,
-                                    const int* offs, float lr, float rho, float b1, float b2, long t) {
-    if (n_rows <= 0) return hipSuccess;
-    if ((row_floats & 3) || !offs) return hipErrorInvalidValue;
-    SbrScatStep st; st.p = p; st.s0 = s0; st.s1 = s1; st.last = nullptr; st.updater = updater; st.t_to = (int)t;
-    st.lr = lr; st.rho = rho; st.b1 = b1; st.b2 = b2; st.a_t = 0.0f;
-    if (updater == SBR_UPD_ADAM)
-        st.a_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
-    const size_t n4 = (size_t)n_rows * (row_floats / 4);
-    const int grid = (int)min((size_t)256 * 16, (n4 + 255) / 256);
-    update_rows_aware_kernel<<<grid, 256, 0, s>>>(st, g, n_rows, row_floats / 4, offs);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------
-// The output layer's gradient AND its optimizer step in one launch (round 5; single-call steps of the dense heads, no bias
-// regulariser): dW_out^T[n][k] = sum_rows dlogits[row][n] h[row][k], db[n] = sum_rows dlogits[row][n], cost = sum_rows rowcost
-// (rnn_one_hot.py:65-77 backward + update_manager.py:24-82).  Before: sum_cost, two column-sum kernels, the dW_out GEMM (+ its
-// split-K reduction) and update_kernel -- five to six launches, 50 - 60 us with their gaps on the side stream, IN FRONT of the
-// polling weight-gradient GEMM of the overlapped tail, which therefore started 68 us into a 138 us BPTT chain and ended 39 us
-// behind it (profiles/round4_z_c2_timeline.txt).  Here a workgroup owns 16 items: its four waves split the batch rows, every
-// wave accumulates D[k][item] over its rows on v_mfma_f32_16x16x4_f32 (k slot q = row r0 + q; operands straight from L2: 64
-// contiguous bytes per 16 lanes), the partial sums meet in LDS, and the thread that holds four consecutive k of an item steps
-// W_out^T[item][k .. k + 3] (update_element's arithmetic: scat_step4); the gradient arrays are never written (they stay zero).
-// ---------------------------------------------------------------------------------------
-template <int HP>
-__global__ void __launch_bounds__(256) out_grad_step_kernel(const float* __restrict__ dlog, const float* __restrict__ h,
-                                                            const float* __restrict__ rowcost, float* __restrict__ cost, SbrScatStep st,
-                                                            float* __restrict__ bp, float* __restrict__ bs0, float* __restrict__ bs1,
-                                                            int R, int N, int Nl) {
-    constexpr int KG = HP / 16;
-    __shared__ __attribute__((aligned(16))) f32x4 part[4][KG][64];
-    __shared__ float dbp[4][16];
-    __shared__ float red[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, q = lane >> 4;
-    const int n0 = blockIdx.x * 16;
-    const bool col_in = n0 + j < N;
-    const int rpw = ((R + 3) / 4 + 3) / 4 * 4;                       // rows per wave, a multiple of 4
-    const int r_lo = wave * rpw, r_hi = min(R, r_lo + rpw);
-    f32x4 acc[KG];
-#pragma unroll
-    for (int kt = 0; kt < KG; ++kt) acc[kt] = f32x4{0, 0, 0, 0};
-    float dbv = 0.0f;
-    for (int r0 = r_lo; r0 < r_hi; r0 += 16) {                      // four row groups per round: their 4 + 4 KG loads in flight together
-        float d[4], hv[4][KG];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int row = r0 + 4 * u + q;
-            const bool in = row < r_hi;
-            d[u] = (in && col_in) ? dlog[(size_t)row * Nl + n0 + j] : 0.0f;
-            const float* hr = h + (size_t)(in ? row : r_lo) * HP + j;
-#pragma unroll
-            for (int kt = 0; kt < KG; ++kt) hv[u][kt] = in ? hr[16 * kt] : 0.0f;
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            dbv += d[u];
-#pragma unroll
-            for (int kt = 0; kt < KG; ++kt) acc[kt] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[u][kt], d[u], acc[kt], 0, 0, 0);
-        }
-    }
-    asm volatile("s_nop 15");                                        // MFMA D -> VALU read across the loop exit
-#pragma unroll
-    for (int kt = 0; kt < KG; ++kt) part[wave][kt][lane] = acc[kt];
-    dbv += __shfl_xor(dbv, 16); dbv += __shfl_xor(dbv, 32);
-    if (q == 0) dbp[wave][j] = dbv;
-    if (blockIdx.x == 0) {                                           // the batch cost: fixed order
-        float c = 0.0f;
-        for (int r = tid; r < R; r += 256) c += rowcost[r];
-        c = block_sum(c, red);
-        if (tid == 0) *cost = c;
-    }
-    __syncthreads();
-    for (int i = tid; i < KG * 64; i += 256) {
-        const int kt = i >> 6, ln = i & 63, item = n0 + (ln & 15), k = 16 * kt + 4 * (ln >> 4);
-        if (item >= N) continue;
-        const f32x4 g = (part[0][kt][ln] + part[1][kt][ln]) + (part[2][kt][ln] + part[3][kt][ln]);
-        const size_t o = (size_t)item * HP + k;
-        f32x4 pv = *(const f32x4*)(st.p + o), av = *(const f32x4*)(st.s0 + o), bv = st.s1 ? *(const f32x4*)(st.s1 + o) : f32x4{0, 0, 0, 0};
-        scat_step4(st, g, pv, av, bv);
-        *(f32x4*)(st.p + o) = pv; *(f32x4*)(st.s0 + o) = av;
-        if (st.s1) *(f32x4*)(st.s1 + o) = bv;
-    }
-    if (tid < 16 && n0 + tid < N) {
-        const float g = (dbp[0][tid] + dbp[1][tid]) + (dbp[2][tid] + dbp[3][tid]);
-        float pe = bp[n0 + tid], ae = bs0[n0 + tid], be = bs1 ? bs1[n0 + tid] : 0.0f;
-        scat_step1(st, g, pe, ae, be);
-        bp[n0 + tid] = pe; bs0[n0 + tid] = ae;
-        if (bs1) bs1[n0 + tid] = be;
-    }
-}
-
-// W: W_out^T [N][Hp] with its state arrays (s1 NULL: one state array), b: b_out [N] likewise; false: shape not served
-bool launch_out_grad_step(hipStream_t s, const float* dlogits, const float* h_last, const float* rowcost, float* cost, int updater,
-                          float* W, float* Ws0, float* Ws1, float* b, float* bs0, float* bs1, int R, int N, int Nl, int Hp, float lr,
-                          float rho, float b1, float b2, long t, hipError_t* err) {
-    if (!(Hp == 32 || Hp == 64 || Hp == 128) || R < 1 || N < 1) return false;
-    SbrScatStep st; st.p = W; st.s0 = Ws0; st.s1 = Ws1; st.last = nullptr; st.updater = updater; st.t_to = (int)t;
-    st.lr = lr; st.rho = rho; st.b1 = b1; st.b2 = b2; st.a_t = 0.0f;
-    if (updater == SBR_UPD_ADAM)
-        st.a_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
-    const int grid = (N + 15) / 16;
-    if (Hp == 128) out_grad_step_kernel<128><<<grid, 256, 0, s>>>(dlogits, h_last, rowcost, cost, st, b, bs0, bs1, R, N, Nl);
-    else if (Hp == 64) out_grad_step_kernel<64><<<grid, 256, 0, s>>>(dlogits, h_last, rowcost, cost, st, b, bs0, bs1, R, N, Nl);
-    else out_grad_step_kernel<32><<<grid, 256, 0, s>>>(dlogits, h_last, rowcost, cost, st, b, bs0, bs1, R, N, Nl);
-    *err = hipGetLastError();
-    return true;
-}
-
-hipError_t launch_update(hipStream_t s, int updater, float* p, float* g, float* s0, float* s1, size_t n, float lr,
-                         float rho, float b1, float b2, long t, size_t gap_at, size_t gap_len) {
-    if (n == 0) return hipSuccess;
-    float a_t = 0.0f;
-    if (updater == SBR_UPD_ADAM)
-        a_t = (float)((double)lr * sqrt(1.0 - pow((double)b2, (double)t)) / (1.0 - pow((double)b1, (double)t)));
-    const int grid = (int)min((size_t)256 * 16, (n + 255) / 256);
-    update_kernel<<<grid, 256, 0, s>>>(updater, p, g, s0, s1, n, lr, rho, b1, b2, a_t, gap_at, gap_len);
     return hipGetLastError();
 }
 

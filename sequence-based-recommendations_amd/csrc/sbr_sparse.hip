@@ -5,7 +5,7 @@
 // [N][H] + b_out) per step -- 3.6 GB (C3) to 72 GB (C5) of HBM traffic for rows whose gradient is exactly zero:
 // only the rows the batch gathers (sparse_lstm.py:368) and the sampled cells (sparse_lstm.py:50-54) receive one.
 //
-// What a step does to a row with zero gradient, per updater (same formulas as update_kernel in sbr_misc.hip):
+// What a step does to a row with zero gradient, per updater (upd_step in sbr_upd.h with g = 0):
 //   adagrad   nothing (acc += 0, p -= lr * 0 / sqrt(acc + eps))                         -> skipping is EXACT
 //   rmsprop   acc *= rho                                                                -> k skipped steps: acc *= rho^k
 //   adadelta  acc *= rho, delta *= rho, p unchanged                                     -> both *= rho^k
@@ -24,24 +24,15 @@
 #include "sbr_common.h"
 #include <algorithm>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct SpUpd {
-    int updater;
-    float lr, rho, b1, b2;
-    const float* at;     // adam: a_t = lr * sqrt(1 - b2^t) / (1 - b1^t) for t = 1..n_at (host double -> float, as the dense launch computes it)
-    int n_at;            // beyond the table a_t == (float)lr
-    int early_exit;      // adam: a missed step's update shrinks monotonically (checked on the host from b1, b2 and the table)
-};
-
-__device__ __forceinline__ float sp_at(const SpUpd& u, long t) { return t <= (long)u.n_at ? u.at[t - 1] : u.lr; }
+__device__ __forceinline__ float sp_at(const SbrSparseUpd& u, long t) { return t <= (long)u.n_at ? u.at[t - 1] : u.rule.lr; }
 
 // k zero-gradient steps t0+1 .. t0+k on the NE elements a lane holds of one row.  The elements advance together, step by
 // step, so that their dependent chains (mul, sqrt, div, sub per step) interleave: one element at a time the replay is
 // latency-bound (measured 264 us for C3's batch rows with gaps <= 25; the loop below issues NE independent chains).
 template <int NE>
-__device__ __forceinline__ void sp_catch_up(const SpUpd& u, float (&p)[NE], float (&s0)[NE], float (&s1)[NE], int k, long t0) {
+__device__ __forceinline__ void sp_catch_up(const SbrSparseUpd& c, float (&p)[NE], float (&s0)[NE], float (&s1)[NE], int k, long t0) {
     if (k <= 0) return;
+    const SbrUpdRule& u = c.rule;
     switch (u.updater) {
         case SBR_UPD_ADAGRAD: return;
         case SBR_UPD_RMSPROP:
@@ -73,7 +64,7 @@ __device__ __forceinline__ void sp_catch_up(const SpUpd& u, float (&p)[NE], floa
             const float rb2 = sqrtf(u.b2);
             int j = 0;
             for (; j < k; ++j) {
-                const float a_t = sp_at(u, t0 + 1 + j);
+                const float a_t = sp_at(c, t0 + 1 + j);
                 bool live = false;
 #pragma unroll
                 for (int e = 0; e < NE; ++e) {
@@ -81,7 +72,7 @@ __device__ __forceinline__ void sp_catch_up(const SpUpd& u, float (&p)[NE], floa
                     rt[e] *= rb2;
                     const float upd = a_t * m * __builtin_amdgcn_rcpf(rt[e] + 1e-8f);
                     s0[e] = m; p[e] -= upd;
-                    live = live || !(m == 0.0f || (u.early_exit && fabsf(upd) < fabsf(p[e]) * 1.4901161e-8f));   // 2^-26 |p|
+                    live = live || !(m == 0.0f || (c.early_exit && fabsf(upd) < fabsf(p[e]) * 1.4901161e-8f));   // 2^-26 |p|
                 }
                 if (!live || j >= 8190) { ++j; break; }
             }
@@ -94,25 +85,6 @@ __device__ __forceinline__ void sp_catch_up(const SpUpd& u, float (&p)[NE], floa
                 for (int e = 0; e < NE; ++e) s0[e] *= f1;
             }
             return;
-        }
-    }
-}
-
-// one real step (gradient g) -- the dense update_kernel's arithmetic
-__device__ __forceinline__ void sp_step(const SpUpd& u, float& p, float g, float& s0, float& s1, float a_t) {
-    switch (u.updater) {
-        case SBR_UPD_ADAGRAD: { const float acc = s0 + g * g; s0 = acc; p -= u.lr * g / sqrtf(acc + 1e-6f); return; }
-        case SBR_UPD_RMSPROP: { const float acc = u.rho * s0 + (1.0f - u.rho) * g * g; s0 = acc; p -= u.lr * g / sqrtf(acc + 1e-6f); return; }
-        case SBR_UPD_ADADELTA: {
-            const float acc = u.rho * s0 + (1.0f - u.rho) * g * g;
-            const float upd = g * sqrtf(s1 + 1e-6f) / sqrtf(acc + 1e-6f);
-            s0 = acc; p -= u.lr * upd; s1 = u.rho * s1 + (1.0f - u.rho) * upd * upd; return;
-        }
-        case SBR_UPD_NESTEROV: { const float v = u.rho * s0 - u.lr * g; s0 = v; p += u.rho * v - u.lr * g; return; }
-        default: {
-            const float m = u.b1 * s0 + (1.0f - u.b1) * g;
-            const float v = u.b2 * s1 + (1.0f - u.b2) * g * g;
-            s0 = m; s1 = v; p -= a_t * m / (sqrtf(v) + 1e-8f); return;
         }
     }
 }
@@ -133,14 +105,15 @@ __device__ __forceinline__ void sp_step(const SpUpd& u, float& p, float g, float
 #endif
 #define SP_NV 2
 template <int SRC, bool STEP>
-__global__ void __launch_bounds__(256) sp_rows_kernel(SbrSparseRows r, SpUpd u, const int* __restrict__ X, const int* __restrict__ len,
+__global__ void __launch_bounds__(256) sp_rows_kernel(SbrSparseRows r, SbrSparseUpd u, const int* __restrict__ X, const int* __restrict__ len,
                                                       int T, int Bp, int F, const int* __restrict__ list, const int* __restrict__ n_list,
                                                       int n_host, int t_to) {
     const int lane = threadIdx.x & 63;
     const int wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const int nwaves = gridDim.x * (blockDim.x >> 6);
     const int total = SRC == 0 ? Bp * T * F : SRC == 1 ? (n_list ? *n_list : n_host) : r.n_rows;
-    const float a_t = STEP ? sp_at(u, t_to) : 0.0f;
+    SbrUpdRule st = u.rule;
+    st.a_t = STEP ? sp_at(u, t_to) : 0.0f;              // this step's own, from the table
     for (int base = wave * SP_CPW; base < total; base += nwaves * SP_CPW) {
         const int i = base + lane;
         int id = -1;
@@ -167,7 +140,7 @@ __global__ void __launch_bounds__(256) sp_rows_kernel(SbrSparseRows r, SpUpd u, 
             owners &= owners - 1;
             const int rid = __shfl(id, src), rold = __shfl(old, src);
             const int k = (STEP ? t_to - 1 : t_to) - rold;            // zero-gradient steps rold+1 .. rold+k
-            if (!STEP && (k <= 0 || u.updater == SBR_UPD_ADAGRAD)) continue;
+            if (!STEP && (k <= 0 || st.updater == SBR_UPD_ADAGRAD)) continue;
             for (int pr = 0; pr < r.npairs; ++pr) {
                 const size_t ro = r.off[pr] + (size_t)rid * r.stride[pr];
                 const int w = r.width[pr];
@@ -194,7 +167,7 @@ __global__ void __launch_bounds__(256) sp_rows_kernel(SbrSparseRows r, SpUpd u, 
                             for (int v = 0; v < SP_NV; ++v)
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) {
-                                    if (STEP) sp_step(u, pe[4 * v + e], g[v][e], ae[4 * v + e], be[4 * v + e], a_t);
+                                    if (STEP) upd_step(st, g[v][e], pe[4 * v + e], ae[4 * v + e], be[4 * v + e]);
                                     p[v][e] = pe[4 * v + e]; s0[v][e] = ae[4 * v + e]; s1[v][e] = be[4 * v + e];
                                 }
                         }
@@ -212,7 +185,7 @@ __global__ void __launch_bounds__(256) sp_rows_kernel(SbrSparseRows r, SpUpd u, 
                     const size_t o = ro + lane;
                     float pe[1] = {r.p[o]}, a[1] = {r.s0[o]}, b[1] = {r.s1 ? r.s1[o] : 0.0f};
                     sp_catch_up<1>(u, pe, a, b, k, (long)rold);
-                    if (STEP) { const float gg = r.g[o]; r.g[o] = 0.0f; sp_step(u, pe[0], gg, a[0], b[0], a_t); }
+                    if (STEP) { const float gg = r.g[o]; r.g[o] = 0.0f; upd_step(st, gg, pe[0], a[0], b[0]); }
                     r.p[o] = pe[0]; r.s0[o] = a[0]; if (r.s1) r.s1[o] = b[0];
                 }
             }
@@ -220,31 +193,26 @@ __global__ void __launch_bounds__(256) sp_rows_kernel(SbrSparseRows r, SpUpd u, 
     }
 }
 
-static SpUpd make_upd(const SbrSparseUpd& c) {
-    SpUpd u; u.updater = c.updater; u.lr = c.lr; u.rho = c.rho; u.b1 = c.b1; u.b2 = c.b2; u.at = c.at; u.n_at = c.n_at;
-    u.early_exit = c.early_exit;
-    return u;
-}
 // one wave per SP_CPW candidates (4 waves per workgroup), at most 16 k workgroups (grid-stride beyond)
 static inline int sp_grid(long total) { return (int)std::max<long>(1, std::min<long>(16384, (total + 4 * SP_CPW - 1) / (4 * SP_CPW))); }
 
 hipError_t launch_sparse_catch_up_batch(hipStream_t s, const SbrSparseRows& r, const SbrSparseUpd& c, const int* X, const int* len, int T,
                                         int Bp, int F, int t_to) {
-    sp_rows_kernel<0, false><<<sp_grid((long)Bp * T * F), 256, 0, s>>>(r, make_upd(c), X, len, T, Bp, F, nullptr, nullptr, 0, t_to);
+    sp_rows_kernel<0, false><<<sp_grid((long)Bp * T * F), 256, 0, s>>>(r, c, X, len, T, Bp, F, nullptr, nullptr, 0, t_to);
     return hipGetLastError();
 }
 hipError_t launch_sparse_catch_up_list(hipStream_t s, const SbrSparseRows& r, const SbrSparseUpd& c, const int* list, const int* n_dev,
                                        int n_host, int n_max, int t_to) {
-    sp_rows_kernel<1, false><<<sp_grid(n_max), 256, 0, s>>>(r, make_upd(c), nullptr, nullptr, 0, 0, 0, list, n_dev, n_host, t_to);
+    sp_rows_kernel<1, false><<<sp_grid(n_max), 256, 0, s>>>(r, c, nullptr, nullptr, 0, 0, 0, list, n_dev, n_host, t_to);
     return hipGetLastError();
 }
 hipError_t launch_sparse_flush(hipStream_t s, const SbrSparseRows& r, const SbrSparseUpd& c, int t_to) {
-    sp_rows_kernel<2, false><<<sp_grid(r.n_rows), 256, 0, s>>>(r, make_upd(c), nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, t_to);
+    sp_rows_kernel<2, false><<<sp_grid(r.n_rows), 256, 0, s>>>(r, c, nullptr, nullptr, 0, 0, 0, nullptr, nullptr, 0, t_to);
     return hipGetLastError();
 }
 hipError_t launch_sparse_step_list(hipStream_t s, const SbrSparseRows& r, const SbrSparseUpd& c, const int* list, const int* n_dev,
                                    int n_host, int n_max, int t_to) {
-    sp_rows_kernel<1, true><<<sp_grid(n_max), 256, 0, s>>>(r, make_upd(c), nullptr, nullptr, 0, 0, 0, list, n_dev, n_host, t_to);
+    sp_rows_kernel<1, true><<<sp_grid(n_max), 256, 0, s>>>(r, c, nullptr, nullptr, 0, 0, 0, list, n_dev, n_host, t_to);
     return hipGetLastError();
 }
 

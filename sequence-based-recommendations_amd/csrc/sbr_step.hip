@@ -201,32 +201,27 @@ static inline hipEvent_t record_shared(sbr_handle* h, hipEvent_t plain, int mk) 
 // ---------------------------------------------------------------------------------------
 static inline long step_no(const sbr_handle* h) { return (long)h->step_count + 1; }
 static inline float* state1(const sbr_handle* h, size_t off) { return h->lay.n_state_arrays > 1 ? h->St(1, off) : nullptr; }
+static inline SbrUpdRule upd_rule(const sbr_handle* h) { return sbr_upd_rule(h->lay.cfg, step_no(h)); }
 // floats [lo, hi) of the parameter section, without the gap_len floats that follow the first gap_at of them (two ranges, one launch)
 static hipError_t step_range(sbr_handle* h, hipStream_t st, size_t lo, size_t hi, size_t gap_at = (size_t)-1, size_t gap_len = 0) {
-    const Layout& y = h->lay;
     if (hi <= lo) return hipSuccess;
-    return launch_update(st, y.cfg.updater, h->P(lo), h->Gd(lo), h->St(0, lo), state1(h, lo), hi - lo - gap_len,
-                         y.cfg.learning_rate, y.cfg.rho, y.cfg.beta1, y.cfg.beta2, step_no(h), gap_at, gap_len);
+    return launch_update(st, upd_rule(h), h->P(lo), h->Gd(lo), h->St(0, lo), state1(h, lo), hi - lo - gap_len, gap_at, gap_len);
 }
 // ... n floats at lo whose gradient is still n_slabs split-K slabs in ws: reduction + step in one launch
 static hipError_t step_from_slabs(sbr_handle* h, hipStream_t st, const float* ws, int n_slabs, size_t lo, size_t n) {
-    const Layout& y = h->lay;
-    return launch_update_from_slabs(st, y.cfg.updater, ws, n_slabs, h->P(lo), h->St(0, lo), state1(h, lo), n,
-                                    y.cfg.learning_rate, y.cfg.rho, y.cfg.beta1, y.cfg.beta2, step_no(h));
+    return launch_update_from_slabs(st, upd_rule(h), ws, n_slabs, h->P(lo), h->St(0, lo), state1(h, lo), n);
 }
 // ... layer 0's index-input block, reading / clearing the gradient of the rows this batch touched only (the plain-key sort's offsets)
 static hipError_t step_rows_aware(sbr_handle* h, hipStream_t st) {
     const Layout& y = h->lay; const size_t lo = y.layer[0].p_Win;
-    return launch_update_rows_aware(st, y.cfg.updater, h->P(lo), h->Gd(lo), h->St(0, lo), state1(h, lo), y.cfg.input_size,
-                                    y.G * y.layer[0].Hp, sort_keys(h, 0).off, y.cfg.learning_rate, y.cfg.rho, y.cfg.beta1,
-                                    y.cfg.beta2, step_no(h));
+    return launch_update_rows_aware(st, upd_rule(h), h->P(lo), h->Gd(lo), h->St(0, lo), state1(h, lo), y.cfg.input_size,
+                                    y.G * y.layer[0].Hp, sort_keys(h, 0).off);
 }
 // ... the dense head: its gradient from dlogits, its step and the batch cost in one launch; false: shape not served
 static bool step_out_grad(sbr_handle* h, hipStream_t st, const float* lg, const float* hl, int R, int Nl, hipError_t* err) {
     const Layout& y = h->lay;
-    return launch_out_grad_step(st, lg, hl, h->A(y.a_rowcost), h->cost_ptr(), y.cfg.updater, h->P(y.p_WoutT), h->St(0, y.p_WoutT),
-                                state1(h, y.p_WoutT), h->P(y.p_bout), h->St(0, y.p_bout), state1(h, y.p_bout),
-                                R, y.N, Nl, y.HLt, y.cfg.learning_rate, y.cfg.rho, y.cfg.beta1, y.cfg.beta2, step_no(h), err);
+    return launch_out_grad_step(st, upd_rule(h), lg, hl, h->A(y.a_rowcost), h->cost_ptr(), h->P(y.p_WoutT), h->St(0, y.p_WoutT),
+                                state1(h, y.p_WoutT), h->P(y.p_bout), h->St(0, y.p_bout), state1(h, y.p_bout), R, y.N, Nl, y.HLt, err);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -242,8 +237,7 @@ SbrSparseRows sparse_rows(sbr_handle* h, int b) {
     return r;
 }
 SbrSparseUpd sparse_upd(sbr_handle* h) {
-    const sbr_config& c = h->lay.cfg;
-    SbrSparseUpd u; u.updater = c.updater; u.lr = c.learning_rate; u.rho = c.rho; u.b1 = c.beta1; u.b2 = c.beta2;
+    SbrSparseUpd u; u.rule = upd_rule(h);
     u.at = h->lay.n_at ? h->A(h->lay.a_at) : nullptr; u.n_at = h->lay.n_at; u.early_exit = h->lay.adam_early_exit;
     return u;
 }
@@ -619,7 +613,7 @@ static int dense_head_grads(sbr_handle* h) {
     float* lg = h->A(y.a_logits);
     float* hl = h_last(h);
     // Single-call step without a bias regulariser: the output layer's gradient, its step and the batch cost in ONE launch
-    // (launch_out_grad_step, sbr_misc.hip) instead of the five or six below -- the polling weight-gradient GEMM of the overlapped
+    // (launch_out_grad_step, sbr_update.hip) instead of the five or six below -- the polling weight-gradient GEMM of the overlapped
     // tail, next on this stream, then starts with the chain instead of 68 us into it.  SBR_OUT_FUSE=0: as before.
     h->out_stepped = false;
     // (taken WITHOUT the overlapped tail only: in front of the polling GEMM of C2 it measured 0.3334 against 0.3294 ms -- that GEMM

@@ -93,13 +93,35 @@ def margin_oracle_batch(batch, N, balance=1.0, unique=True, default_target=None)
 
 
 def engine_for(cfg, N, B, T, S=0, F=1, n_opt=0, updater="adam", lr=0.01, flags=0, reg=0.0, local_batch=None,
-               row_offset=0, balance=1.0, unique=True):
+               row_offset=0, balance=1.0, unique=True, rho=0.9, beta1=0.9, beta2=0.999):
     from sbr_amd.engine import RNNEngine
     return RNNEngine(cell=cfg["cell"], layers=cfg["layers"], n_items=N, max_length=T, batch_size=B, loss=cfg["loss"],
-                     n_samples=S, updater=updater, learning_rate=lr, rho=0.9, beta1=0.9, beta2=0.999,
+                     n_samples=S, updater=updater, learning_rate=lr, rho=rho, beta1=beta1, beta2=beta2,
                      regularization=reg, input_size=N + n_opt, n_feat=F, flags=flags, local_batch=local_batch,
                      row_offset=row_offset, embedding_size=cfg.get("embedding", 0), bidirectional=cfg.get("bidirectional", False),
                      balance=balance, n_targets=max(S, 1), unique=unique)
+
+
+def injected_gradients(n, steps, seed=17):
+    """a flat gradient per step: magnitudes in [0.1, 1], random signs"""
+    rng = np.random.default_rng(seed)
+    return [(rng.uniform(0.1, 1.0, size=n) * rng.choice([-1.0, 1.0], size=n)).astype(np.float32) for _ in range(steps)]
+
+
+def inject_and_step(eng, grads, with_batch=False):
+    """per gradient: sbr_zero_grads, the gradient copied into the gradient section (sbr_section), sbr_apply_update -- the optimizer
+    kernels on their own, on the engine's stream.  with_batch: the phase calls of the batch that is set run in front of the copy and
+    the side streams are joined (the row steps of row-sparse blocks take their ids from the batch's sort); their gradient is
+    overwritten"""
+    import torch
+    sec = eng.section("grads")[0]
+    for g in grads:
+        eng.zero_grads()
+        if with_batch:
+            eng.forward(); eng.loss_backward_output(); eng.backward_recurrent(); eng.join_side()
+        sec[:g.size].copy_(torch.from_numpy(g))
+        eng.apply_update()
+    eng.synchronize()
 
 
 def oracle_batch(batch):
@@ -125,7 +147,8 @@ def params_ok(r, steps=2, bar=1e-3, tol_g=1e-4):
 
 def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater="adam", flags=0, full=False,
                  reg=0.0, steps=2, popscale=1.0, scale=None, emb=0, bi=False, zipf=False, k=None, gap=0.0, tweak=None,
-                 balance=1.0, unique=True, default_target=None, grad_floor=1e-12, queries=(), queries_after=()):
+                 balance=1.0, unique=True, default_target=None, grad_floor=1e-12, queries=(), queries_after=(), lr=0.01, rho=0.9,
+                 beta1=0.9, beta2=0.999):
     """Returns dict of relative errors (engine float32 vs oracle float64).
     grad_floor: added to the largest oracle magnitude of a gradient array before dividing -- arrays far smaller than it are
     compared absolutely (the fp16 split of the BPTT chain's gradient operand has an absolute floor, csrc/sbr_rec_p.hip).
@@ -139,7 +162,8 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
         tweak(batch)
     cfg["regularization"] = reg
     margin = loss in O.MARGIN_LOSSES
-    eng = engine_for(cfg, N, B, T, S=S, F=F, n_opt=n_opt, updater=updater, flags=flags, reg=reg, balance=balance, unique=unique)
+    eng = engine_for(cfg, N, B, T, S=S, F=F, n_opt=n_opt, updater=updater, flags=flags, reg=reg, balance=balance, unique=unique,
+                     lr=lr, rho=rho, beta1=beta1, beta2=beta2)
     obatch = margin_oracle_batch(batch, N, balance, unique, default_target) if margin else oracle_batch(batch)
     out = {}
     try:
@@ -173,7 +197,7 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
             worst = max(worst, e)
         out["grad_worst"] = worst
         # a few optimizer steps on the same batch
-        upd = O.Updater(updater, 0.01, rho=0.9, beta1=0.9, beta2=0.999)
+        upd = O.Updater(updater, lr, rho=rho, beta1=beta1, beta2=beta2)
         oparams = [p.copy() for p in params]
         costs_e, costs_o = [], []
         # ... and the oracle's updater once more as a "twin" that is fed the ENGINE's gradients step by step: Adam turns a gradient
@@ -182,7 +206,7 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
         # the optimizer kernel.  The twin separates the two: `params_twin` = the optimizer kernel alone (same gradients in, same
         # parameters out), `grad_worst_steps` = every step's gradients against the oracle's AT THE SAME parameters,
         # `params_twin_vs_oracle` = what the oracle's own updater makes of the gradient difference (no engine code involved).
-        upd_t = O.Updater(updater, 0.01, rho=0.9, beta1=0.9, beta2=0.999)
+        upd_t = O.Updater(updater, lr, rho=rho, beta1=beta1, beta2=beta2)
         tparams = [p.astype(np.float64) for p in params]
         gsteps = 0.0
         for _ in range(steps):

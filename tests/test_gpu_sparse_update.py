@@ -17,9 +17,9 @@ UPDATERS = ["adagrad", "adadelta", "rmsprop", "nesterov", "adam"]
 
 
 def run_sequence(cell, layers, loss, N, B, T, S, updater, plan, flags, emb=0, bi=False, F=1, n_opt=0, seed=0, oracle=True,
-                 probe_at=None, want_sections=False):
+                 probe_at=None, want_sections=False, hyp=(0.01, 0.9, 0.9, 0.999)):
     """plan: list of batch seeds, one per step (equal seeds = the same batch again).  Returns engine costs / params /
-    probe scores (+ the oracle's)."""
+    probe scores (+ the oracle's).  hyp: learning rate, rho, beta1, beta2."""
     params, cfg, _ = PU.build_case(cell, layers, loss, N, B, T, S=S, seed=seed, F=F, n_opt=n_opt, emb=emb, bi=bi)
     batches = {}
     for sd in set(plan):
@@ -34,7 +34,8 @@ def run_sequence(cell, layers, loss, N, B, T, S, updater, plan, flags, emb=0, bi
             bt["target"] = (bt["target"] % (N // 2)).astype(np.int32)
             bt["samples"] = (bt["samples"] % (N // 2)).astype(np.int32)
         batches[sd] = bt
-    eng = PU.engine_for(cfg, N, B, T, S=S, F=F, n_opt=n_opt, updater=updater, flags=flags)
+    lr, rho, b1, b2 = hyp
+    eng = PU.engine_for(cfg, N, B, T, S=S, F=F, n_opt=n_opt, updater=updater, flags=flags, lr=lr, rho=rho, beta1=b1, beta2=b2)
     out = {}
     try:
         out["sparse_blocks"] = eng.query("sparse_blocks")
@@ -54,7 +55,7 @@ def run_sequence(cell, layers, loss, N, B, T, S, updater, plan, flags, emb=0, bi
     finally:
         eng.close()
     if oracle:
-        upd = O.Updater(updater, 0.01, rho=0.9, beta1=0.9, beta2=0.999)
+        upd = O.Updater(updater, lr, rho=rho, beta1=b1, beta2=b2)
         op = [p.copy() for p in params]
         ocosts, oprobe = [], None
         for i, sd in enumerate(plan):

@@ -26,14 +26,18 @@ QUERIES = ("scatter_form", "step_join_gate", "step_fork_gate", "tail_gate_first"
            "fused_gather", "cluster", "rec_rows_fwd", "rec_rows_bwd", "rec_workgroups_fwd", "rec_workgroups_bwd", "rec_products_fwd",
            "rec_products_bwd")
 STEPS = 3
-FLAGS = dict(SIMPLE_REC=1, SIMPLE_GEMM=2, ATOMIC_SCATTER=4, PROFILE_REC=8, F32_MFMA=16, SPARSE_UPDATE=32, BF16_PROJECTION=128, BF16_LAYERS=256)
+DEFAULT_HYP, OTHER_HYP = (0.01, 0.9, 0.9, 0.999), (0.05, 0.8, 0.7, 0.95)      # lr, rho, beta1, beta2
+UPDATERS = ("adagrad", "adadelta", "rmsprop", "nesterov", "adam")
+FLAGS = dict(SIMPLE_REC=1, SIMPLE_GEMM=2, ATOMIC_SCATTER=4, PROFILE_REC=8, F32_MFMA=16, SPARSE_UPDATE=32, DENSE_UPDATE=64, BF16_PROJECTION=128, BF16_LAYERS=256)
 
 
 def case(name, family, cell, layers, loss, N, B, T, S=0, env=None, flags=0, updater="adam", reg=0.0, emb=0, bi=False, zipf=False,
-         scale=None, phases=None, seed=7, subset=False):
-    """phases: None = sbr_train_step; "join" / "deferred" = the five phase calls, without / with sbr_set_deferred_join"""
+         scale=None, phases=None, seed=7, subset=False, hyp=DEFAULT_HYP):
+    """phases: None = sbr_train_step; "join" / "deferred" = the five phase calls, without / with sbr_set_deferred_join; "inject" = the
+    optimizer alone: sbr_zero_grads, a fixed gradient copied into the gradient section, sbr_apply_update (behind the phase calls of
+    the batch where the engine has row-sparse blocks: their row steps take the ids of the batch's sort).  hyp: lr, rho, beta1, beta2"""
     return dict(name=name, family=family, cell=cell, layers=layers, loss=loss, N=N, B=B, T=T, S=S, env=env or {}, flags=flags,
-                updater=updater, reg=reg, emb=emb, bi=bi, zipf=zipf, scale=scale, phases=phases, seed=seed, subset=subset)
+                updater=updater, reg=reg, emb=emb, bi=bi, zipf=zipf, scale=scale, phases=phases, seed=seed, subset=subset, hyp=hyp)
 
 
 def cases():
@@ -50,6 +54,10 @@ def cases():
                 out.append(case("tail-%s-B%d-%s" % (cell, B, sw), "tail", env={key: val}, subset=(cell == "GRU" and B == 64 and key == "SBR_BWD_CHUNKS"), **k))
             for ph in ("join", "deferred"):
                 out.append(case("tail-%s-B%d-phases-%s" % (cell, B, ph), "phases", phases=ph, subset=(cell == "GRU" and B == 64), **k))
+    for upd in ("adadelta", "nesterov"):      # update_from_slabs_kernel with two and with one state array; without the tail: out_grad_step_kernel
+        k = dict(cell="GRU", layers=[128], loss="CCE", N=300, B=64, T=70, scale=0.1, zipf=True, updater=upd, hyp=OTHER_HYP)
+        out.append(case("tail-GRU-B64-%s" % upd, "tail", **k))
+        out.append(case("tail-GRU-B64-overlap0-%s" % upd, "tail", env={"SBR_TAIL_OVERLAP": "0"}, **k))
     # small layers: the barrier kernels, every head
     for cell in ("GRU", "LSTM", "Vanilla"):
         for H in (16, 12):
@@ -88,6 +96,17 @@ def cases():
         for ra in ("1", "0"):
             out.append(case("scatter-form%d-rowaware%s" % (form, ra), "scatter", cell="LSTM", layers=[256], loss="CCE", N=3000, B=64, T=24,
                             zipf=True, scale=0.03, seed=61, env=dict(env, SBR_ROW_AWARE_UPDATE=ra), flags=fl, subset=(ra == "1")))
+    for upd in ("adadelta", "nesterov"):      # update_rows_aware_kernel likewise (dense by flag: 1536 entries cannot touch 3000 rows)
+        out.append(case("scatter-form1-dense-%s" % upd, "scatter", cell="LSTM", layers=[256], loss="CCE", N=3000, B=64, T=24, zipf=True,
+                        scale=0.03, seed=61, updater=upd, hyp=OTHER_HYP, flags=FLAGS["DENSE_UPDATE"]))
+    # the optimizer alone on an injected gradient (tests/test_gpu_update_rule.py): update_kernel, and with forced row-sparse blocks
+    # sp_rows_kernel behind it.  No float atomics reach the result: these digests reproduce
+    for upd in UPDATERS:
+        for hn, hyp in (("default", DEFAULT_HYP), ("other", OTHER_HYP)):
+            out.append(case("update-%s-%s" % (upd, hn), "update", cell="GRU", layers=[8], loss="CCE", N=19, B=4, T=5, updater=upd, hyp=hyp,
+                            phases="inject", subset=(upd == "adam")))
+            out.append(case("update-sparse-%s-%s" % (upd, hn), "update", cell="GRU", layers=[16], loss="CCE", N=41, B=16, T=12, updater=upd,
+                            hyp=hyp, phases="inject", flags=FLAGS["SPARSE_UPDATE"]))
     # flags
     for nm, fl in (("triage", FLAGS["SIMPLE_REC"] | FLAGS["SIMPLE_GEMM"]), ("f32mfma", FLAGS["F32_MFMA"]), ("bf16proj", FLAGS["BF16_PROJECTION"]),
                    ("bf16layers", FLAGS["BF16_LAYERS"])):
@@ -121,7 +140,8 @@ def run_case(c, dump):
         params, cfg, batch = PU.build_case(c["cell"], c["layers"], c["loss"], c["N"], c["B"], c["T"], S=c["S"], seed=c["seed"],
                                            scale=c["scale"], emb=c["emb"], bi=c["bi"], zipf=c["zipf"])
         cfg["regularization"] = c["reg"]
-        eng = PU.engine_for(cfg, c["N"], c["B"], c["T"], S=c["S"], updater=c["updater"], flags=c["flags"], reg=c["reg"])
+        eng = PU.engine_for(cfg, c["N"], c["B"], c["T"], S=c["S"], updater=c["updater"], flags=c["flags"], reg=c["reg"],
+                            lr=c["hyp"][0], rho=c["hyp"][1], beta1=c["hyp"][2], beta2=c["hyp"][3])
     finally:
         for k, v in saved.items():
             if v is None:
@@ -139,9 +159,13 @@ def run_case(c, dump):
         if c["phases"] == "deferred":
             eng.set_deferred_join(True)
         costs = []
-        for _ in range(STEPS):
+        inject = PU.injected_gradients(eng.section("params")[0].numel(), STEPS) if c["phases"] == "inject" else None
+        for i in range(STEPS):
             if c["phases"] is None:
                 costs.append(eng.train_step(sync=True))
+            elif inject:
+                PU.inject_and_step(eng, inject[i:i + 1], with_batch=bool(c["flags"] & FLAGS["SPARSE_UPDATE"]))
+                costs.append(0.0)
             else:
                 eng.zero_grads(); eng.forward(); eng.loss_backward_output(); eng.backward_recurrent(); eng.apply_update()
                 costs.append(eng.read_cost())
