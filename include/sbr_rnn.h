@@ -559,6 +559,29 @@ int sbr_cluster_evaluate(sbr_cluster* c, sbr_handle* h, sbr_dataset* d, const in
                          int32_t* size_host,           /* NULL or [n]: len(members(c)) (LISTS road) */
                          int32_t* cluster_use_host);   /* NULL or [C]: users per selected cluster */
 
+/* ------------------------------------------------------------------------------------------------
+ * One training iteration of a cluster model on a device-built batch (added under ABI 11: two symbols, no struct change) -- what
+ * RNNCluster.train_function does per batch (rnn_cluster.py:277-287, :354-407), without a host copy and without a wait:
+ *   1. sbr_train_step_lagged(h, prev_cost, have_prev): the network steps on the engine's current batch; its cost comes back one call
+ *      late through the same slots, sbr_lagged_flush serves it;
+ *   2. sbr_cluster_forward_backward on the user representation of that step's forward, with the B targets of that batch (the
+ *      engine's own device buffer) and
+ *        n_cluster_samples == 0   the S negatives of that batch (`cluster_samples = samples`, rnn_cluster.py:384, :392),
+ *        n_cluster_samples  > 0   that many ids drawn on the device by d's law -- uniform, or the inverse of d's CDF table
+ *                                 (sbr_dataset_set_tables) -- from `seed`: a draw of its own, independent of the batch's negatives.
+ *      One launch writes targets ++ cluster samples into the head's id list, drawing where asked;
+ *   3. sbr_cluster_apply_update(c).
+ * Everything is enqueued on the engine's stream behind the step; nothing is synchronised.  SBR_ESTATE: no batch set.  SBR_EINVAL,
+ * found before anything is launched (parameters, gradients and state of engine and head stay untouched): c against h as for
+ * sbr_cluster_rank (items, width and split, stream), d against h (items, stream), a head whose batch_size is not the engine's, an
+ * engine whose loss is not a sampled one, local_batch != batch_size or a batch of fewer rows (the head is single-rank and reads
+ * every row), n_cluster_samples outside [0, max_samples], n_cluster_samples == 0 with S > max_samples. */
+int sbr_cluster_train_step_lagged(sbr_cluster* c, sbr_handle* h, sbr_dataset* d, int n_cluster_samples, uint64_t seed,
+                                  float* prev_cost, int* have_prev);
+/* The id list of the head's last forward/backward (tests and tooling): targets ++ cluster samples, J = B + samples entries.
+ * ids_host [n], n == J.  Synchronises the stream.  SBR_ESTATE: no forward/backward yet. */
+int sbr_cluster_last_ids(sbr_cluster* c, int32_t* ids_host, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -266,6 +266,18 @@ __device__ __forceinline__ int bb_target_pos(unsigned long long seed, int g, int
     return chosen[(j + (int)(r2 % (unsigned long long)k)) % k];
 }
 
+// Draw `si` of a sample set seeded by `seed`: uniform over the items, or the inverse of the CDF table.  The batch's negatives
+// (bb_pack_kernel) and the cluster head's own samples (bb_cluster_ids_kernel) follow this one law.
+__device__ __forceinline__ int bb_draw_item(unsigned long long seed, int si, const double* __restrict__ cdf, int n_items) {
+    const unsigned long long r = mix64(seed ^ mix64(0xA5A5ull + (unsigned long long)si));
+    if (!cdf) return (int)(r % (unsigned long long)n_items);      // np.random.choice(n_items, S) (rnn_sampling.py:191)
+    // bisect(cumsum, uniform(0, cumsum[-1])) (:159-163)
+    const double x = (double)(r >> 11) * (1.0 / 9007199254740992.0) * cdf[n_items - 1];
+    int lo = 0, hi = n_items;                                     // first index with cdf[idx] > x
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] > x) hi = mid; else lo = mid + 1; }
+    return min(lo, n_items - 1);
+}
+
 // One wave per local row: X row (item id, + n_items + rating index with F == 2), length, pop**db of the first target.  Blocks
 // past the rows write the targets (NT per row, -1 behind the last) and draw the S negatives.
 __global__ void __launch_bounds__(64) bb_pack_kernel(const int* __restrict__ items, const int* __restrict__ rate,
@@ -309,16 +321,19 @@ __global__ void __launch_bounds__(64) bb_pack_kernel(const int* __restrict__ ite
         else target[e] = j < k ? items[o + l + bb_target_pos(seed, g, j, k, n_rem, shuffle)] : -1;
     }
     const int si = e - ((tgt_rows * NT + 63) / 64) * 64;
-    if (si >= 0 && si < S) {
-        const unsigned long long r = mix64(seed ^ mix64(0xA5A5ull + (unsigned long long)si));
-        if (!cdf) samples[si] = (int)(r % (unsigned long long)n_items);          // np.random.choice(n_items, S) (rnn_sampling.py:191)
-        else {                                                     // bisect(cumsum, uniform(0, cumsum[-1])) (:159-163)
-            const double x = (double)(r >> 11) * (1.0 / 9007199254740992.0) * cdf[n_items - 1];
-            int lo = 0, hi = n_items;                              // first index with cdf[idx] > x
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] > x) hi = mid; else lo = mid + 1; }
-            samples[si] = min(lo, n_items - 1);
-        }
-    }
+    if (si >= 0 && si < S) samples[si] = bb_draw_item(seed, si, cdf, n_items);
+}
+
+// The id list of the cluster head (rnn_cluster.py:245: targets ++ cluster_samples) from the engine's batch, one launch: the B targets,
+// then either the batch's own negatives (`cluster_samples = samples`, :384 / :392) or n ids drawn by the law of the batch's
+// negatives (bb_draw_item) from a seed of their own (:382, :390).
+__global__ void __launch_bounds__(256) bb_cluster_ids_kernel(const int* __restrict__ targets, int n_tgt, const int* __restrict__ samples,
+                                                             int n, const double* __restrict__ cdf, int n_items,
+                                                             unsigned long long seed, int* __restrict__ ids) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_tgt) ids[i] = targets[i];
+    // (the salt: a caller that hands in the seed its batch was built from still gets another stream of draws than the negatives)
+    else if (i < n_tgt + n) ids[i] = samples ? samples[i - n_tgt] : bb_draw_item(mix64(seed ^ 0xC1057E25A3B1E5ull), i - n_tgt, cdf, n_items);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -722,4 +737,19 @@ extern "C" int sbr_build_batch(sbr_handle* h, sbr_dataset* d, int64_t batch, uin
     h->bb_set = set; h->bb_unread = true;
     h->n_rows = y.B; h->have_batch = true; h->fwd_done = false;
     return SBR_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// what the cluster head's native training step takes from the dataset (sbr_cluster.hip: sbr_cluster_train_step_lagged)
+// ---------------------------------------------------------------------------------------
+int dataset_fits_engine(const sbr_dataset* d, const sbr_handle* h) {
+    CHECK_ARG(d->n_items == h->lay.N, "dataset has %d items, the model %d", d->n_items, h->lay.N);
+    CHECK_ARG(d->stream == h->stream, "dataset and engine must share one stream");
+    return SBR_OK;
+}
+
+hipError_t launch_cluster_ids(hipStream_t s, const sbr_dataset* d, const int* targets, int n_tgt, const int* samples, int n,
+                              unsigned long long seed, int* ids) {
+    bb_cluster_ids_kernel<<<(n_tgt + n + 255) / 256, 256, 0, s>>>(targets, n_tgt, samples, n, d->d_cdf, d->n_items, seed, ids);
+    return hipGetLastError();
 }

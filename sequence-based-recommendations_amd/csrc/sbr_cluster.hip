@@ -266,15 +266,13 @@ extern "C" int sbr_cluster_get_params(sbr_cluster* k, float* R, float* Wc) { CL_
 extern "C" int sbr_cluster_get_grads(sbr_cluster* k, float* dR, float* dWc) { CL_ARG(k, "null handle"); return cl_get(k, dR, dWc, k->dR, k->dWc); }
 extern "C" int sbr_cluster_set_scale(sbr_cluster* k, float scale) { CL_ARG(k && scale > 0.0f, "bad scale"); k->scale = scale; return SBR_OK; }
 
-extern "C" int sbr_cluster_forward_backward(sbr_cluster* k, const float* h_dev, int ld_h, int off2, const int32_t* targets_dev,
-                                            const int32_t* samples_dev, int n_samples, float* cost_host) {
-    CL_ARG(k && h_dev && targets_dev && samples_dev, "null argument");
+// cost_clusters and its gradients for the id list k->ids [B + n_samples] already enqueued on the stream (either road fills it
+// with one launch of its own: cl_concat_ids_kernel, or launch_cluster_ids)
+static int cl_forward_backward_ids(sbr_cluster* k, const float* h_dev, int ld_h, int off2, int n_samples) {
     const sbr_cluster_config& c = k->cfg;
-    CL_ARG(n_samples >= 1 && n_samples <= c.max_samples, "%d cluster samples outside [1, %d]", n_samples, c.max_samples);
     const int B = c.batch_size, C = c.n_clusters, H = c.n_hidden, J = B + n_samples;
     hipStream_t s = k->stream;
     k->J = J;
-    cl_concat_ids_kernel<<<(J + 255) / 256, 256, 0, s>>>(targets_dev, B, samples_dev, n_samples, k->ids);
     const size_t lds = (size_t)(C + 256) * sizeof(float);
     cl_select_kernel<<<B, 256, lds, s>>>(h_dev, ld_h, c.hidden_split, off2, H, k->Wc, C, k->scale, c.noise_std,
                                          0x9E3779B97F4A7C15ull * (++k->noise_ctr) + c.seed, k->z, k->p, nullptr);
@@ -288,10 +286,66 @@ extern "C" int sbr_cluster_forward_backward(sbr_cluster* k, const float* h_dev, 
     cl_back_wc_kernel<<<H, 256, 0, s>>>(h_dev, ld_h, c.hidden_split, off2, k->dz, B, C, k->dWc);
     cl_back_m_kernel<<<J, 64, 0, s>>>(k->score, k->p, k->sm, k->sg, k->ids, B, C, J, k->scale, c.cluster_type, k->dR);
     CL_HIP(hipGetLastError());
+    return SBR_OK;
+}
+
+extern "C" int sbr_cluster_forward_backward(sbr_cluster* k, const float* h_dev, int ld_h, int off2, const int32_t* targets_dev,
+                                            const int32_t* samples_dev, int n_samples, float* cost_host) {
+    CL_ARG(k && h_dev && targets_dev && samples_dev, "null argument");
+    const sbr_cluster_config& c = k->cfg;
+    CL_ARG(n_samples >= 1 && n_samples <= c.max_samples, "%d cluster samples outside [1, %d]", n_samples, c.max_samples);
+    hipStream_t s = k->stream;
+    cl_concat_ids_kernel<<<(c.batch_size + n_samples + 255) / 256, 256, 0, s>>>(targets_dev, c.batch_size, samples_dev, n_samples, k->ids);
+    const int rc = cl_forward_backward_ids(k, h_dev, ld_h, off2, n_samples);
+    if (rc != SBR_OK) return rc;
     if (cost_host) {
         CL_HIP(hipMemcpyAsync(cost_host, k->cost, sizeof(float), hipMemcpyDeviceToHost, s));
         CL_HIP(hipStreamSynchronize(s));
     }
+    return SBR_OK;
+}
+
+// One training iteration of both models on the engine's device-built batch (include/sbr_rnn.h): the network's lagged step, the head
+// on that step's user representation, the head's update -- all enqueued, nothing waited for.
+extern "C" int sbr_cluster_train_step_lagged(sbr_cluster* k, sbr_handle* h, sbr_dataset* d, int n_cluster_samples, uint64_t seed,
+                                             float* prev_cost, int* have_prev) {
+    CL_ARG(k && h && d && prev_cost && have_prev, "null argument");
+    const sbr_cluster_config& c = k->cfg;
+    const Layout& y = h->lay;
+    // every refusal comes before the first launch: a refused call leaves both models as they were
+    if (!h->have_batch) { sbr_set_error("sbr_cluster_train_step_lagged: no batch set"); return SBR_ESTATE; }
+    int rc;
+    if ((rc = cluster_fits_engine(k, h)) != SBR_OK) return rc;
+    if ((rc = dataset_fits_engine(d, h)) != SBR_OK) return rc;
+    CL_ARG(y.S > 0, "the cluster head trains beside a sampled loss (Blackout, BPR, TOP1, SCCE, BPRelu, lin): this engine's has no samples");
+    CL_ARG(c.batch_size == y.Bg, "the cluster head was made for batches of %d rows, the engine's batch has %d", c.batch_size, y.Bg);
+    CL_ARG(y.B == y.Bg && h->n_rows == y.B, "the cluster head is single-rank and reads every row: local_batch %d, %d rows set, batch_size %d",
+           y.B, h->n_rows, y.Bg);
+    CL_ARG(n_cluster_samples >= 0 && n_cluster_samples <= c.max_samples, "%d cluster samples outside [0, %d]", n_cluster_samples, c.max_samples);
+    CL_ARG(n_cluster_samples > 0 || y.S <= c.max_samples, "the batch's %d negatives as cluster samples: the head holds at most %d", y.S, c.max_samples);
+    // The head reads the targets and negatives of the batch set THIS step reads: the pointers are taken here, at enqueue time -- a
+    // sbr_build_batch that follows this call fills the other set and moves h->btgt / h->bsmp on.
+    const int* tgt = h->btgt; const int* smp = n_cluster_samples > 0 ? nullptr : h->bsmp;
+    const int n = n_cluster_samples > 0 ? n_cluster_samples : y.S;
+    if ((rc = sbr_train_step_lagged(h, prev_cost, have_prev)) != SBR_OK) return rc;
+    // Order.  The head goes on the main stream behind the step.  (1) Behind that step's forward, which wrote h_last: the step's own
+    // loss phase read h_last on the main stream, in front of these launches.  (2) In front of the next step's
+    // forward, which overwrites h_last: that forward is enqueued on the main stream by a later call, and what it forks waits for a
+    // main-stream record or start word made behind these launches.  (3) In front of the build that next overwrites the set `tgt` /
+    // `smp` sit in: the next build fills the OTHER set; the one after it waits for a record (or the start word) the next step makes on
+    // the main stream, or -- the slow form -- for a fresh record on every stream of the engine: all behind these launches
+    // (sbr_build_batch).  The network's update does not touch h_last, so the head reads what the forward left.
+    CL_HIP(launch_cluster_ids(k->stream, d, tgt, c.batch_size, smp, n, (unsigned long long)seed, k->ids));
+    if ((rc = cl_forward_backward_ids(k, h_last(h), y.HLt, y.D == 2 ? y.HLp : 0, n)) != SBR_OK) return rc;
+    return sbr_cluster_apply_update(k);
+}
+
+extern "C" int sbr_cluster_last_ids(sbr_cluster* k, int32_t* ids_host, int n) {
+    CL_ARG(k && ids_host, "null argument");
+    if (k->J <= 0) { sbr_set_error("sbr_cluster_last_ids: no forward/backward yet"); return SBR_ESTATE; }
+    CL_ARG(n == k->J, "the last id list has %d entries, not %d", k->J, n);
+    CL_HIP(hipMemcpyAsync(ids_host, k->ids, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, k->stream));
+    CL_HIP(hipStreamSynchronize(k->stream));
     return SBR_OK;
 }
 

@@ -415,6 +415,13 @@ float* h_last(sbr_handle* h);                        // the user representation 
 int check_fault(sbr_handle* h);                      // synchronises the stream; fails the call if a bounded wait of its kernels gave up
 int full_scores(sbr_handle* h, int do_softmax);      // forward_current + the projection into a_logits: the scores of every item
 int forward_current(sbr_handle* h);                  // (sbr_rank_api.hip) forward pass if the batch has none yet + lazily stepped output rows flushed
+// What the cluster head's native training step (sbr_cluster.hip: sbr_cluster_train_step_lagged) needs of its neighbours
+struct sbr_dataset;
+int cluster_fits_engine(const sbr_cluster* c, const sbr_handle* h);      // (sbr_rank_api.hip) items, width and split of the user representation, stream
+int dataset_fits_engine(const sbr_dataset* d, const sbr_handle* h);      // (sbr_batch.hip) items, stream
+// (sbr_batch.hip) ids [n_tgt + n] = targets ++ (samples given: its first n entries; NULL: n draws by d's sampling law from `seed`), one launch
+hipError_t launch_cluster_ids(hipStream_t s, const sbr_dataset* d, const int* targets, int n_tgt, const int* samples, int n,
+                              unsigned long long seed, int* ids);
 
 // What the rest of the engine (sbr_api.hip: sbr_query, sbr_zero_grads, the sparse exchange, the debug calls) needs of the training
 // step (sbr_step.hip), and the one layout piece the step takes from there

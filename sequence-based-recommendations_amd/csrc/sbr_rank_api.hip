@@ -351,7 +351,7 @@ extern "C" int sbr_evaluate_ranks(sbr_handle* h, sbr_dataset* d, const int32_t* 
     return check_fault(h);          // a forward that gave up must not hand out ranks; the call's one wait for the device
 }
 
-static int cluster_fits_engine(const sbr_cluster* c, const sbr_handle* h) {
+int cluster_fits_engine(const sbr_cluster* c, const sbr_handle* h) {
     const Layout& y = h->lay;
     const int HL = y.cfg.layers[y.L - 1];
     CHECK_ARG(c->cfg.n_items == y.N, "the cluster head has %d items, the engine %d", c->cfg.n_items, y.N);

@@ -82,6 +82,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_cluster_create", "sbr_cluster_destroy", "sbr_cluster_set_params", "sbr_cluster_get_params", "sbr_cluster_get_grads",
            "sbr_cluster_set_scale", "sbr_cluster_forward_backward", "sbr_cluster_apply_update", "sbr_cluster_select",
            "sbr_cluster_mask_scores", "sbr_cluster_hard", "sbr_cluster_lists", "sbr_cluster_rank",
+           "sbr_cluster_train_step_lagged", "sbr_cluster_last_ids",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
            "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks"]
@@ -162,6 +163,8 @@ def load_library(path=None):
     lib.sbr_cluster_hard.argtypes = [vp, vp]
     lib.sbr_cluster_lists.argtypes = [vp, vp, vp]
     lib.sbr_cluster_rank.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
+    lib.sbr_cluster_train_step_lagged.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_uint64, f32p, i32p]
+    lib.sbr_cluster_last_ids.argtypes = [vp, vp, ctypes.c_int]
     lib.sbr_dataset_create.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int32, vp, ctypes.POINTER(vp)]
     lib.sbr_dataset_destroy.argtypes = [vp]
     lib.sbr_dataset_set_tables.argtypes = [vp, vp, vp]
@@ -1048,12 +1051,42 @@ class ClusterHead(object):
         self._check(self.lib.sbr_cluster_forward_backward(self.h, ptr, ld, off2, ctypes.c_void_p(self._tgt.data_ptr()),
                                                           ctypes.c_void_p(self._smp.data_ptr()), int(sm.shape[0]),
                                                           ctypes.byref(cost) if read_cost else None))
+        self._last_j = self.batch_size + int(sm.shape[0])
         return float(cost.value) if read_cost else None
 
     def apply_update(self):
         self._check(self.lib.sbr_cluster_apply_update(self.h))
         self._hard = None
         self._lists = None
+
+    def train_step_lagged(self, dataset, n_cluster_samples, seed):
+        """One training iteration of both models on the engine's current, device-built batch (sbr_cluster_train_step_lagged): the
+        network's lagged step, this head's forward/backward on the user representations of that step -- targets: the batch's;
+        cluster samples: the batch's negatives (n_cluster_samples == 0) or that many ids drawn on the device by the law of
+        `dataset` (a DeviceDataset) from `seed` -- and this head's update.  Nothing is waited for and nothing is copied from the host.
+        Returns the network's cost of the PREVIOUS lagged call (None on the first); flush_lagged() returns the last one."""
+        n = int(n_cluster_samples)
+        cost, have = ctypes.c_float(), ctypes.c_int32()
+        # (the engine's mapping of the status: SBR_EINVAL is a ValueError)
+        self.engine._check(self.lib.sbr_cluster_train_step_lagged(self.h, self.engine.h, dataset.d, n, ctypes.c_uint64(int(seed) & (2 ** 64 - 1)),
+                                                                  ctypes.byref(cost), ctypes.byref(have)))
+        self._last_j = self.batch_size + (n if n > 0 else self.engine.n_samples)
+        self._hard = None
+        self._lists = None
+        return float(cost.value) if have.value else None
+
+    def flush_lagged(self):
+        """the network's cost of the last lagged step (None if there is none to collect): RNNEngine.flush_lagged"""
+        return self.engine.flush_lagged()
+
+    def last_ids(self):
+        """The id list of the last forward/backward (tests and tooling): targets ++ cluster samples, int32 (J,).  Waits for the stream."""
+        j = getattr(self, "_last_j", 0)
+        if j <= 0:
+            raise SbrError("ClusterHead.last_ids: no forward/backward yet")
+        ids = np.empty(j, dtype=np.int32)
+        self.engine._check(self.lib.sbr_cluster_last_ids(self.h, _ptr(ids), j))
+        return ids
 
     def select(self, rows, with_activations=False):
         """argmax cluster of the first `rows` user representations (rnn_cluster.py:334) [, the selection activations]"""

@@ -305,7 +305,7 @@ class RNNBase(object):
         rank0 = dp is None or dp.rank == 0
         if dp is not None and native is None:
             raise ValueError("data-parallel training runs on device-built batches only: " + str(self._native_batch_refusal(dataset)))
-        stepper = dp if dp is not None else self.engine
+        stepper = self._native_stepper(native)
         save = self.save if dp is None else (lambda f: self.save(f, write=rank0))
         shared_clock = ranks > 1 and (max_time != np.inf or time_based_progress)
         batch_generator = native if native is not None else self._gen_mini_batch(self.sequence_noise(dataset.training_set()))
@@ -416,13 +416,22 @@ class RNNBase(object):
         pop = np.asarray(dataset.item_popularity, dtype=np.float64)
         db = float(getattr(self, "diversity_bias", 0.0))
         sb = float(getattr(self, "sampling_bias", 0.0))
-        cdf = np.cumsum(np.power(pop, sb)) if (sb > 0.0 and getattr(self, "effective_sampling", 0)) else None
+        cdf = np.cumsum(np.power(pop, sb)) if (sb > 0.0 and self._n_negatives()) else None
         return NativeBatchBuilder(self.engine, dataset.training_set, self.n_items, self.batch_size,
                                   pop_db=np.power(pop, db).astype(np.float32), sample_cdf=cdf,
                                   ratings=self.use_ratings_features, shuffle_targets=ts.shuffle, noise=self.sequence_noise,
                                   keep_prob=(np.power(np.min(np.maximum(1, pop)) / np.maximum(1, pop), ts.bias).astype(np.float32)
                                              if ts.bias >= 0.0 else None),
                                   n_targets=self._engine_targets() if multi else 1, sync=self.dp)
+
+    def _n_negatives(self):
+        """negatives a batch carries for a sampled head (0: the model has none)"""
+        return int(getattr(self, "effective_sampling", 0))
+
+    def _native_stepper(self, builder):
+        """what the training loop steps per device-built batch: an object with train_step_lagged() -- enqueue one iteration on the
+        engine's current batch, return the cost of the previous one or None -- and flush_lagged()"""
+        return self.dp if self.dp is not None else self.engine
 
     def _native_batch_refusal(self, dataset):
         """why this configuration trains on the reference-style host generator instead of device-built batches, or None; needs
@@ -716,14 +725,35 @@ class RNNMargin(RNNBase):
 
 
 
+class _ClusterStepper(object):
+    """RNNCluster's stepper for device-built batches (RNNBase._native_stepper): per iteration the scale rule against the builder's
+    epochs, one ClusterHead.train_step_lagged -- both models step, nothing is waited for --, the cached hard clusters dropped"""
+
+    def __init__(self, model, builder):
+        self.model, self.builder = model, builder
+        self.seed, self.iteration = random.getrandbits(62), 0
+
+    def train_step_lagged(self):
+        m = self.model
+        m._grow_scale()
+        self.iteration += 1
+        cost = m.head.train_step_lagged(self.builder.ds, max(m.n_cluster_samples, 0), self.seed + self.iteration)
+        m._drop_hard_clusters()
+        return cost
+
+    def flush_lagged(self):
+        return self.model.head.flush_lagged()
+
+
 class RNNCluster(RNNBase):
     """RNN + sampled output loss + item clustering, `--clusters C` (rnn_cluster.py:19-539; command_parser.py:71-77, :114-115).
     Two models trained side by side from one forward pass: the recurrent network with its sampled head on `cost` (the engine:
     losses Blackout / CCE over the sampled columns / BPR / TOP1 / BPRelu / lin, rnn_cluster.py:151-180), and the cluster head
     -- selection weights and the item / cluster repartition -- on `cost_clusters` (engine.ClusterHead, csrc/sbr_cluster.hip),
-    each with its own updater state (:277-285).  Host logic as in the reference: filename grammar, batch packing with the cluster
-    samples and the growing scale, the per-user test function and its nine metrics, hard clusters for top_k_recommendations,
-    checkpoints with the two cluster arrays appended."""
+    each with its own updater state (:277-285).  Training runs on device-built batches like every other model (the cluster samples
+    are drawn on the device, ClusterHead.train_step_lagged); the growing scale follows the builder's epochs on the host.  Host logic
+    as in the reference: filename grammar, the host road's batch packing (SBR_NATIVE_BATCHES=0), the per-user test function and its
+    nine metrics, hard clusters for top_k_recommendations, checkpoints with the two cluster arrays appended."""
 
     ENGINE_LOSS = {"CCE": "SCCE", "Blackout": "Blackout", "BPR": "BPR", "TOP1": "TOP1", "BPRelu": "BPRelu", "lin": "lin"}
 
@@ -811,6 +841,12 @@ class RNNCluster(RNNBase):
                 cluster_samples = np.random.choice(self.n_items, self.n_cluster_samples).astype(np.int32)
             else:
                 cluster_samples = samples
+        self._grow_scale()
+        return (X, mask, Y, samples, cluster_samples, None)
+
+    def _grow_scale(self):
+        """the scale follows the epochs of the training set (rnn_cluster.py:395-400), whichever road builds the batches: the head
+        takes it as a kernel argument of the launches enqueued from now on"""
         if not hasattr(self, "_last_epoch"):
             self._last_epoch = self.dataset.training_set.epochs
         elif self.dataset.training_set.epochs > self._last_epoch + 1 and self.scale_growing_rate != 1.0:
@@ -818,13 +854,12 @@ class RNNCluster(RNNBase):
             self._last_epoch += int(self.dataset.training_set.epochs - self._last_epoch)
             print("New scale: ", self.effective_scale)
             self.head.set_scale(float(self.effective_scale))
-        return (X, mask, Y, samples, cluster_samples, None)
 
-    def _native_batch_builder(self, dataset):
-        return None          # the cluster samples and the growing scale are host state: the reference-style generator feeds this model
+    def _n_negatives(self):
+        return self.n_samples
 
-    def _native_batch_refusal(self, dataset):
-        return "--clusters: the cluster samples and the growing scale are host state"
+    def _native_stepper(self, builder):
+        return _ClusterStepper(self, builder)
 
     # ------------------------------------------------------------------ the compiled-function seam
     def train_function(self, X, mask, target, samples, cluster_samples, exclude=None):
