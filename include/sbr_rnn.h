@@ -582,6 +582,46 @@ int sbr_cluster_train_step_lagged(sbr_cluster* c, sbr_handle* h, sbr_dataset* d,
  * ids_host [n], n == J.  Synchronises the stream.  SBR_ESTATE: no forward/backward yet. */
 int sbr_cluster_last_ids(sbr_cluster* c, int32_t* ids_host, int n);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training state (added under ABI 11: nine symbols, no struct change) -- what a run needs beside the reference's checkpoint
+ * (rnn_base.py:470-515 pickles the parameter arrays only) to go on, in a new process, bit for bit as if it had never stopped.
+ * Three objects, each with   *_state_bytes(obj, &bytes)   the exact size of its blob now,
+ *                            *_state_save(obj, blob_host, cap, &written)   cap >= bytes, written == bytes,
+ *                            *_state_load(obj, blob_host, bytes).
+ * A blob is host memory, opaque, little endian, and starts with a magic, a format version, its kind and its own size.
+ * save changes nothing and launches nothing: it waits for the object's streams and copies device memory to the host -- lazily
+ *   stepped rows (see "Row-sparse blocks") are NOT brought up to date, they are saved as they stand with their `last` words, so a
+ *   run with saves in it computes what the run without them computes.
+ * load checks the whole blob before it writes anything -- size, magic, version, kind, and what fixes the layout -- and returns
+ *   SBR_EINVAL with the first mismatch in sbr_last_error(), the object untouched.  It never flushes either.
+ *
+ * sbr_state_*          the engine: parameter section as it lies in the arena (padding included), every optimizer state array, the
+ *                      step count (Adam's t), every row-sparse block's `last` words.  Layout fingerprint: parameter floats, offset of
+ *                      the output layer, number of state arrays, updater, kind / rows / row width of every sparse block, a hash of
+ *                      the logical shapes of the parameter list (20 and 30 units pad to one layout: still two models) -- nothing of
+ *                      local_batch or row_offset, data-parallel replicas hold the same state and read the same blob.
+ *                      save: SBR_ESTATE while a training step is open (between sbr_zero_grads and sbr_apply_update) or a lagged
+ *                      cost is pending (collect it with sbr_lagged_flush first).  load (SBR_ESTATE inside an open step) leaves a
+ *                      fresh step boundary: gradient section zero, no current batch, no forward, no lagged report -- where a fresh
+ *                      engine with these values stands.  save behind load returns the same bytes.
+ * sbr_cluster_state_*  the cluster head: R, Wc, both optimizer state arrays of each, its step count, the noise counter, the scale as
+ *                      sbr_cluster_set_scale left it, and the seed of its config.  load drops the hard clusters and the member lists,
+ *                      as sbr_cluster_set_params does.  Fingerprint: items, clusters, features, updater.
+ * sbr_dataset_state_*  what makes the next sbr_dataset_plan_pass reproduce its plan: the pass counter of the host row planner, the
+ *                      rows (or users) the last planned pass carried over, the batch size they were planned for.  Host memory only.
+ *                      NOT the sequences, tables and options: the caller sets those up from its files as on a fresh start (the target
+ *                      bias included: the blob must agree with it), then loads.  Fingerprint: users, interactions, items; every
+ *                      carried row must index the uploaded sequences.  The plan in force is left alone: plan the next pass. */
+int sbr_state_bytes(sbr_handle* h, size_t* bytes);
+int sbr_state_save(sbr_handle* h, void* blob_host, size_t cap, size_t* written);
+int sbr_state_load(sbr_handle* h, const void* blob_host, size_t bytes);
+int sbr_cluster_state_bytes(sbr_cluster* c, size_t* bytes);
+int sbr_cluster_state_save(sbr_cluster* c, void* blob_host, size_t cap, size_t* written);
+int sbr_cluster_state_load(sbr_cluster* c, const void* blob_host, size_t bytes);
+int sbr_dataset_state_bytes(sbr_dataset* d, size_t* bytes);
+int sbr_dataset_state_save(sbr_dataset* d, void* blob_host, size_t cap, size_t* written);
+int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

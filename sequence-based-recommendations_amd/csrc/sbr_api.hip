@@ -4,6 +4,7 @@
 // The host side mirrors what RNNBase does around its Theano functions
 // (neural_networks/rnn_base.py:175-213, :285-300, :470-515); the arithmetic lives in the kernels.
 #include "sbr_common.h"
+#include "sbr_state.h"
 #include <stdarg.h>
 #include <stdio.h>
 #include <string.h>
@@ -555,6 +556,130 @@ extern "C" int sbr_section(sbr_handle* h, int which, void** dev_ptr, size_t* n_f
     }
     sbr_set_error("unknown section %d", which);
     return SBR_EINVAL;
+}
+
+// ---------------------------------------------------------------------------------------
+// the whole training state as one host blob (include/sbr_rnn.h "Training state"; head and its checks: sbr_state.h)
+// ---------------------------------------------------------------------------------------
+// What fixes the blob's layout.  Nothing of local_batch / row_offset: data-parallel replicas hold the same state.
+struct EngineStateFp {
+    uint64_t n_params, p_split;
+    uint32_t n_state, updater, n_sparse, pad;
+    uint32_t kind[2], rows[2], width[2];
+    uint64_t shapes;        // FNV-1a over the logical shapes of the parameter list: widths that pad alike (20 and 30 units) are still two models
+};
+static EngineStateFp engine_state_fp(const sbr_handle* h) {
+    const Layout& y = h->lay;
+    EngineStateFp f;
+    memset(&f, 0, sizeof(f));
+    f.shapes = 0xcbf29ce484222325ull;
+    for (const ParamDesc& d : h->descs)
+        for (int64_t v : {(int64_t)d.ndim, d.d0, d.ndim == 2 ? d.d1 : (int64_t)1})
+            for (int i = 0; i < 8; ++i) { f.shapes ^= (uint64_t)(v >> (8 * i)) & 0xff; f.shapes *= 0x100000001b3ull; }
+    f.n_params = y.n_params; f.p_split = y.p_split;
+    f.n_state = (uint32_t)y.n_state_arrays; f.updater = (uint32_t)y.cfg.updater; f.n_sparse = (uint32_t)y.n_sparse;
+    for (int b = 0; b < y.n_sparse; ++b) { f.kind[b] = (uint32_t)y.sparse[b].kind; f.rows[b] = (uint32_t)y.sparse[b].n_rows; f.width[b] = (uint32_t)y.sparse[b].W; }
+    return f;
+}
+// head | fingerprint | step_count | parameter section (padded, as it lies in the arena) | state arrays | a_last of every sparse block
+static const size_t kEngineStateFixed = sizeof(SbrStateHead) + sizeof(EngineStateFp) + sizeof(int64_t);
+static size_t engine_state_bytes(const Layout& y) {
+    size_t n = kEngineStateFixed + (1 + y.n_state_arrays) * y.n_params * sizeof(float);
+    for (int b = 0; b < y.n_sparse; ++b) n += (size_t)y.sparse[b].n_rows * sizeof(int);
+    return n;
+}
+static int engine_sync_all(sbr_handle* h) {
+    SBR_HIP(hipStreamSynchronize(h->stream));
+    for (hipStream_t* st : handle_streams(h)) if (*st) SBR_HIP(hipStreamSynchronize(*st));
+    return SBR_OK;
+}
+
+extern "C" int sbr_state_bytes(sbr_handle* h, size_t* bytes) {
+    CHECK_ARG(h && bytes, "null argument");
+    *bytes = engine_state_bytes(h->lay);
+    return SBR_OK;
+}
+
+extern "C" int sbr_state_save(sbr_handle* h, void* blob, size_t cap, size_t* written) {
+    CHECK_ARG(h && blob && written, "null argument");
+    const Layout& y = h->lay;
+    if (h->step_open || h->train_fwd_open) { sbr_set_error("sbr_state_save: a training step is open (finish it with sbr_apply_update)"); return SBR_ESTATE; }
+    if (h->lag_pending >= 0) { sbr_set_error("sbr_state_save: a lagged cost is pending (collect it with sbr_lagged_flush)"); return SBR_ESTATE; }
+    const size_t need = engine_state_bytes(y);
+    CHECK_ARG(cap >= need, "sbr_state_save: the state takes %zu bytes, the buffer holds %zu", need, cap);
+    // no launch, no flush: the lazily stepped rows and their `last` words are saved as they stand
+    { const int rc = engine_sync_all(h); if (rc != SBR_OK) return rc; }
+    char* p = (char*)blob;
+    const SbrStateHead hd = sbr_state_head(SBR_STATE_ENGINE, need);
+    const EngineStateFp fp = engine_state_fp(h);
+    const int64_t steps = h->step_count;
+    memcpy(p, &hd, sizeof(hd)); p += sizeof(hd);
+    memcpy(p, &fp, sizeof(fp)); p += sizeof(fp);
+    memcpy(p, &steps, sizeof(steps)); p += sizeof(steps);
+    const size_t sec = y.n_params * sizeof(float);
+    SBR_HIP(hipMemcpyAsync(p, h->P(0), sec, hipMemcpyDeviceToHost, h->stream)); p += sec;
+    for (size_t k = 0; k < y.n_state_arrays; ++k) { SBR_HIP(hipMemcpyAsync(p, h->St((int)k, 0), sec, hipMemcpyDeviceToHost, h->stream)); p += sec; }
+    for (int b = 0; b < y.n_sparse; ++b) {
+        const size_t n = (size_t)y.sparse[b].n_rows * sizeof(int);
+        SBR_HIP(hipMemcpyAsync(p, h->A(y.sparse[b].a_last), n, hipMemcpyDeviceToHost, h->stream)); p += n;
+    }
+    SBR_HIP(hipStreamSynchronize(h->stream));
+    *written = need;
+    return SBR_OK;
+}
+
+extern "C" int sbr_state_load(sbr_handle* h, const void* blob, size_t bytes) {
+    CHECK_ARG(h, "null handle");
+    const Layout& y = h->lay;
+    if (h->step_open || h->train_fwd_open) { sbr_set_error("sbr_state_load: a training step is open (finish it with sbr_apply_update)"); return SBR_ESTATE; }
+    // everything is checked before anything is written
+    { const int rc = sbr_state_check_head(blob, bytes, SBR_STATE_ENGINE, "sbr_state_load"); if (rc != SBR_OK) return rc; }
+    CHECK_ARG(bytes >= kEngineStateFixed, "sbr_state_load: a blob of %zu bytes is shorter than its fixed part (%zu)", bytes, kEngineStateFixed);
+    const char* p = (const char*)blob + sizeof(SbrStateHead);
+    EngineStateFp got; const EngineStateFp fp = engine_state_fp(h);
+    int64_t steps = 0;
+    memcpy(&got, p, sizeof(got)); p += sizeof(got);
+    memcpy(&steps, p, sizeof(steps)); p += sizeof(steps);
+    CHECK_ARG(got.n_params == fp.n_params && got.p_split == fp.p_split,
+              "sbr_state_load: the blob holds %llu parameters (output layer at %llu), this engine %llu (at %llu): another architecture",
+              (unsigned long long)got.n_params, (unsigned long long)got.p_split, (unsigned long long)fp.n_params, (unsigned long long)fp.p_split);
+    CHECK_ARG(got.shapes == fp.shapes, "sbr_state_load: the blob's parameter arrays have other shapes than this engine's (other layer widths behind the same padding)");
+    CHECK_ARG(got.updater == fp.updater && got.n_state == fp.n_state, "sbr_state_load: the blob is of updater %u with %u state arrays, this engine of updater %u with %u",
+              got.updater, got.n_state, fp.updater, fp.n_state);
+    CHECK_ARG(got.n_sparse == fp.n_sparse, "sbr_state_load: the blob has %u row-sparse blocks, this engine %u", got.n_sparse, fp.n_sparse);
+    for (int b = 0; b < y.n_sparse; ++b)
+        CHECK_ARG(got.kind[b] == fp.kind[b] && got.rows[b] == fp.rows[b] && got.width[b] == fp.width[b],
+                  "sbr_state_load: row-sparse block %d is kind %u, %u rows of %u floats in the blob; kind %u, %u rows of %u here", b, got.kind[b],
+                  got.rows[b], got.width[b], fp.kind[b], fp.rows[b], fp.width[b]);
+    CHECK_ARG(bytes == engine_state_bytes(y), "sbr_state_load: the state of this engine takes %zu bytes, the blob has %zu", engine_state_bytes(y), bytes);
+    CHECK_ARG(steps >= 0, "sbr_state_load: step count %lld", (long long)steps);
+    const size_t sec = y.n_params * sizeof(float);
+    {   // a row is current through a step that has been applied
+        const char* q = p + (1 + y.n_state_arrays) * sec;
+        for (int b = 0; b < y.n_sparse; ++b)
+            for (int r = 0; r < y.sparse[b].n_rows; ++r, q += sizeof(int)) {
+                int last; memcpy(&last, q, sizeof(int));
+                CHECK_ARG(last >= 0 && last <= steps, "sbr_state_load: row %d of block %d is current through step %d of %lld", r, b, last, (long long)steps);
+            }
+    }
+    // from here on the engine changes.  Work in flight may still read what is overwritten: let every stream drain first
+    { const int rc = engine_sync_all(h); if (rc != SBR_OK) return rc; }
+    SBR_HIP(hipMemcpyAsync(h->P(0), p, sec, hipMemcpyHostToDevice, h->stream)); p += sec;
+    for (size_t k = 0; k < y.n_state_arrays; ++k) { SBR_HIP(hipMemcpyAsync(h->St((int)k, 0), p, sec, hipMemcpyHostToDevice, h->stream)); p += sec; }
+    for (int b = 0; b < y.n_sparse; ++b) {
+        const size_t n = (size_t)y.sparse[b].n_rows * sizeof(int);
+        SBR_HIP(hipMemcpyAsync(h->A(y.sparse[b].a_last), p, n, hipMemcpyHostToDevice, h->stream)); p += n;
+    }
+    // a fresh step boundary: no gradients, no batch, no forward, no open step, no report under way
+    SBR_HIP(hipMemsetAsync(h->Gd(0), 0, (y.n_params + 1) * sizeof(float), h->stream));
+    SBR_HIP(hipStreamSynchronize(h->stream));      // the caller's blob may be freed on return
+    h->step_count = steps;
+    h->grads_clean = true;
+    h->fwd_done = false; h->have_batch = false; h->bb_unread = false;
+    h->step_open = false; h->train_fwd_open = false;
+    h->lag_pending = -1;
+    if (h->bb_slow < 1) h->bb_slow = 1;             // the next build trusts no record made before the load
+    return SBR_OK;
 }
 
 // ---------------------------------------------------------------------------------------

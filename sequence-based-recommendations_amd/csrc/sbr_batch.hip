@@ -3,6 +3,7 @@
 // rnn_sampling.py:159-194) with the training set resident in HBM as CSR and every per-batch array produced by
 // two kernels on the engine's stream.  The host only walks the user list once per pass (integer bookkeeping).
 #include "sbr_common.h"
+#include "sbr_state.h"
 #include <algorithm>
 #include <unordered_map>
 
@@ -655,6 +656,84 @@ extern "C" int sbr_dataset_plan_pass(sbr_dataset* d, const int32_t* order, int32
     if ((r = upload(&d->d_batch_begin, &d->cap_bb, d->batch_begin, d->stream)) != SBR_OK) return r;
     SBR_HIP(hipStreamSynchronize(d->stream));
     d->n_batches = nb; *n_batches = nb;
+    return SBR_OK;
+}
+
+// What makes the next sbr_dataset_plan_pass reproduce its plan, as one host blob (include/sbr_rnn.h "Training state"):
+// head | fixed part | hr_pu | hr_ps | hr_pt | pend_user | pend_k.  All of it is host memory: nothing is copied from the device.
+struct DatasetStateFixed {
+    uint64_t n_users, nnz;                  // what the carried rows index: the sequences the caller uploads again
+    uint32_t n_items; int32_t host_rows, hr_targets, batch_size;
+    uint64_t hr_pass;
+    uint32_t n_hr, n_pend;                  // carried rows of the host row planner / of the segment planner
+};
+static size_t dataset_state_bytes(const sbr_dataset* d) {
+    return sizeof(SbrStateHead) + sizeof(DatasetStateFixed) +
+           (d->hr_pu.size() + d->hr_ps.size() + d->hr_pt.size() + d->pend_user.size() + d->pend_k.size()) * sizeof(int);
+}
+extern "C" int sbr_dataset_state_bytes(sbr_dataset* d, size_t* bytes) {
+    CHECK_ARG(d && bytes, "null argument");
+    *bytes = dataset_state_bytes(d);
+    return SBR_OK;
+}
+extern "C" int sbr_dataset_state_save(sbr_dataset* d, void* blob, size_t cap, size_t* written) {
+    CHECK_ARG(d && blob && written, "null argument");
+    const size_t need = dataset_state_bytes(d);
+    CHECK_ARG(cap >= need, "sbr_dataset_state_save: the state takes %zu bytes, the buffer holds %zu", need, cap);
+    CHECK_ARG(d->hr_pt.size() == d->hr_pu.size() * (size_t)d->hr_targets && d->hr_ps.size() == d->hr_pu.size() && d->pend_k.size() == d->pend_user.size(),
+              "sbr_dataset_state_save: inconsistent carried rows");
+    char* p = (char*)blob;
+    const SbrStateHead hd = sbr_state_head(SBR_STATE_DATASET, need);
+    DatasetStateFixed fx;
+    memset(&fx, 0, sizeof(fx));
+    fx.n_users = (uint64_t)d->n_users; fx.nnz = (uint64_t)d->nnz; fx.n_items = (uint32_t)d->n_items;
+    fx.host_rows = d->host_rows; fx.hr_targets = d->hr_targets; fx.batch_size = d->batch_size; fx.hr_pass = d->hr_pass;
+    fx.n_hr = (uint32_t)d->hr_pu.size(); fx.n_pend = (uint32_t)d->pend_user.size();
+    memcpy(p, &hd, sizeof(hd)); p += sizeof(hd);
+    memcpy(p, &fx, sizeof(fx)); p += sizeof(fx);
+    for (const std::vector<int>* v : {&d->hr_pu, &d->hr_ps, &d->hr_pt, &d->pend_user, &d->pend_k}) {
+        if (!v->empty()) memcpy(p, v->data(), v->size() * sizeof(int));
+        p += v->size() * sizeof(int);
+    }
+    *written = need;
+    return SBR_OK;
+}
+extern "C" int sbr_dataset_state_load(sbr_dataset* d, const void* blob, size_t bytes) {
+    CHECK_ARG(d, "null dataset");
+    { const int rc = sbr_state_check_head(blob, bytes, SBR_STATE_DATASET, "sbr_dataset_state_load"); if (rc != SBR_OK) return rc; }
+    CHECK_ARG(bytes >= sizeof(SbrStateHead) + sizeof(DatasetStateFixed), "sbr_dataset_state_load: a blob of %zu bytes is shorter than its fixed part", bytes);
+    const char* p = (const char*)blob + sizeof(SbrStateHead);
+    DatasetStateFixed fx;
+    memcpy(&fx, p, sizeof(fx)); p += sizeof(fx);
+    CHECK_ARG(fx.n_users == (uint64_t)d->n_users && fx.nnz == (uint64_t)d->nnz && fx.n_items == (uint32_t)d->n_items,
+              "sbr_dataset_state_load: the blob is of %llu users, %llu interactions, %u items; this dataset of %lld, %lld, %d", (unsigned long long)fx.n_users,
+              (unsigned long long)fx.nnz, fx.n_items, (long long)d->n_users, (long long)d->nnz, d->n_items);
+    CHECK_ARG(fx.host_rows == d->host_rows && (!fx.host_rows || fx.hr_targets == d->hr_targets),
+              "sbr_dataset_state_load: the blob's rows are planned %s (%d targets), this dataset's %s (%d): set the target bias as the saved run did",
+              fx.host_rows ? "on the host" : "on the device", fx.hr_targets, d->host_rows ? "on the host" : "on the device", d->hr_targets);
+    CHECK_ARG(fx.batch_size >= 0 && fx.hr_targets >= 1 && fx.hr_targets <= 1024, "sbr_dataset_state_load: batch size %d, %d targets", fx.batch_size, fx.hr_targets);
+    const size_t n_hr = fx.n_hr, n_pend = fx.n_pend, NT = (size_t)fx.hr_targets;
+    CHECK_ARG(n_hr <= (size_t)fx.batch_size && n_pend <= (size_t)fx.batch_size, "sbr_dataset_state_load: %zu / %zu carried rows for batches of %d", n_hr, n_pend, fx.batch_size);
+    CHECK_ARG(bytes == sizeof(SbrStateHead) + sizeof(DatasetStateFixed) + (n_hr * (2 + NT) + 2 * n_pend) * sizeof(int),
+              "sbr_dataset_state_load: %zu bytes do not hold %zu + %zu carried rows", bytes, n_hr, n_pend);
+    std::vector<int> pu(n_hr), ps(n_hr), pt(n_hr * NT), qu(n_pend), qk(n_pend);
+    for (std::vector<int>* v : {&pu, &ps, &pt, &qu, &qk}) {
+        if (!v->empty()) memcpy(v->data(), p, v->size() * sizeof(int));
+        p += v->size() * sizeof(int);
+    }
+    // a carried row indexes the uploaded sequences (sbr_build_batch reads items[offsets[u] + split + pos] on the device)
+    for (size_t i = 0; i < n_hr; ++i) {
+        CHECK_ARG(pu[i] >= 0 && pu[i] < d->n_users, "sbr_dataset_state_load: carried row %zu is of user %d", i, pu[i]);
+        const int64_t L = d->len[pu[i]];
+        CHECK_ARG(ps[i] >= 2 && ps[i] < L, "sbr_dataset_state_load: carried row %zu splits a sequence of %lld items at %d", i, (long long)L, ps[i]);
+        for (size_t t = 0; t < NT; ++t)
+            CHECK_ARG(pt[i * NT + t] >= -1 && pt[i * NT + t] < L - ps[i], "sbr_dataset_state_load: carried row %zu has a target at place %d behind a split at %d of %lld",
+                      i, pt[i * NT + t], ps[i], (long long)L);
+    }
+    for (size_t i = 0; i < n_pend; ++i)
+        CHECK_ARG(qu[i] >= 0 && qu[i] < d->n_users && qk[i] >= 1 && qk[i] <= fx.batch_size, "sbr_dataset_state_load: carried user %d with %d rows", qu[i], qk[i]);
+    d->hr_pass = fx.hr_pass; d->batch_size = fx.batch_size;
+    d->hr_pu.swap(pu); d->hr_ps.swap(ps); d->hr_pt.swap(pt); d->pend_user.swap(qu); d->pend_k.swap(qk);
     return SBR_OK;
 }
 

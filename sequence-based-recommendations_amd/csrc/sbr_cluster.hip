@@ -17,6 +17,7 @@
 #include <cstdlib>
 #include <new>
 #include "sbr_common.h"
+#include "sbr_state.h"
 
 extern void sbr_set_error(const char* fmt, ...);
 #define CL_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { sbr_set_error("%s: %s", #x, hipGetErrorString(e_)); return SBR_EHIP; } } while (0)
@@ -265,6 +266,71 @@ static int cl_get(sbr_cluster* k, float* R, float* Wc, const float* dR, const fl
 extern "C" int sbr_cluster_get_params(sbr_cluster* k, float* R, float* Wc) { CL_ARG(k, "null handle"); return cl_get(k, R, Wc, k->R, k->Wc); }
 extern "C" int sbr_cluster_get_grads(sbr_cluster* k, float* dR, float* dWc) { CL_ARG(k, "null handle"); return cl_get(k, dR, dWc, k->dR, k->dWc); }
 extern "C" int sbr_cluster_set_scale(sbr_cluster* k, float scale) { CL_ARG(k && scale > 0.0f, "bad scale"); k->scale = scale; return SBR_OK; }
+
+// The head's training state as one host blob (include/sbr_rnn.h "Training state"):
+// head | fixed part | R | Wc | sR[0] | sR[1] | sWc[0] | sWc[1]  (both state arrays of each, whatever the updater uses: create zeroes them)
+struct ClusterStateFixed {
+    uint32_t n_items, n_clusters, n_hidden, updater;      // what fixes the layout
+    int64_t step;
+    uint64_t noise_ctr, seed;
+    float scale; uint32_t pad;
+};
+static size_t cl_state_bytes(const sbr_cluster* k) {
+    const size_t nR = (size_t)k->cfg.n_items * k->cfg.n_clusters, nW = (size_t)k->cfg.n_hidden * k->cfg.n_clusters;
+    return sizeof(SbrStateHead) + sizeof(ClusterStateFixed) + 3 * (nR + nW) * sizeof(float);
+}
+extern "C" int sbr_cluster_state_bytes(sbr_cluster* k, size_t* bytes) {
+    CL_ARG(k && bytes, "null argument");
+    *bytes = cl_state_bytes(k);
+    return SBR_OK;
+}
+extern "C" int sbr_cluster_state_save(sbr_cluster* k, void* blob, size_t cap, size_t* written) {
+    CL_ARG(k && blob && written, "null argument");
+    const sbr_cluster_config& c = k->cfg;
+    const size_t need = cl_state_bytes(k);
+    CL_ARG(cap >= need, "sbr_cluster_state_save: the state takes %zu bytes, the buffer holds %zu", need, cap);
+    CL_HIP(hipStreamSynchronize(k->stream));        // nothing is launched: the head's steps are complete calls, there is no open one
+    char* p = (char*)blob;
+    const SbrStateHead hd = sbr_state_head(SBR_STATE_CLUSTER, need);
+    ClusterStateFixed fx;
+    memset(&fx, 0, sizeof(fx));
+    fx.n_items = (uint32_t)c.n_items; fx.n_clusters = (uint32_t)c.n_clusters; fx.n_hidden = (uint32_t)c.n_hidden; fx.updater = (uint32_t)c.updater;
+    fx.step = (int64_t)k->step; fx.noise_ctr = k->noise_ctr; fx.seed = c.seed; fx.scale = k->scale;
+    memcpy(p, &hd, sizeof(hd)); p += sizeof(hd);
+    memcpy(p, &fx, sizeof(fx)); p += sizeof(fx);
+    const size_t nR = (size_t)c.n_items * c.n_clusters * sizeof(float), nW = (size_t)c.n_hidden * c.n_clusters * sizeof(float);
+    const float* src[] = {k->R, k->Wc, k->sR[0], k->sR[1], k->sWc[0], k->sWc[1]};
+    const size_t len[] = {nR, nW, nR, nR, nW, nW};
+    for (int i = 0; i < 6; ++i) { CL_HIP(hipMemcpyAsync(p, src[i], len[i], hipMemcpyDeviceToHost, k->stream)); p += len[i]; }
+    CL_HIP(hipStreamSynchronize(k->stream));
+    *written = need;
+    return SBR_OK;
+}
+extern "C" int sbr_cluster_state_load(sbr_cluster* k, const void* blob, size_t bytes) {
+    CL_ARG(k, "null handle");
+    const sbr_cluster_config& c = k->cfg;
+    { const int rc = sbr_state_check_head(blob, bytes, SBR_STATE_CLUSTER, "sbr_cluster_state_load"); if (rc != SBR_OK) return rc; }
+    CL_ARG(bytes >= sizeof(SbrStateHead) + sizeof(ClusterStateFixed), "sbr_cluster_state_load: a blob of %zu bytes is shorter than its fixed part", bytes);
+    const char* p = (const char*)blob + sizeof(SbrStateHead);
+    ClusterStateFixed fx;
+    memcpy(&fx, p, sizeof(fx)); p += sizeof(fx);
+    CL_ARG(fx.n_items == (uint32_t)c.n_items && fx.n_clusters == (uint32_t)c.n_clusters && fx.n_hidden == (uint32_t)c.n_hidden,
+           "sbr_cluster_state_load: the blob is of %u items, %u clusters, %u features; this head of %d, %d, %d", fx.n_items, fx.n_clusters,
+           fx.n_hidden, c.n_items, c.n_clusters, c.n_hidden);
+    CL_ARG(fx.updater == (uint32_t)c.updater, "sbr_cluster_state_load: the blob is of updater %u, this head of updater %d", fx.updater, c.updater);
+    CL_ARG(bytes == cl_state_bytes(k), "sbr_cluster_state_load: the state of this head takes %zu bytes, the blob has %zu", cl_state_bytes(k), bytes);
+    CL_ARG(fx.step >= 0 && fx.scale > 0.0f, "sbr_cluster_state_load: step %lld, scale %g", (long long)fx.step, (double)fx.scale);
+    CL_HIP(hipStreamSynchronize(k->stream));
+    const size_t nR = (size_t)c.n_items * c.n_clusters * sizeof(float), nW = (size_t)c.n_hidden * c.n_clusters * sizeof(float);
+    float* dst[] = {k->R, k->Wc, k->sR[0], k->sR[1], k->sWc[0], k->sWc[1]};
+    const size_t len[] = {nR, nW, nR, nR, nW, nW};
+    for (int i = 0; i < 6; ++i) { CL_HIP(hipMemcpyAsync(dst[i], p, len[i], hipMemcpyHostToDevice, k->stream)); p += len[i]; }
+    CL_HIP(hipStreamSynchronize(k->stream));
+    k->step = (long)fx.step; k->noise_ctr = fx.noise_ctr; k->cfg.seed = fx.seed; k->scale = fx.scale;
+    k->hard_valid = 0; k->hardT_valid = 0; k->lists_valid = 0;
+    k->dR_clean = 0;                                 // the next forward clears dR itself
+    return SBR_OK;
+}
 
 // cost_clusters and its gradients for the id list k->ids [B + n_samples] already enqueued on the stream (either road fills it
 // with one launch of its own: cl_concat_ids_kernel, or launch_cluster_ids)

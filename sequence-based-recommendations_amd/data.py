@@ -104,23 +104,31 @@ class NativeBatchBuilder(object):
             self.ds.set_options(r, shuffle_targets)
         self.sync = sync if (sync is not None and sync.world > 1) else None
         shared = (lambda v: v) if self.sync is None else self.sync.broadcast_seed
+        self._target_bias, self.tb_seed = None, None
         if keep_prob is not None:           # --target_bias: rows planned on the host (a row may run out of targets)
-            self.ds.set_target_bias(keep_prob, n_targets, seed=shared(int(seed if seed is not None else random.getrandbits(62))))
+            self.tb_seed = shared(int(seed if seed is not None else random.getrandbits(62)))
+            self._target_bias = (np.array(keep_prob, dtype=np.float32), int(n_targets))
+            self.ds.set_target_bias(keep_prob, n_targets, seed=self.tb_seed)
         self.n_users = len(lengths)
         self.noise = noise if (noise is not None and getattr(noise, "name", "") != "") else None      # a SequenceNoise
         self.seed = shared(int(seed if seed is not None else random.getrandbits(63)))
         self.passes, self.cursor, self.n_batches, self.built = 0, 0, 0, 0
         self._frac = np.zeros(0)
+        self._before_pass = self.ds.get_state()      # the dataset's state in front of the pass in force (get_state)
 
-    def _plan(self):
-        self.passes += 1
-        if self.sync is None or self.sync.rank == 0:
-            print("Opening file ({})".format(self.passes))
+    def _plan(self, again=False):
+        """Plans the next pass; again=True (set_state): the pass in force once more -- same number, same order, no line printed."""
+        if not again:
+            self.passes += 1
+            if self.sync is None or self.sync.rank == 0:
+                print("Opening file ({})".format(self.passes))
+            self._before_pass = self.ds.get_state()
         order = None
         if self.ts.shuffle:
-            random.shuffle(self.ts.order)
+            if not again:
+                random.shuffle(self.ts.order)
             order = np.asarray(self.ts.order, dtype=np.int32)
-            if self.sync is not None:       # rank 0's order of this pass
+            if self.sync is not None and not again:       # rank 0's order of this pass
                 order = self.sync.broadcast_array(order, order.shape, "int32")
                 self.ts.order = order.tolist()
         if self.noise is not None:      # this pass's noised copy of every sequence; the plan below sees its lengths
@@ -156,6 +164,42 @@ class NativeBatchBuilder(object):
         return b
 
     next = __next__
+
+    def get_state(self):
+        """Everything the batches still to come depend on, as a dict of plain values: seed, passes, cursor, built, the user order and
+        pass fraction of the training set, the --target_bias seed, and the dataset's state (DeviceDataset.get_state) as it was in
+        front of the pass in force -- the pass itself is planned again by set_state."""
+        return {"seed": int(self.seed), "passes": int(self.passes), "cursor": int(self.cursor), "built": int(self.built),
+                "order": [int(u) for u in self.ts.order], "epochs": float(self.ts.epochs), "tb_seed": self.tb_seed,
+                "batch_size": int(self.batch_size), "n_users": int(self.n_users), "dataset": self._before_pass}
+
+    def set_state(self, d):
+        """Stands where the builder that returned `d` stood: the next next() builds the batch it would have built.  The dataset's
+        state goes back to what it was in front of the pass in force and that pass is planned again -- its noise pass seeds from
+        seed + 7919 * passes and so repeats itself -- without its "Opening file" line.  ValueError, before anything changes, for
+        a state of another training set, batch size or target selection."""
+        if int(d["n_users"]) != self.n_users or int(d["batch_size"]) != self.batch_size or len(d["order"]) != len(self.ts.order):
+            raise ValueError("builder state of %d users in batches of %d: this builder has %d users, batches of %d"
+                             % (d["n_users"], d["batch_size"], self.n_users, self.batch_size))
+        if (d["tb_seed"] is None) != (self._target_bias is None):
+            raise ValueError("builder state %s --target_bias, this builder %s" % (("with" if d["tb_seed"] is not None else "without"),
+                                                                                 ("with" if self._target_bias is not None else "without")))
+        if sorted(d["order"]) != list(range(self.n_users)):
+            raise ValueError("builder state: the user order is no permutation")
+        if self._target_bias is not None:       # the seed the row planner draws from is the saved run's (this also empties the carried rows)
+            self.tb_seed = int(d["tb_seed"])
+            self.ds.set_target_bias(self._target_bias[0], self._target_bias[1], seed=self.tb_seed)
+        self.ds.set_state(d["dataset"])
+        self._before_pass = d["dataset"]
+        self.seed, self.passes, self.built = int(d["seed"]), int(d["passes"]), int(d["built"])
+        self.ts.order = [int(u) for u in d["order"]]
+        self.cursor, self.n_batches, self._frac = 0, 0, np.zeros(0)
+        if self.passes > 0:
+            self._plan(again=True)
+            if int(d["cursor"]) > self.n_batches:
+                raise ValueError("builder state: cursor %d in a pass of %d batches" % (d["cursor"], self.n_batches))
+            self.cursor = int(d["cursor"])
+        self.ts.epochs = float(d["epochs"])
 
     def close(self):
         self.ds.close()

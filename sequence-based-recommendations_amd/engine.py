@@ -85,7 +85,9 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_cluster_train_step_lagged", "sbr_cluster_last_ids",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
-           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks"]
+           "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks",
+           "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
+           "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load"]
 
 _lib = None
 
@@ -183,6 +185,11 @@ def load_library(path=None):
     lib.sbr_evaluate_ranks.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, vp]
     lib.sbr_cluster_evaluate.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SbrEvalOut),
                                          ctypes.POINTER(SbrEvalOut), vp, vp, vp]
+    szp = ctypes.POINTER(ctypes.c_size_t)
+    for stem in ("sbr_state", "sbr_cluster_state", "sbr_dataset_state"):
+        getattr(lib, stem + "_bytes").argtypes = [vp, szp]
+        getattr(lib, stem + "_save").argtypes = [vp, vp, ctypes.c_size_t, szp]
+        getattr(lib, stem + "_load").argtypes = [vp, vp, ctypes.c_size_t]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -233,6 +240,20 @@ def _eval_record(n, k, n_items, want_mask, want_ids):
             "item_hits": np.empty(n_items, np.int32),
             "hitmask": np.empty((n, (k + 31) // 32), np.uint32) if want_mask else None,
             "ids": np.empty((n, k), np.int32) if want_ids else None}
+
+
+def _state_get(check, lib, stem, obj):
+    """the blob of `obj` (bytes): <stem>_bytes for the size, <stem>_save into a buffer of that size (include/sbr_rnn.h "Training state")"""
+    n, w = ctypes.c_size_t(), ctypes.c_size_t()
+    check(getattr(lib, stem + "_bytes")(obj, ctypes.byref(n)))
+    buf = np.empty(n.value, dtype=np.uint8)
+    check(getattr(lib, stem + "_save")(obj, buf.ctypes.data, n.value, ctypes.byref(w)))
+    return buf[:w.value].tobytes()
+
+
+def _state_set(check, lib, stem, obj, blob):
+    buf = np.frombuffer(bytes(blob), dtype=np.uint8)
+    check(getattr(lib, stem + "_load")(obj, buf.ctypes.data if len(buf) else None, len(buf)))
 
 
 def mask_to_lengths(mask):
@@ -367,6 +388,15 @@ class DeviceDataset(object):
         self.engine._check(self.lib.sbr_dataset_plan_segments(self.d, ctypes.byref(n), *[ctypes.byref(p) for p in ptrs]))
         return np.stack([np.ctypeslib.as_array(p, shape=(n.value,)).copy() if n.value else np.zeros(0, np.int32)
                          for p in ptrs], axis=1)
+
+    def get_state(self):
+        """What makes the next plan_pass reproduce its plan, as bytes (sbr_dataset_state_save): the rows the last planned pass
+        carried over, the host row planner's pass counter, the batch size.  Not the sequences, tables and options."""
+        return _state_get(self.engine._check, self.lib, "sbr_dataset_state", self.d)
+
+    def set_state(self, blob):
+        """sbr_dataset_state_load: ValueError (nothing changed) for a blob of another dataset; plan the next pass afterwards."""
+        _state_set(self.engine._check, self.lib, "sbr_dataset_state", self.d, blob)
 
     def close(self):
         if getattr(self, "d", None):
@@ -594,6 +624,20 @@ class RNNEngine(object):
                 raise ValueError("mismatch: parameter has shape %r but value to set has shape %r" % (shp, a.shape))
             arrays.append(a)
         self._check(self.lib.sbr_set_params(self.h, len(arrays), self._ptr_array(arrays)))
+
+    def get_state(self):
+        """The whole training state of the engine as bytes (sbr_state_save): parameters, optimizer state, step count, the `last`
+        words of lazily stepped rows -- read without a flush, so the run goes on as if the call had not been made.  SbrError
+        (SBR_ESTATE) inside an open training step or with a lagged cost pending: flush_lagged() first."""
+        with self.torch.cuda.device(self.device):
+            return _state_get(self._check, self.lib, "sbr_state", self.h)
+
+    def set_state(self, blob):
+        """sbr_state_load: the engine stands at the step boundary the blob was taken at (no current batch, no gradients).  ValueError,
+        with the engine untouched, for a blob that is truncated, foreign, or of another architecture or updater.  The same blob
+        serves every data-parallel replica."""
+        with self.torch.cuda.device(self.device):
+            _state_set(self._check, self.lib, "sbr_state", self.h, blob)
 
     def _get(self, fn):
         arrays = [np.empty(shp, dtype=np.float32) for shp in self.param_shapes]
@@ -1039,6 +1083,19 @@ class ClusterHead(object):
 
     def set_scale(self, scale):
         self._check(self.lib.sbr_cluster_set_scale(self.h, float(scale)))
+
+    def get_state(self):
+        """The head's training state as bytes (sbr_cluster_state_save): R, Wc, their optimizer state, the step count, the noise
+        counter, the scale and the seed."""
+        with self.torch.cuda.device(self.engine.device):
+            return _state_get(self.engine._check, self.lib, "sbr_cluster_state", self.h)
+
+    def set_state(self, blob):
+        """sbr_cluster_state_load: ValueError (nothing changed) for a blob of another head; the hard clusters are dropped."""
+        with self.torch.cuda.device(self.engine.device):
+            _state_set(self.engine._check, self.lib, "sbr_cluster_state", self.h, blob)
+        self._hard = None
+        self._lists = None
 
     def forward_backward(self, targets, cluster_samples, read_cost=True):
         """cost_clusters and its gradients on the engine's CURRENT user representations (call after engine.forward / a step)."""

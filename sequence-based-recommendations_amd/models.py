@@ -286,7 +286,13 @@ class RNNBase(object):
 
     def train(self, dataset, max_time=np.inf, progress=2.0, time_based_progress=False, autosave="All", save_dir="",
               min_iterations=0, max_iter=np.inf, max_progress_interval=np.inf, load_last_model=False,
-              early_stopping=None, validation_metrics=("sps",)):
+              early_stopping=None, validation_metrics=("sps",), save_state=False, resume=False):
+        """save_state: at every validation point, behind that point's checkpoint logic (whatever `autosave` decided), the whole
+        training state goes to save_dir + _get_model_filename(round(epochs, 3)) + ".state" (save_state below) and the older state
+        files of this configuration go away: one run keeps one.  resume: the newest such file is loaded once the batch builder and
+        the stepper exist and the loop goes on where that run stood -- iterations, next validation point, histories, clock --, so
+        max_iter, min_iterations and the progress schedule count from the run's beginning; without a file the run starts from
+        scratch.  Both need device-built batches (ValueError otherwise)."""
         self.set_dataset(dataset)
         validation_metrics = list(validation_metrics)
         if len(set(validation_metrics) & set(self.metrics.keys())) < len(validation_metrics):
@@ -305,7 +311,11 @@ class RNNBase(object):
         rank0 = dp is None or dp.rank == 0
         if dp is not None and native is None:
             raise ValueError("data-parallel training runs on device-built batches only: " + str(self._native_batch_refusal(dataset)))
+        if (save_state or resume) and native is None:
+            raise ValueError("--save_state / --resume: the training state lives on device-built batches only: "
+                             + str(self._native_batch_refusal(dataset)))
         stepper = self._native_stepper(native)
+        self._builder, self._stepper = native, stepper      # what save_state / load_state read and restore beside the engine
         save = self.save if dp is None else (lambda f: self.save(f, write=rank0))
         shared_clock = ranks > 1 and (max_time != np.inf or time_based_progress)
         batch_generator = native if native is not None else self._gen_mini_batch(self.sequence_noise(dataset.training_set()))
@@ -318,6 +328,19 @@ class RNNBase(object):
         train_costs, current_train_cost, epochs = [], [], []
         metrics = {name: [] for name in self.metrics.keys()}
         filename = {}
+        if resume:
+            loop = self.load_last_state(save_dir)
+            if loop is not None:
+                iterations, next_save, epochs_offset = loop["iterations"], loop["next_save"], loop["epochs_offset"]
+                epochs, train_costs, current_train_cost = loop["epochs"], loop["train_costs"], loop["current_train_cost"]
+                metrics, filename = loop["metrics"], loop["filename"]
+                start_time = time() - loop["elapsed"]       # the clock goes on from the saved run's
+
+        def after(point):               # the validation point behind `point` (rnn_base.py:337-340)
+            if isinstance(progress, int):
+                return point + min(progress, max_progress_interval)
+            return point + min(max_progress_interval, point * (progress - 1))
+
         def take(cost):                 # rnn_base.py:290-293; with device batches the cost arrives one iteration late
             if cost is not None:
                 if np.isnan(cost):
@@ -361,13 +384,15 @@ class RNNBase(object):
                                     except OSError:
                                         print("Warning : Previous model could not be deleted")
                                     del filename[run]
+                        if save_state:      # every rank enters (a rank-synchronous point); rank 0 alone writes and removes
+                            self.save_state(save_dir + self._get_model_filename(round(epochs[-1], 3)) + ".state",
+                                            dict(iterations=iterations, next_save=after(next_save), epochs=epochs, epochs_offset=epochs_offset,
+                                                 train_costs=train_costs, current_train_cost=current_train_cost, metrics=metrics,
+                                                 filename=filename, elapsed=time() - start_time), write=rank0)
                         if early_stopping is not None:
                             if all([early_stopping(epochs, metrics[m]) for m in validation_metrics]):
                                 break
-                    if isinstance(progress, int):
-                        next_save += min(progress, max_progress_interval)
-                    else:
-                        next_save += min(max_progress_interval, next_save * (progress - 1))
+                    next_save = after(next_save)
         except KeyboardInterrupt:
             print("Training interrupted")
         if native is not None:
@@ -586,6 +611,102 @@ class RNNBase(object):
         with open(filename, "rb") as f:
             param = pickle.load(f, encoding="latin1")
         self.engine.set_all_param_values([np.asarray(i, dtype=np.float32) for i in param])
+
+    # ------------------------------------------------------------------ the whole training state (no counterpart in the reference)
+    STATE_MAGIC = b"SBR-TRAINING-STATE\n"
+    STATE_VERSION = 1
+
+    def _state_files(self, save_dir):
+        """the state files of this configuration in save_dir.  Their names end in ".state" behind a checkpoint's name, so the
+        checkpoint globs (load_last, python -m sbr_amd.test: the bare _get_model_filename pattern) never match one."""
+        return glob.glob(save_dir + self._get_model_filename("*") + ".state")
+
+    def _state_extra(self):
+        """what a subclass holds beside engine, builder, generators and loop (RNNCluster)"""
+        return {}
+
+    def _set_state_extra(self, extra):
+        pass
+
+    def save_state(self, path, loop, write=True):
+        """Everything a new process needs to go on bit for bit as this one would: the engine's state (RNNEngine.get_state: read
+        without a flush, the run is not disturbed), the batch builder's (NativeBatchBuilder.get_state), Python's and NumPy's
+        generators, the subclass's extras and `loop`, the training loop's own dictionary (iterations, next_save, epochs,
+        epochs_offset, train_costs, current_train_cost, metrics, filename, elapsed).  One file, written under a temporary name and
+        moved into place; the older state files of the configuration are removed behind it.  Needs the builder and stepper of a
+        train() call on device-built batches.  write=False (every data-parallel rank but 0): nothing to do."""
+        builder = getattr(self, "_builder", None)
+        if builder is None:
+            raise ValueError("save_state: no device batch builder (the training state lives on device-built batches only)")
+        if not write:       # nothing here is a collective, and the replicas hold rank 0's state: no copy is made that nobody keeps
+            return
+        state = {"version": self.STATE_VERSION, "config": self._get_model_filename("*"),
+                 "engine": self.engine.get_state(), "builder": builder.get_state(),
+                 "random": random.getstate(), "np_random": np.random.get_state(),
+                 "extra": self._state_extra(), "loop": loop}
+        d = os.path.dirname(path)
+        if d and not os.path.exists(d):
+            os.makedirs(d)
+        tmp = path + ".tmp%d" % os.getpid()
+        with open(tmp, "wb") as f:
+            f.write(self.STATE_MAGIC)
+            pickle.dump(state, f, protocol=4)
+        os.replace(tmp, path)
+        for old in self._state_files(path[:len(path) - len(os.path.basename(path))]):      # (save_dir as train() spelt it)
+            if os.path.abspath(old) != os.path.abspath(path):
+                try:
+                    os.remove(old)
+                except OSError:
+                    print("Warning : Previous state could not be deleted")
+
+    def _read_state(self, path):
+        try:
+            with open(path, "rb") as f:
+                if f.read(len(self.STATE_MAGIC)) != self.STATE_MAGIC:
+                    raise ValueError("%s is not a training state file" % path)
+                state = pickle.load(f)
+        except ValueError:
+            raise
+        except Exception as e:      # a truncated pickle: EOFError, UnpicklingError, ...
+            raise ValueError("%s is damaged: %s" % (path, e))
+        keys = ("version", "config", "engine", "builder", "random", "np_random", "extra", "loop")
+        if not isinstance(state, dict) or any(k not in state for k in keys):
+            raise ValueError("%s is not a training state file" % path)
+        if state["version"] != self.STATE_VERSION:
+            raise ValueError("%s has format version %r, this code reads %d" % (path, state["version"], self.STATE_VERSION))
+        if state["config"] != self._get_model_filename("*"):
+            raise ValueError("%s belongs to the configuration %s, this model is %s" % (path, state["config"], self._get_model_filename("*")))
+        return state
+
+    def load_state(self, path):
+        """Restores what save_state wrote and returns the loop dictionary.  ValueError before anything is restored: a truncated or
+        foreign file, another format version, another configuration (the _get_model_filename("*") string).  Every data-parallel
+        rank reads the same file, rank 0's: generators, seeds and order are then equal on all of them."""
+        builder = getattr(self, "_builder", None)
+        if builder is None:
+            raise ValueError("load_state: no device batch builder (the training state lives on device-built batches only)")
+        state = self._read_state(path)
+        self.engine.set_state(state["engine"])      # (validates its own blob before it writes)
+        builder.set_state(state["builder"])
+        self._set_state_extra(state["extra"])
+        random.setstate(state["random"])
+        np.random.set_state(state["np_random"])
+        return state["loop"]
+
+    def load_last_state(self, save_dir):
+        """train(resume=True): the newest state file of this configuration in save_dir -> its loop dictionary, or None with
+        load_last's line when there is none"""
+        def extract_number_of_epochs(filename):
+            m = re.search(r"_ne([0-9]+(\.[0-9]+)?)_", os.path.basename(filename))
+            return float(m.group(1))
+        files = self._state_files(save_dir)
+        if len(files) == 0:
+            print("No previous model, starting from scratch")
+            return None
+        last = max(files, key=lambda f: (extract_number_of_epochs(f), os.path.getmtime(f)))
+        if self.dp is None or self.dp.rank == 0:
+            print("Resuming from state " + last)
+        return self.load_state(last)
 
 
 class RNNOneHot(RNNBase):
@@ -860,6 +981,24 @@ class RNNCluster(RNNBase):
 
     def _native_stepper(self, builder):
         return _ClusterStepper(self, builder)
+
+    def _state_extra(self):
+        st = getattr(self, "_stepper", None)
+        return {"head": self.head.get_state(), "effective_scale": float(self.effective_scale),
+                "last_epoch": getattr(self, "_last_epoch", None),
+                "stepper": None if st is None else (int(st.seed), int(st.iteration))}
+
+    def _set_state_extra(self, extra):
+        self.head.set_state(extra["head"])           # (the scale as the head last took it travels in its blob)
+        self.effective_scale = np.float64(extra["effective_scale"])
+        if extra["last_epoch"] is None:
+            if hasattr(self, "_last_epoch"):
+                del self._last_epoch
+        else:
+            self._last_epoch = extra["last_epoch"]
+        if extra["stepper"] is not None and getattr(self, "_stepper", None) is not None:
+            self._stepper.seed, self._stepper.iteration = extra["stepper"]
+        self._drop_hard_clusters()
 
     # ------------------------------------------------------------------ the compiled-function seam
     def train_function(self, X, mask, target, samples, cluster_samples, exclude=None):

@@ -293,6 +293,11 @@ def training_command_parser(parser):                   # train.py:12-27
     parser.add_argument("--time_based_progress", help="Follow progress based on time rather than iterations.",
                         action="store_true")
     parser.add_argument("--load_last_model", help="Load Last model before starting training.", action="store_true")
+    parser.add_argument("--save_state", help="Write the whole training state (optimizer, batch builder, generators, loop) beside "
+                        "the checkpoints at every validation point, whatever --save says; one file per run.", action="store_true")
+    parser.add_argument("--resume", help="Continue from the newest state file of this configuration exactly where that run "
+                        "stood (--max_iter and --progress count from its beginning); without one, start from scratch.",
+                        action="store_true")
     parser.add_argument("--progress", help="Progress intervals", default="2.", type=str)
     parser.add_argument("--mpi", help="Max progress intervals", default=np.inf, type=float)
     parser.add_argument("--max_iter", help="Max number of iterations", default=np.inf, type=float)

@@ -99,6 +99,8 @@ def main(argv=None):
 
 
 def _train(predictor, dataset, args):
+    # --save_state / --resume (RNNBase.train): handed over only when asked for
+    state = {k: True for k in ("save_state", "resume") if getattr(args, k, False)}
     return predictor.train(dataset,
                            save_dir=dataset.dirname + "models/" + args.dir,
                            time_based_progress=args.time_based_progress,
@@ -110,7 +112,7 @@ def _train(predictor, dataset, args):
                            max_time=args.max_time,
                            early_stopping=get_early_stopper(args),
                            load_last_model=args.load_last_model,
-                           validation_metrics=args.metrics.split(","))
+                           validation_metrics=args.metrics.split(","), **state)
 
 
 if __name__ == "__main__":
