@@ -603,7 +603,7 @@ extern "C" int sbr_state_bytes(sbr_handle* h, size_t* bytes) {
 extern "C" int sbr_state_save(sbr_handle* h, void* blob, size_t cap, size_t* written) {
     CHECK_ARG(h && blob && written, "null argument");
     const Layout& y = h->lay;
-    if (h->step_open || h->train_fwd_open) { sbr_set_error("sbr_state_save: a training step is open (finish it with sbr_apply_update)"); return SBR_ESTATE; }
+    if (h->st.step_open || h->st.train_fwd_open) { sbr_set_error("sbr_state_save: a training step is open (finish it with sbr_apply_update)"); return SBR_ESTATE; }
     if (h->lag_pending >= 0) { sbr_set_error("sbr_state_save: a lagged cost is pending (collect it with sbr_lagged_flush)"); return SBR_ESTATE; }
     const size_t need = engine_state_bytes(y);
     CHECK_ARG(cap >= need, "sbr_state_save: the state takes %zu bytes, the buffer holds %zu", need, cap);
@@ -631,7 +631,7 @@ extern "C" int sbr_state_save(sbr_handle* h, void* blob, size_t cap, size_t* wri
 extern "C" int sbr_state_load(sbr_handle* h, const void* blob, size_t bytes) {
     CHECK_ARG(h, "null handle");
     const Layout& y = h->lay;
-    if (h->step_open || h->train_fwd_open) { sbr_set_error("sbr_state_load: a training step is open (finish it with sbr_apply_update)"); return SBR_ESTATE; }
+    if (h->st.step_open || h->st.train_fwd_open) { sbr_set_error("sbr_state_load: a training step is open (finish it with sbr_apply_update)"); return SBR_ESTATE; }
     // everything is checked before anything is written
     { const int rc = sbr_state_check_head(blob, bytes, SBR_STATE_ENGINE, "sbr_state_load"); if (rc != SBR_OK) return rc; }
     CHECK_ARG(bytes >= kEngineStateFixed, "sbr_state_load: a blob of %zu bytes is shorter than its fixed part (%zu)", bytes, kEngineStateFixed);
@@ -676,7 +676,7 @@ extern "C" int sbr_state_load(sbr_handle* h, const void* blob, size_t bytes) {
     h->step_count = steps;
     h->grads_clean = true;
     h->fwd_done = false; h->have_batch = false; h->bb_unread = false;
-    h->step_open = false; h->train_fwd_open = false;
+    step_reset(h);
     h->lag_pending = -1;
     if (h->bb_slow < 1) h->bb_slow = 1;             // the next build trusts no record made before the load
     return SBR_OK;
@@ -741,8 +741,8 @@ extern "C" int sbr_set_batch(sbr_handle* h, const int32_t* X, const int32_t* len
 
 extern "C" int sbr_zero_grads(sbr_handle* h) {
     CHECK_ARG(h, "null handle");
-    h->step_open = true;                          // a training step begins: sbr_forward may start its batch-only work
-    h->out_early = false; h->dh_slabs_n = 0;
+    step_reset(h);                                // nothing of the step before, however it ended, reaches this one
+    h->st.step_open = true;                       // a training step begins: sbr_forward may start its batch-only work
     if (!h->in_train_step && h->timing) {         // phase-by-phase step (data-parallel driver): this call opens the step
         h->ring_cur = h->ring_used % sbr_handle::kRing;
         mark(h, 0);
@@ -766,23 +766,25 @@ extern "C" int sbr_sparse_info(sbr_handle* h, int b, int64_t* n_rows, int64_t* r
     return SBR_OK;
 }
 
+// this rank's touched rows of block b, deduplicated, into ids_out / rows_out; their running count into *count (NULL: the block's a_count)
+static int sparse_pack_into(sbr_handle* h, int b, int* ids_out, float* rows_out, int* count) {
+    CHECK_ARG(b >= 0 && b < h->lay.n_sparse, "sparse block %d outside [0,%d)", b, h->lay.n_sparse);
+    const SparseBlockLayout& sb = h->lay.sparse[b];
+    if (!count) count = (int*)h->A(sb.a_count);
+    { const int rc = side_join(h); if (rc != SBR_OK) return rc; }      // the block's gradients come from both streams
+    const int epoch = ++h->sp_epoch;
+    const SbrSparseIds c = sparse_ids(h, b);
+    SBR_LAUNCH(launch_sparse_pack(h->stream, sparse_rows(h, b), c.list, c.n_dev, c.n_host, c.n_max, (int*)h->A(sb.a_mark), epoch, ids_out, rows_out,
+                                  sb.W, count));
+    h->st.sp_exchanged[b] = 1; h->st.sp_ncand[b] = 0;      // (a second pack of one step starts its candidate list again)
+    return SBR_OK;
+}
+
 extern "C" int sbr_sparse_pack(sbr_handle* h, int b, int32_t* ids_dev, float* rows_dev, int32_t* count_host) {
     CHECK_ARG(h && ids_dev && rows_dev && count_host, "null argument");
-    CHECK_ARG(b >= 0 && b < h->lay.n_sparse, "sparse block %d outside [0,%d)", b, h->lay.n_sparse);
-    const Layout& y = h->lay; const SparseBlockLayout& sb = y.sparse[b];
-    { const int rc = side_join(h); if (rc != SBR_OK) return rc; }      // the block's gradients come from both streams
-    int* count = (int*)h->A(sb.a_count);
-    const int epoch = ++h->sp_epoch;
-    if (sb.kind == 0) {
-        SBR_LAUNCH(launch_sparse_pack(h->stream, sparse_rows(h, b), sort_keys(h, 0).sid, sort_keys(h, 0).off + y.cfg.input_size, 0,
-                                      y.T * y.Bp * y.F, (int*)h->A(sb.a_mark), epoch, ids_dev, rows_dev, sb.W, count));
-    } else {
-        SBR_LAUNCH(launch_sparse_pack(h->stream, sparse_rows(h, b), (const int*)h->A(y.a_cells), nullptr, y.C, y.C, (int*)h->A(sb.a_mark), epoch,
-                                      ids_dev, rows_dev, sb.W, count));
-    }
-    SBR_HIP(hipMemcpyAsync(count_host, count, sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    { const int rc = sparse_pack_into(h, b, ids_dev, rows_dev, nullptr); if (rc != SBR_OK) return rc; }
+    SBR_HIP(hipMemcpyAsync(count_host, h->A(h->lay.sparse[b].a_count), sizeof(int), hipMemcpyDeviceToHost, h->stream));
     SBR_HIP(hipStreamSynchronize(h->stream));
-    h->sp_exchanged[b] = 1; h->sp_ncand[b] = 0;
     return SBR_OK;
 }
 
@@ -790,43 +792,30 @@ extern "C" int sbr_sparse_unpack_add(sbr_handle* h, int b, const int32_t* ids_de
     CHECK_ARG(h && (count == 0 || (ids_dev && rows_dev)), "null argument");
     CHECK_ARG(b >= 0 && b < h->lay.n_sparse, "sparse block %d outside [0,%d)", b, h->lay.n_sparse);
     const SparseBlockLayout& sb = h->lay.sparse[b];
-    if (!h->sp_exchanged[b]) { sbr_set_error("sbr_sparse_unpack_add: call sbr_sparse_pack for this step first"); return SBR_ESTATE; }
-    CHECK_ARG(count >= 0 && h->sp_ncand[b] + count <= sb.cand_cap, "%d + %d rows exceed the candidate capacity %d", h->sp_ncand[b], count, sb.cand_cap);
-    SBR_LAUNCH(launch_sparse_unpack_add(h->stream, sparse_rows(h, b), ids_dev, rows_dev, count, sb.W, (int*)h->A(sb.a_cand) + h->sp_ncand[b]));
-    h->sp_ncand[b] += count;
+    if (!h->st.sp_exchanged[b]) { sbr_set_error("sbr_sparse_unpack_add: call sbr_sparse_pack for this step first"); return SBR_ESTATE; }
+    CHECK_ARG(count >= 0 && h->st.sp_ncand[b] + count <= sb.cand_cap, "%d + %d rows exceed the candidate capacity %d", h->st.sp_ncand[b], count, sb.cand_cap);
+    SBR_LAUNCH(launch_sparse_unpack_add(h->stream, sparse_rows(h, b), ids_dev, rows_dev, count, sb.W, (int*)h->A(sb.a_cand) + h->st.sp_ncand[b]));
+    h->st.sp_ncand[b] += count;
     h->grads_clean = false;
     return SBR_OK;
 }
 
 extern "C" int sbr_sparse_pack_device(sbr_handle* h, int b, int32_t* ids_dev, float* rows_dev) {
     CHECK_ARG(h && ids_dev && rows_dev, "null argument");
-    CHECK_ARG(b >= 0 && b < h->lay.n_sparse, "sparse block %d outside [0,%d)", b, h->lay.n_sparse);
-    const Layout& y = h->lay; const SparseBlockLayout& sb = y.sparse[b];
-    { const int rc = side_join(h); if (rc != SBR_OK) return rc; }      // the block's gradients come from both streams
-    const int epoch = ++h->sp_epoch;
-    // the running count of the pack kernel IS the in-band word ids_dev[0]
-    if (sb.kind == 0) {
-        SBR_LAUNCH(launch_sparse_pack(h->stream, sparse_rows(h, b), sort_keys(h, 0).sid, sort_keys(h, 0).off + y.cfg.input_size, 0,
-                                      y.T * y.Bp * y.F, (int*)h->A(sb.a_mark), epoch, ids_dev + 1, rows_dev, sb.W, ids_dev));
-    } else {
-        SBR_LAUNCH(launch_sparse_pack(h->stream, sparse_rows(h, b), (const int*)h->A(y.a_cells), nullptr, y.C, y.C, (int*)h->A(sb.a_mark), epoch,
-                                      ids_dev + 1, rows_dev, sb.W, ids_dev));
-    }
-    h->sp_exchanged[b] = 1; h->sp_ncand[b] = 0;
-    return SBR_OK;
+    return sparse_pack_into(h, b, ids_dev + 1, rows_dev, ids_dev);      // the running count of the pack kernel IS the in-band word ids_dev[0]
 }
 
 extern "C" int sbr_sparse_unpack_add_all(sbr_handle* h, int b, const int32_t* ids_all, const float* rows_all, int world) {
     CHECK_ARG(h && ids_all && rows_all, "null argument");
     CHECK_ARG(b >= 0 && b < h->lay.n_sparse, "sparse block %d outside [0,%d)", b, h->lay.n_sparse);
     const SparseBlockLayout& sb = h->lay.sparse[b];
-    if (!h->sp_exchanged[b]) { sbr_set_error("sbr_sparse_unpack_add_all: call sbr_sparse_pack_device for this step first"); return SBR_ESTATE; }
+    if (!h->st.sp_exchanged[b]) { sbr_set_error("sbr_sparse_unpack_add_all: call sbr_sparse_pack_device for this step first"); return SBR_ESTATE; }
     const int cap = sb.max_local;
-    CHECK_ARG(world >= 1 && h->sp_ncand[b] == 0 && (long)world * cap <= sb.cand_cap, "%d ranks x %d rows exceed the candidate capacity %d", world, cap, sb.cand_cap);
+    CHECK_ARG(world >= 1 && h->st.sp_ncand[b] == 0 && (long)world * cap <= sb.cand_cap, "%d ranks x %d rows exceed the candidate capacity %d", world, cap, sb.cand_cap);
     for (int r = 0; r < world; ++r)      // rank order, one stream: every replica adds in the same order
         SBR_LAUNCH(launch_sparse_unpack_add_dev(h->stream, sparse_rows(h, b), ids_all + (size_t)r * (cap + 1), rows_all + (size_t)r * cap * sb.W,
                                                 cap, sb.W, (int*)h->A(sb.a_cand) + (size_t)r * cap));
-    h->sp_ncand[b] = world * cap;          // slots beyond a rank's count hold -1 (skipped by the row-sparse step)
+    h->st.sp_ncand[b] = world * cap;          // slots beyond a rank's count hold -1 (skipped by the row-sparse step)
     h->grads_clean = false;
     return SBR_OK;
 }

@@ -768,7 +768,7 @@ extern "C" int sbr_build_batch(sbr_handle* h, sbr_dataset* d, int64_t batch, uin
     // The dataset's own arrays change only inside calls that synchronise d->stream first and last, i.e. behind (3).
     hipStream_t s = h->s_bb;
     const int set = h->bb_set ^ 1;
-    if (h->train_fwd_open) h->bb_slow = 2;
+    step_abandoned_check(h);      // (a build between the phases of an open step, or behind a step left half way)
     if (h->bb_unread && h->bb_slow == 0) h->bb_slow = 1;      // two builds and no forward between them: whoever read the first did it outside a step
     if (h->bb_slow == 0 && h->ev_step_rec && h->lg_seq > h->set_use[set]) {
         SBR_HIP(hipStreamWaitEvent(s, h->ev_step_rec, 0));

@@ -270,6 +270,37 @@ struct RecPlan {
     size_t fwd_lds, bwd_lds; int bwd_dbuf;   // REC_X6S / REC_X6 / REC_MFMA: dynamic LDS of the launch, the backward's double buffer
 };
 
+// What means something only between the opening of a step (sbr_zero_grads) and its sbr_apply_update, or between an inference forward
+// and its read-out; grouped by the phase that writes it.  step_reset (below sbr_handle) value-initialises all of it where a step can
+// begin, so nothing of one step -- finished, failed or left half way -- reaches the next.
+struct StepState {
+    // sbr_zero_grads, sbr_forward
+    bool step_open = false;      // sbr_zero_grads has opened a training step (cleared by sbr_forward)
+    bool train_fwd_open = false;    // a training forward whose step has not reached sbr_apply_update
+    int tail_nc = 0;                    // this step: tail_chunks for a training step, 0 (plain keys) for any other forward
+    bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
+    bool cells_early = false;    // this step: cells built + their rows caught up on the side stream by sbr_forward (ev_cells)
+    bool fork_gated = false;              // this step: the second side stream was released by the start word (sbr_forward)
+    unsigned marks_shared = 0;   // marks of this step already recorded as a cross-stream event (record_shared)
+    // sbr_loss_backward_output
+    bool fill_done = false;      // the cluster BPTT sentinel fill of this step was issued on the side stream (ev_fill)
+    bool tail_gated = false;     // this step: the side stream is already behind a gate on this step's epoch (sbr_loss_backward_output)
+    hipEvent_t ev_lg_rec = nullptr; // this step: the main-stream record that released the side stream (sbr_loss_backward_output); one of the handle's events (read by side_batch_work, in the same phase: sbr_build_batch reads the handle's ev_step_rec)
+    int dh_slabs_n = 0;          // > 0: dh_last of this step sits in the main workspace as that many unreduced split-K slabs
+    bool og_recorded = false;    // ev_og marks the output-layer gradients of this step complete
+    // data-parallel exchange (sbr_sparse_pack*, sbr_sparse_unpack_add*)
+    int sp_exchanged[2] = {0, 0}; // data-parallel step: rows of block b were packed / gathered (candidates = a_cand[0 .. sp_ncand[b]))
+    int sp_ncand[2] = {0, 0};
+    // Ranges of the parameter section that are already stepped, or whose step is already placed: written by the loss phase and
+    // sbr_backward_recurrent, read by sbr_apply_update -- which, of the groups above, takes og_recorded and the exchange's lists only
+    bool out_stepped = false;    // this step: done, the output layer's range needs no update launch
+    bool out_early = false;      // this step's output-layer parameters were stepped on the side stream beside the BPTT chain
+    bool wout_early = false;     // this step: the sampled head's rows were stepped beside the BPTT chain
+    bool tail_updated = false;   // this step: the overlapped tail has applied the optimizer itself (single-call step)
+    bool tail_swapped = false;   // this step: after the BPTT chain the main stream kept dW_hid, the side stream took the scatter (sbr_apply_update splits its ranges accordingly)
+    bool rows_stepped[2] = {false, false};   // this step: block b's row step already ran in front of the join (update_sparse)
+};
+
 struct sbr_handle {
     Layout lay;
     SbrSwitches sw;
@@ -284,30 +315,41 @@ struct sbr_handle {
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     hipEvent_t ev_sort = nullptr, ev_lg = nullptr, ev_fill = nullptr, ev_og = nullptr, ev_chunk[SBR_BWD_CHUNKS] = {};
     hipEvent_t ev_cells = nullptr, ev_tail = nullptr, ev_tail2 = nullptr, ev_bb = nullptr, ev_bbw = nullptr;
-    bool in_train_step = false;  // phases called from sbr_train_step: the side stream joins only before the update
+    StepState st;                // this step: see above; everything below outlives it
+    // call scope and stream state that outlives the step: a step left half way is joined by whoever comes next (side_join)
+    bool in_train_step = false;  // phases called from sbr_train_step (set and cleared by that call's own scope): the side stream joins only before the update
     bool side_pending = false;   // side-stream work issued and not yet joined by the main stream
     bool deferred_join = false;  // phases called one by one do not join the side stream (sbr_set_deferred_join)
-    bool og_recorded = false;    // ev_og marks the output-layer gradients of this step complete
-    bool fill_done = false;      // the cluster BPTT sentinel fill of this step was issued on the side stream (ev_fill)
-    bool out_early = false;      // this step's output-layer parameters were stepped on the side stream beside the BPTT chain
-    bool cells_early = false;    // this step: cells built + their rows caught up on the side stream by sbr_forward (ev_cells)
-    bool wout_early = false;     // this step: the sampled head's rows were stepped beside the BPTT chain
-    unsigned head_epoch = 0;
-    bool out_stepped = false;    // this step: done, the output layer's range needs no update launch
-    int dh_slabs_n = 0;          // > 0: dh_last of this step sits in the main workspace as that many unreduced split-K slabs
+    bool tail_join_pending = false; // overlapped tail of a phase-by-phase step: the main stream has not joined the consumer streams yet
+    // epochs: each word they stamp must differ from what ANY earlier launch left, so they only ever advance
+    unsigned head_epoch = 0; int cl_epoch = 0, sp_epoch = 0;   // the one-launch head's, the cluster exchange's, the pack epoch
+    int prog_epoch = 0;          // epoch of the chain's progress words: advanced once per step by tail_next_epoch (sbr_step.hip)
+    int join_epoch = 0, fork_epoch = 0;   // epochs of the completion words / the start word: advanced by step_next_epoch (sbr_step.hip), never 0
+    // engine-constant: plans, switches and buffers made by sbr_create or on first use
     std::vector<ParamDesc> descs;
     int rpt = 16;                // rows per workgroup for the bf16x6 recurrent kernels (SbrSwitches.rpt, or chosen by the batch size)
-    int cl_epoch = 0;
-    int sp_exchanged[2] = {0, 0}; // data-parallel step: rows of block b were packed / gathered (candidates = a_cand[0 .. sp_ncand[b]))
-    int sp_ncand[2] = {0, 0};
-    int sp_epoch = 0;            // pack epoch
+    bool timing = false; unsigned timing_marks = 0;   // which of the SBR_N_PHASES event marks a step records (sbr_enable_timing)
+    int tail_chunks = 0, tail_ch = 0;   // the overlapped tail as sbr_create planned it (plan_tail): time chunks of the sort's keys (0: not taken), steps per chunk
+    SbrTChunks tail_bounds = {};        // ... and their bounds
+    unsigned long long* tail_trace = nullptr;    // SbrSwitches.tail_trace: SbrPoll.trace
+    int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
+    std::vector<int> tail_slab_host; int* tail_slab_dev = nullptr; int tail_slab_key[2] = {0, 0};   // the table of the last plan
+    // Words of the step boundary (kStepJoinGate / kStepForkGate): an allocation of its own, made and zeroed on first use and freed by
+    // sbr_destroy; each word on a 128-byte line of its own.  [32]: completion word of the side stream, [96]: of the second side
+    // stream, [128]: the forward chain's start word.
+    int* step_words = nullptr;
+    // the lagged cost report: read one call later
     float* lag_host = nullptr;   // pinned: [2] cost, [2] fault flag, [2] sequence number (sbr_train_step_lagged: lag_report_kernel)
     unsigned lag_seq[2] = {0, 0}, lag_counter = 0;
     int lag_slot = 0, lag_pending = -1;
     // current batch: the arena's own buffers, or (device-resident inputs covering all Bp rows) the caller's
     const int *bX = nullptr, *blen = nullptr, *btgt = nullptr, *bsmp = nullptr; const float* bpop = nullptr;
-    // sbr_build_batch beside the step in flight (sbr_batch.hip): its own stream, the set the current batch sits in, and what
-    // tells it that the set it is about to overwrite is no longer read
+    int n_rows = 0;          // rows of the current batch (<= local_batch)
+    bool have_batch = false, fwd_done = false;   // (fwd_done: ranking and evaluation read the hidden state long after the forward)
+    int64_t step_count = 0;  // adam t
+    bool grads_clean = false;    // the gradient section is all zero (fresh arena, or the update kernel cleared it)
+    // The hand-over to sbr_build_batch beside the step in flight (sbr_batch.hip), read by a build AFTER the step's calls have returned: its
+    // own stream, the set the current batch sits in, and what tells it that the set it is about to overwrite is no longer read
 #ifndef SBR_BB_STREAM
 #define SBR_BB_STREAM 0      // (probe builds: 1 = a stream of its own, 2 = ... at low priority)
 #endif
@@ -315,47 +357,20 @@ struct sbr_handle {
     int bb_set = 0;             // arena set of the current batch (0: also what sbr_set_batch fills)
     uint64_t batch_seq = 0;     // sbr_forward calls so far
     uint64_t set_use[2] = {0, 0};   // batch_seq of the last forward that read set i
-    uint64_t lg_seq = 0;        // batch_seq when ev_lg_rec was last recorded (a main-stream record in the middle of a training step)
+    uint64_t lg_seq = 0;        // batch_seq when ev_step_rec was last set (a main-stream record in the middle of a training step)
     bool bb_unread = false;     // the current batch was built and no forward has read it yet
-    bool train_fwd_open = false;    // a training forward whose step has not reached sbr_apply_update
     int bb_slow = 0;            // builds left that wait for all of the engine's streams (a step was abandoned: its side streams were not joined)
-    int n_rows = 0;          // rows of the current batch (<= local_batch)
-    int64_t step_count = 0;  // adam t
-    bool have_batch = false, fwd_done = false;
-    bool grads_clean = false;    // the gradient section is all zero (fresh arena, or the update kernel cleared it)
-    bool timing = false;
-    unsigned timing_marks = 0;   // which of the SBR_N_PHASES event marks a step records (sbr_enable_timing)
-    int tail_chunks = 0, tail_ch = 0;   // the overlapped tail as sbr_create planned it (plan_tail): time chunks of the sort's keys (0: not taken), steps per chunk
-    SbrTChunks tail_bounds = {};        // ... and their bounds
-    int tail_nc = 0;                    // this step: tail_chunks for a training step, 0 (plain keys) for any other forward
-    unsigned long long* tail_trace = nullptr;    // SbrSwitches.tail_trace: SbrPoll.trace
-    bool tail_sorted = false;    // this step: the sort already ran (sbr_forward)
+    int step_word_epoch = 0;     // != 0: the forward chain of the step in flight publishes this epoch in its start word (sbr_build_batch waits for it
+                                 // where it waited for ev_step_rec)
+    hipEvent_t ev_step_rec = nullptr; // a main-stream record made DURING the step in flight, for sbr_build_batch: StepState.ev_lg_rec, or the forward's fork
+    // what the last call ran, for sbr_query: read at any time
     // sbr_rank: scratch outside the arena (grown on demand, freed by sbr_destroy) and what the last call ran (sbr_query "rank_select" / "rank_sort")
     void* rank_scratch = nullptr; size_t rank_scratch_bytes = 0; int last_rank_select = 0, last_rank_sort = 0;
     int last_goal_rank_form = 0;                                          // sbr_evaluate_ranks: 0 none yet, 1 the row's keys in LDS, 2 streamed
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
-    int scnt_zero_n = 0;                                                  // leading counters of a_scnt known to be zero (launch_scatter_sort)
-    std::vector<int> tail_slab_host; int* tail_slab_dev = nullptr; int tail_slab_key[2] = {0, 0};   // the table of the last plan
-    int prog_epoch = 0;          // epoch of the chain's progress words: advanced once per step by tail_next_epoch (sbr_step.hip)
-    bool tail_gated = false;     // this step: the side stream is already behind a gate on this step's epoch (sbr_loss_backward_output)
-    // Words of the step boundary (kStepJoinGate / kStepForkGate): an allocation of its own, made and zeroed on first use and freed by
-    // sbr_destroy; each word on a 128-byte line of its own.  [32]: completion word of the side stream, [96]: of the second side
-    // stream, [128]: the forward chain's start word.
-    int* step_words = nullptr;
-    int join_epoch = 0, fork_epoch = 0;   // epochs of the completion words / the start word: advanced by step_next_epoch (sbr_step.hip), never 0
-    bool fork_gated = false;              // this step: the second side stream was released by the start word (sbr_forward)
     int last_join_gate = -1, last_fork_gate = -1;                         // what the last step took: sbr_query "step_join_gate" / "step_fork_gate"
-    int step_word_epoch = 0;     // != 0: the forward chain of the step in flight publishes this epoch in its start word (sbr_build_batch waits for it
-                                 // where it waited for ev_step_rec)
-    hipEvent_t ev_step_rec = nullptr; // a main-stream record made DURING the step in flight, for sbr_build_batch: ev_lg_rec, or the forward's fork
-    bool tail_updated = false;   // this step: the overlapped tail has applied the optimizer itself (single-call step)
-    bool tail_join_pending = false; // overlapped tail of a phase-by-phase step: the main stream has not joined the consumer streams yet
-    bool step_open = false;      // sbr_zero_grads has opened a training step (cleared by sbr_forward)
-    hipEvent_t ev_lg_rec = nullptr; // this step: the main-stream record that released the side stream (sbr_loss_backward_output); one of the events above
-    bool tail_swapped = false;   // this step: after the BPTT chain the main stream kept dW_hid, the side stream took the scatter (sbr_apply_update splits its ranges accordingly)
-    unsigned marks_shared = 0;   // marks of this step already recorded as a cross-stream event (record_shared)
     // ring of per-step event sets, read back after the timed region (no per-step sync)
     static const int kRing = 64;
     hipEvent_t ev[kRing][SBR_N_PHASES] = {};
@@ -373,6 +388,12 @@ struct sbr_handle {
     float* A(size_t off) const { return arena + lay.s_act + off; }
     float* cost_ptr() const { return arena + lay.s_grads + lay.n_params; }
 };
+// A training forward still open where a step begins (step_reset) or a batch is built (sbr_build_batch) will not reach its
+// sbr_apply_update, or has not yet: its side streams are not joined, so the next two batch builds wait for every stream.
+static inline void step_abandoned_check(sbr_handle* h) { if (h->st.train_fwd_open) h->bb_slow = 2; }
+// The one reset of the per-step state, which looks before it clears.  Called where a step can begin, ends or is discarded: sbr_zero_grads,
+// sbr_forward when no step is open (predict, top-k, rank, evaluate), the end of sbr_apply_update, sbr_state_load.
+static inline void step_reset(sbr_handle* h) { step_abandoned_check(h); h->st = StepState{}; }
 
 // The cluster head (sbr_cluster.hip; include/sbr_rnn.h "The cluster head of RNNCluster")
 struct sbr_cluster {
@@ -432,6 +453,10 @@ bool head_sampled_taken(const sbr_handle* h, int rows);   // does a step over `r
 void mark(sbr_handle* h, int i);                     // timing mark i of the step in flight, on the main stream
 SbrSparseRows sparse_rows(sbr_handle* h, int b);     // row-sparse block b: where its rows, gradients, state and last-step words are
 SbrSparseUpd sparse_upd(sbr_handle* h);              // ... and the optimizer's constants for the row kernels
+// ... and the ids its own step walks (list, n_dev, n_host, n_max of the launch_sparse_* list kernels).  kind 0: the plain-key sort's
+// ids, counted on the device by the sort's last offset; kind 1: the C sampled cells
+struct SbrSparseIds { const int* list; const int* n_dev; int n_host, n_max; };
+SbrSparseIds sparse_ids(const sbr_handle* h, int b);
 int side_join(sbr_handle* h);                        // the main stream joins whatever the step left pending on the side streams
 // adagrad's zero-gradient step is a no-op: nothing is ever pending
 static inline bool sparse_lazy(const sbr_handle* h) { return h->lay.n_sparse > 0 && h->lay.cfg.updater != SBR_UPD_ADAGRAD; }

@@ -156,9 +156,9 @@ static inline int sort_entries(const Layout& y) { return y.T * y.Bp * y.F; }
 static int tail_sort(sbr_handle* h) {
     const Layout& y = h->lay; const SbrSortKeys k = sort_keys(h, 0);
     SBR_LAUNCH(launch_scatter_sort(h->side2, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, k.cnt, k.off, k.cur, k.sid, k.pos, 0,
-                                   h->tail_ch, h->tail_nc, &h->tail_bounds, &h->scnt_zero_n));
+                                   h->tail_ch, h->st.tail_nc, &h->tail_bounds, &h->scnt_zero_n));
     if (h->scat.tail == SCAT_LDS)
-        SBR_LAUNCH(launch_scatter_cost_scan(h->side2, k.off, (int*)h->A(y.a_sP), y.cfg.input_size, h->tail_nc, h->scat));
+        SBR_LAUNCH(launch_scatter_cost_scan(h->side2, k.off, (int*)h->A(y.a_sP), y.cfg.input_size, h->st.tail_nc, h->scat));
     return SBR_OK;
 }
 
@@ -178,8 +178,7 @@ static inline void chain_mark(sbr_handle* h, hipStream_t st, int dir, int which)
 // is timing mark i of the step in flight recorded?
 static inline bool mark_live(const sbr_handle* h, int i) { return h->timing && ((h->timing_marks >> i) & 1) && h->ev[h->ring_cur][i]; }
 static inline void mark_on(sbr_handle* h, int i, hipStream_t st) {
-    if (i == 0) h->marks_shared = 0;
-    if ((h->marks_shared >> i) & 1) return;              // this step's mark i was recorded by record_shared
+    if ((h->st.marks_shared >> i) & 1) return;              // this step's mark i was recorded by record_shared
     if (mark_live(h, i)) (void)hipEventRecord(h->ev[h->ring_cur][i], st);
 }
 void mark(sbr_handle* h, int i) { mark_on(h, i, h->stream); }
@@ -189,7 +188,7 @@ void mark(sbr_handle* h, int i) { mark_on(h, i, h->stream); }
 static inline hipEvent_t record_shared(sbr_handle* h, hipEvent_t plain, int mk) {
     if (mk >= 0 && mark_live(h, mk)) {
         (void)hipEventRecord(h->ev[h->ring_cur][mk], h->stream);
-        h->marks_shared |= 1u << mk;
+        h->st.marks_shared |= 1u << mk;
         return h->ev[h->ring_cur][mk];
     }
     (void)hipEventRecord(plain, h->stream);
@@ -247,15 +246,18 @@ static int sparse_out_block(const Layout& y) {
     for (int b = 0; b < y.n_sparse; ++b) if (y.sparse[b].kind == 1) kb = b;
     return kb;
 }
-// this step's row step of block b over a host-counted list of ids (the sampled cells, the gathered candidates)
-static hipError_t step_rows_listed(sbr_handle* h, hipStream_t st, int b, const int* list, int n) {
-    return launch_sparse_step_list(st, sparse_rows(h, b), sparse_upd(h), list, nullptr, n, n, (int)step_no(h));
-}
-// ... over the ids the scatter-add's plain-key sort left (their count is the sort's last offset)
-static hipError_t step_rows_scattered(sbr_handle* h, int b) {
+SbrSparseIds sparse_ids(const sbr_handle* h, int b) {
     const Layout& y = h->lay; const SbrSortKeys k = sort_keys(h, 0);
-    return launch_sparse_step_list(h->stream, sparse_rows(h, b), sparse_upd(h), k.sid, k.off + y.cfg.input_size, 0, sort_entries(y),
-                                   (int)step_no(h));
+    if (y.sparse[b].kind == 0) return {k.sid, k.off + y.cfg.input_size, 0, sort_entries(y)};
+    return {(const int*)h->A(y.a_cells), nullptr, y.C, y.C};
+}
+// this step's row step of block b over the ids in `c`: its own (sparse_ids), or the candidates gathered from every rank
+static hipError_t step_rows(sbr_handle* h, hipStream_t st, int b, const SbrSparseIds& c) {
+    return launch_sparse_step_list(st, sparse_rows(h, b), sparse_upd(h), c.list, c.n_dev, c.n_host, c.n_max, (int)step_no(h));
+}
+// block b's rows among `c` current through the last applied step, before the step reads them
+static hipError_t catch_up_rows(sbr_handle* h, hipStream_t st, int b, const SbrSparseIds& c) {
+    return launch_sparse_catch_up_list(st, sparse_rows(h, b), sparse_upd(h), c.list, c.n_dev, c.n_host, c.n_max, (int)h->step_count);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -369,11 +371,10 @@ static int early_cells(sbr_handle* h, bool* forked) {
     if (kb < 0) return SBR_OK;
     SBR_HIP(hipEventRecord(h->ev_fork, h->stream)); *forked = true;      // (device-resident batches are produced on the main stream)
     SBR_HIP(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-    int* cells = (int*)h->A(y.a_cells);
-    SBR_LAUNCH(launch_build_cells(h->side, h->btgt, h->bsmp, y.Bg, y.S, cells));
-    SBR_LAUNCH(launch_sparse_catch_up_list(h->side, sparse_rows(h, kb), sparse_upd(h), cells, nullptr, y.C, y.C, (int)h->step_count));
+    SBR_LAUNCH(launch_build_cells(h->side, h->btgt, h->bsmp, y.Bg, y.S, (int*)h->A(y.a_cells)));
+    SBR_LAUNCH(catch_up_rows(h, h->side, kb, sparse_ids(h, kb)));
     SBR_HIP(hipEventRecord(h->ev_cells, h->side));
-    h->cells_early = true;
+    h->st.cells_early = true;
     h->side_pending = true;      // (parameters, optimizer state and last[] were written over there: a step abandoned behind
                                  // sbr_forward -- an error return, a ranking, an export -- joins before it reads them)
     return SBR_OK;
@@ -381,7 +382,7 @@ static int early_cells(sbr_handle* h, bool* forked) {
 // the overlapped tail's sort beside the forward chain
 static int early_sort(sbr_handle* h) {
     const int rc = tail_sort(h);
-    h->tail_sorted = true;
+    h->st.tail_sorted = true;
     return rc;
 }
 
@@ -401,11 +402,11 @@ static int forward_uni(sbr_handle* h, bool fork_gate) {
             layer_gemm_hint(h, false, false);
             SBR_LAUNCH(input_projection(h, ly, h->A(lo.a_hs) + (size_t)y.Bp * lo.Hp));
         }
-        if (l == 0 && (h->tail_sorted || fork_gate)) ra.fence_kb = kTailFenceKb;
+        if (l == 0 && (h->st.tail_sorted || fork_gate)) ra.fence_kb = kTailFenceKb;
         if (fork_gate) { ra.start_word = h->step_words + 128; ra.start_epoch = step_next_epoch(&h->fork_epoch); }
         SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, h->plan[l]));
         if (fork_gate) {
-            h->fork_gated = true; h->step_word_epoch = h->fork_epoch;
+            h->st.fork_gated = true; h->step_word_epoch = h->fork_epoch;
             SBR_LAUNCH(launch_step_gate(h->side2, h->step_words + 128, nullptr, h->fork_epoch, (int*)h->A(y.a_fault)));
             { const int rc = early_sort(h); if (rc != SBR_OK) return rc; }
         }
@@ -458,15 +459,12 @@ extern "C" int sbr_forward(sbr_handle* h) {
         for (int b = 0; b < y.n_sparse; ++b)
             if (y.sparse[b].kind == 0)
                 SBR_LAUNCH(launch_sparse_catch_up_batch(s, sparse_rows(h, b), sparse_upd(h), h->bX, h->blen, y.T, y.Bp, y.F, (int)h->step_count));
-    h->tail_nc = h->step_open ? h->tail_chunks : 0;      // overlapped tail for this step? (never for predict / top-k)
-    const bool training = h->step_open;
-    h->step_open = false;
-    h->tail_sorted = false;
+    const bool training = h->st.step_open;
+    if (!training) step_reset(h);      // predict, top-k, rank, evaluate (never with the overlapped tail): whatever step was open is discarded
+    else { h->st.step_open = false; h->st.tail_nc = h->tail_chunks; h->st.train_fwd_open = true; }      // (step_open: sbr_zero_grads' hand-over, consumed -- a second forward of the step is no training forward)
     // (sbr_build_batch fills the batch set this forward does not read while the step runs: what it needs to know to do that safely)
     h->set_use[h->bb_set] = ++h->batch_seq; h->bb_unread = false;
-    if (training) { if (h->train_fwd_open) h->bb_slow = 2; h->train_fwd_open = true; }
     bool forked = false;
-    h->cells_early = false;
     if (training) { const int rc = early_cells(h, &forked); if (rc != SBR_OK) return rc; }
     // Overlapped tail, round 3.  Its consumers are throughput-bound once they have the chip's other 192 CUs to themselves (the
     // fence below), so WHEN they start decides when the step ends -- and both waited behind work that does not need the chain:
@@ -478,8 +476,8 @@ extern "C" int sbr_forward(sbr_handle* h) {
     // where the record / wait pair stood -- a word of this epoch means that everything in front of the chain on the main stream is
     // complete and written back, the batch included.  The chain is launched FIRST: a gate is only ever enqueued behind the kernel
     // that releases it, so a forward launch that fails leaves no gate waiting.  
-    h->fork_gated = false; h->step_word_epoch = 0;
-    const bool sort_early = h->tail_nc >= 2 && h->sw.tail_overlap == 1;
+    h->step_word_epoch = 0;
+    const bool sort_early = h->st.tail_nc >= 2 && h->sw.tail_overlap == 1;
     const bool fork_gate = kStepForkGate && sort_early && h->in_train_step && y.L == 1 && y.D == 1 && !forked && !step_boundary_marks(h) &&
                            h->plan[0].fwd == REC_X6P;
     if (sort_early && !fork_gate) {
@@ -512,17 +510,17 @@ static int side_batch_work(sbr_handle* h, bool fill_needed) {
     if (fill_needed) {
         for (int l = 0; l < y.L * y.D; ++l)
             if (h->plan[l].needs_fill) SBR_LAUNCH(sbr_rec_bwd_cl_fill(sd, rec_args(h, l), h->plan[l].bwd == REC_C16));
-        SBR_HIP(hipEventRecord(h->ev_fill, sd)); h->fill_done = true;
+        SBR_HIP(hipEventRecord(h->ev_fill, sd)); h->st.fill_done = true;
     }
     // (round 6, call s3: the sort BEHIND the head's record instead of beside the head lets the one-launch sampled head run in 26 us
     // instead of 24 .. 72 by workgroup -- the sort's counting kernels are all atomics -- but beside the BPTT chain it costs the chain
     // more: rec_bwd_c16 375 -> 441 us at C3, 390 -> 404 at C4.  It stays here.)
-    if (h->tail_nc >= 2) {
+    if (h->st.tail_nc >= 2) {
         // overlapped tail: the time-chunked sort runs on the SECOND side stream, which consumes it (scatter-add beside the
         // chain); that stream is released by the same record as the first one
-        if (h->ev_lg_rec) SBR_HIP(hipStreamWaitEvent(h->side2, h->ev_lg_rec, 0));      // (NULL: released by the gate -- the sort ran
+        if (h->st.ev_lg_rec) SBR_HIP(hipStreamWaitEvent(h->side2, h->st.ev_lg_rec, 0));      // (NULL: released by the gate -- the sort ran
                                                                                     // beside the forward chain, the consumers wait for the chain's progress words)
-        if (!h->tail_sorted) { const int rc = tail_sort(h); if (rc != SBR_OK) return rc; }
+        if (!h->st.tail_sorted) { const int rc = tail_sort(h); if (rc != SBR_OK) return rc; }
     } else if (!(y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) || y.E || y.n_sparse) {
         const SbrSortKeys k = sort_keys(h, 0);
         SBR_LAUNCH(launch_scatter_sort(sd, h->bX, h->blen, y.T, y.Bp, y.F, y.cfg.input_size, k.cnt, k.off, k.cur, k.sid, k.pos,
@@ -545,18 +543,18 @@ static int side_batch_work(sbr_handle* h, bool fill_needed) {
 // record stays for phase-by-phase callers, SBR_TAIL_OVERLAP=2, steps without the overlapped tail and a timing mark there.
 static int release_side(sbr_handle* h, bool fill_needed) {
     const Layout& y = h->lay; hipStream_t sd = h->side;
-    if (kTailGateFirst && h->in_train_step && h->tail_nc >= 2 && h->sw.tail_overlap == 1 && h->tail_sorted && y.L == 1 && y.D == 1 &&
+    if (kTailGateFirst && h->in_train_step && h->st.tail_nc >= 2 && h->sw.tail_overlap == 1 && h->st.tail_sorted && y.L == 1 && y.D == 1 &&
         !fill_needed && !mark_live(h, 3)) {
         int nwaves = 0;
         int* words = tail_words(h, &nwaves);
         SBR_LAUNCH(launch_tail_gate_wave(sd, words, nwaves, tail_next_epoch(h), y.T, (int*)h->A(y.a_fault)));
-        h->tail_gated = true;
+        h->st.tail_gated = true;
         // (what sbr_build_batch orders itself behind: sbr_forward's fork -- its record, or the chain's start word where there is none)
-        h->ev_lg_rec = nullptr; h->ev_step_rec = h->fork_gated ? nullptr : h->ev_fork; h->lg_seq = h->batch_seq;
+        h->ev_step_rec = h->st.fork_gated ? nullptr : h->ev_fork; h->lg_seq = h->batch_seq;      // (no record: st.ev_lg_rec stays NULL)
     } else {
-        h->ev_lg_rec = h->ev_step_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
+        h->st.ev_lg_rec = h->ev_step_rec = record_shared(h, h->ev_lg, 3); h->lg_seq = h->batch_seq;
         h->step_word_epoch = 0;      // (the record is the later point of the step: the builder takes it)
-        SBR_HIP(hipStreamWaitEvent(sd, h->ev_lg_rec, 0));
+        SBR_HIP(hipStreamWaitEvent(sd, h->st.ev_lg_rec, 0));
     }
     return SBR_OK;
 }
@@ -615,33 +613,32 @@ static int dense_head_grads(sbr_handle* h) {
     // Single-call step without a bias regulariser: the output layer's gradient, its step and the batch cost in ONE launch
     // (launch_out_grad_step, sbr_update.hip) instead of the five or six below -- the polling weight-gradient GEMM of the overlapped
     // tail, next on this stream, then starts with the chain instead of 68 us into it.  SBR_OUT_FUSE=0: as before.
-    h->out_stepped = false;
     // (taken WITHOUT the overlapped tail only: in front of the polling GEMM of C2 it measured 0.3334 against 0.3294 ms -- that GEMM
     // then starts 9 us earlier and ends where it did, it is throughput-bound beside the chain; C1: 0.3156 -> 0.3035 together with
     // the one-launch head: profiles/round5_variants.txt call b)
-    const bool will_step_here = h->in_train_step && !y.n_sparse && !sg && h->tail_nc == 0;
+    const bool will_step_here = h->in_train_step && !y.n_sparse && !sg && h->st.tail_nc == 0;
     if (h->sw.out_fuse && will_step_here && y.cfg.regularization == 0.0f && y.D == 1) {
         hipError_t oe = hipSuccess;
         if (step_out_grad(h, sd, lg, hl, R, Nl, &oe)) {
             SBR_LAUNCH(oe);
-            h->out_stepped = true;
+            h->st.out_stepped = true;
         }
     }
-    if (!h->out_stepped) {
+    if (!h->st.out_stepped) {
         SBR_LAUNCH(launch_sum_cost(sd, h->A(y.a_rowcost), R, h->cost_ptr()));
         // data-parallel: every rank adds its share of the bias regulariser, shares sum to reg
         const float reg = y.cfg.regularization * (float)R / (float)y.Bg;
         SBR_LAUNCH(launch_colsum_bias(sd, lg, R, N, Nl, h->Gd(y.p_bout), h->P(y.p_bout), reg, h->cost_ptr(), h->A(y.a_csum)));
         SBR_LAUNCH(launch_gemm(sd, lg, 1, Nl, hl, Hp, 1, h->Gd(y.p_WoutT), Hp, N, Hp, R, nullptr, h->A(y.a_ws2), y.ws2_floats, sg));
     }
-    SBR_HIP(hipEventRecord(h->ev_og, sd)); h->og_recorded = true;   // output-layer gradients + cost complete
+    SBR_HIP(hipEventRecord(h->ev_og, sd)); h->st.og_recorded = true;   // output-layer gradients + cost complete
     // Single-call step, dense updates: the output layer is stepped right here, beside the BPTT chain (nothing reads W_out
     // any more: dh was computed in front of the record the side stream waited on); sbr_apply_update leaves the range
     // out.  C4: 46 us off the end of the step.  (The overlapped tail does the same itself; phase-by-phase callers --
     // data parallel -- reduce the gradients first.)
-    if (h->in_train_step && !y.n_sparse && h->tail_nc == 0 && !simple_gemm(h)) {
-        if (!h->out_stepped) SBR_LAUNCH(step_range(h, sd, y.p_split, y.n_params));
-        h->out_early = true;
+    if (h->in_train_step && !y.n_sparse && h->st.tail_nc == 0 && !simple_gemm(h)) {
+        if (!h->st.out_stepped) SBR_LAUNCH(step_range(h, sd, y.p_split, y.n_params));
+        h->st.out_early = true;
     }
     return SBR_OK;
 }
@@ -656,7 +653,7 @@ static int loss_dense(sbr_handle* h, bool fill_needed) {
     int rc;
     if ((rc = dense_head_fused(h, fold, &keep, &head_done)) != SBR_OK) return rc;
     if (!head_done && (rc = dense_head_launches(h, fold, &keep)) != SBR_OK) return rc;
-    h->dh_slabs_n = keep;
+    h->st.dh_slabs_n = keep;
     if ((rc = release_side(h, fill_needed)) != SBR_OK) return rc;
     if (!fill_needed && (rc = side_batch_work(h, fill_needed)) != SBR_OK) return rc;
     return dense_head_grads(h);
@@ -666,15 +663,14 @@ static int loss_dense(sbr_handle* h, bool fill_needed) {
 static int sampled_cells(sbr_handle* h) {
     const Layout& y = h->lay; hipStream_t s = h->stream;
     int* cells = (int*)h->A(y.a_cells);
-    if (h->cells_early) SBR_HIP(hipStreamWaitEvent(s, h->ev_cells, 0));      // built and caught up beside the forward chain (sbr_forward)
+    if (h->st.cells_early) SBR_HIP(hipStreamWaitEvent(s, h->ev_cells, 0));      // built and caught up beside the forward chain (sbr_forward)
     else {
         SBR_LAUNCH(launch_build_cells(s, h->btgt, h->bsmp, y.Bg, y.S, cells));
         if (sparse_lazy(h))      // ... and so must the rows of W_out^T / b_out the sampled cells gather
             for (int b = 0; b < y.n_sparse; ++b)
-                if (y.sparse[b].kind == 1)
-                    SBR_LAUNCH(launch_sparse_catch_up_list(s, sparse_rows(h, b), sparse_upd(h), cells, nullptr, y.C, y.C, (int)h->step_count));
+                if (y.sparse[b].kind == 1) SBR_LAUNCH(catch_up_rows(h, s, b, sparse_ids(h, b)));
     }
-    h->cells_early = false;
+    h->st.cells_early = false;      // (hand-over from sbr_forward, consumed: a second loss phase of this step builds its cells itself)
     return SBR_OK;
 }
 // sampled heads (BPR, TOP1, Blackout, ...): the loss over the batch's targets and the shared samples
@@ -711,20 +707,19 @@ static int loss_sampled(sbr_handle* h, bool fill_needed) {
     SBR_LAUNCH(launch_colsum_bias(sd, act, R, C, C, dbc, nullptr, 0.0f, nullptr, h->A(y.a_csum)));
     SBR_LAUNCH(launch_gemm(sd, act, 1, C, hl, Hp, 1, dWc, Hp, C, Hp, R, nullptr, nullptr, 0, sg));
     SBR_LAUNCH(launch_scatter_cells(sd, h->Gd(y.p_WoutT), h->Gd(y.p_bout), dWc, dbc, cells, C, Hp));
-    SBR_HIP(hipEventRecord(h->ev_og, sd)); h->og_recorded = true;
+    SBR_HIP(hipEventRecord(h->ev_og, sd)); h->st.og_recorded = true;
     if (!fill_needed) {      // the batch-only side work follows (the side stream has waited for this phase's record)
         const int rc = side_batch_work(h, fill_needed); if (rc != SBR_OK) return rc;
     }
     // Single-call step: the head's row-sparse block (W_out^T rows + b_out of the sampled cells) has its complete gradient now
     // and nothing reads those rows any more (dh is computed): its step runs on the side stream beside the BPTT chain instead
     // of at the end of the step (C3: 35 us, C5: 41 us); sbr_apply_update leaves the block out.
-    h->wout_early = false;
     if (h->in_train_step && h->sw.sparse_out_early)
         for (int b = 0; b < y.n_sparse; ++b)
-            if (y.sparse[b].kind == 1 && !h->sp_exchanged[b]) {
+            if (y.sparse[b].kind == 1 && !h->st.sp_exchanged[b]) {
                 SBR_HIP(hipStreamWaitEvent(sd, h->ev_og, 0));      // (recorded on this very stream)
-                SBR_LAUNCH(step_rows_listed(h, sd, b, cells, C));
-                h->wout_early = true;
+                SBR_LAUNCH(step_rows(h, sd, b, sparse_ids(h, b)));
+                h->st.wout_early = true;
             }
     return SBR_OK;
 }
@@ -735,12 +730,10 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
     if (!h->fwd_done) { sbr_set_error("sbr_loss_backward_output: call sbr_forward first"); return SBR_ESTATE; }
     const Layout& y = h->lay; hipStream_t s = h->stream, sd = h->side;
     h->grads_clean = false;
-    h->dh_slabs_n = 0;
     // (the output layer's input is Bp rows of HLt floats: both directions with --r_bi)
     if (h->n_rows < y.Bp) SBR_HIP(hipMemsetAsync(h->A(y.a_dhlast), 0, (size_t)y.Bp * y.HLt * sizeof(float), s));   // padded rows carry no gradient
     h->side_pending = true;
-    h->fill_done = false;
-    h->tail_gated = false; h->last_tail_gated = 0;
+    h->last_tail_gated = 0;
     h->last_join_gate = 0;
     // the batch-only side work (side_batch_work): beside the head where the cluster BPTT kernels need their sentinel fill, else behind it
     bool fill_needed = false;
@@ -772,7 +765,7 @@ extern "C" int sbr_loss_backward_output(sbr_handle* h) {
 static int bptt_args(sbr_handle* h, int pl, const float* dh_last, bool wait_fill, RecArgs* out) {
     const Layout& y = h->lay; const LayerLayout& ly = y.layer[pl];
     RecArgs a = rec_args(h, pl);
-    if (h->fill_done && h->plan[pl].needs_fill) {
+    if (h->st.fill_done && h->plan[pl].needs_fill) {
         a.sentinel_done = 1;
         if (wait_fill) SBR_HIP(hipStreamWaitEvent(h->stream, h->ev_fill, 0));
     }
@@ -851,14 +844,14 @@ static int tail_slab_table(sbr_handle* h, int K, int cap, SbrPoll* pl) {
 //   main stream   chain -> bias / init-state partial sums (-> their update) -> joins both
 // In a single-call step every stream applies the optimizer to what it has produced (the output layer early, on
 // the side stream); phase-by-phase callers (data parallel) get complete gradients and update in sbr_apply_update.
-// Layer 0 of a one-layer step whose forward planned the tail (h->tail_nc >= 2); the whole of the layer's backward.
+// Layer 0 of a one-layer step whose forward planned the tail (h->st.tail_nc >= 2); the whole of the layer's backward.
 static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nblk) {
     const Layout& y = h->lay; const LayerLayout& ly = y.layer[0];
     hipStream_t s = h->stream, sd = h->side;
     const int GHp = y.G * ly.Hp;
     const size_t slab = wp.slab;
     float* ws2 = h->A(y.a_ws2);
-    const int tnc = h->tail_nc;
+    const int tnc = h->st.tail_nc;
     // SBR_TAIL_OVERLAP=2: the same kernels, all on the main stream behind the chain (nothing has to run concurrently):
     // for tools that serialise kernels (rocprofv3 --pmc) and for triage
     const bool serial = h->sw.tail_overlap == 2;
@@ -874,8 +867,8 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
     int* words = tail_words(h, &nwaves);
     int* done = (int*)h->A(y.a_done);
     // (the side stream's gate of this step may already wait for the epoch: sbr_loss_backward_output)
-    const bool gated = h->tail_gated && !serial;
-    h->tail_gated = false; h->last_tail_gated = gated;
+    const bool gated = h->st.tail_gated && !serial;
+    h->st.tail_gated = false; h->last_tail_gated = gated;      // (hand-over from the loss phase, consumed: the gate waits for ONE chain, this one)
     a.progress = words; a.prog_every = kTailPubEvery; a.prog_epoch = gated ? h->prog_epoch : tail_next_epoch(h);
     const int K = y.T * y.Bp;
     const int cap = (int)std::min<size_t>(256, y.ws2_floats / slab);
@@ -888,7 +881,7 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
     mark(h, 4);
     // side stream: output layer first (its gradients are complete on this stream: dW_out GEMM, bias sums)
     const bool out_early = upd_here && (y.cfg.loss == SBR_LOSS_CCE || SBR_LOSS_IS_MARGIN(y.cfg.loss));
-    if (out_early && !h->out_stepped)       // (else: launch_out_grad_step has stepped the output layer with its gradient, sbr_loss_backward_output)
+    if (out_early && !h->st.out_stepped)       // (else: launch_out_grad_step has stepped the output layer with its gradient, sbr_loss_backward_output)
         SBR_LAUNCH(step_range(h, sd, y.p_split, y.n_params));
     // the monitor: on a stream of its own behind nothing but the chain's first progress words (its own loop waits for them)
     // ... unless the scatter-add launch carries it (default where that launch is the LDS-row one and has its own stream)
@@ -944,9 +937,9 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
     if (upd_here) {      // b, then (behind the gap that is W_hid) peepholes / initial states, and the output layer unless done
         // (a sampled head's gradient kernels run on the side stream since round 5, and this launch reads
         // and clears their output: order it behind them.  Without the wait the chain's length hid the race.)
-        if (!out_early && h->og_recorded) SBR_HIP(hipStreamWaitEvent(s, h->ev_og, 0));
+        if (!out_early && h->st.og_recorded) SBR_HIP(hipStreamWaitEvent(s, h->ev_og, 0));
         SBR_LAUNCH(step_range(h, s, ly.p_b, out_early ? y.p_split : y.n_params, ly.p_Whid - ly.p_b, ly.p_peep - ly.p_Whid));
-        h->tail_updated = true;
+        h->st.tail_updated = true;
     }
     if (h->deferred_join && !h->in_train_step && !serial) {
         // data-parallel driver: it orders one collective behind each producing stream (W_in: second side stream,
@@ -990,7 +983,7 @@ static int backward_chunked(sbr_handle* h, int l, RecArgs& a, const WgradPlan& w
         hipError_t we = hipSuccess;
         // swapped tail: this GEMM's slabs share the second workspace with the split-K slabs of the side stream's dW_out
         // GEMM -- normally long reduced by now, but nothing ordered the two (a wait on a complete event is free)
-        if (sw == s && h->og_recorded) SBR_HIP(hipStreamWaitEvent(s, h->ev_og, 0));
+        if (sw == s && h->st.og_recorded) SBR_HIP(hipStreamWaitEvent(s, h->ev_og, 0));
         if (!wp.gemm && launch_wgrad_slabs(sw, hsc, dxc, dhcc, slabs, ly.Hp, GHp, Kc, nsl, &we)) {
             SBR_LAUNCH(we);
         } else if (launch_gemm_slabs_x6(sw, hsc, 1, ly.Hp, dxc, GHp, 1, ly.Hp, GHp, Kc, slabs, nsl, GHp, slab, dhcc, ly.Hp,
@@ -1006,7 +999,7 @@ static int backward_chunked(sbr_handle* h, int l, RecArgs& a, const WgradPlan& w
     SBR_LAUNCH(launch_splitk_reduce(sw, ws2, nc * nsl, ly.Hp, GHp, h->Gd(ly.p_Whid), GHp, nullptr));
     h->side_pending = true;
     if (l == 0) mark(h, 4);
-    if (wp.swap) h->tail_swapped = true;
+    if (wp.swap) h->st.tail_swapped = true;
     SBR_LAUNCH(reduce_partials(h, sm, ly, a, nc * nblk));
     return SBR_OK;
 }
@@ -1071,7 +1064,7 @@ extern "C" int sbr_debug_scatter(sbr_handle* h, int reps, float* us, int64_t* en
     // the gradient block as a step expects it: zero (the rows the scatter-add wrote, i.e. the whole block)
     SBR_HIP(hipMemsetAsync(h->Gd(ly.p_Win), 0, (size_t)y.cfg.input_size * GHp * sizeof(float), s));
     SBR_HIP(hipStreamSynchronize(s));
-    h->tail_sorted = false;
+    h->st.tail_sorted = false;      // (no reset: called between a forward and its loss phase, the step goes on -- without the time-chunked keys this call's sort overwrote)
     return SBR_OK;
 }
 
@@ -1082,11 +1075,11 @@ static int backward_layer(sbr_handle* h, int l) {
     const bool top = l == y.L - 1;
     RecArgs a;
     { const int rc = bptt_args(h, l, top ? h->A(y.a_dhlast) : nullptr, top, &a); if (rc != SBR_OK) return rc; }
-    if (top && h->dh_slabs_n > 0) { a.dh_slabs = h->A(y.a_ws); a.n_dh_slabs = h->dh_slabs_n; }      // (sbr_loss_backward_output)
+    if (top && h->st.dh_slabs_n > 0) { a.dh_slabs = h->A(y.a_ws); a.n_dh_slabs = h->st.dh_slabs_n; }      // (sbr_loss_backward_output)
     if (a.prof) a.prof = prof_slot(h, 1);
     const int nblk = h->plan[l].bwd_blocks;
     const WgradPlan wp = wgrad_plan(h, ly, a);
-    if (l == 0 && y.L == 1 && h->tail_nc >= 2) return backward_tail(h, a, wp, nblk);      // the whole of the layer
+    if (l == 0 && y.L == 1 && h->st.tail_nc >= 2) return backward_tail(h, a, wp, nblk);      // the whole of the layer
     hipStream_t sw = wp.swap ? s : sd;      // weight-gradient GEMM
     hipStream_t sm = wp.swap ? sd : s;      // partials + scatter
     if (wp.nc > 1 || wp.side) {
@@ -1177,7 +1170,7 @@ extern "C" int sbr_backward_recurrent(sbr_handle* h) {
 // over W_in reads / clears the gradient of the touched rows only (launch_update_rows_aware).  SBR_ROW_AWARE_UPDATE=0: update_kernel.
 static bool row_aware_taken(const sbr_handle* h) {
     const Layout& y = h->lay;
-    return h->sw.row_aware && h->in_train_step && h->scat.wide_rows && !y.n_sparse && y.D == 1 && h->tail_nc < 2 &&
+    return h->sw.row_aware && h->in_train_step && h->scat.wide_rows && !y.n_sparse && y.D == 1 && h->st.tail_nc < 2 &&
            h->scat.plain != SCAT_ATOMIC && !simple_gemm(h) && !simple_rec(h);
 }
 // [0, hi) of the parameter section on the main stream; row_aware: with the row-aware pass over layer 0's W_in
@@ -1200,14 +1193,13 @@ static int update_sparse(sbr_handle* h) {
     // Single rank: the index-input block's row step goes FIRST, in front of the join -- its gradient rows are this stream's own
     // work (the scatter-add), so the pass (HBM-bound, 112 us at C3) runs beside the weight-gradient GEMM the side stream is still
     // busy with instead of behind it (round 6: C3's tail behind the chain 306 -> ~265 us)
-    bool stepped[2] = {false, false};
     for (int b = 0; b < y.n_sparse; ++b) {
         const SparseBlockLayout& sb = y.sparse[b];
-        if (sb.kind != 0 || h->sp_exchanged[b] || !h->side_pending || y.D != 1 || y.E) continue;      // (plain index input, one direction: the scatter-add ran on this stream)
+        if (sb.kind != 0 || h->st.sp_exchanged[b] || !h->side_pending || y.D != 1 || y.E) continue;      // (plain index input, one direction: the scatter-add ran on this stream)
         // (the atomic scatter-add reads no sorted ids, so this stream has not waited for the side stream's sort yet)
         if (y.cfg.flags & SBR_FLAG_ATOMIC_SCATTER) SBR_HIP(hipStreamWaitEvent(s, h->ev_sort, 0));
-        SBR_LAUNCH(step_rows_scattered(h, b));
-        stepped[b] = true;
+        SBR_LAUNCH(step_rows(h, s, b, sparse_ids(h, b)));
+        h->st.rows_stepped[b] = true;
     }
     { const int rc = side_join(h); if (rc != SBR_OK) return rc; }
     size_t pos = 0;
@@ -1215,16 +1207,10 @@ static int update_sparse(sbr_handle* h) {
     SBR_LAUNCH(step_range(h, s, pos, y.n_params));
     for (int b = 0; b < y.n_sparse; ++b) {
         const SparseBlockLayout& sb = y.sparse[b];
-        if ((sb.kind == 1 && h->wout_early) || stepped[b]) {
-            // stepped already: beside the BPTT chain (sbr_loss_backward_output) / in front of the join above
-        } else if (h->sp_exchanged[b]) {
-            SBR_LAUNCH(step_rows_listed(h, s, b, (const int*)h->A(sb.a_cand), h->sp_ncand[b]));
-        } else if (sb.kind == 0) {
-            SBR_LAUNCH(step_rows_scattered(h, b));
-        } else {
-            SBR_LAUNCH(step_rows_listed(h, s, b, (const int*)h->A(y.a_cells), y.C));
-        }
-        h->sp_exchanged[b] = 0; h->sp_ncand[b] = 0;
+        // stepped already: beside the BPTT chain (sbr_loss_backward_output) / in front of the join above
+        if ((sb.kind == 1 && h->st.wout_early) || h->st.rows_stepped[b]) continue;
+        const SbrSparseIds gathered = {(const int*)h->A(sb.a_cand), nullptr, h->st.sp_ncand[b], h->st.sp_ncand[b]};
+        SBR_LAUNCH(step_rows(h, s, b, h->st.sp_exchanged[b] ? gathered : sparse_ids(h, b)));
     }
     return SBR_OK;
 }
@@ -1262,14 +1248,14 @@ extern "C" int sbr_apply_update(sbr_handle* h) {
     // the step in flight is applied: it counts from whichever way this call returns (step_no until then)
     struct Count { sbr_handle* h; ~Count() { h->step_count += 1; } } count{h};
     if (h->tail_join_pending) { const int rc = side_join(h); if (rc != SBR_OK) return rc; }
-    const size_t p_end = h->out_early ? y.p_split : y.n_params;     // the output layer was stepped beside the BPTT chain
+    const size_t p_end = h->st.out_early ? y.p_split : y.n_params;     // the output layer was stepped beside the BPTT chain
     const bool row_aware = row_aware_taken(h);
     h->last_row_aware = row_aware;
     if (y.n_sparse) {
         const int rc = update_sparse(h); if (rc != SBR_OK) return rc;
-    } else if (h->tail_updated) {
+    } else if (h->st.tail_updated) {
         // overlapped tail of a single-call step: every stream has stepped what it produced (sbr_backward_recurrent)
-    } else if (h->side_pending && h->tail_swapped) {
+    } else if (h->side_pending && h->st.tail_swapped) {
         // side stream: everything but W_hid (W_in, b from its own scatter / partials; the output layer's gradients are its
         // own too); main stream: W_hid (its own GEMM) -- no event wait in front of it; then the main stream joins the side
         // stream, normally done by then
@@ -1277,20 +1263,20 @@ extern "C" int sbr_apply_update(sbr_handle* h) {
         SBR_LAUNCH(step_range(h, h->side, 0, p_end, l0.p_Whid, l0.p_peep - l0.p_Whid));
         SBR_LAUNCH(step_range(h, h->stream, l0.p_Whid, l0.p_peep));
         { const int rc = side_join(h); if (rc != SBR_OK) return rc; }
-    } else if (h->side_pending && h->og_recorded) {
+    } else if (h->side_pending && h->st.og_recorded) {
         const int rc = update_around_whid(h, p_end, row_aware); if (rc != SBR_OK) return rc;
     } else {
         { const int rc = side_join(h); if (rc != SBR_OK) return rc; }
         SBR_LAUNCH(step_front(h, p_end, row_aware));
     }
-    h->og_recorded = false; h->tail_swapped = false; h->tail_updated = false; h->out_early = false;
-    h->wout_early = false;
     mark(h, 7);
     if (!h->in_train_step && h->timing) h->ring_used += 1;
     h->grads_clean = true;
     h->fwd_done = false;
-    h->train_fwd_open = false;      // the step is complete and its streams are joined: the next batch build may trust main-stream order
-    if (h->side_pending || h->tail_join_pending) h->bb_slow = 2;
+    // the step is complete: the next batch build may trust main-stream order -- unless a road through this call ended without its join
+    if (h->side_pending || h->tail_join_pending) h->bb_slow = 2;      // (another cause than step_abandoned_check's: a COMPLETED step's streams still apart)
+    h->st.train_fwd_open = false;      // (the step's end, the opposite of abandoned: the reset below must not take it for one)
+    step_reset(h);
     return SBR_OK;
 }
 
