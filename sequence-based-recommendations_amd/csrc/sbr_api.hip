@@ -857,16 +857,8 @@ int full_scores(sbr_handle* h, int do_softmax) {
     int rc;
     if ((rc = forward_current(h)) != SBR_OK) return rc;    // every item is scored: all of W_out^T / b_out must be current
     float* lg = h->A(y.a_logits);
-    // scoring always runs the exact-f32 kernel: a row's scores (hence its ranked ids) must not depend on how many rows
-    // share the call (the bf16x6 kernel takes over at >= 96 rows and rounds differently)
-    // (SBR_FLAG_BF16_PROJECTION: the single-plane bf16 kernel, which serves any number of rows with the same arithmetic)
-    sbr_gemm_set_exact_f32(true);
-    const bool bf16p = (y.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
-    if (bf16p) sbr_gemm_set_planes(1);
-    const hipError_t ge = launch_gemm(h->stream, h_last(h), y.HLt, 1, h->P(y.p_WoutT), 1, y.HLt, lg, y.N, h->n_rows, y.N, y.HLt, nullptr,
-                                      nullptr, 0, simple_gemm(h));
-    sbr_gemm_set_planes(3);
-    SBR_LAUNCH(ge);
+    SBR_LAUNCH(launch_gemm(h->stream, scores_gemm_mode(h), gemm_rowmajor(h_last(h), y.HLt), gemm_transposed(h->P(y.p_WoutT), y.HLt), lg, y.N,
+                           h->n_rows, y.N, y.HLt));
     SBR_LAUNCH(launch_softmax_rows(h->stream, lg, h->P(y.p_bout), h->n_rows, y.N, do_softmax));
     return SBR_OK;
 }
@@ -935,15 +927,17 @@ extern "C" int sbr_debug_gemm(void* stream, const float* A, int64_t sam, int64_t
                               float* C, int64_t ldc, int32_t M, int32_t N, int32_t K, const float* bias, float* ws,
                               size_t ws_floats, int32_t exact_f32) {
     CHECK_ARG(A && B && C, "null operand");
-    sbr_gemm_set_exact_f32(exact_f32 == 1);
-    sbr_gemm_set_planes((exact_f32 == 2 || exact_f32 == 5) ? 1 : 3);
-    if (exact_f32 == 3 || exact_f32 == 4) sbr_gemm_hint(2, 1.0f, 1.0f);      // the two-plane fp16 split (three MFMAs): what the step's logits GEMM takes
-    sbr_gemm_x6_no_wide(exact_f32 == 4 || exact_f32 == 5);
-    const hipError_t ge = launch_gemm((hipStream_t)stream, A, (long)sam, (long)sak, B, (long)sbk, (long)sbn, C, (long)ldc, M, N, K, bias, ws,
-                                      ws_floats, false);
-    sbr_gemm_x6_no_wide(false);
-    sbr_gemm_set_planes(3);
-    SBR_LAUNCH(ge);
+    static const GemmMode modes[6] = {
+        // simple, exact_f32, planes, sa, sb, no_wide, one_pass
+        {false, false, 0, 1.0f, 1.0f, false, false},      // 0: bf16x6 where the shape allows it
+        {false, true, 0, 1.0f, 1.0f, false, false},       // 1: the exact-f32 kernel
+        {false, false, 0, 1.0f, 1.0f, false, true},       // 2: plain bf16 in one pass (SBR_FLAG_BF16_PROJECTION)
+        {false, false, 2, 1.0f, 1.0f, false, false},      // 3: the two-plane fp16 split (three MFMAs): what the step's logits GEMM takes
+        {false, false, 2, 1.0f, 1.0f, true, false},       // 4: as 3, kept on the 128-wide tile
+        {false, false, 0, 1.0f, 1.0f, true, true},        // 5: as 2, kept on the 128-wide tile
+    };
+    SBR_LAUNCH(launch_gemm((hipStream_t)stream, modes[exact_f32 >= 0 && exact_f32 <= 5 ? exact_f32 : 0], GemmOperand{A, (long)sam, (long)sak, 0}, GemmOperand{B, (long)sbk, (long)sbn, 0},
+                           C, (long)ldc, M, N, K, bias, ws, ws_floats));
     return SBR_OK;
 }
 

@@ -649,41 +649,74 @@ size_t sbr_rec_c16_ring_floats(int Bp, int Hp);
 hipError_t launch_rec_reduce_partials(hipStream_t s, const float* part, int nblk, int G, int Hp, int cell,
                                       float* db, float* dpeep, float* dcinit, float* dhinit);
 
-// Generic f32 GEMM on v_mfma_f32_16x16x4_f32:  C[m][n] = sum_k A(m,k) * B(k,n) (+ bias[n])
-// A(m,k) = A[m*sam + k*sak], B(k,n) = B[k*sbk + n*sbn], C row-major with leading dim ldc.
+// The dense GEMM:  C[m][n] = sum_k A(m,k) * B(k,n) (+ bias[n]), C row-major with leading dim ldc.
+// How it runs is a value the caller passes (the engine builds its own from its flags in one place: sbr_step.hip); no launcher
+// keeps a mode between calls.
+struct GemmMode {
+    bool simple = false;      // the triage kernel, one thread per output element (SBR_FLAG_SIMPLE_GEMM)
+    bool exact_f32 = false;   // stay on the v_mfma_f32_16x16x4_f32 kernel, bitwise an fmaf chain (SBR_FLAG_F32_MFMA; scoring)
+    // Operand planes of the tiled kernel (gemm_x6_kernel NP).  0: not stated, which means bf16x6.  1: plain bf16 operands, split-K
+    // allowed (the layer GEMMs under SBR_FLAG_BF16_LAYERS).  2: the two-plane fp16 split (three MFMAs per product instead of
+    // bf16x6's six) for operands the caller knows to be bounded: hidden states behind tanh / sigmoid gates, weights, gradients that
+    // have passed the clip at +-100, with sa / sb the power-of-two scales that bring A / B into fp16's range.  3: bf16x6, stated.
+    int planes = 0;
+    float sa = 1.0f, sb = 1.0f;
+    bool no_wide = false;     // stay on the 128-wide tile where the 256 x 128 one would be taken (parity tests of gemm_x6w_kernel)
+    // Plain bf16 operands in ONE pass over K in a fixed order (no split-K), for any number of rows, so that an output element never
+    // depends on M: the projections under SBR_FLAG_BF16_PROJECTION.  Goes in front of exact_f32 and of `planes`, which hold where
+    // the tiled kernel cannot read the operands
+    bool one_pass = false;
+};
+GemmMode scores_gemm_mode(const sbr_handle* h);      // sbr_step.hip, beside the engine's other modes: the projection of full_scores
+// An operand as a value: element (r, c) at p[r * s_row + c * s_col]; A's rows are m and its columns k, B's rows are k and its
+// columns n.  blk_Bp > 0: a tile-blocked activation [pos = t * Bp + row][col] instead (strides ignored; A: m = pos, k = col over K
+// columns;  B: k = pos, n = col over N columns).
+struct GemmOperand { const float* p; long s_row, s_col; int blk_Bp; };
+static inline GemmOperand gemm_rowmajor(const float* p, long ld) { return GemmOperand{p, ld, 1, 0}; }        // [rows][ld] as stored
+static inline GemmOperand gemm_transposed(const float* p, long ld) { return GemmOperand{p, 1, ld, 0}; }      // the transpose of a stored [cols][ld]
+// What launch_gemm will do with its arguments, decided once: pure host code, no HIP call (tests/test_gemm_plan_table.py)
+enum GemmKernel { GEMM_NAIVE, GEMM_X6, GEMM_F32 };
+struct GemmPlan {
+    GemmKernel kernel;
+    int tile;                 // output tile: x6 64 or 128, or 256 for the wide 256 x 128 one (gemm_x6w_kernel); f32 64; naive 0
+    int nsplit, kchunk;       // split-K slices and the K range of each (0: all of K, the naive kernel)
+    int planes; float sa, sb; // x6: operand planes and scales actually used (else 0, 1, 1)
+    bool reduce;              // nsplit > 1: a split-K reduction follows ...
+    bool keep;                // ... or the slabs stay in ws for the consumer (may_keep and no bias)
+};
+GemmPlan sbr_gemm_plan(const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, const float* C, long ldc, int M, int N, int K,
+                       bool has_bias, const float* ws, size_t ws_floats, bool may_keep);
 // ws: split-K workspace of ws_floats floats (may be NULL -> no split).
-// a_blk_Bp / b_blk_Bp > 0: that operand is a tile-blocked activation [pos = t*Bp + row][col] (strides ignored;
-// A: m = pos, k = col over K columns;  B: k = pos, n = col over N columns).
-hipError_t launch_gemm(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn,
-                       float* C, long ldc, int M, int N, int K, const float* bias, float* ws, size_t ws_floats,
-                       bool simple, int a_blk_Bp = 0, int b_blk_Bp = 0, int* keep_slabs = nullptr);
-void sbr_gemm_x6_no_wide(bool on);                       // this thread's next launches stay on the 128-wide tile (parity tests of gemm_x6w_kernel)
-void sbr_gemm_hint(int planes, float sa, float sb);      // operand planes of the NEXT launch_gemm call (sbr_gemm.hip)
 // keep_slabs != NULL: where the split-K form runs, its slabs stay in ws (slab z at ws + z * M * N, row stride N), the
 // reduction is left to the consumer and *keep_slabs = their number; otherwise *keep_slabs = 0 and C holds the result
+hipError_t launch_gemm(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, float* C, long ldc, int M, int N,
+                       int K, const float* bias = nullptr, float* ws = nullptr, size_t ws_floats = 0, int* keep_slabs = nullptr);
 
-// bf16x6 GEMM (sbr_gemm_x6.hip): false = shape not supported, use the f32 kernel
-bool launch_gemm_x6(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc,
-                    int M, int N, int K, const float* bias, int nsplit, int kchunk, size_t slab_stride, hipError_t* err,
-                    const float* B2 = nullptr, long sbk2 = 0, int n_split = 0, bool small = false, int planes = 3,
-                    float sa = 1.0f, float sb = 1.0f,       // planes = 2: fp16 x3 with operand scales sa, sb (powers of two)
-                    const SbrPoll* poll = nullptr);
-void sbr_gemm_set_exact_f32(bool on);
-// planes = 1: the next launch_gemm calls run on plain bf16 operands (one MFMA per block, no split-K), for any number of rows
-void sbr_gemm_set_planes(int planes);
+// The tiled kernel (sbr_gemm_x6.hip).  sbr_gemm_x6_ok: can it run this shape on these operands with `planes` planes?  (no: a shape
+// too small for its tile, no unit stride, or an operand whose rows are not 16-byte aligned, e.g. N = 3706 item columns: scalar
+// loads would make the split the bottleneck).  sbr_gemm_x6_wide: does launch_gemm_x6 take the 256 x 128 tile there?  Both are
+// pure host code, read by sbr_gemm_plan and by the launcher.
+bool sbr_gemm_x6_ok(const GemmOperand& A, const GemmOperand& B, int M, int N, int K, bool small, int planes);
+bool sbr_gemm_x6_wide(const GemmMode& mode, const GemmOperand& A, const float* C, long ldc, int M, int N, int K, int nsplit, int kchunk,
+                      size_t slab_stride, bool small);
+// mode: planes (0 as 3), sa, sb, no_wide.  false = not launched (sbr_gemm_x6_ok, or B2 / poll ask for what it cannot do).
+// nsplit == 1: C (row stride ldc, + bias); nsplit > 1: slab z at C + z*slab_stride, row stride ldc.
+bool launch_gemm_x6(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, float* C, long ldc, int M, int N,
+                    int K, const float* bias, int nsplit, int kchunk, size_t slab_stride, hipError_t* err, const float* B2 = nullptr,
+                    long sbk2 = 0, int n_split = 0, bool small = false, const SbrPoll* poll = nullptr);
 
 // slabs are [z][slab_stride] with row stride ws_ld: a GEMM may fill only a column range of wider slabs
-hipError_t launch_gemm_slabs(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, int M,
-                             int N, int K, float* ws, int nsplit, long ws_ld, size_t slab_stride);
-// same through the bf16x6 kernel only, with the B columns >= n_split taken from B2 (row stride sbk2); false: not launched
-bool launch_gemm_slabs_x6(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, int M, int N,
-                          int K, float* ws, int nsplit, long ws_ld, size_t slab_stride, const float* B2, long sbk2, int n_split,
-                          hipError_t* err, int planes = 3, float sa = 1.0f, float sb = 1.0f);
+hipError_t launch_gemm_slabs(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, int M, int N, int K,
+                             float* ws, int nsplit, long ws_ld, size_t slab_stride);
+// same through the tiled kernel only, with the B columns >= n_split taken from B2 (row stride sbk2); false: not launched
+bool launch_gemm_slabs_x6(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, int M, int N, int K,
+                          float* ws, int nsplit, long ws_ld, size_t slab_stride, const float* B2, long sbk2, int n_split,
+                          hipError_t* err);
 // the same as a consumer of the running chain: poll.n_slabs slabs of K, poll.slab_lo[0 .. n_slabs] (device) their first rows,
 // shared by n_groups persistent groups of workgroups, each of which leaves ONE partial in ws (n_groups partials to reduce)
-bool launch_gemm_slabs_x6_poll(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, int M, int N,
-                               int K, float* ws, int n_groups, long ws_ld, size_t slab_stride, const float* B2, long sbk2,
-                               int n_split, hipError_t* err, int planes, float sa, float sb, const SbrPoll& poll);
+bool launch_gemm_slabs_x6_poll(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, int M, int N, int K,
+                               float* ws, int n_groups, long ws_ld, size_t slab_stride, const float* B2, long sbk2, int n_split,
+                               hipError_t* err, const SbrPoll& poll);
 // host side of the table: lo[0] = 0 < lo[1] < ... < lo[n] = K, n <= cap.  A slab that starts at time step t has
 // max(1, floor(growth * t - 1)) k steps of 32 rows, at most max_rows / 32 (sizes scaled up until n <= cap).
 int sbr_tail_slab_table(int K, int rows_per_step, int cap, double growth, int max_rows, std::vector<int>& lo);

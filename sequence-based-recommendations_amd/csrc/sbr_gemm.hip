@@ -228,50 +228,34 @@ __global__ void gemm_naive(GemmArgs g) {
     g.C[(long)m * g.ldc + n] = s + (g.bias ? g.bias[n] : 0.0f);
 }
 
-// SBR_FLAG_F32_MFMA: keep every GEMM on the exact-f32 kernel (set per call by the API layer; a handle is not thread-safe)
-// (per host thread: two handles driven from different threads must not steal or leak each other's mode / hint -- ADVICE round 4)
-static thread_local bool g_gemm_exact_f32 = false;
-void sbr_gemm_set_exact_f32(bool on) { g_gemm_exact_f32 = on; }
-static thread_local int g_gemm_planes = 3;
-void sbr_gemm_set_planes(int planes) { g_gemm_planes = planes == 1 ? 1 : 3; }
-// Hint for the NEXT launch_gemm call only (consumed and cleared by it; a handle is not thread-safe): the operand planes of the
-// tiled kernel -- 2: the two-plane fp16 split (three MFMAs per product instead of bf16x6's six) for operands the caller knows to be
-// bounded: hidden states behind tanh / sigmoid gates, weights, gradients that have passed the clip at +-100, with sa / sb the
-// power-of-two scales that bring A / B into fp16's range (gemm_x6_kernel NP = 2); 1: plain bf16 operands, split-K allowed (the
-// layer GEMMs under SBR_FLAG_BF16_LAYERS).  0: none (bf16x6).
-static thread_local int g_hint_planes = 0; static thread_local float g_hint_sa = 1.0f, g_hint_sb = 1.0f;
-void sbr_gemm_hint(int planes, float sa, float sb) { g_hint_planes = planes; g_hint_sa = sa; g_hint_sb = sb; }
-
 // split-K partial products only: writes exactly `nsplit` slabs [z][M][N] at ws (no reduction)
-hipError_t launch_gemm_slabs(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, int M,
-                             int N, int K, float* ws, int nsplit, long ws_ld, size_t slab_stride) {
+hipError_t launch_gemm_slabs(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, int M, int N, int K,
+                             float* ws, int nsplit, long ws_ld, size_t slab_stride) {
     if (M <= 0 || N <= 0 || nsplit < 1) return hipSuccess;
-    if (!g_gemm_exact_f32) {
+    if (!mode.exact_f32) {
         const int kc = ((K + nsplit - 1) / nsplit + 31) / 32 * 32;   // slices past K write zero slabs
         hipError_t e = hipSuccess;
         // nsplit == 1 would take the "write C" form: identical here (slab 0, no bias)
-        if (launch_gemm_x6(s, A, sam, sak, B, sbk, sbn, ws, ws_ld, M, N, K, nullptr, nsplit, kc, slab_stride, &e)) return e;
+        if (launch_gemm_x6(s, mode, A, B, ws, ws_ld, M, N, K, nullptr, nsplit, kc, slab_stride, &e)) return e;
     }
-    GemmArgs g{A, sam, sak, B, sbk, sbn, ws, N, M, N, K, nullptr, 0, 0, K, ws, ws_ld, slab_stride};
+    GemmArgs g{A.p, A.s_row, A.s_col, B.p, B.s_row, B.s_col, ws, N, M, N, K, nullptr, 0, 0, K, ws, ws_ld, slab_stride};
     const int tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
     g.kchunk = ((K + nsplit - 1) / nsplit + BK - 1) / BK * BK;   // slices past K write zero slabs
     gemm_f32_mfma<<<dim3(tn, tm, nsplit), 256, 0, s>>>(g);
     return hipGetLastError();
 }
-bool launch_gemm_slabs_x6(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, int M, int N,
-                          int K, float* ws, int nsplit, long ws_ld, size_t slab_stride, const float* B2, long sbk2, int n_split,
-                          hipError_t* err, int planes, float sa, float sb) {
-    if (g_gemm_exact_f32 || M <= 0 || N <= 0 || nsplit < 1) return false;
+bool launch_gemm_slabs_x6(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, int M, int N, int K,
+                          float* ws, int nsplit, long ws_ld, size_t slab_stride, const float* B2, long sbk2, int n_split,
+                          hipError_t* err) {
+    if (mode.exact_f32 || M <= 0 || N <= 0 || nsplit < 1) return false;
     const int kc = ((K + nsplit - 1) / nsplit + 31) / 32 * 32;
-    return launch_gemm_x6(s, A, sam, sak, B, sbk, sbn, ws, ws_ld, M, N, K, nullptr, nsplit, kc, slab_stride, err, B2, sbk2, n_split, false,
-                          planes, sa, sb);
+    return launch_gemm_x6(s, mode, A, B, ws, ws_ld, M, N, K, nullptr, nsplit, kc, slab_stride, err, B2, sbk2, n_split, false);
 }
-bool launch_gemm_slabs_x6_poll(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, int M, int N,
-                               int K, float* ws, int n_groups, long ws_ld, size_t slab_stride, const float* B2, long sbk2,
-                               int n_split, hipError_t* err, int planes, float sa, float sb, const SbrPoll& poll) {
-    if (g_gemm_exact_f32 || M <= 0 || N <= 0 || n_groups < 1 || !poll.slab_lo) return false;
-    return launch_gemm_x6(s, A, sam, sak, B, sbk, sbn, ws, ws_ld, M, N, K, nullptr, n_groups, 32, slab_stride, err, B2, sbk2,
-                          n_split, false, planes, sa, sb, &poll);
+bool launch_gemm_slabs_x6_poll(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, int M, int N, int K,
+                               float* ws, int n_groups, long ws_ld, size_t slab_stride, const float* B2, long sbk2, int n_split,
+                               hipError_t* err, const SbrPoll& poll) {
+    if (mode.exact_f32 || M <= 0 || N <= 0 || n_groups < 1 || !poll.slab_lo) return false;
+    return launch_gemm_x6(s, mode, A, B, ws, ws_ld, M, N, K, nullptr, n_groups, 32, slab_stride, err, B2, sbk2, n_split, false, &poll);
 }
 int sbr_tail_slab_table(int K, int rows_per_step, int cap, double growth, int max_rows, std::vector<int>& lo) {
     const int max_n = std::max(1, max_rows / 32);
@@ -293,74 +277,77 @@ hipError_t launch_splitk_reduce(hipStream_t s, const float* ws, int nslabs, int 
     return splitk_reduce(s, ws, nslabs, M, N, C, ldc, bias);
 }
 
-hipError_t launch_gemm(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C,
-                       long ldc, int M, int N, int K, const float* bias, float* ws, size_t ws_floats, bool simple,
-                       int a_blk_Bp, int b_blk_Bp, int* keep_slabs) {
-    if (keep_slabs) *keep_slabs = 0;
-    const int hint_planes = g_hint_planes; const float hint_sa = g_hint_sa, hint_sb = g_hint_sb;
-    g_hint_planes = 0; g_hint_sa = g_hint_sb = 1.0f;
-    if (M <= 0 || N <= 0) return hipSuccess;
-    GemmArgs g{A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, bias, a_blk_Bp, b_blk_Bp, K, nullptr, (long)N, (size_t)M * N};
-    if (simple) {
-        const size_t n = (size_t)M * N;
-        gemm_naive<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(g);
-        return hipGetLastError();
+// The ladder, top to bottom: the triage kernel; one pass of plain bf16 (GemmMode.one_pass); the tiled kernel on 128 x 128 tiles, or
+// on 64 x 64 ones where fewer than ~128 workgroups of the large tile would be on the chip (profiles/round1_j_*), split over K
+// where a workspace allows it; the f32 MFMA kernel with its own split.  Blocked operands and whatever sbr_gemm_x6_ok refuses go to
+// the last.
+GemmPlan sbr_gemm_plan(const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, const float* C, long ldc, int M, int N, int K,
+                       bool has_bias, const float* ws, size_t ws_floats, bool may_keep) {
+    GemmPlan p{GEMM_NAIVE, 0, 1, 0, 0, 1.0f, 1.0f, false, false};
+    if (mode.simple) return p;
+    const size_t MN = (size_t)M * N;
+    const bool tiled = A.blk_Bp == 0 && B.blk_Bp == 0;
+    auto tiles = [&](int tile) { return ((M + tile - 1) / tile) * ((N + tile - 1) / tile); };
+    auto x6 = [&](int planes, float sa, float sb, bool small, int ns, int kc) {
+        GemmMode m = mode; m.planes = planes;
+        const bool wide = sbr_gemm_x6_wide(m, A, ns > 1 ? ws : C, ns > 1 ? (long)N : ldc, M, N, K, ns, kc, MN, small);
+        p = GemmPlan{GEMM_X6, wide ? 256 : small ? 64 : 128, ns, kc, planes, sa, sb, false, ns > 1 && may_keep && !has_bias};
+        p.reduce = ns > 1 && !p.keep;
+        return p;
+    };
+    if (mode.one_pass && tiled) {
+        const bool small = tiles(128) < 128 || M < 96;
+        if (sbr_gemm_x6_ok(A, B, M, N, K, small, 1)) return x6(1, 1.0f, 1.0f, small, 1, (K + 31) / 32 * 32);
     }
-    if (g_gemm_planes == 1 && a_blk_Bp == 0 && b_blk_Bp == 0) {
-        // plain bf16 operands: one pass over K in a fixed order (no split-K), so that an output element never depends on M
-        hipError_t e = hipSuccess;
-        const int t128 = ((M + 127) / 128) * ((N + 127) / 128);
-        if (launch_gemm_x6(s, A, sam, sak, B, sbk, sbn, C, ldc, M, N, K, bias, 1, (K + 31) / 32 * 32, (size_t)M * N, &e, nullptr, 0, 0,
-                           t128 < 128 || M < 96, 1))
-            return e;
-    }
-    if (!g_gemm_exact_f32 && a_blk_Bp == 0 && b_blk_Bp == 0 && M >= 48 && N >= 48 && K >= 32) {
-        const int small_below = 128;      // (fewer large tiles than this on the chip: the 64 x 64 x 64 tile -- profiles/round1_j_*)
-        auto plan = [&](int tile, int& ns, int& kc) {
-            const int t = ((M + tile - 1) / tile) * ((N + tile - 1) / tile);
-            ns = 1;
-            if (ws && K >= 512) {
-                ns = std::max(1, 512 / t);
-                ns = std::min(ns, K / 128);
-                ns = (int)std::min<size_t>((size_t)ns, ws_floats / ((size_t)M * N));
-                ns = std::max(ns, 1);
-            }
+    if (!mode.exact_f32 && tiled && M >= 48 && N >= 48 && K >= 32) {
+        auto split = [&](int tile, int& ns, int& kc) {
+            const int t = tiles(tile);
+            ns = 1;      // a split: up to 512 workgroups, 128 of K each at the least, as many slabs as the workspace holds
+            if (ws && K >= 512) ns = std::max(1, (int)std::min<size_t>(std::min(std::max(1, 512 / t), K / 128), ws_floats / MN));
             kc = ((K + ns - 1) / ns + 31) / 32 * 32;
             ns = std::max(1, (K + kc - 1) / kc);
             return t * ns;
         };
         int ns, kc;
-        // fewer than ~128 workgroups of the 128x128 tile: 64x64 tiles put four times as many on the chip
-        const bool small = plan(128, ns, kc) < small_below || M < 96 || N < 96;
-        if (small) plan(64, ns, kc);
-        hipError_t e = hipSuccess;
-        if (launch_gemm_x6(s, A, sam, sak, B, sbk, sbn, ns > 1 ? ws : C, ns > 1 ? (long)N : ldc, M, N, K, bias, ns, kc,
-                           (size_t)M * N, &e, nullptr, 0, 0, small, hint_planes ? hint_planes : 3, hint_sa, hint_sb)) {
-            if (e == hipSuccess && ns > 1) {
-                if (keep_slabs && !bias) *keep_slabs = ns;                // the consumer adds the slabs
-                else e = splitk_reduce(s, ws, ns, M, N, C, ldc, bias);
-            }
-            return e;
-        }
+        const bool small = split(128, ns, kc) < 128 || M < 96 || N < 96;
+        if (small) split(64, ns, kc);
+        const int planes = mode.planes ? mode.planes : 3;
+        if (sbr_gemm_x6_ok(A, B, M, N, K, small, planes)) return x6(planes, mode.sa, mode.sb, small, ns, kc);
     }
-    const int tm = (M + BM - 1) / BM, tn = (N + BN - 1) / BN;
     int nsplit = 1;
-    if (ws && K >= 8 * BK) {
-        nsplit = 1024 / (tm * tn);
-        nsplit = min(nsplit, K / (4 * BK));
-        nsplit = (int)min((size_t)nsplit, ws_floats / ((size_t)M * N));
-        nsplit = max(nsplit, 1);
-    }
+    if (ws && K >= 8 * BK) nsplit = std::max(1, (int)std::min<size_t>(std::min(1024 / tiles(BM), K / (4 * BK)), ws_floats / MN));
     int kchunk = ((K + nsplit - 1) / nsplit + BK - 1) / BK * BK;
     if (kchunk <= 0) kchunk = BK;
     nsplit = max(1, (K + kchunk - 1) / kchunk);
-    g.kchunk = kchunk;
-    g.ws = nsplit > 1 ? ws : nullptr;
-    gemm_f32_mfma<<<dim3(tn, tm, nsplit), 256, 0, s>>>(g);
-    if (nsplit > 1) {
-        const size_t n = (size_t)M * N;
-        gemm_splitk_reduce<<<(unsigned)((n + 63) / 64), 256, 0, s>>>(ws, nsplit, M, N, C, ldc, bias);
+    return GemmPlan{GEMM_F32, BM, nsplit, kchunk, 0, 1.0f, 1.0f, nsplit > 1, false};
+}
+
+hipError_t launch_gemm(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, float* C, long ldc, int M, int N,
+                       int K, const float* bias, float* ws, size_t ws_floats, int* keep_slabs) {
+    if (keep_slabs) *keep_slabs = 0;
+    if (M <= 0 || N <= 0) return hipSuccess;
+    const GemmPlan p = sbr_gemm_plan(mode, A, B, C, ldc, M, N, K, bias != nullptr, ws, ws_floats, keep_slabs != nullptr);
+    const size_t MN = (size_t)M * N;
+    if (p.kernel == GEMM_X6) {
+        GemmMode m = mode; m.planes = p.planes; m.sa = p.sa; m.sb = p.sb;
+        const bool split = p.nsplit > 1;
+        hipError_t e = hipSuccess;
+        if (!launch_gemm_x6(s, m, A, B, split ? ws : C, split ? (long)N : ldc, M, N, K, bias, p.nsplit, p.kchunk, MN, &e, nullptr, 0, 0,
+                            p.tile == 64))
+            return hipErrorInvalidValue;      // (the plan asked sbr_gemm_x6_ok)
+        if (e == hipSuccess && p.keep) *keep_slabs = p.nsplit;                // the consumer adds the slabs
+        else if (e == hipSuccess && p.reduce) e = splitk_reduce(s, ws, p.nsplit, M, N, C, ldc, bias);
+        return e;
     }
+    GemmArgs g{A.p, A.s_row, A.s_col, B.p, B.s_row, B.s_col, C, ldc, M, N, K, bias, A.blk_Bp, B.blk_Bp, K, nullptr, (long)N, MN};
+    if (p.kernel == GEMM_NAIVE) {
+        gemm_naive<<<(unsigned)((MN + 255) / 256), 256, 0, s>>>(g);
+        return hipGetLastError();
+    }
+    g.kchunk = p.kchunk;
+    g.ws = p.reduce ? ws : nullptr;
+    gemm_f32_mfma<<<dim3((N + BN - 1) / BN, (M + BM - 1) / BM, p.nsplit), 256, 0, s>>>(g);
+    if (p.reduce) gemm_splitk_reduce<<<(unsigned)((MN + 63) / 64), 256, 0, s>>>(ws, p.nsplit, M, N, C, ldc, bias);
     return hipGetLastError();
 }
 

@@ -547,38 +547,39 @@ __global__ void __launch_bounds__(512, 1) gemm_x6w_kernel(GemmX6Args g) {
         }
 }
 
-static thread_local bool g_x6_no_wide = false;
-void sbr_gemm_x6_no_wide(bool on) { g_x6_no_wide = on; }
-
 static inline bool x6_aligned(const float* p, long other_stride) {   // 16-byte loads along the unit-stride dimension
     return ((uintptr_t)p & 15) == 0 && (other_stride & 3) == 0;
 }
-
-// true = launched (err holds the launch status).  false = the caller uses the f32 kernel: shape too small for a
-// 128x128 tile, no unit stride, or an operand whose rows are not 16-byte aligned (e.g. N = 3706 item columns: scalar
-// loads would make the split the bottleneck).  nsplit == 1: C (row stride ldc, + bias); nsplit > 1: slab z at
-// C + z*slab_stride, row stride ldc.
-bool launch_gemm_x6(hipStream_t s, const float* A, long sam, long sak, const float* B, long sbk, long sbn, float* C, long ldc,
-                    int M, int N, int K, const float* bias, int nsplit, int kchunk, size_t slab_stride, hipError_t* err,
-                    const float* B2, long sbk2, int n_split, bool small, int planes, float sa, float sb, const SbrPoll* poll) {
+bool sbr_gemm_x6_ok(const GemmOperand& A, const GemmOperand& B, int M, int N, int K, bool small, int planes) {
     if (planes == 1) { if (M < 1 || N < 48 || K < 32) return false; }      // any number of rows: a row's scores must not depend on
     else if (M < (small ? 48 : 96) || N < (small ? 48 : 96) || K < 32) return false;   // how many rows share the call
-    if (B2 && (sbn != 1 || (n_split & 3) || !x6_aligned(B2, sbk2))) return false;
-    if (!(sam == 1 || sak == 1) || !(sbk == 1 || sbn == 1)) return false;
-    const bool ra = sak != 1, rb = sbk != 1;                        // unit stride along the rows (m / n) instead of k
-    if (!x6_aligned(A, ra ? sak : sam) || !x6_aligned(B, rb ? sbk : sbn)) return false;
-    GemmX6Args g{A, sam, sak, B, sbk, sbn, C, ldc, slab_stride, M, N, K, kchunk, nsplit > 1 ? nullptr : bias, B2, sbk2, n_split,
-                 sa, sb, 1.0f / (sa * sb), SbrPoll{nullptr, 0, nullptr, 0, 1, nullptr, 0, 0, nullptr, nullptr, 0}};
+    if (!(A.s_row == 1 || A.s_col == 1) || !(B.s_row == 1 || B.s_col == 1)) return false;
+    return x6_aligned(A.p, A.s_col != 1 ? A.s_col : A.s_row) && x6_aligned(B.p, B.s_row != 1 ? B.s_row : B.s_col);
+}
+// the wide tile where the shape fills it (see gemm_x6w_kernel)
+// (A with unit stride along m -- the weight-gradient GEMMs, contraction over time -- stays on the 128-wide kernel: eight 8-byte LDS
+//  writes per thread and step instead of four 16-byte ones, measured slower there: 582 against 476 us for 512 x 2 048 x 51 200)
+bool sbr_gemm_x6_wide(const GemmMode& mode, const GemmOperand& A, const float* C, long ldc, int M, int N, int K, int nsplit, int kchunk,
+                      size_t slab_stride, bool small) {
+    return !small && !mode.no_wide && A.s_col == 1 && (mode.planes == 1 || mode.planes == 2) && (M & 255) == 0 && (N & 127) == 0 &&
+           (K & 31) == 0 && (kchunk & 31) == 0 && (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0 && (slab_stride & 3) == 0 &&
+           (size_t)(M / 256) * (N / 128) * nsplit >= 128;
+}
+
+bool launch_gemm_x6(hipStream_t s, const GemmMode& mode, const GemmOperand& A, const GemmOperand& B, float* C, long ldc, int M, int N,
+                    int K, const float* bias, int nsplit, int kchunk, size_t slab_stride, hipError_t* err, const float* B2, long sbk2,
+                    int n_split, bool small, const SbrPoll* poll) {
+    const int planes = mode.planes ? mode.planes : 3;
+    if (!sbr_gemm_x6_ok(A, B, M, N, K, small, planes)) return false;
+    if (B2 && (B.s_col != 1 || (n_split & 3) || !x6_aligned(B2, sbk2))) return false;
+    const bool ra = A.s_col != 1, rb = B.s_row != 1;                // unit stride along the rows (m / n) instead of k
+    GemmX6Args g{A.p, A.s_row, A.s_col, B.p, B.s_row, B.s_col, C, ldc, slab_stride, M, N, K, kchunk, nsplit > 1 ? nullptr : bias, B2, sbk2,
+                 n_split, mode.sa, mode.sb, 1.0f / (mode.sa * mode.sb), SbrPoll{nullptr, 0, nullptr, 0, 1, nullptr, 0, 0, nullptr, nullptr, 0}};
     if (poll) {      // (interior tiles only: x6_issue_sc1)
         if (small || nsplit < 1 || planes < 2 || (M & 127) || (N & 127) || (K & 7) || !poll->slab_lo || poll->n_slabs < 1) return false;
         g.poll = *poll;
     }
-    // the wide tile where the shape fills it (see gemm_x6w_kernel); g_x6_no_wide: parity tests of the two kernels against each other
-    // (A with unit stride along m -- the weight-gradient GEMMs, contraction over time -- stays on the 128-wide kernel: eight 8-byte LDS
-    //  writes per thread and step instead of four 16-byte ones, measured slower there: 582 against 476 us for 512 x 2 048 x 51 200)
-    if (!poll && !small && !g_x6_no_wide && !ra && (planes == 1 || planes == 2) && !B2 && (M & 255) == 0 && (N & 127) == 0 && (K & 31) == 0 &&
-        (kchunk & 31) == 0 && (ldc & 3) == 0 && ((uintptr_t)C & 15) == 0 && (slab_stride & 3) == 0 &&
-        (size_t)(M / 256) * (N / 128) * nsplit >= 128) {
+    if (!poll && !B2 && sbr_gemm_x6_wide(mode, A, C, ldc, M, N, K, nsplit, kchunk, slab_stride, small)) {
         const dim3 wgrid((M / 256) * (N / 128), nsplit);
         const size_t lds = (size_t)2 * planes * (256 + 128) * 80;
 #define X6W_GO(NP) do { \

@@ -65,16 +65,34 @@ static const RecPlan& plan_of(const sbr_handle* h, const LayerLayout& ly) { retu
 // their operands are hidden states in [-1, 1] (not behind a rectifier), weights, and -- in the backward pair -- gate gradients
 // that have passed the reference's clip at +-100 (recurrent_layers.py:19): the two-plane fp16 split, three MFMAs per product, f32-class
 // (SBR_GEMM_F16=0: bf16x6 as in rounds 1-3).  SBR_FLAG_BF16_LAYERS: plain bf16 operands, one MFMA (BASELINE configs[4]).
-static inline bool layer_gemm_f16(const sbr_handle* h, bool with_gradient) {
-    const Layout& y = h->lay;
-    if (!h->sw.gemm_f16 || y.cfg.cell == SBR_CELL_VANILLA) return false;
-    return !with_gradient || (y.cfg.grad_clip > 0.0f && y.cfg.grad_clip <= 100.0f);
-}
-static inline void layer_gemm_hint(const sbr_handle* h, bool grad_a, bool grad_b) {
-    if (h->lay.cfg.flags & SBR_FLAG_BF16_LAYERS) sbr_gemm_hint(1, 1.0f, 1.0f);
-    else if (layer_gemm_f16(h, grad_a || grad_b)) sbr_gemm_hint(2, grad_a ? 512.0f : 1.0f, grad_b ? 512.0f : 1.0f);
-}
+// Every GemmMode of an engine is built here, from its flags and switches; the launchers keep nothing between calls.
 bool simple_gemm(const sbr_handle* h) { return h->lay.cfg.flags & SBR_FLAG_SIMPLE_GEMM; }
+// nothing stated: operands of unknown range (behind an embedding, loss gradients, the sampled heads) -- bf16x6, or what the flags say
+static GemmMode gemm_mode(const sbr_handle* h, int planes = 0, float sa = 1.0f, float sb = 1.0f) {
+    return GemmMode{simple_gemm(h), (h->lay.cfg.flags & SBR_FLAG_F32_MFMA) != 0, planes, sa, sb};
+}
+// the fp16 split where it is allowed; grad_a / grad_b: that side carries gradients (scaled by 512 on the way in)
+static GemmMode layer_gemm_f16(const sbr_handle* h, bool grad_a, bool grad_b) {
+    const Layout& y = h->lay;
+    if (!h->sw.gemm_f16 || y.cfg.cell == SBR_CELL_VANILLA) return gemm_mode(h);
+    if ((grad_a || grad_b) && !(y.cfg.grad_clip > 0.0f && y.cfg.grad_clip <= 100.0f)) return gemm_mode(h);
+    return gemm_mode(h, 2, grad_a ? 512.0f : 1.0f, grad_b ? 512.0f : 1.0f);
+}
+static GemmMode layer_gemm_mode(const sbr_handle* h, bool grad_a, bool grad_b) {      // layer >= 2: input projection and its backward pair
+    return (h->lay.cfg.flags & SBR_FLAG_BF16_LAYERS) ? gemm_mode(h, 1) : layer_gemm_f16(h, grad_a, grad_b);
+}
+// The projections onto the catalogue take one pass of plain bf16 under SBR_FLAG_BF16_PROJECTION.  The step's logits (h in [-1, 1] x
+// weights), and full_scores': always the exact-f32 kernel otherwise -- a row's scores (hence its ranked ids) must not depend on how many
+// rows share the call (the bf16x6 kernel takes over at >= 96 rows and rounds differently; the one-pass kernel serves any number alike)
+static GemmMode projection_mode(const sbr_handle* h, bool scoring) {
+    const bool bf16p = (h->lay.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
+    GemmMode m = (bf16p || scoring) ? gemm_mode(h) : layer_gemm_f16(h, false, false);
+    m.one_pass = bf16p; m.exact_f32 |= scoring;
+    return m;
+}
+GemmMode scores_gemm_mode(const sbr_handle* h) { return projection_mode(h, true); }
+// the weight-gradient slabs: hs^T . gradients, scaled where the split is taken (WgradPlan.f16)
+static GemmMode wgrad_gemm_mode(const sbr_handle* h, bool f16) { return gemm_mode(h, f16 ? 2 : 3, 1.0f, f16 ? 512.0f : 1.0f); }
 // Does a step over `rows` batch rows take the one-launch sampled head (head_sampled_kernel)?  Asked by the step and by sbr_query.
 bool head_sampled_taken(const sbr_handle* h, int rows) {
     const Layout& y = h->lay;
@@ -265,16 +283,16 @@ static hipError_t catch_up_rows(sbr_handle* h, hipStream_t st, int b, const SbrS
 // ---------------------------------------------------------------------------------------
 // xt = inp . W_in + b for a dense input [T * Bp][n_in_p]: the flattened embeddings, or the outputs of the level below
 // (Lasagne precompute_input [3P], recurrent_layers.py:94-104)
-static hipError_t input_projection(sbr_handle* h, const LayerLayout& ly, const float* inp) {
+static hipError_t input_projection(sbr_handle* h, const LayerLayout& ly, const float* inp, const GemmMode& mode) {
     const Layout& y = h->lay; const int GHp = y.G * ly.Hp;
-    return launch_gemm(h->stream, inp, ly.n_in_p, 1, h->P(ly.p_Win), GHp, 1, h->A(ly.a_xt), GHp, y.T * y.Bp, GHp, ly.n_in_p,
-                       h->P(ly.p_b), nullptr, 0, simple_gemm(h));
+    return launch_gemm(h->stream, mode, gemm_rowmajor(inp, ly.n_in_p), gemm_rowmajor(h->P(ly.p_Win), GHp), h->A(ly.a_xt), GHp,
+                       y.T * y.Bp, GHp, ly.n_in_p, h->P(ly.p_b));
 }
 // Layer 0's input of the forward pass.  Index input: the rows of W_in gathered inside the forward kernel (ra is told where from),
 // or by a launch of their own.  --r_emb: `emb`, the flattened embeddings of this direction, through a dense input projection.
 static int layer0_input(sbr_handle* h, RecArgs& ra, const LayerLayout& ly, const int* idx, const float* emb) {
     const Layout& y = h->lay;
-    if (y.E) { SBR_LAUNCH(input_projection(h, ly, emb)); return SBR_OK; }
+    if (y.E) { SBR_LAUNCH(input_projection(h, ly, emb, gemm_mode(h))); return SBR_OK; }
     if (plan_of(h, ly).fuse_gather) {
         ra.gX = idx; ra.gWin = h->P(ly.p_Win); ra.gbias = h->P(ly.p_b);   // gathered inside the forward kernel
     } else {
@@ -292,30 +310,27 @@ static hipError_t reduce_partials(sbr_handle* h, hipStream_t st, const LayerLayo
 static int whid_grad_gemm(sbr_handle* h, const LayerLayout& ly, const RecArgs& a) {
     const Layout& y = h->lay; hipStream_t s = h->stream;
     const int GHp = y.G * ly.Hp, TB = y.T * y.Bp;
-    const bool sg = simple_gemm(h);
-    float* ws = h->A(y.a_ws);
+    const GemmMode mode = gemm_mode(h);
+    const GemmOperand hsT = gemm_transposed(h->A(ly.a_hs), ly.Hp);
+    float* dWhid = h->Gd(ly.p_Whid); float* ws = h->A(y.a_ws);
     if (y.cfg.cell == SBR_CELL_GRU) {
-        SBR_LAUNCH(launch_gemm(s, h->A(ly.a_hs), 1, ly.Hp, a.dxt, GHp, 1, h->Gd(ly.p_Whid), GHp, ly.Hp, 2 * ly.Hp, TB, nullptr,
-                               ws, y.ws_floats, sg));
-        SBR_LAUNCH(launch_gemm(s, h->A(ly.a_hs), 1, ly.Hp, a.dhi, ly.Hp, 1, h->Gd(ly.p_Whid) + 2 * ly.Hp, GHp, ly.Hp, ly.Hp, TB,
-                               nullptr, ws, y.ws_floats, sg));
+        SBR_LAUNCH(launch_gemm(s, mode, hsT, gemm_rowmajor(a.dxt, GHp), dWhid, GHp, ly.Hp, 2 * ly.Hp, TB, nullptr, ws, y.ws_floats));
+        SBR_LAUNCH(launch_gemm(s, mode, hsT, gemm_rowmajor(a.dhi, ly.Hp), dWhid + 2 * ly.Hp, GHp, ly.Hp, ly.Hp, TB, nullptr, ws, y.ws_floats));
     } else {
-        SBR_LAUNCH(launch_gemm(s, h->A(ly.a_hs), 1, ly.Hp, a.dxt, GHp, 1, h->Gd(ly.p_Whid), GHp, ly.Hp, GHp, TB, nullptr, ws,
-                               y.ws_floats, sg));
+        SBR_LAUNCH(launch_gemm(s, mode, hsT, gemm_rowmajor(a.dxt, GHp), dWhid, GHp, ly.Hp, GHp, TB, nullptr, ws, y.ws_floats));
     }
     return SBR_OK;
 }
 // dense input [T * Bp][n_in_p]: dW_in = inp^T . dxt, d_inp = dxt . W_in^T.  hinted: between recurrent layers both operands' ranges
-// are known (layer_gemm_hint); behind the embedding they are not
+// are known (layer_gemm_mode); behind the embedding they are not
 static int input_grads_dense(sbr_handle* h, const LayerLayout& ly, const RecArgs& a, const float* inp, float* d_inp, bool hinted) {
     const Layout& y = h->lay; hipStream_t s = h->stream;
     const int GHp = y.G * ly.Hp, TB = y.T * y.Bp;
-    const bool sg = simple_gemm(h);
-    if (hinted) layer_gemm_hint(h, false, true);
-    SBR_LAUNCH(launch_gemm(s, inp, 1, ly.n_in_p, a.dxt, GHp, 1, h->Gd(ly.p_Win), GHp, ly.n_in_p, GHp, TB, nullptr, h->A(y.a_ws),
-                           y.ws_floats, sg));
-    if (hinted) layer_gemm_hint(h, true, false);
-    SBR_LAUNCH(launch_gemm(s, a.dxt, GHp, 1, h->P(ly.p_Win), 1, GHp, d_inp, ly.n_in_p, TB, ly.n_in_p, GHp, nullptr, nullptr, 0, sg));
+    const GemmOperand dxt = gemm_rowmajor(a.dxt, GHp);
+    SBR_LAUNCH(launch_gemm(s, hinted ? layer_gemm_mode(h, false, true) : gemm_mode(h), gemm_transposed(inp, ly.n_in_p), dxt, h->Gd(ly.p_Win),
+                           GHp, ly.n_in_p, GHp, TB, nullptr, h->A(y.a_ws), y.ws_floats));
+    SBR_LAUNCH(launch_gemm(s, hinted ? layer_gemm_mode(h, true, false) : gemm_mode(h), dxt, gemm_transposed(h->P(ly.p_Win), GHp), d_inp,
+                           ly.n_in_p, TB, ly.n_in_p, GHp));
     return SBR_OK;
 }
 // the scatter-add of the F*T*B embedding-gradient rows in a_demb into dW_emb (EmbeddingLayer gradient: duplicates accumulate [3P])
@@ -399,8 +414,7 @@ static int forward_uni(sbr_handle* h, bool fork_gate) {
             mark(h, 1);
         } else {   // dense layers: xt = hid_out(l-1) . W_in + b
             const LayerLayout& lo = y.layer[l - 1];
-            layer_gemm_hint(h, false, false);
-            SBR_LAUNCH(input_projection(h, ly, h->A(lo.a_hs) + (size_t)y.Bp * lo.Hp));
+            SBR_LAUNCH(input_projection(h, ly, h->A(lo.a_hs) + (size_t)y.Bp * lo.Hp, layer_gemm_mode(h, false, false)));
         }
         if (l == 0 && (h->st.tail_sorted || fork_gate)) ra.fence_kb = kTailFenceKb;
         if (fork_gate) { ra.start_word = h->step_words + 128; ra.start_epoch = step_next_epoch(&h->fork_epoch); }
@@ -434,7 +448,7 @@ static int forward_bi(sbr_handle* h) {
             if (l == 0) {      // this direction's ids, or its (reversed) flattened embeddings
                 const int rc = layer0_input(h, ra, ly, d ? Xr : h->bX, h->A(d ? y.a_embr : y.a_emb)); if (rc != SBR_OK) return rc;
             } else {           // the (reversed) concatenated outputs of the level below
-                SBR_LAUNCH(input_projection(h, ly, h->A(d ? y.a_catr[l - 1] : y.a_cat[l - 1])));
+                SBR_LAUNCH(input_projection(h, ly, h->A(d ? y.a_catr[l - 1] : y.a_cat[l - 1]), gemm_mode(h)));
             }
             if (l == 0 && d == 1) mark(h, 1);
             SBR_LAUNCH_CHAIN(0, s, launch_rec_forward(s, ra, h->plan[pl]));
@@ -452,7 +466,6 @@ static int forward_bi(sbr_handle* h) {
 
 extern "C" int sbr_forward(sbr_handle* h) {
     CHECK_ARG(h, "null handle");
-    sbr_gemm_set_exact_f32((h->lay.cfg.flags & SBR_FLAG_F32_MFMA) != 0);
     if (!h->have_batch) { sbr_set_error("sbr_forward: no batch set"); return SBR_ESTATE; }
     const Layout& y = h->lay; hipStream_t s = h->stream;
     if (sparse_lazy(h))      // the rows this batch gathers must be current before they are read
@@ -586,20 +599,15 @@ static int dense_head_fused(sbr_handle* h, bool fold, int* keep, bool* done) {
 static int dense_head_launches(sbr_handle* h, bool fold, int* keep) {
     const Layout& y = h->lay; hipStream_t s = h->stream;
     const int R = h->n_rows, Hp = y.HLt, N = y.N, Nl = (N + 3) & ~3;
-    const bool sg = simple_gemm(h), bf16p = (y.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !sg;
     float* lg = h->A(y.a_logits);
-    if (bf16p) sbr_gemm_set_planes(1);
-    else if (layer_gemm_f16(h, false)) sbr_gemm_hint(2, 1.0f, 1.0f);      // h in [-1, 1] x weights
-    const hipError_t ge = launch_gemm(s, h_last(h), Hp, 1, h->P(y.p_WoutT), 1, Hp, lg, Nl, R, N, Hp, nullptr, nullptr, 0, sg);
-    sbr_gemm_set_planes(3);
-    SBR_LAUNCH(ge);
+    SBR_LAUNCH(launch_gemm(s, projection_mode(h, false), gemm_rowmajor(h_last(h), Hp), gemm_transposed(h->P(y.p_WoutT), Hp), lg, Nl, R, N, Hp));
     if (SBR_LOSS_IS_MARGIN(y.cfg.loss))
         SBR_LAUNCH(launch_margin_loss(s, lg, h->P(y.p_bout), h->btgt, y.NT, h->bX, h->blen, y.T, y.F, h->A(y.a_dflt), h->A(y.a_rowcost), R, N, Nl,
                                       y.Bg, y.cfg.loss, y.cfg.balance, y.cfg.unique));
     else
         SBR_LAUNCH(launch_softmax_cce(s, lg, h->P(y.p_bout), h->btgt, h->bpop, h->A(y.a_rowcost), R, N, Nl, y.Bg));
-    SBR_LAUNCH(launch_gemm(s, lg, Nl, 1, h->P(y.p_WoutT), Hp, 1, h->A(y.a_dhlast), Hp, R, Hp, N, nullptr, h->A(y.a_ws), y.ws_floats, sg, 0, 0,
-                           fold ? keep : nullptr));
+    SBR_LAUNCH(launch_gemm(s, gemm_mode(h), gemm_rowmajor(lg, Nl), gemm_rowmajor(h->P(y.p_WoutT), Hp), h->A(y.a_dhlast), Hp, R, Hp, N, nullptr,
+                           h->A(y.a_ws), y.ws_floats, fold ? keep : nullptr));
     return SBR_OK;
 }
 // beside the BPTT chain, on the side stream: cost, db_out (+ bias regulariser), dW_out^T [N][Hp] = dlogits^T . h -- and, in a
@@ -629,7 +637,8 @@ static int dense_head_grads(sbr_handle* h) {
         // data-parallel: every rank adds its share of the bias regulariser, shares sum to reg
         const float reg = y.cfg.regularization * (float)R / (float)y.Bg;
         SBR_LAUNCH(launch_colsum_bias(sd, lg, R, N, Nl, h->Gd(y.p_bout), h->P(y.p_bout), reg, h->cost_ptr(), h->A(y.a_csum)));
-        SBR_LAUNCH(launch_gemm(sd, lg, 1, Nl, hl, Hp, 1, h->Gd(y.p_WoutT), Hp, N, Hp, R, nullptr, h->A(y.a_ws2), y.ws2_floats, sg));
+        SBR_LAUNCH(launch_gemm(sd, gemm_mode(h), gemm_transposed(lg, Nl), gemm_rowmajor(hl, Hp), h->Gd(y.p_WoutT), Hp, N, Hp, R, nullptr,
+                               h->A(y.a_ws2), y.ws2_floats));
     }
     SBR_HIP(hipEventRecord(h->ev_og, sd)); h->st.og_recorded = true;   // output-layer gradients + cost complete
     // Single-call step, dense updates: the output layer is stepped right here, beside the BPTT chain (nothing reads W_out
@@ -677,7 +686,6 @@ static int sampled_cells(sbr_handle* h) {
 static int loss_sampled(sbr_handle* h, bool fill_needed) {
     const Layout& y = h->lay; hipStream_t s = h->stream, sd = h->side;
     const int R = h->n_rows, Hp = y.HLt, C = y.C;
-    const bool sg = simple_gemm(h);
     float* hl = h_last(h);
     int* cells = (int*)h->A(y.a_cells);
     float *Wc = h->A(y.a_Wc), *bc = h->A(y.a_bc), *act = h->A(y.a_act), *dWc = h->A(y.a_dWc), *dbc = h->A(y.a_dbc);
@@ -694,18 +702,18 @@ static int loss_sampled(sbr_handle* h, bool fill_needed) {
         if (head1) SBR_LAUNCH(he);
     }
     if (!head1) {
-        SBR_LAUNCH(launch_gemm(s, hl, Hp, 1, Wc, 1, Hp, act, C, R, C, Hp, nullptr, nullptr, 0, sg));
+        SBR_LAUNCH(launch_gemm(s, gemm_mode(h), gemm_rowmajor(hl, Hp), gemm_transposed(Wc, Hp), act, C, R, C, Hp));
         SBR_LAUNCH(launch_sampled_loss(s, act, bc, h->bpop, h->A(y.a_rowcost), R, y.Bg, y.S, y.cfg.row_offset,
                                        y.cfg.loss, y.Bg));
     }
     // Round 5: dh feeds the BPTT chain, everything else here only feeds the optimizer -- cost sum, bias column sums, the dWc GEMM
     // and the scatter of the cells' gradients (5 launches, ~75 us at C3 beside the side stream's sort) leave the main stream: dh
     // first, one record, the rest on the side stream beside the chain (as the dense heads always did).
-    if (!head1) SBR_LAUNCH(launch_gemm(s, act, C, 1, Wc, Hp, 1, h->A(y.a_dhlast), Hp, R, Hp, C, nullptr, nullptr, 0, sg));
+    if (!head1) SBR_LAUNCH(launch_gemm(s, gemm_mode(h), gemm_rowmajor(act, C), gemm_rowmajor(Wc, Hp), h->A(y.a_dhlast), Hp, R, Hp, C));
     { const int rc = release_side(h, fill_needed); if (rc != SBR_OK) return rc; }
     SBR_LAUNCH(launch_sum_cost(sd, h->A(y.a_rowcost), R, h->cost_ptr()));
     SBR_LAUNCH(launch_colsum_bias(sd, act, R, C, C, dbc, nullptr, 0.0f, nullptr, h->A(y.a_csum)));
-    SBR_LAUNCH(launch_gemm(sd, act, 1, C, hl, Hp, 1, dWc, Hp, C, Hp, R, nullptr, nullptr, 0, sg));
+    SBR_LAUNCH(launch_gemm(sd, gemm_mode(h), gemm_transposed(act, C), gemm_rowmajor(hl, Hp), dWc, Hp, C, Hp, R));
     SBR_LAUNCH(launch_scatter_cells(sd, h->Gd(y.p_WoutT), h->Gd(y.p_bout), dWc, dbc, cells, C, Hp));
     SBR_HIP(hipEventRecord(h->ev_og, sd)); h->st.og_recorded = true;
     if (!fill_needed) {      // the batch-only side work follows (the side stream has waited for this phase's record)
@@ -726,7 +734,6 @@ static int loss_sampled(sbr_handle* h, bool fill_needed) {
 
 extern "C" int sbr_loss_backward_output(sbr_handle* h) {
     CHECK_ARG(h, "null handle");
-    sbr_gemm_set_exact_f32((h->lay.cfg.flags & SBR_FLAG_F32_MFMA) != 0);
     if (!h->fwd_done) { sbr_set_error("sbr_loss_backward_output: call sbr_forward first"); return SBR_ESTATE; }
     const Layout& y = h->lay; hipStream_t s = h->stream, sd = h->side;
     h->grads_clean = false;
@@ -890,8 +897,8 @@ static int backward_tail(sbr_handle* h, RecArgs& a, const WgradPlan& wp, int nbl
     if (!gated) SBR_LAUNCH(launch_tail_gate(sd, words, nwaves, a.prog_epoch, y.T, a.fault));      // (else: at the head of this stream)
     {
         hipError_t we = hipSuccess;
-        if (!launch_gemm_slabs_x6_poll(sd, h->A(ly.a_hs), 1, ly.Hp, a.dxt, GHp, 1, ly.Hp, GHp, K, ws2, n_slabs, GHp, slab,
-                                       gru ? a.dhi : nullptr, ly.Hp, gru ? 2 * ly.Hp : 0, &we, wp.f16 ? 2 : 3, 1.0f, wp.f16 ? 512.0f : 1.0f, pl)) {
+        if (!launch_gemm_slabs_x6_poll(sd, wgrad_gemm_mode(h, wp.f16), gemm_transposed(h->A(ly.a_hs), ly.Hp), gemm_rowmajor(a.dxt, GHp), ly.Hp,
+                                       GHp, K, ws2, n_slabs, GHp, slab, gru ? a.dhi : nullptr, ly.Hp, gru ? 2 * ly.Hp : 0, &we, pl)) {
             sbr_set_error("overlapped tail: the weight-gradient GEMM rejected the shape"); return SBR_EINVAL;
         }
         SBR_LAUNCH(we);
@@ -975,6 +982,7 @@ static int backward_chunked(sbr_handle* h, int l, RecArgs& a, const WgradPlan& w
         SBR_HIP(hipStreamWaitEvent(sd, ev_chain_end, 0));
         // dW_hid [Hp][G*Hp] += hs[t]^T . dhi[t] over the chunk's positions (hs slot t = h_{t-1})
         const float* hsc = h->A(ly.a_hs) + (size_t)a.t_lo * y.Bp * ly.Hp;
+        const GemmOperand hsT = gemm_transposed(hsc, ly.Hp);
         const int Kc = (a.t_hi - a.t_lo) * y.Bp;
         float* slabs = ws2 + (size_t)c * nsl * slab;
         const bool gru = y.cfg.cell == SBR_CELL_GRU;
@@ -986,14 +994,14 @@ static int backward_chunked(sbr_handle* h, int l, RecArgs& a, const WgradPlan& w
         if (sw == s && h->st.og_recorded) SBR_HIP(hipStreamWaitEvent(s, h->ev_og, 0));
         if (!wp.gemm && launch_wgrad_slabs(sw, hsc, dxc, dhcc, slabs, ly.Hp, GHp, Kc, nsl, &we)) {
             SBR_LAUNCH(we);
-        } else if (launch_gemm_slabs_x6(sw, hsc, 1, ly.Hp, dxc, GHp, 1, ly.Hp, GHp, Kc, slabs, nsl, GHp, slab, dhcc, ly.Hp,
-                                        gru ? 2 * ly.Hp : 0, &we, wp.f16 ? 2 : 3, 1.0f, wp.f16 ? 512.0f : 1.0f)) {
+        } else if (launch_gemm_slabs_x6(sw, wgrad_gemm_mode(h, wp.f16), hsT, gemm_rowmajor(dxc, GHp), ly.Hp, GHp, Kc, slabs, nsl, GHp, slab,
+                                        dhcc, ly.Hp, gru ? 2 * ly.Hp : 0, &we)) {
             SBR_LAUNCH(we);     // one bf16x6 GEMM: columns [0, 2Hp) from dxt, the candidate-gate columns from the compact array
         } else if (gru) {   // hid_input grad = [dxt_r | dxt_u | dhi_c]
-            SBR_LAUNCH(launch_gemm_slabs(sw, hsc, 1, ly.Hp, dxc, GHp, 1, ly.Hp, 2 * ly.Hp, Kc, slabs, nsl, GHp, slab));
-            SBR_LAUNCH(launch_gemm_slabs(sw, hsc, 1, ly.Hp, dhcc, ly.Hp, 1, ly.Hp, ly.Hp, Kc, slabs + 2 * ly.Hp, nsl, GHp, slab));
+            SBR_LAUNCH(launch_gemm_slabs(sw, gemm_mode(h), hsT, gemm_rowmajor(dxc, GHp), ly.Hp, 2 * ly.Hp, Kc, slabs, nsl, GHp, slab));
+            SBR_LAUNCH(launch_gemm_slabs(sw, gemm_mode(h), hsT, gemm_rowmajor(dhcc, ly.Hp), ly.Hp, ly.Hp, Kc, slabs + 2 * ly.Hp, nsl, GHp, slab));
         } else {
-            SBR_LAUNCH(launch_gemm_slabs(sw, hsc, 1, ly.Hp, dxc, GHp, 1, ly.Hp, GHp, Kc, slabs, nsl, GHp, slab));
+            SBR_LAUNCH(launch_gemm_slabs(sw, gemm_mode(h), hsT, gemm_rowmajor(dxc, GHp), ly.Hp, GHp, Kc, slabs, nsl, GHp, slab));
         }
     }
     SBR_LAUNCH(launch_splitk_reduce(sw, ws2, nc * nsl, ly.Hp, GHp, h->Gd(ly.p_Whid), GHp, nullptr));
@@ -1157,7 +1165,6 @@ static int backward_bi(sbr_handle* h) {
 
 extern "C" int sbr_backward_recurrent(sbr_handle* h) {
     CHECK_ARG(h, "null handle");
-    sbr_gemm_set_exact_f32((h->lay.cfg.flags & SBR_FLAG_F32_MFMA) != 0);
     if (!h->fwd_done) { sbr_set_error("sbr_backward_recurrent: call sbr_forward first"); return SBR_ESTATE; }
     h->grads_clean = false;
     return h->lay.D == 2 ? backward_bi(h) : backward_uni(h);

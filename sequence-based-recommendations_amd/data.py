@@ -265,7 +265,9 @@ class DataHandler(object):
                     for line in f:
                         pop[int(line.split()[1])] += 1
                 self.training_set._item_pop = pop
-                np.save(cache, pop)
+                tmp = "%s.%d.tmp.npy" % (cache, os.getpid())      # (another rank may look for the cache while this one writes it)
+                np.save(tmp, pop)
+                os.replace(tmp, cache)
         return self.training_set._item_pop
 
     def _get_path(self, dirname):
