@@ -514,6 +514,42 @@ int sbr_evaluate_ranks(sbr_handle* h, sbr_dataset* d, const int32_t* users, int6
                        int32_t* n_rankable_host);  /* [n] */
 
 /* ------------------------------------------------------------------------------------------------
+ * The rank of the NEXT item at every position of a sequence (added under ABI 11: one symbol and one constant, no struct change) --
+ * sbr_evaluate_ranks' sibling.  Where every other evaluation call asks one question per user (split in the middle, rank once), this
+ * one reads every state ONE forward pass leaves.  User users[j] has items x_0 .. x_{L-1}; T = max_length, m = min_history >= 1:
+ *   fed        the first F = min(L - 1, T) items, from the START of the sequence (not the window of the viewed half);
+ *   positions  p = m .. F: the state is slot p of the top layer (the state after p items), the goal is x_p;
+ *   count      n_pos(j) = max(0, F - m + 1); positions beyond T are not evaluated.
+ * User j's results are [pos_off[j], pos_off[j + 1]), in order of p:
+ *   ranks[pos_off[j] + p - m]       the number of rankable items i with a better score than x_p, or an equal score and i < x_p, among
+ *                                   the scores sbr_rank would rank for a row fed x_0 .. x_{p-1} (the same projection launches, the
+ *                                   same order: key descending, ties to the lowest id); -1 when x_p itself is not rankable (NaN,
+ *                                   -inf, excluded, outside the catalogue);
+ *   n_rankable[pos_off[j] + p - m]  the rankable items at that position.
+ * exclude_mode: SBR_EVAL_EXCL_NONE, or SBR_EVAL_EXCL_PREFIX: the distinct ids among x_0 .. x_{p-1} are not rankable at position p --
+ * what SBR_EVAL_EXCL_VIEWED means for a user whose viewed half is that prefix.  The two agree, value for value, with
+ * sbr_evaluate_ranks (NONE / VIEWED) on an explicit user x_0 .. x_{p-1}, x_p padded to length 2p or 2p + 1 (tests/test_gpu_eval_positions.py).
+ * Per chunk of local_batch users: pack, one forward pass, first-occurrence flags of the rows, then per group of consecutive positions
+ * one projection of their slots (sbr_query "next_rank_slots": up to 8 per GEMM launch where their scores fit 64 MB of scratch; 1 under
+ * SBR_FLAG_BF16_PROJECTION, whose kernel chooses its tile by the row count) and one counting launch (ev_next_rank_kernel,
+ * sbr_eval.hip: one streamed pass over the N scores per row and position, integer counts, nothing written to the scores; sbr_query
+ * "next_rank_form": 1 16-byte loads, 2 4-byte loads -- N no multiple of 4 --, 0 no call yet).  Everything on the engine's stream, no host wait between; the call waits once, at its end.  users may repeat;
+ * the handle is left as sbr_set_batch leaves it.  pos_off follows from the lengths alone: computed on the host and written before
+ * anything is launched.
+ * SBR_EINVAL, found before anything is launched (nothing but pos_off -- and that only once cap is known to suffice -- is written, the
+ * engine stays usable): everything sbr_evaluate rejects (k does not exist here), a mode other than the two above, min_history < 1, a
+ * bidirectional engine (a backwards layer's state at p has seen what lies behind p), a NULL output, cap < pos_off[n]
+ * (sbr_last_error names the count needed).  Parameters, gradients and optimizer state are the same bits after the call as before
+ * it, by the keep-and-restore sbr_evaluate_ranks describes.  Scratch: the handle's ranking scratch (users, n + 1 offsets, twice
+ * pos_off[n] words, local_batch x T flags, the scores of a group of slots; the copy of parameters and optimizer state as for sbr_evaluate_ranks). */
+#define SBR_EVAL_EXCL_PREFIX 4       /* sbr_evaluate_positions only: at position p the distinct items of x_0 .. x_{p-1} are never ranked */
+int sbr_evaluate_positions(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int min_history, int exclude_mode,
+                           int64_t* pos_off_host,      /* [n + 1]: user j's positions are [pos_off[j], pos_off[j + 1]); pos_off[0] = 0 */
+                           int32_t* ranks_host,        /* [cap] */
+                           int32_t* n_rankable_host,   /* [cap] */
+                           int64_t cap);               /* must be >= pos_off[n] = sum over users of max(0, min(L - 1, T) - min_history + 1) */
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation of whole users of a cluster model on the device (added under ABI 11: one symbol and one struct, nothing existing
  * changes) -- sbr_evaluate for `--clusters C`: RNNCluster._compute_validation_metrics (rnn_cluster.py:409-438, one compiled test
  * function call per user) and test.py:61-76 (one top_k_recommendations call per user).  Users are split, fed, chunked

@@ -852,15 +852,23 @@ extern "C" int sbr_dense_ranges(sbr_handle* h, int cap, int64_t* lo, int64_t* hi
 // ---------------------------------------------------------------------------------------
 // predict (the ranking calls, sbr_topk among them: sbr_rank_api.hip)
 // ---------------------------------------------------------------------------------------
-int full_scores(sbr_handle* h, int do_softmax) {
+// The projection of `n_rows` rows of states `rows_in` [n_rows][HLt] into scores `out` [n_rows][N]: the GEMM in scores_gemm_mode, then
+// the bias pass.  ONE statement of the launch pair, so that whatever state is projected -- h_last into a_logits (full_scores), one or
+// several slots of the top layer's a_hs (sbr_evaluate_positions) -- gives the floats sbr_rank ranks for a row in that state: in
+// scores_gemm_mode (exact f32 without a workspace, hence without split-K; or the one-pass bf16 kernel) an output element is one
+// accumulation chain over K whose order does not depend on the rows a launch carries (projection_mode, sbr_step.hip).
+int project_rows(sbr_handle* h, const float* rows_in, int n_rows, float* out, int do_softmax) {
     const Layout& y = h->lay;
+    SBR_LAUNCH(launch_gemm(h->stream, scores_gemm_mode(h), gemm_rowmajor(rows_in, y.HLt), gemm_transposed(h->P(y.p_WoutT), y.HLt), out, y.N,
+                           n_rows, y.N, y.HLt));
+    SBR_LAUNCH(launch_softmax_rows(h->stream, out, h->P(y.p_bout), n_rows, y.N, do_softmax));
+    return SBR_OK;
+}
+
+int full_scores(sbr_handle* h, int do_softmax) {
     int rc;
     if ((rc = forward_current(h)) != SBR_OK) return rc;    // every item is scored: all of W_out^T / b_out must be current
-    float* lg = h->A(y.a_logits);
-    SBR_LAUNCH(launch_gemm(h->stream, scores_gemm_mode(h), gemm_rowmajor(h_last(h), y.HLt), gemm_transposed(h->P(y.p_WoutT), y.HLt), lg, y.N,
-                           h->n_rows, y.N, y.HLt));
-    SBR_LAUNCH(launch_softmax_rows(h->stream, lg, h->P(y.p_bout), h->n_rows, y.N, do_softmax));
-    return SBR_OK;
+    return project_rows(h, h_last(h), h->n_rows, h->A(h->lay.a_logits), do_softmax);
 }
 
 extern "C" int sbr_predict_scores(sbr_handle* h, int probs, float* out_host) {
@@ -987,6 +995,9 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     // the LAST sbr_evaluate_ranks: 0 none yet, 1 the row's keys stayed in LDS, 2 every pass streamed the row; and the goal items of a pass
     else if (w == "goal_rank_form") *value = h->last_goal_rank_form;
     else if (w == "goal_rank_tile") *value = kGoalRankTile;
+    // the LAST sbr_evaluate_positions: 0 none yet, 1 the score row was read in 16-byte loads, 2 in 4-byte loads (N no multiple of 4)
+    else if (w == "next_rank_form") *value = h->last_next_rank_form;
+    else if (w == "next_rank_slots") *value = h->last_next_rank_slots;      // ... and the positions it projected per GEMM launch at the most (0 no call yet)
     else if (w == "row_aware_update") *value = h->last_row_aware ? 1 : 0;      // ... and whether its optimizer pass over W_in was the row-aware one
     else if (w == "cluster") *value = top.needs_fill ? 1 : 0;      // the cluster kernels (the family that wants the sentinel fill)
     else if (w == "rec_kernel") *value = top.family;               // 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other

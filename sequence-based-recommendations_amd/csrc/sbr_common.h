@@ -187,6 +187,8 @@ ScatPlan sbr_scat_plan(int GHp, int Ep, int n_ids, int entries, int D, bool atom
 constexpr int kRankThreads = 1024;        // threads of a row's workgroup in the select and sort kernels (16 waves: one id segment each)
 constexpr int kRankLdsRow = 32768;        // longest row whose keys stay in LDS during the select (128 KB of the CU's 160 KB; C4's 26 744 fits)
 constexpr int kRankSortLds = 2048;        // largest k the LDS bitonic sort takes (16 KB of 64-bit composites); above: the LSD radix sort in scratch
+constexpr int kNextRankSlots = 8;         // sbr_evaluate_positions: positions projected per GEMM launch at the most (consecutive slots of a_hs) ...
+constexpr size_t kNextRankScoreBytes = (size_t)64 << 20;   // ... as long as their scores fit this much ranking scratch; one slot otherwise
 constexpr int kGoalRankTile = 1024;       // goal items ev_goal_rank_kernel ranks per pass over the row (sbr_eval.hip): one per thread; 8 KB of composites
                                           // + 4 KB of counts beside the 128 KB row = 140.1 KB of the CU's 160 KB
 static_assert(kGoalRankTile == kRankThreads, "ev_goal_rank_kernel: a thread owns one goal item of the tile and one word of its scan");
@@ -220,6 +222,27 @@ static_assert(SBR_SPLIT_IS(2, 0, 1, 1, 1) && SBR_SPLIT_IS(2, 1, 1, 1, 0) && SBR_
 static_assert(SBR_SPLIT_IS(3, 0, 1, 2, 1) && SBR_SPLIT_IS(3, 1, 1, 2, 0) && SBR_SPLIT_IS(3, 2, 1, 2, 0), "L = 3: the odd item belongs to the goal");
 static_assert(SBR_SPLIT_IS(7, 2, 3, 4, 1) && SBR_SPLIT_IS(7, 3, 3, 4, 0) && SBR_SPLIT_IS(7, 4, 3, 4, 0), "L = 7: the window is the END of the viewed half");
 #undef SBR_SPLIT_IS
+
+// How sbr_evaluate_positions reads the same sequence x_0 .. x_{L-1}, the one statement of that rule: the row fed is the
+// first fed = min(L - 1, T) items, FROM THE START of the sequence -- not the window of the viewed half --, and every position
+// p = min_history .. fed is evaluated: the state is slot p of the top layer's a_hs (the state after p items), the goal is x_p.
+// Positions beyond T are not evaluated.  Built like UserSplit, from the user's two offsets, the engine's T and the call's min_history.
+struct UserPrefix {
+    int L, fed, first;
+    __host__ __device__ constexpr UserPrefix(long long off_lo, long long off_hi, int T, int min_history)
+        : L((int)(off_hi - off_lo)), fed(L < 1 ? 0 : (L - 1 < T ? L - 1 : T)), first(min_history) {}
+    __host__ __device__ constexpr int n_pos() const { return fed >= first ? fed - first + 1 : 0; }
+    __host__ __device__ constexpr int first_pos() const { return first; }
+    __host__ __device__ constexpr int last_pos() const { return fed; }
+    __host__ __device__ constexpr int place(int p) const { return p - first; }      // of position p among the user's results
+};
+#define SBR_PREFIX_IS(L, T, M, FED, NP) (UserPrefix(100, 100 + (L), (T), (M)).fed == (FED) && UserPrefix(100, 100 + (L), (T), (M)).n_pos() == (NP))
+// (L, T, min_history) -> items fed, positions; L - 1 shorter than, equal to and longer than T
+static_assert(SBR_PREFIX_IS(2, 6, 1, 1, 1) && SBR_PREFIX_IS(2, 6, 2, 1, 0) && SBR_PREFIX_IS(1, 6, 1, 0, 0), "L = 2: one item fed, one position; L = 1: none");
+static_assert(SBR_PREFIX_IS(5, 6, 1, 4, 4) && SBR_PREFIX_IS(7, 6, 1, 6, 6) && SBR_PREFIX_IS(8, 6, 1, 6, 6) && SBR_PREFIX_IS(40, 6, 1, 6, 6), "never more than T items fed");
+static_assert(SBR_PREFIX_IS(4, 6, 3, 3, 1) && SBR_PREFIX_IS(3, 6, 3, 2, 0) && SBR_PREFIX_IS(40, 6, 3, 6, 4), "positions start at min_history");
+static_assert(UserPrefix(100, 140, 6, 3).place(3) == 0 && UserPrefix(100, 140, 6, 3).place(6) == 3, "results in order of p");
+#undef SBR_PREFIX_IS
 
 // Every environment switch the library reads (README.md "Switches"), with its default.  sbr_read_switches (sbr_api.hip) fills one
 // per engine, inside sbr_create, and nothing reads the environment afterwards: an engine keeps the values it was created under.
@@ -367,6 +390,8 @@ struct sbr_handle {
     // sbr_rank: scratch outside the arena (grown on demand, freed by sbr_destroy) and what the last call ran (sbr_query "rank_select" / "rank_sort")
     void* rank_scratch = nullptr; size_t rank_scratch_bytes = 0; int last_rank_select = 0, last_rank_sort = 0;
     int last_goal_rank_form = 0;                                          // sbr_evaluate_ranks: 0 none yet, 1 the row's keys in LDS, 2 streamed
+    int last_next_rank_form = 0;                                          // sbr_evaluate_positions: 0 none yet, 1 16-byte loads of the score row, 2 4-byte loads
+    int last_next_rank_slots = 0;                                         // ... and the positions it projected per GEMM launch at the most
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
@@ -435,6 +460,7 @@ bool simple_gemm(const sbr_handle* h);               // SBR_FLAG_SIMPLE_GEMM: th
 float* h_last(sbr_handle* h);                        // the user representation of the current batch, [Bp][HLt]
 int check_fault(sbr_handle* h);                      // synchronises the stream; fails the call if a bounded wait of its kernels gave up
 int full_scores(sbr_handle* h, int do_softmax);      // forward_current + the projection into a_logits: the scores of every item
+int project_rows(sbr_handle* h, const float* rows_in, int n_rows, float* out, int do_softmax);   // full_scores' launch pair on any [n_rows][HLt] matrix of states
 int forward_current(sbr_handle* h);                  // (sbr_rank_api.hip) forward pass if the batch has none yet + lazily stepped output rows flushed
 // What the cluster head's native training step (sbr_cluster.hip: sbr_cluster_train_step_lagged) needs of its neighbours
 struct sbr_dataset;
@@ -846,6 +872,17 @@ hipError_t launch_ev_hits(hipStream_t s, const SbrEvalView& v, const int* users,
 // 2: streamed)
 hipError_t launch_ev_goal_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* goal_off, int rows, int N,
                                const float* scores, int* ranks, int* n_rankable, int* form);
+// sbr_evaluate_positions (include/sbr_rnn.h; UserPrefix above).  The rows fed: the first min(L - 1, T) items of every user, otherwise
+// what launch_ev_pack writes
+hipError_t launch_ev_pack_prefix(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop);
+// first[r][q] = 1 iff the item at place q of row r of X does not occur at a place in front of q (q < lengths[r]; the rest is not written)
+hipError_t launch_ev_first_seen(hipStream_t s, const int* X, const int* lengths, int rows, int T, int F, int* first);
+// positions p = p0 .. p0 + slots - 1 of every row r with p <= lengths[r]: the rank of x_p = items[off[users[r]] + p] among the scores
+// scores[(p - p0) * slot_stride + r * N ..] and the row's rankable items, at pos_off[r] + p - min_history of ranks / n_rankable;
+// exclude_prefix: the items flagged in first[r][0 .. p) are taken out
+hipError_t launch_ev_next_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* pos_off, const int* X, const int* lengths,
+                               const int* first, int rows, int T, int F, int N, int p0, int slots, int min_history, int exclude_prefix,
+                               const float* scores, size_t slot_stride, int* ranks, int* n_rankable, int* form);
 // sbr_cluster_eval.hip: what sbr_cluster_evaluate needs beyond the kernels above (include/sbr_rnn.h)
 hipError_t launch_cev_transpose(hipStream_t s, const float* hard, int N, int C, float* hardT);
 // prod[r][i] = softmax(logits[r])[i] * hardT[csel[r]][i] (logits: biased, untouched by any exclusion), then with zero_fed +0.0 at the

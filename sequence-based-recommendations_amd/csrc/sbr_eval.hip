@@ -6,6 +6,10 @@
 //   2. ev_hits_kernel      the ordered top-k against the goal: counts, the hit mask, per-item hit counts
 // and, for sbr_evaluate_ranks, in place of select + sort + 2:
 //   3. ev_goal_rank_kernel the place of every goal item in the row's complete ranking, counted and never sorted out
+// and, for sbr_evaluate_positions (the next item at every position of a sequence, from the states one forward pass leaves):
+//   4. ev_pack_kernel<true>  the rows fed: the START of every user's sequence (UserPrefix)
+//   5. ev_first_seen_kernel  per place of a row, whether its item occurs there for the first time
+//   6. ev_next_rank_kernel   per position p, the place of x_p among the scores projected from slot p: one streamed count
 // What of a user's sequence is viewed, fed (the window) and the goal: UserSplit (sbr_common.h).
 // Rows are independent in every kernel; nothing waits on another workgroup.
 #include "sbr_common.h"
@@ -14,6 +18,9 @@
 namespace {
 
 // One wave per row of the batch buffers (what bb_pack_kernel writes for a training row, without targets and samples).
+// PREFIX: the split policy -- false: UserSplit's window (the end of the viewed half); true: UserPrefix's fed items (the start of the
+// sequence, sbr_evaluate_positions).
+template <bool PREFIX>
 __global__ void __launch_bounds__(64) ev_pack_kernel(const int* __restrict__ items, const int* __restrict__ rate, const long long* __restrict__ off,
                                                      const int* __restrict__ users, int n_items, int rows, int T, int F, int* __restrict__ X,
                                                      int* __restrict__ lengths, float* __restrict__ pop) {
@@ -26,7 +33,9 @@ __global__ void __launch_bounds__(64) ev_pack_kernel(const int* __restrict__ ite
     const int u = users[b];
     const long long o = off[u];
     const UserSplit sp(o, off[u + 1], T);
-    const int start = sp.window_begin(), n_in = sp.window_end() - start;   // rnn_base.py:410: at most max_length items before the split
+    const UserPrefix pf(o, off[u + 1], T, 1);
+    // rnn_base.py:410: at most max_length items before the split; PREFIX: at most max_length items from the start, the last item never
+    const int start = PREFIX ? 0 : sp.window_begin(), n_in = PREFIX ? pf.fed : sp.window_end() - start;
     for (int t = lane; t < T; t += 64) {
         X[((size_t)b * T + t) * F] = t < n_in ? items[o + start + t] : 0;
         if (F == 2) X[((size_t)b * T + t) * F + 1] = t < n_in ? n_items + rate[o + start + t] : 0;   // rnn_base.py:637-642
@@ -188,11 +197,133 @@ __global__ void __launch_bounds__(kRankThreads) ev_goal_rank_kernel(const int* _
     if (tid == 0) n_rankable[r] = (int)nrk[0];
 }
 
+// ---- sbr_evaluate_positions: the place of the NEXT item at every position of a row (UserPrefix, sbr_common.h)
+// first[r][q] = 1 iff the item at place q of row r occurs at no place in front of q.  One workgroup per row, a thread per place,
+// O(len^2) reads of a row of at most T ids, once per chunk: with the flags, taking the distinct items of the prefix x_0 .. x_{p-1} out
+// of position p's counts is one pass over p places, not a search per place.
+constexpr int kFirstSeenThreads = 256;
+__global__ void __launch_bounds__(kFirstSeenThreads) ev_first_seen_kernel(const int* __restrict__ X, const int* __restrict__ lengths, int T, int F,
+                                                                          int* __restrict__ first) {
+    const int r = blockIdx.x;
+    const int len = min(lengths[r], T);
+    const int* x = X + (size_t)r * T * F;
+    for (int q = threadIdx.x; q < len; q += kFirstSeenThreads) {
+        const int id = x[(size_t)q * F];
+        int seen = 0;
+        for (int j = 0; j < q; ++j) seen |= (x[(size_t)j * F] == id);
+        first[(size_t)r * T + q] = seen ? 0 : 1;
+    }
+}
+
+// Position p of every row: one workgroup per (row, slot of the launch), rows with fewer than p items fed leave at once.  A slot's
+// scores are the projection of slot p = p0 + blockIdx.y of the top layer's states -- what sbr_rank would rank for a row fed
+// x_0 .. x_{p-1} -- and are only read.  The goal x_p comes from the
+// dataset's CSR (the row holds the items FED: x_p is fed only when a later position exists).  One streamed pass over the N scores
+// counts, in integers, the rankable items (key != 0) and those whose composite key << 32 | ~id is larger than the goal's (sbr_rank's
+// order: key descending, ties to the lowest id); VEC: in 16-byte loads (N a multiple of 4: every row of scores then starts on a
+// 16-byte boundary).  With exclude_prefix the flagged (= distinct) items of the prefix are taken back out of both counts, and the goal
+// is never ranked when it is one of them.  Wave reduction by shuffles, then thread 0 adds the waves in order.
+constexpr int kNextRankWaves = kRankThreads / 64;
+struct NextCount { unsigned nr, ahead; };
+__device__ __forceinline__ void next_count(float v, int i, unsigned long long gcomp, NextCount& c) {
+    const unsigned key = rank_key(v);
+    if (key == 0u) return;
+    ++c.nr;
+    const unsigned long long comp = ((unsigned long long)key << 32) | (unsigned long long)(0xffffffffu - (unsigned)i);
+    c.ahead += comp > gcomp ? 1u : 0u;
+}
+template <bool VEC>
+__global__ void __launch_bounds__(kRankThreads) ev_next_rank_kernel(const int* __restrict__ items, const long long* __restrict__ off,
+                                                                    const int* __restrict__ users, const long long* __restrict__ pos_off,
+                                                                    const int* __restrict__ X, const int* __restrict__ lengths,
+                                                                    const int* __restrict__ first, int T, int F, int N, int p0, int min_history,
+                                                                    int exclude_prefix, const float* __restrict__ scores, size_t slot_stride,
+                                                                    int* __restrict__ ranks, int* __restrict__ n_rankable) {
+    __shared__ unsigned s_w[kNextRankWaves][5];
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nthreads = blockDim.x;
+    const int p = p0 + blockIdx.y;                                 // slot blockIdx.y of the launch holds the scores of position p0 + blockIdx.y
+    if (p > lengths[r]) return;                                    // (uniform over the workgroup) the row has no position p
+    const int gid = items[off[users[r]] + p];                      // p <= fed <= L - 1: inside the user's sequence
+    const float* row = scores + (size_t)blockIdx.y * slot_stride + (size_t)r * N;
+    const bool gin = (unsigned)gid < (unsigned)N;                  // an id outside the catalogue is never ranked
+    const unsigned gkey = gin ? rank_key(row[gid]) : 0u;
+    const unsigned long long gcomp = ((unsigned long long)gkey << 32) | (unsigned long long)(0xffffffffu - (unsigned)gid);
+    NextCount c{0u, 0u};
+    if (VEC) {
+        const float4* row4 = (const float4*)row;
+        for (int i4 = tid; i4 < N / 4; i4 += nthreads) {
+            const float4 v = row4[i4];
+            next_count(v.x, 4 * i4, gcomp, c); next_count(v.y, 4 * i4 + 1, gcomp, c);
+            next_count(v.z, 4 * i4 + 2, gcomp, c); next_count(v.w, 4 * i4 + 3, gcomp, c);
+        }
+    } else
+        for (int i = tid; i < N; i += nthreads) next_count(row[i], i, gcomp, c);
+    // the distinct items of the prefix: out of both counts; a thread per place of the row
+    NextCount x{0u, 0u};
+    unsigned gone = 0u;
+    if (exclude_prefix) {
+        const int* xr = X + (size_t)r * T * F;
+        const int* fr = first + (size_t)r * T;
+        for (int q = tid; q < p; q += nthreads) {                  // p <= lengths[r] <= T
+            if (!fr[q]) continue;
+            const int id = xr[(size_t)q * F];
+            if ((unsigned)id >= (unsigned)N) continue;
+            next_count(row[id], id, gcomp, x);
+            gone |= (id == gid) ? 1u : 0u;
+        }
+    }
+    unsigned v0 = c.nr, v1 = c.ahead, v2 = x.nr, v3 = x.ahead;
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) {
+        v0 += __shfl_xor(v0, o2); v1 += __shfl_xor(v1, o2); v2 += __shfl_xor(v2, o2); v3 += __shfl_xor(v3, o2);
+        gone |= __shfl_xor(gone, o2);
+    }
+    if (lane == 0) { s_w[w][0] = v0; s_w[w][1] = v1; s_w[w][2] = v2; s_w[w][3] = v3; s_w[w][4] = gone; }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned nr = 0, ahead = 0, xnr = 0, xahead = 0, g = 0;
+        for (int i = 0; i < nthreads / 64; ++i) {
+            nr += s_w[i][0]; ahead += s_w[i][1]; xnr += s_w[i][2]; xahead += s_w[i][3]; g |= s_w[i][4];
+        }
+        const long long at = pos_off[r] + (p - min_history);
+        ranks[at] = (gkey == 0u || g) ? -1 : (int)(ahead - xahead);
+        n_rankable[at] = (int)(nr - xnr);
+    }
+}
+
 }  // namespace
 
 hipError_t launch_ev_pack(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop) {
     if (Bp <= 0) return hipSuccess;
-    ev_pack_kernel<<<Bp, 64, 0, s>>>(v.items, v.rate, v.off, users, v.n_items, rows, T, F, X, lengths, pop);
+    ev_pack_kernel<false><<<Bp, 64, 0, s>>>(v.items, v.rate, v.off, users, v.n_items, rows, T, F, X, lengths, pop);
+    return hipGetLastError();
+}
+
+hipError_t launch_ev_pack_prefix(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop) {
+    if (Bp <= 0) return hipSuccess;
+    ev_pack_kernel<true><<<Bp, 64, 0, s>>>(v.items, v.rate, v.off, users, v.n_items, rows, T, F, X, lengths, pop);
+    return hipGetLastError();
+}
+
+hipError_t launch_ev_first_seen(hipStream_t s, const int* X, const int* lengths, int rows, int T, int F, int* first) {
+    if (rows <= 0) return hipSuccess;
+    ev_first_seen_kernel<<<rows, kFirstSeenThreads, 0, s>>>(X, lengths, T, F, first);
+    return hipGetLastError();
+}
+
+hipError_t launch_ev_next_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* pos_off, const int* X, const int* lengths,
+                               const int* first, int rows, int T, int F, int N, int p0, int slots, int min_history, int exclude_prefix,
+                               const float* scores, size_t slot_stride, int* ranks, int* n_rankable, int* form) {
+    const bool vec = N % 4 == 0 && slot_stride % 4 == 0;
+    *form = vec ? 1 : 2;
+    if (rows <= 0 || slots <= 0) return hipSuccess;
+    // a thread takes a few 16-byte loads at least: 256 threads up to 16 384 items, the select kernels' 1024 above
+    const int threads = N <= 16384 ? 256 : kRankThreads;
+    const dim3 grid(rows, slots);
+    if (vec) ev_next_rank_kernel<true><<<grid, threads, 0, s>>>(v.items, v.off, users, pos_off, X, lengths, first, T, F, N, p0, min_history,
+                                                                exclude_prefix, scores, slot_stride, ranks, n_rankable);
+    else ev_next_rank_kernel<false><<<grid, threads, 0, s>>>(v.items, v.off, users, pos_off, X, lengths, first, T, F, N, p0, min_history,
+                                                             exclude_prefix, scores, slot_stride, ranks, n_rankable);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_topk, sbr_rank, sbr_evaluate, sbr_evaluate_ranks,
-// sbr_cluster_rank, sbr_cluster_evaluate.
+// sbr_evaluate_positions, sbr_cluster_rank, sbr_cluster_evaluate.
 // Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_cluster_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
 // sbr_api.hip), built from the shared pieces below: scores, ONE exclusion launch per ranking (launch_exclude: what
 // is excluded is an ExclSources, where it lands an ExclCatalogue or ExclCluster, sbr_device.h), select and sort (rank_rows).
@@ -178,15 +178,16 @@ static int eval_check_args(sbr_handle* h, sbr_dataset* d, const int32_t* users, 
     return sbr_dataset_eval_view(d, &v, 1);      // (first call for this dataset: sorts and uploads the goals)
 }
 
-// a chunk's rows become the current batch, in set 0, as sbr_set_batch would leave it
-static int eval_pack_chunk(sbr_handle* h, const SbrEvalView& v, const int* dusers, int rows) {
+// a chunk's rows become the current batch, in set 0, as sbr_set_batch would leave it; prefix: the rows hold the start of every user's
+// sequence (UserPrefix, sbr_evaluate_positions) where they otherwise hold the window of its viewed half (UserSplit)
+static int eval_pack_chunk(sbr_handle* h, const SbrEvalView& v, const int* dusers, int rows, bool prefix = false) {
     const Layout& y = h->lay;
     hipStream_t s = h->stream;
     h->bX = (const int*)h->A(y.a_X); h->blen = (const int*)h->A(y.a_len); h->btgt = (const int*)h->A(y.a_tgt);
     h->bsmp = (const int*)h->A(y.a_smp); h->bpop = h->A(y.a_pop);
     h->bb_set = 0; h->bb_unread = false;
     if (rows < y.Bp && SBR_LOSS_IS_MARGIN(y.cfg.loss)) SBR_HIP(hipMemsetAsync(h->A(y.a_tgt), 0xFF, (size_t)y.Bp * y.NT * sizeof(int), s));   // no positives
-    SBR_LAUNCH(launch_ev_pack(s, v, dusers, rows, y.Bp, y.T, y.F, (int*)h->A(y.a_X), (int*)h->A(y.a_len), h->A(y.a_pop)));
+    SBR_LAUNCH((prefix ? launch_ev_pack_prefix : launch_ev_pack)(s, v, dusers, rows, y.Bp, y.T, y.F, (int*)h->A(y.a_X), (int*)h->A(y.a_len), h->A(y.a_pop)));
     h->n_rows = rows; h->have_batch = true; h->fwd_done = false;
     return SBR_OK;
 }
@@ -292,6 +293,42 @@ extern "C" int sbr_evaluate(sbr_handle* h, sbr_dataset* d, const int32_t* users,
     return check_fault(h);          // a forward that gave up must not hand out rankings; the call's one wait for the device
 }
 
+// Lazily stepped rows are brought up to date where a call reads them, and WHERE a replay of missed steps is split changes float32
+// roundings (sbr_sparse.hip): a training run with such a call in its middle would differ in the last bit from one without.  So once
+// steps have been applied, sbr_evaluate_ranks and sbr_evaluate_positions keep the parameters, the optimizer state and the rows'
+// last-step words in the ranking scratch and put them back behind the last chunk.
+struct LazyKeep {
+    bool keep = false;
+    size_t np_bytes = 0, o_kp = 0, o_ks = 0, o_kl[2] = {0, 0};
+    void carve(Carver& cv, const sbr_handle* h) {
+        const Layout& y = h->lay;
+        keep = sparse_lazy(h) && h->step_count > 0;
+        np_bytes = y.n_params * sizeof(float);
+        o_kp = cv.take(keep ? np_bytes : 0); o_ks = cv.take(keep ? y.n_state_arrays * np_bytes : 0);
+        for (int b = 0; b < y.n_sparse; ++b) o_kl[b] = cv.take(keep ? (size_t)y.sparse[b].n_rows * sizeof(int) : 0);
+    }
+    int save(sbr_handle* h, char* S) const {
+        if (!keep) return SBR_OK;
+        const Layout& y = h->lay;
+        hipStream_t s = h->stream;
+        SBR_HIP(hipMemcpyAsync(S + o_kp, h->P(0), np_bytes, hipMemcpyDeviceToDevice, s));
+        SBR_HIP(hipMemcpyAsync(S + o_ks, h->St(0, 0), y.n_state_arrays * np_bytes, hipMemcpyDeviceToDevice, s));
+        for (int b = 0; b < y.n_sparse; ++b)
+            SBR_HIP(hipMemcpyAsync(S + o_kl[b], h->A(y.sparse[b].a_last), (size_t)y.sparse[b].n_rows * sizeof(int), hipMemcpyDeviceToDevice, s));
+        return SBR_OK;
+    }
+    int restore(sbr_handle* h, char* S) const {
+        if (!keep) return SBR_OK;
+        const Layout& y = h->lay;
+        hipStream_t s = h->stream;
+        SBR_HIP(hipMemcpyAsync(h->P(0), S + o_kp, np_bytes, hipMemcpyDeviceToDevice, s));
+        SBR_HIP(hipMemcpyAsync(h->St(0, 0), S + o_ks, y.n_state_arrays * np_bytes, hipMemcpyDeviceToDevice, s));
+        for (int b = 0; b < y.n_sparse; ++b)
+            SBR_HIP(hipMemcpyAsync(h->A(y.sparse[b].a_last), S + o_kl[b], (size_t)y.sparse[b].n_rows * sizeof(int), hipMemcpyDeviceToDevice, s));
+        return SBR_OK;
+    }
+};
+
 // The place of every goal item in the complete ranking of its user (include/sbr_rnn.h: sbr_evaluate_ranks): sbr_evaluate's chunks with
 // one counting kernel (ev_goal_rank_kernel, sbr_eval.hip) where that call selects, sorts and compares.  The offsets of the users' goal
 // places follow from the lengths alone: they are written for the caller, and uploaded, before anything is launched.
@@ -312,14 +349,8 @@ extern "C" int sbr_evaluate_ranks(sbr_handle* h, sbr_dataset* d, const int32_t* 
     Carver cv;
     const size_t o_users = cv.take((size_t)n * sizeof(int)), o_goff = cv.take((size_t)(n + 1) * sizeof(long long));
     const size_t o_ranks = cv.take((size_t)total * sizeof(int)), o_nrk = cv.take((size_t)n * sizeof(int));
-    // Lazily stepped rows are brought up to date where the call reads them, and WHERE a replay of missed steps is split changes float32
-    // roundings (sbr_sparse.hip): a training run with this call in its middle would differ in the last bit from one without.  So once
-    // steps have been applied, the parameters, the optimizer state and the rows' last-step words are kept and put back behind the last chunk.
-    const bool keep = sparse_lazy(h) && h->step_count > 0;
-    const size_t np_bytes = y.n_params * sizeof(float);
-    const size_t o_kp = cv.take(keep ? np_bytes : 0), o_ks = cv.take(keep ? y.n_state_arrays * np_bytes : 0);
-    size_t o_kl[2] = {0, 0};
-    for (int b = 0; b < y.n_sparse; ++b) o_kl[b] = cv.take(keep ? (size_t)y.sparse[b].n_rows * sizeof(int) : 0);
+    LazyKeep kept;      // training goes on as if the call had not been made
+    kept.carve(cv, h);
     if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
     char* S = (char*)h->rank_scratch;
     hipStream_t s = h->stream;
@@ -329,25 +360,99 @@ extern "C" int sbr_evaluate_ranks(sbr_handle* h, sbr_dataset* d, const int32_t* 
     // (pageable host memory: the copies have left the caller's arrays when they return)
     SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
     SBR_HIP(hipMemcpyAsync(S + o_goff, goal_off_host, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
-    if (keep) {
-        SBR_HIP(hipMemcpyAsync(S + o_kp, h->P(0), np_bytes, hipMemcpyDeviceToDevice, s));
-        SBR_HIP(hipMemcpyAsync(S + o_ks, h->St(0, 0), y.n_state_arrays * np_bytes, hipMemcpyDeviceToDevice, s));
-        for (int b = 0; b < y.n_sparse; ++b)
-            SBR_HIP(hipMemcpyAsync(S + o_kl[b], h->A(y.sparse[b].a_last), (size_t)y.sparse[b].n_rows * sizeof(int), hipMemcpyDeviceToDevice, s));
-    }
+    { const int rck = kept.save(h, S); if (rck != SBR_OK) return rck; }
     rc = eval_chunks(h, v, dusers, n, exclude_mode, [&](int64_t c0, int rows, float* lg) -> int {
         SBR_LAUNCH(launch_ev_goal_rank(s, v, dusers + c0, dgoff + c0, rows, y.N, lg, (int*)(S + o_ranks), (int*)(S + o_nrk) + c0, &h->last_goal_rank_form));
         return SBR_OK;
     });
-    if (keep) {      // (also behind a chunk that failed: the call leaves the bits it found)
-        SBR_HIP(hipMemcpyAsync(h->P(0), S + o_kp, np_bytes, hipMemcpyDeviceToDevice, s));
-        SBR_HIP(hipMemcpyAsync(h->St(0, 0), S + o_ks, y.n_state_arrays * np_bytes, hipMemcpyDeviceToDevice, s));
-        for (int b = 0; b < y.n_sparse; ++b)
-            SBR_HIP(hipMemcpyAsync(h->A(y.sparse[b].a_last), S + o_kl[b], (size_t)y.sparse[b].n_rows * sizeof(int), hipMemcpyDeviceToDevice, s));
-    }
+    { const int rck = kept.restore(h, S); if (rck != SBR_OK) return rck; }      // (also behind a chunk that failed: the call leaves the bits it found)
     if (rc != SBR_OK) return rc;
     SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
     SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    return check_fault(h);          // a forward that gave up must not hand out ranks; the call's one wait for the device
+}
+
+// The place of the NEXT item at every position of every user's sequence (include/sbr_rnn.h: sbr_evaluate_positions; UserPrefix,
+// sbr_common.h).  Per chunk of local_batch users: pack the start of every sequence -> ONE forward pass -> the
+// first-occurrence flags of the rows -> per group of up to `slots` positions p = min_history .. the chunk's longest row: the projection
+// of those slots of the top layer's states (project_rows: full_scores' launch pair, same mode) and one counting launch
+// (ev_next_rank_kernel), which only reads the scores.  Everything on the main stream; the call waits once, in check_fault.  The
+// offsets of the users' positions follow from the lengths alone: they are written for the caller, and uploaded, before anything is
+// launched.
+extern "C" int sbr_evaluate_positions(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int min_history, int exclude_mode,
+                                      int64_t* pos_off_host, int32_t* ranks_host, int32_t* n_rankable_host, int64_t cap) {
+    CHECK_ARG(h && d && users && pos_off_host && ranks_host && n_rankable_host, "null argument");
+    CHECK_ARG(exclude_mode == SBR_EVAL_EXCL_NONE || exclude_mode == SBR_EVAL_EXCL_PREFIX,
+              "sbr_evaluate_positions takes SBR_EVAL_EXCL_NONE or SBR_EVAL_EXCL_PREFIX, not mode %d", exclude_mode);
+    CHECK_ARG(min_history >= 1, "min_history=%d: a position needs at least one item in front of it", min_history);
+    const Layout& y = h->lay;
+    // a backwards layer's state at place p has read the items behind p: its slots are no states "after p items"
+    CHECK_ARG(y.D == 1, "sbr_evaluate_positions: a bidirectional engine has no state that has seen only the first p items");
+    SbrEvalView v;
+    int rc;
+    if ((rc = eval_check_args(h, d, users, n, 1, v)) != SBR_OK) return rc;      // (no k here: 1 is inside every catalogue)
+    auto prefix = [&](int64_t j) { return UserPrefix(v.h_off[users[j]], v.h_off[users[j] + 1], y.T, min_history); };
+    int64_t total = 0;
+    for (int64_t j = 0; j < n; ++j) total += prefix(j).n_pos();
+    CHECK_ARG(cap >= total, "cap=%lld: these users hold %lld positions", (long long)cap, (long long)total);
+    pos_off_host[0] = 0;
+    for (int64_t j = 0; j < n; ++j) pos_off_host[j + 1] = pos_off_host[j] + prefix(j).n_pos();
+    const int B = y.B;
+    Carver cv;
+    const size_t o_users = cv.take((size_t)n * sizeof(int)), o_poff = cv.take((size_t)(n + 1) * sizeof(long long));
+    const size_t o_ranks = cv.take((size_t)total * sizeof(int)), o_nrk = cv.take((size_t)total * sizeof(int));
+    const size_t o_first = cv.take((size_t)B * y.T * sizeof(int));
+    // Consecutive slots of a_hs are consecutive rows of ONE matrix: up to kNextRankSlots positions share a projection launch where
+    // their scores fit kNextRankScoreBytes of scratch, and where the GEMM's accumulation order does not depend on the rows it carries:
+    // the exact-f32 kernel without a workspace (no split-K) and the triage kernel; the one-pass bf16 kernel chooses its tile by the
+    // row count, so it keeps one slot per launch, in a_logits, with full_scores' n_rows.
+    const size_t slot_floats = (size_t)y.Bp * y.N;
+    const int slots = scores_gemm_mode(h).one_pass ? 1 : (int)std::max<size_t>(1, std::min<size_t>(kNextRankSlots, kNextRankScoreBytes / (slot_floats * sizeof(float))));
+    const size_t o_scores = cv.take(slots > 1 ? slots * slot_floats * sizeof(float) : 0);
+    LazyKeep kept;      // training goes on as if the call had not been made
+    kept.carve(cv, h);
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    const long long* dpoff = (const long long*)(S + o_poff);
+    int* first = (int*)(S + o_first);
+    float* scores = slots > 1 ? (float*)(S + o_scores) : h->A(y.a_logits);
+    h->last_next_rank_slots = slots;
+    // (pageable host memory: the copies have left the caller's arrays when they return)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    SBR_HIP(hipMemcpyAsync(S + o_poff, pos_off_host, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    { const int rck = kept.save(h, S); if (rck != SBR_OK) return rck; }
+    const LayerLayout& top = y.layer[y.L - 1];
+    auto chunks = [&]() -> int {
+        for (int64_t c0 = 0; c0 < n; c0 += B) {
+            const int rows = (int)std::min<int64_t>(B, n - c0);
+            int last = 0;                                              // the chunk's longest row
+            for (int r = 0; r < rows; ++r) last = std::max(last, prefix(c0 + r).last_pos());
+            int rc2;
+            // the chunk becomes the current batch (eval_pack_chunk with the prefix policy)
+            if ((rc2 = eval_pack_chunk(h, v, dusers + c0, rows, true)) != SBR_OK) return rc2;
+            if ((rc2 = forward_current(h)) != SBR_OK) return rc2;
+            if (exclude_mode == SBR_EVAL_EXCL_PREFIX) SBR_LAUNCH(launch_ev_first_seen(s, h->bX, h->blen, rows, y.T, y.F, first));
+            for (int p0 = min_history; p0 <= last; p0 += slots) {
+                const int k = std::min(slots, last - p0 + 1);
+                // slot p = the state after p items: for a row of exactly p items, the very floats of h_last.  k slots = the rows
+                // [p0 * Bp, (p0 + k - 1) * Bp + rows) of a_hs (the padded rows between two slots are projected along)
+                if ((rc2 = project_rows(h, h->A(top.a_hs) + (size_t)p0 * y.Bp * top.Hp, (k - 1) * y.Bp + rows, scores, 0)) != SBR_OK) return rc2;
+                SBR_LAUNCH(launch_ev_next_rank(s, v, dusers + c0, dpoff + c0, h->bX, h->blen, first, rows, y.T, y.F, y.N, p0, k, min_history,
+                                               exclude_mode == SBR_EVAL_EXCL_PREFIX, scores, slot_floats, (int*)(S + o_ranks), (int*)(S + o_nrk),
+                                               &h->last_next_rank_form));
+            }
+        }
+        return SBR_OK;
+    };
+    rc = chunks();
+    { const int rck = kept.restore(h, S); if (rck != SBR_OK) return rck; }      // (also behind a chunk that failed: the call leaves the bits it found)
+    if (rc != SBR_OK) return rc;
+    if (total) {
+        SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+        SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
     return check_fault(h);          // a forward that gave up must not hand out ranks; the call's one wait for the device
 }
 

@@ -602,3 +602,69 @@ class RankEvaluator(Evaluator):
     def user_coverage(self): return self.at(self.k).user_coverage()
     def item_coverage(self): return self.at(self.k).item_coverage()
     def blockbuster_share(self): return self.at(self.k).blockbuster_share()
+
+
+class PositionEvaluator(object):
+    """Metrics over the place of the NEXT item at every position of every sequence (RNNEngine.evaluate_positions, include/sbr_rnn.h:
+    sbr_evaluate_positions): one (history, next item) pair per position where the other evaluators hold one instance per user.
+    A position's history length is p, the number of items in front of the goal x_p.  An unrankable goal (rank -1) counts as a
+    miss everywhere: no hit, reciprocal rank 0, gain 0.  Each position has ONE relevant item, so the ideal DCG is 1 and
+    ndcg(k) is the mean of 1 / log2(2 + rank) over the positions with rank < k."""
+
+    def __init__(self):
+        self._rank, self._hist, self._nrk, self._users = [], [], [], 0
+
+    def add_ranks(self, rec, lengths, min_history):
+        """rec: what RNNEngine.evaluate_positions returned for min_history; lengths (n,): the length L of every user's sequence, in
+        rec's order (a user has at most L - min_history positions: the result is checked against it)."""
+        off = np.asarray(rec["pos_off"], dtype=np.int64)
+        lengths, m = np.asarray(lengths, dtype=np.int64).reshape(-1), int(min_history)
+        n_pos = off[1:] - off[:-1]
+        if m < 1 or len(lengths) != len(n_pos) or len(rec["ranks"]) != off[-1] or len(rec["n_rankable"]) != off[-1] \
+                or np.any(n_pos > np.maximum(0, lengths - m)):
+            raise ValueError("lengths must hold the sequence length of every user of rec, and rec the positions min_history allows")
+        self._rank.append(np.asarray(rec["ranks"], dtype=np.int64))
+        self._nrk.append(np.asarray(rec["n_rankable"], dtype=np.int64))
+        # position i of a user stands behind p = min_history + i items
+        self._hist.append(m + np.arange(int(off[-1]), dtype=np.int64) - np.repeat(off[:-1], n_pos))
+        self._users += len(n_pos)
+
+    def _flat(self):
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        return cat(self._rank), cat(self._hist)
+
+    def n_positions(self):
+        return int(sum(len(r) for r in self._rank))
+
+    def n_users(self):
+        return self._users
+
+    def n_unrankable(self):
+        return int(sum(int(np.count_nonzero(r < 0)) for r in self._rank))
+
+    @staticmethod
+    def _rr(rank):
+        return np.where(rank >= 0, 1.0 / (1.0 + np.maximum(rank, 0)), 0.0)
+
+    def hit_rate(self, k):
+        """the share of positions whose next item is among the first k of the ranking (sps at every position)"""
+        rank, _ = self._flat()
+        return int(np.count_nonzero((rank >= 0) & (rank < int(k)))) / len(rank)
+
+    def mrr(self):
+        rank, _ = self._flat()
+        return float(self._rr(rank).sum()) / len(rank)
+
+    def ndcg(self, k):
+        rank, _ = self._flat()
+        gain = np.where((rank >= 0) & (rank < int(k)), 1.0 / np.log2(2.0 + np.maximum(rank, 0)), 0.0)
+        return float(gain.sum()) / len(rank)
+
+    def by_history(self, k):
+        """{"count", "hits", "rr"}: arrays over the history length h = 0 .. the longest one -- the positions with h items in front
+        of the goal (int64), those of them with rank < k (int64), and the sum of their reciprocal ranks (float64)"""
+        rank, hist = self._flat()
+        size = int(hist.max()) + 1 if len(hist) else 0
+        return {"count": np.bincount(hist, minlength=size).astype(np.int64),
+                "hits": np.bincount(hist[(rank >= 0) & (rank < int(k))], minlength=size).astype(np.int64),
+                "rr": np.bincount(hist, weights=self._rr(rank), minlength=size).astype(np.float64)}

@@ -43,6 +43,7 @@ FLAG_BF16_PROJECTION = 128   # output projection on plain bf16 operands (one MFM
 FLAG_BF16_LAYERS = 256       # the dense GEMMs between stacked layers (input projection of layer >= 2 and its backward pair) on plain bf16 operands
 # sbr_evaluate's exclusion modes (include/sbr_rnn.h)
 EVAL_EXCL_NONE, EVAL_EXCL_VIEWED, EVAL_EXCL_WINDOW, EVAL_EXCL_WINDOW_ZERO = 0, 1, 2, 3
+EVAL_EXCL_PREFIX = 4         # sbr_evaluate_positions only: at position p the distinct items in front of p are never ranked
 # sbr_cluster_evaluate's roads (include/sbr_rnn.h)
 CEVAL_LISTS, CEVAL_PRODUCT = 0, 1
 
@@ -86,6 +87,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
            "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks",
+           "sbr_evaluate_positions",
            "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
            "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load"]
 
@@ -183,6 +185,7 @@ def load_library(path=None):
     lib.sbr_build_batch.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_uint64]
     lib.sbr_evaluate.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
     lib.sbr_evaluate_ranks.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, vp]
+    lib.sbr_evaluate_positions.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int64]
     lib.sbr_cluster_evaluate.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SbrEvalOut),
                                          ctypes.POINTER(SbrEvalOut), vp, vp, vp]
     szp = ctypes.POINTER(ctypes.c_size_t)
@@ -201,6 +204,14 @@ class SbrError(RuntimeError):
 
 def _ptr(a):
     return None if a is None else ctypes.c_void_p(a.ctypes.data)
+
+
+def position_counts(lengths, max_length, min_history=1):
+    """n_pos of sbr_evaluate_positions (UserPrefix, csrc/sbr_common.h) for sequences of these lengths: the first
+    F = min(L - 1, max_length) items are fed and the positions min_history .. F evaluated -- max(0, F - min_history + 1) of them"""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    fed = np.minimum(np.maximum(lengths - 1, 0), int(max_length))
+    return np.maximum(0, fed - int(min_history) + 1)
 
 
 def _check_k(k, n_items):
@@ -858,6 +869,26 @@ class RNNEngine(object):
         with self.torch.cuda.device(self.device):
             self._check(self.lib.sbr_evaluate_ranks(self.h, dataset.d, _ptr(users) if n else None, n, int(exclude_mode), _ptr(out["goal_off"]),
                                                     _ptr(out["ranks"]), cap, _ptr(out["n_rankable"])))
+        return out
+
+    def evaluate_positions(self, dataset, users, exclude_mode, min_history=1):
+        """The place of the NEXT item at every position of every user's sequence, from one forward pass per chunk
+        (sbr_evaluate_positions): user j's first F = min(L - 1, max_length) items are fed from the start of the sequence, and for
+        every p = min_history .. F the item x_p is ranked among the scores of the state after p items.  exclude_mode:
+        EVAL_EXCL_NONE, or EVAL_EXCL_PREFIX (the items in front of p are never ranked).  Returns a dict: "pos_off" (int64 (n + 1,):
+        user j's positions are [pos_off[j], pos_off[j + 1]), in order of p), "ranks" (int32 (pos_off[-1],): the number of
+        rankable items in front of x_p, -1 when x_p is not rankable) and "n_rankable" (int32 (pos_off[-1],))."""
+        self._rank_local_flush("evaluate_positions")
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        n, m = len(users), int(min_history)
+        off, cap = np.asarray(dataset.offsets, dtype=np.int64), 0      # the dataset's host offsets size the result
+        if n and m >= 1 and users.min() >= 0 and users.max() < len(off) - 1:      # (otherwise the library rejects the call: nothing is written)
+            cap = int(position_counts(off[1:][users] - off[:-1][users], self.max_length, m).sum())
+        out = {"pos_off": np.zeros(n + 1, dtype=np.int64), "ranks": np.empty(cap, dtype=np.int32), "n_rankable": np.empty(cap, dtype=np.int32)}
+        self.evaluate_calls += 1
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.sbr_evaluate_positions(self.h, dataset.d, _ptr(users) if n else None, n, m, int(exclude_mode),
+                                                        _ptr(out["pos_off"]), _ptr(out["ranks"]), _ptr(out["n_rankable"]), cap))
         return out
 
     # ---------------------------------------------------------------- debug / timing

@@ -545,6 +545,25 @@ class RNNBase(object):
             return None
         return self._whole_catalogue_rank_evaluator(dataset, which, mode, k)
 
+    def _whole_catalogue_position_evaluator(self, dataset, which, mode, min_history):
+        from .data import PositionEvaluator
+        found = self._native_eval_users(dataset, which, method="evaluate_positions")
+        if found is None:
+            return None
+        ds, users, lens = found
+        ev = PositionEvaluator()
+        ev.add_ranks(self.engine.evaluate_positions(ds, users, mode, min_history=min_history), lens[users], min_history)
+        return ev
+
+    def native_position_evaluator(self, dataset, which, mode, min_history=1):
+        """The place of the next item at EVERY position of every sequence of dataset's "validation" / "test" set, from one engine
+        call (RNNEngine.evaluate_positions: one forward pass per chunk of users), as a data.PositionEvaluator.  mode:
+        engine.EVAL_EXCL_NONE or EVAL_EXCL_PREFIX.  None where there is no native road (_native_eval_users names the cases; a
+        bidirectional model: a backwards layer's state at a position has seen the items behind it) -- nothing else serves this."""
+        if not self.native_eval or self.recurrent_layer.bidirectional:
+            return None
+        return self._whole_catalogue_position_evaluator(dataset, which, mode, min_history)
+
     def _compute_validation_metrics(self, metrics):
         from .data import Evaluator
         from .engine import EVAL_EXCL_NONE, EVAL_EXCL_WINDOW, EVAL_EXCL_WINDOW_ZERO
@@ -1198,6 +1217,13 @@ class RNNCluster(RNNBase):
         if ev is not None:
             ev.nb_of_dp = self.n_items
         return ev
+
+    def native_position_evaluator(self, dataset, which, mode, min_history=1):
+        """--ignore_clusters: RNNBase's whole-catalogue positions; None otherwise -- the place of the next item inside a cluster is
+        not what evaluate_positions counts, and no other road serves it."""
+        if self.predict_with_clusters or self.recurrent_layer.bidirectional:
+            return None
+        return self._whole_catalogue_position_evaluator(dataset, which, mode, min_history)
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per

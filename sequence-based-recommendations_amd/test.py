@@ -150,6 +150,43 @@ def run_tests(predictor, model_file, dataset, args, get_full_recommendation_list
     return evaluator
 
 
+def run_position_tests(predictor, model_file, dataset, args, k=10, file=None, n_batches=None):
+    """--by_position (no counterpart in the reference): how well the model predicts the NEXT item after 1, 2, ... items of every test
+    sequence -- every position p = --min_history .. min(L - 1, max_length) of every user, the first p items fed from the start of
+    the sequence, from one engine call (RNNBase.native_position_evaluator, sbr_evaluate_positions); with unique interactions the
+    items in front of a position are not ranked at it.  Prints seq_sps@k (the share of positions whose next item is in the top k),
+    seq_mrr, seq_ndcg@k and the number of positions, and appends to `file`_by_position one line per history length h:
+    n_batches, h, positions, hits at k, sum of reciprocal ranks.  There is no per-user road to fall back to: where the engine call
+    cannot serve the model or the set, the run stops with the reason."""
+    from .engine import EVAL_EXCL_NONE, EVAL_EXCL_PREFIX
+    if not hasattr(predictor, "native_position_evaluator"):
+        raise SystemExit("--by_position: %s has no native position evaluation" % type(predictor).__name__)
+    predictor.load(model_file)
+    min_history = int(getattr(args, "min_history", 1))
+    start = time.perf_counter()
+    ev = predictor.native_position_evaluator(dataset, "test", EVAL_EXCL_PREFIX if predictor.interactions_are_unique else EVAL_EXCL_NONE,
+                                             min_history=min_history)
+    if ev is None:
+        raise SystemExit("--by_position needs the engine's native evaluation of this model and test set, and there is no other road: "
+                         "not with SBR_NATIVE_EVAL=0, a data-parallel run, a shuffled test set, a bidirectional model (--r_bi) or a "
+                         "cluster model without --ignore_clusters")
+    if ev.n_positions() == 0:
+        raise SystemExit("--by_position: no test sequence has a position at --min_history %d" % min_history)
+    print("Timer (by position): ", time.perf_counter() - start)
+    print("seq_sps@" + str(k) + ": ", ev.hit_rate(k))
+    print("seq_mrr: ", ev.mrr())
+    print("seq_ndcg@" + str(k) + ": ", ev.ndcg(k))
+    print("positions: ", ev.n_positions())
+    if file is not None:
+        if not os.path.exists(os.path.dirname(file)):
+            os.makedirs(os.path.dirname(file))
+        by = ev.by_history(k)
+        with open(file + "_by_position", "a") as f:
+            for h in np.nonzero(by["count"])[0].tolist():
+                f.write("\t".join(map(str, (n_batches, h, int(by["count"][h]), int(by["hits"][h]), float(by["rr"][h])))) + "\n")
+    return ev
+
+
 def print_results(ev, metrics, file=None, n_batches=None, print_full_rank_comparison=False):   # test.py:79-103
     for m in metrics:
         if m not in ev.metrics:
@@ -194,6 +231,9 @@ def test_command_parser(parser):                                      # test.py:
     parser.add_argument("--save", help="Save results to a file", action="store_true")
     parser.add_argument("--dir", help="Model directory.", default="", type=str)
     parser.add_argument("--save_rank", help="Save the full comparison of goal and prediction ranking.", action="store_true")
+    parser.add_argument("--by_position", help="Also rank the next item at every position of every test sequence (seq_sps, seq_mrr, seq_ndcg; "
+                        "with --save, <results file>_by_position holds one line per history length).", action="store_true")
+    parser.add_argument("--min_history", help="With --by_position: the shortest history a position is evaluated at.", default=1, type=int)
 
 
 def main(argv=None):                                                  # test.py:132-160
@@ -219,10 +259,14 @@ def main(argv=None):                                                  # test.py:
                 print("(", i + 1, "/", len(files), ") results on " + files[j])
                 print_results(ev, metrics, file=output_file, n_batches=batches[j], print_full_rank_comparison=args.save_rank)
                 results.append((files[j], {m: ev.metrics[m]() for m in metrics}))
+                if getattr(args, "by_position", False):
+                    run_position_tests(predictor, files[j], dataset, args, k=args.nb_of_predictions, file=output_file, n_batches=batches[j])
     else:
         ev = run_tests(predictor, files, dataset, args, get_full_recommendation_list=args.save_rank, k=args.nb_of_predictions)
         print_results(ev, metrics, file=save_file_name(predictor, dataset, args), print_full_rank_comparison=args.save_rank)
         results.append((files, {m: ev.metrics[m]() for m in metrics}))
+        if getattr(args, "by_position", False):
+            run_position_tests(predictor, files, dataset, args, k=args.nb_of_predictions, file=save_file_name(predictor, dataset, args))
     return results
 
 
