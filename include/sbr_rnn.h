@@ -334,7 +334,7 @@ int sbr_debug_gemm(void* stream, const float* A, int64_t sam, int64_t sak, const
                    float* C, int64_t ldc, int32_t M, int32_t N, int32_t K, const float* bias, float* ws, size_t ws_floats,
                    int32_t exact_f32);
 
-/* Named device buffers for parity tests: "h_last" (rows,Hp), "logits", "xt0", "hs0" ... */
+/* Named device buffers for parity tests: "h_last" (rows,Hp), "logits", "xt0", "hs0", "cs0" (LSTM: the cell states, laid out like hs0) ... */
 int sbr_debug_buffer(sbr_handle* h, const char* name, void** dev_ptr, size_t* n_floats);
 /* Copy n_floats from a device pointer to host (tests without torch). */
 int sbr_copy_to_host(sbr_handle* h, const void* dev_ptr, float* host, size_t n_floats);
@@ -657,6 +657,66 @@ int sbr_cluster_state_load(sbr_cluster* c, const void* blob_host, size_t bytes);
 int sbr_dataset_state_bytes(sbr_dataset* d, size_t* bytes);
 int sbr_dataset_state_save(sbr_dataset* d, void* blob_host, size_t cap, size_t* written);
 int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stateful sessions (added under ABI 11: eight symbols and three constants, no struct change) -- serving at the model's natural
+ * cost.  Every ranking call above feeds a whole window of up to max_length items per row (rnn_base.py:140-165 does so per request); a
+ * session pool KEEPS the recurrent state of `capacity` users, so that a user's next event costs one recurrent step and one projection.
+ * A second object beside the engine, like the cluster head: its memory is its own device allocation (never part of the arena --
+ * sbr_arena_bytes does not change): per layer two planes [capacity][Hp] of hidden states (and of cell states for LSTM; padded
+ * units are kept as the chains keep them), per slot an event count and a ring of the ids of the last `history` events.
+ *
+ * A slot's state after p events is "the state after p items fed from the START of the sequence", the definition of
+ * sbr_evaluate_positions (UserPrefix, not the window of UserSplit): there is no mask (every advance is an event) and NO WINDOW -- a
+ * session carries its state over any number of events, which equals the windowed model of the other calls only while the events fit
+ * max_length.
+ *
+ * Everything runs on the engine's stream.  reset / advance / adopt enqueue and return without waiting for the device; rank waits
+ * once, at its end, like sbr_rank; read and write wait.  A call that reads parameters brings lazily stepped rows up to date first
+ * (see "Row-sparse blocks": advance the index-input block, rank and adopt the output rows), which moves float32 roundings of a
+ * training run as sbr_rank does and is otherwise invisible to it; sessions keep states, not weights: after a training step they go on
+ * under the new weights.  Inside an open training step (between sbr_zero_grads and sbr_apply_update) or with a lagged cost pending,
+ * every call but read returns SBR_ESTATE.  The current batch, its forward pass and the batch buffers stay as they were (adopt runs the
+ * forward pass the batch would get anyway).
+ *
+ *   create   capacity >= 1 slots, a ring of history >= 0 ids per slot; every slot is reset.  SBR_EINVAL with the reason: a
+ *            bidirectional engine (a backwards layer has no state "after p items"), capacity < 1, history < 0.
+ *   reset    the named slots (slots NULL: all of them, n ignored) take the CURRENT hid_init / cell_init -- read by a kernel at that
+ *            point of the stream --, 0 events and an empty ring.
+ *   advance  one event per named slot through every layer: items[r] (and second[r], the second index per step of a model with
+ *            n_feat == 2 -- NULL otherwise) is fed to slot slots[r].  One launch per layer (ses_step_kernel, sbr_session.hip: a
+ *            row-gathered GEMM on v_mfma_f32_16x16x4_f32 plus the cell) and one commit launch that counts the event and appends
+ *            items[r] to the ring.  An output element is one accumulation chain whose order does not depend on the rows that share
+ *            the call: a session fed alone and the same session fed among thousands hold the same bits.
+ *   adopt    the prefill: rows 0 .. n_rows - 1 of the engine's current batch become the sessions slots[0 .. n_rows): the forward
+ *            pass runs on the chain kernels (if the batch has none yet), then ONE launch copies each row's state at the row's length
+ *            (of every layer), its length as the event count and its last `history` fed ids.  No batch set: SBR_ESTATE.
+ *   rank     the next-item ranking of the named slots (they may repeat), n >= 1: the top layer's states are gathered and go through
+ *            sbr_rank's own pipeline (projection, exclusion, select, sort) in chunks of local_batch rows.  k, the order, the ties, the
+ *            -1 / -inf places, scores_host and the caller's lists excl_ids / excl_off (a CSR over the n rows, excluded IN ADDITION)
+ *            are sbr_rank's; ids_host [n][k].  exclude_mode: SBR_SESSION_EXCL_*; with a session longer than `history` only the last
+ *            `history` ids are excluded (history == 0: none).
+ *   read     slot's state in `layer`: h_host / c_host [Hp] floats (Hp = the layer's padded width: 16 / 32 / 64 / 128 / 256 / 512,
+ *            above that the next multiple of 64; c_host is written for LSTM only), *events, history_host [history]: the last
+ *            min(events, history) ids, oldest first, then -1.  Any output may be NULL.
+ *   write    puts h_host (and c_host, LSTM) back as slot's state in `layer`; events and ring stay.  read / write are the hooks for
+ *            evicting and restoring sessions.
+ * SBR_EINVAL, found on the host before anything is launched, the pool untouched, the offender named: a slot outside [0, capacity), a
+ * slot named twice in one advance / adopt / reset, an id outside [0, input_size), `second` missing with n_feat == 2 or given with
+ * n_feat == 1, n above capacity (advance) or n_rows above the batch's rows (adopt), k, exclude_mode or lists as sbr_rank rejects them. */
+typedef struct sbr_sessions sbr_sessions;
+#define SBR_SESSION_EXCL_NONE    0
+#define SBR_SESSION_EXCL_LAST    1   /* the item fed last is not ranked */
+#define SBR_SESSION_EXCL_HISTORY 2   /* the kept history (the ring) is not ranked */
+int  sbr_sessions_create(sbr_handle* h, int64_t capacity, int32_t history, sbr_sessions** out);
+void sbr_sessions_destroy(sbr_sessions* s);            /* before sbr_destroy(h) */
+int  sbr_sessions_reset(sbr_sessions* s, const int32_t* slots, int64_t n);
+int  sbr_sessions_advance(sbr_sessions* s, const int32_t* slots, const int32_t* items, const int32_t* second, int64_t n);
+int  sbr_sessions_adopt(sbr_sessions* s, const int32_t* slots, int32_t n_rows);
+int  sbr_sessions_rank(sbr_sessions* s, const int32_t* slots, int64_t n, int k, int exclude_mode,
+                       const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host);
+int  sbr_sessions_read(sbr_sessions* s, int32_t slot, int32_t layer, float* h_host, float* c_host, int64_t* events, int32_t* history_host);
+int  sbr_sessions_write(sbr_sessions* s, int32_t slot, int32_t layer, const float* h_host, const float* c_host);
 
 #ifdef __cplusplus
 }

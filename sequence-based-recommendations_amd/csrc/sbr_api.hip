@@ -911,6 +911,7 @@ extern "C" int sbr_debug_buffer(sbr_handle* h, const char* name, void** dev_ptr,
         const std::string sfx = std::to_string(l);
         if (nm == "xt" + sfx) { *dev_ptr = h->A(ly.a_xt); *n_floats = tb * y.G * ly.Hp; return SBR_OK; }
         if (nm == "hs" + sfx) { *dev_ptr = h->A(ly.a_hs); *n_floats = (tb + y.Bp) * ly.Hp; return SBR_OK; }
+        if (nm == "cs" + sfx && y.cfg.cell == SBR_CELL_LSTM) { *dev_ptr = h->A(ly.a_cs); *n_floats = (tb + y.Bp) * ly.Hp; return SBR_OK; }
         if (nm == "dxt" + sfx) { *dev_ptr = h->A(ly.a_dxt); *n_floats = tb * y.G * ly.Hp; return SBR_OK; }
         if (nm == "dhi" + sfx) { *dev_ptr = h->A(ly.a_dhi); *n_floats = tb * (y.cfg.cell == SBR_CELL_GRU ? 1 : y.G) * ly.Hp; return SBR_OK; }
     }

@@ -446,6 +446,31 @@ struct sbr_cluster {
     int lmax;                                        // the longest list, padded to a multiple of 4
 };
 
+// The session pool (sbr_session.hip; include/sbr_rnn.h "Stateful sessions").  Own allocations, freed by
+// sbr_sessions_destroy.  A slot's state in layer l is row `slot` of plane (events[slot] & 1) of hs[l] / cs[l]: a step reads that plane
+// and writes the other, and the commit launch at the end of sbr_sessions_advance makes the written one current by counting the event.
+struct SesPool {                                     // what the kernels read: passed by value
+    long long capacity; int L, ring_len, history;
+    int Hp[SBR_MAX_LAYERS];
+    float* hs[SBR_MAX_LAYERS];                       // [2][capacity][Hp]
+    float* cs[SBR_MAX_LAYERS];                       // [2][capacity][Hp], LSTM only (else NULL)
+    long long* events;                               // [capacity] events fed
+    int* ring;                                       // [capacity][ring_len]: the id of event e at e % ring_len (ring_len = max(history, 1))
+};
+struct sbr_sessions {
+    sbr_handle* h;
+    SesPool p;
+    int *d_slots, *d_items, *d_second;               // [capacity] each: the lists of the call in flight (slots of a call are distinct)
+    std::vector<unsigned> stamp; unsigned epoch;     // host: stamp[slot] == epoch: the slot was already named in this call
+};
+// sbr_session.hip: the kernels behind the calls.  Every slot, id and row count was checked on the host
+hipError_t launch_ses_reset(hipStream_t s, const SesPool& p, const sbr_handle* h, const int* slots, long long n);
+hipError_t launch_ses_gather_top(hipStream_t s, const SesPool& p, const int* slots, int rows, float* out);      // out [rows][Hp of the top layer]
+// ... and the two checks every sessions call starts with: no training step open and no lagged cost pending (SBR_ESTATE); the slots
+// inside the pool and, with distinct, named once (SBR_EINVAL)
+int sessions_state_check(const sbr_sessions* s, const char* call);
+int sessions_check_slots(sbr_sessions* s, const char* call, const int32_t* slots, long long n, bool distinct);
+
 void sbr_set_error(const char* fmt, ...);
 #define SBR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     sbr_set_error("%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); return SBR_EHIP; } } while (0)

@@ -59,20 +59,28 @@ __device__ __forceinline__ void crk_exclude_one(float* __restrict__ row, const i
 // ---------------------------------------------------------------------------------------
 // exclusion: "these ids of this row are not ranked", stated once for every ranking call (kernel and launcher: sbr_rank.hip)
 // ---------------------------------------------------------------------------------------
-// Where the excluded ids of row r come from.  Each of the three parts may be absent; the host fills the ones a call has.
+// Where the excluded ids of row r come from.  Each of the four parts may be absent; the host fills the ones a call has.
 struct ExclSources {
     const int* csr_ids = nullptr; const long long* csr_off = nullptr;      // the caller's lists: csr_ids[csr_off[r] .. csr_off[r + 1])
     const int* X = nullptr; const int* len = nullptr; int F = 1;           // the row's input window: X[r][t][0], t < min(len[r], T)
     const int* items = nullptr; const long long* off = nullptr;            // the dataset's CSR and the row's user: the viewed half
     const int* users = nullptr; int mode = SBR_EVAL_EXCL_NONE;             // (SBR_EVAL_EXCL_VIEWED) or the items fed (_WINDOW, _WINDOW_ZERO)
     int T = 0;
+    // a session pool's slot of the row (sbr_sessions_rank): ring[slot][e % ring_len] holds the id of the slot's event e, events[slot] of
+    // them were fed; SBR_SESSION_EXCL_LAST: the last one, _HISTORY: the last min(events, ses_history) -- never more than the ring keeps
+    const int* ses_slots = nullptr; const int* ses_ring = nullptr; const long long* ses_events = nullptr;
+    int ses_ring_len = 0, ses_history = 0, ses_mode = SBR_SESSION_EXCL_NONE;
     ExclSources& lists(const int* ids, const long long* offsets) { csr_ids = ids; csr_off = offsets; return *this; }
     ExclSources& window(const int* X_, const int* len_, int T_, int F_) { X = X_; len = len_; T = T_; F = F_; return *this; }
     ExclSources& dataset(const SbrEvalView& v, const int* users_, int T_, int mode_) {
         if (mode_ != SBR_EVAL_EXCL_NONE) { items = v.items; off = v.off; users = users_; mode = mode_; T = T_; }
         return *this;
     }
-    bool any() const { return csr_off || X || users; }
+    ExclSources& sessions(const int* slots_, const int* ring_, const long long* events_, int ring_len_, int history_, int mode_) {
+        if (mode_ != SBR_SESSION_EXCL_NONE) { ses_slots = slots_; ses_ring = ring_; ses_events = events_; ses_ring_len = ring_len_; ses_history = history_; ses_mode = mode_; }
+        return *this;
+    }
+    bool any() const { return csr_off || X || users || ses_slots; }
 };
 
 // visit(id) for every excluded id of row r, the ids spread over the workgroup's threads; an id may come more than once and is not
@@ -93,6 +101,14 @@ __device__ __forceinline__ void excl_visit(const ExclSources& s, int r, Visit&& 
         // items fed (the compiled test function's exclude, rnn_base.py:200-202)
         for (int t = (s.mode == SBR_EVAL_EXCL_VIEWED ? sp.viewed_begin() : sp.window_begin()) + threadIdx.x; t < sp.viewed_end(); t += blockDim.x)
             visit(seq[t]);
+    }
+    if (s.ses_slots) {
+        const int slot = s.ses_slots[r];
+        const long long ev = s.ses_events[slot];
+        const long long kept = s.ses_mode == SBR_SESSION_EXCL_LAST ? 1 : s.ses_history;
+        const int n = (int)(ev < kept ? ev : kept);
+        const int* ring = s.ses_ring + (size_t)slot * s.ses_ring_len;
+        for (int t = threadIdx.x; t < n; t += blockDim.x) visit(ring[(ev - 1 - t) % s.ses_ring_len]);
     }
 }
 

@@ -160,6 +160,58 @@ extern "C" int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* 
     return check_fault(h);          // a forward that gave up must not hand out rankings
 }
 
+// The next-item ranking of kept session states (include/sbr_rnn.h "Stateful sessions"; the pool and its step: sbr_session.hip):
+// sbr_rank's pipeline on rows that come from the pool instead of a forward pass.  Per chunk of local_batch rows (a_logits holds Bp
+// rows): the top layer's current states of the chunk's slots gathered into a contiguous [rows][HLt] matrix -> project_rows ->
+// launch_exclude (the caller's lists and the slots' history rings, ExclSources::sessions) -> rank_rows.  have_batch / fwd_done and the
+// batch buffers are not touched.  The call waits once, in check_fault.
+extern "C" int sbr_sessions_rank(sbr_sessions* ses, const int32_t* slots, int64_t n, int k, int exclude_mode, const int32_t* excl_ids,
+                                 const int64_t* excl_off, int32_t* ids_host, float* scores_host) {
+    CHECK_ARG(ses && slots && ids_host, "null argument");
+    sbr_handle* h = ses->h;
+    const Layout& y = h->lay;
+    const SesPool& p = ses->p;
+    int rc;
+    if ((rc = sessions_state_check(ses, "sbr_sessions_rank")) != SBR_OK) return rc;
+    CHECK_ARG(n >= 1 && n <= 0x7fffffff, "sbr_sessions_rank: n=%lld sessions: at least one", (long long)n);
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    CHECK_ARG(exclude_mode >= SBR_SESSION_EXCL_NONE && exclude_mode <= SBR_SESSION_EXCL_HISTORY, "unknown exclusion mode %d", exclude_mode);
+    if ((rc = sessions_check_slots(ses, "sbr_sessions_rank", slots, n, false)) != SBR_OK) return rc;
+    ExclLists x;
+    if ((rc = excl_check(excl_ids, excl_off, (int)n, y.N, x)) != SBR_OK) return rc;
+    const int B = y.B;
+    const size_t nk = (size_t)n * k;
+    Carver cv;
+    const size_t o_slots = cv.take((size_t)n * sizeof(int));
+    excl_carve(cv, x);
+    const size_t o_states = cv.take((size_t)B * y.HLt * sizeof(float));
+    const RankWork w = carve_rank_work(cv, B, k, k > kRankSortLds);
+    const size_t o_oid = cv.take(nk * sizeof(int)), o_osc = cv.take(nk * sizeof(float));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;      // every item is scored: all of W_out^T / b_out must be current (forward_current's flush)
+    // (pageable host memory: the copy has left the caller's array when it returns)
+    SBR_HIP(hipMemcpyAsync(S + o_slots, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if ((rc = excl_upload(h, S, x)) != SBR_OK) return rc;
+    const int* dslots = (const int*)(S + o_slots);
+    float* states = (float*)(S + o_states);
+    float* lg = h->A(y.a_logits);
+    for (int64_t c0 = 0; c0 < n; c0 += B) {
+        const int rows = (int)std::min<int64_t>(B, n - c0);
+        SBR_LAUNCH(launch_ses_gather_top(s, p, dslots + c0, rows, states));
+        if ((rc = project_rows(h, states, rows, lg, 0)) != SBR_OK) return rc;      // the floats sbr_rank ranks for a row in that state
+        ExclSources src;
+        if (x.off) src.lists(x.dev_ids(S), x.dev_off(S) + c0);
+        src.sessions(dslots + c0, p.ring, p.events, p.ring_len, p.history, exclude_mode);
+        SBR_LAUNCH(launch_exclude(s, rows, src, ExclCatalogue{lg, y.N, -INFINITY}));
+        if ((rc = rank_rows(h, S, w, lg, rows, y.N, k, (int*)(S + o_oid) + (size_t)c0 * k, (float*)(S + o_osc) + (size_t)c0 * k)) != SBR_OK) return rc;
+    }
+    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, nk * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+    return check_fault(h);
+}
+
 // what sbr_evaluate and sbr_cluster_evaluate check about the users, k and the dataset against the engine; on SBR_OK v holds the sorted goals
 static int eval_check_args(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int k, SbrEvalView& v) {
     const Layout& y = h->lay;

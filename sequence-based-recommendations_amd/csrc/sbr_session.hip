@@ -1,0 +1,421 @@
+// Stateful sessions (include/sbr_rnn.h "Stateful sessions"): a pool of kept recurrent states beside the engine,
+// one recurrent step per event.  sbr_sessions_create / destroy / reset / advance / adopt / read / write and their kernels; the
+// ranking call sbr_sessions_rank is an entry to sbr_rank's pipeline and lives with it (sbr_rank_api.hip).
+//
+// The step (ses_step_kernel), one launch per layer: for the rows r < n of a call, s = slots[r],
+//     x = input(r) . W_in + b        layer 0 with index input: b + the F gathered rows of W_in (gather_xt_kernel's order);
+//                                    --r_emb: the F gathered embedding rows, flattened, as the A operand; layer >= 1: the lower
+//                                    layer's NEW state of slot s
+//     a = h[s] . W_hid               K = Hp
+//     cell_forward<CELL>(x, a, ...)  sbr_cell.h: the chains' cell math, libm transcendentals
+// on v_mfma_f32_16x16x4_f32 (exact f32 products).  A wave owns 16 rows x 16 units x G gates, x and a in accumulators of their own
+// (GRU's candidate is x_c + r * a_c).  Lane (q, j) of the instruction supplies A[row j][k] and B[k][unit j] for the k of its group q
+// and receives D[row 4q + e][unit j]; the wave walks K in blocks of 16, lane group q loading the quad k0 + 4q .. + 3 of its row with
+// one 16-byte load, so the e-th instruction of a block sums k0 + e, + 4, + 8, + 12.  An output element is therefore ONE accumulation
+// chain over K in an order fixed by K alone: it depends on its own row of A and column of B, never on which rows share the tile or
+// the launch (tests/test_gpu_sessions.py holds the kernel to that, bit for bit).  Operands come straight from global memory: the
+// step is launch- and latency-bound (4 096 sessions at 128 units: 0.4 GFLOP; W_hid stays in L2), and one arithmetic serves every
+// cell, width and flag.
+//
+// Geometry: grid (ceil(Hp / 64), ceil(n / 16)), 256 threads = 4 waves = 4 unit tiles of one row tile; no LDS, no barrier.  16 rows
+// at 48 units: 1 workgroup; 4 096 rows at 128 units: 512.
+//
+// The in-place hazard: the workgroups of different unit tiles all read the whole h[s], so no one may overwrite it.  Every slot has
+// two planes per layer; a step reads plane (events[s] & 1) and writes the other, layer l + 1 reads layer l's written plane, and the
+// commit launch behind the last layer counts the event -- which is what makes the written planes current.  Nothing reads a plane
+// that a launch in flight writes: race-free by construction, given that the slots of a call are distinct (checked on the host).
+#include "sbr_common.h"
+#include "sbr_cell.h"
+#include <algorithm>
+#include <new>
+
+namespace {
+
+enum SesInput { SES_IN_INDEX = 0, SES_IN_EMB = 1, SES_IN_DENSE = 2 };
+
+struct SesStep {
+    int n; const int* slots; const long long* events; long long capacity;
+    int Hp, K_in;                      // units of the layer; K of the dense input (F * Ep, or the lower layer's Hp)
+    const float *Whid, *Win, *bias, *peep;
+    float *hs, *cs;                    // this layer's planes
+    const int *items, *second;         // layer 0: the ids fed (second: NULL with one index per step)
+    const float* emb; int Ep;          // SES_IN_EMB: the embedding table [input_size][Ep]
+    const float* in_hs; int in_Hp;     // SES_IN_DENSE: the lower layer's planes
+    int relu;
+};
+
+template <int CELL, int IN>
+__global__ void __launch_bounds__(256) ses_step_kernel(SesStep a) {
+    constexpr int G = Gates<CELL>::G;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, q = lane >> 4;
+    const int u0 = (blockIdx.x * 4 + wave) * 16;
+    if (u0 >= a.Hp) return;                            // (no barrier in this kernel)
+    const int r0 = blockIdx.y * 16, Hp = a.Hp, GHp = G * Hp;
+    const size_t plane = (size_t)a.capacity * Hp;
+    // operand A: this lane's row
+    const int ra = r0 + j;
+    const bool a_ok = ra < a.n;
+    const int sa = a_ok ? a.slots[ra] : 0;
+    const long long ea = a_ok ? a.events[sa] : 0;
+    const float* hrow = a.hs + (size_t)(ea & 1) * plane + (size_t)sa * Hp;
+    f32x4 acc_a[G], acc_x[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) { acc_a[g] = f32x4{0, 0, 0, 0}; acc_x[g] = f32x4{0, 0, 0, 0}; }
+    const float* wcol = a.Whid + u0 + j;
+    for (int k0 = 0; k0 < Hp; k0 += 16) {
+        const int kq = k0 + 4 * q;
+        const f32x4 hv = a_ok ? *(const f32x4*)(hrow + kq) : f32x4{0, 0, 0, 0};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float* w = wcol + (size_t)(kq + e) * GHp;
+#pragma unroll
+            for (int g = 0; g < G; ++g) acc_a[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[e], w[g * Hp], acc_a[g], 0, 0, 0);
+        }
+    }
+    if (IN != SES_IN_INDEX) {
+        const int K = a.K_in;                          // a multiple of 4: a quad is inside or outside
+        const float* in_row = nullptr;
+        int id0 = 0, id1 = 0;
+        if (IN == SES_IN_DENSE) in_row = a.in_hs + (size_t)((ea + 1) & 1) * ((size_t)a.capacity * a.in_Hp) + (size_t)sa * a.in_Hp;
+        else if (a_ok) { id0 = a.items[ra]; id1 = a.second ? a.second[ra] : 0; }
+        const float* vcol = a.Win + u0 + j;
+        for (int k0 = 0; k0 < K; k0 += 16) {
+            const int kq = k0 + 4 * q;
+            const bool in = kq < K;
+            f32x4 xv = {0, 0, 0, 0};
+            if (a_ok && in) {
+                if (IN == SES_IN_DENSE) xv = *(const f32x4*)(in_row + kq);
+                else { const int f = kq / a.Ep; xv = *(const f32x4*)(a.emb + (size_t)(f ? id1 : id0) * a.Ep + (kq - f * a.Ep)); }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float* w = vcol + (size_t)(kq + e) * GHp;
+#pragma unroll
+                for (int g = 0; g < G; ++g) acc_x[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[e], in ? w[g * Hp] : 0.0f, acc_x[g], 0, 0, 0);
+            }
+        }
+    }
+    asm volatile("s_nop 15");                          // MFMA D -> VALU read hazard across the loop exit (see sbr_rec.hip)
+    // the cell: this lane holds rows r0 + 4q + e of unit u
+    const int u = u0 + j;
+    float pi = 0.0f, pf = 0.0f, po = 0.0f;
+    if (CELL == CELL_LSTM) { pi = a.peep[u]; pf = a.peep[Hp + u]; po = a.peep[2 * Hp + u]; }
+    float b[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) b[g] = a.bias[g * Hp + u];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int m = r0 + 4 * q + e;
+        if (m >= a.n) continue;
+        const int s = a.slots[m];
+        const size_t rd = (size_t)(a.events[s] & 1) * plane + (size_t)s * Hp + u;
+        const size_t wr = (size_t)((a.events[s] + 1) & 1) * plane + (size_t)s * Hp + u;
+        float x[G], av[G], sv[4];
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            av[g] = acc_a[g][e];
+            if (IN == SES_IN_INDEX) {
+                float v = b[g] + a.Win[(size_t)a.items[m] * GHp + g * Hp + u];
+                if (a.second) v += a.Win[(size_t)a.second[m] * GHp + g * Hp + u];
+                x[g] = v;
+            } else
+                x[g] = acc_x[g][e] + b[g];
+        }
+        float h = a.hs[rd], c = CELL == CELL_LSTM ? a.cs[rd] : 0.0f;
+        cell_forward<CELL>(x, av, true, h, c, pi, pf, po, sv, a.relu != 0);
+        a.hs[wr] = h;
+        if (CELL == CELL_LSTM) a.cs[wr] = c;
+    }
+}
+
+// behind the last layer: the event is counted (the planes the step wrote become the current ones) and its id enters the ring
+__global__ void __launch_bounds__(256) ses_commit_kernel(SesPool p, const int* __restrict__ slots, const int* __restrict__ items, int n) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const int s = slots[r];
+    const long long e = p.events[s];
+    p.ring[(size_t)s * p.ring_len + (int)(e % p.ring_len)] = items[r];
+    p.events[s] = e + 1;
+}
+
+struct SesInit { const float* hinit[SBR_MAX_LAYERS]; const float* cinit[SBR_MAX_LAYERS]; };
+// slot blockIdx.x of the list (slots NULL: slot blockIdx.x itself): plane 0 of every layer = the initial states as they are now, no events
+__global__ void __launch_bounds__(256) ses_reset_kernel(SesPool p, SesInit in, const int* __restrict__ slots) {
+    const long long s = slots ? slots[blockIdx.x] : blockIdx.x;
+    for (int l = 0; l < p.L; ++l)
+        for (int u = threadIdx.x; u < p.Hp[l]; u += 256) {
+            p.hs[l][(size_t)s * p.Hp[l] + u] = in.hinit[l][u];
+            if (p.cs[l]) p.cs[l][(size_t)s * p.Hp[l] + u] = in.cinit[l][u];
+        }
+    if (threadIdx.x == 0) p.events[s] = 0;
+}
+
+struct SesAdopt { const float* hs[SBR_MAX_LAYERS]; const float* cs[SBR_MAX_LAYERS]; const int* X; const int* len; int T, Bp, F; };
+// row blockIdx.x of the batch -> slot slots[row]: every layer's state at the row's length (slot `len` of a_hs / a_cs = the state after
+// len items), len events, and the ids of its last min(len, history) steps at the ring places those events have
+__global__ void __launch_bounds__(256) ses_adopt_kernel(SesPool p, SesAdopt b, SesInit in, const int* __restrict__ slots) {
+    const int r = blockIdx.x, s = slots[r];
+    const int len = max(0, min(b.len[r], b.T));
+    for (int l = 0; l < p.L; ++l) {
+        const size_t src = ((size_t)len * b.Bp + r) * p.Hp[l], dst = ((size_t)(len & 1) * p.capacity + s) * p.Hp[l];
+        for (int u = threadIdx.x; u < p.Hp[l]; u += 256) {      // (an empty row: the initial states themselves -- not every chain stores slot 0)
+            p.hs[l][dst + u] = len ? b.hs[l][src + u] : in.hinit[l][u];
+            if (p.cs[l]) p.cs[l][dst + u] = len ? b.cs[l][src + u] : in.cinit[l][u];
+        }
+    }
+    for (int t = max(0, len - p.ring_len) + threadIdx.x; t < len; t += 256)
+        p.ring[(size_t)s * p.ring_len + t % p.ring_len] = b.X[((size_t)r * b.T + t) * b.F];
+    if (threadIdx.x == 0) p.events[s] = len;
+}
+
+__global__ void __launch_bounds__(256) ses_gather_top_kernel(SesPool p, const int* __restrict__ slots, float* __restrict__ out) {
+    const int r = blockIdx.x, s = slots[r], l = p.L - 1, Hp = p.Hp[l];
+    const float* src = p.hs[l] + ((size_t)(p.events[s] & 1) * p.capacity + s) * Hp;
+    for (int u = threadIdx.x; u < Hp; u += 256) out[(size_t)r * Hp + u] = src[u];
+}
+
+template <int CELL>
+hipError_t launch_step_cell(hipStream_t st, const SesStep& a, int in) {
+    const dim3 grid((a.Hp + 63) / 64, (a.n + 15) / 16);
+    if (in == SES_IN_INDEX) ses_step_kernel<CELL, SES_IN_INDEX><<<grid, 256, 0, st>>>(a);
+    else if (in == SES_IN_EMB) ses_step_kernel<CELL, SES_IN_EMB><<<grid, 256, 0, st>>>(a);
+    else ses_step_kernel<CELL, SES_IN_DENSE><<<grid, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_ses_step(hipStream_t st, int cell, const SesStep& a, int in) {
+    switch (cell) {
+        case SBR_CELL_LSTM: return launch_step_cell<CELL_LSTM>(st, a, in);
+        case SBR_CELL_GRU: return launch_step_cell<CELL_GRU>(st, a, in);
+        default: return launch_step_cell<CELL_VANILLA>(st, a, in);
+    }
+}
+
+void ses_free(sbr_sessions* s) {
+    for (int l = 0; l < SBR_MAX_LAYERS; ++l) { if (s->p.hs[l]) (void)hipFree(s->p.hs[l]); if (s->p.cs[l]) (void)hipFree(s->p.cs[l]); }
+    if (s->p.events) (void)hipFree(s->p.events);
+    if (s->p.ring) (void)hipFree(s->p.ring);
+    if (s->d_slots) (void)hipFree(s->d_slots);
+    if (s->d_items) (void)hipFree(s->d_items);
+    if (s->d_second) (void)hipFree(s->d_second);
+    delete s;
+}
+
+template <class T>
+int ses_alloc(T** p, size_t n, const char* what) {
+    if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess) {
+        (void)hipGetLastError();
+        *p = nullptr;
+        sbr_set_error("sbr_sessions_create: hipMalloc(%zu) of %s failed", n * sizeof(T), what);
+        return SBR_ENOMEM;
+    }
+    return SBR_OK;
+}
+
+}  // namespace
+
+static SesInit ses_init(const SesPool& p, const sbr_handle* h) {
+    SesInit in{};
+    for (int l = 0; l < p.L; ++l) { in.hinit[l] = h->P(h->lay.layer[l].p_hinit); in.cinit[l] = h->P(h->lay.layer[l].p_cinit); }
+    return in;
+}
+hipError_t launch_ses_reset(hipStream_t st, const SesPool& p, const sbr_handle* h, const int* slots, long long n) {
+    const SesInit in = ses_init(p, h);
+    if (n <= 0) return hipSuccess;
+    ses_reset_kernel<<<(unsigned)n, 256, 0, st>>>(p, in, slots);
+    return hipGetLastError();
+}
+hipError_t launch_ses_gather_top(hipStream_t st, const SesPool& p, const int* slots, int rows, float* out) {
+    if (rows <= 0) return hipSuccess;
+    ses_gather_top_kernel<<<rows, 256, 0, st>>>(p, slots, out);
+    return hipGetLastError();
+}
+
+// the calls keep out of a training step in flight: its side streams read and write the parameters (as the state calls do)
+int sessions_state_check(const sbr_sessions* s, const char* call) {
+    const sbr_handle* h = s->h;
+    if (h->st.step_open || h->st.train_fwd_open) { sbr_set_error("%s: a training step is open (finish it with sbr_apply_update)", call); return SBR_ESTATE; }
+    if (h->lag_pending >= 0) { sbr_set_error("%s: a lagged cost is pending (collect it with sbr_lagged_flush)", call); return SBR_ESTATE; }
+    return SBR_OK;
+}
+// slots[0 .. n): inside the pool and (distinct) named once; found before anything is launched
+int sessions_check_slots(sbr_sessions* s, const char* call, const int32_t* slots, long long n, bool distinct) {
+    if (distinct && ++s->epoch == 0) { std::fill(s->stamp.begin(), s->stamp.end(), 0u); s->epoch = 1; }
+    for (long long r = 0; r < n; ++r) {
+        CHECK_ARG(slots[r] >= 0 && slots[r] < s->p.capacity, "%s: slots[%lld] = %d outside [0,%lld)", call, r, slots[r], s->p.capacity);
+        if (!distinct) continue;
+        CHECK_ARG(s->stamp[slots[r]] != s->epoch, "%s: slot %d is named twice (slots[%lld])", call, slots[r], r);
+        s->stamp[slots[r]] = s->epoch;
+    }
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_create(sbr_handle* h, int64_t capacity, int32_t history, sbr_sessions** out) {
+    CHECK_ARG(h && out, "null argument");
+    const Layout& y = h->lay;
+    CHECK_ARG(y.D == 1, "sbr_sessions_create: a bidirectional engine has no state that has seen only the first p items");
+    CHECK_ARG(capacity >= 1 && capacity <= 0x7fffffff, "sbr_sessions_create: capacity=%lld outside [1,2^31)", (long long)capacity);
+    CHECK_ARG(history >= 0, "sbr_sessions_create: history=%d is negative", history);
+    sbr_sessions* s = new (std::nothrow) sbr_sessions();
+    if (!s) { sbr_set_error("sbr_sessions_create: out of host memory"); return SBR_ENOMEM; }
+    s->h = h;
+    s->p = SesPool{};
+    s->p.capacity = capacity; s->p.L = y.L; s->p.history = history; s->p.ring_len = std::max(history, 1);
+    s->d_slots = s->d_items = s->d_second = nullptr;
+    s->epoch = 0;
+    s->stamp.assign((size_t)capacity, 0u);
+    int rc = SBR_OK;
+    for (int l = 0; l < y.L && rc == SBR_OK; ++l) {
+        s->p.Hp[l] = y.layer[l].Hp;
+        rc = ses_alloc(&s->p.hs[l], (size_t)2 * capacity * y.layer[l].Hp, "the hidden states");
+        if (rc == SBR_OK && y.cfg.cell == SBR_CELL_LSTM) rc = ses_alloc(&s->p.cs[l], (size_t)2 * capacity * y.layer[l].Hp, "the cell states");
+    }
+    if (rc == SBR_OK) rc = ses_alloc(&s->p.events, (size_t)capacity, "the event counts");
+    if (rc == SBR_OK) rc = ses_alloc(&s->p.ring, (size_t)capacity * s->p.ring_len, "the history rings");
+    if (rc == SBR_OK) rc = ses_alloc(&s->d_slots, (size_t)capacity, "the slot list");
+    if (rc == SBR_OK) rc = ses_alloc(&s->d_items, (size_t)capacity, "the item list");
+    if (rc == SBR_OK) rc = ses_alloc(&s->d_second, (size_t)capacity, "the second index list");
+    if (rc != SBR_OK) { ses_free(s); return rc; }
+    // every byte of the pool is defined from here on (the planes no reset writes, the rings), then every slot is reset
+    hipError_t e = hipSuccess;
+    for (int l = 0; l < y.L && e == hipSuccess; ++l) {
+        e = hipMemsetAsync(s->p.hs[l], 0, (size_t)2 * capacity * s->p.Hp[l] * sizeof(float), h->stream);
+        if (e == hipSuccess && s->p.cs[l]) e = hipMemsetAsync(s->p.cs[l], 0, (size_t)2 * capacity * s->p.Hp[l] * sizeof(float), h->stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(s->p.ring, 0xFF, (size_t)capacity * s->p.ring_len * sizeof(int), h->stream);
+    if (e == hipSuccess) e = launch_ses_reset(h->stream, s->p, h, nullptr, capacity);
+    if (e != hipSuccess) { sbr_set_error("sbr_sessions_create: %s", hipGetErrorString(e)); ses_free(s); return SBR_EHIP; }
+    *out = s;
+    return SBR_OK;
+}
+
+extern "C" void sbr_sessions_destroy(sbr_sessions* s) {
+    if (!s) return;
+    (void)hipStreamSynchronize(s->h->stream);      // launches in flight read and write the pool
+    ses_free(s);
+}
+
+extern "C" int sbr_sessions_reset(sbr_sessions* s, const int32_t* slots, int64_t n) {
+    CHECK_ARG(s, "null argument");
+    sbr_handle* h = s->h;
+    int rc;
+    if ((rc = sessions_state_check(s, "sbr_sessions_reset")) != SBR_OK) return rc;
+    if (!slots) { SBR_LAUNCH(launch_ses_reset(h->stream, s->p, h, nullptr, s->p.capacity)); return SBR_OK; }
+    CHECK_ARG(n >= 0 && n <= s->p.capacity, "sbr_sessions_reset: n=%lld outside [0,capacity=%lld]", (long long)n, s->p.capacity);
+    if ((rc = sessions_check_slots(s, "sbr_sessions_reset", slots, n, true)) != SBR_OK) return rc;
+    if (n == 0) return SBR_OK;
+    // (pageable host memory: the copy has left the caller's array when it returns)
+    SBR_HIP(hipMemcpyAsync(s->d_slots, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    SBR_LAUNCH(launch_ses_reset(h->stream, s->p, h, s->d_slots, n));
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_advance(sbr_sessions* s, const int32_t* slots, const int32_t* items, const int32_t* second, int64_t n) {
+    CHECK_ARG(s && slots && items, "null argument");
+    sbr_handle* h = s->h;
+    const Layout& y = h->lay;
+    int rc;
+    if ((rc = sessions_state_check(s, "sbr_sessions_advance")) != SBR_OK) return rc;
+    CHECK_ARG(n >= 0 && n <= s->p.capacity, "sbr_sessions_advance: n=%lld outside [0,capacity=%lld]", (long long)n, s->p.capacity);
+    CHECK_ARG(y.F == 2 || !second, "sbr_sessions_advance: `second` given, but the model feeds one index per step");
+    CHECK_ARG(y.F == 1 || second, "sbr_sessions_advance: the model feeds two indices per step: `second` is required");
+    const int n_ids = y.cfg.input_size;
+    for (int64_t r = 0; r < n; ++r) {
+        CHECK_ARG(items[r] >= 0 && items[r] < n_ids, "sbr_sessions_advance: items[%lld] = %d outside [0,%d)", (long long)r, items[r], n_ids);
+        if (second) CHECK_ARG(second[r] >= 0 && second[r] < n_ids, "sbr_sessions_advance: second[%lld] = %d outside [0,%d)", (long long)r, second[r], n_ids);
+    }
+    if ((rc = sessions_check_slots(s, "sbr_sessions_advance", slots, n, true)) != SBR_OK) return rc;
+    if (n == 0) return SBR_OK;
+    hipStream_t st = h->stream;
+    // the rows of the index-addressed block that are read must be current (advance reads no output row)
+    if ((rc = flush_lazy(h, 0)) != SBR_OK) return rc;
+    // (pageable host memory: the copies have left the caller's arrays when they return)
+    SBR_HIP(hipMemcpyAsync(s->d_slots, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    SBR_HIP(hipMemcpyAsync(s->d_items, items, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    if (second) SBR_HIP(hipMemcpyAsync(s->d_second, second, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
+    for (int l = 0; l < y.L; ++l) {
+        const LayerLayout& ly = y.layer[l];
+        SesStep a{};
+        a.n = (int)n; a.slots = s->d_slots; a.events = s->p.events; a.capacity = s->p.capacity;
+        a.Hp = ly.Hp; a.K_in = ly.n_in_p;
+        a.Whid = h->P(ly.p_Whid); a.Win = h->P(ly.p_Win); a.bias = h->P(ly.p_b); a.peep = h->P(ly.p_peep);
+        a.hs = s->p.hs[l]; a.cs = s->p.cs[l];
+        a.items = s->d_items; a.second = second ? s->d_second : nullptr;
+        a.emb = y.E ? h->P(y.p_Emb) : nullptr; a.Ep = y.Ep;
+        if (l > 0) { a.in_hs = s->p.hs[l - 1]; a.in_Hp = y.layer[l - 1].Hp; }
+        a.relu = (y.cfg.cell == SBR_CELL_VANILLA && (l > 0 || y.E)) ? 1 : 0;      // stock RecurrentLayer: rectify (rec_shape, sbr_step.hip)
+        SBR_LAUNCH(launch_ses_step(st, y.cfg.cell, a, l > 0 ? SES_IN_DENSE : (y.E ? SES_IN_EMB : SES_IN_INDEX)));
+    }
+    ses_commit_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s->p, s->d_slots, s->d_items, (int)n);
+    SBR_LAUNCH(hipGetLastError());
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_adopt(sbr_sessions* s, const int32_t* slots, int32_t n_rows) {
+    CHECK_ARG(s && slots, "null argument");
+    sbr_handle* h = s->h;
+    const Layout& y = h->lay;
+    int rc;
+    if ((rc = sessions_state_check(s, "sbr_sessions_adopt")) != SBR_OK) return rc;
+    if (!h->have_batch) { sbr_set_error("sbr_sessions_adopt: no batch set"); return SBR_ESTATE; }
+    CHECK_ARG(n_rows >= 0 && n_rows <= h->n_rows, "sbr_sessions_adopt: n_rows=%d, the batch has %d rows", n_rows, h->n_rows);
+    CHECK_ARG(n_rows <= s->p.capacity, "sbr_sessions_adopt: n_rows=%d above the capacity %lld", n_rows, s->p.capacity);
+    if ((rc = sessions_check_slots(s, "sbr_sessions_adopt", slots, n_rows, true)) != SBR_OK) return rc;
+    if (n_rows == 0) return SBR_OK;
+    if ((rc = forward_current(h)) != SBR_OK) return rc;      // the chains' forward pass, if the batch has none yet
+    SBR_HIP(hipMemcpyAsync(s->d_slots, slots, (size_t)n_rows * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    SesAdopt b{};
+    for (int l = 0; l < y.L; ++l) { b.hs[l] = h->A(y.layer[l].a_hs); b.cs[l] = h->A(y.layer[l].a_cs); }
+    b.X = h->bX; b.len = h->blen; b.T = y.T; b.Bp = y.Bp; b.F = y.F;
+    ses_adopt_kernel<<<n_rows, 256, 0, h->stream>>>(s->p, b, ses_init(s->p, h), s->d_slots);
+    SBR_LAUNCH(hipGetLastError());
+    return SBR_OK;
+}
+
+// where slot's current state of `layer` lies: its event count is read first (one wait)
+static int ses_locate(sbr_sessions* s, const char* call, int32_t slot, int32_t layer, long long* events, size_t* at) {
+    CHECK_ARG(slot >= 0 && slot < s->p.capacity, "%s: slot %d outside [0,%lld)", call, slot, s->p.capacity);
+    CHECK_ARG(layer >= 0 && layer < s->p.L, "%s: layer %d outside [0,%d)", call, layer, s->p.L);
+    hipStream_t st = s->h->stream;
+    SBR_HIP(hipMemcpyAsync(events, s->p.events + slot, sizeof(long long), hipMemcpyDeviceToHost, st));
+    SBR_HIP(hipStreamSynchronize(st));
+    *at = ((size_t)(*events & 1) * s->p.capacity + slot) * s->p.Hp[layer];
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_read(sbr_sessions* s, int32_t slot, int32_t layer, float* h_host, float* c_host, int64_t* events, int32_t* history_host) {
+    CHECK_ARG(s, "null argument");
+    long long ev = 0; size_t at = 0;
+    int rc;
+    if ((rc = ses_locate(s, "sbr_sessions_read", slot, layer, &ev, &at)) != SBR_OK) return rc;
+    hipStream_t st = s->h->stream;
+    const size_t row = (size_t)s->p.Hp[layer] * sizeof(float);
+    if (h_host) SBR_HIP(hipMemcpyAsync(h_host, s->p.hs[layer] + at, row, hipMemcpyDeviceToHost, st));
+    if (c_host && s->p.cs[layer]) SBR_HIP(hipMemcpyAsync(c_host, s->p.cs[layer] + at, row, hipMemcpyDeviceToHost, st));
+    std::vector<int> ring;
+    if (history_host && s->p.history > 0) {
+        ring.resize((size_t)s->p.ring_len);
+        SBR_HIP(hipMemcpyAsync(ring.data(), s->p.ring + (size_t)slot * s->p.ring_len, ring.size() * sizeof(int), hipMemcpyDeviceToHost, st));
+    }
+    SBR_HIP(hipStreamSynchronize(st));
+    if (history_host && s->p.history > 0) {
+        const long long kept = std::min<long long>(ev, s->p.history);
+        for (long long t = 0; t < s->p.history; ++t) history_host[t] = t < kept ? ring[(size_t)((ev - kept + t) % s->p.ring_len)] : -1;
+    }
+    if (events) *events = ev;
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_write(sbr_sessions* s, int32_t slot, int32_t layer, const float* h_host, const float* c_host) {
+    CHECK_ARG(s && h_host, "null argument");
+    int rc;
+    if ((rc = sessions_state_check(s, "sbr_sessions_write")) != SBR_OK) return rc;
+    CHECK_ARG(!s->p.cs[0] || c_host, "sbr_sessions_write: an LSTM layer's state is h and c: c_host is required");
+    long long ev = 0; size_t at = 0;
+    if ((rc = ses_locate(s, "sbr_sessions_write", slot, layer, &ev, &at)) != SBR_OK) return rc;
+    hipStream_t st = s->h->stream;
+    const size_t row = (size_t)s->p.Hp[layer] * sizeof(float);
+    SBR_HIP(hipMemcpyAsync(s->p.hs[layer] + at, h_host, row, hipMemcpyHostToDevice, st));
+    if (s->p.cs[layer]) SBR_HIP(hipMemcpyAsync(s->p.cs[layer] + at, c_host, row, hipMemcpyHostToDevice, st));
+    SBR_HIP(hipStreamSynchronize(st));
+    return SBR_OK;
+}

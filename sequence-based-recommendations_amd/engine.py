@@ -46,6 +46,8 @@ EVAL_EXCL_NONE, EVAL_EXCL_VIEWED, EVAL_EXCL_WINDOW, EVAL_EXCL_WINDOW_ZERO = 0, 1
 EVAL_EXCL_PREFIX = 4         # sbr_evaluate_positions only: at position p the distinct items in front of p are never ranked
 # sbr_cluster_evaluate's roads (include/sbr_rnn.h)
 CEVAL_LISTS, CEVAL_PRODUCT = 0, 1
+# sbr_sessions_rank's exclusion modes (include/sbr_rnn.h): nothing, the item fed last, the kept history of the slot
+SESSION_EXCL_NONE, SESSION_EXCL_LAST, SESSION_EXCL_HISTORY = 0, 1, 2
 
 
 class SbrEvalOut(ctypes.Structure):
@@ -89,7 +91,9 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks",
            "sbr_evaluate_positions",
            "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
-           "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load"]
+           "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load",
+           "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_reset", "sbr_sessions_advance", "sbr_sessions_adopt",
+           "sbr_sessions_rank", "sbr_sessions_read", "sbr_sessions_write"]
 
 _lib = None
 
@@ -193,6 +197,15 @@ def load_library(path=None):
         getattr(lib, stem + "_bytes").argtypes = [vp, szp]
         getattr(lib, stem + "_save").argtypes = [vp, vp, ctypes.c_size_t, szp]
         getattr(lib, stem + "_load").argtypes = [vp, vp, ctypes.c_size_t]
+    lib.sbr_sessions_create.argtypes = [vp, ctypes.c_int64, ctypes.c_int32, ctypes.POINTER(vp)]
+    lib.sbr_sessions_destroy.restype = None
+    lib.sbr_sessions_destroy.argtypes = [vp]
+    lib.sbr_sessions_reset.argtypes = [vp, vp, ctypes.c_int64]
+    lib.sbr_sessions_advance.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
+    lib.sbr_sessions_adopt.argtypes = [vp, vp, ctypes.c_int32]
+    lib.sbr_sessions_rank.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    lib.sbr_sessions_read.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, i64p, vp]
+    lib.sbr_sessions_write.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -891,6 +904,11 @@ class RNNEngine(object):
                                                         _ptr(out["pos_off"]), _ptr(out["ranks"]), _ptr(out["n_rankable"]), cap))
         return out
 
+    def sessions(self, capacity, history=0):
+        """A SessionPool of `capacity` kept states beside this engine (sbr_sessions_create), each with a ring of its last
+        `history` fed ids."""
+        return SessionPool(self, capacity, history)
+
     # ---------------------------------------------------------------- debug / timing
     def debug_buffer(self, name):
         ptr, n = ctypes.c_void_p(), ctypes.c_size_t()
@@ -1023,6 +1041,123 @@ class RNNEngine(object):
         us, n = (ctypes.c_float * 2)(), (ctypes.c_int * 2)()
         self._check(self.lib.sbr_chain_times(self.h, 0, us, n))
         return {"fwd_us": float(us[0]), "bwd_us": float(us[1]), "fwd_launches": int(n[0]), "bwd_launches": int(n[1])}
+
+
+# ------------------------------------------------------------------------------------------------ stateful sessions
+def pad_hidden(H):
+    """sbr_pad_hidden (csrc/sbr_common.h): the stored width of a layer of H units"""
+    for w in (16, 32, 64, 128, 256, 512):
+        if H <= w:
+            return w
+    return (H + 63) // 64 * 64
+
+
+def _slot_list(slots):
+    return np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
+
+
+class SessionPool(object):
+    """Kept recurrent states beside an RNNEngine (include/sbr_rnn.h "Stateful sessions", csrc/sbr_session.hip): slot s holds the
+    state of one user after all the events fed to it, so the user's next event costs one recurrent step (advance) and one projection
+    (rank) where RNNEngine.rank feeds the whole history again.  A state is "after p items fed from the start of the sequence"
+    (evaluate_positions' definition): no mask, no window of max_length.  Close the pool before the engine."""
+
+    def __init__(self, engine, capacity, history=0):
+        self.engine, self.lib = engine, engine.lib
+        self.capacity, self.history = int(capacity), int(history)
+        handle = ctypes.c_void_p()
+        with engine.torch.cuda.device(engine.device):
+            engine._check(self.lib.sbr_sessions_create(engine.h, self.capacity, self.history, ctypes.byref(handle)))
+        self.s = handle
+
+    def _check(self, rc):
+        self.engine._check(rc)
+
+    def close(self):
+        if getattr(self, "s", None):
+            if getattr(self.engine, "h", None):      # (an engine already destroyed took its stream along: nothing left to wait for)
+                self.lib.sbr_sessions_destroy(self.s)
+            self.s = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def reset(self, slots=None):
+        """the named slots (None: all) take the current hid_init / cell_init, 0 events, an empty history"""
+        if slots is None:
+            self._check(self.lib.sbr_sessions_reset(self.s, None, 0))
+            return
+        slots = _slot_list(slots)
+        self._check(self.lib.sbr_sessions_reset(self.s, _ptr(slots), len(slots)))
+
+    def advance(self, slots, items, second=None):
+        """one event per named slot: items[r] (and second[r], a model with n_feat == 2) is fed to slots[r]; slots distinct"""
+        self.engine._rank_local_flush("SessionPool.advance")
+        slots, items = _slot_list(slots), _slot_list(items)
+        if len(items) != len(slots):
+            raise ValueError("advance: %d items for %d slots" % (len(items), len(slots)))
+        if second is not None:
+            second = _slot_list(second)
+            if len(second) != len(slots):
+                raise ValueError("advance: %d second indices for %d slots" % (len(second), len(slots)))
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._check(self.lib.sbr_sessions_advance(self.s, _ptr(slots), _ptr(items), _ptr(second), len(slots)))
+
+    def adopt(self, slots):
+        """rows 0 .. len(slots) - 1 of the engine's current batch become the named sessions: their state at the row's length from
+        the chain kernels' forward pass, the length as event count, the last `history` fed ids"""
+        self.engine._rank_local_flush("SessionPool.adopt")
+        slots = _slot_list(slots)
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._check(self.lib.sbr_sessions_adopt(self.s, _ptr(slots), len(slots)))
+
+    def rank(self, slots, k, exclude=SESSION_EXCL_HISTORY, excl_ids=None, excl_off=None, return_scores=False):
+        """Ordered top-k of the next item for the named slots, exactly as RNNEngine.rank_csr returns it: ids (n, k) int32, with
+        return_scores also their float32 scores.  exclude: SESSION_EXCL_NONE / _LAST / _HISTORY (only the last `history` ids of a
+        longer session are excluded); excl_ids / excl_off: a CSR of further ids per row."""
+        self.engine._rank_local_flush("SessionPool.rank")
+        slots = _slot_list(slots)
+        n, k = len(slots), _check_k(k, self.engine.n_items)
+        ids = np.empty((n, k), dtype=np.int32)
+        scores = np.empty((n, k), dtype=np.float32) if return_scores else None
+        excl_ids, excl_off = _csr_args(excl_ids, excl_off, n)
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._check(self.lib.sbr_sessions_rank(self.s, _ptr(slots), n, k, int(exclude), _ptr(excl_ids), _ptr(excl_off), _ptr(ids),
+                                                   _ptr(scores)))
+        return (ids, scores) if return_scores else ids
+
+    def read(self, slot, layer, padded=False):
+        """the state of `slot` in `layer`: {"h": (H,) float32, "c": the same for LSTM else None, "events": fed so far, "history":
+        the last min(events, history) ids, oldest first}; padded: h and c at their stored width"""
+        H = int(self.engine.layers[layer]) if 0 <= int(layer) < len(self.engine.layers) else 1
+        Hp = pad_hidden(H)
+        h = np.zeros(Hp, dtype=np.float32)
+        c = np.zeros(Hp, dtype=np.float32) if self.engine.cell == "LSTM" else None
+        ev = ctypes.c_int64()
+        hist = np.full(max(self.history, 1), -1, dtype=np.int32)
+        self._check(self.lib.sbr_sessions_read(self.s, int(slot), int(layer), _ptr(h), _ptr(c), ctypes.byref(ev), _ptr(hist)))
+        w = Hp if padded else H
+        hist = hist[:self.history]
+        return {"h": h[:w], "c": None if c is None else c[:w], "events": int(ev.value), "history": hist[hist >= 0].copy()}
+
+    def write(self, slot, layer, h, c=None):
+        """puts a state read earlier back (H or stored-width values; padded units of the former are zero); events and history stay"""
+        H = int(self.engine.layers[layer]) if 0 <= int(layer) < len(self.engine.layers) else 1
+        Hp = pad_hidden(H)
+
+        def stored(a):
+            a = np.asarray(a, dtype=np.float32).reshape(-1)
+            if len(a) not in (H, Hp):
+                raise ValueError("write: %d values for a layer of %d units (stored width %d)" % (len(a), H, Hp))
+            out = np.zeros(Hp, dtype=np.float32)
+            out[:len(a)] = a
+            return out
+        h = stored(h)
+        c = None if c is None else stored(c)
+        self._check(self.lib.sbr_sessions_write(self.s, int(slot), int(layer), _ptr(h), _ptr(c)))
 
 
 # ------------------------------------------------------------------------------------------------ RNNCluster's cluster head

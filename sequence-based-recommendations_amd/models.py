@@ -247,6 +247,16 @@ class RNNBase(object):
             out.extend([int(j) for j in row[row >= 0]] for row in ids)
         return out
 
+    def session_pool(self, capacity, history=None):
+        """An engine.SessionPool of `capacity` kept states for serving: feed a user's events one by one (advance) or start from an
+        existing history (engine.set_batch + adopt), and rank the next item from the kept state (rank) -- one recurrent step per
+        event where top_k_batch feeds the whole window again.  history: ids kept per session for the exclusion of viewed items
+        (default max_length).  A session has no window: it equals top_k_batch's state only while the events fit max_length."""
+        if self.dp is not None or self.dist is not None:
+            raise NotImplementedError("session pools of a data-parallel model: every rank would need a pool of its own, fed the same "
+                                      "events at the same step; build the pool on a single-rank model")
+        return self.engine.sessions(capacity, self.max_length if history is None else history)
+
     def _rank_chunks(self, sequences, user_ids, exclude):
         """top_k_batch's engine calls: (X, mask, lists) per batch_size sequences; lists: per row the ids never to rank, which carry
         every viewed item already -- the engine need not derive them from its input window again (exclude_input=False)"""
@@ -1224,6 +1234,12 @@ class RNNCluster(RNNBase):
         if self.predict_with_clusters or self.recurrent_layer.bidirectional:
             return None
         return self._whole_catalogue_position_evaluator(dataset, which, mode, min_history)
+
+    def session_pool(self, capacity, history=None):
+        """A cluster model ranks inside each user's cluster, from the user representation of the engine's current batch
+        (ClusterHead.rank): a session pool's rows are not that batch, so nothing could rank them the way this model ranks."""
+        raise NotImplementedError("session pools of a cluster model: ranking inside a user's cluster reads the engine's current batch, "
+                                  "not the rows of a pool")
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per
