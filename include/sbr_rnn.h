@@ -323,6 +323,31 @@ int sbr_topk(sbr_handle* h, int k, int exclude_seen, int32_t* ids_host);
  * last call ran: the select with the row in LDS (1) or streamed (2), the sort in LDS (1) or as a radix sort in scratch (2). */
 int sbr_rank(sbr_handle* h, int k, int exclude_input, const int32_t* excl_ids, const int64_t* excl_off,
              int32_t* ids_host, float* scores_host);
+/* sbr_rank restricted to a candidate list per row (added under ABI 11: two symbols, this one and sbr_sessions_rank_candidates below;
+ * no struct change) -- "of these few hundred items, which k does the user want next?" behind a retrieval stage or a category page,
+ * without scoring the whole catalogue.
+ *   cand_ids / cand_off  HOST arrays, a CSR, both required.  shared == 0: cand_off has n_rows + 1 entries, row r's candidates are
+ *                        cand_ids[cand_off[r] .. cand_off[r + 1]);  shared != 0: cand_off has 2 entries, one list for every row.
+ *                        Every list is STRICTLY ASCENDING in id and inside [0, N); it may be empty and hold up to N ids (all lists of
+ *                        a call together at most 2^31 - 1).
+ *   ids_host             [n_rows][k], 1 <= k <= N: sbr_rank's ordered top-k of the row restricted to its list -- score descending,
+ *                        ties to the lowest id; NaN, -inf and excluded ids are never ranked; the places a row cannot fill (k above
+ *                        the list's length, an empty list) hold -1
+ *   scores_host          NULL, or [n_rows][k]: raw scores, no softmax; -inf in the unfilled places
+ *   exclude_input, excl_ids / excl_off   exactly sbr_rank's; an excluded id that is not in the row's list is ignored
+ * On the default projection a score is the very float sbr_rank ranks for (row, item) -- the same instruction on the same operand
+ * roles in the same k order, the same two adds -- so the call equals sbr_rank at k = N filtered to the row's list, id for id and bit
+ * for bit.  Two forms: 1 scores only the candidates (per-row lists: cand_score_kernel; a shared list: sbr_cluster_rank's scoring
+ * kernel with one cluster of all rows); 2 runs the full projection and picks the candidates' scores out of it -- taken with
+ * SBR_CAND_RANK=0 in the environment at the engine's creation, with SBR_FLAG_BF16_PROJECTION and with SBR_FLAG_SIMPLE_GEMM.
+ * sbr_query "cand_rank_form" tells which the last call took (0: none yet), "rank_select" / "rank_sort" its regimes.
+ * No batch set: SBR_ESTATE.  SBR_EINVAL, found on the host before anything is launched, the offender named by row and position in
+ * its list: cand_ids or cand_off NULL, negative or decreasing offsets, an id outside [0, N), a list that is not strictly ascending,
+ * k or exclusion lists as sbr_rank rejects them; the engine stays usable and untouched.  A forward is run if the batch has none;
+ * lazily stepped output rows are brought up to date (all of them, as sbr_rank does); parameters, gradients and optimizer state are
+ * otherwise untouched.  Scratch: the handle's ranking scratch (see sbr_rank); sbr_arena_bytes does not change.  One wait, at the end. */
+int sbr_rank_candidates(sbr_handle* h, int k, const int32_t* cand_ids, const int64_t* cand_off, int shared, int exclude_input,
+                        const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host);
 
 /* The dense GEMM of the hot path on caller-provided DEVICE buffers (parity tests of the kernels themselves):
  * C[m][n] = sum_k A[m*sam + k*sak] * B[k*sbk + n*sbn] (+ bias[n]); ws: split-K workspace (may be NULL).
@@ -696,6 +721,10 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  *            -1 / -inf places, scores_host and the caller's lists excl_ids / excl_off (a CSR over the n rows, excluded IN ADDITION)
  *            are sbr_rank's; ids_host [n][k].  exclude_mode: SBR_SESSION_EXCL_*; with a session longer than `history` only the last
  *            `history` ids are excluded (history == 0: none).
+ *   rank_candidates   (sbr_sessions_rank_candidates) rank restricted to a candidate list per named slot: cand_ids / cand_off /
+ *            shared, the result, the two forms and their switch are sbr_rank_candidates' (a CSR over the n rows, or one shared list);
+ *            slots, chunks, exclude_mode and the caller's lists are rank's.  On the default projection it equals rank at k = N
+ *            filtered to the row's list, bit for bit.
  *   read     slot's state in `layer`: h_host / c_host [Hp] floats (Hp = the layer's padded width: 16 / 32 / 64 / 128 / 256 / 512,
  *            above that the next multiple of 64; c_host is written for LSTM only), *events, history_host [history]: the last
  *            min(events, history) ids, oldest first, then -1.  Any output may be NULL.
@@ -703,7 +732,8 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  *            evicting and restoring sessions.
  * SBR_EINVAL, found on the host before anything is launched, the pool untouched, the offender named: a slot outside [0, capacity), a
  * slot named twice in one advance / adopt / reset, an id outside [0, input_size), `second` missing with n_feat == 2 or given with
- * n_feat == 1, n above capacity (advance) or n_rows above the batch's rows (adopt), k, exclude_mode or lists as sbr_rank rejects them. */
+ * n_feat == 1, n above capacity (advance) or n_rows above the batch's rows (adopt), k, exclude_mode or lists as sbr_rank rejects them,
+ * candidate lists as sbr_rank_candidates rejects them. */
 typedef struct sbr_sessions sbr_sessions;
 #define SBR_SESSION_EXCL_NONE    0
 #define SBR_SESSION_EXCL_LAST    1   /* the item fed last is not ranked */
@@ -715,6 +745,9 @@ int  sbr_sessions_advance(sbr_sessions* s, const int32_t* slots, const int32_t* 
 int  sbr_sessions_adopt(sbr_sessions* s, const int32_t* slots, int32_t n_rows);
 int  sbr_sessions_rank(sbr_sessions* s, const int32_t* slots, int64_t n, int k, int exclude_mode,
                        const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host);
+int  sbr_sessions_rank_candidates(sbr_sessions* s, const int32_t* slots, int64_t n, int k,
+                                  const int32_t* cand_ids, const int64_t* cand_off, int shared, int exclude_mode,
+                                  const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host);
 int  sbr_sessions_read(sbr_sessions* s, int32_t slot, int32_t layer, float* h_host, float* c_host, int64_t* events, int32_t* history_host);
 int  sbr_sessions_write(sbr_sessions* s, int32_t slot, int32_t layer, const float* h_host, const float* c_host);
 

@@ -360,6 +360,7 @@ static SbrSwitches sbr_read_switches() {
     sw.out_fuse = flag("SBR_OUT_FUSE", sw.out_fuse);
     sw.row_aware = flag("SBR_ROW_AWARE_UPDATE", sw.row_aware);
     sw.cluster_rank = flag("SBR_CLUSTER_RANK", sw.cluster_rank);
+    sw.cand_rank = flag("SBR_CAND_RANK", sw.cand_rank);
     return sw;
 }
 
@@ -993,6 +994,8 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "rank_sort") *value = h->last_rank_sort;
     // the LAST sbr_cluster_rank: 0 none yet, 1 only the members of each row's cluster were scored, 2 they were gathered from the full scores
     else if (w == "cluster_rank_form") *value = h->last_cluster_rank_form;
+    // the LAST sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates were scored, 2 they were gathered from the full scores
+    else if (w == "cand_rank_form") *value = h->last_cand_rank_form;
     // the LAST sbr_evaluate_ranks: 0 none yet, 1 the row's keys stayed in LDS, 2 every pass streamed the row; and the goal items of a pass
     else if (w == "goal_rank_form") *value = h->last_goal_rank_form;
     else if (w == "goal_rank_tile") *value = kGoalRankTile;

@@ -274,6 +274,8 @@ struct SbrSwitches {
     int row_aware = 1;           // SBR_ROW_AWARE_UPDATE: the dense pass over a wide index-input block skips the gradient traffic of the rows the batch did not touch
     int cluster_rank = 1;        // SBR_CLUSTER_RANK: sbr_cluster_rank scores only the members of each row's cluster (sbr_cluster_rank.hip); 0: it
                                  // gathers them from the full score matrix (also the road of the bf16 / triage projections)
+    int cand_rank = 1;           // SBR_CAND_RANK: sbr_rank_candidates scores only each row's candidates (sbr_cand_rank.hip); 0: it gathers them
+                                 // from the full score matrix (also the road of the bf16 / triage projections)
 };
 
 // Which recurrent kernel serves a layer, and everything the step and sbr_query derive from that choice.  Every input of the
@@ -393,6 +395,7 @@ struct sbr_handle {
     int last_next_rank_form = 0;                                          // sbr_evaluate_positions: 0 none yet, 1 16-byte loads of the score row, 2 4-byte loads
     int last_next_rank_slots = 0;                                         // ... and the positions it projected per GEMM launch at the most
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
+    int last_cand_rank_form = 0;                                          // sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates scored, 2 gathered from the full scores
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
     int last_join_gate = -1, last_fork_gate = -1;                         // what the last step took: sbr_query "step_join_gate" / "step_fork_gate"
@@ -873,6 +876,13 @@ hipError_t launch_crk_gather(hipStream_t s, const float* logits, int N, const in
 // places -> item ids, widened from kk to k columns (-1 / -inf); clu / size (nullable) [rows]: the row's cluster and its list's length
 hipError_t launch_crk_translate(hipStream_t s, const int* pos, const float* psc, int kk, int k, const int* csel, const int* mem_ids,
                                 const int* mem_off, int rows, int* out_ids, float* out_scores, int* size);
+// sbr_cand_rank.hip: ranking inside a candidate list per row (include/sbr_rnn.h: sbr_rank_candidates, sbr_sessions_rank_candidates)
+// cs[row][j] = h[row] . WoutT[cand(row)[j]] + bout[...] for the ascending lists cand_ids[cand_off[row] .. cand_off[row + 1]) of rows that
+// do not share them, -inf behind a row's list: the accumulation order of gemm_f32_mfma + softmax_rows_kernel, bit for bit
+hipError_t launch_cand_score(hipStream_t s, const float* h, int ldh, const float* WoutT, const float* bout, int K, const int* cand_ids,
+                             const int* cand_off, int rows, int lmax, float* cs);
+// launch_crk_group's words (sbr_crk_group_words(rows, 1) of them) for one cluster that all `rows` rows select, written on the host
+void cand_shared_work(int rows, int* work);
 // makes c->hard = f(100 R) if R changed since it was made and, with transposed, c->hardT from it; SBR_OK or a negative sbr_status
 int sbr_cluster_build_hard(sbr_cluster* c, int transposed);
 // sbr_eval.hip: evaluation of whole users on the device (include/sbr_rnn.h: sbr_evaluate).  A user's sequence is split in the middle

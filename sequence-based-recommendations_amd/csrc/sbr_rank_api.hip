@@ -1,6 +1,6 @@
 // The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_topk, sbr_rank, sbr_evaluate, sbr_evaluate_ranks,
-// sbr_evaluate_positions, sbr_cluster_rank, sbr_cluster_evaluate.
-// Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_cluster_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
+// sbr_evaluate_positions, sbr_cluster_rank, sbr_cluster_evaluate, sbr_rank_candidates, sbr_sessions_rank_candidates.
+// Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_cluster_rank.hip, sbr_cand_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
 // sbr_api.hip), built from the shared pieces below: scores, ONE exclusion launch per ranking (launch_exclude: what
 // is excluded is an ExclSources, where it lands an ExclCatalogue or ExclCluster, sbr_device.h), select and sort (rank_rows).
 // Every call waits for the device once, in check_fault.
@@ -206,6 +206,214 @@ extern "C" int sbr_sessions_rank(sbr_sessions* ses, const int32_t* slots, int64_
         src.sessions(dslots + c0, p.ring, p.events, p.ring_len, p.history, exclude_mode);
         SBR_LAUNCH(launch_exclude(s, rows, src, ExclCatalogue{lg, y.N, -INFINITY}));
         if ((rc = rank_rows(h, S, w, lg, rows, y.N, k, (int*)(S + o_oid) + (size_t)c0 * k, (float*)(S + o_osc) + (size_t)c0 * k)) != SBR_OK) return rc;
+    }
+    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, nk * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, nk * sizeof(float), hipMemcpyDeviceToHost, s));
+    return check_fault(h);
+}
+
+// ---------------------------------------------------------------------------------------
+// Ranking inside a candidate list the caller brings (include/sbr_rnn.h: sbr_rank_candidates, sbr_sessions_rank_candidates; kernels
+// and the accumulation-order argument: sbr_cand_rank.hip, sbr_cluster_rank.hip)
+// ---------------------------------------------------------------------------------------
+// The caller's candidate lists, a CSR over the rows of the call (shared: ONE list for every row), and where their device copy sits in
+// the scratch: the offsets as int rebased to 0 and, behind them, what makes the lists "clusters" for the shared pieces -- the cluster
+// of a row (its own index, or 0 for the shared list) and, for the shared list, crk_score_kernel's tile tables for a full chunk of rows
+// and for the last, shorter one
+struct CandLists {
+    const int32_t* ids; const int64_t* off; int64_t rows; bool shared; int64_t n;      // n: ids in all
+    int chunk, last;                                     // rows of a full chunk of the call and of its last one
+    size_t o_meta, o_ids, w_csel, w_full, w_last, words; // offsets in the scratch (bytes) and inside the meta words
+    const int* dev_off(const char* S) const { return (const int*)(S + o_meta); }
+    const int* dev_csel(const char* S) const { return (const int*)(S + o_meta) + w_csel; }
+    const int* dev_work(const char* S, int n_rows) const { return (const int*)(S + o_meta) + (n_rows == chunk ? w_full : w_last); }
+    const int* dev_ids(const char* S) const { return (const int*)(S + o_ids); }
+    int64_t lists() const { return shared ? 1 : rows; }
+    // the width of the compact matrix of rows [c0, c0 + n_rows): their longest list, rounded up to 4 as the cluster road's
+    int lmax(int64_t c0, int n_rows) const {
+        int64_t longest = 0;
+        if (shared) longest = off[1] - off[0];
+        else for (int64_t r = c0; r < c0 + n_rows; ++r) longest = std::max<int64_t>(longest, off[r + 1] - off[r]);
+        return (int)std::max<int64_t>(4, (longest + 3) / 4 * 4);
+    }
+};
+// everything about the lists is checked here, before anything is launched; chunk: rows of the call that are ranked together
+static int cand_check(const int32_t* cand_ids, const int64_t* cand_off, int64_t rows, int chunk, int shared, int N, CandLists& c) {
+    CHECK_ARG(cand_ids && cand_off, "cand_ids and cand_off: both are required");
+    CHECK_ARG(rows >= 1, "no rows to rank");
+    c = CandLists{cand_ids, cand_off, rows, shared != 0, 0, (int)std::min<int64_t>(rows, chunk), 0, 0, 0, 0, 0, 0, 0};      // (rows >= 1)
+    c.last = rows % c.chunk ? (int)(rows % c.chunk) : c.chunk;
+    const int64_t nl = c.lists();
+    CHECK_ARG(cand_off[0] >= 0, "cand_off[0] = %lld is negative", (long long)cand_off[0]);
+    for (int64_t r = 0; r < nl; ++r)
+        CHECK_ARG(cand_off[r + 1] >= cand_off[r], "cand_off decreases at row %lld (%lld -> %lld)", (long long)r, (long long)cand_off[r], (long long)cand_off[r + 1]);
+    c.n = cand_off[nl] - cand_off[0];
+    for (int64_t r = 0; r < nl; ++r) {
+        // a pass without branches first (the compiler vectorises it: a third of the time of the walk below, and the lists of a call can
+        // hold millions of ids); only a list that fails is walked again, for the offender
+        const int32_t* l = cand_ids + cand_off[r];
+        const int64_t len = cand_off[r + 1] - cand_off[r];
+        unsigned bad = 0;
+        for (int64_t j = 0; j < len; ++j) bad |= (unsigned)((unsigned)l[j] >= (unsigned)N);
+        for (int64_t j = 1; j < len; ++j) bad |= (unsigned)(l[j - 1] >= l[j]);
+        if (!bad) continue;
+        for (int64_t j = cand_off[r]; j < cand_off[r + 1]; ++j) {
+            const int id = cand_ids[j];
+            CHECK_ARG(id >= 0 && id < N, "candidate %d of row %lld, at position %lld of its list, is outside [0,%d)", id, (long long)r, (long long)(j - cand_off[r]), N);
+            CHECK_ARG(j == cand_off[r] || cand_ids[j - 1] < id, "the candidates of row %lld are not strictly ascending at position %lld (%d after %d)",
+                      (long long)r, (long long)(j - cand_off[r]), id, cand_ids[j - 1]);
+        }
+    }
+    CHECK_ARG(c.n <= 0x7fffffff, "the candidate lists of one call hold %lld ids, at most 2^31 - 1", (long long)c.n);
+    return SBR_OK;
+}
+static void cand_carve(Carver& cv, CandLists& c) {
+    c.w_csel = (size_t)c.lists() + 1;
+    c.w_full = c.w_csel + c.chunk;
+    c.w_last = c.w_full + (c.shared ? sbr_crk_group_words(c.chunk, 1) : 0);
+    c.words = c.w_last + (c.shared && c.last != c.chunk ? sbr_crk_group_words(c.last, 1) : 0);
+    c.o_meta = cv.take(c.words * sizeof(int)); c.o_ids = cv.take((size_t)c.n * sizeof(int));
+}
+// (excl_upload's pattern: two asynchronous copies, one wait)
+static int cand_upload(sbr_handle* h, char* S, const CandLists& c) {
+    std::vector<int> meta(c.words);
+    for (int64_t r = 0; r <= c.lists(); ++r) meta[r] = (int)(c.off[r] - c.off[0]);
+    for (int r = 0; r < c.chunk; ++r) meta[c.w_csel + r] = c.shared ? 0 : r;
+    if (c.shared) {
+        cand_shared_work(c.chunk, meta.data() + c.w_full);
+        if (c.last != c.chunk) cand_shared_work(c.last, meta.data() + c.w_last);
+    }
+    // (pageable host memory: both copies have left the host buffers when they return)
+    SBR_HIP(hipMemcpyAsync(S + c.o_meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (c.n) SBR_HIP(hipMemcpyAsync(S + c.o_ids, c.ids + c.off[0], (size_t)c.n * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    SBR_HIP(hipStreamSynchronize(h->stream));           // `meta` goes out of scope
+    return SBR_OK;
+}
+
+// form 1 restates the exact-f32 projection for the candidates only; the bf16 and the triage projections round differently, and their
+// scores are gathered from the matrix those kernels write (form 2, also SBR_CAND_RANK=0)
+static bool cand_rank_restricted(const sbr_handle* h) {
+    return h->sw.cand_rank && !(h->lay.cfg.flags & SBR_FLAG_BF16_PROJECTION) && !simple_gemm(h);
+}
+
+// what a chunk of a candidate ranking works in beside the lists: the compact score matrix, select + sort, the ranked places
+struct CandWork { size_t cs; RankWork w; size_t pos, psc; };
+static CandWork carve_cand_work(Carver& cv, const CandLists& c, int k) {
+    int lmax = 4;
+    for (int64_t c0 = 0; c0 < c.rows; c0 += c.chunk) lmax = std::max(lmax, c.lmax(c0, (int)std::min<int64_t>(c.chunk, c.rows - c0)));
+    const int kk = std::min(k, lmax);
+    CandWork cw;
+    cw.cs = cv.take((size_t)c.chunk * lmax * sizeof(float));
+    cw.w = carve_rank_work(cv, c.chunk, kk, kk > kRankSortLds);
+    cw.pos = cv.take((size_t)c.chunk * kk * sizeof(int)); cw.psc = cv.take((size_t)c.chunk * kk * sizeof(float));
+    return cw;
+}
+
+// Rows [c0, c0 + rows) of the call: the candidates' scores into cs [rows][lmax] -- scored from `states` [rows][HLt] (restricted: the
+// shared list by crk_score_kernel as one cluster of all rows, per-row lists by cand_score_kernel) or gathered from the full scores `lg`
+// [rows][N] --, then sbr_cluster_rank's pipeline with the row's own list as its cluster: exclusion, select and sort to
+// min(k, lmax) places, places -> ids.
+static int cand_rank_chunk(sbr_handle* h, char* S, const CandLists& c, const CandWork& cw, const float* states, const float* lg, int64_t c0,
+                           int rows, const ExclSources& src, int k, bool restricted, int* out_ids, float* out_scores) {
+    const Layout& y = h->lay;
+    hipStream_t s = h->stream;
+    const int lmax = c.lmax(c0, rows), kk = std::min(k, lmax), C = c.shared ? 1 : rows;
+    const int* moff = c.dev_off(S) + (c.shared ? 0 : c0);
+    const int* csel = c.dev_csel(S);
+    const int* mem = c.dev_ids(S);
+    float* cs = (float*)(S + cw.cs);
+    if (!restricted)
+        SBR_LAUNCH(launch_crk_gather(s, lg, y.N, csel, mem, moff, rows, lmax, cs));
+    else if (c.shared)
+        SBR_LAUNCH(launch_crk_score(s, states, y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, mem, moff, c.dev_work(S, rows), rows, 1, lmax, cs));
+    else
+        SBR_LAUNCH(launch_cand_score(s, states, y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, mem, moff, rows, lmax, cs));
+    h->last_cand_rank_form = restricted ? 1 : 2;
+    SBR_LAUNCH(launch_exclude(s, rows, src, ExclCluster{cs, lmax, csel, C, mem, moff, y.N}));
+    int rc;
+    if ((rc = rank_rows(h, S, cw.w, cs, rows, lmax, kk, (int*)(S + cw.pos), (float*)(S + cw.psc))) != SBR_OK) return rc;
+    SBR_LAUNCH(launch_crk_translate(s, (const int*)(S + cw.pos), (const float*)(S + cw.psc), kk, k, csel, mem, moff, rows, out_ids, out_scores, nullptr));
+    return SBR_OK;
+}
+
+// sbr_rank restricted to each row's candidate list
+extern "C" int sbr_rank_candidates(sbr_handle* h, int k, const int32_t* cand_ids, const int64_t* cand_off, int shared, int exclude_input,
+                                   const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host) {
+    CHECK_ARG(h && ids_host, "null argument");
+    if (!h->have_batch) { sbr_set_error("sbr_rank_candidates: no batch set"); return SBR_ESTATE; }
+    const Layout& y = h->lay;
+    const int rows = h->n_rows;
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    CandLists c;
+    ExclLists x;
+    int rc;
+    if ((rc = cand_check(cand_ids, cand_off, rows, rows, shared, y.N, c)) != SBR_OK) return rc;
+    if ((rc = excl_check(excl_ids, excl_off, rows, y.N, x)) != SBR_OK) return rc;
+    const size_t rk = (size_t)rows * k;
+    Carver cv;
+    excl_carve(cv, x);
+    cand_carve(cv, c);
+    const CandWork cw = carve_cand_work(cv, c, k);
+    const size_t o_oid = cv.take(rk * sizeof(int)), o_osc = cv.take(rk * sizeof(float));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    const bool restricted = cand_rank_restricted(h);
+    if ((rc = restricted ? forward_current(h) : full_scores(h, 0)) != SBR_OK) return rc;
+    if ((rc = excl_upload(h, S, x)) != SBR_OK || (rc = cand_upload(h, S, c)) != SBR_OK) return rc;
+    if ((rc = cand_rank_chunk(h, S, c, cw, h_last(h), h->A(y.a_logits), 0, rows, excl_sources(h, S, x, exclude_input), k, restricted,
+                              (int*)(S + o_oid), (float*)(S + o_osc))) != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, rk * sizeof(int), hipMemcpyDeviceToHost, h->stream));
+    if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, rk * sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    return check_fault(h);          // a forward that gave up must not hand out rankings
+}
+
+// sbr_sessions_rank restricted to each named slot's candidate list: its chunks, its exclusion sources, cand_rank_chunk per chunk
+extern "C" int sbr_sessions_rank_candidates(sbr_sessions* ses, const int32_t* slots, int64_t n, int k, const int32_t* cand_ids,
+                                            const int64_t* cand_off, int shared, int exclude_mode, const int32_t* excl_ids,
+                                            const int64_t* excl_off, int32_t* ids_host, float* scores_host) {
+    CHECK_ARG(ses && slots && ids_host, "null argument");
+    sbr_handle* h = ses->h;
+    const Layout& y = h->lay;
+    const SesPool& p = ses->p;
+    int rc;
+    if ((rc = sessions_state_check(ses, "sbr_sessions_rank_candidates")) != SBR_OK) return rc;
+    CHECK_ARG(n >= 1 && n <= 0x7fffffff, "sbr_sessions_rank_candidates: n=%lld sessions: at least one", (long long)n);
+    CHECK_ARG(k >= 1 && k <= y.N, "k=%d outside [1,N=%d]", k, y.N);
+    CHECK_ARG(exclude_mode >= SBR_SESSION_EXCL_NONE && exclude_mode <= SBR_SESSION_EXCL_HISTORY, "unknown exclusion mode %d", exclude_mode);
+    if ((rc = sessions_check_slots(ses, "sbr_sessions_rank_candidates", slots, n, false)) != SBR_OK) return rc;
+    const int B = y.B;
+    CandLists c;
+    ExclLists x;
+    if ((rc = cand_check(cand_ids, cand_off, n, B, shared, y.N, c)) != SBR_OK) return rc;
+    if ((rc = excl_check(excl_ids, excl_off, (int)n, y.N, x)) != SBR_OK) return rc;
+    const size_t nk = (size_t)n * k;
+    Carver cv;
+    const size_t o_slots = cv.take((size_t)n * sizeof(int));
+    excl_carve(cv, x);
+    cand_carve(cv, c);
+    const size_t o_states = cv.take((size_t)B * y.HLt * sizeof(float));
+    const CandWork cw = carve_cand_work(cv, c, k);
+    const size_t o_oid = cv.take(nk * sizeof(int)), o_osc = cv.take(nk * sizeof(float));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;      // all of W_out^T / b_out current, as sbr_sessions_rank leaves it
+    // (pageable host memory: the copy has left the caller's array when it returns)
+    SBR_HIP(hipMemcpyAsync(S + o_slots, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    if ((rc = excl_upload(h, S, x)) != SBR_OK || (rc = cand_upload(h, S, c)) != SBR_OK) return rc;
+    const int* dslots = (const int*)(S + o_slots);
+    float* states = (float*)(S + o_states);
+    float* lg = h->A(y.a_logits);
+    const bool restricted = cand_rank_restricted(h);
+    for (int64_t c0 = 0; c0 < n; c0 += B) {
+        const int rows = (int)std::min<int64_t>(B, n - c0);
+        SBR_LAUNCH(launch_ses_gather_top(s, p, dslots + c0, rows, states));
+        if (!restricted && (rc = project_rows(h, states, rows, lg, 0)) != SBR_OK) return rc;
+        ExclSources src;
+        if (x.off) src.lists(x.dev_ids(S), x.dev_off(S) + c0);
+        src.sessions(dslots + c0, p.ring, p.events, p.ring_len, p.history, exclude_mode);
+        if ((rc = cand_rank_chunk(h, S, c, cw, states, lg, c0, rows, src, k, restricted, (int*)(S + o_oid) + (size_t)c0 * k,
+                                  (float*)(S + o_osc) + (size_t)c0 * k)) != SBR_OK) return rc;
     }
     SBR_HIP(hipMemcpyAsync(ids_host, S + o_oid, nk * sizeof(int), hipMemcpyDeviceToHost, s));
     if (scores_host) SBR_HIP(hipMemcpyAsync(scores_host, S + o_osc, nk * sizeof(float), hipMemcpyDeviceToHost, s));

@@ -78,7 +78,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_param_shape", "sbr_describe_param", "sbr_set_params", "sbr_get_params", "sbr_get_grads", "sbr_section", "sbr_set_batch",
            "sbr_set_default_target",
            "sbr_train_step", "sbr_train_step_lagged", "sbr_cost_lagged", "sbr_lagged_flush", "sbr_zero_grads", "sbr_forward", "sbr_loss_backward_output", "sbr_backward_recurrent",
-           "sbr_apply_update", "sbr_read_cost", "sbr_predict_scores", "sbr_topk", "sbr_rank", "sbr_debug_buffer",
+           "sbr_apply_update", "sbr_read_cost", "sbr_predict_scores", "sbr_topk", "sbr_rank", "sbr_rank_candidates", "sbr_debug_buffer",
            "sbr_copy_to_host", "sbr_synchronize", "sbr_enable_timing", "sbr_phase_times", "sbr_chain_times", "sbr_query",
            "sbr_set_deferred_join", "sbr_join_side", "sbr_debug_gemm", "sbr_debug_scatter", "sbr_debug_occupy", "sbr_flush_lazy", "sbr_sparse_info", "sbr_sparse_pack",
            "sbr_sparse_unpack_add", "sbr_dense_ranges", "sbr_sparse_pack_device", "sbr_sparse_unpack_add_all",
@@ -93,7 +93,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
            "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load",
            "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_reset", "sbr_sessions_advance", "sbr_sessions_adopt",
-           "sbr_sessions_rank", "sbr_sessions_read", "sbr_sessions_write"]
+           "sbr_sessions_rank", "sbr_sessions_rank_candidates", "sbr_sessions_read", "sbr_sessions_write"]
 
 _lib = None
 
@@ -139,6 +139,7 @@ def load_library(path=None):
     lib.sbr_predict_scores.argtypes = [vp, ctypes.c_int, vp]
     lib.sbr_topk.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp]
     lib.sbr_rank.argtypes = [vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    lib.sbr_rank_candidates.argtypes = [vp, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     lib.sbr_debug_buffer.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(vp), ctypes.POINTER(ctypes.c_size_t)]
     lib.sbr_copy_to_host.argtypes = [vp, vp, vp, ctypes.c_size_t]
     lib.sbr_enable_timing.argtypes = [vp, ctypes.c_int]
@@ -204,6 +205,7 @@ def load_library(path=None):
     lib.sbr_sessions_advance.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
     lib.sbr_sessions_adopt.argtypes = [vp, vp, ctypes.c_int32]
     lib.sbr_sessions_rank.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
+    lib.sbr_sessions_rank_candidates.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     lib.sbr_sessions_read.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, i64p, vp]
     lib.sbr_sessions_write.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp]
     if path == LIB_PATH:
@@ -256,6 +258,38 @@ def _csr_args(excl_ids, excl_off, rows):
         if excl_off.shape != (rows + 1,):
             raise ValueError("excl_off must have %d entries (rows + 1), got %r" % (rows + 1, excl_off.shape))
     return excl_ids, excl_off
+
+
+def _cand_csr(candidates, n):
+    """rank_candidates()'s `candidates` as the CSR sbr_rank_candidates takes: (int32 ids, int64 offsets, shared).  A single 1-D array
+    of ids is ONE list shared by all n rows; anything else holds one id list per row (None or empty: no candidates).  Every list
+    comes out strictly ascending: sorted and de-duplicated (np.unique)."""
+    shared = isinstance(candidates, np.ndarray) and candidates.ndim == 1 and candidates.dtype != object
+    if not shared and len(candidates) > 0 and all(np.ndim(c) == 0 and c is not None for c in candidates):
+        shared = True                                                 # a plain list of ids
+    if shared:
+        lists = [candidates]
+    else:
+        lists = list(candidates)
+        if len(lists) != n:
+            raise ValueError("candidates must hold one id list per row: %d lists for %d rows" % (len(lists), n))
+    lists = [np.zeros(0, dtype=np.int32) if c is None else np.unique(np.asarray(c, dtype=np.int32).reshape(-1)) for c in lists]
+    off_arr = np.zeros(len(lists) + 1, dtype=np.int64)
+    np.cumsum([len(c) for c in lists], out=off_arr[1:])
+    ids_arr = np.ascontiguousarray(np.concatenate(lists + [np.zeros(1, dtype=np.int32)]))   # (never empty: its pointer is not NULL)
+    return ids_arr, off_arr, shared
+
+
+def _cand_args(cand_ids, cand_off, shared, rows):
+    """rank_candidates_csr()'s lists in the C-ABI's types"""
+    if cand_ids is not None:
+        cand_ids = np.ascontiguousarray(np.asarray(cand_ids, dtype=np.int32))
+    if cand_off is not None:
+        cand_off = np.ascontiguousarray(np.asarray(cand_off, dtype=np.int64))
+        want = 2 if shared else rows + 1
+        if cand_off.shape != (want,):
+            raise ValueError("cand_off must have %d entries (%s), got %r" % (want, "a shared list" if shared else "rows + 1", cand_off.shape))
+    return cand_ids, cand_off
 
 
 def _eval_record(n, k, n_items, want_mask, want_ids):
@@ -847,6 +881,33 @@ class RNNEngine(object):
         self._check(self.lib.sbr_rank(self.h, k, int(bool(exclude_input)), _ptr(excl_ids), _ptr(excl_off), _ptr(ids), _ptr(scores)))
         return (ids, scores) if return_scores else ids
 
+    def rank_candidates(self, X, mask, k, candidates, exclude=None, exclude_input=True, return_scores=False):
+        """rank() restricted to candidate lists (sbr_rank_candidates): for every row the ordered top-k among ITS candidates only,
+        without scoring the whole catalogue.  candidates: a sequence of per-row id arrays (any order, duplicates allowed: each is
+        sorted and de-duplicated; None or empty: nothing to rank), or a single 1-D array of ids, one list shared by every row.  ids
+        (rows, k) int32 and, with return_scores, float32 scores exactly as rank() at k = n_items returns them filtered to the row's
+        list; -1 / -inf where a row has fewer than k rankable candidates.  exclude / exclude_input: rank()'s."""
+        self._rank_local_flush("rank_candidates")
+        n = self.set_batch(X, mask)
+        cand_ids, cand_off, shared = _cand_csr(candidates, n)
+        ids_arr, off_arr = _excl_csr(exclude, n)
+        return self.rank_candidates_csr(n, k, cand_ids, cand_off, shared, ids_arr, off_arr, exclude_input=exclude_input,
+                                        return_scores=return_scores)
+
+    def rank_candidates_csr(self, rows, k, cand_ids, cand_off, shared, excl_ids=None, excl_off=None, exclude_input=True,
+                            return_scores=False):
+        """sbr_rank_candidates on the batch already set (`rows` rows); the lists as the C-ABI takes them: every candidate list
+        strictly ascending, int32 ids and int64 offsets (rows + 1 of them, or 2 with shared)."""
+        self._rank_local_flush("rank_candidates")
+        k = _check_k(k, self.n_items)
+        ids = np.empty((rows, k), dtype=np.int32)
+        scores = np.empty((rows, k), dtype=np.float32) if return_scores else None
+        cand_ids, cand_off = _cand_args(cand_ids, cand_off, shared, rows)
+        excl_ids, excl_off = _csr_args(excl_ids, excl_off, rows)
+        self._check(self.lib.sbr_rank_candidates(self.h, k, _ptr(cand_ids), _ptr(cand_off), int(bool(shared)), int(bool(exclude_input)),
+                                                 _ptr(excl_ids), _ptr(excl_off), _ptr(ids), _ptr(scores)))
+        return (ids, scores) if return_scores else ids
+
     def evaluate(self, dataset, users, k, exclude_mode, want_ids=False, want_mask=True):
         """Whole users of a DeviceDataset evaluated on the device (sbr_evaluate): each user's sequence is split in the middle, the
         last max_length items of the viewed half go in, the ranking to depth k is compared with the rest.  exclude_mode: one of
@@ -1127,6 +1188,31 @@ class SessionPool(object):
         with self.engine.torch.cuda.device(self.engine.device):
             self._check(self.lib.sbr_sessions_rank(self.s, _ptr(slots), n, k, int(exclude), _ptr(excl_ids), _ptr(excl_off), _ptr(ids),
                                                    _ptr(scores)))
+        return (ids, scores) if return_scores else ids
+
+    def rank_candidates(self, slots, k, candidates, exclude=SESSION_EXCL_HISTORY, excl_ids=None, excl_off=None, return_scores=False):
+        """rank() restricted to candidate lists (sbr_sessions_rank_candidates): candidates as RNNEngine.rank_candidates takes them --
+        one id array per named slot (sorted and de-duplicated here), or a single 1-D array shared by all of them.  The result equals
+        rank(k = n_items) filtered to each row's list."""
+        slots = _slot_list(slots)
+        cand_ids, cand_off, shared = _cand_csr(candidates, len(slots))
+        return self.rank_candidates_csr(slots, k, cand_ids, cand_off, shared, exclude=exclude, excl_ids=excl_ids, excl_off=excl_off,
+                                        return_scores=return_scores)
+
+    def rank_candidates_csr(self, slots, k, cand_ids, cand_off, shared, exclude=SESSION_EXCL_HISTORY, excl_ids=None, excl_off=None,
+                            return_scores=False):
+        """sbr_sessions_rank_candidates with the lists as the C-ABI takes them: every candidate list strictly ascending, int32 ids
+        and int64 offsets (len(slots) + 1 of them, or 2 with shared)"""
+        self.engine._rank_local_flush("SessionPool.rank_candidates")
+        slots = _slot_list(slots)
+        n, k = len(slots), _check_k(k, self.engine.n_items)
+        ids = np.empty((n, k), dtype=np.int32)
+        scores = np.empty((n, k), dtype=np.float32) if return_scores else None
+        cand_ids, cand_off = _cand_args(cand_ids, cand_off, shared, n)
+        excl_ids, excl_off = _csr_args(excl_ids, excl_off, n)
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._check(self.lib.sbr_sessions_rank_candidates(self.s, _ptr(slots), n, k, _ptr(cand_ids), _ptr(cand_off), int(bool(shared)),
+                                                              int(exclude), _ptr(excl_ids), _ptr(excl_off), _ptr(ids), _ptr(scores)))
         return (ids, scores) if return_scores else ids
 
     def read(self, slot, layer, padded=False):

@@ -235,15 +235,24 @@ class RNNBase(object):
 
     batched_top_k = True        # top_k_batch ranks what top_k_recommendations ranks (RNNCluster: inside the user's cluster, and it returns (ids, n_scored))
 
-    def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
+    def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None, candidates=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)], batch_size rows per engine
         call (engine.rank): per sequence the last max_length items go in; every item of the WHOLE sequence is excluded when
         interactions are unique -- also the part that no longer fits the window -- plus the row's own exclude list; any
         1 <= k <= n_items.  Returns a list of id lists, best first; a row with fewer than k rankable items returns only
-        those (top_k_recommendations would go on with excluded ids, in no defined order)."""
-        out = []
+        those (top_k_recommendations would go on with excluded ids, in no defined order).
+        candidates: None, or what engine.rank_candidates takes -- one id list per sequence, or a single 1-D array shared by all of
+        them: only these items are scored and ranked (the same ids, in the same order, as the full ranking filtered to the list)."""
+        from .engine import _cand_csr
+        shared = candidates is not None and _cand_csr(candidates, len(sequences))[2]      # (also: one list per sequence, or it raises)
+        out, lo = [], 0
         for X, mask, lists in self._rank_chunks(sequences, user_ids, exclude):
-            ids = self._rd().rank(X, mask, k, exclude=lists, exclude_input=False)
+            if candidates is None:
+                ids = self._rd().rank(X, mask, k, exclude=lists, exclude_input=False)
+            else:
+                cand = candidates if shared else candidates[lo:lo + len(X)]
+                ids = self._rd().rank_candidates(X, mask, k, cand, exclude=lists, exclude_input=False)
+            lo += len(X)
             out.extend([int(j) for j in row[row >= 0]] for row in ids)
         return out
 
@@ -1241,13 +1250,17 @@ class RNNCluster(RNNBase):
         raise NotImplementedError("session pools of a cluster model: ranking inside a user's cluster reads the engine's current batch, "
                                   "not the rows of a pool")
 
-    def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None):
+    def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None, candidates=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per
         call (ClusterHead.rank): one (ids, n_scored) per sequence -- the ranked ids inside the user's cluster, best first, and the
         number of items in that cluster.  Per sequence the last max_length items go in; with unique interactions the WHOLE sequence
         is excluded, plus the row's own list; any 1 <= k <= n_items.  A row with fewer than k rankable members returns only those
         (the host road goes on with excluded ids, in numpy's partition order).  --ignore_clusters: the whole catalogue, as
-        RNNBase.top_k_batch ranks it, with n_scored = n_items."""
+        RNNBase.top_k_batch ranks it, with n_scored = n_items.  candidates: refused -- this model's ranking is restricted already,
+        to the user's cluster."""
+        if candidates is not None:
+            raise NotImplementedError("candidates for a cluster model: its ranking is already restricted, to the members of the user's "
+                                      "cluster (ClusterHead.rank)")
         if not self.predict_with_clusters:
             ranked = super(RNNCluster, self).top_k_batch(sequences, user_ids=user_ids, k=k, exclude=exclude)
             return [(ids, self.n_items) for ids in ranked]
