@@ -575,6 +575,61 @@ int sbr_evaluate_positions(sbr_handle* h, sbr_dataset* d, const int32_t* users, 
                            int64_t cap);               /* must be >= pos_off[n] = sum over users of max(0, min(L - 1, T) - min_history + 1) */
 
 /* ------------------------------------------------------------------------------------------------
+ * The rank of every goal item among a candidate set of its user (added under ABI 11: two symbols and one constant, no struct change)
+ * -- the protocol of the sequential-recommendation papers: each positive against S negatives the user never interacted with, HR@k /
+ * NDCG@k / MRR from the ranks -- without scoring the whole catalogue.  Users are split, fed and chunked (local_batch per chunk)
+ * exactly as by sbr_evaluate_ranks; users may repeat; the handle is left as sbr_set_batch leaves it.  The candidate set C_j of
+ * users[j] comes from exactly one of two sources:
+ *   explicit   cand_ids / cand_off: HOST arrays, a CSR with n + 1 offsets as sbr_rank_candidates takes it (shared == 0): every list
+ *              strictly ascending in id, inside [0, N), possibly empty, up to N ids; n_negatives = 0, neg_cdf and negatives_host NULL;
+ *   sampled    cand_ids = cand_off = NULL, 1 <= n_negatives <= min(N - 1, SBR_EVAL_MAX_NEGATIVES): drawn on the device by a rule the
+ *              host restates (sbr_eval_negatives_host).  With s_u = mix64(seed ^ mix64(0xCA4D + u)), u the user's id in the dataset
+ *              (not its place in the call) and mix64 the splitmix64 finaliser, attempt t = 0, 1, .. draws item
+ *              r_t % N (neg_cdf NULL: uniform) or the first i with neg_cdf[i] > (r_t >> 11) * 2^-53 * neg_cdf[N - 1] (neg_cdf: HOST
+ *              [N], non-decreasing with positive mass, as sbr_dataset_set_tables checks sample_cdf), r_t = mix64(s_u ^ mix64(0xA5A5 + t))
+ *              -- the law of the batch builder's negatives.  An attempt is accepted when its item occurs nowhere in user u's uploaded
+ *              sequence (viewed or goal) and was not accepted before; the draw ends at n_negatives accepted or after
+ *              16 * n_negatives + 256 attempts, so a row may hold fewer (n_cand and negatives say so).  The list depends on
+ *              (seed, u, n_negatives, neg_cdf) only: not on the chunk, the order or the repetition of users.
+ * For goal place p (sequence order, p < L - L / 2), with g the item there:
+ *   ranks[goal_off[j] + p]   the number of rankable i in C_j that stand before g in sbr_rank's order (key descending, ties to the lowest
+ *                            id); -1 when g itself is not rankable (NaN, -inf, excluded by the mode, outside the catalogue).  g need
+ *                            not be in C_j; a goal item competes with the list alone, not with the other goal items (unless the list
+ *                            names them); a goal that repeats an item holds the same rank at each of its places.
+ *   n_cand[j]                the rankable members of C_j.
+ *   negatives[j][..]         NULL, or (sampled only) [n][n_negatives]: the accepted ids in draw order, -1 behind the last.
+ * With C_j = all N items, ranks and n_cand are sbr_evaluate_ranks' ranks and n_rankable.
+ * exclude_mode: SBR_EVAL_EXCL_NONE, _VIEWED or _WINDOW -- an excluded item is neither ranked as a goal nor counted as a candidate;
+ * _WINDOW_ZERO is SBR_EINVAL (a 0.0 for the items fed exists in the whole-catalogue matrix only).
+ * Per chunk: pack, forward, ev_cand_build_kernel ([the draw,] candidates and distinct goal ids merged ascending into a device CSR),
+ * the scores of those ids by sbr_rank_candidates' two forms -- 1: cand_score_kernel, on the default projection the very floats sbr_rank
+ * ranks; 2: the full projection, gathered (SBR_CAND_RANK=0, SBR_FLAG_BF16_PROJECTION, SBR_FLAG_SIMPLE_GEMM) --, ev_cand_place_kernel
+ * (exclusion from the dataset's CSR, then integer counts; sbr_eval_cand.hip).  sbr_query "eval_cand_form": the form of the last call
+ * (0: none yet); "eval_cand_lmax": the width of its last chunk's compact score matrix.  goal_off is computed on the host and written
+ * before anything is launched; everything is enqueued on the engine's stream and the call waits once, at its end (explicit lists are
+ * uploaded once, in front of the first chunk, as sbr_rank_candidates uploads them).
+ * SBR_EINVAL, found on the host before anything is launched (nothing but goal_off -- and that only once cap is known to suffice -- is
+ * written, the engine stays usable): everything sbr_evaluate_ranks rejects, both or neither candidate source, a bad CSR (the offender
+ * named by user and position, as sbr_rank_candidates names it), n_negatives or neg_cdf out of bounds, neg_cdf or negatives_host
+ * together with explicit lists, cap < goal_off[n].  SBR_ESTATE inside an open training step.  Parameters, gradients and optimizer
+ * state are the same bits after the call as before it, by the keep-and-restore sbr_evaluate_ranks describes.  Scratch: the handle's
+ * ranking scratch (the lists, per chunk the merged lists and local_batch x width scores; the copy of parameters as for sbr_evaluate_ranks). */
+#define SBR_EVAL_MAX_NEGATIVES 4096
+int sbr_evaluate_candidates(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int exclude_mode,
+                            const int32_t* cand_ids, const int64_t* cand_off,   /* explicit, or both NULL */
+                            int32_t n_negatives, uint64_t seed, const double* neg_cdf,   /* sampled, or 0 / ignored / NULL */
+                            int64_t* goal_off_host,     /* [n + 1], as sbr_evaluate_ranks */
+                            int32_t* ranks_host,        /* [cap] */
+                            int64_t cap,                /* must be >= goal_off[n] */
+                            int32_t* n_cand_host,       /* [n] */
+                            int32_t* negatives_host);   /* NULL, or [n][n_negatives] (sampled only) */
+/* The draw above for ONE user, restated on the host (pure host code: no device, no handle) -- the documented way to reproduce a
+ * published candidate set.  seq [L]: the user's whole uploaded sequence; out [n_negatives]: the accepted ids in draw order, -1 behind
+ * the last; *n_out: how many were accepted.  SBR_EINVAL: a NULL output, n_negatives or neg_cdf out of the bounds above. */
+int sbr_eval_negatives_host(const int32_t* seq, int32_t L, int32_t user, int32_t n_items, int32_t n_negatives, uint64_t seed,
+                            const double* neg_cdf, int32_t* out, int32_t* n_out);
+
+/* ------------------------------------------------------------------------------------------------
  * Evaluation of whole users of a cluster model on the device (added under ABI 11: one symbol and one struct, nothing existing
  * changes) -- sbr_evaluate for `--clusters C`: RNNCluster._compute_validation_metrics (rnn_cluster.py:409-438, one compiled test
  * function call per user) and test.py:61-76 (one top_k_recommendations call per user).  Users are split, fed, chunked

@@ -996,6 +996,9 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "cluster_rank_form") *value = h->last_cluster_rank_form;
     // the LAST sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates were scored, 2 they were gathered from the full scores
     else if (w == "cand_rank_form") *value = h->last_cand_rank_form;
+    // the LAST sbr_evaluate_candidates: the same two forms (0 none yet), and the width of its last chunk's compact score matrix
+    else if (w == "eval_cand_form") *value = h->last_eval_cand_form;
+    else if (w == "eval_cand_lmax") *value = h->last_eval_cand_lmax;
     // the LAST sbr_evaluate_ranks: 0 none yet, 1 the row's keys stayed in LDS, 2 every pass streamed the row; and the goal items of a pass
     else if (w == "goal_rank_form") *value = h->last_goal_rank_form;
     else if (w == "goal_rank_tile") *value = kGoalRankTile;

@@ -165,10 +165,7 @@ extern "C" int sbr_plan_rows_host(const int32_t* items, const int64_t* offsets, 
 // ---------------------------------------------------------------------------------------
 // device side
 // ---------------------------------------------------------------------------------------
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {      // splitmix64 finaliser
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
-    return x;
-}
+// (mix64, the splitmix64 finaliser every draw here hashes with, and bb_draw_item: sbr_common.h -- the host restates a draw from them)
 __device__ __forceinline__ unsigned key32(unsigned long long seed, unsigned a, unsigned b) {
     return (unsigned)(mix64(seed ^ mix64(((unsigned long long)a << 32) | b)) >> 32);
 }
@@ -265,18 +262,6 @@ __device__ __forceinline__ int bb_target_pos(unsigned long long seed, int g, int
     // uniformly random set element works for j = 0, which is all the one-target heads read)
     const unsigned long long r2 = mix64(seed ^ mix64(0x0DDull + (unsigned long long)(unsigned)g));
     return chosen[(j + (int)(r2 % (unsigned long long)k)) % k];
-}
-
-// Draw `si` of a sample set seeded by `seed`: uniform over the items, or the inverse of the CDF table.  The batch's negatives
-// (bb_pack_kernel) and the cluster head's own samples (bb_cluster_ids_kernel) follow this one law.
-__device__ __forceinline__ int bb_draw_item(unsigned long long seed, int si, const double* __restrict__ cdf, int n_items) {
-    const unsigned long long r = mix64(seed ^ mix64(0xA5A5ull + (unsigned long long)si));
-    if (!cdf) return (int)(r % (unsigned long long)n_items);      // np.random.choice(n_items, S) (rnn_sampling.py:191)
-    // bisect(cumsum, uniform(0, cumsum[-1])) (:159-163)
-    const double x = (double)(r >> 11) * (1.0 / 9007199254740992.0) * cdf[n_items - 1];
-    int lo = 0, hi = n_items;                                     // first index with cdf[idx] > x
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] > x) hi = mid; else lo = mid + 1; }
-    return min(lo, n_items - 1);
 }
 
 // One wave per local row: X row (item id, + n_items + rating index with F == 2), length, pop**db of the first target.  Blocks

@@ -244,6 +244,40 @@ static_assert(SBR_PREFIX_IS(4, 6, 3, 3, 1) && SBR_PREFIX_IS(3, 6, 3, 2, 0) && SB
 static_assert(UserPrefix(100, 140, 6, 3).place(3) == 0 && UserPrefix(100, 140, 6, 3).place(6) == 3, "results in order of p");
 #undef SBR_PREFIX_IS
 
+// The hashed draws of the batch builder (sbr_batch.hip) and of sbr_evaluate_candidates' negatives, stated for the device and the host
+// alike: what a kernel draws, sbr_eval_negatives_host restates bit for bit.
+__host__ __device__ __forceinline__ unsigned long long mix64(unsigned long long x) {      // splitmix64 finaliser
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return x;
+}
+// Draw `si` of a sample set seeded by `seed`: uniform over the items, or the inverse of the CDF table.  The batch's negatives
+// (bb_pack_kernel), the cluster head's own samples (bb_cluster_ids_kernel) and the evaluation's negatives follow this one law.
+__host__ __device__ __forceinline__ int bb_draw_item(unsigned long long seed, int si, const double* __restrict__ cdf, int n_items) {
+    const unsigned long long r = mix64(seed ^ mix64(0xA5A5ull + (unsigned long long)si));
+    if (!cdf) return (int)(r % (unsigned long long)n_items);      // np.random.choice(n_items, S) (rnn_sampling.py:191)
+    // bisect(cumsum, uniform(0, cumsum[-1])) (:159-163)
+    const double x = (double)(r >> 11) * (1.0 / 9007199254740992.0) * cdf[n_items - 1];
+    int lo = 0, hi = n_items;                                     // first index with cdf[idx] > x
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (cdf[mid] > x) hi = mid; else lo = mid + 1; }
+    return lo < n_items - 1 ? lo : n_items - 1;
+}
+// The negatives of user u in sbr_evaluate_candidates (include/sbr_rnn.h), the one statement of the rule: attempt
+// t = 0, 1, .. draws bb_draw_item(ev_neg_seed(seed, u), t, neg_cdf, N); an attempt is accepted when its item occurs nowhere in the
+// user's sequence and was not accepted before; the draw ends at n_negatives accepted or after ev_neg_attempts(n_negatives) attempts.
+__host__ __device__ __forceinline__ unsigned long long ev_neg_seed(unsigned long long seed, int user) {
+    return mix64(seed ^ mix64(0xCA4Dull + (unsigned long long)user));
+}
+__host__ __device__ constexpr int ev_neg_attempts(int n_negatives) { return 16 * n_negatives + 256; }
+static_assert(ev_neg_attempts(250) == 4256 && ev_neg_attempts(299) == 5040, "the attempt cap of the draw");
+constexpr int kEvCandSeqLds = 1024;       // ev_cand_build_kernel: longest sequence kept as a hash set in LDS (8 KB); above: searched in memory
+constexpr int kEvCandThreads = 256;       // threads of a row's workgroup in ev_cand_build_kernel = attempts of the draw decided per round
+// slots of the LDS hash set of the accepted negatives: a power of two with room for n_negatives + one round of attempts at 2/3 load
+static inline int ev_neg_hash_slots(int n_negatives) {
+    int slots = 64;
+    while (slots < (n_negatives + kEvCandThreads) * 3 / 2) slots <<= 1;
+    return slots;
+}
+
 // Every environment switch the library reads (README.md "Switches"), with its default.  sbr_read_switches (sbr_api.hip) fills one
 // per engine, inside sbr_create, and nothing reads the environment afterwards: an engine keeps the values it was created under.
 #define HEAD_WAIT_TICKS 6000ull      // 60 us of the 100 MHz clock: how long a chunk's statistics are waited for before they are recomputed
@@ -274,7 +308,7 @@ struct SbrSwitches {
     int row_aware = 1;           // SBR_ROW_AWARE_UPDATE: the dense pass over a wide index-input block skips the gradient traffic of the rows the batch did not touch
     int cluster_rank = 1;        // SBR_CLUSTER_RANK: sbr_cluster_rank scores only the members of each row's cluster (sbr_cluster_rank.hip); 0: it
                                  // gathers them from the full score matrix (also the road of the bf16 / triage projections)
-    int cand_rank = 1;           // SBR_CAND_RANK: sbr_rank_candidates scores only each row's candidates (sbr_cand_rank.hip); 0: it gathers them
+    int cand_rank = 1;           // SBR_CAND_RANK: sbr_rank_candidates / sbr_evaluate_candidates score only each row's candidates (sbr_cand_rank.hip); 0: they gather them
                                  // from the full score matrix (also the road of the bf16 / triage projections)
 };
 
@@ -396,6 +430,7 @@ struct sbr_handle {
     int last_next_rank_slots = 0;                                         // ... and the positions it projected per GEMM launch at the most
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_cand_rank_form = 0;                                          // sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates scored, 2 gathered from the full scores
+    int last_eval_cand_form = 0, last_eval_cand_lmax = 0;                 // sbr_evaluate_candidates: the same two forms (0 none yet); the width of the last chunk's compact score matrix
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
     int last_scatter_form = -1; bool last_row_aware = false;              // what the last step launched: sbr_query "scatter_form" / "row_aware_update"
     int last_join_gate = -1, last_fork_gate = -1;                         // what the last step took: sbr_query "step_join_gate" / "step_fork_gate"
@@ -918,6 +953,28 @@ hipError_t launch_ev_first_seen(hipStream_t s, const int* X, const int* lengths,
 hipError_t launch_ev_next_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* pos_off, const int* X, const int* lengths,
                                const int* first, int rows, int T, int F, int N, int p0, int slots, int min_history, int exclude_prefix,
                                const float* scores, size_t slot_stride, int* ranks, int* n_rankable, int* form);
+// sbr_eval_cand.hip: goal items ranked among a candidate set per user (include/sbr_rnn.h: sbr_evaluate_candidates)
+// What ev_cand_build_kernel reads and writes for the rows of one chunk.  The candidates of row r are either the explicit list
+// cand_ids[cand_off[r] .. cand_off[r + 1]) (strictly ascending) or, with cand_ids == nullptr, n_neg negatives drawn by the rule above.
+// cap_off [rows + 1]: where row r's merged list may lie, cap_off[r + 1] - cap_off[r] >= its candidates + its goal items (the host's bound).
+struct EvCandBuild {
+    const int* users; int rows, N;
+    const int* cand_ids; const int* cand_off;
+    int n_neg; unsigned long long seed; const double* cdf; int hash_slots;
+    int* negatives;                    // nullptr, or [rows][n_neg]: the accepted items in draw order, -1 behind the last
+    const long long* cap_off;
+    // written: the device CSR launch_cand_score / launch_crk_gather read -- moff [rows + 1] = cap_off rebased to 0, mem: per row its
+    // candidates and distinct goal items in the catalogue merged strictly ascending, mlen[r] of them, the rest of the row's capacity
+    // padded with a copy of its last id (0 for an empty row); flag per entry: 1 candidate, 0 goal item only, 2 padding; csel[r] = r
+    int* moff; int* mem; unsigned char* flag; int* mlen; int* csel;
+};
+hipError_t launch_ev_cand_build(hipStream_t s, const SbrEvalView& v, const EvCandBuild& a);
+// ranks[goal_off[r] + p]: the rankable candidates (flag 1) of row r that stand before goal item p in sbr_rank's order among the compact
+// scores cs [rows][lmax] (place j of row r: item mem[moff[r] + j]), -1 for a goal item that is never ranked; n_cand [rows]: the rankable
+// candidates.  The items exclude_mode names (SBR_EVAL_EXCL_VIEWED / _WINDOW, read from the dataset's CSR) are set to -inf in cs first.
+hipError_t launch_ev_cand_place(hipStream_t s, const SbrEvalView& v, const int* users, const long long* goal_off, int rows, int T, int N,
+                                int exclude_mode, const int* mem, const int* moff, const unsigned char* flag, const int* mlen, float* cs,
+                                int lmax, int* ranks, int* n_cand);
 // sbr_cluster_eval.hip: what sbr_cluster_evaluate needs beyond the kernels above (include/sbr_rnn.h)
 hipError_t launch_cev_transpose(hipStream_t s, const float* hard, int N, int C, float* hardT);
 // prod[r][i] = softmax(logits[r])[i] * hardT[csel[r]][i] (logits: biased, untouched by any exclusion), then with zero_fed +0.0 at the

@@ -1,6 +1,6 @@
 // The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_topk, sbr_rank, sbr_evaluate, sbr_evaluate_ranks,
-// sbr_evaluate_positions, sbr_cluster_rank, sbr_cluster_evaluate, sbr_rank_candidates, sbr_sessions_rank_candidates.
-// Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_cluster_rank.hip, sbr_cand_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
+// sbr_evaluate_positions, sbr_evaluate_candidates, sbr_cluster_rank, sbr_cluster_evaluate, sbr_rank_candidates, sbr_sessions_rank_candidates.
+// Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_eval_cand.hip, sbr_cluster_rank.hip, sbr_cand_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
 // sbr_api.hip), built from the shared pieces below: scores, ONE exclusion launch per ranking (launch_exclude: what
 // is excluded is an ExclSources, where it lands an ExclCatalogue or ExclCluster, sbr_device.h), select and sort (rank_rows).
 // Every call waits for the device once, in check_fault.
@@ -713,6 +713,171 @@ extern "C" int sbr_evaluate_positions(sbr_handle* h, sbr_dataset* d, const int32
         SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
         SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
     }
+    return check_fault(h);          // a forward that gave up must not hand out ranks; the call's one wait for the device
+}
+
+// what sbr_dataset_set_tables asks of sample_cdf
+static int neg_cdf_check(const double* cdf, int N) {
+    for (int i = 1; i < N; ++i) CHECK_ARG(cdf[i] >= cdf[i - 1], "neg_cdf must be non-decreasing (at item %d)", i);
+    CHECK_ARG(cdf[N - 1] > 0, "neg_cdf has no mass");
+    return SBR_OK;
+}
+static int neg_count_check(int n_negatives, int N) {
+    CHECK_ARG(n_negatives >= 1 && n_negatives <= std::min(N - 1, SBR_EVAL_MAX_NEGATIVES), "n_negatives=%d outside [1,min(N - 1,%d)=%d]",
+              n_negatives, SBR_EVAL_MAX_NEGATIVES, std::min(N - 1, SBR_EVAL_MAX_NEGATIVES));
+    return SBR_OK;
+}
+
+// The draw of sbr_evaluate_candidates restated on the host, one attempt after the other (the rule: ev_neg_seed, sbr_common.h):
+// pure host code, no device, no handle.
+extern "C" int sbr_eval_negatives_host(const int32_t* seq, int32_t L, int32_t user, int32_t n_items, int32_t n_negatives, uint64_t seed,
+                                       const double* neg_cdf, int32_t* out, int32_t* n_out) {
+    CHECK_ARG(out && n_out && L >= 0 && (seq || L == 0), "null argument");
+    CHECK_ARG(n_items >= 2 && user >= 0, "n_items=%d, user=%d: at least two items, a user id >= 0", n_items, user);
+    int rc;
+    if ((rc = neg_count_check(n_negatives, n_items)) != SBR_OK) return rc;
+    if (neg_cdf && (rc = neg_cdf_check(neg_cdf, n_items)) != SBR_OK) return rc;
+    std::vector<int> sorted(seq, seq + L);
+    std::sort(sorted.begin(), sorted.end());
+    std::vector<char> taken((size_t)n_items, 0);
+    const unsigned long long su = ev_neg_seed(seed, user);
+    int na = 0;
+    for (int t = 0; t < ev_neg_attempts(n_negatives) && na < n_negatives; ++t) {
+        const int it = bb_draw_item(su, t, neg_cdf, n_items);
+        if (taken[it] || std::binary_search(sorted.begin(), sorted.end(), it)) continue;
+        taken[it] = 1;
+        out[na++] = it;
+    }
+    for (int i = na; i < n_negatives; ++i) out[i] = -1;
+    *n_out = na;
+    return SBR_OK;
+}
+
+// Every goal item ranked among the candidate set of its user (include/sbr_rnn.h: sbr_evaluate_candidates; kernels: sbr_eval_cand.hip;
+// DESIGN.md 3q): sbr_evaluate_ranks' chunks -- pack, forward, keep-and-restore of lazily stepped rows -- with, per chunk, the build of
+// the merged lists (ev_cand_build_kernel), sbr_rank_candidates' scoring of them (launch_cand_score, or the full projection and
+// launch_crk_gather) and one counting kernel over the compact rows (ev_cand_place_kernel).  Where a row's merged list lies follows
+// from the lengths alone -- its candidates (or n_negatives) plus its goal places, an upper bound that the kernel pads --, so the offsets
+// and the width of every chunk's compact matrix are host values: nothing waits for the device before the end of the call.
+extern "C" int sbr_evaluate_candidates(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int exclude_mode,
+                                       const int32_t* cand_ids, const int64_t* cand_off, int32_t n_negatives, uint64_t seed,
+                                       const double* neg_cdf, int64_t* goal_off_host, int32_t* ranks_host, int64_t cap, int32_t* n_cand_host,
+                                       int32_t* negatives_host) {
+    CHECK_ARG(h && d && users && goal_off_host && ranks_host && n_cand_host, "null argument");
+    if (h->st.step_open || h->st.train_fwd_open) {
+        sbr_set_error("sbr_evaluate_candidates: a training step is open (finish it with sbr_apply_update)");
+        return SBR_ESTATE;
+    }
+    CHECK_ARG(exclude_mode != SBR_EVAL_EXCL_WINDOW_ZERO, "sbr_evaluate_candidates: SBR_EVAL_EXCL_WINDOW_ZERO scores the items fed 0.0 in the "
+              "whole-catalogue matrix; the compact candidate scores have no such mode (take SBR_EVAL_EXCL_WINDOW or sbr_evaluate_ranks)");
+    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW, "unknown exclusion mode %d", exclude_mode);
+    const bool expl = cand_ids || cand_off;
+    CHECK_ARG(!(expl && n_negatives != 0), "explicit lists (cand_ids / cand_off) and n_negatives=%d: exactly one candidate source", n_negatives);
+    CHECK_ARG(expl || n_negatives != 0, "no candidate source: neither cand_ids / cand_off nor n_negatives");
+    CHECK_ARG(!expl || !neg_cdf, "neg_cdf belongs to the sampled negatives, not to explicit lists");
+    CHECK_ARG(!expl || !negatives_host, "negatives_host belongs to the sampled negatives: explicit lists are the caller's");
+    const Layout& y = h->lay;
+    SbrEvalView v;
+    int rc;
+    if ((rc = eval_check_args(h, d, users, n, 1, v)) != SBR_OK) return rc;      // (no k here: 1 is inside every catalogue)
+    const int B = y.B, N = y.N;
+    CandLists c;
+    if (expl) {
+        if ((rc = cand_check(cand_ids, cand_off, n, B, 0, N, c)) != SBR_OK) return rc;
+    } else {
+        if ((rc = neg_count_check(n_negatives, N)) != SBR_OK) return rc;
+        if (neg_cdf && (rc = neg_cdf_check(neg_cdf, N)) != SBR_OK) return rc;
+    }
+    auto goal_len = [&](int64_t j) -> int64_t { return UserSplit(v.h_off[users[j]], v.h_off[users[j] + 1], y.T).goal_len(); };
+    // where the merged lists lie: row j holds at most its candidates and one entry per goal place
+    std::vector<long long> cap_off((size_t)n + 1, 0);
+    int64_t total = 0, chunk_cap = 0;
+    int lmax_all = 4;
+    for (int64_t c0 = 0; c0 < n; c0 += B) {
+        int64_t widest = 0;
+        for (int64_t j = c0; j < std::min<int64_t>(n, c0 + B); ++j) {
+            const int64_t w = (expl ? cand_off[j + 1] - cand_off[j] : (int64_t)n_negatives) + goal_len(j);
+            cap_off[j + 1] = cap_off[j] + w;
+            widest = std::max(widest, w);
+            total += goal_len(j);
+        }
+        const int64_t in_chunk = cap_off[std::min<int64_t>(n, c0 + B)] - cap_off[c0];
+        CHECK_ARG(in_chunk <= 0x7fffffff && widest <= 0x7ffffff0, "the lists and goals of the %d users from users[%lld] hold %lld ids, at most 2^31 - 1 per chunk",
+                  B, (long long)c0, (long long)in_chunk);
+        chunk_cap = std::max(chunk_cap, in_chunk);
+        lmax_all = std::max(lmax_all, (int)((widest + 3) / 4 * 4));
+    }
+    CHECK_ARG(cap >= total, "cap=%lld: the goals of these users hold %lld items", (long long)cap, (long long)total);
+    goal_off_host[0] = 0;
+    for (int64_t j = 0; j < n; ++j) goal_off_host[j + 1] = goal_off_host[j] + goal_len(j);
+    Carver cv;
+    const size_t o_users = cv.take((size_t)n * sizeof(int)), o_goff = cv.take((size_t)(n + 1) * sizeof(long long));
+    const size_t o_coff = cv.take((size_t)(n + 1) * sizeof(long long));
+    const size_t o_ranks = cv.take((size_t)total * sizeof(int)), o_ncand = cv.take((size_t)n * sizeof(int));
+    const size_t o_neg = cv.take(negatives_host ? (size_t)n * n_negatives * sizeof(int) : 0);
+    const size_t o_cdf = cv.take(neg_cdf ? (size_t)N * sizeof(double) : 0);
+    if (expl) cand_carve(cv, c);
+    const size_t o_moff = cv.take((size_t)(B + 1) * sizeof(int)), o_csel = cv.take((size_t)B * sizeof(int)), o_mlen = cv.take((size_t)B * sizeof(int));
+    const size_t o_mem = cv.take((size_t)chunk_cap * sizeof(int)), o_flag = cv.take((size_t)chunk_cap);
+    const size_t o_cs = cv.take((size_t)B * lmax_all * sizeof(float));
+    LazyKeep kept;      // training goes on as if the call had not been made
+    kept.carve(cv, h);
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    const long long* dgoff = (const long long*)(S + o_goff);
+    const long long* dcoff = (const long long*)(S + o_coff);
+    // (pageable host memory: the copies have left the host arrays when they return)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    SBR_HIP(hipMemcpyAsync(S + o_goff, goal_off_host, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    SBR_HIP(hipMemcpyAsync(S + o_coff, cap_off.data(), (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    if (neg_cdf) SBR_HIP(hipMemcpyAsync(S + o_cdf, neg_cdf, (size_t)N * sizeof(double), hipMemcpyHostToDevice, s));
+    if (expl && (rc = cand_upload(h, S, c)) != SBR_OK) return rc;      // once per call, as sbr_rank_candidates uploads them
+    { const int rck = kept.save(h, S); if (rck != SBR_OK) return rck; }
+    const bool restricted = cand_rank_restricted(h);
+    int* mem = (int*)(S + o_mem);
+    int* moff = (int*)(S + o_moff);
+    int* csel = (int*)(S + o_csel);
+    int* mlen = (int*)(S + o_mlen);
+    unsigned char* flag = (unsigned char*)(S + o_flag);
+    float* cs = (float*)(S + o_cs);
+    auto chunks = [&]() -> int {
+        for (int64_t c0 = 0; c0 < n; c0 += B) {
+            const int rows = (int)std::min<int64_t>(B, n - c0);
+            int rc2;
+            if ((rc2 = eval_pack_chunk(h, v, dusers + c0, rows)) != SBR_OK) return rc2;
+            // restricted: the candidates are scored from the hidden state; otherwise the very floats sbr_rank ranks, gathered
+            if ((rc2 = restricted ? forward_current(h) : full_scores(h, 0)) != SBR_OK) return rc2;
+            long long widest = 0;
+            for (int64_t j = c0; j < c0 + rows; ++j) widest = std::max(widest, cap_off[j + 1] - cap_off[j]);
+            const int lmax = (int)std::max<long long>(4, (widest + 3) / 4 * 4);      // (rounded up to 4 as the cluster road's)
+            EvCandBuild a;
+            a.users = dusers + c0; a.rows = rows; a.N = N;
+            a.cand_ids = expl ? c.dev_ids(S) : nullptr; a.cand_off = expl ? c.dev_off(S) + c0 : nullptr;
+            a.n_neg = expl ? 0 : n_negatives; a.seed = seed; a.cdf = neg_cdf ? (const double*)(S + o_cdf) : nullptr;
+            a.hash_slots = expl ? 0 : ev_neg_hash_slots(n_negatives);
+            a.negatives = negatives_host ? (int*)(S + o_neg) + (size_t)c0 * n_negatives : nullptr;
+            a.cap_off = dcoff + c0;
+            a.moff = moff; a.mem = mem; a.flag = flag; a.mlen = mlen; a.csel = csel;
+            SBR_LAUNCH(launch_ev_cand_build(s, v, a));
+            if (restricted)
+                SBR_LAUNCH(launch_cand_score(s, h_last(h), y.HLt, h->P(y.p_WoutT), h->P(y.p_bout), y.HLt, mem, moff, rows, lmax, cs));
+            else
+                SBR_LAUNCH(launch_crk_gather(s, h->A(y.a_logits), N, csel, mem, moff, rows, lmax, cs));
+            h->last_eval_cand_form = restricted ? 1 : 2;
+            h->last_eval_cand_lmax = lmax;
+            SBR_LAUNCH(launch_ev_cand_place(s, v, dusers + c0, dgoff + c0, rows, y.T, N, exclude_mode, mem, moff, flag, mlen, cs, lmax,
+                                            (int*)(S + o_ranks), (int*)(S + o_ncand) + c0));
+        }
+        return SBR_OK;
+    };
+    rc = chunks();
+    { const int rck = kept.restore(h, S); if (rck != SBR_OK) return rck; }      // (also behind a chunk that failed: the call leaves the bits it found)
+    if (rc != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+    SBR_HIP(hipMemcpyAsync(n_cand_host, S + o_ncand, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (negatives_host) SBR_HIP(hipMemcpyAsync(negatives_host, S + o_neg, (size_t)n * n_negatives * sizeof(int), hipMemcpyDeviceToHost, s));
     return check_fault(h);          // a forward that gave up must not hand out ranks; the call's one wait for the device
 }
 

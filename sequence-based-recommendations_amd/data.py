@@ -668,3 +668,82 @@ class PositionEvaluator(object):
         return {"count": np.bincount(hist, minlength=size).astype(np.int64),
                 "hits": np.bincount(hist[(rank >= 0) & (rank < int(k))], minlength=size).astype(np.int64),
                 "rr": np.bincount(hist, weights=self._rr(rank), minlength=size).astype(np.float64)}
+
+
+class CandidateEvaluator(object):
+    """Metrics over the place of every goal item among a candidate set of its user (RNNEngine.evaluate_candidates, include/sbr_rnn.h:
+    sbr_evaluate_candidates) -- the sampled protocol: each positive against n_negatives items the user never interacted with.  A
+    rank counts the candidates in front of the goal item, so one add_ranks answers every depth.  Per user the FIRST goal item is
+    "the" positive of sps, ndcg and mrr (one relevant item: the ideal DCG is 1); recall looks at all of the user's distinct goal
+    items.  An unrankable goal item (rank -1) is a miss everywhere.  The metrics table binds the depth-dependent ones at this
+    evaluator's own k; at(k) gives all four at any depth."""
+
+    def __init__(self, n_negatives=None, k=10):
+        self.n_negatives, self.k = n_negatives, int(k)
+        self._rk, self._items, self._glen, self._ncand = [], [], [], []
+        self.metrics = {"sampled_sps": lambda: self.sps(self.k), "sampled_ndcg": lambda: self.ndcg(self.k),
+                        "sampled_recall": lambda: self.recall(self.k), "sampled_mrr": self.mrr}
+
+    def add_ranks(self, rec, goal_items):
+        """rec: what RNNEngine.evaluate_candidates returned; goal_items: per user of rec, in order, the goal ids in sequence order
+        (the DeviceDataset's host copy: items[off + L // 2 : off + L])."""
+        off = np.asarray(rec["goal_off"], dtype=np.int64)
+        glen = off[1:] - off[:-1]
+        flat = np.concatenate([np.asarray(g, dtype=np.int64).reshape(-1) for g in goal_items]) if len(goal_items) else np.zeros(0, np.int64)
+        if len(goal_items) != len(glen) or [len(g) for g in goal_items] != glen.tolist() or len(rec["ranks"]) != len(flat) \
+                or len(rec["n_cand"]) != len(glen) or np.any(glen < 1):
+            raise ValueError("goal_items must hold the goal of every user of rec, as long as its ranks")
+        self._rk.append(np.asarray(rec["ranks"], dtype=np.int64)); self._items.append(flat)
+        self._glen.append(glen); self._ncand.append(np.asarray(rec["n_cand"], dtype=np.int64))
+
+    def _flat(self):
+        cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int64)
+        glen = cat(self._glen)
+        return cat(self._rk), cat(self._items), glen, np.concatenate([[0], np.cumsum(glen)]).astype(np.int64)
+
+    def n_users(self):
+        return int(sum(len(g) for g in self._glen))
+
+    def n_unrankable(self):
+        """goal places whose item is never ranked (rank -1: excluded, NaN or -inf score)"""
+        return int(sum(int(np.count_nonzero(r < 0)) for r in self._rk))
+
+    def n_short(self):
+        """users with fewer than n_negatives rankable candidates: the draw ended at its attempt cap before n_negatives eligible
+        items had come up (or a candidate scored NaN / -inf)"""
+        if self.n_negatives is None:
+            raise RuntimeError("n_short() needs the n_negatives this evaluator was made for")
+        return int(sum(int(np.count_nonzero(c < int(self.n_negatives))) for c in self._ncand))
+
+    def _head(self):
+        rank, _, _, off = self._flat()
+        return rank[off[:-1]]
+
+    def sps(self, k):
+        """the share of users whose first goal item has fewer than k candidates in front of it (HR@k of the sampled protocol)"""
+        head = self._head()
+        return int(np.count_nonzero((head >= 0) & (head < int(k)))) / len(head)
+
+    def ndcg(self, k):
+        head = self._head()
+        gain = np.where((head >= 0) & (head < int(k)), 1.0 / np.log2(2.0 + np.maximum(head, 0)), 0.0)
+        return float(gain.sum()) / len(head)
+
+    def recall(self, k):
+        """per user the share of its distinct goal items with a rank in [0, k), then the mean over the users"""
+        rank, items, glen, _ = self._flat()
+        n = len(glen)
+        user = np.repeat(np.arange(n, dtype=np.int64), glen)
+        first_place = np.zeros(len(rank), dtype=bool)      # one place per distinct (user, item): a repeated item holds one rank
+        first_place[np.unique(user * (int(items.max()) + 1 if len(items) else 1) + items, return_index=True)[1]] = True
+        distinct = np.bincount(user[first_place], minlength=n)
+        hit = np.bincount(user[first_place & (rank >= 0) & (rank < int(k))], minlength=n)
+        return float((hit / distinct).sum()) / n
+
+    def mrr(self):
+        head = self._head()
+        return float(np.where(head >= 0, 1.0 / (1.0 + np.maximum(head, 0)), 0.0).sum()) / len(head)
+
+    def at(self, k):
+        """{"sampled_sps", "sampled_ndcg", "sampled_recall", "sampled_mrr"} at depth k"""
+        return {"sampled_sps": self.sps(k), "sampled_ndcg": self.ndcg(k), "sampled_recall": self.recall(k), "sampled_mrr": self.mrr()}

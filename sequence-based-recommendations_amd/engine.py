@@ -89,7 +89,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_dataset_create", "sbr_dataset_destroy", "sbr_dataset_set_tables", "sbr_dataset_set_options", "sbr_dataset_noise_pass", "sbr_dataset_current_sequences", "sbr_dataset_set_target_bias",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
            "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks",
-           "sbr_evaluate_positions",
+           "sbr_evaluate_positions", "sbr_evaluate_candidates", "sbr_eval_negatives_host",
            "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
            "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load",
            "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_reset", "sbr_sessions_advance", "sbr_sessions_adopt",
@@ -191,6 +191,9 @@ def load_library(path=None):
     lib.sbr_evaluate.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
     lib.sbr_evaluate_ranks.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, vp]
     lib.sbr_evaluate_positions.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int64]
+    lib.sbr_evaluate_candidates.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int32, ctypes.c_uint64, vp, vp, vp,
+                                            ctypes.c_int64, vp, vp]
+    lib.sbr_eval_negatives_host.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, vp, vp, vp]
     lib.sbr_cluster_evaluate.argtypes = [vp, vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(SbrEvalOut),
                                          ctypes.POINTER(SbrEvalOut), vp, vp, vp]
     szp = ctypes.POINTER(ctypes.c_size_t)
@@ -227,6 +230,38 @@ def position_counts(lengths, max_length, min_history=1):
     lengths = np.asarray(lengths, dtype=np.int64)
     fed = np.minimum(np.maximum(lengths - 1, 0), int(max_length))
     return np.maximum(0, fed - int(min_history) + 1)
+
+
+EVAL_MAX_NEGATIVES = 4096    # SBR_EVAL_MAX_NEGATIVES (include/sbr_rnn.h)
+
+
+def _neg_cdf_arg(neg_cdf, n_items):
+    """evaluate_candidates' / sampled_negatives' neg_cdf in the C-ABI's type: float64 (n_items,), or None"""
+    if neg_cdf is None:
+        return None
+    neg_cdf = np.ascontiguousarray(np.asarray(neg_cdf, dtype=np.float64).reshape(-1))
+    if neg_cdf.shape != (n_items,):
+        raise ValueError("neg_cdf must have n_items=%d entries, got %r" % (n_items, neg_cdf.shape))
+    return neg_cdf
+
+
+def sampled_negatives(seq, user, n_items, n_negatives, seed, neg_cdf=None):
+    """The negatives RNNEngine.evaluate_candidates(n_negatives=, seed=, neg_cdf=) draws for dataset user `user` whose whole uploaded
+    sequence is `seq` (sbr_eval_negatives_host: pure host code, no device) -- the documented way to reproduce a published candidate
+    set.  Returns the accepted ids in draw order, int32; fewer than n_negatives when the attempt cap of 16 * n_negatives + 256 ends
+    the draw first."""
+    lib = load_library()
+    seq = np.ascontiguousarray(np.asarray(seq, dtype=np.int32).reshape(-1))
+    n_negatives = int(n_negatives)
+    if not 1 <= n_negatives <= min(int(n_items) - 1, EVAL_MAX_NEGATIVES):     # (the library checks it too: here before `out` is sized by it)
+        raise ValueError("n_negatives=%d outside [1,min(N - 1,%d)]" % (n_negatives, EVAL_MAX_NEGATIVES))
+    neg_cdf = _neg_cdf_arg(neg_cdf, int(n_items))
+    out, n_out = np.empty(n_negatives, dtype=np.int32), ctypes.c_int32()
+    rc = lib.sbr_eval_negatives_host(_ptr(seq) if len(seq) else None, len(seq), int(user), int(n_items), n_negatives,
+                                     int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(neg_cdf), _ptr(out), ctypes.byref(n_out))
+    if rc != 0:
+        raise SbrError(lib.sbr_last_error().decode())
+    return out[:n_out.value].copy()
 
 
 def _check_k(k, n_items):
@@ -963,6 +998,51 @@ class RNNEngine(object):
         with self.torch.cuda.device(self.device):
             self._check(self.lib.sbr_evaluate_positions(self.h, dataset.d, _ptr(users) if n else None, n, m, int(exclude_mode),
                                                         _ptr(out["pos_off"]), _ptr(out["ranks"]), _ptr(out["n_rankable"]), cap))
+        return out
+
+    def evaluate_candidates(self, dataset, users, exclude_mode, candidates=None, n_negatives=None, seed=0, neg_cdf=None,
+                            want_negatives=False):
+        """Every goal item ranked among a candidate set of its user (sbr_evaluate_candidates) -- the sampled protocol of the
+        sequential-recommendation papers, without scoring the whole catalogue.  Users are split, fed and excluded as by
+        evaluate_ranks() (exclude_mode: EVAL_EXCL_NONE, _VIEWED or _WINDOW).  Exactly one source of candidates: `candidates`, one
+        id list per user (any order, duplicates allowed: each is sorted and de-duplicated; None or empty: no candidates), or
+        `n_negatives` items per user that occur nowhere in its sequence, drawn on the device from (seed, user id) -- uniformly, or
+        by the cumulative weights neg_cdf (float64 (n_items,)); sampled_negatives() restates the draw on the host.  Returns a
+        dict: "goal_off" (int64 (n + 1,)) and "ranks" (int32 (goal_off[-1],): the rankable candidates in front of the goal item,
+        -1 when it is not rankable itself) as evaluate_ranks() lays them out, "n_cand" (int32 (n,): the rankable candidates) and,
+        with want_negatives, "negatives" (int32 (n, n_negatives): the ids in draw order, -1 behind the last)."""
+        self._rank_local_flush("evaluate_candidates")
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        n = len(users)
+        if (candidates is None) == (n_negatives is None):
+            raise ValueError("evaluate_candidates takes exactly one of candidates= and n_negatives=")
+        cand_ids = cand_off = negatives = None
+        if candidates is not None:
+            if want_negatives or neg_cdf is not None:
+                raise ValueError("want_negatives and neg_cdf belong to n_negatives=, not to candidates=")
+            lists = list(candidates)
+            if len(lists) != n:
+                raise ValueError("candidates must hold one id list per user: %d lists for %d users" % (len(lists), n))
+            cand_ids, cand_off, _ = _cand_csr(lists, n) if n else (np.zeros(1, np.int32), np.zeros(1, np.int64), False)
+            s = 0
+        else:
+            s = int(n_negatives)
+            if not 1 <= s <= min(self.n_items - 1, EVAL_MAX_NEGATIVES):       # (the library checks it too: here before `negatives` is sized by it)
+                raise ValueError("n_negatives=%d outside [1,min(N - 1,%d)]" % (s, EVAL_MAX_NEGATIVES))
+            neg_cdf = _neg_cdf_arg(neg_cdf, self.n_items)
+            negatives = np.empty((n, s), dtype=np.int32) if want_negatives else None
+        off, cap = np.asarray(dataset.offsets, dtype=np.int64), 0      # the dataset's host offsets size the result
+        if n and users.min() >= 0 and users.max() < len(off) - 1:      # (otherwise the library rejects the users: nothing is written)
+            lens = off[1:][users] - off[:-1][users]
+            cap = int((lens - lens // 2).sum())
+        out = {"ranks": np.empty(cap, dtype=np.int32), "goal_off": np.zeros(n + 1, dtype=np.int64), "n_cand": np.empty(n, dtype=np.int32)}
+        self.evaluate_calls += 1
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.sbr_evaluate_candidates(self.h, dataset.d, _ptr(users) if n else None, n, int(exclude_mode), _ptr(cand_ids),
+                                                         _ptr(cand_off), s, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(neg_cdf),
+                                                         _ptr(out["goal_off"]), _ptr(out["ranks"]), cap, _ptr(out["n_cand"]), _ptr(negatives)))
+        if want_negatives:
+            out["negatives"] = negatives
         return out
 
     def sessions(self, capacity, history=0):

@@ -583,6 +583,25 @@ class RNNBase(object):
             return None
         return self._whole_catalogue_position_evaluator(dataset, which, mode, min_history)
 
+    def native_candidate_evaluator(self, dataset, which, mode, n_negatives, seed=0, bias=None, k=10):
+        """Every goal item of dataset's "validation" / "test" set ranked among n_negatives items its user never interacted with,
+        drawn on the device from (seed, user id), from ONE engine call (RNNEngine.evaluate_candidates), as a
+        data.CandidateEvaluator: sampled_sps / sampled_ndcg / sampled_recall at any depth, sampled_mrr.  bias: None draws
+        uniformly, otherwise with the cumulative sum of the training popularity ** bias as neg_cdf.  mode: engine.EVAL_EXCL_NONE,
+        _VIEWED or _WINDOW.  None where there is no native road (_native_eval_users names the cases) -- nothing else serves this."""
+        from .data import CandidateEvaluator
+        if not self.native_eval:
+            return None
+        found = self._native_eval_users(dataset, which, method="evaluate_candidates")
+        if found is None:
+            return None
+        ds, users, lens = found
+        neg_cdf = None if bias is None else np.cumsum(np.power(np.asarray(dataset.item_popularity, dtype=np.float64), float(bias)))
+        rec = self.engine.evaluate_candidates(ds, users, mode, n_negatives=n_negatives, seed=seed, neg_cdf=neg_cdf)
+        ev = CandidateEvaluator(n_negatives, k=k)
+        ev.add_ranks(rec, [ds.items[ds.offsets[u] + lens[u] // 2:ds.offsets[u + 1]] for u in users.tolist()])
+        return ev
+
     def _compute_validation_metrics(self, metrics):
         from .data import Evaluator
         from .engine import EVAL_EXCL_NONE, EVAL_EXCL_WINDOW, EVAL_EXCL_WINDOW_ZERO
@@ -1243,6 +1262,11 @@ class RNNCluster(RNNBase):
         if self.predict_with_clusters or self.recurrent_layer.bidirectional:
             return None
         return self._whole_catalogue_position_evaluator(dataset, which, mode, min_history)
+
+    def native_candidate_evaluator(self, dataset, which, mode, n_negatives, seed=0, bias=None, k=10):
+        """None: a cluster model's ranking is restricted already -- to the user's cluster --, and sampled negatives from the whole
+        catalogue are not what it competes with."""
+        return None
 
     def session_pool(self, capacity, history=None):
         """A cluster model ranks inside each user's cluster, from the user representation of the engine's current batch

@@ -187,6 +187,41 @@ def run_position_tests(predictor, model_file, dataset, args, k=10, file=None, n_
     return ev
 
 
+def run_sampled_tests(predictor, model_file, dataset, args, k=10, file=None, n_batches=None):
+    """--sampled_negatives S (no counterpart in the reference): the protocol of the sequential-recommendation papers -- every goal item
+    of every test user ranked among S items the user never interacted with, drawn on the device from (--negatives_seed, user id),
+    uniformly or by training popularity ** --negatives_bias, from one engine call (RNNBase.native_candidate_evaluator,
+    sbr_evaluate_candidates); with unique interactions the viewed items are not ranked.  Prints sampled_sps@k, sampled_ndcg@k,
+    sampled_recall@k and sampled_mrr, and appends to `file`_sampled one line: n_batches, S, seed, bias, k, the four values, users,
+    users whose draw ended short.  There is no per-user road to fall back to: where the engine call cannot serve the model or the
+    set, the run stops with the reason."""
+    from .engine import EVAL_EXCL_NONE, EVAL_EXCL_VIEWED
+    if not hasattr(predictor, "native_candidate_evaluator"):
+        raise SystemExit("--sampled_negatives: %s has no native evaluation among sampled negatives" % type(predictor).__name__)
+    predictor.load(model_file)
+    n_negatives, seed, bias = int(args.sampled_negatives), int(getattr(args, "negatives_seed", 0)), getattr(args, "negatives_bias", None)
+    start = time.perf_counter()
+    ev = predictor.native_candidate_evaluator(dataset, "test", EVAL_EXCL_VIEWED if predictor.interactions_are_unique else EVAL_EXCL_NONE,
+                                              n_negatives, seed, bias)
+    if ev is None:
+        raise SystemExit("--sampled_negatives needs the engine's native evaluation of this model and test set, and there is no other "
+                         "road: not with SBR_NATIVE_EVAL=0, a data-parallel run, a shuffled test set or a cluster model (its ranking "
+                         "is restricted to the user's cluster already)")
+    print("Timer (sampled negatives): ", time.perf_counter() - start)
+    values = ev.at(k)
+    names = ("sampled_sps", "sampled_ndcg", "sampled_recall", "sampled_mrr")
+    for name in names:
+        print(name + ("" if name == "sampled_mrr" else "@" + str(k)) + ": ", values[name])
+    print("users: ", ev.n_users(), " short of", n_negatives, "negatives: ", ev.n_short(), " unrankable goal items: ", ev.n_unrankable())
+    if file is not None:
+        if not os.path.exists(os.path.dirname(file)):
+            os.makedirs(os.path.dirname(file))
+        with open(file + "_sampled", "a") as f:
+            f.write("\t".join(map(str, [n_batches, n_negatives, seed, bias, k] + [values[name] for name in names]
+                                  + [ev.n_users(), ev.n_short()])) + "\n")
+    return ev
+
+
 def print_results(ev, metrics, file=None, n_batches=None, print_full_rank_comparison=False):   # test.py:79-103
     for m in metrics:
         if m not in ev.metrics:
@@ -234,6 +269,13 @@ def test_command_parser(parser):                                      # test.py:
     parser.add_argument("--by_position", help="Also rank the next item at every position of every test sequence (seq_sps, seq_mrr, seq_ndcg; "
                         "with --save, <results file>_by_position holds one line per history length).", action="store_true")
     parser.add_argument("--min_history", help="With --by_position: the shortest history a position is evaluated at.", default=1, type=int)
+    parser.add_argument("--sampled_negatives", help="Also rank every goal item among this many sampled items the user never interacted with "
+                        "(sampled_sps, sampled_ndcg, sampled_recall, sampled_mrr; with --save, <results file>_sampled holds one line per "
+                        "checkpoint).", default=0, type=int)
+    parser.add_argument("--negatives_seed", help="With --sampled_negatives: the seed of the draw (the negatives of a user follow from it and "
+                        "the user's id).", default=0, type=int)
+    parser.add_argument("--negatives_bias", help="With --sampled_negatives: draw item i with weight training popularity ** bias "
+                        "(default: uniformly).", default=None, type=float)
 
 
 def main(argv=None):                                                  # test.py:132-160
@@ -261,12 +303,16 @@ def main(argv=None):                                                  # test.py:
                 results.append((files[j], {m: ev.metrics[m]() for m in metrics}))
                 if getattr(args, "by_position", False):
                     run_position_tests(predictor, files[j], dataset, args, k=args.nb_of_predictions, file=output_file, n_batches=batches[j])
+                if getattr(args, "sampled_negatives", 0):
+                    run_sampled_tests(predictor, files[j], dataset, args, k=args.nb_of_predictions, file=output_file, n_batches=batches[j])
     else:
         ev = run_tests(predictor, files, dataset, args, get_full_recommendation_list=args.save_rank, k=args.nb_of_predictions)
         print_results(ev, metrics, file=save_file_name(predictor, dataset, args), print_full_rank_comparison=args.save_rank)
         results.append((files, {m: ev.metrics[m]() for m in metrics}))
         if getattr(args, "by_position", False):
             run_position_tests(predictor, files, dataset, args, k=args.nb_of_predictions, file=save_file_name(predictor, dataset, args))
+        if getattr(args, "sampled_negatives", 0):
+            run_sampled_tests(predictor, files, dataset, args, k=args.nb_of_predictions, file=save_file_name(predictor, dataset, args))
     return results
 
 
