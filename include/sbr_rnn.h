@@ -739,7 +739,7 @@ int sbr_dataset_state_save(sbr_dataset* d, void* blob_host, size_t cap, size_t* 
 int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
 
 /* ------------------------------------------------------------------------------------------------
- * Stateful sessions (added under ABI 11: eight symbols and three constants, no struct change) -- serving at the model's natural
+ * Stateful sessions (added under ABI 11: symbols and three constants, no struct change) -- serving at the model's natural
  * cost.  Every ranking call above feeds a whole window of up to max_length items per row (rnn_base.py:140-165 does so per request); a
  * session pool KEEPS the recurrent state of `capacity` users, so that a user's next event costs one recurrent step and one projection.
  * A second object beside the engine, like the cluster head: its memory is its own device allocation (never part of the arena --
@@ -751,9 +751,9 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  * session carries its state over any number of events, which equals the windowed model of the other calls only while the events fit
  * max_length.
  *
- * Everything runs on the engine's stream.  reset / advance / adopt enqueue and return without waiting for the device; rank waits
+ * Everything runs on the engine's stream.  reset / advance / replay / adopt enqueue and return without waiting for the device; rank waits
  * once, at its end, like sbr_rank; read and write wait.  A call that reads parameters brings lazily stepped rows up to date first
- * (see "Row-sparse blocks": advance the index-input block, rank and adopt the output rows), which moves float32 roundings of a
+ * (see "Row-sparse blocks": advance and replay the index-input block, rank and adopt the output rows), which moves float32 roundings of a
  * training run as sbr_rank does and is otherwise invisible to it; sessions keep states, not weights: after a training step they go on
  * under the new weights.  Inside an open training step (between sbr_zero_grads and sbr_apply_update) or with a lagged cost pending,
  * every call but read returns SBR_ESTATE.  The current batch, its forward pass and the batch buffers stay as they were (adopt runs the
@@ -768,6 +768,20 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  *            row-gathered GEMM on v_mfma_f32_16x16x4_f32 plus the cell) and one commit launch that counts the event and appends
  *            items[r] to the ring.  An output element is one accumulation chain whose order does not depend on the rows that share
  *            the call: a session fed alone and the same session fed among thousands hold the same bits.
+ *   replay   a run of events per named slot, applied in order FROM THE SLOT'S KEPT STATE, in one launch: off is a CSR over the n rows
+ *            (n + 1 non-decreasing offsets, off[0] == 0), row r feeds items[off[r] .. off[r + 1]) (and second[..], as advance takes
+ *            it) to slot slots[r], oldest first.  Exactly advance called once per event: afterwards the slot has events + len events,
+ *            its state in every layer (padded units included) holds the very bits len advance calls would have left, its ring the
+ *            last min(events + len, history) ids at the places those events have; a row with len == 0 leaves its slot untouched.  No
+ *            limit on a row's length, none on n beyond capacity.  ses_replay_kernel (sbr_session.hip) owns a 16-row tile and every
+ *            unit tile of every layer per workgroup, with the time loop and the layer loop inside and the step's own tile arithmetic
+ *            (one __device__ function serves both kernels); the rows of a call are tiled longest first, a row whose list has ended is
+ *            frozen; the states are exchanged through the slot's own two planes, and the same launch counts the events and writes the
+ *            rings: sbr_query "session_replay_launches" (the launches the most recent replay on this engine enqueued) is 1.  The
+ *            device buffer of a call's events belongs to the pool, grows when a call needs more and is kept (SBR_ENOMEM before
+ *            anything is launched); a call that grows it frees the old one first, and hipFree WAITS for the device -- only such a
+ *            call (the first one, and one with more events than any before) does not return at once.  THIS, not adopt, is the road for histories longer than max_length and for continuing a kept
+ *            state (a returning user's new events, a pool rebuilt from a log, a slot restored with write and caught up).
  *   adopt    the prefill: rows 0 .. n_rows - 1 of the engine's current batch become the sessions slots[0 .. n_rows): the forward
  *            pass runs on the chain kernels (if the batch has none yet), then ONE launch copies each row's state at the row's length
  *            (of every layer), its length as the event count and its last `history` fed ids.  No batch set: SBR_ESTATE.
@@ -786,8 +800,8 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  *   write    puts h_host (and c_host, LSTM) back as slot's state in `layer`; events and ring stay.  read / write are the hooks for
  *            evicting and restoring sessions.
  * SBR_EINVAL, found on the host before anything is launched, the pool untouched, the offender named: a slot outside [0, capacity), a
- * slot named twice in one advance / adopt / reset, an id outside [0, input_size), `second` missing with n_feat == 2 or given with
- * n_feat == 1, n above capacity (advance) or n_rows above the batch's rows (adopt), k, exclude_mode or lists as sbr_rank rejects them,
+ * slot named twice in one advance / replay / adopt / reset, an id outside [0, input_size), `second` missing with n_feat == 2 or given
+ * with n_feat == 1, n above capacity (advance, replay) or n_rows above the batch's rows (adopt), off not starting at 0 or decreasing, k, exclude_mode or lists as sbr_rank rejects them,
  * candidate lists as sbr_rank_candidates rejects them. */
 typedef struct sbr_sessions sbr_sessions;
 #define SBR_SESSION_EXCL_NONE    0
@@ -797,6 +811,8 @@ int  sbr_sessions_create(sbr_handle* h, int64_t capacity, int32_t history, sbr_s
 void sbr_sessions_destroy(sbr_sessions* s);            /* before sbr_destroy(h) */
 int  sbr_sessions_reset(sbr_sessions* s, const int32_t* slots, int64_t n);
 int  sbr_sessions_advance(sbr_sessions* s, const int32_t* slots, const int32_t* items, const int32_t* second, int64_t n);
+int  sbr_sessions_replay(sbr_sessions* s, const int32_t* slots, int64_t n,
+                         const int32_t* items, const int32_t* second, const int64_t* off);
 int  sbr_sessions_adopt(sbr_sessions* s, const int32_t* slots, int32_t n_rows);
 int  sbr_sessions_rank(sbr_sessions* s, const int32_t* slots, int64_t n, int k, int exclude_mode,
                        const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host);

@@ -996,6 +996,8 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "cluster_rank_form") *value = h->last_cluster_rank_form;
     // the LAST sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates were scored, 2 they were gathered from the full scores
     else if (w == "cand_rank_form") *value = h->last_cand_rank_form;
+    // the kernel launches the LAST sbr_sessions_replay of any pool on this engine enqueued: 1 (0: no events, or none yet)
+    else if (w == "session_replay_launches") *value = h->last_replay_launches;
     // the LAST sbr_evaluate_candidates: the same two forms (0 none yet), and the width of its last chunk's compact score matrix
     else if (w == "eval_cand_form") *value = h->last_eval_cand_form;
     else if (w == "eval_cand_lmax") *value = h->last_eval_cand_lmax;

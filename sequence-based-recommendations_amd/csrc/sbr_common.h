@@ -429,6 +429,7 @@ struct sbr_handle {
     int last_next_rank_form = 0;                                          // sbr_evaluate_positions: 0 none yet, 1 16-byte loads of the score row, 2 4-byte loads
     int last_next_rank_slots = 0;                                         // ... and the positions it projected per GEMM launch at the most
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
+    int last_replay_launches = 0;                                         // sbr_sessions_replay: the kernel launches the most recent one enqueued
     int last_cand_rank_form = 0;                                          // sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates scored, 2 gathered from the full scores
     int last_eval_cand_form = 0, last_eval_cand_lmax = 0;                 // sbr_evaluate_candidates: the same two forms (0 none yet); the width of the last chunk's compact score matrix
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
@@ -495,10 +496,15 @@ struct SesPool {                                     // what the kernels read: p
     long long* events;                               // [capacity] events fed
     int* ring;                                       // [capacity][ring_len]: the id of event e at e % ring_len (ring_len = max(history, 1))
 };
+struct SesRow { long long start, len; int slot; };   // a row of sbr_sessions_replay: items[start .. start + len) go to slot
 struct sbr_sessions {
     sbr_handle* h;
     SesPool p;
     int *d_slots, *d_items, *d_second;               // [capacity] each: the lists of the call in flight (slots of a call are distinct)
+    // sbr_sessions_replay: its rows ([capacity], allocated by the first replay) and the events of the call in flight ([ev_cap] each,
+    // grown when a call needs more and kept); rows: the host's copy, longest first
+    SesRow* d_rows; int *d_ev_items, *d_ev_second; long long ev_cap;
+    std::vector<SesRow> rows;
     std::vector<unsigned> stamp; unsigned epoch;     // host: stamp[slot] == epoch: the slot was already named in this call
 };
 // sbr_session.hip: the kernels behind the calls.  Every slot, id and row count was checked on the host

@@ -1,8 +1,9 @@
-// Stateful sessions (include/sbr_rnn.h "Stateful sessions"): a pool of kept recurrent states beside the engine,
-// one recurrent step per event.  sbr_sessions_create / destroy / reset / advance / adopt / read / write and their kernels; the
+// Stateful sessions (include/sbr_rnn.h "Stateful sessions"; DESIGN.md sections 3o and 3r): a pool of kept recurrent states beside the
+// engine, one recurrent step per event.  sbr_sessions_create / destroy / reset / advance / replay / adopt / read / write and their kernels; the
 // ranking call sbr_sessions_rank is an entry to sbr_rank's pipeline and lives with it (sbr_rank_api.hip).
 //
-// The step (ses_step_kernel), one launch per layer: for the rows r < n of a call, s = slots[r],
+// The step (ses_step_kernel; its tile computation, ses_tile, is shared with ses_replay_kernel below), one launch per layer: for the
+// rows r < n of a call, s = slots[r],
 //     x = input(r) . W_in + b        layer 0 with index input: b + the F gathered rows of W_in (gather_xt_kernel's order);
 //                                    --r_emb: the F gathered embedding rows, flattened, as the A operand; layer >= 1: the lower
 //                                    layer's NEW state of slot s
@@ -33,99 +34,253 @@ namespace {
 
 enum SesInput { SES_IN_INDEX = 0, SES_IN_EMB = 1, SES_IN_DENSE = 2 };
 
-struct SesStep {
-    int n; const int* slots; const long long* events; long long capacity;
+// one layer as the tile computation reads it
+struct SesLayer {
+    long long capacity;
     int Hp, K_in;                      // units of the layer; K of the dense input (F * Ep, or the lower layer's Hp)
     const float *Whid, *Win, *bias, *peep;
     float *hs, *cs;                    // this layer's planes
-    const int *items, *second;         // layer 0: the ids fed (second: NULL with one index per step)
     const float* emb; int Ep;          // SES_IN_EMB: the embedding table [input_size][Ep]
     const float* in_hs; int in_Hp;     // SES_IN_DENSE: the lower layer's planes
     int relu;
 };
+// a row of the tile as a lane sees it: is it fed an event now, its slot, the events it had BEFORE this one (the plane to read:
+// ev & 1), the ids fed (layer 0)
+struct SesRowIn { bool ok; int s; long long ev; int id0, id1; };
 
-template <int CELL, int IN>
-__global__ void __launch_bounds__(256) ses_step_kernel(SesStep a) {
+// The tile computation of one layer and one event, shared by ses_step_kernel and ses_replay_kernel -- one arithmetic, so that the two
+// leave the same bits: 16 rows x the 16 units from u0 x G gates by one wave.  ra: the row this lane supplies to operand A (row j of
+// the tile), rm[e]: the rows whose results it holds (rows 4q + e).  A row that is not ok is computed as zeros and not written.
+// U: the K blocks whose operands are loaded before the first of their instructions is issued.  The instructions and their order are
+// the same for every U -- an output element stays the one chain over K --; only how many loads are in flight differs.  The step
+// takes U = 1 (its launch hides nothing else either); the replay, whose every event waits for this walk, keeps ~60 loads in flight.
+template <int CELL, int IN, int U>
+__device__ __forceinline__ void ses_tile(const SesLayer& a, const int u0, const int j, const int q, const SesRowIn& ra,
+                                         const SesRowIn (&rm)[4], const bool has_second) {
     constexpr int G = Gates<CELL>::G;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, q = lane >> 4;
-    const int u0 = (blockIdx.x * 4 + wave) * 16;
-    if (u0 >= a.Hp) return;                            // (no barrier in this kernel)
-    const int r0 = blockIdx.y * 16, Hp = a.Hp, GHp = G * Hp;
+    const int Hp = a.Hp, GHp = G * Hp;
     const size_t plane = (size_t)a.capacity * Hp;
-    // operand A: this lane's row
-    const int ra = r0 + j;
-    const bool a_ok = ra < a.n;
-    const int sa = a_ok ? a.slots[ra] : 0;
-    const long long ea = a_ok ? a.events[sa] : 0;
+    const bool a_ok = ra.ok;
+    const int sa = ra.s;
+    const long long ea = ra.ev;
     const float* hrow = a.hs + (size_t)(ea & 1) * plane + (size_t)sa * Hp;
     f32x4 acc_a[G], acc_x[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) { acc_a[g] = f32x4{0, 0, 0, 0}; acc_x[g] = f32x4{0, 0, 0, 0}; }
-    const float* wcol = a.Whid + u0 + j;
-    for (int k0 = 0; k0 < Hp; k0 += 16) {
-        const int kq = k0 + 4 * q;
-        const f32x4 hv = a_ok ? *(const f32x4*)(hrow + kq) : f32x4{0, 0, 0, 0};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float* w = wcol + (size_t)(kq + e) * GHp;
-#pragma unroll
-            for (int g = 0; g < G; ++g) acc_a[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[e], w[g * Hp], acc_a[g], 0, 0, 0);
-        }
-    }
-    if (IN != SES_IN_INDEX) {
-        const int K = a.K_in;                          // a multiple of 4: a quad is inside or outside
-        const float* in_row = nullptr;
-        int id0 = 0, id1 = 0;
-        if (IN == SES_IN_DENSE) in_row = a.in_hs + (size_t)((ea + 1) & 1) * ((size_t)a.capacity * a.in_Hp) + (size_t)sa * a.in_Hp;
-        else if (a_ok) { id0 = a.items[ra]; id1 = a.second ? a.second[ra] : 0; }
-        const float* vcol = a.Win + u0 + j;
-        for (int k0 = 0; k0 < K; k0 += 16) {
-            const int kq = k0 + 4 * q;
-            const bool in = kq < K;
-            f32x4 xv = {0, 0, 0, 0};
-            if (a_ok && in) {
-                if (IN == SES_IN_DENSE) xv = *(const f32x4*)(in_row + kq);
-                else { const int f = kq / a.Ep; xv = *(const f32x4*)(a.emb + (size_t)(f ? id1 : id0) * a.Ep + (kq - f * a.Ep)); }
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float* w = vcol + (size_t)(kq + e) * GHp;
-#pragma unroll
-                for (int g = 0; g < G; ++g) acc_x[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[e], in ? w[g * Hp] : 0.0f, acc_x[g], 0, 0, 0);
-            }
-        }
-    }
-    asm volatile("s_nop 15");                          // MFMA D -> VALU read hazard across the loop exit (see sbr_rec.hip)
-    // the cell: this lane holds rows r0 + 4q + e of unit u
+    // what the cell reads besides the two products, asked for before the walk over K so that it arrives behind it: the unit's
+    // peepholes and biases, the rows' old state, the gathered rows of an index input
     const int u = u0 + j;
     float pi = 0.0f, pf = 0.0f, po = 0.0f;
     if (CELL == CELL_LSTM) { pi = a.peep[u]; pf = a.peep[Hp + u]; po = a.peep[2 * Hp + u]; }
     float b[G];
 #pragma unroll
     for (int g = 0; g < G; ++g) b[g] = a.bias[g * Hp + u];
+    float h_old[4], c_old[4], x0[4][G], x1[4][G];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-        const int m = r0 + 4 * q + e;
-        if (m >= a.n) continue;
-        const int s = a.slots[m];
-        const size_t rd = (size_t)(a.events[s] & 1) * plane + (size_t)s * Hp + u;
-        const size_t wr = (size_t)((a.events[s] + 1) & 1) * plane + (size_t)s * Hp + u;
+        h_old[e] = c_old[e] = 0.0f;
+#pragma unroll
+        for (int g = 0; g < G; ++g) x0[e][g] = x1[e][g] = 0.0f;
+        if (!rm[e].ok) continue;
+        const size_t rd = (size_t)(rm[e].ev & 1) * plane + (size_t)rm[e].s * Hp + u;
+        h_old[e] = a.hs[rd];
+        if (CELL == CELL_LSTM) c_old[e] = a.cs[rd];
+        if (IN == SES_IN_INDEX) {
+#pragma unroll
+            for (int g = 0; g < G; ++g) {
+                x0[e][g] = a.Win[(size_t)rm[e].id0 * GHp + g * Hp + u];
+                if (has_second) x1[e][g] = a.Win[(size_t)rm[e].id1 * GHp + g * Hp + u];
+            }
+        }
+    }
+    const unsigned col = (unsigned)(u0 + j);               // 32-bit element offsets from the uniform bases: W_hid and a dense W_in have far fewer than 2^31 elements
+    // a group = U blocks of K: its operands are asked for (ld), then its instructions issued in the order of K (mm)
+    auto ld = [&](const int k0, f32x4 (&hv)[U], float (&wv)[U][4][G]) {
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            const int kq = k0 + 16 * i + 4 * q;
+            hv[i] = f32x4{0, 0, 0, 0};
+            if (U > 1 && k0 + 16 * i >= Hp) continue;      // (uniform)
+            if (a_ok) hv[i] = *(const f32x4*)(hrow + kq);
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int g = 0; g < G; ++g) wv[i][e][g] = a.Whid[(unsigned)(kq + e) * (unsigned)GHp + (unsigned)(g * Hp) + col];
+        }
+    };
+    auto mm = [&](const int k0, const f32x4 (&hv)[U], const float (&wv)[U][4][G]) {
+#pragma unroll
+        for (int i = 0; i < U; ++i) {
+            if (U > 1 && k0 + 16 * i >= Hp) continue;
+#pragma unroll
+            for (int e = 0; e < 4; ++e)
+#pragma unroll
+                for (int g = 0; g < G; ++g) acc_a[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(hv[i][e], wv[i][e][g], acc_a[g], 0, 0, 0);
+        }
+    };
+    if (U == 1) {
+        for (int k0 = 0; k0 < Hp; k0 += 16) {
+            f32x4 hv[U]; float wv[U][4][G];
+            ld(k0, hv, wv);
+            mm(k0, hv, wv);
+        }
+    } else {
+        // two groups in flight: the next group's operands are asked for before this group's instructions issue, so that the matrix
+        // pipe works while they travel
+        f32x4 hv0[U], hv1[U]; float wv0[U][4][G], wv1[U][4][G];
+        ld(0, hv0, wv0);
+        for (int k0 = 0; k0 < Hp; k0 += 32 * U) {
+            const int k1 = k0 + 16 * U, k2 = k0 + 32 * U;
+            if (k1 < Hp) ld(k1, hv1, wv1);
+            mm(k0, hv0, wv0);
+            if (k1 < Hp) {
+                if (k2 < Hp) ld(k2, hv0, wv0);
+                mm(k1, hv1, wv1);
+            }
+        }
+    }
+    if (IN != SES_IN_INDEX) {
+        const int K = a.K_in;                          // a multiple of 4: a quad is inside or outside
+        const float* in_row = nullptr;
+        if (IN == SES_IN_DENSE) in_row = a.in_hs + (size_t)((ea + 1) & 1) * ((size_t)a.capacity * a.in_Hp) + (size_t)sa * a.in_Hp;
+        const int id0 = ra.id0, id1 = ra.id1;
+        for (int k0 = 0; k0 < K; k0 += 16 * U) {
+            f32x4 xv[U]; float wv[U][4][G];
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                const int kq = k0 + 16 * i + 4 * q;
+                const bool in = kq < K;
+                xv[i] = f32x4{0, 0, 0, 0};
+                if (U > 1 && k0 + 16 * i >= K) continue;      // (uniform)
+                if (a_ok && in) {
+                    if (IN == SES_IN_DENSE) xv[i] = *(const f32x4*)(in_row + kq);
+                    else { const int f = kq / a.Ep; xv[i] = *(const f32x4*)(a.emb + (size_t)(f ? id1 : id0) * a.Ep + (kq - f * a.Ep)); }
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int g = 0; g < G; ++g) wv[i][e][g] = in ? a.Win[(unsigned)(kq + e) * (unsigned)GHp + (unsigned)(g * Hp) + col] : 0.0f;
+            }
+#pragma unroll
+            for (int i = 0; i < U; ++i) {
+                if (U > 1 && k0 + 16 * i >= K) continue;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int g = 0; g < G; ++g) acc_x[g] = __builtin_amdgcn_mfma_f32_16x16x4f32(xv[i][e], wv[i][e][g], acc_x[g], 0, 0, 0);
+            }
+        }
+    }
+    asm volatile("s_nop 15");                          // MFMA D -> VALU read hazard across the loop exit (see sbr_rec.hip)
+    // the cell: this lane holds rows 4q + e of unit u
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (!rm[e].ok) continue;
+        const size_t wr = (size_t)((rm[e].ev + 1) & 1) * plane + (size_t)rm[e].s * Hp + u;
         float x[G], av[G], sv[4];
 #pragma unroll
         for (int g = 0; g < G; ++g) {
             av[g] = acc_a[g][e];
             if (IN == SES_IN_INDEX) {
-                float v = b[g] + a.Win[(size_t)a.items[m] * GHp + g * Hp + u];
-                if (a.second) v += a.Win[(size_t)a.second[m] * GHp + g * Hp + u];
+                float v = b[g] + x0[e][g];
+                if (has_second) v += x1[e][g];
                 x[g] = v;
             } else
                 x[g] = acc_x[g][e] + b[g];
         }
-        float h = a.hs[rd], c = CELL == CELL_LSTM ? a.cs[rd] : 0.0f;
+        float h = h_old[e], c = c_old[e];
         cell_forward<CELL>(x, av, true, h, c, pi, pf, po, sv, a.relu != 0);
         a.hs[wr] = h;
         if (CELL == CELL_LSTM) a.cs[wr] = c;
     }
+}
+
+struct SesStep {
+    int n; const int* slots; const long long* events;
+    SesLayer ly;
+    const int *items, *second;         // layer 0: the ids fed (second: NULL with one index per step)
+};
+
+template <int CELL, int IN>
+__global__ void __launch_bounds__(256) ses_step_kernel(SesStep a) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, q = lane >> 4;
+    const int u0 = (blockIdx.x * 4 + wave) * 16;
+    if (u0 >= a.ly.Hp) return;                         // (no barrier in this kernel)
+    const int r0 = blockIdx.y * 16;
+    const bool ids = IN != SES_IN_DENSE;
+    auto row = [&](int m) {
+        SesRowIn r{m < a.n, 0, 0, 0, 0};
+        if (r.ok) {
+            r.s = a.slots[m]; r.ev = a.events[r.s];
+            if (ids) { r.id0 = a.items[m]; r.id1 = a.second ? a.second[m] : 0; }
+        }
+        return r;
+    };
+    const SesRowIn ra = row(r0 + j);
+    const SesRowIn rm[4] = {row(r0 + 4 * q), row(r0 + 4 * q + 1), row(r0 + 4 * q + 2), row(r0 + 4 * q + 3)};
+    ses_tile<CELL, IN, 1>(a.ly, u0, j, q, ra, rm, a.second != nullptr);
+}
+
+// The replay (sbr_sessions_replay): the time loop and the layer loop of a run of events inside ONE launch.  A workgroup owns the 16
+// rows of blockIdx.x (the rows of a call arrive longest first, so a tile's rows end together) and every unit tile of every layer:
+// wave w walks the unit tiles w, w + 4, ... with ses_tile, the step's own arithmetic.  Between events and layers the states are
+// exchanged through the slots' own two planes in global memory, exactly as a sequence of advance calls leaves them: event t of a row
+// that had e0 events reads plane (e0 + t) & 1 and writes the other, so the final state lies in plane (e0 + len) & 1 with nothing
+// copied.  A workgroup barrier behind every layer orders the planes' writes before their reads (all of them by this workgroup:
+// workgroup scope); layer 0 of event t + 1 overwrites the plane layer 0 read at event t and nobody reads any more.  No workgroup
+// waits for another.  A row whose list has ended is frozen: not computed, not written.  At the end the same launch counts the events
+// and writes the ring, as len commit launches would have.
+struct SesReplay {
+    int n, L; const SesRow* rows; const int *items, *second;
+    long long* events; int* ring; int ring_len;
+    SesLayer ly[SBR_MAX_LAYERS];
+};
+
+template <int CELL, int IN>
+__global__ void __launch_bounds__(256) ses_replay_kernel(SesReplay a) {
+    constexpr int U = CELL == CELL_VANILLA ? 4 : 2;    // 4 * G loads per K block, two groups of U blocks in flight: 32 to 64 loads
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, q = lane >> 4;
+    const int r0 = blockIdx.x * 16;
+    const SesRow none{0, 0, 0};
+    const int ma = r0 + j;
+    const SesRow rowa = ma < a.n ? a.rows[ma] : none;
+    const long long ea0 = ma < a.n ? a.events[rowa.slot] : 0;
+    SesRow rowm[4]; long long em0[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int m = r0 + 4 * q + e;
+        rowm[e] = m < a.n ? a.rows[m] : none;
+        em0[e] = m < a.n ? a.events[rowm[e].slot] : 0;
+    }
+    const long long T = a.rows[r0].len;                // the longest row of the tile
+    const bool has_second = a.second != nullptr;
+    for (long long t = 0; t < T; ++t) {
+        SesRowIn ra{t < rowa.len, rowa.slot, ea0 + t, 0, 0}, rm[4];
+        if (ra.ok) { ra.id0 = a.items[rowa.start + t]; ra.id1 = has_second ? a.second[rowa.start + t] : 0; }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            rm[e] = SesRowIn{t < rowm[e].len, rowm[e].slot, em0[e] + t, 0, 0};
+            if (rm[e].ok) { rm[e].id0 = a.items[rowm[e].start + t]; rm[e].id1 = has_second ? a.second[rowm[e].start + t] : 0; }
+        }
+        for (int l = 0; l < a.L; ++l) {
+            const SesLayer& ly = a.ly[l];
+            for (int u0 = wave * 16; u0 < ly.Hp; u0 += 64) {
+                if (l == 0) ses_tile<CELL, IN, U>(ly, u0, j, q, ra, rm, has_second);
+                else ses_tile<CELL, SES_IN_DENSE, U>(ly, u0, j, q, ra, rm, false);
+            }
+            __syncthreads();
+        }
+    }
+    // the commit: row (thread / 16) of the tile, its last min(len, ring_len) ids by 16 threads (T >= 1: the barriers above lie
+    // between every read of events[] and this write; T == 0: nothing to write)
+    const int m = r0 + (threadIdx.x >> 4);
+    if (m >= a.n) return;
+    const SesRow row = a.rows[m];
+    if (row.len == 0) return;
+    const long long e0 = a.events[row.slot];
+    for (long long t = max(0ll, row.len - a.ring_len) + (threadIdx.x & 15); t < row.len; t += 16)
+        a.ring[(size_t)row.slot * a.ring_len + (int)((e0 + t) % a.ring_len)] = a.items[row.start + t];
+    if ((threadIdx.x & 15) == 0) a.events[row.slot] = e0 + row.len;
 }
 
 // behind the last layer: the event is counted (the planes the step wrote become the current ones) and its id enters the ring
@@ -176,7 +331,7 @@ __global__ void __launch_bounds__(256) ses_gather_top_kernel(SesPool p, const in
 
 template <int CELL>
 hipError_t launch_step_cell(hipStream_t st, const SesStep& a, int in) {
-    const dim3 grid((a.Hp + 63) / 64, (a.n + 15) / 16);
+    const dim3 grid((a.ly.Hp + 63) / 64, (a.n + 15) / 16);
     if (in == SES_IN_INDEX) ses_step_kernel<CELL, SES_IN_INDEX><<<grid, 256, 0, st>>>(a);
     else if (in == SES_IN_EMB) ses_step_kernel<CELL, SES_IN_EMB><<<grid, 256, 0, st>>>(a);
     else ses_step_kernel<CELL, SES_IN_DENSE><<<grid, 256, 0, st>>>(a);
@@ -190,6 +345,37 @@ hipError_t launch_ses_step(hipStream_t st, int cell, const SesStep& a, int in) {
     }
 }
 
+template <int CELL>
+hipError_t launch_replay_cell(hipStream_t st, const SesReplay& a, int in) {
+    const unsigned grid = (unsigned)((a.n + 15) / 16);
+    if (in == SES_IN_INDEX) ses_replay_kernel<CELL, SES_IN_INDEX><<<grid, 256, 0, st>>>(a);
+    else ses_replay_kernel<CELL, SES_IN_EMB><<<grid, 256, 0, st>>>(a);
+    return hipGetLastError();
+}
+hipError_t launch_ses_replay(hipStream_t st, int cell, const SesReplay& a, int in) {
+    switch (cell) {
+        case SBR_CELL_LSTM: return launch_replay_cell<CELL_LSTM>(st, a, in);
+        case SBR_CELL_GRU: return launch_replay_cell<CELL_GRU>(st, a, in);
+        default: return launch_replay_cell<CELL_VANILLA>(st, a, in);
+    }
+}
+
+// layer l of the engine as the tile computation reads it
+SesLayer ses_layer(const sbr_sessions* s, int l) {
+    const sbr_handle* h = s->h;
+    const Layout& y = h->lay;
+    const LayerLayout& ly = y.layer[l];
+    SesLayer a{};
+    a.capacity = s->p.capacity;
+    a.Hp = ly.Hp; a.K_in = ly.n_in_p;
+    a.Whid = h->P(ly.p_Whid); a.Win = h->P(ly.p_Win); a.bias = h->P(ly.p_b); a.peep = h->P(ly.p_peep);
+    a.hs = s->p.hs[l]; a.cs = s->p.cs[l];
+    a.emb = y.E ? h->P(y.p_Emb) : nullptr; a.Ep = y.Ep;
+    if (l > 0) { a.in_hs = s->p.hs[l - 1]; a.in_Hp = y.layer[l - 1].Hp; }
+    a.relu = (y.cfg.cell == SBR_CELL_VANILLA && (l > 0 || y.E)) ? 1 : 0;      // stock RecurrentLayer: rectify (rec_shape, sbr_step.hip)
+    return a;
+}
+
 void ses_free(sbr_sessions* s) {
     for (int l = 0; l < SBR_MAX_LAYERS; ++l) { if (s->p.hs[l]) (void)hipFree(s->p.hs[l]); if (s->p.cs[l]) (void)hipFree(s->p.cs[l]); }
     if (s->p.events) (void)hipFree(s->p.events);
@@ -197,15 +383,18 @@ void ses_free(sbr_sessions* s) {
     if (s->d_slots) (void)hipFree(s->d_slots);
     if (s->d_items) (void)hipFree(s->d_items);
     if (s->d_second) (void)hipFree(s->d_second);
+    if (s->d_rows) (void)hipFree(s->d_rows);
+    if (s->d_ev_items) (void)hipFree(s->d_ev_items);
+    if (s->d_ev_second) (void)hipFree(s->d_ev_second);
     delete s;
 }
 
 template <class T>
-int ses_alloc(T** p, size_t n, const char* what) {
+int ses_alloc(T** p, size_t n, const char* what, const char* call = "sbr_sessions_create") {
     if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess) {
         (void)hipGetLastError();
         *p = nullptr;
-        sbr_set_error("sbr_sessions_create: hipMalloc(%zu) of %s failed", n * sizeof(T), what);
+        sbr_set_error("%s: hipMalloc(%zu) of %s failed", call, n * sizeof(T), what);
         return SBR_ENOMEM;
     }
     return SBR_OK;
@@ -261,6 +450,7 @@ extern "C" int sbr_sessions_create(sbr_handle* h, int64_t capacity, int32_t hist
     s->p = SesPool{};
     s->p.capacity = capacity; s->p.L = y.L; s->p.history = history; s->p.ring_len = std::max(history, 1);
     s->d_slots = s->d_items = s->d_second = nullptr;
+    s->d_rows = nullptr; s->d_ev_items = s->d_ev_second = nullptr; s->ev_cap = 0;
     s->epoch = 0;
     s->stamp.assign((size_t)capacity, 0u);
     int rc = SBR_OK;
@@ -333,20 +523,78 @@ extern "C" int sbr_sessions_advance(sbr_sessions* s, const int32_t* slots, const
     SBR_HIP(hipMemcpyAsync(s->d_items, items, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
     if (second) SBR_HIP(hipMemcpyAsync(s->d_second, second, (size_t)n * sizeof(int), hipMemcpyHostToDevice, st));
     for (int l = 0; l < y.L; ++l) {
-        const LayerLayout& ly = y.layer[l];
         SesStep a{};
-        a.n = (int)n; a.slots = s->d_slots; a.events = s->p.events; a.capacity = s->p.capacity;
-        a.Hp = ly.Hp; a.K_in = ly.n_in_p;
-        a.Whid = h->P(ly.p_Whid); a.Win = h->P(ly.p_Win); a.bias = h->P(ly.p_b); a.peep = h->P(ly.p_peep);
-        a.hs = s->p.hs[l]; a.cs = s->p.cs[l];
+        a.n = (int)n; a.slots = s->d_slots; a.events = s->p.events;
+        a.ly = ses_layer(s, l);
         a.items = s->d_items; a.second = second ? s->d_second : nullptr;
-        a.emb = y.E ? h->P(y.p_Emb) : nullptr; a.Ep = y.Ep;
-        if (l > 0) { a.in_hs = s->p.hs[l - 1]; a.in_Hp = y.layer[l - 1].Hp; }
-        a.relu = (y.cfg.cell == SBR_CELL_VANILLA && (l > 0 || y.E)) ? 1 : 0;      // stock RecurrentLayer: rectify (rec_shape, sbr_step.hip)
         SBR_LAUNCH(launch_ses_step(st, y.cfg.cell, a, l > 0 ? SES_IN_DENSE : (y.E ? SES_IN_EMB : SES_IN_INDEX)));
     }
     ses_commit_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(s->p, s->d_slots, s->d_items, (int)n);
     SBR_LAUNCH(hipGetLastError());
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_replay(sbr_sessions* s, const int32_t* slots, int64_t n, const int32_t* items, const int32_t* second,
+                                   const int64_t* off) {
+    CHECK_ARG(s, "null argument");
+    sbr_handle* h = s->h;
+    const Layout& y = h->lay;
+    int rc;
+    if ((rc = sessions_state_check(s, "sbr_sessions_replay")) != SBR_OK) return rc;
+    CHECK_ARG(n >= 0 && n <= s->p.capacity, "sbr_sessions_replay: n=%lld outside [0,capacity=%lld]", (long long)n, s->p.capacity);
+    CHECK_ARG(y.F == 2 || !second, "sbr_sessions_replay: `second` given, but the model feeds one index per step");
+    CHECK_ARG(y.F == 1 || second || n == 0, "sbr_sessions_replay: the model feeds two indices per step: `second` is required");
+    h->last_replay_launches = 0;
+    if (n == 0) return SBR_OK;
+    CHECK_ARG(slots && off, "null argument");
+    CHECK_ARG(off[0] == 0, "sbr_sessions_replay: off[0] = %lld, not 0", (long long)off[0]);
+    for (int64_t r = 0; r < n; ++r)
+        CHECK_ARG(off[r + 1] >= off[r], "sbr_sessions_replay: off[%lld] = %lld is below off[%lld] = %lld", (long long)(r + 1), (long long)off[r + 1],
+                  (long long)r, (long long)off[r]);
+    const int64_t total = off[n];
+    CHECK_ARG(total == 0 || items, "null argument");
+    if ((rc = sessions_check_slots(s, "sbr_sessions_replay", slots, n, true)) != SBR_OK) return rc;
+    const int n_ids = y.cfg.input_size;
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t i = off[r]; i < off[r + 1]; ++i) {
+            CHECK_ARG(items[i] >= 0 && items[i] < n_ids, "sbr_sessions_replay: items[%lld] = %d outside [0,%d) (event %lld of slot %d)", (long long)i,
+                      items[i], n_ids, (long long)(i - off[r]), slots[r]);
+            if (second) CHECK_ARG(second[i] >= 0 && second[i] < n_ids, "sbr_sessions_replay: second[%lld] = %d outside [0,%d) (event %lld of slot %d)",
+                                  (long long)i, second[i], n_ids, (long long)(i - off[r]), slots[r]);
+        }
+    if (total == 0) return SBR_OK;
+    // the rows that have events, longest first (stable): a tile's rows end together.  No output depends on which rows share a tile.
+    std::vector<SesRow>& rows = s->rows;
+    rows.clear();
+    for (int64_t r = 0; r < n; ++r)
+        if (off[r + 1] > off[r]) rows.push_back(SesRow{off[r], off[r + 1] - off[r], slots[r]});
+    std::stable_sort(rows.begin(), rows.end(), [](const SesRow& a, const SesRow& b) { return a.len > b.len; });
+    // the call's buffers: the pool's own, grown when a call needs more and kept (hipFree waits for a replay still reading the old ones)
+    if (!s->d_rows && (rc = ses_alloc(&s->d_rows, (size_t)s->p.capacity, "the row list", "sbr_sessions_replay")) != SBR_OK) return rc;
+    if (total > s->ev_cap) {
+        if (s->d_ev_items) (void)hipFree(s->d_ev_items);
+        if (s->d_ev_second) (void)hipFree(s->d_ev_second);
+        s->d_ev_items = s->d_ev_second = nullptr; s->ev_cap = 0;
+        const int64_t cap = std::max<int64_t>(total, 1024);
+        if ((rc = ses_alloc(&s->d_ev_items, (size_t)cap, "the event list", "sbr_sessions_replay")) != SBR_OK) return rc;
+        if (y.F == 2 && (rc = ses_alloc(&s->d_ev_second, (size_t)cap, "the second index list", "sbr_sessions_replay")) != SBR_OK) return rc;
+        s->ev_cap = cap;
+    }
+    hipStream_t st = h->stream;
+    // the rows of the index-addressed block that are read must be current, as in advance
+    if ((rc = flush_lazy(h, 0)) != SBR_OK) return rc;
+    // (pageable host memory: the copies have left the host arrays when they return)
+    SBR_HIP(hipMemcpyAsync(s->d_rows, rows.data(), rows.size() * sizeof(SesRow), hipMemcpyHostToDevice, st));
+    SBR_HIP(hipMemcpyAsync(s->d_ev_items, items, (size_t)total * sizeof(int), hipMemcpyHostToDevice, st));
+    if (second) SBR_HIP(hipMemcpyAsync(s->d_ev_second, second, (size_t)total * sizeof(int), hipMemcpyHostToDevice, st));
+    SesReplay a{};
+    a.n = (int)rows.size(); a.L = y.L; a.rows = s->d_rows;
+    a.items = s->d_ev_items; a.second = second ? s->d_ev_second : nullptr;
+    a.events = s->p.events; a.ring = s->p.ring; a.ring_len = s->p.ring_len;
+    for (int l = 0; l < y.L; ++l) a.ly[l] = ses_layer(s, l);
+    // ONE launch: the events of every layer, the event counts and the rings (ses_replay_kernel's end is the commit)
+    SBR_LAUNCH(launch_ses_replay(st, y.cfg.cell, a, y.E ? SES_IN_EMB : SES_IN_INDEX));
+    h->last_replay_launches = 1;
     return SBR_OK;
 }
 

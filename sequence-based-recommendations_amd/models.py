@@ -256,15 +256,21 @@ class RNNBase(object):
             out.extend([int(j) for j in row[row >= 0]] for row in ids)
         return out
 
-    def session_pool(self, capacity, history=None):
-        """An engine.SessionPool of `capacity` kept states for serving: feed a user's events one by one (advance) or start from an
-        existing history (engine.set_batch + adopt), and rank the next item from the kept state (rank) -- one recurrent step per
-        event where top_k_batch feeds the whole window again.  history: ids kept per session for the exclusion of viewed items
-        (default max_length).  A session has no window: it equals top_k_batch's state only while the events fit max_length."""
+    def session_pool(self, capacity, history=None, warm=None):
+        """An engine.SessionPool of `capacity` kept states for serving: feed a user's events one by one (advance) or a run of them
+        in one launch (replay), and rank the next item from the kept state (rank) -- one recurrent step per event where top_k_batch
+        feeds the whole window again.  history: ids kept per session for the exclusion of viewed items (default max_length).
+        warm: an optional (slots, sequences) pair replayed into the fresh pool (SessionPool.replay: histories of any length, where
+        engine.set_batch + adopt stops at max_length).  A session has no window: it equals top_k_batch's state only while the
+        events fit max_length."""
         if self.dp is not None or self.dist is not None:
             raise NotImplementedError("session pools of a data-parallel model: every rank would need a pool of its own, fed the same "
                                       "events at the same step; build the pool on a single-rank model")
-        return self.engine.sessions(capacity, self.max_length if history is None else history)
+        pool = self.engine.sessions(capacity, self.max_length if history is None else history)
+        if warm is not None:
+            slots, sequences = warm
+            pool.replay(slots, sequences)
+        return pool
 
     def _rank_chunks(self, sequences, user_ids, exclude):
         """top_k_batch's engine calls: (X, mask, lists) per batch_size sequences; lists: per row the ids never to rank, which carry
@@ -1268,7 +1274,7 @@ class RNNCluster(RNNBase):
         catalogue are not what it competes with."""
         return None
 
-    def session_pool(self, capacity, history=None):
+    def session_pool(self, capacity, history=None, warm=None):
         """A cluster model ranks inside each user's cluster, from the user representation of the engine's current batch
         (ClusterHead.rank): a session pool's rows are not that batch, so nothing could rank them the way this model ranks."""
         raise NotImplementedError("session pools of a cluster model: ranking inside a user's cluster reads the engine's current batch, "
