@@ -751,9 +751,9 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  * session carries its state over any number of events, which equals the windowed model of the other calls only while the events fit
  * max_length.
  *
- * Everything runs on the engine's stream.  reset / advance / replay / adopt enqueue and return without waiting for the device; rank waits
- * once, at its end, like sbr_rank; read and write wait.  A call that reads parameters brings lazily stepped rows up to date first
- * (see "Row-sparse blocks": advance and replay the index-input block, rank and adopt the output rows), which moves float32 roundings of a
+ * Everything runs on the engine's stream.  reset / advance / replay / adopt enqueue and return without waiting for the device; rank and replay_ranks wait
+ * once, at their end, like sbr_rank; read and write wait.  A call that reads parameters brings lazily stepped rows up to date first
+ * (see "Row-sparse blocks": advance and replay the index-input block, rank and adopt the output rows, replay_ranks both), which moves float32 roundings of a
  * training run as sbr_rank does and is otherwise invisible to it; sessions keep states, not weights: after a training step they go on
  * under the new weights.  Inside an open training step (between sbr_zero_grads and sbr_apply_update) or with a lagged cost pending,
  * every call but read returns SBR_ESTATE.  The current batch, its forward pass and the batch buffers stay as they were (adopt runs the
@@ -782,6 +782,36 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  *            anything is launched); a call that grows it frees the old one first, and hipFree WAITS for the device -- only such a
  *            call (the first one, and one with more events than any before) does not return at once.  THIS, not adopt, is the road for histories longer than max_length and for continuing a kept
  *            state (a returning user's new events, a pool rebuilt from a log, a slot restored with write and caught up).
+ *   replay_ranks   (sbr_sessions_replay_ranks) replay that also ranks every event before it is fed -- the online hit rate of the model
+ *            being served on a log, or next-item ranks at every event of test sequences of any length, from the arithmetic that
+ *            serves.  slots / n / items / second / off and everything replay refuses are replay's, and so is the effect on the pool:
+ *            states of every layer (padded units included), event counts and rings hold the very bits replay -- one advance per
+ *            event -- leaves.  Row r names slot s = slots[r], which has e0 events when the call arrives; for its event t,
+ *            x_t = items[off[r] + t]:  ranks_host[off[r] + t] = the rankable items that stand before x_t in sbr_rank's order (key
+ *            descending, ties to the lowest id) among the scores sbr_sessions_rank(s, exclude_mode) would rank at the moment the slot
+ *            has e0 + t events, before x_t is fed; -1 when x_t itself is not rankable there (NaN, -inf, excluded by the mode, id >= N;
+ *            with n_feat == 2 only `items` is ranked).  n_rankable_host[off[r] + t] = the rankable items at that moment.  Both
+ *            [off[n]].  events_before_host [n], may be NULL: e0 of every row, empty rows included.  The exclusion at event t is
+ *            rank's at that moment: the last min(e0 + t, kept) ids fed (kept = 1 for _LAST, `history` for _HISTORY), which come
+ *            from x_0 .. x_{t-1} and, where t < kept, from the ring as it stood BEFORE the call (kept aside before the first
+ *            launch); an id repeated in that window is excluded once.  On the default projection (and the triage one) an
+ *            element of the scores is one accumulation chain whose order does not depend on the rows of a launch, so the result
+ *            equals, integer for integer, the loop "rank at k = N, find x_t, advance".  Under SBR_FLAG_BF16_PROJECTION the one-pass
+ *            kernel chooses its tile by the row count: there the call gives the ranks of the scores that projection gives for the
+ *            group of states it projects together, with no bit promise against the loop (as sbr_evaluate_positions).
+ *            The call is cut in time into passes: one tracing launch of ses_replay_kernel from the kept state per pass -- the replay
+ *            itself, which also writes the top layer's state in front of every event --, then per group of states the projection
+ *            and one counting launch (ses_event_rank_kernel, sbr_eval.hip: one streamed pass over the N scores per event, 16-byte
+ *            loads when N % 4 == 0).  group_rows > 0: the most (row, event) pairs whose scores the call holds at once (their
+ *            states too, unless more rows than that have events: a pass then takes one event of each and projects them in groups);
+ *            0: as many as fit 64 MB of scores.  It bounds the ranking scratch and NOTHING else: results and pool bits are the same
+ *            for every value.  sbr_query "session_replay_rank_passes": the passes of the most recent call;
+ *            "session_event_rank_form": 1 / 2, 16- / 4-byte loads.  Trace, scores and results live in the handle's ranking scratch, the
+ *            events in the pool's buffer (replay's caveat about hipFree holds for both).  SBR_EINVAL before anything is launched, the
+ *            pool untouched: everything replay refuses, a mode outside the three, group_rows < 0, ranks_host / n_rankable_host NULL
+ *            with off[n] > 0, more than 2^31 - 1 events.  SBR_ESTATE as replay.  Lazily stepped rows: the index-input block as
+ *            for replay AND the output rows as for rank.  Waits once, at its end.  n == 0 or no events at all: no replay, no
+ *            projection, nothing written but events_before (one small launch gathers it when it is asked for).
  *   adopt    the prefill: rows 0 .. n_rows - 1 of the engine's current batch become the sessions slots[0 .. n_rows): the forward
  *            pass runs on the chain kernels (if the batch has none yet), then ONE launch copies each row's state at the row's length
  *            (of every layer), its length as the event count and its last `history` fed ids.  No batch set: SBR_ESTATE.
@@ -813,6 +843,10 @@ int  sbr_sessions_reset(sbr_sessions* s, const int32_t* slots, int64_t n);
 int  sbr_sessions_advance(sbr_sessions* s, const int32_t* slots, const int32_t* items, const int32_t* second, int64_t n);
 int  sbr_sessions_replay(sbr_sessions* s, const int32_t* slots, int64_t n,
                          const int32_t* items, const int32_t* second, const int64_t* off);
+int  sbr_sessions_replay_ranks(sbr_sessions* s, const int32_t* slots, int64_t n,
+                               const int32_t* items, const int32_t* second, const int64_t* off,
+                               int exclude_mode, int64_t group_rows,
+                               int32_t* ranks_host, int32_t* n_rankable_host, int64_t* events_before_host);
 int  sbr_sessions_adopt(sbr_sessions* s, const int32_t* slots, int32_t n_rows);
 int  sbr_sessions_rank(sbr_sessions* s, const int32_t* slots, int64_t n, int k, int exclude_mode,
                        const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host);

@@ -998,6 +998,10 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "cand_rank_form") *value = h->last_cand_rank_form;
     // the kernel launches the LAST sbr_sessions_replay of any pool on this engine enqueued: 1 (0: no events, or none yet)
     else if (w == "session_replay_launches") *value = h->last_replay_launches;
+    // the LAST sbr_sessions_replay_ranks of any pool on this engine: its passes (tracing replay launches; 0: no events, or none yet), and
+    // how its counting kernel read the score rows: 1 in 16-byte loads, 2 in 4-byte loads (N no multiple of 4), 0 none yet
+    else if (w == "session_replay_rank_passes") *value = h->last_replay_rank_passes;
+    else if (w == "session_event_rank_form") *value = h->last_event_rank_form;
     // the LAST sbr_evaluate_candidates: the same two forms (0 none yet), and the width of its last chunk's compact score matrix
     else if (w == "eval_cand_form") *value = h->last_eval_cand_form;
     else if (w == "eval_cand_lmax") *value = h->last_eval_cand_lmax;

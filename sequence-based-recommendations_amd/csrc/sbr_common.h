@@ -430,6 +430,7 @@ struct sbr_handle {
     int last_next_rank_slots = 0;                                         // ... and the positions it projected per GEMM launch at the most
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_replay_launches = 0;                                         // sbr_sessions_replay: the kernel launches the most recent one enqueued
+    int last_replay_rank_passes = 0, last_event_rank_form = 0;            // sbr_sessions_replay_ranks: the passes (tracing replay launches) of the most recent call; its count's loads as last_next_rank_form
     int last_cand_rank_form = 0;                                          // sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates scored, 2 gathered from the full scores
     int last_eval_cand_form = 0, last_eval_cand_lmax = 0;                 // sbr_evaluate_candidates: the same two forms (0 none yet); the width of the last chunk's compact score matrix
     int last_tail_gated = -1;                                             // ... sbr_query "tail_gate_first"
@@ -497,6 +498,10 @@ struct SesPool {                                     // what the kernels read: p
     int* ring;                                       // [capacity][ring_len]: the id of event e at e % ring_len (ring_len = max(history, 1))
 };
 struct SesRow { long long start, len; int slot; };   // a row of sbr_sessions_replay: items[start .. start + len) go to slot
+// beside a SesRow of a tracing pass (sbr_sessions_replay_ranks): the state before its event t goes to row at + t of the pass's trace;
+// first: where the row's list starts in the call's events (event t of the pass is event start + t - first of the call); call_row:
+// the row of the call, which names the event count and ring kept aside
+struct SesTraceRow { long long at, first; int call_row; };
 struct sbr_sessions {
     sbr_handle* h;
     SesPool p;
@@ -514,6 +519,23 @@ hipError_t launch_ses_gather_top(hipStream_t s, const SesPool& p, const int* slo
 // inside the pool and, with distinct, named once (SBR_EINVAL)
 int sessions_state_check(const sbr_sessions* s, const char* call);
 int sessions_check_slots(sbr_sessions* s, const char* call, const int32_t* slots, long long n, bool distinct);
+// ... and the pieces of sbr_sessions_replay that sbr_sessions_replay_ranks (sbr_rank_api.hip) runs as well: what is refused about the
+// lists, the device copy of the events (the pool's d_ev_items / d_ev_second; flushes the lazily stepped index-input rows), one replay
+// launch over device rows (trace != NULL: the tracing form), and the event counts [n] and rings [n][ring_len] (NULL: not) of the
+// call's slots kept aside
+int ses_replay_check(sbr_sessions* s, const char* call, const int32_t* slots, int64_t n, const int32_t* items, const int32_t* second,
+                     const int64_t* off);
+int ses_replay_events(sbr_sessions* s, const char* call, const int32_t* items, const int32_t* second, int64_t total);
+hipError_t launch_ses_replay_rows(sbr_sessions* s, const SesRow* d_rows, int n_rows, bool second, const SesTraceRow* trows, float* trace);
+hipError_t launch_ses_keep(hipStream_t st, const SesPool& p, const int* slots, long long n, long long* e0, int* ring);
+// sbr_eval.hip: one workgroup per row of a group of traced states, g0 the group's first trace row; scores [rows][N] are written (-inf
+// at the excluded ids) and then counted
+struct SesEventRank {
+    const SesRow* rows; const SesTraceRow* trows; int n_rows;      // the pass
+    const int* items; const long long* keep_e0; const int* keep_ring; int ring_len, history, mode;
+    long long g0; float* scores; int N; int *ranks, *n_rankable;
+};
+hipError_t launch_ses_event_rank(hipStream_t s, const SesEventRank& a, int rows, int* form);
 
 void sbr_set_error(const char* fmt, ...);
 #define SBR_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \

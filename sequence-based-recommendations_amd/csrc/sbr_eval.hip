@@ -291,7 +291,72 @@ __global__ void __launch_bounds__(kRankThreads) ev_next_rank_kernel(const int* _
     }
 }
 
+// ---- sbr_sessions_replay_ranks: the place of every replayed event among the scores of the state in front of it
+// One workgroup per row g0 + blockIdx.x of a pass's trace.  The pass row it belongs to is found by bisection over the rows' first
+// trace rows (ascending); with that the event is items[pos], pos = start + (its place in the pass row), and it is event
+// t = pos - first of the row's list in this call, the slot having had e0 + t events in front of it.  What sbr_sessions_rank would
+// exclude then -- excl_visit's session window: the last min(e0 + t, kept) ids fed -- lies in the call's own events as far as they
+// reach (x_{t-1} .. x_0) and beyond them in the ring as it stood BEFORE the call, kept aside by the host.  The pair's score row is
+// its own (nobody else reads it), so the window's ids are written -inf there, as launch_exclude does for a ranking, behind one
+// workgroup barrier; a repeated id is simply written twice, and a goal inside the window reads key 0 like any unrankable one.  Then
+// ev_next_rank_kernel's streamed count (next_count, the same two load forms) and its reduction.
+template <bool VEC>
+__global__ void __launch_bounds__(kRankThreads) ses_event_rank_kernel(SesEventRank a) {
+    __shared__ unsigned s_w[kNextRankWaves][2];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nthreads = blockDim.x;
+    const long long g = a.g0 + blockIdx.x;
+    int lo = 0, hi = a.n_rows - 1;                                 // the last pass row with at <= g (uniform)
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (a.trows[mid].at <= g) lo = mid; else hi = mid - 1; }
+    const SesTraceRow tw = a.trows[lo];
+    const long long pos = a.rows[lo].start + (g - tw.at);
+    const long long t = pos - tw.first, ev = a.keep_e0[tw.call_row] + t;
+    const int gid = a.items[pos];
+    float* row = a.scores + (size_t)blockIdx.x * a.N;
+    const long long kept = a.mode == SBR_SESSION_EXCL_NONE ? 0 : a.mode == SBR_SESSION_EXCL_LAST ? 1 : a.history;
+    const int nwin = (int)(ev < kept ? ev : kept);
+    const int* ring = a.keep_ring + (size_t)tw.call_row * a.ring_len;
+    for (int i = tid; i < nwin; i += nthreads) {
+        const int id = i < t ? a.items[pos - 1 - i] : ring[(ev - 1 - i) % a.ring_len];
+        if ((unsigned)id < (unsigned)a.N) row[id] = -INFINITY;
+    }
+    __syncthreads();
+    const bool gin = (unsigned)gid < (unsigned)a.N;                // an id outside the catalogue is never ranked
+    const unsigned gkey = gin ? rank_key(row[gid]) : 0u;
+    const unsigned long long gcomp = ((unsigned long long)gkey << 32) | (unsigned long long)(0xffffffffu - (unsigned)gid);
+    NextCount c{0u, 0u};
+    if (VEC) {
+        const float4* row4 = (const float4*)row;
+        for (int i4 = tid; i4 < a.N / 4; i4 += nthreads) {
+            const float4 v = row4[i4];
+            next_count(v.x, 4 * i4, gcomp, c); next_count(v.y, 4 * i4 + 1, gcomp, c);
+            next_count(v.z, 4 * i4 + 2, gcomp, c); next_count(v.w, 4 * i4 + 3, gcomp, c);
+        }
+    } else
+        for (int i = tid; i < a.N; i += nthreads) next_count(row[i], i, gcomp, c);
+    unsigned v0 = c.nr, v1 = c.ahead;
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) { v0 += __shfl_xor(v0, o2); v1 += __shfl_xor(v1, o2); }
+    if (lane == 0) { s_w[w][0] = v0; s_w[w][1] = v1; }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned nr = 0, ahead = 0;
+        for (int i = 0; i < nthreads / 64; ++i) { nr += s_w[i][0]; ahead += s_w[i][1]; }
+        a.ranks[pos] = gkey == 0u ? -1 : (int)ahead;
+        a.n_rankable[pos] = (int)nr;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_ses_event_rank(hipStream_t s, const SesEventRank& a, int rows, int* form) {
+    const bool vec = a.N % 4 == 0;                                 // (the score rows start on 16-byte boundaries then: the scratch is carved in 256 bytes)
+    *form = vec ? 1 : 2;
+    if (rows <= 0) return hipSuccess;
+    const int threads = a.N <= 16384 ? 256 : kRankThreads;         // as launch_ev_next_rank
+    if (vec) ses_event_rank_kernel<true><<<rows, threads, 0, s>>>(a);
+    else ses_event_rank_kernel<false><<<rows, threads, 0, s>>>(a);
+    return hipGetLastError();
+}
 
 hipError_t launch_ev_pack(hipStream_t s, const SbrEvalView& v, const int* users, int rows, int Bp, int T, int F, int* X, int* lengths, float* pop) {
     if (Bp <= 0) return hipSuccess;

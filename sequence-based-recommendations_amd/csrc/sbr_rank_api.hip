@@ -212,6 +212,125 @@ extern "C" int sbr_sessions_rank(sbr_sessions* ses, const int32_t* slots, int64_
     return check_fault(h);
 }
 
+// sbr_sessions_replay that also ranks every event before it is fed (include/sbr_rnn.h "Stateful sessions").  The call
+// is cut in time into passes, all planned on the host before the first launch: a pass takes the rows that still have events, at
+// most P events each, P the largest for which the pass's (row, event) pairs stay within group_rows (P = 1 where the rows alone
+// exceed it), longest first.  Per pass: ONE tracing replay launch from the kept state (launch_ses_replay_rows: the replay itself, which
+// also writes the top layer's state in front of every event into `trace`), then per group of at most group_rows trace rows
+// project_rows -- the floats sbr_sessions_rank projects for a slot in that state -- and ses_event_rank_kernel.  The replay's commit
+// overwrites event counts and rings, so those of the named slots are kept aside first (launch_ses_keep).  Everything on the engine's
+// stream without a host wait; the call waits once, in check_fault.  Rows, trace, scores, what is kept aside and the results live in
+// the handle's ranking scratch; the events in the pool's buffers, as for replay.
+extern "C" int sbr_sessions_replay_ranks(sbr_sessions* ses, const int32_t* slots, int64_t n, const int32_t* items, const int32_t* second,
+                                         const int64_t* off, int exclude_mode, int64_t group_rows, int32_t* ranks_host,
+                                         int32_t* n_rankable_host, int64_t* events_before_host) {
+    static const char* const call = "sbr_sessions_replay_ranks";
+    CHECK_ARG(ses, "null argument");
+    sbr_handle* h = ses->h;
+    const Layout& y = h->lay;
+    const SesPool& p = ses->p;
+    int rc;
+    if ((rc = sessions_state_check(ses, call)) != SBR_OK) return rc;
+    CHECK_ARG(exclude_mode >= SBR_SESSION_EXCL_NONE && exclude_mode <= SBR_SESSION_EXCL_HISTORY, "%s: unknown exclusion mode %d", call, exclude_mode);
+    CHECK_ARG(group_rows >= 0, "%s: group_rows=%lld is negative", call, (long long)group_rows);
+    if ((rc = ses_replay_check(ses, call, slots, n, items, second, off)) != SBR_OK) return rc;
+    const int64_t total = n ? off[n] : 0;
+    CHECK_ARG(total == 0 || (ranks_host && n_rankable_host), "%s: ranks_host and n_rankable_host are required (%lld events)", call, (long long)total);
+    CHECK_ARG(total <= 0x7fffffff, "%s: %lld events in one call, at most 2^31 - 1", call, (long long)total);
+    h->last_replay_rank_passes = 0;
+    if (n == 0 || (total == 0 && !events_before_host)) return SBR_OK;
+    const int64_t G = group_rows ? group_rows : (int64_t)std::max<size_t>(1, kNextRankScoreBytes / ((size_t)y.N * sizeof(float)));
+    // --- the passes
+    struct Left { int64_t at, left; int row; };                       // a row of the call: its next event, how many are left
+    std::vector<Left> left;
+    for (int64_t r = 0; r < n; ++r)
+        if (off[r + 1] > off[r]) left.push_back(Left{off[r], off[r + 1] - off[r], (int)r});
+    std::vector<SesRow> rows;                                         // the rows of every pass, one pass behind the other
+    std::vector<SesTraceRow> trows;
+    std::vector<size_t> pass_at;                                      // where a pass starts in rows (and, at the end, rows.size())
+    std::vector<int64_t> pass_trace;                                  // its trace rows
+    int64_t max_trace = 0;
+    while (!left.empty()) {
+        auto pairs = [&](int64_t P) { int64_t sum = 0; for (const Left& l : left) sum += std::min(l.left, P); return sum; };
+        int64_t P = 1, hi = 0;
+        for (const Left& l : left) hi = std::max(hi, l.left);
+        while (P < hi) {                                              // the largest P in [1, hi] whose pairs fit G (1 if none does)
+            const int64_t mid = P + (hi - P + 1) / 2;
+            if (pairs(mid) <= G) P = mid; else hi = mid - 1;
+        }
+        const size_t r0 = rows.size();
+        pass_at.push_back(r0);
+        for (const Left& l : left) rows.push_back(SesRow{l.at, std::min(l.left, P), slots[l.row]});
+        // longest first (stable): a tile's rows end together; the trace rows follow that order
+        std::vector<size_t> order(left.size());
+        for (size_t i = 0; i < order.size(); ++i) order[i] = i;
+        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return rows[r0 + a].len > rows[r0 + b].len; });
+        std::vector<SesRow> sorted(order.size());
+        int64_t at = 0;
+        for (size_t i = 0; i < order.size(); ++i) {
+            sorted[i] = rows[r0 + order[i]];
+            const int row = left[order[i]].row;
+            trows.push_back(SesTraceRow{at, off[row], row});
+            at += sorted[i].len;
+        }
+        std::copy(sorted.begin(), sorted.end(), rows.begin() + r0);
+        pass_trace.push_back(at);
+        max_trace = std::max(max_trace, at);
+        std::vector<Left> next;
+        for (const Left& l : left) { const int64_t k = std::min(l.left, P); if (l.left > k) next.push_back(Left{l.at + k, l.left - k, l.row}); }
+        left.swap(next);
+    }
+    pass_at.push_back(rows.size());
+    // --- the scratch
+    const LayerLayout& top = y.layer[y.L - 1];
+    const int64_t score_rows = std::min(G, max_trace);
+    Carver cv;
+    const size_t o_slots = cv.take((size_t)n * sizeof(int)), o_e0 = cv.take((size_t)n * sizeof(long long));
+    const size_t o_ring = cv.take(total ? (size_t)n * p.ring_len * sizeof(int) : 0);
+    const size_t o_rows = cv.take(rows.size() * sizeof(SesRow)), o_trows = cv.take(trows.size() * sizeof(SesTraceRow));
+    const size_t o_ranks = cv.take((size_t)total * sizeof(int)), o_nrk = cv.take((size_t)total * sizeof(int));
+    const size_t o_trace = cv.take((size_t)max_trace * top.Hp * sizeof(float));
+    const size_t o_scores = cv.take((size_t)score_rows * y.N * sizeof(float));
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    // lazily stepped rows: the index-input block as for replay (ses_replay_events), the output rows as for rank
+    if (total) {
+        if ((rc = ses_replay_events(ses, call, items, second, total)) != SBR_OK) return rc;
+        if ((rc = flush_lazy(h, 1)) != SBR_OK) return rc;
+    }
+    // (pageable host memory: the copies have left the host arrays when they return)
+    SBR_HIP(hipMemcpyAsync(S + o_slots, slots, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    SBR_LAUNCH(launch_ses_keep(s, p, (const int*)(S + o_slots), n, (long long*)(S + o_e0), total ? (int*)(S + o_ring) : nullptr));
+    if (total) {
+        SBR_HIP(hipMemcpyAsync(S + o_rows, rows.data(), rows.size() * sizeof(SesRow), hipMemcpyHostToDevice, s));
+        SBR_HIP(hipMemcpyAsync(S + o_trows, trows.data(), trows.size() * sizeof(SesTraceRow), hipMemcpyHostToDevice, s));
+    }
+    float* trace = (float*)(S + o_trace);
+    float* scores = (float*)(S + o_scores);
+    for (size_t ps = 0; ps + 1 < pass_at.size(); ++ps) {
+        const SesRow* drows = (const SesRow*)(S + o_rows) + pass_at[ps];
+        const SesTraceRow* dtrows = (const SesTraceRow*)(S + o_trows) + pass_at[ps];
+        const int n_rows = (int)(pass_at[ps + 1] - pass_at[ps]);
+        SBR_LAUNCH(launch_ses_replay_rows(ses, drows, n_rows, second != nullptr, dtrows, trace));
+        for (int64_t g0 = 0; g0 < pass_trace[ps]; g0 += score_rows) {
+            const int gr = (int)std::min<int64_t>(score_rows, pass_trace[ps] - g0);
+            if ((rc = project_rows(h, trace + (size_t)g0 * top.Hp, gr, scores, 0)) != SBR_OK) return rc;
+            const SesEventRank a{drows, dtrows, n_rows, ses->d_ev_items, (const long long*)(S + o_e0), (const int*)(S + o_ring), p.ring_len, p.history,
+                                 exclude_mode, g0, scores, y.N, (int*)(S + o_ranks), (int*)(S + o_nrk)};
+            SBR_LAUNCH(launch_ses_event_rank(s, a, gr, &h->last_event_rank_form));
+        }
+    }
+    h->last_replay_rank_passes = (int)pass_trace.size();
+    if (total) {
+        SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+        SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    static_assert(sizeof(long long) == sizeof(int64_t), "the event counts are fetched as they are");
+    if (events_before_host) SBR_HIP(hipMemcpyAsync(events_before_host, S + o_e0, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost, s));
+    return check_fault(h);          // the call's one wait for the device
+}
+
 // ---------------------------------------------------------------------------------------
 // Ranking inside a candidate list the caller brings (include/sbr_rnn.h: sbr_rank_candidates, sbr_sessions_rank_candidates; kernels
 // and the accumulation-order argument: sbr_cand_rank.hip, sbr_cluster_rank.hip)

@@ -230,13 +230,22 @@ __global__ void __launch_bounds__(256) ses_step_kernel(SesStep a) {
 // workgroup scope); layer 0 of event t + 1 overwrites the plane layer 0 read at event t and nobody reads any more.  No workgroup
 // waits for another.  A row whose list has ended is frozen: not computed, not written.  At the end the same launch counts the events
 // and writes the ring, as len commit launches would have.
+//
+// TRACE (sbr_sessions_replay_ranks): the same kernel also writes the top layer's state BEFORE event t of row m to
+// trace[trows[m].at + t][0 .. Hp_top), the rows sbr_sessions_rank would have projected at that moment.  At the head of iteration t the
+// workgroup copies, for its rows that have an event t, the top layer's plane (e0 + t) & 1: the slot's current plane for t == 0, and
+// for t >= 1 the plane the top layer wrote at event t - 1, behind that event's last layer barrier.  No barrier is added: that plane
+// is next written by the top layer at event t + 1, behind the L >= 1 barriers that end iteration t (with L == 1 the top layer is
+// layer 0, which in iteration t itself writes the OTHER plane), and a wave's loads have returned when it passes a barrier.  The state
+// after the last event is not traced.  The TRACE = false instantiation holds none of this.
 struct SesReplay {
     int n, L; const SesRow* rows; const int *items, *second;
     long long* events; int* ring; int ring_len;
     SesLayer ly[SBR_MAX_LAYERS];
+    const SesTraceRow* trows; float* trace;          // TRACE only
 };
 
-template <int CELL, int IN>
+template <int CELL, int IN, bool TRACE>
 __global__ void __launch_bounds__(256) ses_replay_kernel(SesReplay a) {
     constexpr int U = CELL == CELL_VANILLA ? 4 : 2;    // 4 * G loads per K block, two groups of U blocks in flight: 32 to 64 loads
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, j = lane & 15, q = lane >> 4;
@@ -254,7 +263,20 @@ __global__ void __launch_bounds__(256) ses_replay_kernel(SesReplay a) {
     }
     const long long T = a.rows[r0].len;                // the longest row of the tile
     const bool has_second = a.second != nullptr;
+    // TRACE: row (thread / 16) of the tile is copied by 16 threads, a 16-byte access each per 64 units
+    const int mc = r0 + (threadIdx.x >> 4);
+    SesRow rowc = none; long long ec0 = 0; float* tr = nullptr;
+    if (TRACE && mc < a.n) {
+        rowc = a.rows[mc]; ec0 = a.events[rowc.slot];
+        tr = a.trace + (size_t)a.trows[mc].at * a.ly[a.L - 1].Hp;
+    }
     for (long long t = 0; t < T; ++t) {
+        if (TRACE && t < rowc.len) {
+            const SesLayer& top = a.ly[a.L - 1];
+            const float* src = top.hs + (size_t)((ec0 + t) & 1) * ((size_t)top.capacity * top.Hp) + (size_t)rowc.slot * top.Hp;
+            float* dst = tr + (size_t)t * top.Hp;
+            for (int u = (threadIdx.x & 15) * 4; u < top.Hp; u += 64) *(f32x4*)(dst + u) = *(const f32x4*)(src + u);
+        }
         SesRowIn ra{t < rowa.len, rowa.slot, ea0 + t, 0, 0}, rm[4];
         if (ra.ok) { ra.id0 = a.items[rowa.start + t]; ra.id1 = has_second ? a.second[rowa.start + t] : 0; }
 #pragma unroll
@@ -329,6 +351,15 @@ __global__ void __launch_bounds__(256) ses_gather_top_kernel(SesPool p, const in
     for (int u = threadIdx.x; u < Hp; u += 256) out[(size_t)r * Hp + u] = src[u];
 }
 
+// sbr_sessions_replay_ranks, before its first replay launch: row blockIdx.x of the call keeps its slot's event count and ring aside
+// (the replay's own commit overwrites both)
+__global__ void __launch_bounds__(64) ses_keep_kernel(SesPool p, const int* __restrict__ slots, long long* __restrict__ e0, int* __restrict__ ring) {
+    const int r = blockIdx.x, s = slots[r];
+    if (threadIdx.x == 0) e0[r] = p.events[s];
+    if (ring)
+        for (int t = threadIdx.x; t < p.ring_len; t += 64) ring[(size_t)r * p.ring_len + t] = p.ring[(size_t)s * p.ring_len + t];
+}
+
 template <int CELL>
 hipError_t launch_step_cell(hipStream_t st, const SesStep& a, int in) {
     const dim3 grid((a.ly.Hp + 63) / 64, (a.n + 15) / 16);
@@ -348,8 +379,11 @@ hipError_t launch_ses_step(hipStream_t st, int cell, const SesStep& a, int in) {
 template <int CELL>
 hipError_t launch_replay_cell(hipStream_t st, const SesReplay& a, int in) {
     const unsigned grid = (unsigned)((a.n + 15) / 16);
-    if (in == SES_IN_INDEX) ses_replay_kernel<CELL, SES_IN_INDEX><<<grid, 256, 0, st>>>(a);
-    else ses_replay_kernel<CELL, SES_IN_EMB><<<grid, 256, 0, st>>>(a);
+    if (a.trace) {
+        if (in == SES_IN_INDEX) ses_replay_kernel<CELL, SES_IN_INDEX, true><<<grid, 256, 0, st>>>(a);
+        else ses_replay_kernel<CELL, SES_IN_EMB, true><<<grid, 256, 0, st>>>(a);
+    } else if (in == SES_IN_INDEX) ses_replay_kernel<CELL, SES_IN_INDEX, false><<<grid, 256, 0, st>>>(a);
+    else ses_replay_kernel<CELL, SES_IN_EMB, false><<<grid, 256, 0, st>>>(a);
     return hipGetLastError();
 }
 hipError_t launch_ses_replay(hipStream_t st, int cell, const SesReplay& a, int in) {
@@ -416,6 +450,12 @@ hipError_t launch_ses_reset(hipStream_t st, const SesPool& p, const sbr_handle* 
 hipError_t launch_ses_gather_top(hipStream_t st, const SesPool& p, const int* slots, int rows, float* out) {
     if (rows <= 0) return hipSuccess;
     ses_gather_top_kernel<<<rows, 256, 0, st>>>(p, slots, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_ses_keep(hipStream_t st, const SesPool& p, const int* slots, long long n, long long* e0, int* ring) {
+    if (n <= 0) return hipSuccess;
+    ses_keep_kernel<<<(unsigned)n, 64, 0, st>>>(p, slots, e0, ring);
     return hipGetLastError();
 }
 
@@ -534,34 +574,79 @@ extern "C" int sbr_sessions_advance(sbr_sessions* s, const int32_t* slots, const
     return SBR_OK;
 }
 
+// Everything sbr_sessions_replay (and sbr_sessions_replay_ranks, `call`) refuses about its lists, before anything is launched
+int ses_replay_check(sbr_sessions* s, const char* call, const int32_t* slots, int64_t n, const int32_t* items, const int32_t* second,
+                     const int64_t* off) {
+    const Layout& y = s->h->lay;
+    int rc;
+    CHECK_ARG(n >= 0 && n <= s->p.capacity, "%s: n=%lld outside [0,capacity=%lld]", call, (long long)n, s->p.capacity);
+    CHECK_ARG(y.F == 2 || !second, "%s: `second` given, but the model feeds one index per step", call);
+    CHECK_ARG(y.F == 1 || second || n == 0, "%s: the model feeds two indices per step: `second` is required", call);
+    if (n == 0) return SBR_OK;
+    CHECK_ARG(slots && off, "null argument");
+    CHECK_ARG(off[0] == 0, "%s: off[0] = %lld, not 0", call, (long long)off[0]);
+    for (int64_t r = 0; r < n; ++r)
+        CHECK_ARG(off[r + 1] >= off[r], "%s: off[%lld] = %lld is below off[%lld] = %lld", call, (long long)(r + 1), (long long)off[r + 1],
+                  (long long)r, (long long)off[r]);
+    const int64_t total = off[n];
+    CHECK_ARG(total == 0 || items, "null argument");
+    if ((rc = sessions_check_slots(s, call, slots, n, true)) != SBR_OK) return rc;
+    const int n_ids = y.cfg.input_size;
+    for (int64_t r = 0; r < n; ++r)
+        for (int64_t i = off[r]; i < off[r + 1]; ++i) {
+            CHECK_ARG(items[i] >= 0 && items[i] < n_ids, "%s: items[%lld] = %d outside [0,%d) (event %lld of slot %d)", call, (long long)i,
+                      items[i], n_ids, (long long)(i - off[r]), slots[r]);
+            if (second) CHECK_ARG(second[i] >= 0 && second[i] < n_ids, "%s: second[%lld] = %d outside [0,%d) (event %lld of slot %d)", call,
+                                  (long long)i, second[i], n_ids, (long long)(i - off[r]), slots[r]);
+        }
+    return SBR_OK;
+}
+
+// The device copy of a call's events: the pool's own buffers, grown when a call needs more and kept (hipFree waits for a replay still
+// reading the old ones); then the index-input rows are made current (as in advance) and the events uploaded
+int ses_replay_events(sbr_sessions* s, const char* call, const int32_t* items, const int32_t* second, int64_t total) {
+    sbr_handle* h = s->h;
+    int rc;
+    if (total > s->ev_cap) {
+        if (s->d_ev_items) (void)hipFree(s->d_ev_items);
+        if (s->d_ev_second) (void)hipFree(s->d_ev_second);
+        s->d_ev_items = s->d_ev_second = nullptr; s->ev_cap = 0;
+        const int64_t cap = std::max<int64_t>(total, 1024);
+        if ((rc = ses_alloc(&s->d_ev_items, (size_t)cap, "the event list", call)) != SBR_OK) return rc;
+        if (h->lay.F == 2 && (rc = ses_alloc(&s->d_ev_second, (size_t)cap, "the second index list", call)) != SBR_OK) return rc;
+        s->ev_cap = cap;
+    }
+    // the rows of the index-addressed block that are read must be current, as in advance
+    if ((rc = flush_lazy(h, 0)) != SBR_OK) return rc;
+    // (pageable host memory: the copies have left the host arrays when they return)
+    SBR_HIP(hipMemcpyAsync(s->d_ev_items, items, (size_t)total * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    if (second) SBR_HIP(hipMemcpyAsync(s->d_ev_second, second, (size_t)total * sizeof(int), hipMemcpyHostToDevice, h->stream));
+    return SBR_OK;
+}
+
+// ONE launch over n_rows device rows (longest first): the events of every layer, the event counts and the rings (ses_replay_kernel's
+// end is the commit); trace != NULL: the tracing form, trows beside rows
+hipError_t launch_ses_replay_rows(sbr_sessions* s, const SesRow* d_rows, int n_rows, bool second, const SesTraceRow* trows, float* trace) {
+    const Layout& y = s->h->lay;
+    SesReplay a{};
+    a.n = n_rows; a.L = y.L; a.rows = d_rows;
+    a.items = s->d_ev_items; a.second = second ? s->d_ev_second : nullptr;
+    a.events = s->p.events; a.ring = s->p.ring; a.ring_len = s->p.ring_len;
+    for (int l = 0; l < y.L; ++l) a.ly[l] = ses_layer(s, l);
+    a.trows = trows; a.trace = trace;
+    return launch_ses_replay(s->h->stream, y.cfg.cell, a, y.E ? SES_IN_EMB : SES_IN_INDEX);
+}
+
 extern "C" int sbr_sessions_replay(sbr_sessions* s, const int32_t* slots, int64_t n, const int32_t* items, const int32_t* second,
                                    const int64_t* off) {
     CHECK_ARG(s, "null argument");
     sbr_handle* h = s->h;
-    const Layout& y = h->lay;
     int rc;
     if ((rc = sessions_state_check(s, "sbr_sessions_replay")) != SBR_OK) return rc;
-    CHECK_ARG(n >= 0 && n <= s->p.capacity, "sbr_sessions_replay: n=%lld outside [0,capacity=%lld]", (long long)n, s->p.capacity);
-    CHECK_ARG(y.F == 2 || !second, "sbr_sessions_replay: `second` given, but the model feeds one index per step");
-    CHECK_ARG(y.F == 1 || second || n == 0, "sbr_sessions_replay: the model feeds two indices per step: `second` is required");
     h->last_replay_launches = 0;
+    if ((rc = ses_replay_check(s, "sbr_sessions_replay", slots, n, items, second, off)) != SBR_OK) return rc;
     if (n == 0) return SBR_OK;
-    CHECK_ARG(slots && off, "null argument");
-    CHECK_ARG(off[0] == 0, "sbr_sessions_replay: off[0] = %lld, not 0", (long long)off[0]);
-    for (int64_t r = 0; r < n; ++r)
-        CHECK_ARG(off[r + 1] >= off[r], "sbr_sessions_replay: off[%lld] = %lld is below off[%lld] = %lld", (long long)(r + 1), (long long)off[r + 1],
-                  (long long)r, (long long)off[r]);
     const int64_t total = off[n];
-    CHECK_ARG(total == 0 || items, "null argument");
-    if ((rc = sessions_check_slots(s, "sbr_sessions_replay", slots, n, true)) != SBR_OK) return rc;
-    const int n_ids = y.cfg.input_size;
-    for (int64_t r = 0; r < n; ++r)
-        for (int64_t i = off[r]; i < off[r + 1]; ++i) {
-            CHECK_ARG(items[i] >= 0 && items[i] < n_ids, "sbr_sessions_replay: items[%lld] = %d outside [0,%d) (event %lld of slot %d)", (long long)i,
-                      items[i], n_ids, (long long)(i - off[r]), slots[r]);
-            if (second) CHECK_ARG(second[i] >= 0 && second[i] < n_ids, "sbr_sessions_replay: second[%lld] = %d outside [0,%d) (event %lld of slot %d)",
-                                  (long long)i, second[i], n_ids, (long long)(i - off[r]), slots[r]);
-        }
     if (total == 0) return SBR_OK;
     // the rows that have events, longest first (stable): a tile's rows end together.  No output depends on which rows share a tile.
     std::vector<SesRow>& rows = s->rows;
@@ -569,31 +654,10 @@ extern "C" int sbr_sessions_replay(sbr_sessions* s, const int32_t* slots, int64_
     for (int64_t r = 0; r < n; ++r)
         if (off[r + 1] > off[r]) rows.push_back(SesRow{off[r], off[r + 1] - off[r], slots[r]});
     std::stable_sort(rows.begin(), rows.end(), [](const SesRow& a, const SesRow& b) { return a.len > b.len; });
-    // the call's buffers: the pool's own, grown when a call needs more and kept (hipFree waits for a replay still reading the old ones)
     if (!s->d_rows && (rc = ses_alloc(&s->d_rows, (size_t)s->p.capacity, "the row list", "sbr_sessions_replay")) != SBR_OK) return rc;
-    if (total > s->ev_cap) {
-        if (s->d_ev_items) (void)hipFree(s->d_ev_items);
-        if (s->d_ev_second) (void)hipFree(s->d_ev_second);
-        s->d_ev_items = s->d_ev_second = nullptr; s->ev_cap = 0;
-        const int64_t cap = std::max<int64_t>(total, 1024);
-        if ((rc = ses_alloc(&s->d_ev_items, (size_t)cap, "the event list", "sbr_sessions_replay")) != SBR_OK) return rc;
-        if (y.F == 2 && (rc = ses_alloc(&s->d_ev_second, (size_t)cap, "the second index list", "sbr_sessions_replay")) != SBR_OK) return rc;
-        s->ev_cap = cap;
-    }
-    hipStream_t st = h->stream;
-    // the rows of the index-addressed block that are read must be current, as in advance
-    if ((rc = flush_lazy(h, 0)) != SBR_OK) return rc;
-    // (pageable host memory: the copies have left the host arrays when they return)
-    SBR_HIP(hipMemcpyAsync(s->d_rows, rows.data(), rows.size() * sizeof(SesRow), hipMemcpyHostToDevice, st));
-    SBR_HIP(hipMemcpyAsync(s->d_ev_items, items, (size_t)total * sizeof(int), hipMemcpyHostToDevice, st));
-    if (second) SBR_HIP(hipMemcpyAsync(s->d_ev_second, second, (size_t)total * sizeof(int), hipMemcpyHostToDevice, st));
-    SesReplay a{};
-    a.n = (int)rows.size(); a.L = y.L; a.rows = s->d_rows;
-    a.items = s->d_ev_items; a.second = second ? s->d_ev_second : nullptr;
-    a.events = s->p.events; a.ring = s->p.ring; a.ring_len = s->p.ring_len;
-    for (int l = 0; l < y.L; ++l) a.ly[l] = ses_layer(s, l);
-    // ONE launch: the events of every layer, the event counts and the rings (ses_replay_kernel's end is the commit)
-    SBR_LAUNCH(launch_ses_replay(st, y.cfg.cell, a, y.E ? SES_IN_EMB : SES_IN_INDEX));
+    if ((rc = ses_replay_events(s, "sbr_sessions_replay", items, second, total)) != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(s->d_rows, rows.data(), rows.size() * sizeof(SesRow), hipMemcpyHostToDevice, h->stream));
+    SBR_LAUNCH(launch_ses_replay_rows(s, s->d_rows, (int)rows.size(), second != nullptr, nullptr, nullptr));
     h->last_replay_launches = 1;
     return SBR_OK;
 }

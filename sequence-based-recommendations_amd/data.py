@@ -629,6 +629,21 @@ class PositionEvaluator(object):
         self._hist.append(m + np.arange(int(off[-1]), dtype=np.int64) - np.repeat(off[:-1], n_pos))
         self._users += len(n_pos)
 
+    def add_events(self, rec, min_history=1):
+        """rec: what SessionPool.replay_ranks returned ({"off", "ranks", "n_rankable", "events_before"}): one pair per replayed
+        event, whose history length is the events its slot had in front of it (events_before -- not bounded by max_length: a
+        session has no window).  Pairs with fewer than min_history events in front of them are dropped."""
+        off = np.asarray(rec["off"], dtype=np.int64)
+        rank, nrk = np.asarray(rec["ranks"], dtype=np.int64), np.asarray(rec["n_rankable"], dtype=np.int64)
+        hist = np.asarray(rec["events_before"], dtype=np.int64)
+        if len(off) < 1 or not (len(rank) == len(nrk) == len(hist) == off[-1]) or np.any(hist < 0):
+            raise ValueError("rec must hold one rank, one n_rankable and one events_before per event of its off")
+        keep = hist >= int(min_history)
+        self._rank.append(rank[keep])
+        self._nrk.append(nrk[keep])
+        self._hist.append(hist[keep])
+        self._users += len(off) - 1
+
     def _flat(self):
         cat = lambda parts: np.concatenate(parts) if parts else np.zeros(0, np.int64)
         return cat(self._rank), cat(self._hist)

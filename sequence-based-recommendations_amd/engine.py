@@ -92,7 +92,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_evaluate_positions", "sbr_evaluate_candidates", "sbr_eval_negatives_host",
            "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
            "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load",
-           "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_reset", "sbr_sessions_advance", "sbr_sessions_replay", "sbr_sessions_adopt",
+           "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_reset", "sbr_sessions_advance", "sbr_sessions_replay", "sbr_sessions_replay_ranks", "sbr_sessions_adopt",
            "sbr_sessions_rank", "sbr_sessions_rank_candidates", "sbr_sessions_read", "sbr_sessions_write"]
 
 _lib = None
@@ -207,6 +207,7 @@ def load_library(path=None):
     lib.sbr_sessions_reset.argtypes = [vp, vp, ctypes.c_int64]
     lib.sbr_sessions_advance.argtypes = [vp, vp, vp, vp, ctypes.c_int64]
     lib.sbr_sessions_replay.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp]
+    lib.sbr_sessions_replay_ranks.argtypes = [vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int, ctypes.c_int64, vp, vp, vp]
     lib.sbr_sessions_adopt.argtypes = [vp, vp, ctypes.c_int32]
     lib.sbr_sessions_rank.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     lib.sbr_sessions_rank_candidates.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
@@ -1248,44 +1249,79 @@ class SessionPool(object):
         with self.engine.torch.cuda.device(self.engine.device):
             self._check(self.lib.sbr_sessions_advance(self.s, _ptr(slots), _ptr(items), _ptr(second), len(slots)))
 
-    def replay(self, slots, sequences, second=None):
-        """a run of events per named slot in one launch (sbr_sessions_replay): sequences[r], a 1-D id array of any length (and
-        second[r] of the same length, a model with n_feat == 2), is fed to slots[r] in order FROM THE SLOT'S KEPT STATE -- bit for
-        bit what one advance per event leaves.  This, not adopt, is the road for histories longer than max_length and for continuing
-        a kept state."""
+    @staticmethod
+    def _event_lists(what, slots, sequences, second):
+        """ragged lists -> the CSR of replay / replay_ranks: (slots, items, off, second)"""
         slots = _slot_list(slots)
         sequences = [_slot_list(q) for q in sequences]
         if len(sequences) != len(slots):
-            raise ValueError("replay: %d sequences for %d slots" % (len(sequences), len(slots)))
+            raise ValueError("%s: %d sequences for %d slots" % (what, len(sequences), len(slots)))
         off = np.zeros(len(slots) + 1, dtype=np.int64)
         np.cumsum([len(q) for q in sequences], out=off[1:])
         items = np.concatenate(sequences + [np.zeros(0, dtype=np.int32)]).astype(np.int32, copy=False)
         if second is not None:
             second = [_slot_list(q) for q in second]
             if len(second) != len(slots):
-                raise ValueError("replay: %d second-index sequences for %d slots" % (len(second), len(slots)))
+                raise ValueError("%s: %d second-index sequences for %d slots" % (what, len(second), len(slots)))
             for r, (a, b) in enumerate(zip(sequences, second)):
                 if len(a) != len(b):
-                    raise ValueError("replay: row %d has %d items and %d second indices" % (r, len(a), len(b)))
+                    raise ValueError("%s: row %d has %d items and %d second indices" % (what, r, len(a), len(b)))
             second = np.concatenate(second + [np.zeros(0, dtype=np.int32)]).astype(np.int32, copy=False)
-        self.replay_csr(slots, items, off, second)
+        return slots, items, off, second
+
+    @staticmethod
+    def _event_csr(what, slots, items, off, second):
+        """the CSR as the C-ABI takes it: converted to its types, contiguous, the lengths checked"""
+        slots, items = _slot_list(slots), _slot_list(items)
+        off = np.ascontiguousarray(np.asarray(off, dtype=np.int64).reshape(-1))
+        if len(off) != len(slots) + 1:
+            raise ValueError("%s: off must have %d entries (slots + 1), got %d" % (what, len(slots) + 1, len(off)))
+        if int(off.max()) > len(items):      # (the library reads items up to there; the order of off is its own check)
+            raise ValueError("%s: off reaches %d, but there are %d items" % (what, int(off.max()), len(items)))
+        if second is not None:
+            second = _slot_list(second)
+            if len(second) != len(items):
+                raise ValueError("%s: %d second indices for %d items" % (what, len(second), len(items)))
+        return slots, items, off, second
+
+    def replay(self, slots, sequences, second=None):
+        """a run of events per named slot in one launch (sbr_sessions_replay): sequences[r], a 1-D id array of any length (and
+        second[r] of the same length, a model with n_feat == 2), is fed to slots[r] in order FROM THE SLOT'S KEPT STATE -- bit for
+        bit what one advance per event leaves.  This, not adopt, is the road for histories longer than max_length and for continuing
+        a kept state."""
+        self.replay_csr(*self._event_lists("replay", slots, sequences, second))
 
     def replay_csr(self, slots, items, off, second=None):
         """sbr_sessions_replay with the lists as the C-ABI takes them: int32 ids, int64 offsets (len(slots) + 1, off[0] == 0,
         non-decreasing): items[off[r] : off[r + 1]] go to slots[r], oldest first"""
         self.engine._rank_local_flush("SessionPool.replay")
-        slots, items = _slot_list(slots), _slot_list(items)
-        off = np.ascontiguousarray(np.asarray(off, dtype=np.int64).reshape(-1))
-        if len(off) != len(slots) + 1:
-            raise ValueError("replay: off must have %d entries (slots + 1), got %d" % (len(slots) + 1, len(off)))
-        if int(off.max()) > len(items):      # (the library reads items up to there; the order of off is its own check)
-            raise ValueError("replay: off reaches %d, but there are %d items" % (int(off.max()), len(items)))
-        if second is not None:
-            second = _slot_list(second)
-            if len(second) != len(items):
-                raise ValueError("replay: %d second indices for %d items" % (len(second), len(items)))
+        slots, items, off, second = self._event_csr("replay", slots, items, off, second)
         with self.engine.torch.cuda.device(self.engine.device):
             self._check(self.lib.sbr_sessions_replay(self.s, _ptr(slots), len(slots), _ptr(items), _ptr(second), _ptr(off)))
+
+    def replay_ranks(self, slots, sequences, second=None, exclude=SESSION_EXCL_HISTORY, group_rows=0):
+        """replay() that also ranks every event before it is fed (sbr_sessions_replay_ranks): the pool is left exactly as replay
+        leaves it, and for event t of row r -- at off[r] + t of the flat result -- `ranks` holds the place of the item fed among the
+        scores rank(slots[r], exclude=exclude) would have ranked at that moment (-1: not rankable there), `n_rankable` the rankable
+        items, `events_before` the events the slot had in front of it (int64).  Equal, integer for integer, to the loop
+        "rank at k = n_items, find the item, advance"; group_rows bounds the scratch (0: the library's default) and changes nothing
+        else.  Returns {"off", "ranks", "n_rankable", "events_before"}."""
+        return self.replay_ranks_csr(*self._event_lists("replay_ranks", slots, sequences, second), exclude=exclude, group_rows=group_rows)
+
+    def replay_ranks_csr(self, slots, items, off, second=None, exclude=SESSION_EXCL_HISTORY, group_rows=0):
+        """sbr_sessions_replay_ranks with the lists as the C-ABI takes them (replay_csr's)"""
+        self.engine._rank_local_flush("SessionPool.replay_ranks")
+        slots, items, off, second = self._event_csr("replay_ranks", slots, items, off, second)
+        n, total = len(slots), int(off[-1])
+        ranks, nrk = np.empty(total, dtype=np.int32), np.empty(total, dtype=np.int32)
+        before = np.zeros(n, dtype=np.int64)
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._check(self.lib.sbr_sessions_replay_ranks(self.s, _ptr(slots), n, _ptr(items), _ptr(second), _ptr(off), int(exclude),
+                                                           int(group_rows), _ptr(ranks), _ptr(nrk), _ptr(before)))
+        lens = off[1:] - off[:-1]
+        # event t of row r had e0[r] + t events in front of it
+        events_before = np.repeat(before, lens) + np.arange(total, dtype=np.int64) - np.repeat(off[:-1], lens)
+        return {"off": off, "ranks": ranks, "n_rankable": nrk, "events_before": events_before}
 
     def adopt(self, slots):
         """rows 0 .. len(slots) - 1 of the engine's current batch become the named sessions: their state at the row's length from

@@ -589,6 +589,35 @@ class RNNBase(object):
             return None
         return self._whole_catalogue_position_evaluator(dataset, which, mode, min_history)
 
+    def native_event_evaluator(self, dataset, which, exclude, min_history=1, capacity=4096, history=None):
+        """The place of EVERY event of every sequence of dataset's "validation" / "test" set (two items or more, file order) among
+        the scores of the state kept in front of it -- the protocol of the session-based recommenders, on the arithmetic that
+        serves: a session pool (session_pool: `history` ids kept for the exclusion, default max_length), and per chunk of
+        `capacity` users reset, then SessionPool.replay_ranks of the users' WHOLE sequences, as a data.PositionEvaluator
+        (add_events: a pair's history length is the events in front of it, so positions beyond max_length are there).  exclude:
+        engine.SESSION_EXCL_*.  The models session_pool refuses -- cluster-ranked, data-parallel, bidirectional -- are refused
+        here with its reason; nothing else serves this."""
+        from .data import PositionEvaluator
+        gen = getattr(dataset, which + "_set")
+        if not hasattr(gen, "users"):
+            gen.load()
+        users = [u for u in range(len(gen.items)) if len(gen.items[u]) >= 2]      # SequenceGenerator's min_length = 2
+        pool = self.session_pool(int(capacity), history)
+        ev = PositionEvaluator()
+        try:
+            for lo in range(0, len(users), int(capacity)):
+                chunk = users[lo:lo + int(capacity)]
+                seqs = [np.asarray(gen.items[u], dtype=np.int32) for u in chunk]
+                second = None
+                if self.use_ratings_features:
+                    second = [np.array([self._get_features((0, r))[1] for r in gen.ratings[u]], dtype=np.int32) for u in chunk]
+                slots = np.arange(len(chunk), dtype=np.int32)
+                pool.reset(slots)
+                ev.add_events(pool.replay_ranks(slots, seqs, second, exclude=exclude), min_history=min_history)
+        finally:
+            pool.close()
+        return ev
+
     def native_candidate_evaluator(self, dataset, which, mode, n_negatives, seed=0, bias=None, k=10):
         """Every goal item of dataset's "validation" / "test" set ranked among n_negatives items its user never interacted with,
         drawn on the device from (seed, user id), from ONE engine call (RNNEngine.evaluate_candidates), as a

@@ -187,6 +187,41 @@ def run_position_tests(predictor, model_file, dataset, args, k=10, file=None, n_
     return ev
 
 
+def run_event_tests(predictor, model_file, dataset, args, k=10, file=None, n_batches=None):
+    """--by_event (no counterpart in the reference): the protocol of the session-based recommenders on the arithmetic that serves --
+    EVERY event of every test sequence, whatever its length, ranked from the state a session pool keeps in front of it
+    (RNNBase.native_event_evaluator, sbr_sessions_replay_ranks; no window of max_length); with unique interactions the last max_length
+    items fed are not ranked.  Prints evt_sps@k, evt_mrr, evt_ndcg@k and the number of events, and appends to `file`_by_event one
+    line per history length h, in the format of _by_position: n_batches, h, events, hits at k, sum of reciprocal ranks.  There is no
+    per-user road to fall back to: a model without a session pool ends the run with the reason."""
+    from .engine import SESSION_EXCL_HISTORY, SESSION_EXCL_NONE
+    if not hasattr(predictor, "native_event_evaluator"):
+        raise SystemExit("--by_event: %s has no native event evaluation" % type(predictor).__name__)
+    predictor.load(model_file)
+    min_history = int(getattr(args, "min_history", 1))
+    start = time.perf_counter()
+    try:
+        ev = predictor.native_event_evaluator(dataset, "test", SESSION_EXCL_HISTORY if predictor.interactions_are_unique else SESSION_EXCL_NONE,
+                                              min_history=min_history)
+    except (NotImplementedError, ValueError) as e:
+        raise SystemExit("--by_event needs a session pool of this model, and there is no other road: %s" % e)
+    if ev.n_positions() == 0:
+        raise SystemExit("--by_event: no test sequence has an event at --min_history %d" % min_history)
+    print("Timer (by event): ", time.perf_counter() - start)
+    print("evt_sps@" + str(k) + ": ", ev.hit_rate(k))
+    print("evt_mrr: ", ev.mrr())
+    print("evt_ndcg@" + str(k) + ": ", ev.ndcg(k))
+    print("events: ", ev.n_positions())
+    if file is not None:
+        if not os.path.exists(os.path.dirname(file)):
+            os.makedirs(os.path.dirname(file))
+        by = ev.by_history(k)
+        with open(file + "_by_event", "a") as f:
+            for h in np.nonzero(by["count"])[0].tolist():
+                f.write("\t".join(map(str, (n_batches, h, int(by["count"][h]), int(by["hits"][h]), float(by["rr"][h])))) + "\n")
+    return ev
+
+
 def run_sampled_tests(predictor, model_file, dataset, args, k=10, file=None, n_batches=None):
     """--sampled_negatives S (no counterpart in the reference): the protocol of the sequential-recommendation papers -- every goal item
     of every test user ranked among S items the user never interacted with, drawn on the device from (--negatives_seed, user id),
@@ -268,7 +303,11 @@ def test_command_parser(parser):                                      # test.py:
     parser.add_argument("--save_rank", help="Save the full comparison of goal and prediction ranking.", action="store_true")
     parser.add_argument("--by_position", help="Also rank the next item at every position of every test sequence (seq_sps, seq_mrr, seq_ndcg; "
                         "with --save, <results file>_by_position holds one line per history length).", action="store_true")
-    parser.add_argument("--min_history", help="With --by_position: the shortest history a position is evaluated at.", default=1, type=int)
+    parser.add_argument("--by_event", help="Also rank every event of every test sequence, of any length, from the state a session pool keeps "
+                        "in front of it (evt_sps, evt_mrr, evt_ndcg; with --save, <results file>_by_event holds one line per history length).",
+                        action="store_true")
+    parser.add_argument("--min_history", help="With --by_position / --by_event: the shortest history a position or event is evaluated at.",
+                        default=1, type=int)
     parser.add_argument("--sampled_negatives", help="Also rank every goal item among this many sampled items the user never interacted with "
                         "(sampled_sps, sampled_ndcg, sampled_recall, sampled_mrr; with --save, <results file>_sampled holds one line per "
                         "checkpoint).", default=0, type=int)
@@ -303,6 +342,8 @@ def main(argv=None):                                                  # test.py:
                 results.append((files[j], {m: ev.metrics[m]() for m in metrics}))
                 if getattr(args, "by_position", False):
                     run_position_tests(predictor, files[j], dataset, args, k=args.nb_of_predictions, file=output_file, n_batches=batches[j])
+                if getattr(args, "by_event", False):
+                    run_event_tests(predictor, files[j], dataset, args, k=args.nb_of_predictions, file=output_file, n_batches=batches[j])
                 if getattr(args, "sampled_negatives", 0):
                     run_sampled_tests(predictor, files[j], dataset, args, k=args.nb_of_predictions, file=output_file, n_batches=batches[j])
     else:
@@ -311,6 +352,8 @@ def main(argv=None):                                                  # test.py:
         results.append((files, {m: ev.metrics[m]() for m in metrics}))
         if getattr(args, "by_position", False):
             run_position_tests(predictor, files, dataset, args, k=args.nb_of_predictions, file=save_file_name(predictor, dataset, args))
+        if getattr(args, "by_event", False):
+            run_event_tests(predictor, files, dataset, args, k=args.nb_of_predictions, file=save_file_name(predictor, dataset, args))
         if getattr(args, "sampled_negatives", 0):
             run_sampled_tests(predictor, files, dataset, args, k=args.nb_of_predictions, file=save_file_name(predictor, dataset, args))
     return results
