@@ -165,7 +165,7 @@ def split_params(params, cell, layers, names_fn, embedding=0, bidirectional=Fals
 
 
 def network_cost(params, cfg, batch, names_fn, scripted=False):
-    """cost tensor of the whole network (rnn_one_hot.py:37-78 / rnn_sampling.py:93-137)."""
+    """cost tensor of the whole network (rnn_one_hot.py:37-78 / rnn_sampling.py:93-137 / rnn_margin.py:62-110)."""
     lf = layer_forward_scripted if scripted else layer_forward
     cell, layers, emb, bi = cfg["cell"], cfg["layers"], cfg.get("embedding", 0), cfg.get("bidirectional", False)
     per, W_out, b_out = split_params(params, cell, layers, names_fn, emb, bi)
@@ -196,6 +196,16 @@ def network_cost(params, cfg, batch, names_fn, scripted=False):
         elif reg < 0:
             cost = cost - reg * b_out.abs().sum()
         return cost, h, logits
+    if cfg["loss"] in ("hinge", "logit", "logsig"):     # RNNMargin (rnn_margin.py:62-69, :104-110): linear DenseLayer, dense (Y, weight)
+        p = h @ W_out + b_out
+        Y, Wt = batch["Y"], batch["weight"]
+        if cfg["loss"] == "hinge":
+            L = torch.relu((p - Y) * Wt).sum(dim=1)
+        elif cfg["loss"] == "logit":
+            L = (torch.sigmoid(p - Y) * Wt).sum(dim=1)
+        else:
+            L = -torch.log(torch.sigmoid((Y - p) * Wt)).sum(dim=1)
+        return L.mean(), h, p
     cells = torch.cat([batch["target"].long(), batch["samples"].long()])
     a = h @ W_out[:, cells] + b_out[cells]
     rows = torch.arange(B)

@@ -45,9 +45,29 @@ def rel_err(a, b, floor=1e-12):
     return float(np.abs(a - b).max() / (np.abs(b).max() + floor))
 
 
+def apply_trained(params, names, trained):
+    """Moves an initialisation-shaped parameter list (in place) to where training takes a model: trained = dict(bias_sd=, gain=, span=,
+    seed=).  A generator of its own walks the arrays in `names` order (O.model_param_shapes): every recurrent-layer bias gets
+    += N(0, bias_sd) (saturated gates), out.W *= gain (a peaked softmax), out.b += a Zipf log-popularity profile over `span` nats,
+    span * (-ln(1..N) / ln N) through a permutation drawn first.  W_in, W_hid, peepholes, initial states, embeddings and the cluster
+    arrays stay: at larger recurrent weights the recurrence is chaotic and no float32 computation is a yardstick any more."""
+    rng = np.random.default_rng(trained["seed"])
+    for name, p in zip(names, params):
+        layer, base = name.split(".")
+        if layer[0] == "l" and base.startswith("b_"):
+            p += rng.normal(0, trained["bias_sd"], size=p.shape)
+        elif name == "out.W":
+            p *= trained["gain"]
+        elif name == "out.b":
+            n = p.shape[0]
+            perm = rng.permutation(n)
+            p += trained["span"] * (-np.log(np.arange(1, n + 1)) / np.log(n))[perm]
+    return params
+
+
 def build_case(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, full=False, scale=None, popscale=1.0, emb=0, bi=False,
-               zipf=False, clusters=None):
-    """clusters: dict(n=, type="mix" | "softmax" | "sigmoid", scale=, c_sampling=0) -> an RNNCluster case (rnn_cluster.py): the
+               zipf=False, clusters=None, trained=None):
+    """trained: see apply_trained (None: a model at initialisation, every parameter moved off zero by N(0, scale)).  clusters: dict(n=, type="mix" | "softmax" | "sigmoid", scale=, c_sampling=0) -> an RNNCluster case (rnn_cluster.py): the
     parameter list gains the repartition R (N, n) and the selection weights Wc (H_top, n), the batch its cluster samples"""
     if scale is None:      # a tanh-only cell with wide layers is chaotic at large weights: keep it well conditioned
         scale = 0.3 if (cell != "Vanilla" or max(layers) <= 64) else 0.05
@@ -55,6 +75,8 @@ def build_case(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, full=Fals
     params = O.init_params(cell, layers, N, rng, n_in0=N + n_opt, embedding=emb, n_feat=F, bidirectional=bi)
     for p in params:                      # move every parameter (biases, inits, peepholes) off zero
         p += rng.normal(0, scale, size=p.shape)
+    if trained is not None:
+        apply_trained(params, [n for n, _ in O.model_param_shapes(cell, layers, N, N + n_opt, emb, F, bi)], trained)
     params = [p.astype(np.float32).astype(np.float64) for p in params]
     batch = make_batch(rng, B, T, N, S=S, F=F, n_in0=N + n_opt, full=full, zipf=zipf)
     batch["pop"] = (batch["pop"] * popscale).astype(np.float32)
@@ -145,11 +167,28 @@ def params_ok(r, steps=2, bar=1e-3, tol_g=1e-4):
     return True
 
 
+def separated_rows(ologits, excl, k, gap, margin=False):
+    """the rows compare_step compares ranked ids on: all of them, or with gap > 0 those whose k + 1 best admissible oracle logits
+    are pairwise further apart than `gap`"""
+    rows = np.ones(len(ologits), dtype=bool)
+    if gap > 0.0:
+        for b in range(len(ologits)):
+            row = ologits[b].copy()
+            row[np.asarray(excl[b], dtype=np.int64)] = 0.0 if margin else -np.inf
+            top = -np.sort(-row)[:k + 1]
+            rows[b] = bool(np.all(top[:-1] - top[1:] > gap))
+    return rows
+
+
 def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater="adam", flags=0, full=False,
                  reg=0.0, steps=2, popscale=1.0, scale=None, emb=0, bi=False, zipf=False, k=None, gap=0.0, tweak=None,
                  balance=1.0, unique=True, default_target=None, grad_floor=1e-12, queries=(), queries_after=(), lr=0.01, rho=0.9,
-                 beta1=0.9, beta2=0.999):
+                 beta1=0.9, beta2=0.999, trained=None, log_extra=None):
     """Returns dict of relative errors (engine float32 vs oracle float64).
+    trained: build_case's (apply_trained); the result then also says whether the engine's numbers are sane at all -- "cost_value",
+    "grads_nonfinite" (NaN / inf elements over every gradient array), "predict_nonfinite", and for the softmax head
+    "predict_min" / "predict_rowsum_err" (a row of probabilities: non-negative, sums to 1).
+    log_extra: a dict that joins the SBR_PARITY_LOG line of this comparison.
     grad_floor: added to the largest oracle magnitude of a gradient array before dividing -- arrays far smaller than it are
     compared absolutely (the fp16 split of the BPTT chain's gradient operand has an absolute floor, csrc/sbr_rec_p.hip).
     k: length of the ranked list compared (default min(5, N - T)); gap > 0: the ranked ids are compared on the rows
@@ -157,7 +196,7 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
     assertion, `topk_rows_compared` reports how many rows that is; tweak(batch): edits the batch in place (e.g. plants
     duplicate sampled cells)."""
     params, cfg, batch = build_case(cell, layers, loss, N, B, T, S=S, seed=seed, F=F, n_opt=n_opt, full=full,
-                                    popscale=popscale, scale=scale, emb=emb, bi=bi, zipf=zipf)
+                                    popscale=popscale, scale=scale, emb=emb, bi=bi, zipf=zipf, trained=trained)
     if tweak is not None:
         tweak(batch)
     cfg["regularization"] = reg
@@ -196,6 +235,9 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
             out["grad:" + n] = e
             worst = max(worst, e)
         out["grad_worst"] = worst
+        if trained is not None:
+            out["cost_value"] = float(cost)
+            out["grads_nonfinite"] = float(sum(int((~np.isfinite(g)).sum()) for g in grads))
         # a few optimizer steps on the same batch
         upd = O.Updater(updater, lr, rho=rho, beta1=beta1, beta2=beta2)
         oparams = [p.copy() for p in params]
@@ -232,19 +274,18 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
         scores = eng.predict_function(batch["X"], batch["mask"])
         oscores, ologits = O.predict_scores(oparams, cfg, batch["X"], batch["mask"])
         out["predict_scores"] = rel_err(scores, oscores)
+        if trained is not None:
+            out["predict_nonfinite"] = float((~np.isfinite(scores)).sum())
+            if loss == "CCE":
+                out["predict_min"] = float(np.min(scores))
+                out["predict_rowsum_err"] = float(np.abs(np.asarray(scores, dtype=np.float64).sum(axis=1) - 1.0).max())
         if k is None:
             k = min(5, N - T) if N - T >= 1 else 1
         # (RNNMargin: the compiled test function's semantics, a viewed item scores 0: exclude mode 2)
         ids = eng.test_function((batch["X"], batch["mask"]), k=k, exclude_seen=2 if margin else True)
         excl = [[int(i) for i in batch["X"][b, :int(batch["mask"][b].sum()), 0]] for b in range(B)]
         oids = O.test_function(oparams, cfg, batch["X"], batch["mask"], excl, k=k)
-        rows = np.ones(B, dtype=bool)
-        if gap > 0.0:      # rows whose k + 1 best admissible logits are pairwise further apart than `gap`
-            for b in range(B):
-                row = ologits[b].copy()
-                row[np.asarray(excl[b], dtype=np.int64)] = 0.0 if margin else -np.inf
-                top = -np.sort(-row)[:k + 1]
-                rows[b] = bool(np.all(top[:-1] - top[1:] > gap))
+        rows = separated_rows(ologits, excl, k, gap, margin)
         oids = np.array(oids)
         for b in range(B):      # a row with fewer than k rankable items: the engine fills the places it cannot rank with -1
             if not margin:
@@ -257,6 +298,7 @@ def compare_step(cell, layers, loss, N, B, T, S=0, seed=0, F=1, n_opt=0, updater
     if log:
         with open(log, "a") as f:
             f.write(json.dumps(dict(case=dict(cell=cell, layers=list(layers), loss=loss, N=N, B=B, T=T, S=S, updater=updater,
-                                              full=bool(full), zipf=bool(zipf), steps=steps, k=k, gap=gap),
-                                    **{kk: float(v) for kk, v in out.items()})) + "\n")
+                                              full=bool(full), zipf=bool(zipf), steps=steps, k=k, gap=gap,
+                                              **(dict(trained=trained, flags=flags, emb=emb, bi=bool(bi)) if trained else {})),
+                                    **(log_extra or {}), **{kk: float(v) for kk, v in out.items()})) + "\n")
     return out

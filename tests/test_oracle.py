@@ -231,6 +231,29 @@ def test_margin_head_gradients_against_finite_differences(loss):
             assert abs(num - grads[pi][idx]) <= 1e-6 * max(1.0, abs(num)), (pi, idx, num, grads[pi][idx])
 
 
+@pytest.mark.parametrize("cell", ["LSTM", "GRU", "Vanilla"])
+@pytest.mark.parametrize("layers", [[4], [5, 3]])
+@pytest.mark.parametrize("loss", ["hinge", "logit", "logsig"])
+@pytest.mark.parametrize("unique", [True, False])
+def test_margin_heads_numpy_bptt_matches_torch_autograd(cell, layers, loss, unique):
+    """the margin heads of the torch restatement (the float32 yardstick of tests/trained_shape.py) against the oracle, as
+    test_numpy_bptt_matches_torch_autograd holds the other four: rows with one to three positives, one repeated, one that is also
+    an input item, a popularity-based default target"""
+    import parity_util as PU
+    N, B, T = 23, 5, 6
+    params, cfg, batch = PU.build_case(cell, layers, loss, N, B, T, S=3, seed=11)
+    dflt = O.margin_default_target(np.random.default_rng(3).integers(1, 40, size=N), 50, 0.1)
+    ob = PU.margin_oracle_batch(batch, N, balance=1.5, unique=unique, default_target=dflt)
+    c1, g1, aux = O.cost_and_grads(params, cfg, ob)
+    c2, g2, h2, a2 = R.cost_and_grads(params, cfg, ob, O.recurrent_param_shapes)
+    assert abs(c1 - c2) <= 1e-10 * abs(c2)
+    assert np.allclose(aux["h"], h2, rtol=0, atol=1e-12) and np.allclose(aux["act"], a2, rtol=0, atol=1e-12)
+    assert max(np.abs(g).max() for g in g2[-2:]) > 0
+    for a, b in zip(g1, g2):
+        assert a.shape == b.shape
+        assert np.abs(a - b).max() <= 1e-10 * max(1.0, np.abs(b).max())
+
+
 @pytest.mark.parametrize("cell,H", [("LSTM", 20), ("GRU", 32)])
 def test_scripted_cpu_port_equals_the_eager_port(cell, H):
     """bench.py's cpu_baseline times the torch port with its T-step scan under torch.jit.script (oracle/torch_ref.py,
