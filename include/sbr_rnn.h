@@ -827,8 +827,43 @@ int sbr_dataset_state_load(sbr_dataset* d, const void* blob_host, size_t bytes);
  *   read     slot's state in `layer`: h_host / c_host [Hp] floats (Hp = the layer's padded width: 16 / 32 / 64 / 128 / 256 / 512,
  *            above that the next multiple of 64; c_host is written for LSTM only), *events, history_host [history]: the last
  *            min(events, history) ids, oldest first, then -1.  Any output may be NULL.
- *   write    puts h_host (and c_host, LSTM) back as slot's state in `layer`; events and ring stay.  read / write are the hooks for
- *            evicting and restoring sessions.
+ *   write    puts h_host (and c_host, LSTM) back as slot's state in `layer`; events and ring stay.  read / write move ONE layer's
+ *            state of ONE slot and nothing else (a slot restored with write keeps the event count, the ring and the plane parity of
+ *            whoever held it before, and each call waits twice): the hooks for evicting and restoring sessions are export / import.
+ *
+ * The record of a parked session (record version 1; little-endian, as the machine has it) -- one session off the device:
+ *     int64   events
+ *     int32   ids[ring_len]     ring_len = max(history, 1): the last min(events, ring_len) ids fed, OLDEST FIRST, then -1
+ *             (zeros up to a multiple of 16 bytes)
+ *     per layer l = 0 .. L-1:
+ *     float   h[Hp_l]           the slot's CURRENT plane (plane events & 1), padded units as the pool keeps them
+ *     float   c[Hp_l]           LSTM only
+ * record_bytes is a multiple of 16.  The ids stand in canonical order, as read returns them, not as the ring lies in memory, and the
+ * record holds no plane parity: it means the same in every slot of every pool of the same layout.  It holds states, not weights: like
+ * the pool, it goes on under whatever parameters the engine has.  The layout fingerprint is FNV-1a (64 bit, offset basis
+ * 0xcbf29ce484222325, prime 0x100000001b3) over the 32-bit little-endian words (1, cell, L, Hp_0 .. Hp_{L-1}, ring_len).
+ *
+ *   record_layout   (sbr_sessions_record_layout) record_bytes and the fingerprint for a config and a `history`: pure host code, no
+ *            device and no pool (as sbr_arena_bytes).  SBR_EINVAL with the reason: what sbr_create refuses about the config, a
+ *            bidirectional config, history < 0.
+ *   export   (sbr_sessions_export) the record of slots[r] to records_host + r * record_bytes, n of them (the slots may repeat: the call
+ *            only reads the pool).  ses_pack_kernel (sbr_session.hip) reads each slot's event count ON THE DEVICE, takes plane
+ *            events & 1 of every layer and puts the ring in canonical order, into the pool's staging buffer; one device-to-host copy
+ *            per chunk follows and ONE wait at the end.  cap: the bytes records_host holds; cap < n * record_bytes is SBR_EINVAL.
+ *   import   (sbr_sessions_import) the inverse: slot slots[r] (distinct) takes record r -- ses_unpack_kernel sets its event count, writes
+ *            h (and c) of every layer to plane events & 1 (the other plane is left alone: nothing reads it before a step writes it)
+ *            and rewrites its WHOLE ring: id t of the record at place (events - kept + t) % ring_len, kept = min(events, ring_len),
+ *            -1 at every other place.  Nothing of the former occupant survives: afterwards the slot is indistinguishable, through
+ *            every call of the pool, from the slot the record was exported from.  Returns when records_host may be reused (pageable
+ *            host memory), without waiting for the kernel.  SBR_EINVAL, found on the host before anything is launched, the pool
+ *            untouched, the offender named: bytes != n * record_bytes, n above capacity, a slot named twice, events < 0, among the first
+ *            `kept` ids one outside [0, input_size), anything but -1 behind them.  The floats are not inspected (as write's are not).
+ *   Both run on the engine's stream, return SBR_ESTATE inside an open training step or with a lagged cost pending, and read and write
+ *   NOTHING in the arena -- no parameter, no batch buffer, no flush of lazily stepped rows: a training run with parks in it is the run
+ *   without them.  n == 0 does nothing.  chunk_slots > 0: the most records staged on the device at once; 0: as many as fit 64 MB;
+ *   < 0: SBR_EINVAL.  It bounds the staging buffer and NOTHING else: no byte of the result or of the pool depends on it.  The staging
+ *   buffer belongs to the pool, grows when a call needs more and is kept (SBR_ENOMEM before anything is launched; replay's caveat
+ *   about hipFree holds).  sbr_query "session_park_chunks": the chunks of the most recent export or import on the engine.
  * SBR_EINVAL, found on the host before anything is launched, the pool untouched, the offender named: a slot outside [0, capacity), a
  * slot named twice in one advance / replay / adopt / reset, an id outside [0, input_size), `second` missing with n_feat == 2 or given
  * with n_feat == 1, n above capacity (advance, replay) or n_rows above the batch's rows (adopt), off not starting at 0 or decreasing, k, exclude_mode or lists as sbr_rank rejects them,
@@ -855,6 +890,9 @@ int  sbr_sessions_rank_candidates(sbr_sessions* s, const int32_t* slots, int64_t
                                   const int32_t* excl_ids, const int64_t* excl_off, int32_t* ids_host, float* scores_host);
 int  sbr_sessions_read(sbr_sessions* s, int32_t slot, int32_t layer, float* h_host, float* c_host, int64_t* events, int32_t* history_host);
 int  sbr_sessions_write(sbr_sessions* s, int32_t slot, int32_t layer, const float* h_host, const float* c_host);
+int  sbr_sessions_record_layout(const sbr_config* cfg, int32_t history, size_t* record_bytes, uint64_t* fingerprint);
+int  sbr_sessions_export(sbr_sessions* s, const int32_t* slots, int64_t n, int64_t chunk_slots, void* records_host, size_t cap);
+int  sbr_sessions_import(sbr_sessions* s, const int32_t* slots, int64_t n, int64_t chunk_slots, const void* records_host, size_t bytes);
 
 #ifdef __cplusplus
 }

@@ -998,6 +998,8 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     else if (w == "cand_rank_form") *value = h->last_cand_rank_form;
     // the kernel launches the LAST sbr_sessions_replay of any pool on this engine enqueued: 1 (0: no events, or none yet)
     else if (w == "session_replay_launches") *value = h->last_replay_launches;
+    // the chunks the LAST sbr_sessions_export / sbr_sessions_import of any pool on this engine staged (0: n == 0, refused, or none yet)
+    else if (w == "session_park_chunks") *value = h->last_park_chunks;
     // the LAST sbr_sessions_replay_ranks of any pool on this engine: its passes (tracing replay launches; 0: no events, or none yet), and
     // how its counting kernel read the score rows: 1 in 16-byte loads, 2 in 4-byte loads (N no multiple of 4), 0 none yet
     else if (w == "session_replay_rank_passes") *value = h->last_replay_rank_passes;

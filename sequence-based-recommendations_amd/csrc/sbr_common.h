@@ -430,6 +430,7 @@ struct sbr_handle {
     int last_next_rank_slots = 0;                                         // ... and the positions it projected per GEMM launch at the most
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_replay_launches = 0;                                         // sbr_sessions_replay: the kernel launches the most recent one enqueued
+    int last_park_chunks = 0;                                             // sbr_sessions_export / _import: the chunks the most recent one staged
     int last_replay_rank_passes = 0, last_event_rank_form = 0;            // sbr_sessions_replay_ranks: the passes (tracing replay launches) of the most recent call; its count's loads as last_next_rank_form
     int last_cand_rank_form = 0;                                          // sbr_rank_candidates / sbr_sessions_rank_candidates: 0 none yet, 1 only the candidates scored, 2 gathered from the full scores
     int last_eval_cand_form = 0, last_eval_cand_lmax = 0;                 // sbr_evaluate_candidates: the same two forms (0 none yet); the width of the last chunk's compact score matrix
@@ -497,6 +498,9 @@ struct SesPool {                                     // what the kernels read: p
     long long* events;                               // [capacity] events fed
     int* ring;                                       // [capacity][ring_len]: the id of event e at e % ring_len (ring_len = max(history, 1))
 };
+// A parked session (include/sbr_rnn.h "The record of a parked session"): int64 events, int32 ids[ring_len]
+// oldest first then -1, zeros up to `head` (a multiple of 16 bytes), then per layer h[Hp] (and c[Hp], LSTM) of the CURRENT plane
+struct SesRecLayout { size_t bytes, head; int L, ring_len, lstm; int Hp[SBR_MAX_LAYERS]; };
 struct SesRow { long long start, len; int slot; };   // a row of sbr_sessions_replay: items[start .. start + len) go to slot
 // beside a SesRow of a tracing pass (sbr_sessions_replay_ranks): the state before its event t goes to row at + t of the pass's trace;
 // first: where the row's list starts in the call's events (event t of the pass is event start + t - first of the call); call_row:
@@ -511,6 +515,10 @@ struct sbr_sessions {
     SesRow* d_rows; int *d_ev_items, *d_ev_second; long long ev_cap;
     std::vector<SesRow> rows;
     std::vector<unsigned> stamp; unsigned epoch;     // host: stamp[slot] == epoch: the slot was already named in this call
+    // sbr_sessions_export / _import: the record layout of this pool and the staging buffer of the chunk in flight (park_cap bytes:
+    // the chunk's records, then its slot list; grown when a call needs more and kept)
+    SesRecLayout rec; unsigned char* d_park; size_t park_cap;
+    std::vector<int> park_ids;                       // host: the ids of the record import is checking
 };
 // sbr_session.hip: the kernels behind the calls.  Every slot, id and row count was checked on the host
 hipError_t launch_ses_reset(hipStream_t s, const SesPool& p, const sbr_handle* h, const int* slots, long long n);

@@ -1,6 +1,7 @@
 // Stateful sessions (include/sbr_rnn.h "Stateful sessions"; DESIGN.md sections 3o and 3r): a pool of kept recurrent states beside the
 // engine, one recurrent step per event.  sbr_sessions_create / destroy / reset / advance / replay / adopt / read / write and their kernels; the
-// ranking call sbr_sessions_rank is an entry to sbr_rank's pipeline and lives with it (sbr_rank_api.hip).
+// ranking call sbr_sessions_rank is an entry to sbr_rank's pipeline and lives with it (sbr_rank_api.hip).  Parking -- the record of a
+// session off the device, sbr_sessions_record_layout / export / import and their two kernels -- is at the end.
 //
 // The step (ses_step_kernel; its tile computation, ses_tile, is shared with ses_replay_kernel below), one launch per layer: for the
 // rows r < n of a call, s = slots[r],
@@ -28,6 +29,7 @@
 #include "sbr_common.h"
 #include "sbr_cell.h"
 #include <algorithm>
+#include <cstring>
 #include <new>
 
 namespace {
@@ -345,6 +347,74 @@ __global__ void __launch_bounds__(256) ses_adopt_kernel(SesPool p, SesAdopt b, S
     if (threadIdx.x == 0) p.events[s] = len;
 }
 
+// Parking (sbr_sessions_export / sbr_sessions_import): records [n][y.bytes] in a staging buffer <-> the slots
+// slots[0 .. n).  `tps` threads (16 / 64 / 256, chosen on the host by the size of a record's state part) own one record, so a
+// workgroup moves 256 / tps of them: a GRU-16 record (64 bytes of state) takes 16 threads, a two-layer LSTM-512 one (8 KB) the whole
+// workgroup.  The state part moves in 16-byte pieces, thread t of a record the pieces t, t + tps, ... of every row, each byte read and
+// written once (the records start on 16 bytes: the staging buffer does, y.bytes and y.head are multiples of 16, Hp is one of 16 floats).
+// Both read the slot's event count where it decides the plane: pack from the pool, unpack from the record.
+//
+// pack: the record is CANONICAL -- id t of it is the id at ring place (events - kept + t) % ring_len, kept = min(events, ring_len),
+// then -1 and zeros up to y.head; the states come from plane events & 1 of every layer.  It only reads the pool.
+__global__ void __launch_bounds__(256) ses_pack_kernel(SesPool p, SesRecLayout y, const int* __restrict__ slots, int n, int tps,
+                                                        unsigned char* __restrict__ out) {
+    const int t = threadIdx.x % tps;
+    const long long r = (long long)blockIdx.x * (256 / tps) + threadIdx.x / tps;
+    if (r >= n) return;                                  // (no barrier in this kernel)
+    const int s = slots[r];
+    const long long ev = p.events[s];
+    unsigned char* rec = out + (size_t)r * y.bytes;
+    if (t == 0) *(long long*)rec = ev;
+    const long long kept = min(ev, (long long)y.ring_len);
+    const int* ring = p.ring + (size_t)s * y.ring_len;
+    int* ids = (int*)(rec + 8);
+    for (int i = t; i < (int)(y.head - 8) / 4; i += tps)
+        ids[i] = i < kept ? ring[(int)((ev - kept + i) % y.ring_len)] : (i < y.ring_len ? -1 : 0);
+    float* dst = (float*)(rec + y.head);
+    for (int l = 0; l < y.L; ++l) {
+        const int Hp = y.Hp[l];
+        const size_t at = ((size_t)(ev & 1) * p.capacity + s) * Hp;
+        for (int u = 4 * t; u < Hp; u += 4 * tps) *(f32x4*)(dst + u) = *(const f32x4*)(p.hs[l] + at + u);
+        dst += Hp;
+        if (!y.lstm) continue;
+        for (int u = 4 * t; u < Hp; u += 4 * tps) *(f32x4*)(dst + u) = *(const f32x4*)(p.cs[l] + at + u);
+        dst += Hp;
+    }
+}
+
+// unpack, the inverse: the slot takes the record's event count, its states into plane events & 1 of every layer (the other plane is
+// left alone: nothing reads it before a step writes it), and its WHOLE ring: place j holds id t of the record where
+// (events - kept + t) % ring_len == j and t < kept, -1 otherwise -- nothing of the former occupant survives.  The slots of a call are
+// distinct and every count and id was checked on the host.
+__global__ void __launch_bounds__(256) ses_unpack_kernel(SesPool p, SesRecLayout y, const int* __restrict__ slots, int n, int tps,
+                                                          const unsigned char* __restrict__ in) {
+    const int t = threadIdx.x % tps;
+    const long long r = (long long)blockIdx.x * (256 / tps) + threadIdx.x / tps;
+    if (r >= n) return;
+    const int s = slots[r];
+    const unsigned char* rec = in + (size_t)r * y.bytes;
+    const long long ev = *(const long long*)rec;
+    if (t == 0) p.events[s] = ev;
+    const long long kept = min(ev, (long long)y.ring_len);
+    const int first = (int)((ev - kept) % y.ring_len);      // the ring place of the record's id 0
+    const int* ids = (const int*)(rec + 8);
+    int* ring = p.ring + (size_t)s * y.ring_len;
+    for (int j = t; j < y.ring_len; j += tps) {
+        const int i = (j - first + y.ring_len) % y.ring_len;
+        ring[j] = i < kept ? ids[i] : -1;
+    }
+    const float* src = (const float*)(rec + y.head);
+    for (int l = 0; l < y.L; ++l) {
+        const int Hp = y.Hp[l];
+        const size_t at = ((size_t)(ev & 1) * p.capacity + s) * Hp;
+        for (int u = 4 * t; u < Hp; u += 4 * tps) *(f32x4*)(p.hs[l] + at + u) = *(const f32x4*)(src + u);
+        src += Hp;
+        if (!y.lstm) continue;
+        for (int u = 4 * t; u < Hp; u += 4 * tps) *(f32x4*)(p.cs[l] + at + u) = *(const f32x4*)(src + u);
+        src += Hp;
+    }
+}
+
 __global__ void __launch_bounds__(256) ses_gather_top_kernel(SesPool p, const int* __restrict__ slots, float* __restrict__ out) {
     const int r = blockIdx.x, s = slots[r], l = p.L - 1, Hp = p.Hp[l];
     const float* src = p.hs[l] + ((size_t)(p.events[s] & 1) * p.capacity + s) * Hp;
@@ -420,6 +490,7 @@ void ses_free(sbr_sessions* s) {
     if (s->d_rows) (void)hipFree(s->d_rows);
     if (s->d_ev_items) (void)hipFree(s->d_ev_items);
     if (s->d_ev_second) (void)hipFree(s->d_ev_second);
+    if (s->d_park) (void)hipFree(s->d_park);
     delete s;
 }
 
@@ -459,6 +530,25 @@ hipError_t launch_ses_keep(hipStream_t st, const SesPool& p, const int* slots, l
     return hipGetLastError();
 }
 
+// The record of a parked session for this engine and ring (include/sbr_rnn.h): pure host arithmetic
+static SesRecLayout ses_record_layout(const Layout& y, int history) {
+    SesRecLayout r{};
+    r.L = y.L; r.ring_len = std::max(history, 1); r.lstm = y.cfg.cell == SBR_CELL_LSTM ? 1 : 0;
+    r.head = (8 + (size_t)4 * r.ring_len + 15) / 16 * 16;
+    r.bytes = r.head;
+    for (int l = 0; l < y.L; ++l) { r.Hp[l] = y.layer[l].Hp; r.bytes += (size_t)r.Hp[l] * sizeof(float) * (r.lstm ? 2 : 1); }
+    return r;
+}
+// FNV-1a, 64 bit, over the 32-bit little-endian words (record version 1, cell, L, Hp_0 .. Hp_{L-1}, ring_len)
+static uint64_t ses_record_fingerprint(const SesRecLayout& r, int cell) {
+    uint64_t f = 0xcbf29ce484222325ull;
+    auto word = [&](uint32_t w) { for (int b = 0; b < 4; ++b) { f ^= (w >> (8 * b)) & 0xffu; f *= 0x100000001b3ull; } };
+    word(1u); word((uint32_t)cell); word((uint32_t)r.L);
+    for (int l = 0; l < r.L; ++l) word((uint32_t)r.Hp[l]);
+    word((uint32_t)r.ring_len);
+    return f;
+}
+
 // the calls keep out of a training step in flight: its side streams read and write the parameters (as the state calls do)
 int sessions_state_check(const sbr_sessions* s, const char* call) {
     const sbr_handle* h = s->h;
@@ -493,6 +583,7 @@ extern "C" int sbr_sessions_create(sbr_handle* h, int64_t capacity, int32_t hist
     s->d_rows = nullptr; s->d_ev_items = s->d_ev_second = nullptr; s->ev_cap = 0;
     s->epoch = 0;
     s->stamp.assign((size_t)capacity, 0u);
+    s->rec = ses_record_layout(y, history); s->d_park = nullptr; s->park_cap = 0;
     int rc = SBR_OK;
     for (int l = 0; l < y.L && rc == SBR_OK; ++l) {
         s->p.Hp[l] = y.layer[l].Hp;
@@ -729,5 +820,125 @@ extern "C" int sbr_sessions_write(sbr_sessions* s, int32_t slot, int32_t layer, 
     SBR_HIP(hipMemcpyAsync(s->p.hs[layer] + at, h_host, row, hipMemcpyHostToDevice, st));
     if (s->p.cs[layer]) SBR_HIP(hipMemcpyAsync(s->p.cs[layer] + at, c_host, row, hipMemcpyHostToDevice, st));
     SBR_HIP(hipStreamSynchronize(st));
+    return SBR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- parking
+extern "C" int sbr_sessions_record_layout(const sbr_config* cfg, int32_t history, size_t* record_bytes, uint64_t* fingerprint) {
+    CHECK_ARG(cfg && record_bytes && fingerprint, "null argument");
+    Layout lay; std::string err;
+    if (sbr_build_layout(*cfg, lay, err) != SBR_OK) { sbr_set_error("%s", err.c_str()); return SBR_EINVAL; }
+    CHECK_ARG(lay.D == 1, "sbr_sessions_record_layout: a bidirectional engine has no state that has seen only the first p items");
+    CHECK_ARG(history >= 0, "sbr_sessions_record_layout: history=%d is negative", history);
+    const SesRecLayout r = ses_record_layout(lay, history);
+    *record_bytes = r.bytes;
+    *fingerprint = ses_record_fingerprint(r, lay.cfg.cell);
+    return SBR_OK;
+}
+
+// The staging of one export / import: how many records a chunk holds, the buffer grown to hold them and their slot list (the old one
+// is freed first, and hipFree waits for the device: replay's caveat), the threads per record.  Before anything is launched.
+struct SesPark { int64_t chunk; size_t slots_at; int tps; };
+static int ses_park_stage(sbr_sessions* s, const char* call, int64_t n, int64_t chunk_slots, SesPark* out) {
+    const SesRecLayout& y = s->rec;
+    int64_t chunk = chunk_slots > 0 ? chunk_slots : std::max<int64_t>(1, (int64_t)(((size_t)64 << 20) / y.bytes));
+    chunk = std::min(chunk, n);
+    const size_t slots_at = (size_t)chunk * y.bytes, need = slots_at + ((size_t)chunk * sizeof(int) + 15) / 16 * 16;
+    if (need > s->park_cap) {
+        if (s->d_park) (void)hipFree(s->d_park);
+        s->d_park = nullptr; s->park_cap = 0;
+        int rc;
+        if ((rc = ses_alloc(&s->d_park, need, "the staging buffer", call)) != SBR_OK) return rc;
+        s->park_cap = need;
+    }
+    const size_t pieces = (y.bytes - y.head) / 16;
+    out->chunk = chunk; out->slots_at = slots_at;
+    out->tps = pieces <= 32 ? 16 : (pieces <= 256 ? 64 : 256);
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_export(sbr_sessions* s, const int32_t* slots, int64_t n, int64_t chunk_slots, void* records_host, size_t cap) {
+    CHECK_ARG(s, "null argument");
+    sbr_handle* h = s->h;
+    const SesRecLayout& y = s->rec;
+    int rc;
+    if ((rc = sessions_state_check(s, "sbr_sessions_export")) != SBR_OK) return rc;
+    h->last_park_chunks = 0;
+    CHECK_ARG(n >= 0 && n <= 0x7fffffff, "sbr_sessions_export: n=%lld outside [0,2^31)", (long long)n);
+    CHECK_ARG(chunk_slots >= 0, "sbr_sessions_export: chunk_slots=%lld is negative", (long long)chunk_slots);
+    if (n == 0) return SBR_OK;
+    CHECK_ARG(slots && records_host, "null argument");
+    CHECK_ARG(cap >= (size_t)n * y.bytes, "sbr_sessions_export: cap=%zu is below n * record_bytes = %lld * %zu = %zu", cap, (long long)n,
+              y.bytes, (size_t)n * y.bytes);
+    if ((rc = sessions_check_slots(s, "sbr_sessions_export", slots, n, false)) != SBR_OK) return rc;
+    SesPark pk;
+    if ((rc = ses_park_stage(s, "sbr_sessions_export", n, chunk_slots, &pk)) != SBR_OK) return rc;
+    hipStream_t st = h->stream;
+    int* d_slots = (int*)(s->d_park + pk.slots_at);
+    int chunks = 0;
+    for (int64_t r0 = 0; r0 < n; r0 += pk.chunk, ++chunks) {
+        const int m = (int)std::min(pk.chunk, n - r0);
+        // (the stream orders this chunk's kernel behind the copy that empties the buffer of the chunk before it)
+        SBR_HIP(hipMemcpyAsync(d_slots, slots + r0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+        const int per = 256 / pk.tps;
+        ses_pack_kernel<<<(unsigned)((m + per - 1) / per), 256, 0, st>>>(s->p, y, d_slots, m, pk.tps, s->d_park);
+        SBR_LAUNCH(hipGetLastError());
+        SBR_HIP(hipMemcpyAsync((unsigned char*)records_host + (size_t)r0 * y.bytes, s->d_park, (size_t)m * y.bytes, hipMemcpyDeviceToHost, st));
+    }
+    SBR_HIP(hipStreamSynchronize(st));
+    h->last_park_chunks = chunks;
+    return SBR_OK;
+}
+
+extern "C" int sbr_sessions_import(sbr_sessions* s, const int32_t* slots, int64_t n, int64_t chunk_slots, const void* records_host, size_t bytes) {
+    CHECK_ARG(s, "null argument");
+    sbr_handle* h = s->h;
+    const SesRecLayout& y = s->rec;
+    int rc;
+    if ((rc = sessions_state_check(s, "sbr_sessions_import")) != SBR_OK) return rc;
+    h->last_park_chunks = 0;
+    CHECK_ARG(n >= 0 && n <= s->p.capacity, "sbr_sessions_import: n=%lld outside [0,capacity=%lld]", (long long)n, s->p.capacity);
+    CHECK_ARG(chunk_slots >= 0, "sbr_sessions_import: chunk_slots=%lld is negative", (long long)chunk_slots);
+    CHECK_ARG(bytes == (size_t)n * y.bytes, "sbr_sessions_import: bytes=%zu is not n * record_bytes = %lld * %zu = %zu", bytes, (long long)n,
+              y.bytes, (size_t)n * y.bytes);
+    if (n == 0) return SBR_OK;
+    CHECK_ARG(slots && records_host, "null argument");
+    if ((rc = sessions_check_slots(s, "sbr_sessions_import", slots, n, true)) != SBR_OK) return rc;
+    // every count and id, as advance would take them (the floats are not inspected, as write does not inspect them)
+    const int n_ids = h->lay.cfg.input_size;
+    std::vector<int>& ids = s->park_ids;
+    ids.resize((size_t)y.ring_len);
+    for (int64_t r = 0; r < n; ++r) {
+        const unsigned char* rec = (const unsigned char*)records_host + (size_t)r * y.bytes;
+        long long ev;
+        memcpy(&ev, rec, sizeof(ev));
+        memcpy(ids.data(), rec + 8, ids.size() * sizeof(int));
+        CHECK_ARG(ev >= 0, "sbr_sessions_import: record %lld (slot %d): events = %lld is negative", (long long)r, slots[r], ev);
+        const long long kept = std::min<long long>(ev, y.ring_len);
+        for (int t = 0; t < y.ring_len; ++t) {
+            if (t < kept)
+                CHECK_ARG(ids[t] >= 0 && ids[t] < n_ids, "sbr_sessions_import: record %lld (slot %d): ids[%d] = %d outside [0,%d) among its %lld kept ids",
+                          (long long)r, slots[r], t, ids[t], n_ids, kept);
+            else
+                CHECK_ARG(ids[t] == -1, "sbr_sessions_import: record %lld (slot %d): ids[%d] = %d behind its %lld kept ids, where only -1 may stand",
+                          (long long)r, slots[r], t, ids[t], kept);
+        }
+    }
+    SesPark pk;
+    if ((rc = ses_park_stage(s, "sbr_sessions_import", n, chunk_slots, &pk)) != SBR_OK) return rc;
+    hipStream_t st = h->stream;
+    int* d_slots = (int*)(s->d_park + pk.slots_at);
+    int chunks = 0;
+    for (int64_t r0 = 0; r0 < n; r0 += pk.chunk, ++chunks) {
+        const int m = (int)std::min(pk.chunk, n - r0);
+        // (pageable host memory: the copies have left the caller's arrays when they return; the stream orders them behind the kernel
+        // that reads the chunk before)
+        SBR_HIP(hipMemcpyAsync(d_slots, slots + r0, (size_t)m * sizeof(int), hipMemcpyHostToDevice, st));
+        SBR_HIP(hipMemcpyAsync(s->d_park, (const unsigned char*)records_host + (size_t)r0 * y.bytes, (size_t)m * y.bytes, hipMemcpyHostToDevice, st));
+        const int per = 256 / pk.tps;
+        ses_unpack_kernel<<<(unsigned)((m + per - 1) / per), 256, 0, st>>>(s->p, y, d_slots, m, pk.tps, s->d_park);
+        SBR_LAUNCH(hipGetLastError());
+    }
+    h->last_park_chunks = chunks;
     return SBR_OK;
 }

@@ -93,7 +93,8 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
            "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load",
            "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_reset", "sbr_sessions_advance", "sbr_sessions_replay", "sbr_sessions_replay_ranks", "sbr_sessions_adopt",
-           "sbr_sessions_rank", "sbr_sessions_rank_candidates", "sbr_sessions_read", "sbr_sessions_write"]
+           "sbr_sessions_rank", "sbr_sessions_rank_candidates", "sbr_sessions_read", "sbr_sessions_write",
+           "sbr_sessions_record_layout", "sbr_sessions_export", "sbr_sessions_import"]
 
 _lib = None
 
@@ -213,6 +214,9 @@ def load_library(path=None):
     lib.sbr_sessions_rank_candidates.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp]
     lib.sbr_sessions_read.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp, i64p, vp]
     lib.sbr_sessions_write.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, vp, vp]
+    lib.sbr_sessions_record_layout.argtypes = [ctypes.POINTER(SbrConfig), ctypes.c_int32, szp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.sbr_sessions_export.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_size_t]
+    lib.sbr_sessions_import.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, vp, ctypes.c_size_t]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -1199,6 +1203,146 @@ def _slot_list(slots):
     return np.ascontiguousarray(np.asarray(slots, dtype=np.int32).reshape(-1))
 
 
+# ---------------------------------------------------------------- parked sessions (include/sbr_rnn.h "The record of a parked session")
+RECORD_VERSION = 1
+
+
+class RecordLayout(object):
+    """Where the fields of a parked session's record lie, from the rule of include/sbr_rnn.h: int64 events, int32 ids[ring_len]
+    (ring_len = max(history, 1)), zeros up to a multiple of 16 bytes, then per layer h[Hp] and, LSTM, c[Hp].  at[l] = (byte offset
+    of h, byte offset of c or None, Hp); fingerprint: FNV-1a 64 over the 32-bit words (1, cell, L, Hp_0 .., ring_len)."""
+
+    def __init__(self, cell, layers, history):
+        self.cell, self.layers, self.history = cell, [int(H) for H in layers], int(history)
+        self.ring_len = max(self.history, 1)
+        self.head = (8 + 4 * self.ring_len + 15) // 16 * 16
+        self.at, off = [], self.head
+        for H in self.layers:
+            Hp = pad_hidden(H)
+            h_at, off = off, off + 4 * Hp
+            c_at = None
+            if cell == "LSTM":
+                c_at, off = off, off + 4 * Hp
+            self.at.append((h_at, c_at, Hp))
+        self.record_bytes = off
+        f = 0xcbf29ce484222325
+        for w in [RECORD_VERSION, CELLS[cell], len(self.layers)] + [a[2] for a in self.at] + [self.ring_len]:
+            for b in int(w).to_bytes(4, "little"):
+                f = ((f ^ b) * 0x100000001b3) & 0xFFFFFFFFFFFFFFFF
+        self.fingerprint = f
+
+    def __str__(self):
+        return "%s %s ring_len=%d record_bytes=%d fingerprint=%016x" % (self.cell, [a[2] for a in self.at], self.ring_len, self.record_bytes,
+                                                                         self.fingerprint)
+
+
+class SessionRecords(object):
+    """n parked sessions: .raw uint8 [n][record_bytes] as sbr_sessions_export writes it, and numpy VIEWS into it -- .events int64 [n],
+    .history int32 [n][ring_len] (oldest first, then -1), .h(layer) / .c(layer) float32 [n][Hp].  records[i] (an index, a slice,
+    an index array) and SessionRecords.concatenate select and join rows."""
+
+    def __init__(self, layout, raw=None, n=0):
+        self.layout = layout
+        if raw is None:
+            raw = np.zeros((int(n), layout.record_bytes), dtype=np.uint8)
+        raw = np.asarray(raw)
+        if raw.dtype != np.uint8 or raw.ndim != 2 or raw.shape[1] != layout.record_bytes or not raw.flags["C_CONTIGUOUS"]:
+            raise ValueError("SessionRecords: raw must be contiguous uint8 [n][%d], got %s %s" % (layout.record_bytes, raw.dtype, raw.shape))
+        self.raw = raw
+
+    @property
+    def fingerprint(self):
+        return self.layout.fingerprint
+
+    def __len__(self):
+        return self.raw.shape[0]
+
+    def _view(self, dtype, at, count):
+        return self.raw[:, at:at + count * np.dtype(dtype).itemsize].view(dtype)
+
+    @property
+    def events(self):
+        return self._view(np.int64, 0, 1)[:, 0]
+
+    @property
+    def history(self):
+        return self._view(np.int32, 8, self.layout.ring_len)
+
+    def h(self, layer):
+        h_at, _, Hp = self.layout.at[layer]
+        return self._view(np.float32, h_at, Hp)
+
+    def c(self, layer):
+        _, c_at, Hp = self.layout.at[layer]
+        if c_at is None:
+            raise ValueError("SessionRecords.c: a %s layer has no cell state" % self.layout.cell)
+        return self._view(np.float32, c_at, Hp)
+
+    def __getitem__(self, i):
+        if isinstance(i, (int, np.integer)):
+            i = slice(i, i + 1) if i != -1 else slice(i, None)
+        return SessionRecords(self.layout, np.ascontiguousarray(self.raw[i]))
+
+    @staticmethod
+    def concatenate(parts):
+        parts = list(parts)
+        for q in parts[1:]:
+            if q.fingerprint != parts[0].fingerprint:
+                raise ValueError("SessionRecords.concatenate: records of two layouts: %s and %s" % (parts[0].layout, q.layout))
+        return SessionRecords(parts[0].layout, np.concatenate([q.raw for q in parts], axis=0))
+
+
+# A file of parked sessions: this head, then the n ids the records belong to (slots of a pool: int32; users of a serving.SessionStore:
+# int64), then the n records.  magic, version, ring_len, fingerprint, record_bytes, n
+PARK_HEAD = "<8sIIQQQ"
+PARK_MAGIC_POOL, PARK_MAGIC_STORE = b"SBRSESS1", b"SBRSTOR1"
+PARK_FILE_VERSION = 1
+
+
+def pack_park_file(magic, layout, ids, records):
+    """the bytes of a file of parked sessions (PARK_HEAD)"""
+    import struct
+    ids = np.ascontiguousarray(ids, dtype=np.int32 if magic == PARK_MAGIC_POOL else np.int64).reshape(-1)
+    if len(ids) != len(records):
+        raise ValueError("pack_park_file: %d ids for %d records" % (len(ids), len(records)))
+    head = struct.pack(PARK_HEAD, magic, PARK_FILE_VERSION, layout.ring_len, layout.fingerprint, layout.record_bytes, len(ids))
+    return head + ids.tobytes() + records.raw.tobytes()
+
+
+def parse_park_file(data, magic, layout):
+    """(ids, SessionRecords) of a file of parked sessions; the WHOLE head and the length are checked against `magic` and `layout`
+    before anything is returned: ValueError with the reason"""
+    import struct
+    size = struct.calcsize(PARK_HEAD)
+    if len(data) < size:
+        raise ValueError("parked sessions: the file is cut short: %d bytes, the head alone has %d" % (len(data), size))
+    got_magic, version, ring_len, fingerprint, record_bytes, n = struct.unpack(PARK_HEAD, data[:size])
+    if got_magic != magic:
+        raise ValueError("parked sessions: magic %r, not %r" % (got_magic, magic))
+    if version != PARK_FILE_VERSION:
+        raise ValueError("parked sessions: file version %d, this code reads version %d" % (version, PARK_FILE_VERSION))
+    if fingerprint != layout.fingerprint:
+        raise ValueError("parked sessions: layout fingerprint %016x (ring_len=%d, record_bytes=%d) in the file, the pool has %s"
+                         % (fingerprint, ring_len, record_bytes, layout))
+    if record_bytes != layout.record_bytes or ring_len != layout.ring_len:
+        raise ValueError("parked sessions: record_bytes=%d ring_len=%d in the file, the pool has %s" % (record_bytes, ring_len, layout))
+    id_type = np.dtype(np.int32 if magic == PARK_MAGIC_POOL else np.int64)
+    want = size + n * id_type.itemsize + n * record_bytes
+    if len(data) != want:
+        raise ValueError("parked sessions: the file is cut short or overlong: %d bytes, %d records need %d" % (len(data), n, want))
+    ids = np.frombuffer(data, dtype=id_type, count=n, offset=size).copy()
+    raw = np.frombuffer(data, dtype=np.uint8, count=n * record_bytes, offset=size + n * id_type.itemsize).reshape(n, record_bytes).copy()
+    return ids, SessionRecords(layout, raw)
+
+
+def write_replacing(path, data):
+    """`data` to a temporary name beside `path`, then moved into place: a reader never sees half a file"""
+    tmp = "%s.tmp.%d" % (path, os.getpid())
+    with open(tmp, "wb") as f:
+        f.write(data)
+    os.replace(tmp, path)
+
+
 class SessionPool(object):
     """Kept recurrent states beside an RNNEngine (include/sbr_rnn.h "Stateful sessions", csrc/sbr_session.hip): slot s holds the
     state of one user after all the events fed to it, so the user's next event costs one recurrent step (advance) and one projection
@@ -1212,6 +1356,14 @@ class SessionPool(object):
         with engine.torch.cuda.device(engine.device):
             engine._check(self.lib.sbr_sessions_create(engine.h, self.capacity, self.history, ctypes.byref(handle)))
         self.s = handle
+        # the record of a parked session: Python's offsets (the views of SessionRecords) against the library's record
+        self.layout = RecordLayout(engine.cell, engine.layers, self.history)
+        nbytes, fp = ctypes.c_size_t(), ctypes.c_uint64()
+        self._check(self.lib.sbr_sessions_record_layout(ctypes.byref(engine.cfg), self.history, ctypes.byref(nbytes), ctypes.byref(fp)))
+        if (nbytes.value, fp.value) != (self.layout.record_bytes, self.layout.fingerprint):
+            self.close()
+            raise SbrError("SessionPool: the library's record has %d bytes, fingerprint %016x; engine.RecordLayout says %s"
+                           % (nbytes.value, fp.value, self.layout))
 
     def _check(self, rc):
         self.engine._check(rc)
@@ -1400,6 +1552,43 @@ class SessionPool(object):
         h = stored(h)
         c = None if c is None else stored(c)
         self._check(self.lib.sbr_sessions_write(self.s, int(slot), int(layer), _ptr(h), _ptr(c)))
+
+    def export_records(self, slots, chunk_slots=0):
+        """the named sessions off the device (sbr_sessions_export; the slots may repeat): SessionRecords that import_records puts
+        into any slot of any pool of the same layout.  One wait, however many slots; chunk_slots bounds the staging buffer on the
+        device (0: the library's default) and changes nothing else."""
+        slots = _slot_list(slots)
+        out = SessionRecords(self.layout, n=len(slots))
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._check(self.lib.sbr_sessions_export(self.s, _ptr(slots), len(slots), int(chunk_slots), _ptr(out.raw), out.raw.nbytes))
+        return out
+
+    def import_records(self, slots, records, chunk_slots=0):
+        """records[r] becomes slot slots[r] (distinct; sbr_sessions_import): event count, the whole history ring and the state of
+        every layer -- afterwards the slot is the session the record was exported from, through every call of the pool"""
+        slots = _slot_list(slots)
+        if records.fingerprint != self.layout.fingerprint:
+            raise ValueError("import_records: records of another layout: %s; this pool has %s" % (records.layout, self.layout))
+        if len(records) != len(slots):
+            raise ValueError("import_records: %d records for %d slots" % (len(records), len(slots)))
+        with self.engine.torch.cuda.device(self.engine.device):
+            self._check(self.lib.sbr_sessions_import(self.s, _ptr(slots), len(slots), int(chunk_slots), _ptr(records.raw), records.raw.nbytes))
+
+    def save(self, path, slots=None):
+        """the named slots (None: every slot) to a file (PARK_HEAD), written beside `path` and moved into place"""
+        slots = np.arange(self.capacity, dtype=np.int32) if slots is None else _slot_list(slots)
+        write_replacing(path, pack_park_file(PARK_MAGIC_POOL, self.layout, slots, self.export_records(slots)))
+
+    def load(self, path, slots=None):
+        """the sessions of a file written by save into the slot numbers saved (slots: into these instead, one per record); the whole
+        head and the file's length are checked before the pool is touched (ValueError with the reason).  Returns the slots."""
+        with open(path, "rb") as f:
+            saved, records = parse_park_file(f.read(), PARK_MAGIC_POOL, self.layout)
+        slots = saved if slots is None else _slot_list(slots)
+        if len(slots) != len(records):
+            raise ValueError("load: %d slots for the %d records of %s" % (len(slots), len(records), path))
+        self.import_records(slots, records)
+        return slots
 
 
 # ------------------------------------------------------------------------------------------------ RNNCluster's cluster head

@@ -272,6 +272,13 @@ class RNNBase(object):
             pool.replay(slots, sequences)
         return pool
 
+    def session_store(self, capacity, history=None):
+        """A serving.SessionStore over a fresh session_pool(capacity, history): any number of users (Python ints) served through
+        `capacity` slots, the least recently used parked on the host and restored when they return, bit for bit.  Refused where
+        session_pool is refused, with its reason, before any engine call."""
+        from .serving import SessionStore
+        return SessionStore(RNNBase.session_pool(self, capacity, history))
+
     def _rank_chunks(self, sequences, user_ids, exclude):
         """top_k_batch's engine calls: (X, mask, lists) per batch_size sequences; lists: per row the ids never to rank, which carry
         every viewed item already -- the engine need not derive them from its input window again (exclude_input=False)"""
@@ -1308,6 +1315,10 @@ class RNNCluster(RNNBase):
         (ClusterHead.rank): a session pool's rows are not that batch, so nothing could rank them the way this model ranks."""
         raise NotImplementedError("session pools of a cluster model: ranking inside a user's cluster reads the engine's current batch, "
                                   "not the rows of a pool")
+
+    def session_store(self, capacity, history=None):
+        """refused as session_pool is: the store serves through a pool"""
+        return RNNCluster.session_pool(self, capacity, history)
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None, candidates=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per
