@@ -575,6 +575,51 @@ int sbr_evaluate_positions(sbr_handle* h, sbr_dataset* d, const int32_t* users, 
                            int64_t cap);               /* must be >= pos_off[n] = sum over users of max(0, min(L - 1, T) - min_history + 1) */
 
 /* ------------------------------------------------------------------------------------------------
+ * The log-probability of held-out items on the device (added under ABI 11: three symbols, no struct change) -- the validation loss:
+ * where every call above answers a ranking question, these two give the full-softmax log-likelihood of the same goal items from the
+ * same score rows.  For one score row of N floats, with "rankable" the counting kernels' rule (not NaN, not -inf,
+ * not excluded), m the largest rankable score and S the sum over the rankable items of exp(s_i - m):
+ *   log_z    = m + log(S)                   -inf for a row without a rankable item
+ *   logp(g)  = (s_g - m) - log(S)           -inf where g is not rankable (excluded, NaN, -inf, an id outside [0, N))
+ * A +inf score is rankable and makes m = +inf: log_z and every logp of that row are NaN.  s_g - m beyond the float range is -inf.
+ * The scores are the floats sbr_rank ranks (raw outputs, biased; whatever the head was trained with), so the number compares models
+ * as probability models.  Exclusion is a WRITE of -inf into the row before the reduction, never a subtraction from a finished sum.
+ * The float additions run in an order fixed by N alone (row_log_z, sbr_eval.hip: 256 threads whatever the launch, each adding its
+ * groups of four items in ascending order, then a fixed tree of depth 8; no atomics): a row's log_z and logp are the same bits
+ * whichever users, chunks, slots or groups share the call, and the same in all three calls.  |log_z - exact| <=
+ * (4 * ceil(ceil(N / 4) / 256) + 8 + 8) * 2^-24 for |log_z| < 16.  sbr_query "logprob_form": 1 the rows were read in 16-byte loads,
+ * 2 in 4-byte loads (N no multiple of 4), 0 no call yet -- the bits do not depend on it.
+ *
+ * sbr_evaluate_logprob is sbr_evaluate_ranks' call: the same split, window, chunks, offsets (goal_off), repeated users, one wait at
+ * the end, keep-and-restore of lazily stepped rows, and errors; exclude_mode SBR_EVAL_EXCL_NONE, _VIEWED or _WINDOW (_WINDOW_ZERO is
+ * SBR_EINVAL: an item scored 0.0 has not left the softmax).  logp[goal_off[j] + p] belongs to goal place p of users[j], log_z[j] to
+ * its row.  ranks / n_rankable, where given, are exactly sbr_evaluate_ranks' (its kernel runs on the same rows in the same call).
+ * sbr_evaluate_positions_logprob is sbr_evaluate_positions' call in the same way (SBR_EVAL_EXCL_NONE or _PREFIX; bidirectional
+ * engines are refused): logp, log_z, ranks and n_rankable at pos_off[j] + p - min_history.  Under _PREFIX the ids of x_0 .. x_{p-1}
+ * are written -inf into the position's own score row (behind the integer counts, which read the row as projected).  On an explicit
+ * user x_0 .. x_{p-1}, x_p padded to length 2p or 2p + 1 sbr_evaluate_logprob gives the same bits (NONE / VIEWED).
+ * Both: SBR_ESTATE inside an open training step or with a lagged cost pending.
+ * sbr_debug_row_logprob is the test hook of the reduction: the same device function on rows [rows][ld] of DEVICE scores (only read),
+ * goal_ids_dev [rows][goals_per_row], results into logp_dev [rows][goals_per_row] and log_z_dev [rows] (NULL: not written); on the
+ * engine's stream, waits for the device. */
+int sbr_evaluate_logprob(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int exclude_mode,
+                         int64_t* goal_off_host,     /* [n + 1], as sbr_evaluate_ranks writes it */
+                         float* logp_host,           /* [cap] */
+                         int64_t cap,                /* must be >= goal_off[n] */
+                         float* log_z_host,          /* NULL, or [n] */
+                         int32_t* ranks_host,        /* NULL, or [cap]: exactly sbr_evaluate_ranks' */
+                         int32_t* n_rankable_host);  /* NULL, or [n] */
+int sbr_evaluate_positions_logprob(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int min_history, int exclude_mode,
+                                   int64_t* pos_off_host,      /* [n + 1], as sbr_evaluate_positions writes it */
+                                   float* logp_host,           /* [cap] */
+                                   float* log_z_host,          /* NULL, or [cap] */
+                                   int32_t* ranks_host,        /* NULL, or [cap]: exactly sbr_evaluate_positions' */
+                                   int32_t* n_rankable_host,   /* NULL, or [cap] */
+                                   int64_t cap);               /* must be >= pos_off[n] */
+int sbr_debug_row_logprob(sbr_handle* h, const float* scores_dev, int64_t ld, int64_t rows, int32_t N, const int32_t* goal_ids_dev,
+                          int32_t goals_per_row, float* logp_dev, float* log_z_dev);
+
+/* ------------------------------------------------------------------------------------------------
  * The rank of every goal item among a candidate set of its user (added under ABI 11: two symbols and one constant, no struct change)
  * -- the protocol of the sequential-recommendation papers: each positive against S negatives the user never interacted with, HR@k /
  * NDCG@k / MRR from the ranks -- without scoring the whole catalogue.  Users are split, fed and chunked (local_batch per chunk)

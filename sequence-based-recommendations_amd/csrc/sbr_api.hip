@@ -1013,6 +1013,8 @@ extern "C" int sbr_query(sbr_handle* h, const char* what, int64_t* value) {
     // the LAST sbr_evaluate_positions: 0 none yet, 1 the score row was read in 16-byte loads, 2 in 4-byte loads (N no multiple of 4)
     else if (w == "next_rank_form") *value = h->last_next_rank_form;
     else if (w == "next_rank_slots") *value = h->last_next_rank_slots;      // ... and the positions it projected per GEMM launch at the most (0 no call yet)
+    // the LAST sbr_evaluate_logprob / sbr_evaluate_positions_logprob / sbr_debug_row_logprob: the same two load forms, 0 no call yet
+    else if (w == "logprob_form") *value = h->last_logprob_form;
     else if (w == "row_aware_update") *value = h->last_row_aware ? 1 : 0;      // ... and whether its optimizer pass over W_in was the row-aware one
     else if (w == "cluster") *value = top.needs_fill ? 1 : 0;      // the cluster kernels (the family that wants the sentinel fill)
     else if (w == "rec_kernel") *value = top.family;               // 0 triage, 1 cluster, 2 x6p (128 units), 3 x6q (32/64), 4 other

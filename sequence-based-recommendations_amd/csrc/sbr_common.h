@@ -427,6 +427,7 @@ struct sbr_handle {
     void* rank_scratch = nullptr; size_t rank_scratch_bytes = 0; int last_rank_select = 0, last_rank_sort = 0;
     int last_goal_rank_form = 0;                                          // sbr_evaluate_ranks: 0 none yet, 1 the row's keys in LDS, 2 streamed
     int last_next_rank_form = 0;                                          // sbr_evaluate_positions: 0 none yet, 1 16-byte loads of the score row, 2 4-byte loads
+    int last_logprob_form = 0;                                            // sbr_evaluate_logprob, _positions_logprob, sbr_debug_row_logprob: the same two forms
     int last_next_rank_slots = 0;                                         // ... and the positions it projected per GEMM launch at the most
     int last_cluster_rank_form = 0;                                       // sbr_cluster_rank: 0 none yet, 1 restricted scoring, 2 gathered from the full scores
     int last_replay_launches = 0;                                         // sbr_sessions_replay: the kernel launches the most recent one enqueued
@@ -989,6 +990,18 @@ hipError_t launch_ev_first_seen(hipStream_t s, const int* X, const int* lengths,
 hipError_t launch_ev_next_rank(hipStream_t s, const SbrEvalView& v, const int* users, const long long* pos_off, const int* X, const int* lengths,
                                const int* first, int rows, int T, int F, int N, int p0, int slots, int min_history, int exclude_prefix,
                                const float* scores, size_t slot_stride, int* ranks, int* n_rankable, int* form);
+// sbr_evaluate_logprob / sbr_evaluate_positions_logprob (include/sbr_rnn.h): the log-probability of launch_ev_goal_rank's
+// and launch_ev_next_rank's goal items under the softmax over the rankable items of the same score rows, at the same places of logp;
+// log_z (NULL: not written) [rows], or at the places of logp for the positions.  The positions form WRITES -inf at the ids of the
+// prefix into its score rows when exclude_prefix is set.  *form: 1 16-byte loads, 2 4-byte loads; the bits do not depend on it.
+hipError_t launch_ev_goal_logprob(hipStream_t s, const SbrEvalView& v, const int* users, const long long* goal_off, int rows, int N,
+                                  const float* scores, float* logp, float* log_z, int* form);
+hipError_t launch_ev_next_logprob(hipStream_t s, const SbrEvalView& v, const int* users, const long long* pos_off, const int* X, const int* lengths,
+                                  int rows, int T, int F, int N, int p0, int slots, int min_history, int exclude_prefix, float* scores,
+                                  size_t slot_stride, float* logp, float* log_z, int* form);
+// ... and the same reduction on any rows [rows][ld] of device scores, goal_ids [rows][goals_per_row] (sbr_debug_row_logprob)
+hipError_t launch_debug_row_logprob(hipStream_t s, const float* scores, size_t ld, int rows, int N, const int* goal_ids, int goals_per_row,
+                                    float* logp, float* log_z, int* form);
 // sbr_eval_cand.hip: goal items ranked among a candidate set per user (include/sbr_rnn.h: sbr_evaluate_candidates)
 // What ev_cand_build_kernel reads and writes for the rows of one chunk.  The candidates of row r are either the explicit list
 // cand_ids[cand_off[r] .. cand_off[r + 1]) (strictly ascending) or, with cand_ids == nullptr, n_neg negatives drawn by the rule above.

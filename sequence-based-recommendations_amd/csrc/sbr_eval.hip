@@ -10,6 +10,9 @@
 //   4. ev_pack_kernel<true>  the rows fed: the START of every user's sequence (UserPrefix)
 //   5. ev_first_seen_kernel  per place of a row, whether its item occurs there for the first time
 //   6. ev_next_rank_kernel   per position p, the place of x_p among the scores projected from slot p: one streamed count
+// and, for sbr_evaluate_logprob / sbr_evaluate_positions_logprob (the log-probability of the same goal items):
+//   7. row_log_z             the one float reduction of a score row, in an order fixed by N alone
+//   8. ev_goal_logprob_kernel / ev_next_logprob_kernel / debug_row_logprob_kernel   its three launch shapes
 // What of a user's sequence is viewed, fed (the window) and the goal: UserSplit (sbr_common.h).
 // Rows are independent in every kernel; nothing waits on another workgroup.
 #include "sbr_common.h"
@@ -346,7 +349,174 @@ __global__ void __launch_bounds__(kRankThreads) ses_event_rank_kernel(SesEventRa
     }
 }
 
+// ---- sbr_evaluate_logprob, sbr_evaluate_positions_logprob, sbr_debug_row_logprob: the log-probability of the goal items under the
+// softmax over the RANKABLE items of a score row.  Rankable: rank_key(v) != 0, the counting kernels' rule; m the largest
+// rankable score, S the sum over the rankable items of exp(s_i - m); log_z = m + log(S), logp(g) = (s_g - m) - log(S).  A row without a
+// rankable item has log_z = -inf; a goal that is not rankable (excluded, NaN, -inf, an id outside [0, N)) has logp = -inf.  A +inf
+// score is rankable: m is then +inf, exp(s_i - m) is NaN at that item, and log_z and every logp of the row are NaN.  s_g - m below
+// -3.4e38 (scores of both signs near the float range) rounds to -inf like any float subtraction.
+// row_log_z is the one statement of the reduction, for all three launch shapes; the ORDER of its float additions is a function of N
+// alone.  The row is taken in groups of four consecutive items, group q = items 4q .. 4q + 3 (the last one short when N is no
+// multiple of 4); thread t of kLogpThreads -- a constant, never the launch's blockDim -- owns the groups t, t + kLogpThreads, .. and
+// adds the terms of its groups in ascending item order into one float (at most 4 * ceil(ceil(N / 4) / kLogpThreads) terms); the
+// kLogpThreads partials are then added by a fixed tree: six xor-shuffle levels inside each wave (offsets 32 .. 1), and the four wave
+// sums as (w0 + w1) + (w2 + w3) -- depth 8.  No float atomics.  VEC only chooses how a group is LOADED (one 16-byte load, or up to
+// four 4-byte loads): the same items meet the same thread in the same order.  Two passes over the row, the maximum and then the sum;
+// the second finds the row in the cache.  Exclusion is never a subtraction from S: the excluded ids hold -inf in the row before the
+// first pass (launch_exclude, or the prefix write of ev_next_logprob_kernel).
+constexpr int kLogpThreads = 256;
+constexpr int kLogpWaves = kLogpThreads / 64;
+static_assert(kLogpWaves == 4, "row_log_z adds the wave sums as (w0 + w1) + (w2 + w3)");
+struct RowLogZ { float m, log_s; };                                // log_z = m + log_s; no rankable item: m = log_s = -inf
+template <bool VEC, class Term>
+__device__ __forceinline__ void logp_groups(const float* row, int N, Term&& term) {
+    const int groups = (N + 3) >> 2;
+    for (int q = threadIdx.x; q < groups; q += kLogpThreads) {
+        if (VEC) {                                                 // (N a multiple of 4: every group is whole)
+            const float4 v = ((const float4*)row)[q];
+            term(v.x); term(v.y); term(v.z); term(v.w);
+        } else {
+            const int i0 = 4 * q, n = min(4, N - i0);
+            for (int j = 0; j < n; ++j) term(row[i0 + j]);
+        }
+    }
+}
+template <bool VEC>
+__device__ __forceinline__ RowLogZ row_log_z(const float* row, int N, float* s_red /* [kLogpWaves] of LDS, free again on return */) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    float m = -INFINITY;
+    logp_groups<VEC>(row, N, [&](float v) { if (rank_key(v) != 0u) m = fmaxf(m, v); });
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) m = fmaxf(m, __shfl_xor(m, o2));
+    if (lane == 0) s_red[w] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(s_red[0], s_red[1]), fmaxf(s_red[2], s_red[3]));
+    __syncthreads();
+    if (!(m > -INFINITY)) return RowLogZ{-INFINITY, -INFINITY};    // (uniform) no rankable item
+    float sum = 0.0f;
+    logp_groups<VEC>(row, N, [&](float v) { if (rank_key(v) != 0u) sum += expf(v - m); });
+#pragma unroll
+    for (int o2 = 32; o2 > 0; o2 >>= 1) sum += __shfl_xor(sum, o2);   // a + b == b + a: both lanes of a pair hold the same bits
+    if (lane == 0) s_red[w] = sum;
+    __syncthreads();
+    const float S = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
+    __syncthreads();
+    return RowLogZ{m, logf(S)};
+}
+__device__ __forceinline__ float row_log_z_value(const RowLogZ& z) { return z.m > -INFINITY ? z.m + z.log_s : -INFINITY; }
+// the goal's log-probability from the row as the reduction read it
+__device__ __forceinline__ float goal_logp(const float* row, int N, int gid, const RowLogZ& z) {
+    if ((unsigned)gid >= (unsigned)N) return -INFINITY;            // an id outside the catalogue is never ranked
+    const float sg = row[gid];
+    if (rank_key(sg) == 0u) return -INFINITY;
+    return (sg - z.m) - z.log_s;
+}
+
+// One workgroup per row of a chunk, the goal items of sbr_evaluate_ranks: logp[goal_off[r] + j] for goal place j, log_z[r].  The row
+// already holds -inf at what the call excludes.
+template <bool VEC>
+__global__ void __launch_bounds__(kLogpThreads) ev_goal_logprob_kernel(const int* __restrict__ items, const long long* __restrict__ off,
+                                                                       const int* __restrict__ users, const long long* __restrict__ goal_off,
+                                                                       const float* __restrict__ scores, int N, float* __restrict__ logp,
+                                                                       float* __restrict__ log_z) {
+    __shared__ float s_red[kLogpWaves];
+    const int r = blockIdx.x;
+    const int u = users[r];
+    const long long o = off[u];
+    const UserSplit sp(o, off[u + 1], 0);                          // (no window here)
+    const float* row = scores + (size_t)r * N;
+    const RowLogZ z = row_log_z<VEC>(row, N, s_red);
+    const int* g = items + o + sp.half;                            // the goal in sequence order
+    float* out = logp + goal_off[r];
+    for (int j = threadIdx.x; j < sp.goal_len(); j += kLogpThreads) out[j] = goal_logp(row, N, g[j], z);
+    if (threadIdx.x == 0 && log_z) log_z[r] = row_log_z_value(z);
+}
+
+// One workgroup per (row, position slot), the goal of ev_next_rank_kernel.  The (row, slot) score row belongs to this position alone:
+// with exclude_prefix the ids of x_0 .. x_{p-1} are written -inf there behind one workgroup barrier (a repeated id is written twice),
+// as ses_event_rank_kernel writes its window; the integer counts of the same position, where the call wants them, ran BEFORE this launch.
+template <bool VEC>
+__global__ void __launch_bounds__(kLogpThreads) ev_next_logprob_kernel(const int* __restrict__ items, const long long* __restrict__ off,
+                                                                       const int* __restrict__ users, const long long* __restrict__ pos_off,
+                                                                       const int* __restrict__ X, const int* __restrict__ lengths, int T, int F,
+                                                                       int N, int p0, int min_history, int exclude_prefix, float* scores,
+                                                                       size_t slot_stride, float* __restrict__ logp, float* __restrict__ log_z) {
+    __shared__ float s_red[kLogpWaves];
+    const int r = blockIdx.x;
+    const int p = p0 + blockIdx.y;                                 // slot blockIdx.y of the launch holds the scores of position p0 + blockIdx.y
+    if (p > lengths[r]) return;                                    // (uniform over the workgroup) the row has no position p
+    const int gid = items[off[users[r]] + p];                      // p <= fed <= L - 1: inside the user's sequence
+    float* row = scores + (size_t)blockIdx.y * slot_stride + (size_t)r * N;
+    if (exclude_prefix) {
+        const int* xr = X + (size_t)r * T * F;
+        for (int q = threadIdx.x; q < p; q += kLogpThreads) {      // p <= lengths[r] <= T
+            const int id = xr[(size_t)q * F];
+            if ((unsigned)id < (unsigned)N) row[id] = -INFINITY;
+        }
+        __syncthreads();
+    }
+    const RowLogZ z = row_log_z<VEC>(row, N, s_red);
+    if (threadIdx.x == 0) {
+        const long long at = pos_off[r] + (p - min_history);
+        logp[at] = goal_logp(row, N, gid, z);
+        if (log_z) log_z[at] = row_log_z_value(z);
+    }
+}
+
+// The test hook: the same device functions on the caller's rows, goals [rows][goals_per_row]
+template <bool VEC>
+__global__ void __launch_bounds__(kLogpThreads) debug_row_logprob_kernel(const float* __restrict__ scores, size_t ld, int N,
+                                                                         const int* __restrict__ goal_ids, int goals_per_row,
+                                                                         float* __restrict__ logp, float* __restrict__ log_z) {
+    __shared__ float s_red[kLogpWaves];
+    const int r = blockIdx.x;
+    const float* row = scores + (size_t)r * ld;
+    const RowLogZ z = row_log_z<VEC>(row, N, s_red);
+    for (int j = threadIdx.x; j < goals_per_row; j += kLogpThreads)
+        logp[(size_t)r * goals_per_row + j] = goal_logp(row, N, goal_ids[(size_t)r * goals_per_row + j], z);
+    if (threadIdx.x == 0 && log_z) log_z[r] = row_log_z_value(z);
+}
+
 }  // namespace
+
+// 16-byte loads: every row of the matrix starts on a 16-byte boundary and holds whole groups
+static bool logp_vec(const float* scores, int N, size_t row_stride, size_t slot_stride = 0) {
+    return N % 4 == 0 && row_stride % 4 == 0 && slot_stride % 4 == 0 && ((size_t)scores & 15) == 0;
+}
+
+hipError_t launch_ev_goal_logprob(hipStream_t s, const SbrEvalView& v, const int* users, const long long* goal_off, int rows, int N,
+                                  const float* scores, float* logp, float* log_z, int* form) {
+    const bool vec = logp_vec(scores, N, (size_t)N);
+    *form = vec ? 1 : 2;
+    if (rows <= 0) return hipSuccess;
+    if (vec) ev_goal_logprob_kernel<true><<<rows, kLogpThreads, 0, s>>>(v.items, v.off, users, goal_off, scores, N, logp, log_z);
+    else ev_goal_logprob_kernel<false><<<rows, kLogpThreads, 0, s>>>(v.items, v.off, users, goal_off, scores, N, logp, log_z);
+    return hipGetLastError();
+}
+
+hipError_t launch_ev_next_logprob(hipStream_t s, const SbrEvalView& v, const int* users, const long long* pos_off, const int* X, const int* lengths,
+                                  int rows, int T, int F, int N, int p0, int slots, int min_history, int exclude_prefix, float* scores,
+                                  size_t slot_stride, float* logp, float* log_z, int* form) {
+    const bool vec = logp_vec(scores, N, (size_t)N, slot_stride);
+    *form = vec ? 1 : 2;
+    if (rows <= 0 || slots <= 0) return hipSuccess;
+    const dim3 grid(rows, slots);
+    if (vec) ev_next_logprob_kernel<true><<<grid, kLogpThreads, 0, s>>>(v.items, v.off, users, pos_off, X, lengths, T, F, N, p0, min_history,
+                                                                      exclude_prefix, scores, slot_stride, logp, log_z);
+    else ev_next_logprob_kernel<false><<<grid, kLogpThreads, 0, s>>>(v.items, v.off, users, pos_off, X, lengths, T, F, N, p0, min_history,
+                                                                     exclude_prefix, scores, slot_stride, logp, log_z);
+    return hipGetLastError();
+}
+
+hipError_t launch_debug_row_logprob(hipStream_t s, const float* scores, size_t ld, int rows, int N, const int* goal_ids, int goals_per_row,
+                                    float* logp, float* log_z, int* form) {
+    const bool vec = logp_vec(scores, N, ld);
+    *form = vec ? 1 : 2;
+    if (rows <= 0) return hipSuccess;
+    if (vec) debug_row_logprob_kernel<true><<<rows, kLogpThreads, 0, s>>>(scores, ld, N, goal_ids, goals_per_row, logp, log_z);
+    else debug_row_logprob_kernel<false><<<rows, kLogpThreads, 0, s>>>(scores, ld, N, goal_ids, goals_per_row, logp, log_z);
+    return hipGetLastError();
+}
 
 hipError_t launch_ses_event_rank(hipStream_t s, const SesEventRank& a, int rows, int* form) {
     const bool vec = a.N % 4 == 0;                                 // (the score rows start on 16-byte boundaries then: the scratch is carved in 256 bytes)

@@ -1,5 +1,5 @@
 // The ranking and evaluation calls of the C-ABI (include/sbr_rnn.h): sbr_topk, sbr_rank, sbr_evaluate, sbr_evaluate_ranks,
-// sbr_evaluate_positions, sbr_evaluate_candidates, sbr_cluster_rank, sbr_cluster_evaluate, sbr_rank_candidates, sbr_sessions_rank_candidates.
+// sbr_evaluate_positions, sbr_evaluate_logprob, sbr_evaluate_positions_logprob, sbr_evaluate_candidates, sbr_cluster_rank, sbr_cluster_evaluate, sbr_rank_candidates, sbr_sessions_rank_candidates.
 // Host code only (kernels: sbr_rank.hip, sbr_eval.hip, sbr_eval_cand.hip, sbr_cluster_rank.hip, sbr_cand_rank.hip, sbr_cluster_eval.hip; forward pass and projection:
 // sbr_api.hip), built from the shared pieces below: scores, ONE exclusion launch per ranking (launch_exclude: what
 // is excluded is an ExclSources, where it lands an ExclCatalogue or ExclCluster, sbr_device.h), select and sort (rank_rows).
@@ -833,6 +833,162 @@ extern "C" int sbr_evaluate_positions(sbr_handle* h, sbr_dataset* d, const int32
         SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
     }
     return check_fault(h);          // a forward that gave up must not hand out ranks; the call's one wait for the device
+}
+
+// what both log-probability calls refuse about the engine's state before anything else
+static int logprob_state_check(const sbr_handle* h, const char* call) {
+    if (h->st.step_open || h->st.train_fwd_open) { sbr_set_error("%s: a training step is open (finish it with sbr_apply_update)", call); return SBR_ESTATE; }
+    if (h->lag_pending >= 0) { sbr_set_error("%s: a lagged cost is pending (collect it with sbr_lagged_flush)", call); return SBR_ESTATE; }
+    return SBR_OK;
+}
+
+// The log-probability of every goal item under the softmax over its row's rankable items (include/sbr_rnn.h: sbr_evaluate_logprob;
+// DESIGN.md 3u): sbr_evaluate_ranks' call -- the same split, window, chunks, exclusion launch, offsets and keep-and-restore -- with the
+// float reduction (ev_goal_logprob_kernel, sbr_eval.hip) behind the exclusion, and ev_goal_rank_kernel in front of it on the same row
+// when the caller takes ranks or n_rankable.
+extern "C" int sbr_evaluate_logprob(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int exclude_mode, int64_t* goal_off_host,
+                                    float* logp_host, int64_t cap, float* log_z_host, int32_t* ranks_host, int32_t* n_rankable_host) {
+    CHECK_ARG(h && d && users && goal_off_host && logp_host, "null argument");
+    CHECK_ARG(exclude_mode >= SBR_EVAL_EXCL_NONE && exclude_mode <= SBR_EVAL_EXCL_WINDOW,
+              "sbr_evaluate_logprob takes SBR_EVAL_EXCL_NONE, _VIEWED or _WINDOW, not mode %d (an item scored 0.0 is no exclusion from a softmax)", exclude_mode);
+    const Layout& y = h->lay;
+    SbrEvalView v;
+    int rc;
+    if ((rc = logprob_state_check(h, "sbr_evaluate_logprob")) != SBR_OK) return rc;
+    if ((rc = eval_check_args(h, d, users, n, 1, v)) != SBR_OK) return rc;      // (no k here: 1 is inside every catalogue)
+    int64_t total = 0;
+    auto goal_len = [&](int64_t j) -> int64_t { return UserSplit(v.h_off[users[j]], v.h_off[users[j] + 1], y.T).goal_len(); };
+    for (int64_t j = 0; j < n; ++j) total += goal_len(j);
+    CHECK_ARG(cap >= total, "cap=%lld: the goals of these users hold %lld items", (long long)cap, (long long)total);
+    goal_off_host[0] = 0;
+    for (int64_t j = 0; j < n; ++j) goal_off_host[j + 1] = goal_off_host[j] + goal_len(j);
+    const bool counts = ranks_host || n_rankable_host;
+    Carver cv;
+    const size_t o_users = cv.take((size_t)n * sizeof(int)), o_goff = cv.take((size_t)(n + 1) * sizeof(long long));
+    const size_t o_logp = cv.take((size_t)total * sizeof(float)), o_logz = cv.take((size_t)n * sizeof(float));
+    const size_t o_ranks = cv.take(counts ? (size_t)total * sizeof(int) : 0), o_nrk = cv.take(counts ? (size_t)n * sizeof(int) : 0);
+    LazyKeep kept;      // training goes on as if the call had not been made
+    kept.carve(cv, h);
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    const long long* dgoff = (const long long*)(S + o_goff);
+    // (pageable host memory: the copies have left the caller's arrays when they return)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    SBR_HIP(hipMemcpyAsync(S + o_goff, goal_off_host, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    { const int rck = kept.save(h, S); if (rck != SBR_OK) return rck; }
+    rc = eval_chunks(h, v, dusers, n, exclude_mode, [&](int64_t c0, int rows, float* lg) -> int {
+        if (counts)
+            SBR_LAUNCH(launch_ev_goal_rank(s, v, dusers + c0, dgoff + c0, rows, y.N, lg, (int*)(S + o_ranks), (int*)(S + o_nrk) + c0, &h->last_goal_rank_form));
+        SBR_LAUNCH(launch_ev_goal_logprob(s, v, dusers + c0, dgoff + c0, rows, y.N, lg, (float*)(S + o_logp), (float*)(S + o_logz) + c0,
+                                          &h->last_logprob_form));
+        return SBR_OK;
+    });
+    { const int rck = kept.restore(h, S); if (rck != SBR_OK) return rck; }      // (also behind a chunk that failed: the call leaves the bits it found)
+    if (rc != SBR_OK) return rc;
+    SBR_HIP(hipMemcpyAsync(logp_host, S + o_logp, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (log_z_host) SBR_HIP(hipMemcpyAsync(log_z_host, S + o_logz, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, s));
+    if (ranks_host) SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+    if (n_rankable_host) SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
+    return check_fault(h);          // a forward that gave up must not hand out results; the call's one wait for the device
+}
+
+// The log-probability of the NEXT item at every position (include/sbr_rnn.h: sbr_evaluate_positions_logprob): sbr_evaluate_positions'
+// call -- the same prefix, chunks, groups of slots and projections -- with, per group, the integer counts first (only when the caller
+// takes ranks or n_rankable: they read the scores as projected) and then ev_next_logprob_kernel, which writes -inf at the prefix's ids
+// into its own (row, slot) score rows before it reduces them.  The scores of a group are projected anew for the next one.
+extern "C" int sbr_evaluate_positions_logprob(sbr_handle* h, sbr_dataset* d, const int32_t* users, int64_t n, int min_history, int exclude_mode,
+                                              int64_t* pos_off_host, float* logp_host, float* log_z_host, int32_t* ranks_host,
+                                              int32_t* n_rankable_host, int64_t cap) {
+    CHECK_ARG(h && d && users && pos_off_host && logp_host, "null argument");
+    CHECK_ARG(exclude_mode == SBR_EVAL_EXCL_NONE || exclude_mode == SBR_EVAL_EXCL_PREFIX,
+              "sbr_evaluate_positions_logprob takes SBR_EVAL_EXCL_NONE or SBR_EVAL_EXCL_PREFIX, not mode %d", exclude_mode);
+    CHECK_ARG(min_history >= 1, "min_history=%d: a position needs at least one item in front of it", min_history);
+    const Layout& y = h->lay;
+    // a backwards layer's state at place p has read the items behind p: its slots are no states "after p items"
+    CHECK_ARG(y.D == 1, "sbr_evaluate_positions_logprob: a bidirectional engine has no state that has seen only the first p items");
+    SbrEvalView v;
+    int rc;
+    if ((rc = logprob_state_check(h, "sbr_evaluate_positions_logprob")) != SBR_OK) return rc;
+    if ((rc = eval_check_args(h, d, users, n, 1, v)) != SBR_OK) return rc;      // (no k here: 1 is inside every catalogue)
+    auto prefix = [&](int64_t j) { return UserPrefix(v.h_off[users[j]], v.h_off[users[j] + 1], y.T, min_history); };
+    int64_t total = 0;
+    for (int64_t j = 0; j < n; ++j) total += prefix(j).n_pos();
+    CHECK_ARG(cap >= total, "cap=%lld: these users hold %lld positions", (long long)cap, (long long)total);
+    pos_off_host[0] = 0;
+    for (int64_t j = 0; j < n; ++j) pos_off_host[j + 1] = pos_off_host[j] + prefix(j).n_pos();
+    const int B = y.B;
+    const bool counts = ranks_host || n_rankable_host, excl = exclude_mode == SBR_EVAL_EXCL_PREFIX;
+    Carver cv;
+    const size_t o_users = cv.take((size_t)n * sizeof(int)), o_poff = cv.take((size_t)(n + 1) * sizeof(long long));
+    const size_t o_logp = cv.take((size_t)total * sizeof(float)), o_logz = cv.take(log_z_host ? (size_t)total * sizeof(float) : 0);
+    const size_t o_ranks = cv.take(counts ? (size_t)total * sizeof(int) : 0), o_nrk = cv.take(counts ? (size_t)total * sizeof(int) : 0);
+    const size_t o_first = cv.take((size_t)B * y.T * sizeof(int));
+    // the slots of a group: sbr_evaluate_positions' rule, so that a position's scores are the floats that call counts
+    const size_t slot_floats = (size_t)y.Bp * y.N;
+    const int slots = scores_gemm_mode(h).one_pass ? 1 : (int)std::max<size_t>(1, std::min<size_t>(kNextRankSlots, kNextRankScoreBytes / (slot_floats * sizeof(float))));
+    const size_t o_scores = cv.take(slots > 1 ? slots * slot_floats * sizeof(float) : 0);
+    LazyKeep kept;      // training goes on as if the call had not been made
+    kept.carve(cv, h);
+    if ((rc = rank_scratch(h, cv.at)) != SBR_OK) return rc;
+    char* S = (char*)h->rank_scratch;
+    hipStream_t s = h->stream;
+    const int* dusers = (const int*)(S + o_users);
+    const long long* dpoff = (const long long*)(S + o_poff);
+    int* first = (int*)(S + o_first);
+    float* scores = slots > 1 ? (float*)(S + o_scores) : h->A(y.a_logits);
+    float* dlogz = log_z_host ? (float*)(S + o_logz) : nullptr;
+    h->last_next_rank_slots = slots;
+    // (pageable host memory: the copies have left the caller's arrays when they return)
+    SBR_HIP(hipMemcpyAsync(S + o_users, users, (size_t)n * sizeof(int), hipMemcpyHostToDevice, s));
+    SBR_HIP(hipMemcpyAsync(S + o_poff, pos_off_host, (size_t)(n + 1) * sizeof(long long), hipMemcpyHostToDevice, s));
+    { const int rck = kept.save(h, S); if (rck != SBR_OK) return rck; }
+    const LayerLayout& top = y.layer[y.L - 1];
+    auto chunks = [&]() -> int {
+        for (int64_t c0 = 0; c0 < n; c0 += B) {
+            const int rows = (int)std::min<int64_t>(B, n - c0);
+            int last = 0;                                              // the chunk's longest row
+            for (int r = 0; r < rows; ++r) last = std::max(last, prefix(c0 + r).last_pos());
+            int rc2;
+            if ((rc2 = eval_pack_chunk(h, v, dusers + c0, rows, true)) != SBR_OK) return rc2;
+            if ((rc2 = forward_current(h)) != SBR_OK) return rc2;
+            if (excl && counts) SBR_LAUNCH(launch_ev_first_seen(s, h->bX, h->blen, rows, y.T, y.F, first));
+            for (int p0 = min_history; p0 <= last; p0 += slots) {
+                const int k = std::min(slots, last - p0 + 1);
+                if ((rc2 = project_rows(h, h->A(top.a_hs) + (size_t)p0 * y.Bp * top.Hp, (k - 1) * y.Bp + rows, scores, 0)) != SBR_OK) return rc2;
+                if (counts)
+                    SBR_LAUNCH(launch_ev_next_rank(s, v, dusers + c0, dpoff + c0, h->bX, h->blen, first, rows, y.T, y.F, y.N, p0, k, min_history,
+                                                   excl, scores, slot_floats, (int*)(S + o_ranks), (int*)(S + o_nrk), &h->last_next_rank_form));
+                SBR_LAUNCH(launch_ev_next_logprob(s, v, dusers + c0, dpoff + c0, h->bX, h->blen, rows, y.T, y.F, y.N, p0, k, min_history, excl,
+                                                  scores, slot_floats, (float*)(S + o_logp), dlogz, &h->last_logprob_form));
+            }
+        }
+        return SBR_OK;
+    };
+    rc = chunks();
+    { const int rck = kept.restore(h, S); if (rck != SBR_OK) return rck; }      // (also behind a chunk that failed: the call leaves the bits it found)
+    if (rc != SBR_OK) return rc;
+    if (total) {
+        SBR_HIP(hipMemcpyAsync(logp_host, S + o_logp, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (log_z_host) SBR_HIP(hipMemcpyAsync(log_z_host, S + o_logz, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, s));
+        if (ranks_host) SBR_HIP(hipMemcpyAsync(ranks_host, S + o_ranks, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+        if (n_rankable_host) SBR_HIP(hipMemcpyAsync(n_rankable_host, S + o_nrk, (size_t)total * sizeof(int), hipMemcpyDeviceToHost, s));
+    }
+    return check_fault(h);          // a forward that gave up must not hand out results; the call's one wait for the device
+}
+
+// The test hook of the float reduction (include/sbr_rnn.h: sbr_debug_row_logprob): row_log_z on the caller's device rows, on the engine's
+// stream; the scores are only read.  Waits for the device.
+extern "C" int sbr_debug_row_logprob(sbr_handle* h, const float* scores_dev, int64_t ld, int64_t rows, int32_t N, const int32_t* goal_ids_dev,
+                                     int32_t goals_per_row, float* logp_dev, float* log_z_dev) {
+    CHECK_ARG(h && scores_dev && (logp_dev || goals_per_row == 0) && (goal_ids_dev || goals_per_row == 0), "null argument");
+    CHECK_ARG(N >= 1 && ld >= N && rows >= 0 && rows <= 0x7fffffff && goals_per_row >= 0, "N=%d, ld=%lld, rows=%lld, goals_per_row=%d: N >= 1, ld >= N, counts >= 0",
+              N, (long long)ld, (long long)rows, goals_per_row);
+    SBR_LAUNCH(launch_debug_row_logprob(h->stream, scores_dev, (size_t)ld, (int)rows, N, goal_ids_dev, goals_per_row, logp_dev, log_z_dev,
+                                        &h->last_logprob_form));
+    SBR_HIP(hipStreamSynchronize(h->stream));
+    return SBR_OK;
 }
 
 // what sbr_dataset_set_tables asks of sample_cdf

@@ -762,3 +762,87 @@ class CandidateEvaluator(object):
     def at(self, k):
         """{"sampled_sps", "sampled_ndcg", "sampled_recall", "sampled_mrr"} at depth k"""
         return {"sampled_sps": self.sps(k), "sampled_ndcg": self.ndcg(k), "sampled_recall": self.recall(k), "sampled_mrr": self.mrr()}
+
+
+class LikelihoodEvaluator(object):
+    """The validation loss: reductions over the log-probability of held-out items (RNNEngine.evaluate_logprob and
+    evaluate_positions_logprob, include/sbr_rnn.h: sbr_evaluate_logprob) -- the full-softmax negative log-likelihood (NLL) of the
+    next item, the one number that compares models trained with different heads as probability models.  Every reduction runs in
+    float64 on the host over the float32 values the device returned.  A goal that is not rankable (logp = -inf: excluded, NaN or
+    -inf score, outside the catalogue) has no likelihood: it is counted in n_unrankable and left out of every mean."""
+
+    def __init__(self):
+        self._logp, self._first, self._hist, self._users = [], [], [], 0
+        self.metrics = {"nll": self.nll, "ppl": self.perplexity, "first_nll": self.first_nll}
+
+    def add_logprob(self, rec):
+        """rec: what RNNEngine.evaluate_logprob returned: one logp per goal place, user j's at [goal_off[j], goal_off[j + 1])"""
+        off = np.asarray(rec["goal_off"], dtype=np.int64)
+        logp = np.asarray(rec["logp"], dtype=np.float64).reshape(-1)
+        if len(off) < 1 or off[0] != 0 or np.any(off[1:] < off[:-1]) or len(logp) != off[-1]:
+            raise ValueError("rec must hold one logp per goal place of its goal_off")
+        first = np.zeros(len(logp), dtype=bool)
+        first[off[:-1][off[1:] > off[:-1]]] = True
+        self._logp.append(logp); self._first.append(first); self._hist.append(np.full(len(logp), -1, dtype=np.int64))
+        self._users += len(off) - 1
+
+    def add_positions(self, rec, min_history):
+        """rec: what RNNEngine.evaluate_positions_logprob returned for min_history: one logp per position, in order of p"""
+        off = np.asarray(rec["pos_off"], dtype=np.int64)
+        logp, m = np.asarray(rec["logp"], dtype=np.float64).reshape(-1), int(min_history)
+        if m < 1 or len(off) < 1 or off[0] != 0 or np.any(off[1:] < off[:-1]) or len(logp) != off[-1]:
+            raise ValueError("rec must hold one logp per position of its pos_off, and min_history >= 1")
+        n_pos = off[1:] - off[:-1]
+        first = np.zeros(len(logp), dtype=bool)
+        first[off[:-1][n_pos > 0]] = True
+        self._logp.append(logp); self._first.append(first)
+        # position i of a user stands behind p = min_history + i items
+        self._hist.append(m + np.arange(int(off[-1]), dtype=np.int64) - np.repeat(off[:-1], n_pos))
+        self._users += len(n_pos)
+
+    def _flat(self):
+        cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dt)
+        return cat(self._logp, np.float64), cat(self._first, bool), cat(self._hist, np.int64)
+
+    def n_users(self):
+        return self._users
+
+    def n_goals(self):
+        return int(sum(len(x) for x in self._logp))
+
+    @property
+    def n_unrankable(self):
+        """goal places without a likelihood (logp = -inf)"""
+        return int(sum(int(np.count_nonzero(np.isneginf(x))) for x in self._logp))
+
+    @staticmethod
+    def _mean_nll(logp):
+        keep = ~np.isneginf(logp)
+        return float(-logp[keep].sum() / np.count_nonzero(keep)) if np.any(keep) else float("nan")
+
+    def nll(self):
+        """the mean of -logp over the rankable goals (nan when there is none)"""
+        return self._mean_nll(self._flat()[0])
+
+    def perplexity(self):
+        """exp(nll())"""
+        with np.errstate(over="ignore"):
+            return float(np.exp(np.float64(self.nll())))
+
+    def first_nll(self):
+        """nll() over the FIRST goal item of every user only (the first position of a positions record): the analogue of sps"""
+        logp, first, _ = self._flat()
+        return self._mean_nll(logp[first])
+
+    def by_history_length(self):
+        """positions records only: {"count", "unrankable", "nll_sum"}, arrays over the history length h = 0 .. the longest one --
+        the rankable positions with h items in front of the goal (int64), the unrankable ones (int64) and the sum of -logp over
+        the rankable ones (float64): nll at h is nll_sum[h] / count[h]"""
+        logp, _, hist = self._flat()
+        if np.any(hist < 0):
+            raise RuntimeError("by_history_length() needs position records (add_positions) only")
+        size = int(hist.max()) + 1 if len(hist) else 0
+        keep = ~np.isneginf(logp)
+        return {"count": np.bincount(hist[keep], minlength=size).astype(np.int64),
+                "unrankable": np.bincount(hist[~keep], minlength=size).astype(np.int64),
+                "nll_sum": np.bincount(hist[keep], weights=-logp[keep], minlength=size).astype(np.float64)}

@@ -90,6 +90,7 @@ EXPORTS = ["sbr_last_error", "sbr_abi_version", "sbr_arena_bytes", "sbr_create",
            "sbr_plan_rows_host", "sbr_dataset_plan_pass",
            "sbr_dataset_plan_segments", "sbr_plan_pass_host", "sbr_build_batch", "sbr_evaluate", "sbr_cluster_evaluate", "sbr_evaluate_ranks",
            "sbr_evaluate_positions", "sbr_evaluate_candidates", "sbr_eval_negatives_host",
+           "sbr_evaluate_logprob", "sbr_evaluate_positions_logprob", "sbr_debug_row_logprob",
            "sbr_state_bytes", "sbr_state_save", "sbr_state_load", "sbr_cluster_state_bytes", "sbr_cluster_state_save",
            "sbr_cluster_state_load", "sbr_dataset_state_bytes", "sbr_dataset_state_save", "sbr_dataset_state_load",
            "sbr_sessions_create", "sbr_sessions_destroy", "sbr_sessions_reset", "sbr_sessions_advance", "sbr_sessions_replay", "sbr_sessions_replay_ranks", "sbr_sessions_adopt",
@@ -192,6 +193,9 @@ def load_library(path=None):
     lib.sbr_evaluate.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, vp]
     lib.sbr_evaluate_ranks.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, vp]
     lib.sbr_evaluate_positions.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, ctypes.c_int64]
+    lib.sbr_evaluate_logprob.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int64, vp, vp, vp]
+    lib.sbr_evaluate_positions_logprob.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, vp, vp, vp, vp, vp, ctypes.c_int64]
+    lib.sbr_debug_row_logprob.argtypes = [vp, vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int32, vp, ctypes.c_int32, vp, vp]
     lib.sbr_evaluate_candidates.argtypes = [vp, vp, vp, ctypes.c_int64, ctypes.c_int, vp, vp, ctypes.c_int32, ctypes.c_uint64, vp, vp, vp,
                                             ctypes.c_int64, vp, vp]
     lib.sbr_eval_negatives_host.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, vp, vp, vp]
@@ -1005,6 +1009,69 @@ class RNNEngine(object):
             self._check(self.lib.sbr_evaluate_positions(self.h, dataset.d, _ptr(users) if n else None, n, m, int(exclude_mode),
                                                         _ptr(out["pos_off"]), _ptr(out["ranks"]), _ptr(out["n_rankable"]), cap))
         return out
+
+    def evaluate_logprob(self, dataset, users, exclude_mode, want_ranks=False):
+        """The log-probability of every goal item under the softmax over the rankable items of its user's score row
+        (sbr_evaluate_logprob) -- the validation loss: users are split, fed, chunked and excluded as by evaluate_ranks();
+        exclude_mode: EVAL_EXCL_NONE, _VIEWED or _WINDOW (an excluded item leaves the softmax; _WINDOW_ZERO is refused).  Returns a
+        dict: "goal_off" (evaluate_ranks' layout), "logp" (float32 (goal_off[-1],): log p of the goal item, -inf where it is not
+        rankable), "log_z" (float32 (n,): the row's log partition sum, -inf for a row without a rankable item) and, with
+        want_ranks, "ranks" and "n_rankable" exactly as evaluate_ranks() returns them, from the same call."""
+        self._rank_local_flush("evaluate_logprob")
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        n = len(users)
+        off, cap = np.asarray(dataset.offsets, dtype=np.int64), 0      # the dataset's host offsets size the result
+        if n and users.min() >= 0 and users.max() < len(off) - 1:      # (otherwise the library rejects the users: nothing is written)
+            lens = off[1:][users] - off[:-1][users]
+            cap = int((lens - lens // 2).sum())
+        out = {"goal_off": np.zeros(n + 1, dtype=np.int64), "logp": np.empty(cap, dtype=np.float32), "log_z": np.empty(n, dtype=np.float32)}
+        if want_ranks:
+            out["ranks"], out["n_rankable"] = np.empty(cap, dtype=np.int32), np.empty(n, dtype=np.int32)
+        self.evaluate_calls += 1
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.sbr_evaluate_logprob(self.h, dataset.d, _ptr(users) if n else None, n, int(exclude_mode), _ptr(out["goal_off"]),
+                                                      _ptr(out["logp"]), cap, _ptr(out["log_z"]), _ptr(out.get("ranks")),
+                                                      _ptr(out.get("n_rankable"))))
+        return out
+
+    def evaluate_positions_logprob(self, dataset, users, exclude_mode, min_history=1, want_ranks=False):
+        """The log-probability of the NEXT item at every position of every user's sequence (sbr_evaluate_positions_logprob):
+        evaluate_positions()' users, prefix, positions and layout.  exclude_mode: EVAL_EXCL_NONE, or EVAL_EXCL_PREFIX (the items in
+        front of p leave the softmax at p).  Returns a dict: "pos_off", "logp" and "log_z" (float32 (pos_off[-1],)) and, with
+        want_ranks, "ranks" and "n_rankable" exactly as evaluate_positions() returns them, from the same call."""
+        self._rank_local_flush("evaluate_positions_logprob")
+        users = np.ascontiguousarray(np.asarray(users, dtype=np.int32).reshape(-1))
+        n, m = len(users), int(min_history)
+        off, cap = np.asarray(dataset.offsets, dtype=np.int64), 0      # the dataset's host offsets size the result
+        if n and m >= 1 and users.min() >= 0 and users.max() < len(off) - 1:      # (otherwise the library rejects the call: nothing is written)
+            cap = int(position_counts(off[1:][users] - off[:-1][users], self.max_length, m).sum())
+        out = {"pos_off": np.zeros(n + 1, dtype=np.int64), "logp": np.empty(cap, dtype=np.float32), "log_z": np.empty(cap, dtype=np.float32)}
+        if want_ranks:
+            out["ranks"], out["n_rankable"] = np.empty(cap, dtype=np.int32), np.empty(cap, dtype=np.int32)
+        self.evaluate_calls += 1
+        with self.torch.cuda.device(self.device):
+            self._check(self.lib.sbr_evaluate_positions_logprob(self.h, dataset.d, _ptr(users) if n else None, n, m, int(exclude_mode),
+                                                                _ptr(out["pos_off"]), _ptr(out["logp"]), _ptr(out["log_z"]),
+                                                                _ptr(out.get("ranks")), _ptr(out.get("n_rankable")), cap))
+        return out
+
+    def debug_row_logprob(self, scores, goal_ids, n_items=None):
+        """The test hook of the log-probability reduction (sbr_debug_row_logprob): scores, a float32 device tensor [rows][ld], are
+        reduced over their first n_items columns (default: all); goal_ids int32 [rows][G].  Returns (logp float32 [rows][G],
+        log_z float32 [rows]) as host arrays."""
+        torch = self.torch
+        assert scores.dtype == torch.float32 and scores.dim() == 2 and scores.is_contiguous() and scores.is_cuda
+        rows, ld = scores.shape
+        N = ld if n_items is None else int(n_items)
+        goals = torch.as_tensor(np.ascontiguousarray(np.asarray(goal_ids, dtype=np.int32).reshape(rows, -1)), device=scores.device)
+        G = goals.shape[1]
+        logp = torch.empty((rows, max(G, 1)), dtype=torch.float32, device=scores.device)
+        log_z = torch.empty(rows, dtype=torch.float32, device=scores.device)
+        with torch.cuda.device(self.device):
+            torch.cuda.current_stream().synchronize()      # the tensors were written on torch's stream, the call runs on the engine's
+            self._check(self.lib.sbr_debug_row_logprob(self.h, ctypes.c_void_p(scores.data_ptr()), ld, rows, N, ctypes.c_void_p(goals.data_ptr()), G,
+                                                       ctypes.c_void_p(logp.data_ptr()), ctypes.c_void_p(log_z.data_ptr())))
+        return logp.cpu().numpy()[:, :G], log_z.cpu().numpy()
 
     def evaluate_candidates(self, dataset, users, exclude_mode, candidates=None, n_negatives=None, seed=0, neg_cdf=None,
                             want_negatives=False):

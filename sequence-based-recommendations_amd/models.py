@@ -596,6 +596,49 @@ class RNNBase(object):
             return None
         return self._whole_catalogue_position_evaluator(dataset, which, mode, min_history)
 
+    def _likelihood_users(self, dataset, which, what):
+        """(DeviceDataset, users, lengths) for a log-probability call over dataset's "validation" / "test" set (two items or more,
+        file order); a data-parallel model is refused with the reason, as session_pool refuses it"""
+        if self.dp is not None or self.dist is not None:
+            raise NotImplementedError("%s of a data-parallel model: the users are not sharded over the ranks, and a rank-local call "
+                                      "would bring lazily stepped rows up to date on one replica alone; evaluate the likelihood on a "
+                                      "single-rank model" % what)
+        ds = dataset.device_set(which, self.engine, ratings=self.use_ratings_features)
+        lens = ds.offsets[1:] - ds.offsets[:-1]
+        return ds, np.nonzero(lens >= 2)[0].astype(np.int32), lens      # SequenceGenerator's min_length = 2 (data_handling.py:143)
+
+    def native_likelihood_evaluator(self, dataset, which, mode):
+        """The validation loss: the log-probability of every goal item of dataset's "validation" / "test" set under the softmax
+        over the rankable items of its user's row, from ONE engine call (RNNEngine.evaluate_logprob), as a data.LikelihoodEvaluator:
+        nll(), perplexity(), first_nll(), n_unrankable.  mode: engine.EVAL_EXCL_NONE, _VIEWED or _WINDOW (excluded items leave the
+        softmax).  Cluster-ranked models (RNNCluster: the softmax over the catalogue is not what they rank) and data-parallel
+        models are refused with the reason (NotImplementedError), as session_pool refuses them; nothing else serves this."""
+        from .data import LikelihoodEvaluator
+        ds, users, _ = self._likelihood_users(dataset, which, "native_likelihood_evaluator")
+        ev = LikelihoodEvaluator()
+        ev.add_logprob(self.engine.evaluate_logprob(ds, users, mode))
+        return ev
+
+    def native_position_likelihood_evaluator(self, dataset, which, mode, min_history=1, want_ranks=False):
+        """The log-probability of the next item at EVERY position of every sequence of dataset's "validation" / "test" set, from one
+        engine call (RNNEngine.evaluate_positions_logprob), as a data.LikelihoodEvaluator (by_history_length()); with want_ranks
+        the pair (LikelihoodEvaluator, data.PositionEvaluator): ranks and log-probabilities from the SAME call.  mode:
+        engine.EVAL_EXCL_NONE or EVAL_EXCL_PREFIX.  Cluster-ranked, data-parallel and bidirectional models are refused with the
+        reason (NotImplementedError), as session_pool refuses the first two; nothing else serves this."""
+        from .data import LikelihoodEvaluator, PositionEvaluator
+        if self.recurrent_layer.bidirectional:
+            raise NotImplementedError("native_position_likelihood_evaluator of a bidirectional model: a backwards layer's state at a "
+                                      "position has seen the items behind it")
+        ds, users, lens = self._likelihood_users(dataset, which, "native_position_likelihood_evaluator")
+        rec = self.engine.evaluate_positions_logprob(ds, users, mode, min_history=min_history, want_ranks=want_ranks)
+        ev = LikelihoodEvaluator()
+        ev.add_positions(rec, min_history)
+        if not want_ranks:
+            return ev
+        pos = PositionEvaluator()
+        pos.add_ranks(rec, lens[users], min_history)
+        return ev, pos
+
     def native_event_evaluator(self, dataset, which, exclude, min_history=1, capacity=4096, history=None):
         """The place of EVERY event of every sequence of dataset's "validation" / "test" set (two items or more, file order) among
         the scores of the state kept in front of it -- the protocol of the session-based recommenders, on the arithmetic that
@@ -660,7 +703,20 @@ class RNNBase(object):
         metrics["user_coverage"].append(ev.user_coverage())
         metrics["item_coverage"].append(ev.item_coverage())
         metrics["blockbuster_share"].append(ev.blockbuster_share())
+        if "nll" in self.metrics:       # --val_nll (enable_validation_nll)
+            # WINDOW_ZERO (RNNMargin's raw outputs: the items fed score 0.0 and stay rankable) excludes nothing from a softmax: NONE
+            lik_mode = EVAL_EXCL_NONE if mode == EVAL_EXCL_WINDOW_ZERO else mode
+            metrics["nll"].append(self.native_likelihood_evaluator(self.dataset, "validation", lik_mode).nll())
         return metrics
+
+    def enable_validation_nll(self):
+        """train --val_nll: 'nll' (direction -1: lower is better) joins this model's validation metrics -- the full-softmax negative
+        log-likelihood of the validation goal items (native_likelihood_evaluator: one RNNEngine.evaluate_logprob call per
+        validation point).  It is then printed at every progress point, usable as a validation metric (--metrics nll: --save Best
+        and both early stoppers) and carried in the --save_state histories.  The exclusion mode is the one the ranking metrics
+        use (_exclude_mode), with EVAL_EXCL_WINDOW_ZERO mapped to EVAL_EXCL_NONE: an item scored 0.0 has not left the softmax.
+        Without this call the metrics, the progress output and the stderr line are what they were."""
+        self.metrics["nll"] = {"direction": -1}
 
     def _print_progress(self, iterations, epochs, start_time, train_costs, metrics, validation_metrics):
         print(self.name, iterations, "batchs, ", epochs, " epochs in", time() - start_time, "s")
@@ -1319,6 +1375,20 @@ class RNNCluster(RNNBase):
     def session_store(self, capacity, history=None):
         """refused as session_pool is: the store serves through a pool"""
         return RNNCluster.session_pool(self, capacity, history)
+
+    def native_likelihood_evaluator(self, dataset, which, mode):
+        """A cluster model ranks inside each user's cluster: the softmax over the whole catalogue is not the distribution it
+        predicts from, and the log-probability calls know no cluster head."""
+        raise NotImplementedError("log-likelihood of a cluster model: sbr_evaluate_logprob normalises over the whole catalogue, "
+                                  "not over the members of the user's cluster")
+
+    def native_position_likelihood_evaluator(self, dataset, which, mode, min_history=1, want_ranks=False):
+        """refused as native_likelihood_evaluator is"""
+        return RNNCluster.native_likelihood_evaluator(self, dataset, which, mode)
+
+    def enable_validation_nll(self):
+        """train --val_nll: refused as native_likelihood_evaluator is, before the run starts"""
+        return RNNCluster.native_likelihood_evaluator(self, None, "validation", None)
 
     def top_k_batch(self, sequences, user_ids=None, k=10, exclude=None, candidates=None):
         """[top_k_recommendations(s, u, k, e) for s, u, e in zip(sequences, user_ids, exclude)] on the device, batch_size rows per

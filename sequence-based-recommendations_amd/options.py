@@ -298,6 +298,9 @@ def training_command_parser(parser):                   # train.py:12-27
     parser.add_argument("--resume", help="Continue from the newest state file of this configuration exactly where that run "
                         "stood (--max_iter and --progress count from its beginning); without one, start from scratch.",
                         action="store_true")
+    parser.add_argument("--val_nll", help="Also compute the validation loss at every progress point: 'nll', the full-softmax negative "
+                        "log-likelihood of the validation goal items (lower is better), printed with the other metrics and usable in "
+                        "--metrics.", action="store_true")
     parser.add_argument("--progress", help="Progress intervals", default="2.", type=str)
     parser.add_argument("--mpi", help="Max progress intervals", default=np.inf, type=float)
     parser.add_argument("--max_iter", help="Max number of iterations", default=np.inf, type=float)

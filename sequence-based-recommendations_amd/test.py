@@ -164,8 +164,14 @@ def run_position_tests(predictor, model_file, dataset, args, k=10, file=None, n_
     predictor.load(model_file)
     min_history = int(getattr(args, "min_history", 1))
     start = time.perf_counter()
-    ev = predictor.native_position_evaluator(dataset, "test", EVAL_EXCL_PREFIX if predictor.interactions_are_unique else EVAL_EXCL_NONE,
-                                             min_history=min_history)
+    mode, lik = EVAL_EXCL_PREFIX if predictor.interactions_are_unique else EVAL_EXCL_NONE, None
+    if getattr(args, "nll", False):      # --nll: ranks and log-probabilities from ONE call (sbr_evaluate_positions_logprob)
+        try:
+            lik, ev = predictor.native_position_likelihood_evaluator(dataset, "test", mode, min_history=min_history, want_ranks=True)
+        except (AttributeError, NotImplementedError) as e:
+            raise SystemExit("--nll --by_position needs the engine's log-probability call for this model, and there is no other road: %s" % e)
+    else:
+        ev = predictor.native_position_evaluator(dataset, "test", mode, min_history=min_history)
     if ev is None:
         raise SystemExit("--by_position needs the engine's native evaluation of this model and test set, and there is no other road: "
                          "not with SBR_NATIVE_EVAL=0, a data-parallel run, a shuffled test set, a bidirectional model (--r_bi) or a "
@@ -177,6 +183,9 @@ def run_position_tests(predictor, model_file, dataset, args, k=10, file=None, n_
     print("seq_mrr: ", ev.mrr())
     print("seq_ndcg@" + str(k) + ": ", ev.ndcg(k))
     print("positions: ", ev.n_positions())
+    if lik is not None:
+        print("seq_nll: ", lik.nll())
+        print("seq_ppl: ", lik.perplexity())
     if file is not None:
         if not os.path.exists(os.path.dirname(file)):
             os.makedirs(os.path.dirname(file))
@@ -184,6 +193,40 @@ def run_position_tests(predictor, model_file, dataset, args, k=10, file=None, n_
         with open(file + "_by_position", "a") as f:
             for h in np.nonzero(by["count"])[0].tolist():
                 f.write("\t".join(map(str, (n_batches, h, int(by["count"][h]), int(by["hits"][h]), float(by["rr"][h])))) + "\n")
+        if lik is not None:      # one line per history length h: n_batches, h, rankable positions, unrankable positions, sum of -logp
+            by = lik.by_history_length()
+            with open(file + "_by_position_nll", "a") as f:
+                for h in np.nonzero(by["count"] + by["unrankable"])[0].tolist():
+                    f.write("\t".join(map(str, (n_batches, h, int(by["count"][h]), int(by["unrankable"][h]), float(by["nll_sum"][h])))) + "\n")
+    return ev
+
+
+def run_nll_tests(predictor, model_file, dataset, args, file=None, n_batches=None):
+    """--nll (no counterpart in the reference): the loss of the model on the test set -- the full-softmax negative log-likelihood of
+    every goal item of every test user, from one engine call (RNNBase.native_likelihood_evaluator, sbr_evaluate_logprob); with
+    unique interactions the viewed items leave the softmax.  Prints nll (the mean over the rankable goal items), ppl = exp(nll)
+    and first_nll (the first goal item of every user only: the analogue of sps), and appends to `file`_nll one line per checkpoint:
+    n_batches, nll, ppl, first_nll, goal items, unrankable goal items.  There is no per-user road to fall back to: a model the
+    call cannot serve (cluster-ranked, data-parallel) ends the run with the reason."""
+    from .engine import EVAL_EXCL_NONE, EVAL_EXCL_VIEWED
+    if not hasattr(predictor, "native_likelihood_evaluator"):
+        raise SystemExit("--nll: %s has no native log-likelihood evaluation" % type(predictor).__name__)
+    predictor.load(model_file)
+    start = time.perf_counter()
+    try:
+        ev = predictor.native_likelihood_evaluator(dataset, "test", EVAL_EXCL_VIEWED if predictor.interactions_are_unique else EVAL_EXCL_NONE)
+    except NotImplementedError as e:
+        raise SystemExit("--nll needs the engine's log-probability call for this model, and there is no other road: %s" % e)
+    print("Timer (nll): ", time.perf_counter() - start)
+    values = [ev.nll(), ev.perplexity(), ev.first_nll()]
+    for name, v in zip(("nll", "ppl", "first_nll"), values):
+        print(name + ": ", v)
+    print("goal items: ", ev.n_goals(), " unrankable: ", ev.n_unrankable)
+    if file is not None:
+        if not os.path.exists(os.path.dirname(file)):
+            os.makedirs(os.path.dirname(file))
+        with open(file + "_nll", "a") as f:
+            f.write("\t".join(map(str, [n_batches] + values + [ev.n_goals(), ev.n_unrankable])) + "\n")
     return ev
 
 
@@ -306,6 +349,10 @@ def test_command_parser(parser):                                      # test.py:
     parser.add_argument("--by_event", help="Also rank every event of every test sequence, of any length, from the state a session pool keeps "
                         "in front of it (evt_sps, evt_mrr, evt_ndcg; with --save, <results file>_by_event holds one line per history length).",
                         action="store_true")
+    parser.add_argument("--nll", help="Also compute the loss on the test set: the full-softmax negative log-likelihood of every goal item (nll, "
+                        "ppl, first_nll; with --save, <results file>_nll holds one line per checkpoint).  With --by_position also seq_nll / "
+                        "seq_ppl over every position, from the same engine call as its ranks (<results file>_by_position_nll: one line per "
+                        "history length).", action="store_true")
     parser.add_argument("--min_history", help="With --by_position / --by_event: the shortest history a position or event is evaluated at.",
                         default=1, type=int)
     parser.add_argument("--sampled_negatives", help="Also rank every goal item among this many sampled items the user never interacted with "
@@ -340,6 +387,8 @@ def main(argv=None):                                                  # test.py:
                 print("(", i + 1, "/", len(files), ") results on " + files[j])
                 print_results(ev, metrics, file=output_file, n_batches=batches[j], print_full_rank_comparison=args.save_rank)
                 results.append((files[j], {m: ev.metrics[m]() for m in metrics}))
+                if getattr(args, "nll", False):
+                    run_nll_tests(predictor, files[j], dataset, args, file=output_file, n_batches=batches[j])
                 if getattr(args, "by_position", False):
                     run_position_tests(predictor, files[j], dataset, args, k=args.nb_of_predictions, file=output_file, n_batches=batches[j])
                 if getattr(args, "by_event", False):
@@ -350,6 +399,8 @@ def main(argv=None):                                                  # test.py:
         ev = run_tests(predictor, files, dataset, args, get_full_recommendation_list=args.save_rank, k=args.nb_of_predictions)
         print_results(ev, metrics, file=save_file_name(predictor, dataset, args), print_full_rank_comparison=args.save_rank)
         results.append((files, {m: ev.metrics[m]() for m in metrics}))
+        if getattr(args, "nll", False):
+            run_nll_tests(predictor, files, dataset, args, file=save_file_name(predictor, dataset, args))
         if getattr(args, "by_position", False):
             run_position_tests(predictor, files, dataset, args, k=args.nb_of_predictions, file=save_file_name(predictor, dataset, args))
         if getattr(args, "by_event", False):

@@ -81,7 +81,14 @@ def main(argv=None):
             raise ValueError("data-parallel training: batch size %d does not divide by the world size %d" % (args.batch_size, world))
         if args.clusters > 0:
             raise ValueError("data-parallel training: --clusters is not supported (the cluster head is single-rank)")
+        if getattr(args, "val_nll", False):
+            raise ValueError("data-parallel training: --val_nll is not supported (the log-probability call is single-rank: its users "
+                             "are not sharded)")
     predictor = parse.get_predictor(args)
+    if getattr(args, "val_nll", False):          # 'nll' joins the metrics of THIS run only, before --metrics is checked against them
+        if not hasattr(predictor, "enable_validation_nll"):
+            raise ValueError("--val_nll: %s has no native log-likelihood evaluation" % type(predictor).__name__)
+        predictor.enable_validation_nll()
     dataset = DataHandler(dirname=args.dataset, extended_training_set=args.extended_set, shuffle_training=args.tshuffle)
     if world > 1:
         reason = predictor._native_batch_refusal(dataset)
